@@ -37,6 +37,7 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8 TB/s spec
 L2_PEAK_GBS = 34500.0        # same guide: aggregate L2 bandwidth over the 8 XCDs
 FORCE_ALL_ITERS = -3.0e38    # dist_diff_thr that never stops the loop: exactly icp_it_thr iterations
 PMC_FILE = os.path.join(ROOT, "profiles", "r04_pmc.json")
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: at most this much in all; larger batches write a fixed sample of frames
 
 
 def parse():
@@ -84,7 +85,14 @@ def parse():
                     help="no GPU work: every rank joins the process group (gloo), one all-reduce, rank 0 prints the line's "
                          "launch fields -- the CPU test of the --gpus N self-launch")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launch (0 = pick a free one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(rank 0's frames when --gpus > 1); same arguments, same inputs")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.shard == "templates":
+        ap.error("--dump-outputs covers the frame-sharded path (--shard frames) only")
     if a.levels == 0:
         a.levels = 3 if a.config == "c3" else 2
     if a.batch == 0:
@@ -367,6 +375,47 @@ class Runner:
             self.torch.cuda.empty_cache()
 
 
+def step_outputs(run, res):
+    """What a caller of the timed path receives for the last timed step, one array per field with the frame on the leading
+    axis: the fl_recognition_result of every frame (c2), or every frame's match count and first 64 matches, best first,
+    padded with template_id -1 (c3)."""
+    from fealess_amd import api
+    from fealess_amd.bank import MATCH_DTYPE
+    out = {}
+
+    def walk(a, prefix):
+        for name in a.dtype.names:
+            if a[name].dtype.names:
+                walk(a[name], prefix + name + "_")
+            else:
+                out[prefix + name] = a[name]
+    if run.args.config == "c3":
+        got = [run.det.match_batch_collect(i, 64) for i in range(run.B)]
+        m = np.zeros((run.B, 64), MATCH_DTYPE)
+        m["template_id"] = -1
+        for i, (ms, _) in enumerate(got):
+            m[i, :len(ms)] = ms
+        out["n_matches"] = np.array([n for _, n in got], np.int64)
+        walk(m, "match_")
+    else:
+        walk(np.frombuffer(res, dtype=api.RESULT_DTYPE), "")
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, integers as float64 (exact), float32 as it is.  When every frame would pass
+    DUMP_MAX_BYTES, a fixed seeded sample of frames is written; `frame_index` names the frames written."""
+    n = len(next(iter(arrays.values())))
+    per_frame = 8 + sum(a[0].size * (4 if a.dtype == np.float32 else 8) for a in arrays.values())
+    idx = np.arange(n)
+    if n * per_frame > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // per_frame, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_index.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a[idx] if a.dtype == np.float32 else a[idx].astype(np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` started plainly (no WORLD_SIZE): this parent -- which never imports torch and never
     touches the GPU -- starts the N ranks as a CHILD process (torch.distributed.run, one rank per GPU, rendezvous on
@@ -465,6 +514,8 @@ def main():
         tmax = torch.tensor([el], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         el = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(run, res))
     if os.environ.get("FL_ICP_PHASES") and args.config != "c3":   # dev aid (tools/dev): a library built with -DFL_ICP_PHASES returns phase cycles in R
         ph = np.array([[r.det.icp.R[k] for k in range(8)] for r in res]).mean(0)
         print("icp phase Mcycles mean: grid %.2f A1 %.2f A2 %.2f svd %.2f B %.2f | before icp_run %.2f, whole kernel %.2f" %

@@ -1,8 +1,13 @@
-// A caller compiled ONLY against the reference's own headers (-I<reference>/CadReco: obj_reco_temp.h, lotus_common.h),
-// linked against libcadreco_hip.so: prints the layout table as the reference defines the types, then drives the library
-// through a CObjRecoCAD* exactly like test/linemod_recon.cpp:35-80 does -- Create, AddObj, Recognition, Destroy.
-// Without a GPU the calls must return the documented error codes (no crash, no CPU path).
+// A caller written against the reference's CadReco interface, linked against libcadreco_hip.so: prints the layout table,
+// then drives the library through a CObjRecoCAD* exactly like test/linemod_recon.cpp:35-80 does -- Create, AddObj,
+// Recognition, Destroy.  Without a GPU the calls must return the documented error codes (no crash, no CPU path).
+// tests/test_dropin_cpu.py compiles it against fealess_cadreco.h; tests/golden/make_golden.py --reference compiles it with
+// -DFL_REFERENCE_HEADERS against the reference's own headers (-I<reference>/CadReco) to record what they define.
+#ifdef FL_REFERENCE_HEADERS
 #include "obj_reco_temp.h"
+#else
+#include "fealess_cadreco.h"
+#endif
 #include <cstdio>
 #include <cstring>
 #include "layout_table.inc"

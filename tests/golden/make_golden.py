@@ -6,9 +6,17 @@ be built or run here (OpenCV 3.x is absent), so these vectors pin the oracle *re
 against regressions and give the HIP path a data-only target that travels to the GPU box --
 they do NOT pin the oracle to the reference ("parity unpinned").
 Run:  python tests/golden/make_golden.py     (inputs are seeded; output is deterministic)
+
+`--reference DIR` instead records what the CPU tests compare against the reference's own sources, as data, so that the
+tests need no copy of the reference: the two tables of DIR/linemod (reference_tables.npz) and the layout table and linked
+symbols of a CadReco caller compiled against DIR/CadReco's headers (cadreco_reference_abi.txt; needs build() first).
 """
 import os
+import re
+import shutil
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -87,7 +95,39 @@ def recognition_fixture():
     print("recognition fixture: found", res["found"], "tid", res["best"]["template_id"], "iters", res["det"]["icp"]["iters"])
 
 
+def reference_fixtures(ref):
+    src = open(os.path.join(ref, "linemod", "linemod.cpp"), errors="replace").read()
+    line = [l for l in src.splitlines() if l.startswith("CV_DECL_ALIGNED(16) static const unsigned char SIMILARITY_LUT")][0]
+    sim = np.array([int(v) for v in re.findall(r"\d+", line[line.index("{"):])], np.uint8)
+    txt = open(os.path.join(ref, "linemod", "normal_lut.i")).read()
+    nrm = np.array([int(v) for v in re.findall(r"\d+", txt[txt.index("{"):])][:8000], np.uint8)
+    assert sim.size == 256 and nrm.size == 8000
+    np.savez_compressed(os.path.join(HERE, "reference_tables.npz"), similarity_lut=sim, normal_lut=nrm)
+
+    cad, dropin = os.path.join(ROOT, "fealess_amd", "cadreco"), os.path.join(ROOT, "tests", "dropin")
+    tmp = tempfile.mkdtemp()
+    exe = os.path.join(tmp, "tu_reference_caller")
+    try:
+        subprocess.check_call(["g++", "-std=c++14", "-O1", "-w", "-DFL_REFERENCE_HEADERS", "-I", os.path.join(ref, "CadReco"), "-I", dropin,
+                               os.path.join(dropin, "tu_reference_caller.cpp"), "-o", exe, "-L", cad, "-lcadreco_hip",
+                               "-Wl,-rpath," + cad, "-Wl,-rpath," + os.path.join(ROOT, "fealess_amd", "csrc")])
+        out = subprocess.run([exe], stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()
+        syms = subprocess.run(["nm", "-u", exe], stdout=subprocess.PIPE, text=True, check=True).stdout.split()
+    finally:
+        shutil.rmtree(tmp)
+    layout = out[:out.index("--calls")]
+    syms = sorted(s for s in syms if "CObjRecoCAD" in s)
+    with open(os.path.join(HERE, "cadreco_reference_abi.txt"), "w") as f:
+        f.write("# tests/dropin/tu_reference_caller.cpp compiled against the reference's CadReco headers "
+                "(tests/golden/make_golden.py --reference):\n# its layout table, then the library symbols it links\n")
+        f.write("\n".join(layout + ["--symbols"] + syms) + "\n")
+    print("reference fixtures:", len(layout), "layout rows,", len(syms), "symbols")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--reference":
+        reference_fixtures(sys.argv[2])
+        sys.exit(0)
     linemod_fixture()
     frontend_fixture()
     icp_fixture()

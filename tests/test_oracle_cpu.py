@@ -1,4 +1,4 @@
-"""CPU tests of the ORACLE (oracle/liboracle.so): tables vs the reference text (when present),
+"""CPU tests of the ORACLE (oracle/liboracle.so): tables vs the reference text (as recorded under tests/golden/),
 independent naive re-derivations on tiny inputs, hand-worked known answers, domain properties,
 and the committed golden fixtures.  No GPU needed.
 
@@ -7,18 +7,12 @@ here can pin the oracle to the reference's *outputs*: "parity unpinned".  What i
 data tables against the reference's own text, the algorithm against independent formulations,
 and the oracle against its committed fixtures.
 """
-import os
-import re
-
 import numpy as np
 import pytest
 
 import util
 from fealess_amd import synth
 from fealess_amd.bank import TemplateBank
-
-REF = "/root/reference"
-
 
 # ---- tables ------------------------------------------------------------------------------------
 def test_similarity_lut_rule(oracle):
@@ -32,15 +26,12 @@ def test_similarity_lut_rule(oracle):
     assert int(lut.astype(np.int64).sum()) == 460 and int((lut.astype(np.int64) * np.arange(256)).sum()) == 59268
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference text not available on this box")
 def test_tables_equal_reference_text(oracle):
-    src = open(os.path.join(REF, "linemod", "linemod.cpp"), errors="replace").read()
-    line = [l for l in src.splitlines() if l.startswith("CV_DECL_ALIGNED(16) static const unsigned char SIMILARITY_LUT")][0]
-    ref_lut = np.array([int(v) for v in re.findall(r"\d+", line[line.index("{"):])], np.uint8)
-    assert ref_lut.size == 256 and np.array_equal(ref_lut, oracle.similarity_lut())
-    txt = open(os.path.join(REF, "linemod", "normal_lut.i")).read()
-    nums = [int(v) for v in re.findall(r"\d+", txt[txt.index("{"):])]
-    assert np.array_equal(np.array(nums[:8000], np.uint8), oracle.normal_lut())
+    """Both tables byte for byte as the reference's text writes them (linemod/linemod.cpp SIMILARITY_LUT, linemod/normal_lut.i),
+    recorded in tests/golden/reference_tables.npz by `make_golden.py --reference`."""
+    ref = util.golden("reference_tables.npz")
+    assert ref["similarity_lut"].size == 256 and np.array_equal(ref["similarity_lut"], oracle.similarity_lut())
+    assert ref["normal_lut"].size == 8000 and np.array_equal(ref["normal_lut"], oracle.normal_lut())
 
 
 def test_normal_lut_digest(oracle):
