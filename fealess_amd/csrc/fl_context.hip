@@ -88,14 +88,6 @@ extern "C" int fl_context_create(int device, fl_context **out)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->cus = prop.multiProcessorCount;
   }
-  if (hipMalloc((void **)&ctx->d_cu_chain, sizeof(unsigned) * FL_CU_TABLE) != hipSuccess ||
-      hipMemset(ctx->d_cu_chain, 0, sizeof(unsigned) * FL_CU_TABLE) != hipSuccess) {
-    (void)hipGetLastError();
-    if (ctx->d_cu_chain) (void)hipFree(ctx->d_cu_chain);
-    (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
-    return FL_ERR_HIP;
-  }
   // the development switches' initial values: the environment is read here and nowhere else
   for (const FlOptionName &o : fl_option_names)
     if (const char *e = getenv(o.env)) ctx->opt.*(o.field) = o.hex ? (long)strtoul(e, nullptr, 16) : atol(e);
@@ -130,7 +122,6 @@ static void context_release(fl_context *ctx)
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
-  if (ctx->d_cu_chain) (void)hipFree(ctx->d_cu_chain);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;

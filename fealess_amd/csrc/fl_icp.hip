@@ -48,10 +48,7 @@
 #include <set>
 #include <utility>
 
-#ifndef FL_ICP_BS_SMALL
-#define FL_ICP_BS_SMALL 256
-#endif
-#define ICP_BS_SMALL FL_ICP_BS_SMALL
+#define ICP_BS_SMALL 256
 #define ICP_BS_WIDE 1024
 #define ICP_DT 512                 // terms per block of the deferred dist_mean chain (two float4 per lane of the chain wave)
 #ifdef FL_ICP_PHASES
@@ -69,76 +66,29 @@
 #define CH_STAMP_END(k) { }
 #define PR_STAMP_BARRIER(k, every) tile_barrier()
 #endif
-#ifndef FL_ICP_WPE
-#define FL_ICP_WPE 4               // waves per SIMD the default 256-thread recognition kernel is compiled for (4 -> 128 VGPRs, 5 -> 96; a
+#define ICP_PARITY_WPE 4          // waves per SIMD the default 256-thread recognition kernel is compiled for (4 -> 128 VGPRs, 5 -> 96; a
                                   // second instance for 5 is always built, see k_icp_pipeline).  ICP us per frame, one box: mid-round
                                   // 5 @ 1280 frames 11.65, 4 @ 2048 10.4 (the 96-VGPR build spilled in the search loop); after the scan
                                   // batches lost 10 instructions and a few registers: 5 @ 2560 9.76, 4 @ 2048 10.15
-#endif
-#ifndef FL_ICP_FAST_F32
-#define FL_ICP_FAST_F32 1          // FL_ICP_FAST keeps its per-thread partial sums (~60 terms) in float32, like the point-to-plane mode;
-                                  // the cross-thread tree is fp64.  0: fp64 partials
-#endif
-#ifndef FL_ICP_FAST_WPE
-#define FL_ICP_FAST_WPE 4
-#endif
-#ifndef FL_ICP_PLANE_WPE
-#define FL_ICP_PLANE_WPE 4
-#endif
+#define ICP_FAST_WPE 4
+#define ICP_PLANE_WPE 4
 // waves per SIMD kernel k_icp_pipeline<MODE, 256> is compiled for
-#define ICP_MODE_WPE(MODE) ((MODE) == FL_ICP_PARITY ? FL_ICP_WPE : ((MODE) == FL_ICP_POINT_TO_PLANE ? FL_ICP_PLANE_WPE : FL_ICP_FAST_WPE))
-#ifndef FL_ICP_NBQ
-#define FL_ICP_NBQ 4              // organised search: candidate positions fetched per batch (4 VGPRs each)
-#endif
-#ifndef FL_ICP_NBUF_SMALL
-#define FL_ICP_NBUF_SMALL 4       // 16-row register batches of a chain in the 256-thread kernel.  Round 3: 2 / 3 / 4 measured the same; since
-                                  // the dist_mean chain runs over blocks of four tiles (FL_ICP_BMACRO) 2 / 3 / 4 / 6 give 29.5 / 29.2 / 29.1 /
+#define ICP_MODE_WPE(MODE) ((MODE) == FL_ICP_PARITY ? ICP_PARITY_WPE : ((MODE) == FL_ICP_POINT_TO_PLANE ? ICP_PLANE_WPE : ICP_FAST_WPE))
+#define ICP_NBQ 4                 // organised search: candidate positions fetched per batch (4 VGPRs each)
+#define ICP_NBUF_SMALL 4          // 16-row register batches of a chain in the 256-thread kernel.  Round 3: 2 / 3 / 4 measured the same; since
+                                  // the dist_mean chain runs over blocks of four tiles (ICP_BMACRO) 2 / 3 / 4 / 6 give 29.5 / 29.2 / 29.1 /
                                   // 38.1 ms per 4096 frames (6: the batches spill)
-#endif
-#ifndef FL_ICP_BSUM
-#define FL_ICP_BSUM 1             // parity mode: the dist_mean chain (non-negative terms) adds whole blocks exactly (chain_block_nonneg) and falls
-                                  // back to the term-by-term chain only where a block holds a rounding tie or crosses a binade.  1: in the
-                                  // 1024-thread kernel (a frame alone on its CU waits for that chain: ICP 3.07 -> 2.71 ms per 8 frames);
-                                  // 2: in the 256-thread kernel too (measured at 4096 frames: 34.1 against 33.5 ms -- with four workgroups
-                                  // per CU nobody waits for the chain, and a phase B that runs as fast as memory lets it only takes the
-                                  // memory side from the co-resident workgroups' phases); 0: always term by term
-#endif
-#ifndef FL_ICP_ZIMG
-#define FL_ICP_ZIMG 1             // organised search, parity mode: the staged rectangles and the partner gather read a 4-byte image (the
-                                  // pixel's depth factor, NaN where the pixel was dropped) and rebuild the 12-byte point by crop_clouds'
-                                  // own expression -- bit for bit the point the 12-byte image holds -- instead of reading it
-#endif
-#ifndef FL_ICP_TILE_W
-#define FL_ICP_TILE_W 16          // organised search: the queries of a step come from FL_ICP_TILE_W x (64 / FL_ICP_TILE_W)-pixel tiles.  Wider tiles =
+#define ICP_TILE_W 16             // organised search: the queries of a step come from ICP_TILE_W x (64 / ICP_TILE_W)-pixel tiles.  Wider tiles =
                                   // longer contiguous runs in the tile-ordered gathers / scatters (mod, bnd, nn: 192 instead of 96 bytes per row piece)
                                   // against a larger staged rectangle; measured at 4096 frames, ICP ms per launch: 4 x 16 35.4, 8 x 8 33.9 / 33.8,
                                   // 16 x 4 33.6 / 33.6, 32 x 2 35.8
-#endif
-#ifndef FL_ICP_BMACRO
-#define FL_ICP_BMACRO 4           // dist_mean phase, 256-thread parity kernel: tiles per barrier (l2dist_phase)
-#endif
-#ifndef FL_ICP_TILE_COLMAJOR
-#define FL_ICP_TILE_COLMAJOR 1    // the order of the pixels inside a search tile (build_tile_order)
-#endif
-#ifndef FL_ICP_BPD
-#define FL_ICP_BPD 1              // dist_mean phase: tiles of (mod, ref, bnd) loads a producer thread keeps in flight (1 or 2)
-#endif
-#ifndef FL_ICP_ALLPROD
-#define FL_ICP_ALLPROD 1          // with the block sums in the 256-thread kernel: the chain wave produces rows too (tiles of 256 rows)
-#endif
-#ifndef FL_ICP_CHAIN_SIMD
-#define FL_ICP_CHAIN_SIMD 0       // 256-thread kernel: elect the chain wave so that the chain waves of a CU's workgroups sit on different SIMDs
-                                  // (chain_elect).  Measured at 4096 frames, one box: 33.49 against 33.50 ms per launch -- SIMD issue
-                                  // slots are not what the launch waits for (profiles/README.md, round 4) -- so wave 0 chains; 1 builds it in
-#endif
-#ifndef FL_ICP_SPEC
-#define FL_ICP_SPEC 1             // parity mode, organised search: the next iteration's search runs while the chain wave adds dist_mean
-                                  // (1: in the 1024-thread kernel, 2: in both, 0: off)
-#endif
+#define ICP_BMACRO 4              // dist_mean phase, 256-thread parity kernel: tiles per barrier (l2dist_phase)
 #define ICP_STAGE_CAP 384         // points a wave stages per search step: six passes of 64
-#ifndef FL_ICP_NB
-#define FL_ICP_NB 10              // candidates fetched per round trip of the NN search (measured: 8..20)
-#endif
+#define ICP_NB 10                 // candidates fetched per round trip of the NN search (measured: 8..20)
+// Variants measured and not adopted (profiles/README.md): exact block sums of the dist_mean chain in the 256-thread kernel
+// (it keeps the term-by-term chain: with four workgroups per CU nobody waits for it), chain waves elected onto distinct
+// SIMDs, a 16-bit depth image, two tiles of loads in flight per producer, fp64 partials in FL_ICP_FAST, row-major search tiles,
+// the search running ahead of the chain in the 256-thread kernel, and extra LDS per workgroup.
 
 // HBM layout of one frame's ICP workspace (n = capacity in points):
 //   ref   n x 3 f32   reference cloud, index order (pairing + iteration 1)
@@ -219,7 +169,6 @@ struct IcpArgs {
   fl_recognition_result *results;
   const FlRefineJob *jobs;     // kind 0 with caller-chosen matches (fl_refine_matches): job b refines jobs[b].match on frame jobs[b].frame
   const int *order;            // kind 0 batches: workgroup b runs job order[b] (longest first, see k_icp_order); null: job b
-  unsigned *cu_chain;          // per-CU bookings of the chain waves' SIMDs (chain_elect); null: wave 0 chains
 };
 
 // LDS state of one frame workgroup of BS_ threads.  Parity mode: virtual wave 0 chains, the other BS/64 - 1 waves
@@ -232,15 +181,12 @@ struct IcpSharedT {
   // waves that share wave 0's SIMD (waves 4, 8, 12: the SPI deals a workgroup's waves round-robin over the 4 SIMDs) out
   // of the producer role, so the chain wave has its SIMD's issue slots to itself.
   static constexpr int NPROD = NW >= 8 ? NW - NW / 4 : NW - 1;
-  static constexpr int CHAIN_NBUF = BS_ >= 1024 ? 4 : FL_ICP_NBUF_SMALL;
+  static constexpr int CHAIN_NBUF = BS_ >= 1024 ? 4 : ICP_NBUF_SMALL;
   static constexpr int TQ = NPROD * 64;   // rows per LDS tile
-  // Which wave chains.  The 1024-thread workgroup: wave 0.  The 256-thread one: wave `cw`, elected per workgroup so that the
-  // chain waves of the workgroups that share a CU sit on DIFFERENT SIMDs (chain_elect): a chain wave issues one dependent
-  // add per 8 cycles -- half of its SIMD's issue slots for one to fifteen useful lanes -- and two of them on one SIMD leave
-  // the other two waves of that SIMD the scraps while the neighbouring SIMDs idle.
+  // Which wave chains in the 256-thread workgroup: always wave 0, but read from LDS as a runtime value (set to 0 at kernel
+  // entry) for the register allocation's sake, not for flexibility -- a literal 0 here raises the scratch of
+  // k_icp_pipeline<0, 256, 4> from 240 to 368 bytes per lane and of <0, 256, 5> from 352 to 496.
   int cw;
-  int wsimd[NW];                         // chain_elect: the SIMD each wave runs on
-  int cu_slot, cu_simd;                  // chain_elect: what this workgroup booked in the per-CU table (cu_slot < 0: nothing)
   // tile row of this thread, or -1 (chain wave / idle wave)
   __device__ __forceinline__ int producer_slot() const
   {
@@ -275,14 +221,11 @@ struct IcpSharedT {
   // double-buffered LDS tiles feeding the sequential float32 chains (FL_ICP_PARITY):
   // prod[b][k][r] = scalar k (9 products, 3 model coords, 3 reference coords) of row r of tile b
   alignas(16) float prod[2][15][TS];
-  // rows per tile of the dist_mean phase: with the exact block sums the chain wave of a 4-wave workgroup has time to produce too
-  static constexpr bool BSUM = FL_ICP_BSUM == 2 || (FL_ICP_BSUM == 1 && NW >= 8);   // exact block sums of the dist_mean chain in this kernel
-  static constexpr bool ALLPROD = BSUM && FL_ICP_ALLPROD && NW < 8;
-  static constexpr int DTQ = ALLPROD ? BS_ : TQ;
-  alignas(16) float dtile[2][DTQ];
+  static constexpr bool BSUM = NW >= 8;  // exact block sums of the dist_mean chain in this kernel
+  alignas(16) float dtile[2][TQ];
   // the organised search stages ICP_STAGE_CAP points per wave in the tile region above: a workgroup with few waves has small
   // tiles (TQ rows), so the region is padded up to what its waves stage
-  static constexpr int STAGE_FLOATS = NW * 384 * 4, TILE_FLOATS = 2 * 15 * TS + 2 * DTQ;
+  static constexpr int STAGE_FLOATS = NW * 384 * 4, TILE_FLOATS = 2 * 15 * TS + 2 * TQ;
   alignas(16) float stage_pad[STAGE_FLOATS > TILE_FLOATS ? STAGE_FLOATS - TILE_FLOATS : 4];
   alignas(16) float dchain[2][ICP_DT];   // the deferred dist_mean chain's staging (chain wave only)
 #ifdef FL_ICP_PHASES
@@ -589,7 +532,6 @@ __device__ __forceinline__ float chain_deferred(const float *__restrict__ dterm,
       r0 = *(const float4 *)(dterm + (size_t)(b + 1) * ICP_DT + 4 * lane);
       r1 = *(const float4 *)(dterm + (size_t)(b + 1) * ICP_DT + 256 + 4 * lane);
     }
-#if FL_ICP_BSUM
     {
       // the block straight from the registers it arrived in, as one exact integer sum (chain_block_nonneg); the words behind
       // term n - 1 of the last block are padding
@@ -601,7 +543,6 @@ __device__ __forceinline__ float chain_deferred(const float *__restrict__ dterm,
       for (int k = 0; k < 8; ++k) blk_term(bs, (k < 4 ? 4 * lane + k : 256 + 4 * lane + k - 4) < cnt ? v[k] : 0.0f, isum, bad);
       if (blk_finish(bs, isum, bad, acc)) continue;
     }
-#endif
     float *dst = buf[b & 1];
     *(float4 *)(dst + 4 * lane) = c0;
     *(float4 *)(dst + 256 + 4 * lane) = c1;
@@ -660,9 +601,6 @@ __device__ __forceinline__ float sqrt_upper(float x) { return __builtin_amdgcn_s
 // computed -- without a register move per candidate.
 __device__ __forceinline__ float4 nn_point(float x, float y, float z, int index) { return make_float4(__int_as_float(index), x, y, z); }
 __device__ __forceinline__ int nn_point_index(const float4 &p) { return __float_as_int(p.x); }
-#ifndef FL_ICP_BATCH_CLAMP
-#define FL_ICP_BATCH_CLAMP 1
-#endif
 #define NN_OVERRUN 3                // readable points behind the last position of a staged window / of the reference image
 #define NN_IDX_NONE 0x7fffffff      // index stored with a dropped pixel of the reference image (real indices are below it)
 
@@ -856,7 +794,7 @@ __device__ __forceinline__ void nn_search_grid(const NnGrid &S, const float4 *__
   }
   // The search is latency-bound and a wave pays for its slowest lane, so round trips are what counts:
   // the headers of 4 grid rows (8 loads) are fetched together, then the candidates of all 4 row segments
-  // are enumerated as ONE flat list, FL_ICP_NB per round trip -- a lane needs ceil(total / NB) rounds however the
+  // are enumerated as ONE flat list, ICP_NB per round trip -- a lane needs ceil(total / NB) rounds however the
   // candidates are spread over the rows.  Slots past the end of the list are NOT masked: they read points that
   // follow the last row segment (clamped to the cloud), and looking at extra reference points never changes the
   // answer -- the minimum over a superset that still contains every point within the search radius is the same
@@ -876,10 +814,10 @@ __device__ __forceinline__ void nn_search_grid(const NnGrid &S, const float4 *__
     const int pre1 = re[0] - rb[0], pre2 = pre1 + (re[1] - rb[1]), pre3 = pre2 + (re[2] - rb[2]);
     const int tot = pre3 + (re[3] - rb[3]);
     const int adj0 = rb[0], adj1 = rb[1] - pre1, adj2 = rb[2] - pre2, adj3 = rb[3] - pre3;
-    for (int base = 0; base < tot; base += FL_ICP_NB) {
-      float4 p[FL_ICP_NB];
+    for (int base = 0; base < tot; base += ICP_NB) {
+      float4 p[ICP_NB];
 #pragma unroll
-      for (int v = 0; v < FL_ICP_NB; ++v) {
+      for (int v = 0; v < ICP_NB; ++v) {
         const int k = base + v;
         int adj = k >= pre1 ? adj1 : adj0;
         adj = k >= pre2 ? adj2 : adj;
@@ -887,7 +825,7 @@ __device__ __forceinline__ void nn_search_grid(const NnGrid &S, const float4 *__
         p[v] = ld_u32(sref, min(k + adj, last));
       }
 #pragma unroll
-      for (int v = 0; v < FL_ICP_NB; ++v) NN_CONSIDER(p[v])
+      for (int v = 0; v < ICP_NB; ++v) NN_CONSIDER(p[v])
     }
   }
   NN_UNPACK(best, bi, bd)
@@ -912,21 +850,6 @@ struct OrgGeom {
 // The reference point of crop pixel (u, v) from its depth factor zsf, by crop_clouds' own expression (depth_to_3d.cpp:119,132 +
 // scale_mat_vec3f): bit for bit what the 12-byte image holds.  A dropped pixel (zsf = NaN) gives a NaN point, whose distance
 // is NaN: its key orders behind every real one.
-// element of the depth-factor image: the factor itself (float, NaN = dropped) or (FL_ICP_ZIMG == 2) the scene's 16-bit depth
-// (0 = dropped, which rescaleDepth turns into NaN anyway: depth_to_3d.cpp:257-259)
-#if FL_ICP_ZIMG == 2
-typedef uint16_t zimg_t;
-__device__ __forceinline__ float zimg_ld(const zimg_t *__restrict__ z, int i)
-{
-  const unsigned d = ld_u32(z, i);
-  return d == 0 ? NAN : (float)d * (float)(1 / 1000.0);
-}
-__device__ __forceinline__ zimg_t zimg_pack(bool keep, unsigned ds, float) { return (zimg_t)(keep ? ds : 0u); }
-#else
-typedef float zimg_t;
-__device__ __forceinline__ float zimg_ld(const zimg_t *__restrict__ z, int i) { return ld_u32(z, i); }
-__device__ __forceinline__ zimg_t zimg_pack(bool keep, unsigned, float zsf) { return keep ? zsf : NAN; }
-#endif
 // (suf, svf): the SCENE pixel as floats, (float)(g.sx0 + u) and (float)(g.sy0 + v)
 __device__ __forceinline__ F3 org_point_f(const OrgGeom &g, float suf, float svf, float zsf)
 {
@@ -1074,18 +997,17 @@ __device__ __forceinline__ bool org_window2(const OrgGeom &g, float cul, float c
   return u_lo <= u_hi && v_lo <= v_hi;
 }
 
-// every lane's window enumerated in lockstep, maxh rows of maxw positions, FL_ICP_NBQ positions per batch (lanes with a
+// every lane's window enumerated in lockstep, maxh rows of maxw positions, ICP_NBQ positions per batch (lanes with a
 // smaller window re-read their own last column / row: duplicates do not change a minimum);
 // fetch((v - ov) * RS + (u - ou)) returns the point of crop pixel (u, v)
 template <typename F>
 __device__ __forceinline__ unsigned long long org_scan(F fetch, int RS, int ou, int ov, float qx, float qy, float qz, int u_lo, int u_hi,
                                                        int v_lo, int v_hi, int maxw, int maxh)
 {
-  constexpr int NBQ = FL_ICP_NBQ;
+  constexpr int NBQ = ICP_NBQ;
   unsigned long long best = NN_KEY_NONE;
   const int wl = u_hi - u_lo, hl = v_hi - v_lo;
   const int b0 = (v_lo - ov) * RS + (u_lo - ou);
-#if FL_ICP_BATCH_CLAMP
   // A batch is NBQ CONSECUTIVE positions from a clamped start (one address and immediate offsets instead of a clamp and
   // an address per position).  A window narrower than NBQ reads up to NBQ - 1 = NN_OVERRUN positions past its right edge:
   // the next pixels of the row, the start of the next row, or -- behind the last row -- the points the caller keeps there
@@ -1093,19 +1015,13 @@ __device__ __forceinline__ unsigned long long org_scan(F fetch, int RS, int ou, 
   // frame or points at infinity, and looking at more reference points never changes the nearest one.
   static_assert(NBQ - 1 <= NN_OVERRUN, "the overrun guard behind the staged window / the image is NN_OVERRUN points");
   const int wlc = max(wl - (NBQ - 1), 0);
-#endif
   for (int dv = 0; dv < maxh; ++dv) {
     const int rb = b0 + min(dv, hl) * RS;
     for (int du = 0; du < maxw; du += NBQ) {               // one batch at a time: the other waves of the SIMD cover the LDS latency
       float4 cur[NBQ];
-#if FL_ICP_BATCH_CLAMP
       const int bb = rb + min(du, wlc);
 #pragma unroll
       for (int e = 0; e < NBQ; ++e) cur[e] = fetch(bb + e);
-#else
-#pragma unroll
-      for (int e = 0; e < NBQ; ++e) cur[e] = fetch(rb + min(du + e, wl));
-#endif
 #pragma unroll
       for (int e = 0; e < NBQ; ++e) NN_CONSIDER(cur[e])
     }
@@ -1128,11 +1044,8 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
                                              const float *Ropt, const float *Topt)
 {
   constexpr bool parity = MODE == FL_ICP_PARITY && !DEFER;   // chains in this phase
-  // With the exact block sums (FL_ICP_BSUM) the chain costs its wave a few dozen instructions per tile, so in the 4-wave
-  // workgroup the chain wave produces as well: tiles of BS rows, four producer waves instead of three.
-  constexpr bool allprod = parity && SH::ALLPROD;
-  constexpr int TQ = parity && !allprod ? SH::TQ : SH::BS;   // rows per tile
-  const int slot = parity && !allprod ? S.producer_slot() : (int)threadIdx.x;
+  constexpr int TQ = parity ? SH::TQ : SH::BS;           // rows per tile
+  const int slot = parity ? S.producer_slot() : (int)threadIdx.x;
   const int clane = parity ? S.chain_lane() : -1;        // lane of this thread in the chain wave, or -1
   int counter = 0, inl = 0;
   double dsum[1] = {0.0};
@@ -1144,7 +1057,7 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
   // the chain starts a block after the producers and ends a block after them, which is why 4 beats 8 and 15; blocks graded
   // 1, 1, 2, 2, 4, 4, 8 ... from both ends cost more in bookkeeping than they saved).  The terms of a block go to one of two
   // buffers of KB tiles in the (idle) tiles of phase A2.
-  constexpr int KB = parity && !allprod && !SH::BSUM && SH::NW < 8 ? FL_ICP_BMACRO : 1;
+  constexpr int KB = parity && !SH::BSUM ? ICP_BMACRO : 1;
   static_assert(KB == 1 || sizeof(S.prod) >= (size_t)2 * KB * TQ * sizeof(float), "two blocks of KB tiles of terms fit the A2 tiles");
   // Block 0 is tile 0 alone (the chain starts after one tile, not after KB), block m >= 1 the tiles (m - 1) KB + 1 .. m KB.
   auto dbuf = [&](int t) -> float * {                    // where the terms of tile t go
@@ -1226,51 +1139,7 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
     if (KB == 1 || t % KB == 0) tile_barrier();
   };
   const bool chain_wave = __builtin_amdgcn_readfirstlane(clane) >= 0;
-  // producer loop: `before_barrier(t)` runs behind the rows of tile t (the chain wave's block sum of tile t - 1 when every wave
-  // produces).  FL_ICP_BPD tiles of loads in flight per thread: register sets that trade roles by unrolling (see above).
-  auto produce = [&](auto &&before_barrier) {
-#if FL_ICP_BPD >= 2
-    Row X, Y, Z;
-    if (ntiles > 0) { row_load(X, 0); row_load(Y, 1); }
-    for (int t = 0; t < ntiles; t += 3) {
-      row_load(Z, t + 2);
-      row_process(X, t);
-      before_barrier(t);
-      block_barrier(t);
-      if (t + 1 < ntiles) {
-        row_load(X, t + 3);
-        row_process(Y, t + 1);
-        before_barrier(t + 1);
-        block_barrier(t + 1);
-      }
-      if (t + 2 < ntiles) {
-        row_load(Y, t + 4);
-        row_process(Z, t + 2);
-        before_barrier(t + 2);
-        block_barrier(t + 2);
-      }
-    }
-#else
-    Row A, B;
-    if (ntiles > 0) row_load(A, 0);
-    for (int t = 0; t < ntiles; t += 2) {
-      row_load(B, t + 1);
-      row_process(A, t);
-      before_barrier(t);
-      block_barrier(t);
-      if (t + 1 < ntiles) {
-        row_load(A, t + 2);
-        row_process(B, t + 1);
-        before_barrier(t + 1);
-        block_barrier(t + 1);
-      }
-    }
-#endif
-  };
-  if (allprod) {
-    // every wave produces; the chain wave adds tile t - 1 (complete since the last barrier, the other buffer) behind its own rows of tile t
-    produce([&](int t) { if (chain_wave && t > 0) chain_step(t - 1); });
-  } else if (chain_wave) {
+  if (chain_wave) {
     // the chain wave's own loop (see the A2 phase): one barrier per tile like the producers' below
     CH_STAMP_BEGIN;
     for (int t = 0; t < nbar; ++t) {
@@ -1281,13 +1150,25 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
     }
     CH_STAMP_END(26);
   } else if (slot >= 0) {
-    produce([&](int) {});
+    // one tile of loads in flight per thread: two register sets trade roles by unrolling (see above)
+    Row A, B;
+    if (ntiles > 0) row_load(A, 0);
+    for (int t = 0; t < ntiles; t += 2) {
+      row_load(B, t + 1);
+      row_process(A, t);
+      block_barrier(t);
+      if (t + 1 < ntiles) {
+        row_load(A, t + 2);
+        row_process(B, t + 1);
+        block_barrier(t + 1);
+      }
+    }
   } else {
     for (int t = 0; t < nbar; ++t) tile_barrier();         // a wave that neither chains nor produces (1024-thread workgroup)
   }
   __syncthreads();                                         // the phase's stores (mod, bnd, dterm) are visible to the workgroup
   if (parity && chain_wave)                                // the blocks the loop above has not added: the last one, or the last two
-    for (int t = max((allprod ? nblocks : nbar) - 1, 0); t < nblocks; ++t) chain_step(t);
+    for (int t = max(nbar - 1, 0); t < nblocks; ++t) chain_step(t);
   counter = block_sum_int(S, counter);
   inl = block_sum_int(S, inl);
   if (DEFER) {
@@ -1394,7 +1275,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   // visits more pixels; the neighbour found is the same.  If the chain ends the loop, the search is abandoned (S.stop).
   // Only the 1024-thread workgroup (batches that leave CUs idle) does this: with four 256-thread workgroups per CU the
   // other workgroups already fill the chain's shadow, and the extra traffic (dterm, nd) costs 7 % there (profiles/README.md).
-  constexpr bool SPEC = (FL_ICP_SPEC == 2 || (FL_ICP_SPEC == 1 && BS >= ICP_BS_WIDE)) && MODE == FL_ICP_PARITY && ORG;
+  constexpr bool SPEC = BS >= ICP_BS_WIDE && MODE == FL_ICP_PARITY && ORG;
   float mean_ub = l2dist_phase<MODE, SPEC>(S, mod, ref, bnd, dterm, n_model, FLT_MAX, nullptr, nullptr);             // :670
   int pending = SPEC ? 1 : 0;                            // 1: the initial distances await their chain, 2: an iteration's
   bool have_nn = false;                                  // nn[] / nd[] hold the neighbours of the current model cloud
@@ -1423,8 +1304,8 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     const float *rimg = (const float *)sref;
     // (the 1024-thread kernel keeps the 12-byte image: a frame alone on its CU waits for the rebuilt points -- 2.92 against 2.67 ms
     // per 8 frames -- where four workgroups per CU gain from the bytes: 32.9 against 34.2 ms per 4096)
-    constexpr bool ZIMG = FL_ICP_ZIMG && MODE == FL_ICP_PARITY && NW < 8;
-    const zimg_t *zimg = (const zimg_t *)(wsb + L.zimg);
+    constexpr bool ZIMG = MODE == FL_ICP_PARITY && NW < 8;
+    const float *zimg = (const float *)(wsb + L.zimg);
     const int last_s = n_model - 1;
     const float cul = uniform_f(og.offu + 0.01f), cuh = uniform_f(og.offu - 0.01f), cvl = uniform_f(og.offv + 0.01f), cvh = uniform_f(og.offv - 0.01f);
     constexpr int stride = NW * 64;
@@ -1530,7 +1411,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
               if (ZIMG) {
                 // 4 bytes per staged point instead of 12: the pixel's depth factor; its point rebuilt by crop_clouds' expression
                 // (pixel (U0 + col, V0 + row); a slot clamped to the guard behind the image reads NaN whatever its pixel)
-                const float zf = zimg_ld(zimg, pos);
+                const float zf = ld_u32(zimg, pos);
                 const F3 pt = org_point(og, U0 + col, V0 + row, zf);
                 R[p] = nn_point(pt.x, pt.y, pt.z, zf != zf ? NN_IDX_NONE : pos);
               } else {
@@ -1551,8 +1432,8 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
           ST_STAMP(2)
           // scan: maxh rows (a lane with fewer re-reads its last one) of nbw batches of 4 consecutive points (a window narrower
           // than 4 reads on into the next points of its row, of the next row, or of the slots behind the rectangle)
-          static_assert(FL_ICP_NBQ == 4 && NN_OVERRUN == 3, "the staged scan is written for 4-wide batches (cur[4], wl - 3, area + 3): "
-                                                            "build org_scan's FL_ICP_NBQ variants only with this path rewritten to match");
+          static_assert(ICP_NBQ == 4 && NN_OVERRUN == 3, "the staged scan is written for 4-wide batches (cur[4], wl - 3, area + 3): "
+                                                            "build org_scan's ICP_NBQ variants only with this path rewritten to match");
           const float4 *row0 = stage + (v_lo - V0) * W + (u_lo - U0);
           if (nbw == 1) {                                      // every lane's window is at most 4 wide: one batch per row
             for (int dv = 0; dv < maxh; ++dv) {
@@ -1609,18 +1490,12 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   // With the 4-byte image a step's staged data is a handful of dwords per lane, so the NEXT step can be prepared -- its
   // windows, its union rectangle, its staging loads issued -- before this step is scanned: the loads' round trip (a third of a
   // step) runs underneath the scan instead of in front of it.  Two prepared-step states trade roles by unrolling the loop
-  // twice (never by moves: see the chain phases).  A state issues its loads in wave-uniform pairs of passes (FL_ICP_PIPE_COND; the
+  // twice (never by moves: see the chain phases).  A state issues its loads in wave-uniform pairs of passes (the
   // first version always issued ICP_PIPE_NP, slots past the rectangle reading the guard behind the image, for fear that a branch
   // between issue and use would make the compiler drain the queue: it does not -- the wait in front of the first use is
   // counted for the shortest path -- and with the column-major tiles seven steps in ten need only two passes).  Same windows,
   // same candidates, same keys: bit-identical to org_search.
-#ifndef FL_ICP_PIPE
-#define FL_ICP_PIPE 1
-#endif
 #define ICP_PIPE_NP 6
-#ifndef FL_ICP_PIPE_COND
-#define FL_ICP_PIPE_COND 1
-#endif
 
   // Slot s = lane + 64 p of a staged W-wide rectangle -> its row and column and the crop position base + row * cw + col, in
   // float32: every value is an integer below 2^24 (small_crop), so each product, fma and sum is exact, at full rate, where the
@@ -1652,7 +1527,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     float4 *stage = (float4 *)&S.prod[0][0][0] + wv * ICP_STAGE_CAP;
     const float *rimg = (const float *)sref;
-    const zimg_t *zimg = (const zimg_t *)(wsb + L.zimg);
+    const float *zimg = (const float *)(wsb + L.zimg);
     const int last_s = n_model - 1, last_pt = og.cw * og.ch + NN_OVERRUN - 1;
     const float lanef = (float)lane;
     const float cul = uniform_f(og.offu + 0.01f), cuh = uniform_f(og.offu - 0.01f), cvl = uniform_f(og.offv + 0.01f), cvh = uniform_f(og.offv - 0.01f);
@@ -1688,25 +1563,16 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       P.U0 = U0; P.V0 = V0; P.W = W;
       const float Wf = (float)W, invW = uniform_f(__builtin_amdgcn_rcpf(Wf));
       const float basef = (float)((int)__umul24((unsigned)P.V0, (unsigned)og.cw) + P.U0);
-#if FL_ICP_PIPE_COND
       // two passes always, the others in pairs where the rectangle needs them (wave-uniform: with the column-major tiles seven
       // steps in ten need two)
       auto ldz = [&](int p) {
         const SlotPos sp = slot_pos(lanef + (float)(64 * p), Wf, invW, basef);
-        P.z[p] = zimg_ld(zimg, P.staged ? min((int)sp.pos, last_pt) : last_pt);
+        P.z[p] = ld_u32(zimg, P.staged ? min((int)sp.pos, last_pt) : last_pt);
       };
       ldz(0);
       ldz(1);
       if (P.staged && P.npass > 2) { ldz(2); ldz(3); }
       if (P.staged && P.npass > 4) { ldz(4); ldz(5); }
-#else
-      const int np_eff = P.staged ? P.npass : 0;               // passes that hold the rectangle; the others read the guard
-#pragma unroll
-      for (int p = 0; p < ICP_PIPE_NP; ++p) {
-        const SlotPos sp = slot_pos(lanef + (float)(64 * p), Wf, invW, basef);
-        P.z[p] = zimg_ld(zimg, p < np_eff ? min((int)sp.pos, last_pt) : last_pt);
-      }
-#endif
     };
     // the step itself: rebuild and stage its rectangle, scan, unpack
     auto finish = [&](const Prep &P, int &j, float &d) {
@@ -1890,10 +1756,10 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     constexpr int mode = MODE;
     int kept = 0;
     const bool index_pairs = iter == 1 && !plane;       // :700-704
-    // fast: per-thread partials.  point-to-plane: the thread's ~60 terms are summed in float32 (27 registers
-    // instead of 54) and only the cross-thread tree runs in fp64; the 6x6 system is re-linearised every
+    // fast and point-to-plane: per-thread partials.  The thread's ~60 terms are summed in float32 (27 registers
+    // instead of 54) and only the cross-thread tree runs in fp64; the point-to-plane 6x6 system is re-linearised every
     // iteration, so a 1e-6 relative error in a sum is immaterial.
-    typename std::conditional<plane || FL_ICP_FAST_F32 != 0, float, double>::type ds[NSUM];
+    float ds[NSUM];
 #pragma unroll
     for (int k = 0; k < NSUM; ++k) ds[k] = 0.0;
     // a kept pair (model point m, reference point r with index j) enters the sums of the modes that do not chain
@@ -1928,7 +1794,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       // cloud visits only a handful of candidates per point; the result is still the exact 1-NN.
       const float r_thr = uniform_f(sqrtf(thr));
       if (ORG) {
-        constexpr bool PIPE = FL_ICP_PIPE && FL_ICP_ZIMG && MODE == FL_ICP_PARITY && NW < 8;
+        constexpr bool PIPE = MODE == FL_ICP_PARITY && NW < 8;
         auto on_found = [&](bool active, int i, float qx, float qy, float qz, int j, float d) {
             const bool keep = d <= thr;                       // dists[i][0] <= dist_thr (:268)
             if (active) {
@@ -1993,10 +1859,10 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
         int j;                                             // nearest reference index (valid from the gather on)
         float d;                                           // SPEC: its squared distance
         bool in;                                           // the row exists (below `rows`)
-        F3 m, r;                                           // model point, reference point (FL_ICP_ZIMG: r.x = its depth factor until row_write)
+        F3 m, r;                                           // model point, reference point (ZIMG: r.x = its depth factor until row_write)
       };
-      constexpr bool ZIMG = FL_ICP_ZIMG && ORG && NW < 8;
-      const zimg_t *zimg = (const zimg_t *)(wsb + L.zimg);
+      constexpr bool ZIMG = ORG && NW < 8;
+      const float *zimg = (const float *)(wsb + L.zimg);
       const float inv_cw = uniform_f(1.0f / (float)max(og.cw, 1));
       auto row_load = [&](Row &w, int t) {                 // issue only: nothing here reads what it loads
         const int i = t * TQ + slot;
@@ -2008,7 +1874,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       };
       auto row_gather = [&](Row &w) {                      // SPEC: nn[] holds the neighbour whatever its distance; the pair is kept
         if (!(w.in && (!SPEC || w.d <= thr))) w.j = -1;    // if d <= dist_thr (:268; NaN = none found)
-        if (ZIMG) w.r.x = zimg_ld(zimg, max(w.j, 0));      // 4 (2) bytes: the partner pixel's depth factor (rebuilt in row_write)
+        if (ZIMG) w.r.x = ld_u32(zimg, max(w.j, 0));      // 4 bytes: the partner pixel's depth factor (rebuilt in row_write)
         else w.r = ld3_u32(jsrc, max(w.j, 0));
       };
       auto row_write = [&](const Row &w, int t) {
@@ -2292,7 +2158,7 @@ __device__ __forceinline__ void scene_normal(const uint16_t *__restrict__ scene,
 
 template <class SH>
 __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16_t *scene, const uint16_t *model, bool model_01mm,
-                           const int *rm, const int *rr, float *ref, float *mod, float *nrm, float *rimg, int *idximg, zimg_t *zimg)
+                           const int *rm, const int *rr, float *ref, float *mod, float *nrm, float *rimg, int *idximg, float *zimg)
 {
   constexpr int BS = SH::BS, NW = SH::NW;
   const int cw = rm[2], ch = rm[3], np = cw * ch;
@@ -2309,7 +2175,6 @@ __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16
     const int p = base + threadIdx.x;
     float A[3] = {0, 0, 0}, B[3] = {0, 0, 0};
     float zsf_keep = NAN;                                   // the scene pixel's depth factor (what org_point rebuilds A from)
-    unsigned ds_keep = 0;
     int keep = 0;
     if (p < np) {
       const int y = np < (1 << 20) && cw <= 1024 ? (int)(((float)p + 0.5f) * inv_cw) : p / cw, x = p - y * cw;
@@ -2322,7 +2187,6 @@ __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16
       }
       const float zsf = ds == 0 ? NAN : (float)ds * zs;                           // rescaleDepth :257-259
       zsf_keep = zsf;
-      ds_keep = ds;
       const float zmf = dm == 0 ? NAN : (float)dm * zs;
       A[0] = ((((float)sx - a.cx) * inv_fx) * zsf) * 1000;                        // :119,:132; scale_mat_vec3f
       A[1] = ((((float)sy - a.cy) * inv_fy) * zsf) * 1000;
@@ -2345,7 +2209,7 @@ __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16
       const F3 pt = {keep ? A[0] : INFINITY, keep ? A[1] : INFINITY, keep ? A[2] : INFINITY};
       __builtin_memcpy(rimg + 3 * p, &pt, 12);
       idximg[p] = keep ? kept_before + before + in_wave : NN_IDX_NONE;
-      if (zimg) zimg[p] = zimg_pack(keep, ds_keep, zsf_keep);
+      if (zimg) zimg[p] = keep ? zsf_keep : NAN;
     }
     if (keep) {
       const int k = kept_before + before + in_wave;
@@ -2360,13 +2224,13 @@ __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16
     kept_before += total;
   }
   if (threadIdx.x < 3 * NN_OVERRUN) rimg[3 * np + threadIdx.x] = INFINITY;     // overrun guard: points at infinity behind the image (org_scan)
-  if (zimg && threadIdx.x < NN_OVERRUN + 1) zimg[np + threadIdx.x] = zimg_pack(false, 0u, NAN);
+  if (zimg && threadIdx.x < NN_OVERRUN + 1) zimg[np + threadIdx.x] = NAN;
   __syncthreads();                                         // the clouds are complete for every thread
   return kept_before;
 }
 
-// The model indices in tile order (FL_ICP_TILE_W x 64 / FL_ICP_TILE_W pixels: 16 x 4) (tile rows alternately left-to-right and right-to-left, so consecutive tiles
-// are neighbours; inside a tile column by column: FL_ICP_TILE_COLMAJOR): the 64 queries a wave takes per step then project into a
+// The model indices in tile order (ICP_TILE_W x 64 / ICP_TILE_W pixels: 16 x 4) (tile rows alternately left-to-right and right-to-left, so consecutive tiles
+// are neighbours; inside a tile column by column): the 64 queries a wave takes per step then project into a
 // compact window of the reference image.
 // Index k of crop pixel p is idximg[p] (the paired compaction keeps the same pixels of both clouds).
 template <class SH>
@@ -2375,7 +2239,7 @@ __device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int c
   constexpr int BS = SH::BS, NW = SH::NW;
   int *cnt = (int *)&S.prod[0][0][0];
   constexpr int CAP = (int)(sizeof(S.prod) / 4);
-  constexpr int TW = FL_ICP_TILE_W, TH = 64 / FL_ICP_TILE_W;
+  constexpr int TW = ICP_TILE_W, TH = 64 / ICP_TILE_W;
   static_assert(TW * TH == 64 && (TW & (TW - 1)) == 0, "a tile is one wavefront of pixels");
   const int ntx = (cw + TW - 1) / TW, nty = (ch + TH - 1) / TH, ntile = ntx * nty;
   if (ntile > CAP) {                                       // more tiles than the scratch holds (crops beyond 1.5 Mpixel): index order
@@ -2389,14 +2253,10 @@ __device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int c
     const int ty = (int)(((float)t + 0.5f) * inv_ntx);
     int tx = t - ty * ntx;
     if (ty & 1) tx = ntx - 1 - tx;
-#if FL_ICP_TILE_COLMAJOR
     // column by column inside a tile, in the direction the tile row is walked: 64 consecutive entries of perm[] -- a search
     // step -- then always cover ONE contiguous run of columns of the tile row (row by row, a step that starts in the middle of
     // a tile takes its lower rows, the next tile and the upper rows of the one after: up to three tiles wide)
     const int c = lane / TH, x = tx * TW + ((ty & 1) ? TW - 1 - c : c), y = ty * TH + (lane & (TH - 1));
-#else
-    const int x = tx * TW + (lane & (TW - 1)), y = ty * TH + lane / TW;
-#endif
     int k = NN_IDX_NONE;
     if (x < cw && y < ch) k = idximg[y * cw + x];
     has = (unsigned)k < (unsigned)NN_IDX_NONE;
@@ -2439,53 +2299,6 @@ __device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int c
   __syncthreads();
 }
 
-// ---- which wave chains (256-thread workgroups) ---------------------------------------------------------------------------
-// Four (or five) of these workgroups share a CU, one wave of each on every SIMD, and each has ONE wave that spends the two
-// chain phases issuing a dependent add every 8 cycles: half a SIMD's issue slots.  Were it always wave 0, the SIMD a CU's
-// chain waves land on would be whatever the dispatcher's rotation made it -- two or three on one SIMD as often as not, with
-// that SIMD saturated and its neighbours idle.  So a workgroup books its chain SIMD in a per-CU table (4 x 8-bit counts, keyed
-// by XCC_ID and HW_ID's SE / SH / CU fields): the least booked SIMD among those its waves run on, released at the end.
-// Purely a scheduling choice: which wave adds does not change what is added, or in which order.
-template <class SH>
-__device__ __forceinline__ void chain_elect(SH &S, unsigned *cu_chain)
-{
-  if (threadIdx.x == 0) { S.cw = 0; S.cu_slot = -1; S.cu_simd = 0; }
-  if (SH::NW >= 8 || !FL_ICP_CHAIN_SIMD || !cu_chain) { __syncthreads(); return; }
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);          // HW_REG_HW_ID: SIMD_ID [5:4], CU_ID [11:8], SH_ID [12], SE_ID [15:13]
-  if ((threadIdx.x & 63) == 0) S.wsimd[threadIdx.x >> 6] = (int)((hw >> 4) & 3u);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID
-    const int slot = (int)(((xcc << 8) | ((hw >> 8) & 0xffu)) & (FL_CU_TABLE - 1));
-    unsigned have = 0;
-    for (int w = 0; w < SH::NW; ++w) have |= 1u << S.wsimd[w];
-    unsigned old = atomicAdd(&cu_chain[slot], 0u), best_s = 0;
-    for (;;) {
-      unsigned best_c = 256;
-      for (unsigned sd = 0; sd < 4; ++sd) {
-        const unsigned c = (old >> (8 * sd)) & 0xffu;
-        if (((have >> sd) & 1u) && c < best_c) { best_c = c; best_s = sd; }
-      }
-      if (best_c >= 255u) { best_s = 4; break; }                            // a stale table: do not book
-      const unsigned seen = atomicCAS(&cu_chain[slot], old, old + (1u << (8 * best_s)));
-      if (seen == old) break;
-      old = seen;
-    }
-    if (best_s < 4) {
-      S.cu_slot = slot;
-      S.cu_simd = (int)best_s;
-      for (int w = SH::NW - 1; w >= 0; --w)
-        if (S.wsimd[w] == (int)best_s) S.cw = w;
-    }
-  }
-  __syncthreads();
-}
-template <class SH>
-__device__ __forceinline__ void chain_release(SH &S, unsigned *cu_chain)
-{
-  if (threadIdx.x == 0 && cu_chain && S.cu_slot >= 0) { atomicSub(&cu_chain[S.cu_slot], 1u << (8 * S.cu_simd)); S.cu_slot = -1; }
-}
-
 // waves per SIMD a kernel instance is compiled for: the 256-thread one shares a CU with up to ICP_MODE_WPE - 1 others,
 // a 1024-thread workgroup is 4 waves per SIMD by itself
 #define ICP_WPE(MODE, BS) ((BS) == ICP_BS_SMALL ? ICP_MODE_WPE(MODE) : (BS) / 256)
@@ -2500,7 +2313,8 @@ __global__ __launch_bounds__(BS) void k_icp_clouds(IcpArgs a)
   const IcpWsLayout L = icp_layout(a.n_max);
   uint8_t *wsb = a.ws + (size_t)blockIdx.x * a.ws_stride;
   const OrgGeom none = {0, 0, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0, 0.f, 0.f, 0.f, 0.f};
-  chain_elect(S, nullptr);
+  if (threadIdx.x == 0) S.cw = 0;                         // the chain wave (IcpSharedT::cw)
+  __syncthreads();
   icp_run<MODE, false>(S, wsb, L, a.job.n_ref, a.job.n_model, a.it_thr, a.dmt, a.ddt, &a.results[blockIdx.x].det.icp, none);
 }
 
@@ -2587,12 +2401,13 @@ void k_icp_pipeline(IcpArgs a)
       return;
     }
   }
-  chain_elect(S, a.cu_chain);                            // (behind the last early return: what is booked here is released below)
+  if (threadIdx.x == 0) S.cw = 0;                         // the chain wave (IcpSharedT::cw)
+  __syncthreads();
   float *rimg = (float *)(wsb + L.sref);                  // image of 12-byte points, then the image of their indices (16 bytes per pixel in all)
   const int np = crop_clouds(S, a, scene, model, model_01mm, S.rect_m, S.rect_r, ref, mod,
                              MODE == FL_ICP_POINT_TO_PLANE ? (float *)(wsb + L.nrm) : nullptr, rimg,
                              (int *)((uint8_t *)rimg + org_idximg_offset(S.rect_m[2] * S.rect_m[3])),
-                             FL_ICP_ZIMG && MODE == FL_ICP_PARITY && BS < ICP_BS_WIDE ? (zimg_t *)(wsb + L.zimg) : nullptr);
+                             MODE == FL_ICP_PARITY && BS < ICP_BS_WIDE ? (float *)(wsb + L.zimg) : nullptr);
   // wave-uniform values read from LDS are VGPRs unless told otherwise: the search loop keeps them in SGPRs
   const OrgGeom og = {__builtin_amdgcn_readfirstlane(S.rect_r[2]), __builtin_amdgcn_readfirstlane(S.rect_r[3]),
                       uniform_f((float)S.rect_r[0] - a.cx), uniform_f((float)S.rect_r[1] - a.cy), a.fx, a.fy,
@@ -2652,7 +2467,6 @@ void k_icp_pipeline(IcpArgs a)
   }
   __syncthreads();
   icp_run<MODE, true>(S, wsb, L, np, np, a.it_thr, a.dmt, a.ddt, &res->det.icp, og);      // :228
-  chain_release(S, a.cu_chain);
   if (threadIdx.x == 0) {
     const fl_icp_result &ic = res->det.icp;
     float Rt[3];
@@ -2799,11 +2613,7 @@ static_assert(sizeof(IcpSharedT<ICP_BS_WIDE>) + 16 <= 160 * 1024, "IcpSharedT<10
 template <int BS, typename K>
 static int icp_launch_one(fl_context *ctx, K kern, int n_jobs, const IcpArgs &a)
 {
-#ifdef FL_ICP_LDS_PAD                                      // dev builds: extra dynamic LDS per workgroup = fewer workgroups per CU (occupancy experiment)
-  size_t lds = ((sizeof(IcpSharedT<BS>) + 15) & ~(size_t)15) + (BS == ICP_BS_SMALL ? (size_t)(FL_ICP_LDS_PAD) : 0);
-#else
   size_t lds = (sizeof(IcpSharedT<BS>) + 15) & ~(size_t)15;
-#endif
   // option icp_wg_per_cu = 1 .. 3: no more than that many 256-thread workgroups per CU (the launch asks for so much LDS that
   // one more does not fit) -- leaves registers and LDS to the kernels of ANOTHER stream (a second pipeline's LINEMOD stages)
   const long cap = ctx->opt.icp_wg_per_cu;
@@ -2973,7 +2783,6 @@ extern "C" int fl_detection(fl_context *ctx, const uint16_t *model_depth, const 
   a.job.model_depth = dm;
   a.job.scene_depth = dsn;
   a.results = dres;
-  a.cu_chain = ctx->d_cu_chain;
   rc = icp_launch(ctx, 1, a);
   if (rc) return rc;
   fl_recognition_result *hres = nullptr;
@@ -3024,7 +2833,6 @@ int fl_launch_detection_topk(fl_detector *det, int n_frames, int k, const fl_int
   a.poses = det->d_poses;
   a.depth_ptrs = det->d_depth_ptrs;
   a.results = d_results;
-  a.cu_chain = ctx->d_cu_chain;
   return icp_launch(ctx, n_frames * k, a);
 }
 
@@ -3063,7 +2871,6 @@ int fl_launch_detection_jobs(fl_detector *det, int n_jobs, const FlRefineJob *d_
   a.depth_ptrs = det->d_depth_ptrs;
   a.results = det->d_results;
   a.jobs = d_jobs;
-  a.cu_chain = ctx->d_cu_chain;
   return icp_launch(ctx, n_jobs, a);
 }
 
@@ -3110,7 +2917,6 @@ int fl_launch_detection_batch(fl_detector *det, int n_frames, const fl_intrinsic
   a.poses = det->d_poses;
   a.depth_ptrs = det->d_depth_ptrs;
   a.results = det->d_results;
-  a.cu_chain = ctx->d_cu_chain;
   // more jobs than the chip has slots: deal them longest first (see k_icp_order); option icp_order = 0 keeps the frame order
   if (n_frames > 4 * ctx->cus && n_frames <= ICP_ORDER_MAX && det->d_icp_order && ctx->opt.icp_order != 0) {
     int *d_size = det->d_icp_order + det->max_batch;

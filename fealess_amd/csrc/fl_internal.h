@@ -8,7 +8,6 @@
 #include "../../include/fealess_hip.h"
 
 #define FL_WAVE 64
-#define FL_CU_TABLE 4096              // entries of fl_context::d_cu_chain: (XCC_ID << 8) | HW_ID[15:8]
 
 struct fl_context {
   int device = 0;
@@ -21,8 +20,6 @@ struct fl_context {
   void *pinned = nullptr;       // small pinned host buffer for result read-back
   size_t pinned_bytes = 0;
   int cus = 256;                // multiProcessorCount of the device (launch heuristics), read once
-  // per-CU bookings of the ICP kernel's chain waves (IcpSharedT::cw): 4 x 8-bit counts per compute unit, zeroed once
-  unsigned *d_cu_chain = nullptr;
   // Development / comparison switches (fl_context_set_option).  Speed only: results are identical whatever they hold.
   // Initial values come from the environment ONCE, when the context is created; no launch path reads the environment.
   struct Options {
