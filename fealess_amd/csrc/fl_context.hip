@@ -56,18 +56,27 @@ int fl_pinned(fl_context *ctx, size_t bytes, void **out)
 
 extern "C" int fl_abi_version(void) { return FL_ABI_VERSION; }
 
-struct FlOptionName { const char *name, *env; long fl_context::Options::*field; bool hex; };
+// name, environment variable, field, environment value in hex, accepted values lo .. hi (icp_occ: 0, 4 or 5)
+struct FlOptionName { const char *name, *env; long fl_context::Options::*field; bool hex; long lo, hi; };
 static const FlOptionName fl_option_names[] = {
-  {"scan_prune", "FL_SCAN_PRUNE", &fl_context::Options::scan_prune, false},
-  {"scan_prune_mid", "FL_SCAN_PRUNE_MID", &fl_context::Options::scan_prune_mid, true},
-  {"icp_wide", "FL_ICP_WIDE", &fl_context::Options::icp_wide, false},
-  {"icp_occ", "FL_ICP_OCC", &fl_context::Options::icp_occ, false},
-  {"icp_order", "FL_ICP_ORDER", &fl_context::Options::icp_order, false},
-  {"icp_wg_per_cu", "FL_ICP_WG_PER_CU", &fl_context::Options::icp_wg_per_cu, false},
-  {"eager_frontend", "FL_EAGER_FRONTEND", &fl_context::Options::eager_frontend, false},
-  {"dev_poison", "FL_DEV_POISON", &fl_context::Options::dev_poison, false},
-  {"ws_pad", "FL_DEV_WS_PAD", &fl_context::Options::ws_pad, false},
+  {"scan_prune", "FL_SCAN_PRUNE", &fl_context::Options::scan_prune, false, 0, 1},
+  {"scan_prune_mid", "FL_SCAN_PRUNE_MID", &fl_context::Options::scan_prune_mid, true, -1, 0xFF},
+  {"icp_wide", "FL_ICP_WIDE", &fl_context::Options::icp_wide, false, -1, 1},
+  {"icp_occ", "FL_ICP_OCC", &fl_context::Options::icp_occ, false, 0, 5},
+  {"icp_order", "FL_ICP_ORDER", &fl_context::Options::icp_order, false, 0, 1},
+  {"icp_wg_per_cu", "FL_ICP_WG_PER_CU", &fl_context::Options::icp_wg_per_cu, false, 0, 3},
+  {"eager_frontend", "FL_EAGER_FRONTEND", &fl_context::Options::eager_frontend, false, 0, 1},
+  {"dev_poison", "FL_DEV_POISON", &fl_context::Options::dev_poison, false, 0, 1},
+  {"ws_pad", "FL_DEV_WS_PAD", &fl_context::Options::ws_pad, false, 0, 16l << 20},
 };
+
+// A value outside an option's range is refused rather than taken for "default": a forced kernel variant with a mistyped
+// value would otherwise run the default one without anyone noticing.
+static bool fl_option_valid(const FlOptionName &o, long v)
+{
+  if (v < o.lo || v > o.hi) return false;
+  return o.field != &fl_context::Options::icp_occ || v == 0 || v >= 4;
+}
 
 extern "C" int fl_context_create(int device, fl_context **out)
 {
@@ -89,8 +98,12 @@ extern "C" int fl_context_create(int device, fl_context **out)
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->cus = prop.multiProcessorCount;
   }
   // the development switches' initial values: the environment is read here and nowhere else
+  // (a value outside the option's range keeps the built-in default)
   for (const FlOptionName &o : fl_option_names)
-    if (const char *e = getenv(o.env)) ctx->opt.*(o.field) = o.hex ? (long)strtoul(e, nullptr, 16) : atol(e);
+    if (const char *e = getenv(o.env)) {
+      const long v = o.hex ? (long)strtoul(e, nullptr, 16) : atol(e);
+      if (fl_option_valid(o, v)) ctx->opt.*(o.field) = v;
+    }
   *out = ctx;
   return FL_OK;
 }
@@ -103,7 +116,11 @@ extern "C" int fl_context_set_option(fl_context *ctx, const char *name, long val
 {
   if (!ctx || !name) return FL_ERR_INVALID;
   for (const FlOptionName &o : fl_option_names)
-    if (!strcmp(name, o.name)) { ctx->opt.*(o.field) = value; return FL_OK; }
+    if (!strcmp(name, o.name)) {
+      if (!fl_option_valid(o, value)) return fl_set_error(ctx, FL_ERR_INVALID, "option '%s': %ld is out of range", name, value);
+      ctx->opt.*(o.field) = value;
+      return FL_OK;
+    }
   return fl_set_error(ctx, FL_ERR_INVALID, "unknown option '%s'", name);
 }
 

@@ -45,7 +45,7 @@
 #include <string.h>
 #include <type_traits>
 #include <mutex>
-#include <set>
+#include <map>
 #include <utility>
 
 #define ICP_BS_SMALL 256
@@ -2621,14 +2621,18 @@ static int icp_launch_one(fl_context *ctx, K kern, int n_jobs, const IcpArgs &a)
     const size_t want = ((size_t)(160 * 1024) / (size_t)cap - 256) & ~(size_t)15;
     if (want > lds) lds = want;
   }
-  const size_t attr = lds > (size_t)(82 * 1024) ? lds : (size_t)(82 * 1024);
-  {                                                        // the attribute is set once per kernel and device, not per launch
+  // The attribute is set per kernel and device, not per launch: at the first launch, and again whenever a launch needs more
+  // than it was set to (icp_wg_per_cu changed after that kernel's first launch: cap 1 asks for about 160 KB).
+  {
     static std::mutex mu;
-    static std::set<std::pair<const void *, int>> done;
+    static std::map<std::pair<const void *, int>, size_t> attr_set;
     std::lock_guard<std::mutex> lock(mu);
-    if (!done.count({(const void *)kern, ctx->device})) {
-      FL_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(attr > (size_t)(160 * 1024) ? (size_t)(160 * 1024) : attr)));
-      done.insert({(const void *)kern, ctx->device});
+    size_t &cur = attr_set[{(const void *)kern, ctx->device}];
+    if (cur < lds) {
+      size_t attr = lds > (size_t)(82 * 1024) ? lds : (size_t)(82 * 1024);
+      if (attr > (size_t)(160 * 1024)) attr = (size_t)(160 * 1024);
+      FL_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr));
+      cur = attr;
     }
   }
   hipLaunchKernelGGL(kern, dim3(n_jobs), dim3(BS), lds, ctx->stream, a);

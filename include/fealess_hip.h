@@ -148,7 +148,10 @@ fl_context *fl_detector_get_context(fl_detector *det);
  * with 0xFF), "ws_pad" (extra bytes of frame-workspace stride).  Their INITIAL values are read once from the environment
  * when the context is created (FL_SCAN_PRUNE, FL_SCAN_PRUNE_MID (hex), FL_ICP_WIDE, FL_ICP_OCC, FL_ICP_ORDER, FL_ICP_WG_PER_CU,
  * FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
- * process later on changes nothing.  Unknown names: FL_ERR_INVALID. */
+ * process later on changes nothing.  Unknown names: FL_ERR_INVALID.
+ * Accepted values: scan_prune, icp_order, eager_frontend, dev_poison {0, 1}; scan_prune_mid -1 .. 0xFF; icp_wide {-1, 0, 1};
+ * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
+ * FL_ERR_INVALID and leaves the option as it was; an environment value outside its range keeps the built-in default. */
 int  fl_context_set_option(fl_context *ctx, const char *name, long value);
 int  fl_context_get_option(const fl_context *ctx, const char *name, long *value);
 

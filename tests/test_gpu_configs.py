@@ -227,7 +227,8 @@ def test_cxx_multi_gpu_host_with_one_rank_equals_fl_recognize_batch(ctx, oracle)
 def test_context_options_are_explicit_state_not_the_environment(ctx, monkeypatch):
     """fl_context_set_option / _get_option: the development switches are context state.  Their initial values come from the
     environment ONCE, at fl_context_create; a variable that appears in the process environment afterwards changes nothing
-    (round 3 read FL_SCAN_PRUNE & co. with getenv on every launch)."""
+    (round 3 read FL_SCAN_PRUNE & co. with getenv on every launch).  Values outside an option's range are refused, and ignored in
+    the environment, so that a forced kernel variant can never quietly be the default one."""
     assert ctx.get_option("scan_prune") == 1 and ctx.get_option("icp_wide") == -1 and ctx.get_option("icp_order") == 1
     monkeypatch.setenv("FL_SCAN_PRUNE", "0")                 # a stray variable in a host's environment, after the context exists
     monkeypatch.setenv("FL_ICP_WIDE", "1")
@@ -238,4 +239,28 @@ def test_context_options_are_explicit_state_not_the_environment(ctx, monkeypatch
     assert c2.get_option("scan_prune") == 1
     with pytest.raises(api.FealessError):
         c2.set_option("no_such_switch", 1)
+    # every value the option matrix of test_gpu_clutter.py forces is accepted and read back as set
+    for name, values in (("scan_prune", (0, 1)), ("scan_prune_mid", (-1, 0, 0x01, 0x55, 0x7F, 0xFF)), ("icp_wide", (-1, 0, 1)),
+                         ("icp_occ", (0, 4, 5)), ("icp_order", (0, 1)), ("icp_wg_per_cu", (0, 1, 2, 3)), ("eager_frontend", (0, 1)),
+                         ("dev_poison", (0, 1)), ("ws_pad", (0, 4096, 16 << 20))):
+        before = c2.get_option(name)
+        for v in values:
+            c2.set_option(name, v)
+            assert c2.get_option(name) == v, (name, v)
+        c2.set_option(name, before)
+    # a value outside the range is refused and leaves the option as it was: a mistyped value must not quietly mean "default"
+    for name, bad in (("icp_occ", 7), ("icp_occ", 3), ("icp_wg_per_cu", 4), ("icp_wide", 2), ("scan_prune", 2),
+                      ("scan_prune_mid", 0x100), ("scan_prune_mid", -2), ("ws_pad", -1), ("ws_pad", (16 << 20) + 1)):
+        before = c2.get_option(name)
+        with pytest.raises(api.FealessError) as e:
+            c2.set_option(name, bad)
+        assert e.value.code == L.FL_ERR_INVALID and c2.get_option(name) == before, (name, bad)
     c2.close()
+    # out of range in the environment: the built-in default, and the context is still created
+    monkeypatch.setenv("FL_ICP_OCC", "7")
+    monkeypatch.setenv("FL_ICP_WG_PER_CU", "9")
+    monkeypatch.setenv("FL_SCAN_PRUNE_MID", "100")           # hex: 0x100
+    c3 = api.Context(0)
+    assert c3.get_option("icp_occ") == 0 and c3.get_option("icp_wg_per_cu") == 0 and c3.get_option("scan_prune_mid") == -1
+    assert c3.get_option("scan_prune") == 0 and c3.get_option("icp_wide") == 1   # the values in range are still taken
+    c3.close()
