@@ -309,6 +309,24 @@ class Detector:
             o += a * b
         return out
 
+    def dev_frame_image(self, frame, kind, level, modality=0):
+        """DEVELOPMENT ONLY (fl_dev_frame_image, not part of the C ABI): frame `frame`'s workspace image of the last batch, as
+        it is (lazy batches included).  kind 0: quantised (h, w) u8; 1: pyrDown BGR (h, w, 3) of a level >= 1; 2: spread (h, w)
+        of a fine level; 3: the coarsest level's linear memories (8, fl_lm_label_stride)."""
+        fn = self.lib.fl_dev_frame_image
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        h, w = self.h0 >> level, self.w0 >> level
+        if kind == 3:
+            shape = (8, self.lib.fl_lm_label_stride(w, h, self.T[level]))
+        else:
+            shape = (h, w, 3) if kind == 1 else (h, w)
+        out = np.empty(shape, np.uint8)
+        n = C.c_size_t(0)
+        self.ctx.check(fn(self.h, frame, kind, level, modality, _ptr(out), out.nbytes, C.byref(n)))
+        assert n.value == out.nbytes
+        return out
+
     def _params(self, threshold, icp_it_thr, dist_mean_thr, dist_diff_thr, mode):
         return L.RecognitionParams(threshold, icp_it_thr, dist_mean_thr, dist_diff_thr, mode)
 
@@ -324,6 +342,27 @@ class Detector:
         p = self._params(threshold, icp_it_thr, dist_mean_thr, dist_diff_thr, mode)
         res = (L.RecognitionResult * n)()
         self.ctx.check(self.lib.fl_recognize_batch(self.h, n, bp, dp, L.FL_MEM_HOST, C.byref(k), C.byref(p), res))
+        return [recognition_result_to_dict(r) for r in res]
+
+    def recognize_batch_zoom(self, bgrs, depths, K, threshold=75.0, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01,
+                             mode=L.FL_ICP_PARITY, mem=L.FL_MEM_HOST, src_size=None):
+        """PrepareInputData's zoom + Recognition (fl_recognize_batch_zoom): sources of one size, resized (INTER_LINEAR) on the
+        device to the finalized size; K is the finalized size's.  Host arrays in, or with mem=FL_MEM_DEVICE lists of device
+        pointers and src_size = (w, h).  List of result dicts."""
+        if mem == L.FL_MEM_HOST:
+            bs = [np.ascontiguousarray(b, np.uint8) for b in bgrs]
+            ds = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            sw, sh = ds[0].shape[1], ds[0].shape[0]
+            bptrs, dptrs = [b.ctypes.data for b in bs], [d.ctypes.data for d in ds]
+        else:
+            (sw, sh), bptrs, dptrs = src_size, bgrs, depths
+        n = len(bptrs)
+        bp = (C.c_void_p * n)(*bptrs)
+        dp = (C.c_void_p * n)(*dptrs)
+        k = L.Intrinsics(self.w0, self.h0, *K)
+        p = self._params(threshold, icp_it_thr, dist_mean_thr, dist_diff_thr, mode)
+        res = (L.RecognitionResult * n)()
+        self.ctx.check(self.lib.fl_recognize_batch_zoom(self.h, n, bp, dp, sw, sh, mem, C.byref(k), C.byref(p), res))
         return [recognition_result_to_dict(r) for r in res]
 
     def recognize_topk(self, bgr, depth, K, k, threshold=75.0, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01,

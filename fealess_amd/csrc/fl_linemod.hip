@@ -1252,6 +1252,47 @@ extern "C" int fl_last_quantized(fl_detector *det, uint8_t *out)
   return FL_OK;
 }
 
+// Development read-back (not in include/fealess_hip.h; tests/test_gpu_batch_frontend.py): what frame `frame` of the last batch
+// holds in its workspace, as it is -- lazy batches included, where the finer levels' colour quantisation and spreads exist only
+// in the marked tiles.  kind 0: quantised image of (level, modality), w*h bytes; 1: pyrDown BGR of a level >= 1, w*h*3 bytes
+// (level 0 may have been read in place, so it is not offered); 2: spread image of a fine level, w*h bytes; 3: the coarsest
+// level's 8 linear memories, 8 * fl_lm_label_stride bytes in the layout of fl_build_linear_memories.  Nothing after the match
+// (ICP, fl_export_topk*, fl_similarity_maps) writes these regions: the ICP stages use off_icp only.  The next call that runs a
+// front-end (any fl_match_* / fl_recognize_*) overwrites them, fl_recognize_topk and fl_match_frame* in workspace 0.
+// *bytes is set whenever the request is valid, also when cap is too small (FL_ERR_INVALID).
+extern "C" int fl_dev_frame_image(fl_detector *det, int frame, int kind, int level, int modality, uint8_t *out, size_t cap,
+                                  size_t *bytes)
+{
+  if (!det || !bytes) return FL_ERR_INVALID;
+  fl_context *ctx = det->ctx;
+  if (!det->finalized || det->last_batch < 1) return fl_set_error(ctx, FL_ERR_STATE, "no batch matched yet");
+  if (frame < 0 || frame >= det->last_batch) return fl_set_error(ctx, FL_ERR_INVALID, "frame %d is not in the last batch", frame);
+  if (level < 0 || level >= det->L || modality < 0 || modality >= det->M)
+    return fl_set_error(ctx, FL_ERR_INVALID, "level %d / modality %d out of range", level, modality);
+  const FlLevelGeom &g = det->geom[level];
+  const bool coarsest = level == det->L - 1;
+  size_t off = 0, n = 0;
+  switch (kind) {
+  case 0: off = g.quant_off[modality]; n = (size_t)g.w * g.h; break;
+  case 1:
+    if (level == 0) return fl_set_error(ctx, FL_ERR_INVALID, "level 0's colour image is the input frame");
+    off = g.bgr_off; n = (size_t)g.w * g.h * 3; break;
+  case 2:
+    if (coarsest) return fl_set_error(ctx, FL_ERR_INVALID, "the coarsest level has linear memories, not a spread image");
+    off = g.spread_off[modality]; n = (size_t)g.w * g.h; break;
+  case 3:
+    if (!coarsest) return fl_set_error(ctx, FL_ERR_INVALID, "only the coarsest level has linear memories");
+    off = g.lm_off[modality]; n = (size_t)8 * g.stride; break;
+  default: return fl_set_error(ctx, FL_ERR_INVALID, "kind %d", kind);
+  }
+  *bytes = n;
+  if (!out || cap < n) return fl_set_error(ctx, FL_ERR_INVALID, "%zu bytes needed, %zu given", n, cap);
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  FL_HIP(ctx, hipMemcpyAsync(out, det->d_ws + (size_t)frame * det->ws_stride + off, n, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FL_OK;
+}
+
 extern "C" int fl_build_linear_memories(fl_context *ctx, const uint8_t *quantized, int w, int h, int T, uint8_t *out,
                                         int mem)
 {

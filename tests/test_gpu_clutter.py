@@ -4,14 +4,13 @@ candidate of an instance has neighbours that tie or nearly tie with it, which is
 argmax, the sort / unique and the lazy fine levels have to get every tie right; the ICP crops hold background and parts of
 neighbouring instances.  Everything is compared with the oracle bit for bit, under every value of the runtime options
 (fl_context_set_option: "speed only: results are identical whatever they hold")."""
-import contextlib
-
 import numpy as np
 import pytest
 
 import clutter
 from fealess_amd import api
 from fealess_amd import _lib as L
+from util import options as _options
 
 pytestmark = pytest.mark.gpu
 
@@ -126,20 +125,6 @@ OPTION_RUNS = [
     {"icp_wide": 0, "icp_occ": 4}, {"icp_wide": 0, "icp_occ": 5},
     {"icp_wide": 0, "icp_wg_per_cu": 1}, {"icp_wide": 0, "icp_wg_per_cu": 2}, {"icp_wide": 0, "icp_wg_per_cu": 3},
 ]
-
-
-@contextlib.contextmanager
-def _options(c, opts):
-    """The options set on context c for the with-block, restored however the block ends."""
-    before = {k: c.get_option(k) for k in opts}
-    try:
-        for k, v in opts.items():
-            c.set_option(k, v)
-            assert c.get_option(k) == v
-        yield
-    finally:
-        for k, v in before.items():
-            c.set_option(k, v)
 
 
 def test_clutter_results_do_not_depend_on_runtime_options(oracle, scene, expected):

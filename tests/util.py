@@ -1,4 +1,5 @@
-"""Shared helpers for the test-suite (fixture loading, naive Python re-derivations)."""
+"""Shared helpers for the test-suite (fixture loading, runtime options, naive Python re-derivations)."""
+import contextlib
 import os
 
 import numpy as np
@@ -10,6 +11,20 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 def golden(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+
+
+@contextlib.contextmanager
+def options(c, opts):
+    """The options set on context c for the with-block, restored however the block ends."""
+    before = {k: c.get_option(k) for k in opts}
+    try:
+        for k, v in opts.items():
+            c.set_option(k, v)
+            assert c.get_option(k) == v
+        yield
+    finally:
+        for k, v in before.items():
+            c.set_option(k, v)
 
 
 def bank_from_arrays(templates, features, poses, levels, modalities, class_id="obj", model_depths=None):
