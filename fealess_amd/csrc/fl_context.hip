@@ -427,12 +427,7 @@ int fl_grow_candidates(fl_detector *det, int needed)
   if (want > (1ll << 28)) return fl_set_error(ctx, FL_ERR_OVERFLOW, "%d candidates in one frame", needed);
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int old_cap = det->cap;
-  // the frame workspaces (and with them any depth frames gathered into them) are about to be freed: nothing queued
-  // before this point may be refined afterwards
-  det->last_refinable = false;
-  det->last_depth_base = nullptr;
-  det->last_depth_stride = 0;
-  det->last_batch = 0;
+  fl_batch_forget(det);                                  // the frame workspaces are about to be freed
   (void)hipFree(det->d_ws);
   det->d_ws = nullptr;
   int rc = layout_workspace(det, (int)want);
@@ -443,6 +438,20 @@ int fl_grow_candidates(fl_detector *det, int needed)
   return FL_OK;
 }
 
+// The synchronous entry points' retry policy, after attempt `attempt` returned *rc: on FL_ERR_OVERFLOW grow the candidate
+// buffers to what the fullest of the last batch's n_frames frames needs and return true (run the call again), up to 6 times.
+// A valid Detector::match input never becomes an error unless the caller asked for a hard cap: then, or without the memory,
+// *rc becomes fl_grow_candidates' error.
+bool fl_grow_after_overflow(fl_detector *det, int n_frames, int attempt, int *rc)
+{
+  if (!det || *rc != FL_ERR_OVERFLOW || attempt >= 6) return false;
+  int needed = 0;
+  if (fl_overflow_needed(det, n_frames, &needed) != FL_OK || needed <= 0) return false;
+  const int g = fl_grow_candidates(det, needed);
+  if (g != FL_OK) { *rc = g; return false; }
+  return true;
+}
+
 extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_batch, int max_candidates)
 {
   if (!det || w0 <= 0 || h0 <= 0 || max_batch <= 0) return FL_ERR_INVALID;
@@ -451,6 +460,7 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_device_tables(det);
   det->finalized = false;
+  fl_batch_forget(det);
   const int L = det->L, M = det->M;
   // max_candidates > 0: initial per-frame capacity of the candidate / match buffers, grown on demand (the reference's
   // vectors are unbounded, linemod.cpp:1490-1504); < 0: a hard cap of -max_candidates (FL_ERR_OVERFLOW beyond it);
@@ -623,9 +633,5 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
                             hipHostMallocDefault));
   for (auto &e : det->ev) FL_HIP(ctx, hipEventCreate(&e));
   det->finalized = true;
-  det->last_batch = 0;
-  det->last_refinable = false;
-  det->last_depth_base = nullptr;
-  det->last_depth_stride = 0;
   return FL_OK;
 }

@@ -2682,6 +2682,33 @@ static int icp_launch(fl_context *ctx, int n_jobs, const IcpArgs &a)
   }
 }
 
+// the fields every ICP launch sets; all others zero
+static IcpArgs icp_args(uint8_t *ws, int n_max, int it_thr, float dmt, float ddt, int mode)
+{
+  IcpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ws = ws;
+  a.n_max = n_max;
+  a.it_thr = it_thr;
+  a.dmt = dmt;
+  a.ddt = ddt;
+  a.mode = mode;
+  return a;
+}
+
+// one job (kinds 1, 2) with its result slot at a.results: launch it and read the result back
+static int icp_run_one(fl_context *ctx, const IcpArgs &a, fl_recognition_result *out)
+{
+  int rc = icp_launch(ctx, 1, a);
+  if (rc) return rc;
+  fl_recognition_result *h = nullptr;
+  if ((rc = fl_pinned(ctx, sizeof(*h), (void **)&h))) return rc;
+  FL_HIP(ctx, hipMemcpyAsync(h, a.results, sizeof(*h), hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = *h;
+  return FL_OK;
+}
+
 static int icp_clouds(fl_context *ctx, const float *ref, const float *ref_normals, int n_ref, const float *model, int n_model,
                       int icp_it_thr, float dist_mean_thr, float dist_diff_thr, int icp_mode, int mem, fl_icp_result *res)
 {
@@ -2695,32 +2722,18 @@ static int icp_clouds(fl_context *ctx, const float *ref, const float *ref_normal
   int rc = fl_scratch(ctx, L.total + 4096, &s);
   if (rc) return rc;
   uint8_t *wsb = (uint8_t *)s;
-  fl_recognition_result *dres = (fl_recognition_result *)(wsb + L.total);
   const hipMemcpyKind kind = mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (n_ref) FL_HIP(ctx, hipMemcpyAsync(wsb + L.ref, ref, 12 * (size_t)n_ref, kind, ctx->stream));
   if (n_model) FL_HIP(ctx, hipMemcpyAsync(wsb + L.mod, model, 12 * (size_t)n_model, kind, ctx->stream));
   if (n_ref && ref_normals) FL_HIP(ctx, hipMemcpyAsync(wsb + L.nrm, ref_normals, 12 * (size_t)n_ref, kind, ctx->stream));
-  IcpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ws = wsb;
-  a.ws_stride = 0;
-  a.n_max = n_max;
-  a.it_thr = icp_it_thr;
-  a.dmt = dist_mean_thr;
-  a.ddt = dist_diff_thr;
-  a.mode = icp_mode;
+  IcpArgs a = icp_args(wsb, n_max, icp_it_thr, dist_mean_thr, dist_diff_thr, icp_mode);
   a.job.kind = 2;
   a.job.n_ref = n_ref;
   a.job.n_model = n_model;
-  a.results = dres;
-  rc = icp_launch(ctx, 1, a);
-  if (rc) return rc;
-  fl_recognition_result *h = nullptr;
-  rc = fl_pinned(ctx, sizeof(*h), (void **)&h);
-  if (rc) return rc;
-  FL_HIP(ctx, hipMemcpyAsync(h, dres, sizeof(*h), hipMemcpyDeviceToHost, ctx->stream));
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *res = h->det.icp;
+  a.results = (fl_recognition_result *)(wsb + L.total);
+  fl_recognition_result r;
+  if ((rc = icp_run_one(ctx, a, &r))) return rc;
+  *res = r.det.icp;
   return FL_OK;
 }
 
@@ -2766,20 +2779,13 @@ extern "C" int fl_detection(fl_context *ctx, const uint16_t *model_depth, const 
     dsn = (const uint16_t *)(b + img);
   }
   FL_HIP(ctx, hipMemsetAsync(dres, 0, sizeof(*dres), ctx->stream));
-  IcpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ws = wsb;
-  a.n_max = n_max;
+  IcpArgs a = icp_args(wsb, n_max, icp_it_thr, dist_mean_thr, dist_diff_thr, icp_mode);
   a.w = w;
   a.h = h;
   a.fx = (float)K->fx;
   a.fy = (float)K->fy;
   a.cx = (float)K->cx;
   a.cy = (float)K->cy;
-  a.it_thr = icp_it_thr;
-  a.dmt = dist_mean_thr;
-  a.ddt = dist_diff_thr;
-  a.mode = icp_mode;
   a.job.kind = 1;
   for (int k = 0; k < 4; ++k) { a.job.rect_model[k] = rect_model[k]; a.job.rect_ref[k] = rect_ref[k]; }
   for (int k = 0; k < 9; ++k) a.job.r_match[k] = r_match[k];
@@ -2787,95 +2793,14 @@ extern "C" int fl_detection(fl_context *ctx, const uint16_t *model_depth, const 
   a.job.model_depth = dm;
   a.job.scene_depth = dsn;
   a.results = dres;
-  rc = icp_launch(ctx, 1, a);
-  if (rc) return rc;
-  fl_recognition_result *hres = nullptr;
-  rc = fl_pinned(ctx, sizeof(*hres), (void **)&hres);
-  if (rc) return rc;
-  FL_HIP(ctx, hipMemcpyAsync(hres, dres, sizeof(*hres), hipMemcpyDeviceToHost, ctx->stream));
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *res = hres->det;
-  if (hres->status == FL_ERR_ASSERT) {
+  fl_recognition_result r;
+  if ((rc = icp_run_one(ctx, a, &r))) return rc;
+  *res = r.det;
+  if (r.status == FL_ERR_ASSERT) {
     res->status = FL_ERR_ASSERT;
     return fl_set_error(ctx, FL_ERR_ASSERT, "crop rectangle leaves the image (cv::Mat ROI assert, detection.cpp:43-44)");
   }
   return FL_OK;
-}
-
-// batch: one workgroup per frame of the detector workspace
-// Multi-hypothesis refinement: the first `k` matches of each of n_frames frames are refined by
-// n_frames * k workgroups of the same kernel, each with an ICP workspace of its own in `ws`.
-int fl_launch_detection_topk(fl_detector *det, int n_frames, int k, const fl_intrinsics *K, const fl_recognition_params *p,
-                             const uint16_t *depth, size_t depth_stride, uint8_t *ws, fl_recognition_result *d_results)
-{
-  fl_context *ctx = det->ctx;
-  IcpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ws = ws;
-  a.ws_stride = fl_icp_ws_bytes(det->n_pts_max);
-  a.n_max = det->n_pts_max;
-  a.w = det->w0;
-  a.h = det->h0;
-  a.fx = (float)K->fx;
-  a.fy = (float)K->fy;
-  a.cx = (float)K->cx;
-  a.cy = (float)K->cy;
-  a.it_thr = p->icp_it_thr;
-  a.dmt = p->dist_mean_thr;
-  a.ddt = p->dist_diff_thr;
-  a.mode = p->icp_mode;
-  a.job.kind = 0;
-  a.frame_ws = det->d_ws;
-  a.frame_stride = det->ws_stride;
-  a.ranks = k;
-  a.scene_base = depth;
-  a.scene_stride = depth_stride;
-  a.off_count = det->off_count;
-  a.off_match = det->off_match;
-  a.pyr = det->d_pyr;
-  a.class_first = det->d_class_first;
-  a.poses = det->d_poses;
-  a.depth_ptrs = det->d_depth_ptrs;
-  a.results = d_results;
-  return icp_launch(ctx, n_frames * k, a);
-}
-
-// refinement of caller-chosen matches (template-sharded recognition: the rank that owns the winning template refines it):
-// job b = (frame, match) read from the device array `jobs`, ICP workspace and result slot b
-int fl_launch_detection_jobs(fl_detector *det, int n_jobs, const FlRefineJob *d_jobs, const fl_intrinsics *K, const fl_recognition_params *p,
-                             const uint16_t *depth, size_t depth_stride)
-{
-  fl_context *ctx = det->ctx;
-  IcpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ws = det->d_ws + det->off_icp;
-  a.ws_stride = det->ws_stride;
-  a.n_max = det->n_pts_max;
-  a.w = det->w0;
-  a.h = det->h0;
-  a.fx = (float)K->fx;
-  a.fy = (float)K->fy;
-  a.cx = (float)K->cx;
-  a.cy = (float)K->cy;
-  a.it_thr = p->icp_it_thr;
-  a.dmt = p->dist_mean_thr;
-  a.ddt = p->dist_diff_thr;
-  a.mode = p->icp_mode;
-  a.job.kind = 0;
-  a.frame_ws = det->d_ws;
-  a.frame_stride = det->ws_stride;
-  a.ranks = 1;
-  a.scene_base = depth;
-  a.scene_stride = depth_stride;
-  a.off_count = det->off_count;
-  a.off_match = det->off_match;
-  a.pyr = det->d_pyr;
-  a.class_first = det->d_class_first;
-  a.poses = det->d_poses;
-  a.depth_ptrs = det->d_depth_ptrs;
-  a.results = det->d_results;
-  a.jobs = d_jobs;
-  return icp_launch(ctx, n_jobs, a);
 }
 
 // once per detector (fl_detector_finalize): the job-order buffer and k_icp_order's LDS size, so that no launch path allocates
@@ -2889,29 +2814,28 @@ int fl_icp_prepare(fl_detector *det)
   return FL_OK;
 }
 
-int fl_launch_detection_batch(fl_detector *det, int n_frames, const fl_intrinsics *K, const fl_recognition_params *p,
-                              const uint16_t *depth, size_t depth_stride)
+// Recognition refinement on the detector's frames (depth of frame i at depth + i * depth_stride bytes): n_jobs workgroups,
+// job b with the ICP workspace ws + b * ws_stride and result slot b.  Job b refines match (b % ranks) of frame (b / ranks) -- the
+// first `ranks` matches of each frame (multi-hypothesis) -- or, with d_jobs, the caller-chosen match d_jobs[b] (template-sharded
+// recognition: the rank that owns the winning template refines it).  longest_first: a batch with more jobs than the chip has
+// slots is dealt longest first (see k_icp_order; option icp_order = 0 keeps the frame order).
+int fl_launch_detection(fl_detector *det, int n_jobs, const fl_intrinsics *K, const fl_recognition_params *p, const uint16_t *depth,
+                        size_t depth_stride, uint8_t *ws, size_t ws_stride, int ranks, const FlRefineJob *d_jobs,
+                        fl_recognition_result *d_results, bool longest_first)
 {
   fl_context *ctx = det->ctx;
-  IcpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ws = det->d_ws + det->off_icp;
-  a.ws_stride = det->ws_stride;
-  a.n_max = det->n_pts_max;
+  IcpArgs a = icp_args(ws, det->n_pts_max, p->icp_it_thr, p->dist_mean_thr, p->dist_diff_thr, p->icp_mode);
+  a.ws_stride = ws_stride;
   a.w = det->w0;
   a.h = det->h0;
   a.fx = (float)K->fx;
   a.fy = (float)K->fy;
   a.cx = (float)K->cx;
   a.cy = (float)K->cy;
-  a.it_thr = p->icp_it_thr;
-  a.dmt = p->dist_mean_thr;
-  a.ddt = p->dist_diff_thr;
-  a.mode = p->icp_mode;
   a.job.kind = 0;
   a.frame_ws = det->d_ws;
   a.frame_stride = det->ws_stride;
-  a.ranks = 1;
+  a.ranks = ranks;
   a.scene_base = depth;
   a.scene_stride = depth_stride;
   a.off_count = det->off_count;
@@ -2920,18 +2844,17 @@ int fl_launch_detection_batch(fl_detector *det, int n_frames, const fl_intrinsic
   a.class_first = det->d_class_first;
   a.poses = det->d_poses;
   a.depth_ptrs = det->d_depth_ptrs;
-  a.results = det->d_results;
-  // more jobs than the chip has slots: deal them longest first (see k_icp_order); option icp_order = 0 keeps the frame order
-  if (n_frames > 4 * ctx->cus && n_frames <= ICP_ORDER_MAX && det->d_icp_order && ctx->opt.icp_order != 0) {
+  a.results = d_results;
+  a.jobs = d_jobs;
+  if (longest_first && n_jobs > 4 * ctx->cus && n_jobs <= ICP_ORDER_MAX && det->d_icp_order && ctx->opt.icp_order != 0) {
     int *d_size = det->d_icp_order + det->max_batch;
-    hipLaunchKernelGGL(k_icp_count, dim3(n_frames), dim3(256), 0, ctx->stream, a, d_size);
+    hipLaunchKernelGGL(k_icp_count, dim3(n_jobs), dim3(256), 0, ctx->stream, a, d_size);
     int m = 1;
-    while (m < n_frames) m <<= 1;
-    hipLaunchKernelGGL(k_icp_order, dim3(1), dim3(1024), sizeof(unsigned long long) * (size_t)m, ctx->stream, (const int *)d_size, n_frames,
+    while (m < n_jobs) m <<= 1;
+    hipLaunchKernelGGL(k_icp_order, dim3(1), dim3(1024), sizeof(unsigned long long) * (size_t)m, ctx->stream, (const int *)d_size, n_jobs,
                        det->d_icp_order);
     FL_HIP(ctx, hipGetLastError());
     a.order = det->d_icp_order;
   }
-  return icp_launch(ctx, n_frames, a);
+  return icp_launch(ctx, n_jobs, a);
 }
-

@@ -120,6 +120,17 @@ struct FlClass {
   int dw = 0, dh = 0;
 };
 
+// The batch whose front-end images, match lists and counters the frame workspaces hold, and where its depth frames are.
+// A call forgets it once its arguments pass their checks, before it overwrites frame workspaces or input buffers, and
+// records its own batch as soon as that batch's front-end and match are queued (a frame that overflows its candidate
+// buffers does not undo that).  A call that fails in between leaves no batch.
+struct FlBatch {
+  int n = 0;                             // frames (0: none)
+  const uint16_t *depth = nullptr;       // the frames' depth on the device; null: the batch cannot be refined (fl_refine_*)
+  size_t depth_stride = 0;
+  bool match_only = false;               // fl_match_batch_submit: no ICP stage to time
+};
+
 struct fl_detector {
   fl_context *ctx = nullptr;
   int M = 0, L = 0;
@@ -174,13 +185,7 @@ struct fl_detector {
   uint8_t *d_zoom_src = nullptr;         // and the un-zoomed host frames uploaded for it
   size_t zoom_src_bytes = 0;
   int n_pts_max = 0;
-  int last_batch = 0;
-  bool last_from_images = false;
-  const uint16_t *last_depth_base = nullptr;   // the last batch's depth frames on the device (fl_refine_matches reads them)
-  size_t last_depth_stride = 0;
-  bool last_match_only = false;          // the last batch was fl_match_batch_submit (no ICP stage to time)
-  bool last_refinable = false;           // the last batch came from a batch submit (stage_and_match) and its depth frames are still where
-                                         // last_depth_base says: only then may fl_refine_matches / fl_export_topk_batch follow
+  FlBatch batch;                         // what the last call left in the workspaces: fl_batch_forget / fl_batch_record only
 
   int *d_icp_order = nullptr;            // ICP launch: job order (longest first) + the jobs' size estimates, 2 * max_batch ints, on first use
   // template-sharded recognition on the device: the jobs fl_select_best_batch chose (frame = -1: not this rank's)
@@ -197,8 +202,29 @@ struct fl_detector {
   double scan_bytes_per_frame = 0;       // SURVEY 8(d) B_tmpl summed over the bank
 };
 
+static inline void fl_batch_forget(fl_detector *det) { det->batch = FlBatch(); }
+static inline void fl_batch_record(fl_detector *det, int n, const uint16_t *depth, size_t depth_stride, bool match_only)
+{
+  det->batch = FlBatch{n, depth, depth_stride, match_only};
+}
+
+// argument checks shared by entry points that return the same codes for them
+static inline int fl_check_frames(fl_detector *det, int n_frames)     // finalized (FL_ERR_STATE), n_frames <= max_batch (FL_ERR_INVALID)
+{
+  if (!det->finalized) return fl_set_error(det->ctx, FL_ERR_STATE, "fl_detector_finalize first");
+  if (n_frames > det->max_batch) return fl_set_error(det->ctx, FL_ERR_INVALID, "n_frames %d > max_batch %d", n_frames, det->max_batch);
+  return FL_OK;
+}
+static inline int fl_check_intrinsics(fl_detector *det, const fl_intrinsics *K)   // the finalized image size (FL_ERR_INVALID)
+{
+  if (K->width == det->w0 && K->height == det->h0) return FL_OK;
+  return fl_set_error(det->ctx, FL_ERR_INVALID, "intrinsics are %dx%d, detector finalized for %dx%d", K->width, K->height, det->w0, det->h0);
+}
+
 int fl_apply_class_filter(fl_detector *det);
 int fl_grow_candidates(fl_detector *det, int needed);      // re-lays the frame workspaces out for >= needed candidates per frame
+bool fl_grow_after_overflow(fl_detector *det, int n_frames, int attempt, int *rc);   // the synchronous entry points' retry policy
+int fl_upload_frame0(fl_detector *det, const uint8_t *bgr, const uint16_t *depth, int mem);   // a single frame into workspace 0
 int fl_overflow_needed(fl_detector *det, int n_frames, int *needed);   // after a sync: largest candidate count of an overflowed frame, 0 if none
 void fl_update_stage_times(fl_detector *det, int n_frames, const fl_recognition_result *results);
 
@@ -233,11 +259,6 @@ int fl_launch_resize_linear_u16(fl_context *ctx, const uint16_t *src, int sw, in
 // icp
 size_t fl_icp_ws_bytes(int n_pts_max);
 int fl_icp_prepare(fl_detector *det);      // fl_detector_finalize: job-order buffer, function attributes
-int fl_launch_detection_topk(fl_detector *det, int n_frames, int k, const fl_intrinsics *K, const fl_recognition_params *p,
-                             const uint16_t *depth, size_t depth_stride, uint8_t *ws, fl_recognition_result *d_results);
-size_t fl_icp_ws_bytes(int n_pts_max);
-int fl_launch_detection_jobs(fl_detector *det, int n_jobs, const FlRefineJob *d_jobs, const fl_intrinsics *K, const fl_recognition_params *p,
-                             const uint16_t *depth, size_t depth_stride);
-int fl_launch_detection_batch(fl_detector *det, int n_frames, const fl_intrinsics *K,
-                              const fl_recognition_params *p, const uint16_t *depth,
-                              size_t depth_stride);
+int fl_launch_detection(fl_detector *det, int n_jobs, const fl_intrinsics *K, const fl_recognition_params *p, const uint16_t *depth,
+                        size_t depth_stride, uint8_t *ws, size_t ws_stride, int ranks, const FlRefineJob *d_jobs,
+                        fl_recognition_result *d_results, bool longest_first);

@@ -1016,18 +1016,6 @@ int fl_overflow_needed(fl_detector *det, int n_frames, int *needed)
   return FL_OK;
 }
 
-// a synchronous entry point's retry policy: on FL_ERR_OVERFLOW grow the candidate buffers to what the frame needs and
-// run the call again (a valid Detector::match input never becomes an error unless the caller asked for a hard cap)
-static bool grow_after_overflow(fl_detector *det, int n_frames, int attempt, int *rc)
-{
-  if (*rc != FL_ERR_OVERFLOW || attempt >= 6) return false;
-  int needed = 0;
-  if (fl_overflow_needed(det, n_frames, &needed) != FL_OK || needed <= 0) return false;
-  const int g = fl_grow_candidates(det, needed);
-  if (g != FL_OK) { *rc = g; return false; }
-  return true;
-}
-
 // The queued entry points cannot replay a batch themselves; their caller can: after a batch in which a frame reported
 // FL_ERR_OVERFLOW (fl_recognition_result.status, or FL_TOPK_OVERFLOW in the exported records), this waits for the stream,
 // grows the candidate buffers to what the fullest of the last batch's first n_frames frames needs, and the caller submits
@@ -1037,14 +1025,14 @@ extern "C" int fl_detector_grow_candidates(fl_detector *det, int n_frames, int *
   if (!det || n_frames <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
   if (!det->finalized || n_frames > det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "n_frames");
-  if (det->last_batch == 0) {                            // nothing matched yet: no counters to read, just report the capacity
+  if (det->batch.n == 0) {                               // nothing matched yet: no counters to read, just report the capacity
     if (new_cap) *new_cap = det->cap;
     return FL_OK;
   }
   // only the last batch's frames have counters that mean anything: a flag left by an earlier, larger batch must not trigger a
   // stream sync, a free and a re-layout of every frame workspace
-  if (n_frames > det->last_batch)
-    return fl_set_error(ctx, FL_ERR_STATE, "n_frames %d > the %d frames of the last batch", n_frames, det->last_batch);
+  if (n_frames > det->batch.n)
+    return fl_set_error(ctx, FL_ERR_STATE, "n_frames %d > the %d frames of the last batch", n_frames, det->batch.n);
   FL_HIP(ctx, hipSetDevice(ctx->device));
   int needed = 0;
   int rc = fl_overflow_needed(det, n_frames, &needed);
@@ -1058,9 +1046,10 @@ extern "C" int fl_match_quantized(fl_detector *det, const uint8_t *const *quanti
 {
   if (!det || !quantized || cap < 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized) return fl_set_error(ctx, FL_ERR_STATE, "fl_detector_finalize first");
+  if (int rc = fl_check_frames(det, 1)) return rc;
   FL_HIP(ctx, hipSetDevice(ctx->device));
   for (int attempt = 0;; ++attempt) {
+    fl_batch_forget(det);
     for (int l = 0; l < det->L; ++l)
       for (int m = 0; m < det->M; ++m) {
         const FlLevelGeom &g = det->geom[l];
@@ -1071,12 +1060,9 @@ extern "C" int fl_match_quantized(fl_detector *det, const uint8_t *const *quanti
     det->lazy = false;                     // every level's quantised image was just supplied
     int rc = fl_launch_match_core(det, 1, threshold);
     if (rc) return rc;
-    det->last_batch = 1;
-    det->last_from_images = false;
-    det->last_refinable = false;           // no depth frame belongs to this batch
-    det->last_depth_base = nullptr;
+    fl_batch_record(det, 1, nullptr, 0, false);    // no depth frame belongs to this batch
     rc = read_matches(det, 0, out, cap, n_total);
-    if (!grow_after_overflow(det, 1, attempt, &rc)) return rc;
+    if (!fl_grow_after_overflow(det, 1, attempt, &rc)) return rc;
   }
 }
 
@@ -1098,23 +1084,34 @@ __global__ __launch_bounds__(256) void k_apply_mask(uint8_t *__restrict__ quant,
   if (!mask[(size_t)y * w0 + x]) quant[o] = 0;
 }
 
+// a single frame into workspace 0, where the single-frame entry points (fl_match_frame*, fl_recognize_topk) run it
+int fl_upload_frame0(fl_detector *det, const uint8_t *bgr, const uint16_t *depth, int mem)
+{
+  fl_context *ctx = det->ctx;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  const hipMemcpyKind kind = mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const size_t px = (size_t)det->w0 * det->h0;
+  FL_HIP(ctx, hipMemcpyAsync(det->d_ws + det->off_bgr, bgr, px * 3, kind, ctx->stream));
+  if (det->M == 2) FL_HIP(ctx, hipMemcpyAsync(det->d_ws + det->off_depth, depth, px * 2, kind, ctx->stream));
+  return FL_OK;
+}
+
 static int match_frame_masked_once(fl_detector *det, const uint8_t *bgr, const uint16_t *depth,
                                    const uint8_t *const *masks, int mem, float threshold, fl_match *out, int cap,
                                    int *n_total)
 {
   if (!det || !bgr || cap < 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized) return fl_set_error(ctx, FL_ERR_STATE, "fl_detector_finalize first");
+  int rc = fl_check_frames(det, 1);
+  if (rc) return rc;
   if (det->M == 2 && !depth) return fl_set_error(ctx, FL_ERR_INVALID, "sources.size() != modalities.size() (linemod.cpp:1364)");
-  FL_HIP(ctx, hipSetDevice(ctx->device));
-  const hipMemcpyKind kind = mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const size_t px = (size_t)det->w0 * det->h0;
-  FL_HIP(ctx, hipMemcpyAsync(det->d_ws + det->off_bgr, bgr, px * 3, kind, ctx->stream));
-  if (det->M == 2) FL_HIP(ctx, hipMemcpyAsync(det->d_ws + det->off_depth, depth, px * 2, kind, ctx->stream));
+  fl_batch_forget(det);
+  if ((rc = fl_upload_frame0(det, bgr, depth, mem))) return rc;
   det->have_times = false;
+  const size_t px = (size_t)det->w0 * det->h0;
   // whole quantised pyramids (masks apply to them, fl_last_quantized returns them): no lazy levels here
-  int rc = fl_launch_frontend(det, 1, det->d_ws + det->off_bgr, det->ws_stride,
-                              (const uint16_t *)(det->d_ws + det->off_depth), det->ws_stride, false);
+  rc = fl_launch_frontend(det, 1, det->d_ws + det->off_bgr, det->ws_stride, (const uint16_t *)(det->d_ws + det->off_depth),
+                          det->ws_stride, false);
   if (rc) return rc;
   uint8_t *d_mask = nullptr;
   if (masks) {
@@ -1136,10 +1133,7 @@ static int match_frame_masked_once(fl_detector *det, const uint8_t *bgr, const u
   }
   if (rc == FL_OK) rc = fl_launch_match_core(det, 1, threshold);
   if (rc == FL_OK) {
-    det->last_batch = 1;
-    det->last_from_images = true;
-    det->last_refinable = false;           // single-frame Detector::match: fl_refine_matches belongs to fl_match_batch_submit
-    det->last_depth_base = nullptr;
+    fl_batch_record(det, 1, nullptr, 0, false);    // single-frame Detector::match: fl_refine_matches belongs to batch submits
     rc = read_matches(det, 0, out, cap, n_total);
   } else if (rc == FL_ERR_HIP) {
     fl_set_error(ctx, rc, "mask upload / k_apply_mask launch failed");
@@ -1157,7 +1151,7 @@ extern "C" int fl_match_frame_masked(fl_detector *det, const uint8_t *bgr, const
 {
   for (int attempt = 0;; ++attempt) {
     int rc = match_frame_masked_once(det, bgr, depth, masks, mem, threshold, out, cap, n_total);
-    if (!det || !grow_after_overflow(det, 1, attempt, &rc)) return rc;
+    if (!fl_grow_after_overflow(det, 1, attempt, &rc)) return rc;
   }
 }
 
@@ -1173,10 +1167,10 @@ extern "C" int fl_match_batch_collect(fl_detector *det, int frame, fl_match *out
 {
   if (!det || cap < 0 || (cap > 0 && !out)) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized || frame < 0 || frame >= det->last_batch) return fl_set_error(ctx, FL_ERR_STATE, "no such frame in the last batch");
+  if (!det->finalized || frame < 0 || frame >= det->batch.n) return fl_set_error(ctx, FL_ERR_STATE, "no such frame in the last batch");
   FL_HIP(ctx, hipSetDevice(ctx->device));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  fl_update_stage_times(det, det->last_batch, nullptr);
+  fl_update_stage_times(det, det->batch.n, nullptr);
   return read_matches(det, frame, out, cap, n_total);
 }
 
@@ -1184,7 +1178,7 @@ extern "C" int fl_similarity_maps(fl_detector *det, int first, int count, uint16
 {
   if (!det || !out || first < 0 || count <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized || det->last_batch < 1) return fl_set_error(ctx, FL_ERR_STATE, "no frame matched yet");
+  if (!det->finalized || det->batch.n < 1) return fl_set_error(ctx, FL_ERR_STATE, "no frame matched yet");
   if (first + count > det->n_pyr) return fl_set_error(ctx, FL_ERR_INVALID, "pyramid range");
   FL_HIP(ctx, hipSetDevice(ctx->device));
   const FlLevelGeom &g = det->geom[det->L - 1];
@@ -1220,7 +1214,7 @@ extern "C" int fl_frame_counters(fl_detector *det, int frame, int32_t out[4])
   FL_HIP(ctx, hipSetDevice(ctx->device));
   FL_HIP(ctx, hipMemcpyAsync(out, det->d_ws + (size_t)frame * det->ws_stride + det->off_count, 16, hipMemcpyDeviceToHost, ctx->stream));
   uint32_t bm[2 * FL_TILE_WORDS];
-  const bool lazy = det->lazy && det->L > 1 && frame < det->last_batch;
+  const bool lazy = det->lazy && det->L > 1 && frame < det->batch.n;
   if (lazy)        // level 0's two tile bitmaps: [0] tiles whose spread bytes are read, [1] tiles whose pixels are quantised
     FL_HIP(ctx, hipMemcpyAsync(bm, det->d_ws + (size_t)frame * det->ws_stride + det->off_tiles, sizeof(bm), hipMemcpyDeviceToHost, ctx->stream));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1237,7 +1231,7 @@ extern "C" int fl_last_quantized(fl_detector *det, uint8_t *out)
 {
   if (!det || !out) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized || det->last_batch < 1) return fl_set_error(ctx, FL_ERR_STATE, "no frame matched yet");
+  if (!det->finalized || det->batch.n < 1) return fl_set_error(ctx, FL_ERR_STATE, "no frame matched yet");
   if (det->lazy)
     return fl_set_error(ctx, FL_ERR_STATE, "the last batch (fl_recognize_*) quantised its finer levels only around the candidates; "
                                            "use fl_match_frame, or FL_EAGER_FRONTEND=1, for whole quantised pyramids");
@@ -1265,8 +1259,8 @@ extern "C" int fl_dev_frame_image(fl_detector *det, int frame, int kind, int lev
 {
   if (!det || !bytes) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized || det->last_batch < 1) return fl_set_error(ctx, FL_ERR_STATE, "no batch matched yet");
-  if (frame < 0 || frame >= det->last_batch) return fl_set_error(ctx, FL_ERR_INVALID, "frame %d is not in the last batch", frame);
+  if (!det->finalized || det->batch.n < 1) return fl_set_error(ctx, FL_ERR_STATE, "no batch matched yet");
+  if (frame < 0 || frame >= det->batch.n) return fl_set_error(ctx, FL_ERR_INVALID, "frame %d is not in the last batch", frame);
   if (level < 0 || level >= det->L || modality < 0 || modality >= det->M)
     return fl_set_error(ctx, FL_ERR_INVALID, "level %d / modality %d out of range", level, modality);
   const FlLevelGeom &g = det->geom[level];
@@ -1370,7 +1364,7 @@ extern "C" int fl_export_topk_batch(fl_detector *det, int n_frames, int k, int t
   if (!det || !dev_out || k <= 0 || n_frames <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
   if (!det->finalized || n_frames > det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "n_frames");
-  if (n_frames > det->last_batch) return fl_set_error(ctx, FL_ERR_STATE, "%d frames asked for, the last batch had %d", n_frames, det->last_batch);
+  if (n_frames > det->batch.n) return fl_set_error(ctx, FL_ERR_STATE, "%d frames asked for, the last batch had %d", n_frames, det->batch.n);
   FL_HIP(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_export_topk_batch, dim3(n_frames), dim3(64), 0, ctx->stream, det->d_ws, det->ws_stride, det->off_count,
                      det->off_match, k, template_id_base, (fl_match *)dev_out);
@@ -1421,8 +1415,7 @@ extern "C" int fl_select_best_batch(fl_detector *det, const void *dev_gathered, 
 {
   if (!det || !dev_gathered || !dev_best || n_ranks <= 0 || n_frames <= 0 || k <= 0 || tid_first < 0 || tid_count < 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized) return fl_set_error(ctx, FL_ERR_STATE, "fl_detector_finalize first");
-  if (n_frames > det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "n_frames %d > max_batch %d", n_frames, det->max_batch);
+  if (int rc = fl_check_frames(det, n_frames)) return rc;
   if (det->classes.size() != 1 || tid_count != det->classes[0].n_pyramids)
     return fl_set_error(ctx, FL_ERR_INVALID, "template-sharded refinement: one class per detector, tid_count = its %d pyramids",
                         det->classes.empty() ? 0 : det->classes[0].n_pyramids);

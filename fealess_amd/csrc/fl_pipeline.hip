@@ -21,8 +21,8 @@ static bool uniform_stride(const void *const *ptrs, int n, size_t min_bytes, siz
   return true;
 }
 
-// argument checks, frame staging, front-end and Detector::match of a batch; the depth frames' device location comes back
-// (K == nullptr: Detector::match only, no intrinsics to check)
+// argument checks, frame staging, front-end and Detector::match of a batch, which it records (refinable when depth frames were
+// given); the depth frames' device location comes back (K == nullptr: Detector::match only, no intrinsics to check)
 static int stage_and_match(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth, int mem,
                            const fl_intrinsics *K, float threshold, const uint16_t **depth_base_out,
                            size_t *depth_stride_out, int *host_buf_out)
@@ -30,16 +30,15 @@ static int stage_and_match(fl_detector *det, int n_frames, const uint8_t *const 
   int host_buf = -1;     // the input buffer the batch was uploaded to (host frames), released by input_done()
   if (!det || !bgr || n_frames <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized) return fl_set_error(ctx, FL_ERR_STATE, "fl_detector_finalize first");
-  if (n_frames > det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "n_frames %d > max_batch %d", n_frames, det->max_batch);
+  int rc = fl_check_frames(det, n_frames);
+  if (rc) return rc;
   if (det->M == 2 && !depth) return fl_set_error(ctx, FL_ERR_INVALID, "depth frames required (2 modalities)");
   // PrepareInputData (obj_reco_lmicp.cpp:216-259): image size must equal the intrinsics' size
-  if (K && (K->width != det->w0 || K->height != det->h0))
-    return fl_set_error(ctx, FL_ERR_INVALID, "intrinsics are %dx%d, detector finalized for %dx%d", K->width, K->height,
-                        det->w0, det->h0);
+  if (K && (rc = fl_check_intrinsics(det, K))) return rc;
   for (int i = 0; i < n_frames; ++i)
     if (!bgr[i] || (det->M == 2 && !depth[i])) return fl_set_error(ctx, FL_ERR_INVALID, "frame %d: null pData (CheckTImage)", i);
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  fl_batch_forget(det);
 
   const size_t bgr_bytes = (size_t)det->w0 * det->h0 * 3, depth_bytes = (size_t)det->w0 * det->h0 * 2;
   const uint8_t *bgr_base = det->d_ws + det->off_bgr;
@@ -95,15 +94,11 @@ static int stage_and_match(fl_detector *det, int n_frames, const uint8_t *const 
   }
   det->have_times = true;
   FL_HIP(ctx, hipEventRecord(det->ev[0], ctx->stream));
-  int rc = fl_launch_frontend(det, n_frames, bgr_base, bgr_stride, depth_base, depth_stride, true);
-  if (rc) return rc;
-  rc = fl_launch_match_core(det, n_frames, threshold);
-  if (rc) return rc;
+  if ((rc = fl_launch_frontend(det, n_frames, bgr_base, bgr_stride, depth_base, depth_stride, true))) return rc;
+  if ((rc = fl_launch_match_core(det, n_frames, threshold))) return rc;
+  fl_batch_record(det, n_frames, depth ? depth_base : nullptr, depth_stride, K == nullptr);
   *depth_base_out = depth_base;
   *depth_stride_out = depth_stride;
-  det->last_depth_base = depth_base;
-  det->last_depth_stride = depth_stride;
-  det->last_refinable = depth != nullptr;  // fl_refine_matches runs the ICP half: it needs the batch's depth frames
   *host_buf_out = host_buf;
   return FL_OK;
 }
@@ -125,10 +120,10 @@ void fl_update_stage_times(fl_detector *det, int n_frames, const fl_recognition_
     t.refine_ms -= t.lazy_frontend_ms;
   }
   t.sort_ms = el(4, 5);
-  t.icp_ms = det->last_match_only ? 0.f : el(5, 6);
+  t.icp_ms = det->batch.match_only ? 0.f : el(5, 6);
   t.total_ms = el(0, 6);
   t.backproject_ms = 0;                 // fused into the per-frame ICP workgroup
-  t.icp_launches = det->last_match_only ? 0 : 1;
+  t.icp_launches = det->batch.match_only ? 0 : 1;
   if (results)
     for (int i = 0; i < n_frames; ++i) t.icp_iters_total += results[i].found ? results[i].det.icp.iters : 0;
   t.scan_algorithmic_bytes = det->scan_bytes_per_frame * n_frames;
@@ -157,15 +152,13 @@ extern "C" int fl_recognize_submit(fl_detector *det, int n_frames, const uint8_t
   if (rc) return rc;
   fl_context *ctx = det->ctx;
   FL_HIP(ctx, hipMemsetAsync(det->d_results, 0, sizeof(fl_recognition_result) * (size_t)n_frames, ctx->stream));
-  rc = fl_launch_detection_batch(det, n_frames, K, params, depth_base, depth_stride);
+  rc = fl_launch_detection(det, n_frames, K, params, depth_base, depth_stride, det->d_ws + det->off_icp, det->ws_stride, 1, nullptr,
+                           det->d_results, true);
   if (rc) return rc;
   if ((rc = input_done(det, host_buf))) return rc;
   FL_HIP(ctx, hipEventRecord(det->ev[6], ctx->stream));
   FL_HIP(ctx, hipMemcpyAsync(det->h_results, det->d_results, sizeof(fl_recognition_result) * (size_t)n_frames,
                              hipMemcpyDeviceToHost, ctx->stream));
-  det->last_batch = n_frames;
-  det->last_from_images = true;
-  det->last_match_only = false;
   return FL_OK;
 }
 
@@ -180,12 +173,8 @@ extern "C" int fl_match_batch_submit(fl_detector *det, int n_frames, const uint8
   int host_buf = -1;
   int rc = stage_and_match(det, n_frames, bgr, depth, mem, nullptr, threshold, &depth_base, &depth_stride, &host_buf);
   if (rc) return rc;
-  fl_context *ctx = det->ctx;
   if ((rc = input_done(det, host_buf))) return rc;
-  FL_HIP(ctx, hipEventRecord(det->ev[6], ctx->stream));
-  det->last_batch = n_frames;
-  det->last_from_images = true;
-  det->last_match_only = true;
+  FL_HIP(det->ctx, hipEventRecord(det->ev[6], det->ctx->stream));
   return FL_OK;
 }
 
@@ -193,7 +182,7 @@ extern "C" int fl_recognize_collect(fl_detector *det, int n_frames, fl_recogniti
 {
   if (!det || !results || n_frames <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized || n_frames > det->last_batch) return fl_set_error(ctx, FL_ERR_STATE, "nothing submitted");
+  if (!det->finalized || n_frames > det->batch.n) return fl_set_error(ctx, FL_ERR_STATE, "nothing submitted");
   FL_HIP(ctx, hipSetDevice(ctx->device));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(results, det->h_results, sizeof(fl_recognition_result) * (size_t)n_frames);
@@ -211,12 +200,9 @@ extern "C" int fl_recognize_batch(fl_detector *det, int n_frames, const uint8_t 
     int rc = fl_recognize_submit(det, n_frames, bgr, depth, mem, K, params);
     if (rc) return rc;
     if ((rc = fl_recognize_collect(det, n_frames, results))) return rc;
-    bool over = false;
-    for (int i = 0; i < n_frames; ++i) over = over || results[i].status == FL_ERR_OVERFLOW;
-    if (!over || attempt >= 6) return FL_OK;
-    int needed = 0;
-    if (fl_overflow_needed(det, n_frames, &needed) != FL_OK || needed <= 0) return FL_OK;
-    if (fl_grow_candidates(det, needed) != FL_OK) return FL_OK;      // hard cap / no memory: the per-frame statuses say so
+    for (int i = 0; i < n_frames; ++i)
+      if (results[i].status == FL_ERR_OVERFLOW) rc = FL_ERR_OVERFLOW;
+    if (!fl_grow_after_overflow(det, n_frames, attempt, &rc)) return FL_OK;   // a failed growth too: the per-frame statuses say why
   }
 }
 
@@ -229,11 +215,11 @@ extern "C" int fl_recognize_batch_zoom(fl_detector *det, int n_frames, const uin
 {
   if (!det || !bgr || !depth || !K || !params || !results || n_frames <= 0 || src_w <= 0 || src_h <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized) return fl_set_error(ctx, FL_ERR_STATE, "fl_detector_finalize first");
-  if (n_frames > det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "n_frames %d > max_batch %d", n_frames, det->max_batch);
+  if (int rc = fl_check_frames(det, n_frames)) return rc;
   for (int i = 0; i < n_frames; ++i)
     if (!bgr[i] || !depth[i]) return fl_set_error(ctx, FL_ERR_INVALID, "frame %d: null pData (CheckTImage)", i);
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  fl_batch_forget(det);                  // d_zoom may hold the last batch's depth frames
   const int w = det->w0, h = det->h0;
   const size_t zb = fl_align((size_t)w * h * 3, 256), zf = zb + fl_align((size_t)w * h * 2, 256);
   if (!det->d_zoom) FL_HIP(ctx, hipMalloc((void **)&det->d_zoom, zf * (size_t)det->max_batch));
@@ -276,15 +262,13 @@ extern "C" int fl_refine_matches(fl_detector *det, int n_jobs, const int32_t *fr
 {
   if (!det || !frames || !matches || !K || !params || !results || n_jobs <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  // only a batch submit leaves the depth frames of the batch where last_depth_base says; fl_match_frame*, fl_match_quantized,
-  // fl_recognize_topk and a candidate-buffer growth (which frees the frame workspaces) all clear last_refinable
-  if (!det->finalized || det->last_batch < 1 || !det->last_from_images || !det->last_refinable || !det->last_depth_base)
-    return fl_set_error(ctx, FL_ERR_STATE, "fl_match_batch_submit first");
-  if (n_jobs > det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "n_jobs %d > max_batch %d", n_jobs, det->max_batch);
-  if (K->width != det->w0 || K->height != det->h0) return fl_set_error(ctx, FL_ERR_INVALID, "intrinsics size");
+  // the batch record has depth frames only while they are where it says (see FlBatch)
+  if (!det->finalized || det->batch.n < 1 || !det->batch.depth) return fl_set_error(ctx, FL_ERR_STATE, "fl_match_batch_submit first");
+  int rc = fl_check_frames(det, n_jobs);
+  if (rc || (rc = fl_check_intrinsics(det, K))) return rc;
   std::vector<FlRefineJob> jobs((size_t)n_jobs);
   for (int j = 0; j < n_jobs; ++j) {
-    if (frames[j] < 0 || frames[j] >= det->last_batch) return fl_set_error(ctx, FL_ERR_INVALID, "job %d: frame %d is not in the last batch", j, frames[j]);
+    if (frames[j] < 0 || frames[j] >= det->batch.n) return fl_set_error(ctx, FL_ERR_INVALID, "job %d: frame %d is not in the last batch", j, frames[j]);
     const fl_match &m = matches[j];
     if (m.class_idx < 0 || m.class_idx >= (int)det->classes.size() || m.template_id < 0 ||
         m.template_id >= det->classes[m.class_idx].n_pyramids)
@@ -294,12 +278,13 @@ extern "C" int fl_refine_matches(fl_detector *det, int n_jobs, const int32_t *fr
   }
   FL_HIP(ctx, hipSetDevice(ctx->device));
   void *sv = nullptr;
-  int rc = fl_scratch(ctx, sizeof(FlRefineJob) * (size_t)n_jobs, &sv);
-  if (rc) return rc;
+  if ((rc = fl_scratch(ctx, sizeof(FlRefineJob) * (size_t)n_jobs, &sv))) return rc;
   FL_HIP(ctx, hipMemcpyAsync(sv, jobs.data(), sizeof(FlRefineJob) * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
   FL_HIP(ctx, hipMemsetAsync(det->d_results, 0, sizeof(fl_recognition_result) * (size_t)n_jobs, ctx->stream));
   det->have_times = false;
-  if ((rc = fl_launch_detection_jobs(det, n_jobs, (const FlRefineJob *)sv, K, params, det->last_depth_base, det->last_depth_stride))) return rc;
+  if ((rc = fl_launch_detection(det, n_jobs, K, params, det->batch.depth, det->batch.depth_stride, det->d_ws + det->off_icp, det->ws_stride, 1,
+                                (const FlRefineJob *)sv, det->d_results, false)))
+    return rc;
   FL_HIP(ctx, hipMemcpyAsync(det->h_results, det->d_results, sizeof(fl_recognition_result) * (size_t)n_jobs, hipMemcpyDeviceToHost, ctx->stream));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));          // also covers the pageable `jobs` upload
   memcpy(results, det->h_results, sizeof(fl_recognition_result) * (size_t)n_jobs);
@@ -325,17 +310,18 @@ extern "C" int fl_refine_selected(fl_detector *det, int n_frames, const fl_intri
   fl_context *ctx = det->ctx;
   if (!det->finalized || !det->d_jobs || det->selected_frames != n_frames)
     return fl_set_error(ctx, FL_ERR_STATE, "fl_select_best_batch for these %d frames first", n_frames);
-  if (K->width != det->w0 || K->height != det->h0) return fl_set_error(ctx, FL_ERR_INVALID, "intrinsics size");
+  if (int rc = fl_check_intrinsics(det, K)) return rc;
   if (!depth_base) {
-    if (!det->last_refinable || !det->last_depth_base || n_frames > det->last_batch)
+    if (!det->batch.depth || n_frames > det->batch.n)
       return fl_set_error(ctx, FL_ERR_STATE, "no depth frames given and fl_match_batch_submit did not leave any");
-    depth_base = det->last_depth_base;
-    depth_stride = det->last_depth_stride;
+    depth_base = det->batch.depth;
+    depth_stride = det->batch.depth_stride;
   }
   FL_HIP(ctx, hipSetDevice(ctx->device));
   FL_HIP(ctx, hipMemsetAsync(det->d_results, 0, sizeof(fl_recognition_result) * (size_t)n_frames, ctx->stream));
   det->have_times = false;
-  int rc = fl_launch_detection_jobs(det, n_frames, det->d_jobs, K, params, depth_base, depth_stride);
+  int rc = fl_launch_detection(det, n_frames, K, params, depth_base, depth_stride, det->d_ws + det->off_icp, det->ws_stride, 1, det->d_jobs,
+                               det->d_results, false);
   if (rc) return rc;
   hipLaunchKernelGGL(k_pack_pose_rows, dim3(n_frames), dim3(64), 0, ctx->stream, det->d_results, n_frames, dev_rows);
   FL_HIP(ctx, hipGetLastError());
@@ -349,46 +335,30 @@ static int recognize_topk_once(fl_detector *det, const uint8_t *bgr, const uint1
 {
   if (!det || !bgr || !depth || !K || !params || !results || !n_results || k < 1 || k > 1024) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
-  if (!det->finalized) return fl_set_error(ctx, FL_ERR_STATE, "fl_detector_finalize first");
+  int rc = fl_check_frames(det, 1);
+  if (rc) return rc;
   if (det->M != 2) return fl_set_error(ctx, FL_ERR_INVALID, "needs the colour + depth modalities");
-  if (K->width != det->w0 || K->height != det->h0)
-    return fl_set_error(ctx, FL_ERR_INVALID, "intrinsics are %dx%d, detector finalized for %dx%d", K->width, K->height, det->w0, det->h0);
-  FL_HIP(ctx, hipSetDevice(ctx->device));
-  const hipMemcpyKind kind = mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  FL_HIP(ctx, hipMemcpyAsync(det->d_ws + det->off_bgr, bgr, (size_t)det->w0 * det->h0 * 3, kind, ctx->stream));
-  FL_HIP(ctx, hipMemcpyAsync(det->d_ws + det->off_depth, depth, (size_t)det->w0 * det->h0 * 2, kind, ctx->stream));
+  if ((rc = fl_check_intrinsics(det, K))) return rc;
+  fl_batch_forget(det);
+  if ((rc = fl_upload_frame0(det, bgr, depth, mem))) return rc;
   det->have_times = false;
   const uint16_t *d_depth = (const uint16_t *)(det->d_ws + det->off_depth);
-  int rc = fl_launch_frontend(det, 1, det->d_ws + det->off_bgr, det->ws_stride, d_depth, det->ws_stride, true);
-  if (rc) return rc;
-  rc = fl_launch_match_core(det, 1, params->matching_threshold);
-  if (rc) return rc;
+  if ((rc = fl_launch_frontend(det, 1, det->d_ws + det->off_bgr, det->ws_stride, d_depth, det->ws_stride, true))) return rc;
+  if ((rc = fl_launch_match_core(det, 1, params->matching_threshold))) return rc;
+  fl_batch_record(det, 1, nullptr, 0, false);   // the frame lives in workspace 0 only until the next call: not a batch to refine later
   const size_t icp_bytes = fl_align(fl_icp_ws_bytes(det->n_pts_max), 256) * (size_t)k, res_bytes = sizeof(fl_recognition_result) * (size_t)k;
   void *sv = nullptr;
   if ((rc = fl_scratch(ctx, icp_bytes + fl_align(res_bytes, 256), &sv))) return rc;
   fl_recognition_result *d_res = (fl_recognition_result *)((uint8_t *)sv + icp_bytes);
   FL_HIP(ctx, hipMemsetAsync(d_res, 0, res_bytes, ctx->stream));
-  if ((rc = fl_launch_detection_topk(det, 1, k, K, params, d_depth, 0, (uint8_t *)sv, d_res))) return rc;
+  if ((rc = fl_launch_detection(det, k, K, params, d_depth, 0, (uint8_t *)sv, fl_icp_ws_bytes(det->n_pts_max), k, nullptr, d_res, false)))
+    return rc;
   FL_HIP(ctx, hipMemcpyAsync(results, d_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  det->last_batch = 1;
-  det->last_from_images = true;
-  det->last_refinable = false;             // the frame lives in workspace 0 only until the next call: not a batch to refine later
-  det->last_depth_base = nullptr;
   if (results[0].status == FL_ERR_OVERFLOW) return fl_set_error(ctx, FL_ERR_OVERFLOW, "more than %d candidates in the frame", det->cap);
   const int n = results[0].n_matches < k ? results[0].n_matches : k;
   *n_results = n < 0 ? 0 : n;
   return FL_OK;
-}
-
-static bool grow_and_retry(fl_detector *det, int n_frames, int attempt, int *rc)
-{
-  if (!det || *rc != FL_ERR_OVERFLOW || attempt >= 6) return false;
-  int needed = 0;
-  if (fl_overflow_needed(det, n_frames, &needed) != FL_OK || needed <= 0) return false;
-  const int g = fl_grow_candidates(det, needed);
-  if (g != FL_OK) { *rc = g; return false; }
-  return true;
 }
 
 extern "C" int fl_recognize_topk(fl_detector *det, const uint8_t *bgr, const uint16_t *depth, int mem, const fl_intrinsics *K,
@@ -396,7 +366,7 @@ extern "C" int fl_recognize_topk(fl_detector *det, const uint8_t *bgr, const uin
 {
   for (int attempt = 0;; ++attempt) {
     int rc = recognize_topk_once(det, bgr, depth, mem, K, params, k, results, n_results);
-    if (!grow_and_retry(det, 1, attempt, &rc)) return rc;
+    if (!fl_grow_after_overflow(det, 1, attempt, &rc)) return rc;
   }
 }
 
@@ -424,12 +394,12 @@ static int recognize_batch_topk_once(fl_detector *det, int n_frames, const uint8
   if ((rc = fl_scratch(ctx, icp_bytes + fl_align(res_bytes, 256), &sv))) return rc;
   fl_recognition_result *d_res = (fl_recognition_result *)((uint8_t *)sv + icp_bytes);
   FL_HIP(ctx, hipMemsetAsync(d_res, 0, res_bytes, ctx->stream));
-  if ((rc = fl_launch_detection_topk(det, n_frames, k, K, params, depth_base, depth_stride, (uint8_t *)sv, d_res))) return rc;
+  if ((rc = fl_launch_detection(det, n_frames * k, K, params, depth_base, depth_stride, (uint8_t *)sv, fl_icp_ws_bytes(det->n_pts_max), k,
+                                nullptr, d_res, false)))
+    return rc;
   if ((rc = input_done(det, host_buf))) return rc;
   FL_HIP(ctx, hipMemcpyAsync(results, d_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  det->last_batch = n_frames;
-  det->last_from_images = true;
   for (int f = 0; f < n_frames; ++f) {
     const fl_recognition_result &r0 = results[(size_t)f * k];
     if (r0.status == FL_ERR_OVERFLOW) return fl_set_error(ctx, FL_ERR_OVERFLOW, "frame %d: more than %d candidates", f, det->cap);
@@ -445,7 +415,7 @@ extern "C" int fl_recognize_batch_topk(fl_detector *det, int n_frames, const uin
 {
   for (int attempt = 0;; ++attempt) {
     int rc = recognize_batch_topk_once(det, n_frames, bgr, depth, mem, K, params, k, results, n_results);
-    if (!grow_and_retry(det, n_frames, attempt, &rc)) return rc;
+    if (!fl_grow_after_overflow(det, n_frames, attempt, &rc)) return rc;
   }
 }
 

@@ -623,7 +623,33 @@ def test_refine_matches_argument_checks_and_result(ctx, oracle):
     with pytest.raises(api.FealessError) as ex:
         det.refine_matches([0], best, sc["K"], params)
     assert ex.value.code == L.FL_ERR_STATE
+    # a multi-hypothesis batch does leave its depth frames
+    det.recognize_batch_topk([sc["bgr"]], [sc["depth"]], sc["K"], 2, 75.0, 7, 0.0, -3.0e38)
+    res = det.refine_matches([0], best, sc["K"], params)
+    assert res[0].found == 1 and np.array_equal(_bits(np.array(list(res[0].pose), np.float32)), _bits(ref["pose"].reshape(-1)))
+    import ctypes as C
+    # a call refused for its arguments (intrinsics of another size) leaves the previous batch refinable
+    det.match_batch([sc["bgr"]], [sc["depth"]], 75.0)
+    bp = (C.c_void_p * 1)(sc["bgr"].ctypes.data)
+    dp = (C.c_void_p * 1)(sc["depth"].ctypes.data)
+    out = (L.RecognitionResult * 1)()
+    rc = det.lib.fl_recognize_batch(det.h, 1, bp, dp, L.FL_MEM_HOST, C.byref(L.Intrinsics(320, 240, *sc["K"])), C.byref(params), out)
+    assert rc == L.FL_ERR_INVALID
+    assert det.refine_matches([0], best, sc["K"], params)[0].found == 1
     det.close()
+    # a frame that overflows its candidate buffers leaves the batch refinable; the growth that follows frees the workspaces
+    small = api.Detector(ctx, 2, [5, 8])
+    small.add_class(sc["bank"])
+    small.finalize(640, 480, max_batch=1, max_candidates=16)
+    small.match_batch_submit([sc["bgr"].ctypes.data], [sc["depth"].ctypes.data], -100.0, L.FL_MEM_HOST)
+    assert small.frame_counters(0)[2] != 0
+    res = small.refine_matches([0], best, sc["K"], params)
+    assert res[0].found == 1 and np.array_equal(_bits(np.array(list(res[0].pose), np.float32)), _bits(ref["pose"].reshape(-1)))
+    assert small.grow_candidates(1) > 16
+    with pytest.raises(api.FealessError) as ex:
+        small.refine_matches([0], best, sc["K"], params)
+    assert ex.value.code == L.FL_ERR_STATE
+    small.close()
 
 
 def test_large_batch_jobs_dealt_longest_first_keep_their_results(ctx, oracle):
