@@ -17,11 +17,15 @@ configs[3]: every rank holds templates/N templates and sees the same frames, the
 all-gathered (RCCL), merged as one Detector::match would order them, and the rank that owns the winning template
 refines it (ICP); see fealess_amd/bench_sharded.py.
 
-The JSON line carries `roofline` (dominant kernel, algorithmic bytes of SURVEY.md section 8(d)
-over the launch duration measured with HIP events on the launch stream) and `cpu_baseline` (the
-oracle = CPU restatement of the reference, timed on this box's host cores on a bounded sample).
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line, whose
+`roofline` (dominant kernel, algorithmic bytes of SURVEY.md section 8(d) over the launch duration measured
+with HIP events on the launch stream) comes from the last timed step.  `--full` adds every figure that needs
+work of its own: `cpu_baseline` (the oracle = CPU restatement of the reference, timed on the host cores on
+a bounded sample), the unpruned scan (`scan_kernel`, c3's roofline), the PCIe-inclusive rate, and on the
+default workload the batch sweeps, the other banks, front-end orders, ICP mode and configurations (`extras`).
 """
 import argparse
+import concurrent.futures as cf
 import hashlib
 import json
 import os
@@ -68,11 +72,16 @@ def parse():
                          "libfealess_mg.so (include/fealess_mg.h: ncclAllGather / ncclAllReduce from C++; needs one GPU per rank)")
     ap.add_argument("--verify-sharded", action="store_true",
                     help="--shard templates: rank 0 also runs one detector over the whole bank and checks every frame's result bit for bit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="--shard frames: also every figure that takes work of its own -- CPU baseline, unpruned scan (scan_kernel, "
+                         "c3's roofline), PCIe-inclusive rate and on the default workload the extras (batch sweeps, other banks, "
+                         "front-end order, ICP mode and configurations); a plain run reports the headline and what its last timed "
+                         "step measured")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full or --shard templates: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra figures of the default line (360 templates, eager front-end, batch sweep, PCIe-inclusive)")
+                    help="--full: skip the extra figures of the default line (360 templates, eager front-end, batch sweep, PCIe-inclusive)")
     ap.add_argument("--host-frames-steps", type=int, default=6,
-                    help="extra untimed-for-value steps with the frames in pinned HOST memory (upload inside the step): the "
+                    help="--full: extra untimed-for-value steps with the frames in pinned HOST memory (upload inside the step): the "
                          "PCIe-inclusive rate reported as pcie_inclusive (0 = skip)")
     ap.add_argument("--eager-frontend", action="store_true",
                     help="quantise and spread the finer pyramid levels in full before the scan (the reference's order) instead of "
@@ -121,29 +130,32 @@ def build_bank(ctx, args, n_templates, w, h, K, spread_trained=False):
     levels = args.levels
     fx, fy, cx, cy = K
 
-    def trained_template(Rv, tv, seed):
-        d_bg, bgr_v, mask = synth.render(w, h, Rv, tv, seed=seed, noise=False, background=True, fx=fx, fy=fy, cx=cx, cy=cy)
-        ex = ctx.extract_template_pyramid(bgr_v, d_bg, (mask * 255).astype(np.uint8), levels)
-        if ex is None:
-            return None
-        d_obj, _, _ = synth.render(w, h, Rv, tv, seed=seed, noise=False, background=False, fx=fx, fy=fy, cx=cx, cy=cy)
-        return ex[0], synth.pose13(Rv, tv), (d_obj.astype(np.uint32) * 10).clip(0, 65535).astype(np.uint16)
-
+    # every pose first, in the generator's order; then the renders (each draws from its own seeded generator, so
+    # rendering them side by side on host threads gives what one after the other gives); then the extraction, in order
     rng = np.random.default_rng(1234)
-    scenes = []
-    trained = []
+    poses, views = [], []
     for s in range(args.scenes):
         R, t = synth.object_pose(tx=float(rng.uniform(-60, 60)), ty=float(rng.uniform(-40, 40)),
                                  tz=float(rng.uniform(620, 700)), yaw=float(rng.uniform(-0.4, 0.4)),
                                  tilt=float(rng.uniform(0.25, 0.45)), roll=float(rng.uniform(-0.1, 0.2)))
-        depth, bgr, _ = synth.render(w, h, R, t, seed=100 + s, fx=fx, fy=fy, cx=cx, cy=cy)
-        scenes.append((bgr, depth))
+        poses.append((R, t))
         for v in range(2):
             dR = synth.rot_z(np.deg2rad(rng.uniform(-2, 2))) @ synth.rot_x(np.deg2rad(rng.uniform(-2, 2)))
             tt = t + np.array([rng.uniform(-20, 20), rng.uniform(-15, 15), rng.uniform(-8, 8)])
-            out = trained_template(dR @ R, tt, seed=1000 + 10 * s + v)
-            if out is not None and len(trained) < n_templates:
-                trained.append(out)
+            views.append((dR @ R, tt, 1000 + 10 * s + v))
+    cam = dict(fx=fx, fy=fy, cx=cx, cy=cy)
+    jobs = [dict(R_obj=R, t_obj=t, seed=100 + s, **cam) for s, (R, t) in enumerate(poses)]
+    for Rv, tv, seed in views:                    # a view with its background (extraction) and alone (ICP's model depth)
+        jobs += [dict(R_obj=Rv, t_obj=tv, seed=seed, noise=False, background=bg, **cam) for bg in (True, False)]
+    with cf.ThreadPoolExecutor(max(1, min(len(jobs), host_cores()[0]))) as pool:
+        images = list(pool.map(lambda kw: synth.render(w, h, **kw), jobs))
+    scenes = [(bgr, depth) for depth, bgr, _ in images[:len(poses)]]
+    trained = []
+    for j, (Rv, tv, _) in enumerate(views):
+        (d_bg, bgr_v, mask), (d_obj, _, _) = images[len(poses) + 2 * j:len(poses) + 2 * j + 2]
+        ex = ctx.extract_template_pyramid(bgr_v, d_bg, (mask * 255).astype(np.uint8), levels)
+        if ex is not None and len(trained) < n_templates:
+            trained.append((ex[0], synth.pose13(Rv, tv), (d_obj.astype(np.uint32) * 10).clip(0, 65535).astype(np.uint16)))
     # where the trained views sit in the bank: leading it (default), or every (n / trained)-th pyramid
     nt = len(trained)
     at = {((j * n_templates) // nt if spread_trained else j): j for j in range(nt)}
@@ -250,7 +262,6 @@ def cpu_baseline(args, bank, scenes, K):
                                 "the GPU's per-frame figures for the same two stages are gpu_stage_ms_per_frame")
     # SURVEY 8(d) also asks for the restatement over all host cores: frames are independent, one per thread
     # (ctypes releases the GIL during the call; the oracle keeps no shared mutable state)
-    import concurrent.futures as cf
     cores, cores_src = host_cores()
     per_thread = max(1, int(round(n / el * args.cpu_seconds / 2)))       # about cpu_seconds / 2 of work per thread
 
@@ -573,9 +584,9 @@ def main():
                           "data_path": "none (frame-sharded: disjoint frames per rank, whole bank replicated)",
                           "timing": "barrier + all_reduce(MAX) of the ranks' elapsed time" if dist is not None else "single rank"}
     if rank == 0:
-        if not args.no_extras and world == 1 and args.config == "c2":
+        if args.full and not args.no_extras and world == 1 and args.config == "c2":
             out.update(extras(args, ctx, run, bank, bgrs, depths, w, h, K))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cb = cpu_baseline(args, bank, scenes, K)
             out["speedup_vs_cpu_baseline"] = round(value / cb["value"], 1)
             if "linemod_ms" in cb and "stage_ms_last_step" in out:
@@ -684,10 +695,20 @@ def line_c2(args, run, res, times, value, el, world, bank, T, bgrs, depths, sync
                                      note="SURVEY 8(d)'s B_icp as written: iters*n*72 + 2*14*W*H per frame, i.e. with the reference's two "
                                           "FULL-FRAME back-projections, which the fused kernel does not perform -- a flattering numerator, "
                                           "kept for comparison with earlier rounds only")
-    scan_full_ms = unpruned_scan_ms(run)
-    scan_ach = gbs(scan_bytes, scan_full_ms)
+    scan_kernel = None
+    if args.full:
+        scan_full_ms = unpruned_scan_ms(run)
+        scan_ach = gbs(scan_bytes, scan_full_ms)
+        scan_kernel = {"scan_ms": round(times["scan_ms"], 4), "unpruned_scan_ms": round(scan_full_ms, 4),
+                       "achieved_GBs": round(scan_ach, 1), "frac": round(scan_ach / HBM_PEAK_GBS, 4),
+                       "l2_frac": round(scan_ach / L2_PEAK_GBS, 4), "l2_peak_GBs": L2_PEAK_GBS,
+                       "note": "achieved_GBs / l2_frac: algorithmic bytes (SURVEY 8d N*B_tmpl) over the duration of the UNPRUNED kernel "
+                               "(option scan_prune = 0: every addition performed); the linear memories are L2-resident, so the meaningful roof is "
+                               "the aggregate L2 bandwidth (l2_frac), not HBM (frac may exceed 1).  scan_ms is the kernel the headline runs: "
+                               "it stops a (template, chunk) between the modalities once no position can reach the coarse threshold "
+                               "(exact, data-dependent: same match lists)"}
     pcie = None
-    if args.host_frames_steps > 0 and world == 1 and not args.no_extras:          # like cpu_baseline: N = 1 only
+    if args.full and args.host_frames_steps > 0 and world == 1 and not args.no_extras:          # like cpu_baseline: N = 1 only
         # informational: the same step with host frames (pinned), i.e. 1.54 MB per frame over PCIe inside the step
         torch = run.torch
         h_bgr = torch.from_numpy(bgrs).pin_memory()
@@ -727,34 +748,29 @@ def line_c2(args, run, res, times, value, el, world, bank, T, bgrs, depths, sync
         "icp_points_mean": round(npts / max(1, found), 1),
         "stage_ms_last_step": {k: round(v, 4) for k, v in times.items() if k.endswith("_ms")},
         "roofline": roofline,
-        "scan_kernel": {"scan_ms": round(times["scan_ms"], 4), "unpruned_scan_ms": round(scan_full_ms, 4),
-                        "achieved_GBs": round(scan_ach, 1), "frac": round(scan_ach / HBM_PEAK_GBS, 4),
-                        "l2_frac": round(scan_ach / L2_PEAK_GBS, 4), "l2_peak_GBs": L2_PEAK_GBS,
-                        "note": "achieved_GBs / l2_frac: algorithmic bytes (SURVEY 8d N*B_tmpl) over the duration of the UNPRUNED kernel "
-                                "(option scan_prune = 0: every addition performed); the linear memories are L2-resident, so the meaningful roof is "
-                                "the aggregate L2 bandwidth (l2_frac), not HBM (frac may exceed 1).  scan_ms is the kernel the headline runs: "
-                                "it stops a (template, chunk) between the modalities once no position can reach the coarse threshold "
-                                "(exact, data-dependent: same match lists)"},
+        "scan_kernel": scan_kernel,
     }
 
 
 def line_c3(args, run, res, times, value, el, world, bank, T):
     B = args.batch
-    scan_bytes = times["scan_algorithmic_bytes"]
-    scan_full_ms = unpruned_scan_ms(run)
-    scan_ach = gbs(scan_bytes, scan_full_ms)
     stage = {k: round(v, 4) for k, v in times.items() if k.endswith("_ms")}
-    dom = max(("frontend_ms", "linmem_ms", "scan_ms", "refine_ms", "lazy_frontend_ms"), key=lambda k: times[k])
-    traffic, traffic_detail = pmc_traffic(args, bank, "k_scan")
-    roofline = dict(bound="hbm", kernel="k_scan", achieved=round(scan_ach, 2), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(scan_ach / HBM_PEAK_GBS, 5), traffic=traffic, launch_ms=round(scan_full_ms, 4),
-                    pruned_launch_ms=round(times["scan_ms"], 4),
-                    algorithmic_bytes_per_launch=scan_bytes, numerator="SURVEY 8(d): N*B_tmpl per frame",
-                    l2_frac=round(scan_ach / L2_PEAK_GBS, 5), l2_peak=L2_PEAK_GBS, traffic_detail=traffic_detail,
-                    note="launch_ms / achieved / frac: the UNPRUNED kernel (option scan_prune = 0: every addition of N*B_tmpl performed); `value` runs "
-                         "the pruning kernel (pruned_launch_ms: a (template, chunk) stops between the modalities once no position can reach "
-                         "the threshold -- exact, data-dependent).  The scan's linear memories are L2-resident: judge it against the L2 roof "
-                         "(l2_frac); longest stage of the step: " + dom)
+    roofline = None                                      # judged on the unpruned scan: a run of its own, --full only
+    if args.full:
+        scan_bytes = times["scan_algorithmic_bytes"]
+        scan_full_ms = unpruned_scan_ms(run)
+        scan_ach = gbs(scan_bytes, scan_full_ms)
+        dom = max(("frontend_ms", "linmem_ms", "scan_ms", "refine_ms", "lazy_frontend_ms"), key=lambda k: times[k])
+        traffic, traffic_detail = pmc_traffic(args, bank, "k_scan")
+        roofline = dict(bound="hbm", kernel="k_scan", achieved=round(scan_ach, 2), peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=round(scan_ach / HBM_PEAK_GBS, 5), traffic=traffic, launch_ms=round(scan_full_ms, 4),
+                        pruned_launch_ms=round(times["scan_ms"], 4),
+                        algorithmic_bytes_per_launch=scan_bytes, numerator="SURVEY 8(d): N*B_tmpl per frame",
+                        l2_frac=round(scan_ach / L2_PEAK_GBS, 5), l2_peak=L2_PEAK_GBS, traffic_detail=traffic_detail,
+                        note="launch_ms / achieved / frac: the UNPRUNED kernel (option scan_prune = 0: every addition of N*B_tmpl performed); `value` runs "
+                             "the pruning kernel (pruned_launch_ms: a (template, chunk) stops between the modalities once no position can reach "
+                             "the threshold -- exact, data-dependent).  The scan's linear memories are L2-resident: judge it against the L2 roof "
+                             "(l2_frac); longest stage of the step: " + dom)
     return {
         "metric": "frames/sec (1280x720 RGB-D x N templates, Detector::match only)",
         "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

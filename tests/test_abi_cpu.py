@@ -292,3 +292,43 @@ def test_bench_gpus_flag_launches_its_own_ranks():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--launch-check"], env=env,
                          capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "WORLD_SIZE" in bad.stderr
+
+
+def test_bench_bank_does_not_depend_on_the_render_threads(monkeypatch):
+    """bench.build_bank renders its scenes and training views on host threads: one thread and several give the same scenes,
+    the same extraction calls in the same order and the same bank.  A stand-in for the extraction (no GPU) derives a template
+    from the bytes it is handed and rejects some views, so that both branches of the training loop run."""
+    import hashlib
+    import bench
+
+    class Extractor:
+        def __init__(self):
+            self.calls = []
+
+        def extract_template_pyramid(self, bgr, depth, mask, levels):
+            key = hashlib.sha256(bgr.tobytes() + depth.tobytes() + mask.tobytes()).digest()
+            self.calls.append(key)
+            if key[0] % 4 == 0:
+                return None
+            f = (np.frombuffer(key, np.uint8)[:30].astype(np.int32) % 8).reshape(-1, 3)
+            return ([dict(width=40, height=40, offset_x=2 * l, offset_y=4, pyramid_level=l, features=f)
+                     for l in range(levels) for _ in range(2)],)
+
+    monkeypatch.setattr("sys.argv", ["bench.py", "--scenes", "3"])
+    args = bench.parse()
+    w, h, K = bench.geometry(args)
+    got = []
+    for threads in ("1", "4"):
+        monkeypatch.setenv("FL_BENCH_CPU_THREADS", threads)
+        ex = Extractor()
+        bank, scenes = bench.build_bank(ex, args, 40, w, h, K, spread_trained=True)
+        got.append((ex.calls, scenes, bank))
+    (calls1, scenes1, bank1), (calls4, scenes4, bank4) = got
+    assert len(calls1) == 6 and calls1 == calls4
+    assert len(scenes1) == len(scenes4) == 3
+    assert all(np.array_equal(a, b) for s1, s4 in zip(scenes1, scenes4) for a, b in zip(s1, s4))
+    assert bank1.n_pyramids == bank4.n_pyramids == 40
+    assert all(np.array_equal(a, b) for a, b in zip(bank1.arrays(), bank4.arrays()))
+    depths1 = [None if d is None else d.tobytes() for d in bank1.model_depths]
+    assert depths1 == [None if d is None else d.tobytes() for d in bank4.model_depths]
+    assert sum(d is not None for d in depths1) > 0

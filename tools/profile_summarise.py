@@ -1,4 +1,4 @@
-"""Turn the raw rocprofv3 output of tools/profile_round.sh (under gpurun_out/) into the committed summaries:
+"""Turn the raw rocprofv3 output of tools/profile_round.sh (under $PROFILE_RAW, default profile_raw/) into the committed summaries:
 profiles/<tag>_kernel_stats.csv, profiles/<tag>_pmc.json (stamped with the digest of the kernel sources it was
 collected on: bench.py quotes `traffic` from it only while that digest matches), profiles/<tag>_bench.json,
 profiles/<tag>_bench_c3.json.
@@ -22,12 +22,12 @@ tag = argv[1]
 batch = int(argv[2]) if len(argv) > 2 else 1280
 templates = int(argv[3]) if len(argv) > 3 else 2000
 out = os.path.join(ROOT, "profiles")
-src = os.path.join(ROOT, "gpurun_out")
+src = os.path.join(ROOT, os.environ.get("PROFILE_RAW", "profile_raw"))
 
-# gpurun merges every call's output into gpurun_out/, so older runs may still be there: take the newest file only
+# the folder may still hold the output of older runs: take the newest file only
 if not pmc_only:
     stats = sorted(glob.glob(os.path.join(src, "prof_final", "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)
-    assert stats, "no kernel_stats.csv under gpurun_out/prof_final"
+    assert stats, f"no kernel_stats.csv under {src}/prof_final"
     shutil.copy(stats[-1], os.path.join(out, f"{tag}_kernel_stats.csv"))
 
 acc = collections.defaultdict(lambda: collections.defaultdict(float))
