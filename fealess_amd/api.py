@@ -160,6 +160,19 @@ class Context:
                                                   icp_it_thr, dist_mean_thr, dist_diff_thr, L.FL_MEM_HOST, C.byref(res)))
         return icp_result_to_dict(res)
 
+    def dev_scene_normals(self, depth_mm, K, xs, ys):
+        """DEVELOPMENT ONLY (fl_dev_scene_normals, not part of the C ABI): the unit normals FL_ICP_POINT_TO_PLANE gives the scene
+        pixels (xs[i], ys[i]) of a u16 depth image (mm) with intrinsics K = (fx, fy, cx, cy); (0, 0, 0) where it gives none."""
+        fn = self.lib.fl_dev_scene_normals
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
+        d = np.ascontiguousarray(depth_mm, np.uint16)
+        h, w = d.shape
+        xy = np.ascontiguousarray(np.stack([np.asarray(xs).ravel(), np.asarray(ys).ravel()], 1), np.int32)
+        out = np.zeros((len(xy), 3), np.float32)
+        self.check(fn(_ptr(d), w, h, *[float(v) for v in K], _ptr(xy), len(xy), _ptr(out)))
+        return out
+
     def detection(self, model_depth_mm, scene_depth_mm, K, rect_model, rect_ref, icp_it_thr, dist_mean_thr,
                   dist_diff_thr, r_match, t_match, mode=L.FL_ICP_PARITY):
         md = np.ascontiguousarray(model_depth_mm, np.uint16)

@@ -2156,6 +2156,46 @@ __device__ __forceinline__ void scene_normal(const uint16_t *__restrict__ scene,
   n[0] = c[0] / len; n[1] = c[1] / len; n[2] = c[2] / len;
 }
 
+// dev / tests: scene_normal at n pixels (xy[2 k], xy[2 k + 1]) of a w x h depth image (tests/test_gpu_icp.py checks it against
+// the fp64 restatement in tests/p2plane_model.py)
+__global__ void k_dev_scene_normals(const uint16_t *depth, int w, int h, float fx, float fy, float cx, float cy, const int *xy, int n,
+                                    float *out)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  float nv[3];
+  scene_normal(depth, w, h, xy[2 * k], xy[2 * k + 1], fx, fy, cx, cy, nv);
+  out[3 * k] = nv[0]; out[3 * k + 1] = nv[1]; out[3 * k + 2] = nv[2];
+}
+
+// host entry for the test: pixels outside the image are refused (scene_normal's window test assumes 0 <= x < w, 0 <= y < h);
+// plain HIP calls on the null stream.  The image is followed by one spare row of zeros, so that a window rule that is off by
+// one reads a zero inside the allocation and the test reports a wrong normal.
+extern "C" int fl_dev_scene_normals(const uint16_t *depth_host, int w, int h, float fx, float fy, float cx, float cy, const int *xy_host,
+                                    int n, float *out_host)
+{
+  if (w <= 0 || h <= 0 || n <= 0 || (long long)w * (h + 1) > (1ll << 28)) return FL_ERR_INVALID;
+  for (int k = 0; k < n; ++k)
+    if (xy_host[2 * k] < 0 || xy_host[2 * k] >= w || xy_host[2 * k + 1] < 0 || xy_host[2 * k + 1] >= h) return FL_ERR_INVALID;
+  const size_t img = sizeof(uint16_t) * (size_t)w * h, pad = sizeof(uint16_t) * (size_t)w;
+  uint16_t *d_depth = nullptr;
+  int *d_xy = nullptr;
+  float *d_out = nullptr;
+  bool ok = hipMalloc(&d_depth, img + pad) == hipSuccess && hipMalloc(&d_xy, 2 * sizeof(int) * (size_t)n) == hipSuccess &&
+            hipMalloc(&d_out, 3 * sizeof(float) * (size_t)n) == hipSuccess;
+  ok = ok && hipMemcpy(d_depth, depth_host, img, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemset((uint8_t *)d_depth + img, 0, pad) == hipSuccess &&
+       hipMemcpy(d_xy, xy_host, 2 * sizeof(int) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_dev_scene_normals, dim3((n + 255) / 256), dim3(256), 0, 0, d_depth, w, h, fx, fy, cx, cy, d_xy, n, d_out);
+    ok = hipGetLastError() == hipSuccess && hipMemcpy(out_host, d_out, 3 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  (void)hipFree(d_depth);
+  (void)hipFree(d_xy);
+  (void)hipFree(d_out);
+  return ok ? FL_OK : FL_ERR_HIP;
+}
+
 template <class SH>
 __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16_t *scene, const uint16_t *model, bool model_01mm,
                            const int *rm, const int *rr, float *ref, float *mod, float *nrm, float *rimg, int *idximg, float *zimg)
@@ -2664,8 +2704,10 @@ template <int MODE>
 static int icp_launch_mode(fl_context *ctx, int n_jobs, const IcpArgs &a)
 {
   const bool wide = icp_wide(ctx, n_jobs);
-  if (MODE == FL_ICP_PARITY && a.job.kind != 2 && !wide && icp_small_wpe(ctx, n_jobs) == 5)
-    return icp_launch_one<ICP_BS_SMALL>(ctx, k_icp_pipeline<MODE, ICP_BS_SMALL, 5>, n_jobs, a);
+  if constexpr (MODE == FL_ICP_PARITY) {              // the 5-per-CU build exists for the parity kernel only
+    if (a.job.kind != 2 && !wide && icp_small_wpe(ctx, n_jobs) == 5)
+      return icp_launch_one<ICP_BS_SMALL>(ctx, k_icp_pipeline<MODE, ICP_BS_SMALL, 5>, n_jobs, a);
+  }
   if (a.job.kind == 2)
     return wide ? icp_launch_one<ICP_BS_WIDE>(ctx, k_icp_clouds<MODE, ICP_BS_WIDE>, n_jobs, a)
                 : icp_launch_one<ICP_BS_SMALL>(ctx, k_icp_clouds<MODE, ICP_BS_SMALL>, n_jobs, a);

@@ -382,7 +382,7 @@ def _reco_dict(res, rc=0):
 
 
 def recognition_topk(bgr, depth, K, T_pyramid, bank, k, threshold=75.0, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01,
-                     nms_dist=None):
+                     nms_dist=None, accum64=False):
     """First k matches refined like Recognition() does for matches[0]; with nms_dist also the NMS winners."""
     b = np.ascontiguousarray(bgr, np.uint8)
     d = np.ascontiguousarray(depth, np.uint16)
@@ -398,7 +398,7 @@ def recognition_topk(bgr, depth, K, T_pyramid, bank, k, threshold=75.0, icp_it_t
     res = (OrcRecognitionResult * k)()
     n = lib().orc_recognition_topk(_p(b), _p(d), w, h, C.c_double(K[0]), C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]),
                                    levels, T, C.byref(arr[0]), _p(p), mptr, C.c_float(threshold), icp_it_thr,
-                                   C.c_float(dist_mean_thr), C.c_float(dist_diff_thr), 0, 1, k, res)
+                                   C.c_float(dist_mean_thr), C.c_float(dist_diff_thr), int(accum64), 1, k, res)
     if n < 0:
         raise AssertionError("reference CV_Assert")
     out = [_reco_dict(res[i]) for i in range(n)]

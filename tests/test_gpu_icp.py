@@ -3,13 +3,16 @@
 FL_ICP_PARITY accumulates the reference's float32 sums as sequential chains, so every number is
 expected to be bit-identical to the oracle's float32 mode (tolerance 0 is asserted where the
 whole chain is deterministic; the pose bar from BASELINE.json's north_star is 1e-4).
-FL_ICP_FAST is compared with the oracle's fp64-accumulation yardstick.
+FL_ICP_FAST is compared with the oracle's fp64-accumulation yardstick, FL_ICP_POINT_TO_PLANE with the fp64 statements in
+tests/p2plane_model.py; both on their 1024- and 256-thread builds (MODE_WIDTHS).
 """
 import numpy as np
 import pytest
 
 from fealess_amd import api, synth
 from fealess_amd import _lib as L
+
+import util
 
 pytestmark = pytest.mark.gpu
 
@@ -87,6 +90,24 @@ def width(request, ctx):
     ctx.set_option("icp_occ", 0)
 
 
+# Both builds of the FL_ICP_FAST and FL_ICP_POINT_TO_PLANE kernels (k_icp_pipeline and k_icp_clouds, 1024 and 256 threads): a
+# single job gets the 1024-thread one by default, a batch of more than two jobs per CU the 256-thread one; icp_wide forces
+# either.  Those modes have no 5-per-CU build (the width fixture's 256x5 is the parity kernel's).
+MODE_WIDTHS = (1024, 256)
+
+
+def _mode_width(ctx, w):
+    """The options that force the w-thread build for the with-block (restored however it ends)."""
+    return util.options(ctx, {"icp_wide": 1 if w == 1024 else 0, "icp_occ": 0})
+
+
+@pytest.fixture(params=MODE_WIDTHS)
+def mode_width(request, ctx):
+    """Each of MODE_WIDTHS in turn.  The tests that predate it loop over MODE_WIDTHS themselves (and keep their names)."""
+    with _mode_width(ctx, request.param):
+        yield request.param
+
+
 @pytest.mark.parametrize("seed,n,it", [(1, 6000, 20), (2, 1500, 10), (3, 12000, 6)])
 def test_icp_parity_mode_matches_oracle32(ctx, oracle, seed, n, it, width):
     ref, model = _clouds(seed, n)
@@ -123,44 +144,68 @@ def test_icp_fast_mode_close_to_fp64_yardstick(ctx, oracle):
     would be without float32 summation noise) and the oracle's float32 mode = the reference's own arithmetic, the bar the
     north_star's 1e-4 is stated against (ICP.cpp:8-25,731-735: sequential float32 sums).  |f32 - f64| is the reference's
     own summation noise floor (measured on the box: R 1.2e-5, T 1.6e-3 mm); FAST cannot be closer to f32 than that floor
-    (it sits 5e-7 / 7e-5 mm from the exact sums), and must be within 1e-4 of both, T relative to the clouds' size."""
+    (it sits 5e-7 / 7e-5 mm from the exact sums), and must be within 1e-4 of both, T relative to the clouds' size.  On each
+    of MODE_WIDTHS."""
     worst = [0.0] * 6
     for seed, n in ((5, 6000), (6, 9000), (7, 3000)):
         ref, model = _clouds(seed, n)
-        got = ctx.icp_cloud_to_cloud_ex(ref, model, 20, 0.0, -3.0e38, L.FL_ICP_FAST)
         e64 = oracle.icp(ref, model, 20, 0.0, -3.0e38, accum64=True)
         e32 = oracle.icp(ref, model, 20, 0.0, -3.0e38, accum64=False)
-        assert got["iters"] == e64["iters"] == e32["iters"]
-        scale = float(np.abs(ref).max())                        # ~ 700 mm: the clouds' coordinates
-        d = _pose_dist(got, e64, scale) + _pose_dist(got, e32, scale) + _pose_dist(e32, e64, scale)
-        worst = [max(a, b) for a, b in zip(worst, d)]
-        assert np.abs(got["T"] - e64["T"]).max() <= 1e-3          # mm, against the exact sums
+        for w in MODE_WIDTHS:
+            with _mode_width(ctx, w):
+                got = ctx.icp_cloud_to_cloud_ex(ref, model, 20, 0.0, -3.0e38, L.FL_ICP_FAST)
+            assert got["iters"] == e64["iters"] == e32["iters"], w
+            scale = float(np.abs(ref).max())                    # ~ 700 mm: the clouds' coordinates
+            d = _pose_dist(got, e64, scale) + _pose_dist(got, e32, scale) + _pose_dist(e32, e64, scale)
+            worst = [max(a, b) for a, b in zip(worst, d)]
+            assert np.abs(got["T"] - e64["T"]).max() <= 1e-3, (w, seed)     # mm, against the exact sums
     print("FL_ICP_FAST on clouds: |FAST-f64| R %.3g T(rel) %.3g; |FAST-f32| R %.3g T(rel) %.3g; |f32-f64| R %.3g T(rel) %.3g" % tuple(worst))
     assert worst[0] <= POSE_TOL and worst[1] <= POSE_TOL          # vs the fp64 yardstick
     assert worst[2] <= POSE_TOL and worst[3] <= POSE_TOL          # vs the reference's float32 arithmetic (north_star's bar)
 
 
+@pytest.mark.parametrize("seed,n", [(9, 300), (14, 1000)])
+def test_icp_fast_mode_small_shuffled_clouds_close_to_fp64_yardstick(ctx, oracle, seed, n, mode_width):
+    """FL_ICP_FAST on small clouds in random point order, where one pair is a larger share of every sum and the points at
+    both ends of the arrays (the first and the last, partial, stride of the workgroup) are inliers rather than the object's
+    outline: within the bars of test_icp_fast_mode_close_to_fp64_yardstick of the oracle's fp64 yardstick, with the same
+    number of pairs at the end."""
+    ref, model = _clouds(seed, n)
+    p = np.random.default_rng(seed).permutation(n)
+    ref, model = ref[p], model[p]
+    got = ctx.icp_cloud_to_cloud_ex(ref, model, 20, 0.0, -3.0e38, L.FL_ICP_FAST)
+    e64 = oracle.icp(ref, model, 20, 0.0, -3.0e38, accum64=True)
+    assert got["iters"] == e64["iters"] == 20 and got["n_corr_last"] == e64["n_corr_last"]
+    dr, dt = _pose_dist(got, e64, float(np.abs(ref).max()))
+    print("FL_ICP_FAST on %d shuffled points, %d threads: |FAST-f64| R %.3g T %.3g mm" % (n, mode_width, dr, np.abs(got["T"] - e64["T"]).max()))
+    assert dr <= POSE_TOL and dt <= POSE_TOL
+    assert np.abs(got["T"] - e64["T"]).max() <= 1e-3
+
+
 def test_icp_fast_mode_recognition_vs_the_f32_oracle(ctx, oracle):
     """The same question for the whole Recognition() (crop back-projection, pre-alignment, ICP, pose composition): the
-    final 4x4 of FL_ICP_FAST against the float32 oracle's (what the reference computes) and against the fp64 yardstick."""
+    final 4x4 of FL_ICP_FAST against the float32 oracle's (what the reference computes) and against the fp64 yardstick.
+    On each of MODE_WIDTHS."""
     worst = [0.0] * 6
+
+    def pose(r):
+        return dict(R=r["pose"][:3, :3], T=r["pose"][:3, 3])
     for seed in (3, 4, 5):
         sc = synth.recognition_scene(lambda b, d, l: oracle.quantize_pyramid(b, d, l), levels=2, seed=seed, n_views=3)
+        e32 = oracle.recognition(sc["bgr"], sc["depth"], sc["K"], [5, 8], sc["bank"], 75.0, 20, 0.0, -3.0e38, accum64=False)
+        e64 = oracle.recognition(sc["bgr"], sc["depth"], sc["K"], [5, 8], sc["bank"], 75.0, 20, 0.0, -3.0e38, accum64=True)
         det = api.Detector(ctx, 2, [5, 8])
         det.add_class(sc["bank"])
         det.finalize(640, 480, max_batch=1)
-        got = det.recognize_batch([sc["bgr"]], [sc["depth"]], sc["K"], 75.0, 20, 0.0, -3.0e38, mode=L.FL_ICP_FAST)[0]
+        for w in MODE_WIDTHS:
+            with _mode_width(ctx, w):
+                got = det.recognize_batch([sc["bgr"]], [sc["depth"]], sc["K"], 75.0, 20, 0.0, -3.0e38, mode=L.FL_ICP_FAST)[0]
+            assert got["found"] == e32["found"] == e64["found"] == 1, w
+            assert got["best"]["template_id"] == e32["best"]["template_id"], w
+            scale = float(np.abs(e32["pose"][:3, 3]).max())       # ~ 650 mm: the object's distance
+            d = _pose_dist(pose(got), pose(e64), scale) + _pose_dist(pose(got), pose(e32), scale) + _pose_dist(pose(e32), pose(e64), scale)
+            worst = [max(a, b) for a, b in zip(worst, d)]
         det.close()
-        e32 = oracle.recognition(sc["bgr"], sc["depth"], sc["K"], [5, 8], sc["bank"], 75.0, 20, 0.0, -3.0e38, accum64=False)
-        e64 = oracle.recognition(sc["bgr"], sc["depth"], sc["K"], [5, 8], sc["bank"], 75.0, 20, 0.0, -3.0e38, accum64=True)
-        assert got["found"] == e32["found"] == e64["found"] == 1
-        assert got["best"]["template_id"] == e32["best"]["template_id"]
-
-        def pose(r):
-            return dict(R=r["pose"][:3, :3], T=r["pose"][:3, 3])
-        scale = float(np.abs(e32["pose"][:3, 3]).max())           # ~ 650 mm: the object's distance
-        d = _pose_dist(pose(got), pose(e64), scale) + _pose_dist(pose(got), pose(e32), scale) + _pose_dist(pose(e32), pose(e64), scale)
-        worst = [max(a, b) for a, b in zip(worst, d)]
     print("FL_ICP_FAST Recognition: |FAST-f64| R %.3g T(rel) %.3g; |FAST-f32| R %.3g T(rel) %.3g; |f32-f64| R %.3g T(rel) %.3g" % tuple(worst))
     assert worst[0] <= POSE_TOL and worst[1] <= POSE_TOL
     # On these 15 k-point clouds the reference's own float32 summation noise |f32 - f64| is 1.1e-4 (R) / 1.1e-4 (T relative),
@@ -346,28 +391,32 @@ PLANE_CASES = [((0.05, 0.03, -0.04), (6, -4, 5)), ((0.03, -0.05, 0.02), (-5, 3, 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_point_to_plane_detection_vs_model_and_ground_truth(ctx, seed):
+    """On each of MODE_WIDTHS."""
     import p2plane_model as P
     c = _plane_case(seed, *PLANE_CASES[seed])
     K = (608.0, 608.0, 320.0, 240.0)
     args = (c["model"], c["scene"], K, c["rect_model"], c["rect_ref"], 20, 0.0, -3.0e38, c["Rm"], c["tm"])
-    got = ctx.detection(*args, L.FL_ICP_POINT_TO_PLANE)
     exp = P.detection_point_to_plane(*args)
-    assert got["n_points"] == exp["n_points"] > 5000
-    assert got["icp"]["iters"] == exp["icp"]["iters"] == 20
-    # the kernel against the independent model: same pairs, same sums up to fp rounding
-    assert abs(got["icp"]["n_corr_last"] - exp["icp"]["n_corr_last"]) <= 5
-    assert _angle_deg(got["R_final"], exp["R_final"]) <= 0.02
-    assert np.abs(got["T_final"] - exp["T_final"]).max() <= 0.05
-    assert abs(got["icp"]["dist_mean"] - exp["icp"]["dist_mean"]) <= 1e-2
-    # both against the truth, and against the reference's point-to-point ICP on the same input
-    p2p = ctx.detection(*args, L.FL_ICP_PARITY)
-    e_plane, e_p2p = _angle_deg(got["R_final"], c["Rs"]), _angle_deg(p2p["R_final"], c["Rs"])
-    assert e_plane <= 1.0 and e_plane <= 0.5 * e_p2p, (e_plane, e_p2p)
-    assert np.linalg.norm(got["T_final"] - c["ts"]) <= 0.5
-    assert np.linalg.norm(got["T_final"] - c["ts"]) <= np.linalg.norm(p2p["T_final"] - c["ts"])
+    for w in MODE_WIDTHS:
+        with _mode_width(ctx, w):
+            got = ctx.detection(*args, L.FL_ICP_POINT_TO_PLANE)
+            p2p = ctx.detection(*args, L.FL_ICP_PARITY)
+        assert got["n_points"] == exp["n_points"] > 5000, w
+        assert got["icp"]["iters"] == exp["icp"]["iters"] == 20, w
+        # the kernel against the independent model: same pairs, same sums up to fp rounding
+        assert abs(got["icp"]["n_corr_last"] - exp["icp"]["n_corr_last"]) <= 5, w
+        assert _angle_deg(got["R_final"], exp["R_final"]) <= 0.02, w
+        assert np.abs(got["T_final"] - exp["T_final"]).max() <= 0.05, w
+        assert abs(got["icp"]["dist_mean"] - exp["icp"]["dist_mean"]) <= 1e-2, w
+        # both against the truth, and against the reference's point-to-point ICP on the same input
+        e_plane, e_p2p = _angle_deg(got["R_final"], c["Rs"]), _angle_deg(p2p["R_final"], c["Rs"])
+        assert e_plane <= 1.0 and e_plane <= 0.5 * e_p2p, (w, e_plane, e_p2p)
+        assert np.linalg.norm(got["T_final"] - c["ts"]) <= 0.5, w
+        assert np.linalg.norm(got["T_final"] - c["ts"]) <= np.linalg.norm(p2p["T_final"] - c["ts"]), w
 
 
 def test_point_to_plane_on_clouds_and_argument_checks(ctx):
+    """On each of MODE_WIDTHS."""
     import p2plane_model as P
     c = _plane_case(1, *PLANE_CASES[1])
     K = (608.0, 608.0, 320.0, 240.0)
@@ -375,42 +424,299 @@ def test_point_to_plane_on_clouds_and_argument_checks(ctx):
     nrm = P.scene_normals(c["scene"], K, sx, sy)
     assert (np.abs(np.linalg.norm(nrm, axis=1) - 1) < 1e-5).mean() > 0.8       # most points have a normal
     mod = (mod + (ref.mean(0) - mod.mean(0))).astype(np.float32)
-    got = ctx.icp_point_to_plane(ref, nrm, mod, 15, 0.0, -3.0e38)
-    exp = P.icp_point_to_plane(ref, nrm, mod, 15, 0.0, -3.0e38)
-    assert got["iters"] == exp["iters"] == 15
-    assert _angle_deg(got["R"], exp["R"]) <= 0.02 and np.abs(got["T"] - exp["T"]).max() <= 0.2
-    # default thresholds stop early, exactly like icpCloudToCloud_Ex's loop control
-    got = ctx.icp_point_to_plane(ref, nrm, mod, 50, 0.5, 0.01)
-    exp = P.icp_point_to_plane(ref, nrm, mod, 50, 0.5, 0.01)
-    assert got["iters"] == exp["iters"] < 50
-    # all-zero normals constrain nothing: every iteration is skipped (counted), the pose stays the identity
-    r = ctx.icp_point_to_plane(ref, np.zeros_like(nrm), mod, 4, 0.0, -3.0e38)
-    assert r["iters"] == 4 and np.array_equal(r["R"], np.eye(3, dtype=np.float32)) and not r["T"].any()
-    # fl_icp has no normals to offer
-    with pytest.raises(api.FealessError) as e:
-        ctx.icp_cloud_to_cloud_ex(ref, mod, 4, 0.0, 0.0, L.FL_ICP_POINT_TO_PLANE)
-    assert e.value.code == L.FL_ERR_INVALID
-    with pytest.raises(api.FealessError):
-        ctx.icp_cloud_to_cloud_ex(ref, mod, 4, 0.0, 0.0, 7)
-    r = ctx.icp_point_to_plane(ref[:2], nrm[:2], mod[:2], 4)
-    assert r["dist_mean"] == -1.0 and r["iters"] == 0
+    exp15 = P.icp_point_to_plane(ref, nrm, mod, 15, 0.0, -3.0e38)
+    exp50 = P.icp_point_to_plane(ref, nrm, mod, 50, 0.5, 0.01)
+    for w in MODE_WIDTHS:
+        with _mode_width(ctx, w):
+            got = ctx.icp_point_to_plane(ref, nrm, mod, 15, 0.0, -3.0e38)
+            assert got["iters"] == exp15["iters"] == 15, w
+            assert _angle_deg(got["R"], exp15["R"]) <= 0.02 and np.abs(got["T"] - exp15["T"]).max() <= 0.2, w
+            # default thresholds stop early, exactly like icpCloudToCloud_Ex's loop control
+            got = ctx.icp_point_to_plane(ref, nrm, mod, 50, 0.5, 0.01)
+            assert got["iters"] == exp50["iters"] < 50, w
+            # all-zero normals constrain nothing: every iteration is skipped (counted), the pose stays the identity
+            r = ctx.icp_point_to_plane(ref, np.zeros_like(nrm), mod, 4, 0.0, -3.0e38)
+            assert r["iters"] == 4 and np.array_equal(r["R"], np.eye(3, dtype=np.float32)) and not r["T"].any(), w
+            # fl_icp has no normals to offer
+            with pytest.raises(api.FealessError) as e:
+                ctx.icp_cloud_to_cloud_ex(ref, mod, 4, 0.0, 0.0, L.FL_ICP_POINT_TO_PLANE)
+            assert e.value.code == L.FL_ERR_INVALID
+            with pytest.raises(api.FealessError):
+                ctx.icp_cloud_to_cloud_ex(ref, mod, 4, 0.0, 0.0, 7)
+            r = ctx.icp_point_to_plane(ref[:2], nrm[:2], mod[:2], 4)
+            assert r["dist_mean"] == -1.0 and r["iters"] == 0, w
 
 
 def test_point_to_plane_recognition_improves_the_pose(ctx, oracle):
+    """On each of MODE_WIDTHS."""
     sc = synth.recognition_scene(lambda b, d, l: oracle.quantize_pyramid(b, d, l), levels=2, seed=3, n_views=5, n_random=10)
     det = api.Detector(ctx, 2, [5, 8])
     det.add_class(sc["bank"])
     det.finalize(640, 480, max_batch=2)
     frames_b, frames_d = [sc["bgr"], sc["bgr"]], [sc["depth"], sc["depth"]]
-    p2p = det.recognize_batch(frames_b, frames_d, sc["K"], 75.0, 20, 0.0, -3.0e38, L.FL_ICP_PARITY)
-    pl = det.recognize_batch(frames_b, frames_d, sc["K"], 75.0, 20, 0.0, -3.0e38, L.FL_ICP_POINT_TO_PLANE)
-    for a, b in zip(p2p, pl):
-        assert a["found"] == b["found"] == 1 and a["best"] == b["best"]        # the LINEMOD half is untouched
-        ea, eb = _angle_deg(a["pose"][:3, :3], sc["R_true"]), _angle_deg(b["pose"][:3, :3], sc["R_true"])
-        assert eb <= max(1.0, 0.75 * ea), (ea, eb)
-        assert np.linalg.norm(b["pose"][:3, 3] - sc["t_true"]) <= max(1.0, np.linalg.norm(a["pose"][:3, 3] - sc["t_true"]))
-    assert np.array_equal(pl[0]["pose"], pl[1]["pose"])
+    for w in MODE_WIDTHS:
+        with _mode_width(ctx, w):
+            p2p = det.recognize_batch(frames_b, frames_d, sc["K"], 75.0, 20, 0.0, -3.0e38, L.FL_ICP_PARITY)
+            pl = det.recognize_batch(frames_b, frames_d, sc["K"], 75.0, 20, 0.0, -3.0e38, L.FL_ICP_POINT_TO_PLANE)
+        for a, b in zip(p2p, pl):
+            assert a["found"] == b["found"] == 1 and a["best"] == b["best"], w      # the LINEMOD half is untouched
+            ea, eb = _angle_deg(a["pose"][:3, :3], sc["R_true"]), _angle_deg(b["pose"][:3, :3], sc["R_true"])
+            assert eb <= max(1.0, 0.75 * ea), (w, ea, eb)
+            assert np.linalg.norm(b["pose"][:3, 3] - sc["t_true"]) <= max(1.0, np.linalg.norm(a["pose"][:3, 3] - sc["t_true"])), w
+        assert np.array_equal(pl[0]["pose"], pl[1]["pose"]), w
     det.close()
+
+
+def test_scene_normals_vs_fp64_restatement(ctx):
+    """scene_normal (the device function behind FL_ICP_POINT_TO_PLANE's normals, run through fl_dev_scene_normals) against
+    its fp64 restatement (tests/p2plane_model.scene_normals_fp64): the border and depth-step rules are definitions, so the
+    pixels that get a zero normal must be exactly the restatement's; every other component must lie within the per-pixel
+    float32 error bound derived from |Pu|, |Pv| and |Pu x Pv|.  Cases: p2plane_model.normal_cases."""
+    import p2plane_model as P
+    n_zero = n_set = 0
+    for depth, K, xs, ys, label in P.normal_cases():
+        got = ctx.dev_scene_normals(depth, K, xs, ys)
+        n64, zero, bound = P.scene_normals_fp64(depth, K, xs, ys)
+        assert np.array_equal(~got.any(1), zero), (label, np.nonzero(~got.any(1) != zero)[0])
+        err = np.abs(got.astype(np.float64) - n64).max(1)
+        bad = np.nonzero(~zero & (err > bound))[0]
+        assert len(bad) == 0, (label, [(int(xs[i]), int(ys[i]), err[i], bound[i]) for i in bad[:5]])
+        n_zero += int(zero.sum())
+        n_set += int((~zero).sum())
+    assert n_zero >= 100 and n_set >= 250, (n_zero, n_set)
+    with pytest.raises(api.FealessError):                  # a pixel outside the image is refused, not read
+        ctx.dev_scene_normals(np.zeros((8, 8), np.uint16), (500.0, 500.0, 4.0, 4.0), [8], [0])
+
+
+def _one_iteration_bar(fl, got, label):
+    """The kernel's (R, T) after one point-to-plane iteration against the fp64 solution: within 4 x the float32 summation
+    noise floor (p2plane_model.one_iteration_noise_floor) plus two float32 ulps of the entries (both results are rounded
+    from fp64 to float32)."""
+    ulp_R = 2.0 ** -23
+    ulp_T = float(np.spacing(np.float32(np.abs(fl["T"]).max())))
+    dR = float(np.abs(got["R"].astype(np.float64) - fl["R"]).max())
+    dT = float(np.abs(got["T"].astype(np.float64) - fl["T"]).max())
+    assert dR <= 4 * fl["floor_R"] + 2 * ulp_R, (label, dR, fl["floor_R"])
+    assert dT <= 4 * fl["floor_T"] + 2 * ulp_T, (label, dT, fl["floor_T"])
+    return dR, dT
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_point_to_plane_one_iteration_within_the_summation_noise_floor(ctx, seed, mode_width):
+    """icp_it_thr = 1 on clouds (fl_icp_point_to_plane) and through detection(): the pairs are fixed by the first search, so
+    n_corr_last must equal the model's, and (R, T) must lie within a small multiple of the float32 summation noise floor of
+    the 27 sums (p2plane_model.one_iteration_noise_floor, partitioned over as many partials as the build has threads).
+    These seeds have no near-tie: every pair's squared distance is at least 1e-5 (relative) from the gate and every nearest
+    neighbour at least 1e-6 closer than the second nearest, so float rounding cannot change a pair."""
+    import p2plane_model as P
+    c = _plane_case(seed, *PLANE_CASES[seed])
+    K = (608.0, 608.0, 320.0, 240.0)
+    ref, mod0, sx, sy = P.crop_pairs(c["model"], c["scene"], K, c["rect_model"], c["rect_ref"])
+    # on clouds: the caller's normals (the model's), the model cloud centred on the reference
+    nrm = P.scene_normals(c["scene"], K, sx, sy)
+    mod = (mod0 + (ref.mean(0) - mod0.mean(0))).astype(np.float32)
+    fl = P.one_iteration_noise_floor(ref, nrm, mod, mode_width, seed=seed)
+    assert fl["gate_gap"] > 1e-5 and fl["tie_gap"] > 1e-6, fl
+    got = ctx.icp_point_to_plane(ref, nrm, mod, 1, 0.0, -3.0e38)
+    assert got["iters"] == 1 and got["n_corr_last"] == fl["n_corr"] > 5000
+    _one_iteration_bar(fl, got, "clouds")
+    # detection(): the kernel's back-projection, its own normals (checked against fp64 by
+    # test_scene_normals_vs_fp64_restatement) and its pre-alignment, t = float32(mean(ref)) - float32(mean(mod)) of fp64
+    # means (detection.cpp:177,206)
+    ref, mod0, sx, sy = P.crop_clouds_f32(c["model"], c["scene"], K, c["rect_model"], c["rect_ref"])
+    nrm_k = ctx.dev_scene_normals(c["scene"], K, sx, sy)
+    t_tmp = (ref.astype(np.float64).mean(0).astype(np.float32) - mod0.astype(np.float64).mean(0).astype(np.float32)).astype(np.float32)
+    mod_d = (mod0 + t_tmp).astype(np.float32)
+    fl = P.one_iteration_noise_floor(ref, nrm_k, mod_d, mode_width, seed=seed)
+    assert fl["gate_gap"] > 1e-5 and fl["tie_gap"] > 1e-6, fl
+    got = ctx.detection(c["model"], c["scene"], K, c["rect_model"], c["rect_ref"], 1, 0.0, -3.0e38, c["Rm"], c["tm"],
+                        L.FL_ICP_POINT_TO_PLANE)
+    assert got["n_points"] == len(ref)
+    assert got["icp"]["iters"] == 1 and got["icp"]["n_corr_last"] == fl["n_corr"]
+    dR, dT = _one_iteration_bar(fl, got["icp"], "detection")
+    print("one iteration, %d threads, seed %d: |R - fp64| %.3g (floor %.3g), |T - fp64| %.3g mm (floor %.3g)" %
+          (mode_width, seed, dR, fl["floor_R"], dT, fl["floor_T"]))
+
+
+def _at_border(c, corner, inset=12):
+    """_plane_case with both crops shrunk by `inset` pixels a side (so that they cut through the object) and the scene rolled
+    so that the reference crop touches the image border: the top-left corner (the crop starts at pixel 0 of both axes) or
+    the bottom-right one (it ends at the last pixel).  scene_normal's border rule then zeroes the normals of the kept pairs
+    in the outer three rows and columns."""
+    x0, y0, cw, ch = c["rect_ref"]
+    mx, my = c["rect_model"][:2]
+    x0, y0, mx, my, cw, ch = x0 + inset, y0 + inset, mx + inset, my + inset, cw - 2 * inset, ch - 2 * inset
+    h, w = c["scene"].shape
+    sx, sy = (-x0, -y0) if corner == "top_left" else (w - (x0 + cw), h - (y0 + ch))
+    scene = np.roll(np.roll(c["scene"], sy, axis=0), sx, axis=1)
+    return scene, (mx, my, cw, ch), (x0 + sx, y0 + sy, cw, ch)
+
+
+@pytest.mark.parametrize("corner", ["top_left", "bottom_right"])
+def test_fast_and_point_to_plane_detection_with_the_crop_at_the_border(ctx, oracle, corner, mode_width):
+    """detection() whose reference crop touches the image border: FL_ICP_PARITY equals the float32 oracle bit for bit,
+    FL_ICP_FAST is held to the oracle's fp64 yardstick and FL_ICP_POINT_TO_PLANE to tests/p2plane_model.py, with the bars of
+    test_detection_matches_oracle and test_point_to_plane_detection_vs_model_and_ground_truth.  These crops cut through
+    the object, and 20 iterations of them are sensitive to a pair that crosses the gate: the oracle's own float32 result
+    lies up to 0.03 mm from its fp64 one.  FAST's translation bar is 1e-3 mm or that distance, whichever is larger."""
+    import p2plane_model as P
+    c = _plane_case(1, *PLANE_CASES[1])
+    scene, rect_model, rect_ref = _at_border(c, corner)
+    h, w = scene.shape
+    assert rect_ref[:2] == (0, 0) if corner == "top_left" else (rect_ref[0] + rect_ref[2], rect_ref[1] + rect_ref[3]) == (w, h)
+    K = (608.0, 608.0, 320.0, 240.0)
+    args = (c["model"], scene, K, rect_model, rect_ref, 20, 0.0, -3.0e38, c["Rm"], c["tm"])
+    got = ctx.detection(*args, L.FL_ICP_PARITY)
+    e32 = oracle.detection(*args, accum64=False)
+    assert got["n_points"] == e32["n_points"] > 5000 and got["icp"]["n_corr_last"] == e32["icp"]["n_corr_last"]
+    assert np.array_equal(_bits(got["R_final"]), _bits(e32["R_final"])) and np.array_equal(_bits(got["T_final"]), _bits(e32["T_final"]))
+    got = ctx.detection(*args, L.FL_ICP_FAST)
+    exp = oracle.detection(*args, accum64=True)
+    assert got["n_points"] == exp["n_points"] > 5000
+    assert got["icp"]["iters"] == exp["icp"]["iters"] == 20
+    assert np.abs(got["R_final"] - exp["R_final"]).max() <= POSE_TOL
+    assert np.abs(got["T_final"] - exp["T_final"]).max() <= max(1e-3, float(np.abs(e32["T_final"] - exp["T_final"]).max()))
+    got = ctx.detection(*args, L.FL_ICP_POINT_TO_PLANE)
+    exp = P.detection_point_to_plane(*args)
+    n = exp["normals"]
+    _, _, sx, sy = P.crop_pairs(c["model"], scene, K, rect_model, rect_ref)
+    rim = (sx < 3) | (sy < 3) | (sx >= w - 3) | (sy >= h - 3)
+    assert rim.sum() > 100 and not n[rim].any()            # the crop reaches the rows and columns the border rule zeroes
+    assert got["n_points"] == exp["n_points"]
+    assert got["icp"]["iters"] == exp["icp"]["iters"] == 20
+    assert abs(got["icp"]["n_corr_last"] - exp["icp"]["n_corr_last"]) <= 5
+    assert _angle_deg(got["R_final"], exp["R_final"]) <= 0.02
+    assert np.abs(got["T_final"] - exp["T_final"]).max() <= 0.05
+    assert abs(got["icp"]["dist_mean"] - exp["icp"]["dist_mean"]) <= 1e-2
+
+
+def _match_of(best):
+    m = np.zeros(1, api.MATCH_DTYPE)
+    for k in ("x", "y", "similarity", "class_idx", "template_id"):
+        m[k] = best[k]
+    return m
+
+
+def test_fast_and_point_to_plane_batch_topk(ctx, oracle, mode_width):
+    """fl_recognize_batch_topk in FL_ICP_FAST and FL_ICP_POINT_TO_PLANE: every FAST hypothesis against the oracle's fp64
+    yardstick of the same hypothesis (oracle recognition_topk, accum64) with the bars of
+    test_icp_fast_mode_recognition_vs_the_f32_oracle; every point-to-plane hypothesis equals the same match refined alone
+    (fl_refine_matches, one job on the same build), bit for bit."""
+    sc = synth.recognition_scene(lambda b, d, l: oracle.quantize_pyramid(b, d, l), levels=2, seed=21, n_views=6)
+    frames_b = [sc["bgr"], np.roll(sc["bgr"], 40, axis=1)]
+    frames_d = [sc["depth"], np.roll(sc["depth"], 40, axis=1)]
+    det = api.Detector(ctx, 2, [5, 8])
+    det.add_class(sc["bank"])
+    det.finalize(640, 480, max_batch=2)
+    k, p = 4, (60.0, 8, 0.0, -3.0e38)
+    got = det.recognize_batch_topk(frames_b, frames_d, sc["K"], k, *p, mode=L.FL_ICP_FAST)
+    worst = [0.0, 0.0]
+    for f in range(2):
+        exp = oracle.recognition_topk(frames_b[f], frames_d[f], sc["K"], [5, 8], sc["bank"], k, *p, accum64=True)
+        assert len(got[f]) == len(exp) >= 2
+        for g, e in zip(got[f], exp):
+            assert g["found"] == e["found"] and g["best"]["template_id"] == e["best"]["template_id"]
+            assert (g["best"]["x"], g["best"]["y"]) == (e["best"]["x"], e["best"]["y"])
+            if not e["found"]:
+                continue
+            assert g["det"]["n_points"] == e["det"]["n_points"] and g["det"]["icp"]["iters"] == e["det"]["icp"]["iters"]
+            scale = float(np.abs(e["pose"][:3, 3]).max())
+            d = _pose_dist(dict(R=g["pose"][:3, :3], T=g["pose"][:3, 3]), dict(R=e["pose"][:3, :3], T=e["pose"][:3, 3]), scale)
+            worst = [max(a, b) for a, b in zip(worst, d)]
+    print("FL_ICP_FAST batch top-k, %d threads: |FAST-f64| R %.3g T(rel) %.3g" % (mode_width, *worst))
+    assert worst[0] <= POSE_TOL and worst[1] <= POSE_TOL
+    got = det.recognize_batch_topk(frames_b, frames_d, sc["K"], k, *p, mode=L.FL_ICP_POINT_TO_PLANE)
+    params = L.RecognitionParams(*p, L.FL_ICP_POINT_TO_PLANE)
+    n_found = 0
+    for f in range(2):
+        assert len(got[f]) >= 2
+        for g in got[f]:
+            one = api.recognition_result_to_dict(det.refine_matches([f], _match_of(g["best"]), sc["K"], params)[0])
+            assert one["found"] == g["found"] and one["best"] == g["best"]
+            assert one["det"]["n_points"] == g["det"]["n_points"] and one["det"]["icp"]["iters"] == g["det"]["icp"]["iters"]
+            assert one["det"]["icp"]["n_corr_last"] == g["det"]["icp"]["n_corr_last"]
+            assert np.array_equal(_bits(one["pose"]), _bits(g["pose"]))
+            assert _bits(one["det"]["icp"]["dist_mean"]) == _bits(g["det"]["icp"]["dist_mean"])
+            n_found += g["found"]
+    assert n_found >= 4
+    det.close()
+
+
+def _assert_same_bits(g, e, tag):
+    assert g["status"] == e["status"] == 0 and g["found"] == e["found"] and g["n_matches"] == e["n_matches"], tag
+    assert g["best"] == e["best"], tag
+    if e["found"]:
+        gi, ei = g["det"]["icp"], e["det"]["icp"]
+        assert g["det"]["n_points"] == e["det"]["n_points"] and gi["iters"] == ei["iters"], tag
+        assert gi["n_corr_last"] == ei["n_corr_last"], tag
+        assert np.array_equal(_bits(g["pose"]), _bits(e["pose"])), tag
+        assert _bits(gi["dist_mean"]) == _bits(ei["dist_mean"]), tag
+
+
+@pytest.mark.parametrize("mode", [L.FL_ICP_FAST, L.FL_ICP_POINT_TO_PLANE], ids=["fast", "plane"])
+def test_fast_and_point_to_plane_batches_do_not_depend_on_runtime_options(oracle, mode):
+    """A job's arithmetic depends only on its data and the workgroup width.  On the 256-thread build, every frame of a batch
+    of 1100 passed by device pointer (more than two jobs per CU: the default width is 256; more than four: the jobs are dealt
+    longest first, or in frame order with icp_order 0) and of a small batch under icp_wg_per_cu 1, 2, 3 equals the same frame
+    of a small batch, bit for bit.  Across the widths the results differ within the mode's tolerance only: FL_ICP_FAST the
+    north_star's 1e-4 (R absolute, T relative), FL_ICP_POINT_TO_PLANE the bars of its test against the model."""
+    import torch
+    c = api.Context(0)                      # a context of its own: an option left set cannot leak into other tests
+    try:
+        scenes = [synth.recognition_scene(lambda b, d, l: oracle.quantize_pyramid(b, d, l), levels=2, seed=s, n_views=3) for s in (3, 5)]
+        sc = scenes[0]
+        frames_b, frames_d = [], []
+        for k in range(6):                                   # two scenes x three shifts: different crops, different cloud sizes
+            s2 = scenes[k % 2]
+            frames_b.append(np.roll(s2["bgr"], 14 * (k // 2), axis=1))
+            frames_d.append(np.roll(s2["depth"], 14 * (k // 2), axis=1))
+        n = 1100
+        det = api.Detector(c, 2, [5, 8])
+        det.add_class(sc["bank"])
+        det.finalize(640, 480, max_batch=n, max_candidates=4096)
+        p = (75.0, 8, 0.0, -3.0e38)
+        runs = {}
+        for wide in (0, 1):
+            with util.options(c, {"icp_wide": wide}):
+                runs[wide] = det.recognize_batch(frames_b, frames_d, sc["K"], *p, mode=mode)
+        small, wide1024 = runs[0], runs[1]
+        assert sum(r["found"] for r in small) >= 3 and len({r["det"]["n_points"] for r in small if r["found"]}) >= 2
+        for cap in (1, 2, 3):
+            with util.options(c, {"icp_wide": 0, "icp_wg_per_cu": cap}):
+                got = det.recognize_batch(frames_b, frames_d, sc["K"], *p, mode=mode)
+            for i in range(6):
+                _assert_same_bits(got[i], small[i], ("icp_wg_per_cu", cap, i))
+        d_b = torch.from_numpy(np.stack(frames_b)).cuda()
+        d_d = torch.from_numpy(np.stack(frames_d).view(np.int16)).cuda()
+        torch.cuda.synchronize()
+        order = [(7 * i) % 6 for i in range(n)]
+        bp = [d_b.data_ptr() + o * 640 * 480 * 3 for o in order]
+        dp = [d_d.data_ptr() + o * 640 * 480 * 2 for o in order]
+        params = L.RecognitionParams(*p, mode)
+        for icp_order in (1, 0):
+            with util.options(c, {"icp_order": icp_order}):
+                det.recognize_submit_device(bp, dp, sc["K"], params)
+                res = [api.recognition_result_to_dict(r) for r in det.recognize_collect(n)]
+            for i in range(n):
+                _assert_same_bits(res[i], small[order[i]], ("batch", icp_order, i))
+        for i in range(6):
+            a, b = small[i], wide1024[i]
+            assert a["found"] == b["found"] and a["best"] == b["best"]
+            if not a["found"]:
+                continue
+            assert a["det"]["n_points"] == b["det"]["n_points"] and a["det"]["icp"]["iters"] == b["det"]["icp"]["iters"]
+            if mode == L.FL_ICP_FAST:
+                dr, dt = _pose_dist(dict(R=a["pose"][:3, :3], T=a["pose"][:3, 3]), dict(R=b["pose"][:3, :3], T=b["pose"][:3, 3]),
+                                    float(np.abs(a["pose"][:3, 3]).max()))
+                assert dr <= POSE_TOL and dt <= POSE_TOL, (i, dr, dt)
+            else:
+                assert abs(a["det"]["icp"]["n_corr_last"] - b["det"]["icp"]["n_corr_last"]) <= 5
+                assert _angle_deg(a["pose"][:3, :3], b["pose"][:3, :3]) <= 0.02
+                assert np.abs(a["pose"][:3, 3] - b["pose"][:3, 3]).max() <= 0.05
+                assert abs(a["det"]["icp"]["dist_mean"] - b["det"]["icp"]["dist_mean"]) <= 1e-2
+        det.close()
+    finally:
+        c.close()
 
 
 # ---- lazy fine levels: fl_recognize_* quantise / spread the finer levels only in the tiles the candidates touch ----

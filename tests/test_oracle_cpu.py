@@ -462,3 +462,55 @@ def test_point_to_plane_model_recovers_ground_truth():
     n = out["normals"]
     has = np.linalg.norm(n, axis=1) > 0
     assert has.mean() > 0.8 and np.abs(np.linalg.norm(n[has], axis=1) - 1).max() < 1e-5
+
+
+def _scene_normal_f32(depth, K, x, y):
+    """scene_normal (fl_icp.hip) step by step in float32 (numpy float32 operations round like the kernel's, built without
+    contraction): what the fp64 yardstick's error bound has to cover."""
+    f = np.float32
+    fx, fy, cx, cy = (f(v) for v in K)
+    h, w = depth.shape
+    r = 3
+    if x < r or y < r or x + r >= w or y + r >= h:
+        return np.zeros(3, np.float32)
+    zc = f(depth[y, x])
+    gate = f(f(0.02) * zc) + f(2.0)
+    su = sv = f(0.0)
+    ok = zc > 0
+    for dv in range(-r, r + 1):
+        for du in range(-r, r + 1):
+            z = f(depth[y + dv, x + du])
+            ok = ok and z > 0 and abs(z - zc) <= gate
+            su = f(su + f(du) * z)
+            sv = f(sv + f(dv) * z)
+    if not ok:
+        return np.zeros(3, np.float32)
+    s2 = f(196.0)
+    zu, zv, X, Y = su / s2, sv / s2, (f(x) - cx) / fx, (f(y) - cy) / fy
+    pu = [zc / fx + X * zu, Y * zu, zu]
+    pv = [X * zv, zc / fy + Y * zv, zv]
+    c = [pu[1] * pv[2] - pu[2] * pv[1], pu[2] * pv[0] - pu[0] * pv[2], pu[0] * pv[1] - pu[1] * pv[0]]
+    ln = np.sqrt(f(f(c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]))
+    if not ln > 0:
+        return np.zeros(3, np.float32)
+    return np.array([c[0] / ln, c[1] / ln, c[2] / ln], np.float32)
+
+
+def test_scene_normal_fp64_yardstick_and_its_bound():
+    """tests/p2plane_model.scene_normals_fp64 is the yardstick of the kernel's normals (test_gpu_icp.py): a float32 statement
+    of the kernel's formula must give a zero normal at exactly the pixels the yardstick marks, and stay within its derived
+    bound everywhere else; the existing model (scene_normals) agrees with it; the bound is a few dozen float32 ulps."""
+    import p2plane_model as P
+    n_zero = n_set = 0
+    for depth, K, xs, ys, label in P.normal_cases():
+        n64, zero, bound = P.scene_normals_fp64(depth, K, xs, ys)
+        n32 = np.array([_scene_normal_f32(depth, K, int(x), int(y)) for x, y in zip(xs, ys)])
+        assert np.array_equal(~n32.any(1), zero), label
+        err = np.abs(n32.astype(np.float64) - n64).max(1)
+        assert (err[~zero] <= bound[~zero]).all(), (label, (err / np.maximum(bound, 1e-30)).max())
+        assert (bound[~zero] < 200 * P.F32_EPS).all(), label
+        old = P.scene_normals(depth, K, xs, ys)
+        assert np.array_equal(~old.any(1), zero) and np.abs(old - n64).max() <= 2e-6, label
+        n_zero += int(zero.sum())
+        n_set += int((~zero).sum())
+    assert n_zero >= 100 and n_set >= 250, (n_zero, n_set)
