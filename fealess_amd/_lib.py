@@ -96,6 +96,7 @@ SIGNATURES = {
     "fl_quantized_normals": (_I, [_P, _P, _I, _I, _I, _I, _P, _I]),
     "fl_pyrdown_bgr": (_I, [_P, _P, _I, _I, _P, _I]),
     "fl_extract_template_pyramid": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, C.POINTER(_I)]),
+    "fl_extract_template_batch": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "fl_resize_linear_bgr8": (_I, [_P, _P, _I, _I, _P, _I, _I, _I]),
     "fl_resize_linear_u16": (_I, [_P, _P, _I, _I, _P, _I, _I, _I]),
     "fl_lm_label_stride": (C.c_size_t, [_I, _I, _I]),

@@ -30,6 +30,17 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _pyramid_dicts(t, f):
+    """One extracted pyramid (templates t, feat_begin into f) as the dicts TemplateBank.add_pyramid takes."""
+    out = []
+    for k in range(len(t)):
+        fb, fc = int(t[k]["feat_begin"]), int(t[k]["feat_count"])
+        feats = np.stack([f["x"][fb:fb + fc], f["y"][fb:fb + fc], f["label"][fb:fb + fc]], axis=1).astype(np.int32)
+        out.append(dict(width=int(t[k]["width"]), height=int(t[k]["height"]), offset_x=int(t[k]["offset_x"]),
+                        offset_y=int(t[k]["offset_y"]), pyramid_level=int(t[k]["pyramid_level"]), features=feats))
+    return out
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = L.load()
@@ -116,13 +127,37 @@ class Context:
         if rc == L.FL_ERR_NO_TEMPLATE:
             return None
         self.check(rc)
-        out = []
-        for k in range(levels * 2):
-            fb, fc = int(t[k]["feat_begin"]), int(t[k]["feat_count"])
-            feats = np.stack([f["x"][fb:fb + fc], f["y"][fb:fb + fc], f["label"][fb:fb + fc]], axis=1).astype(np.int32)
-            out.append(dict(width=int(t[k]["width"]), height=int(t[k]["height"]), offset_x=int(t[k]["offset_x"]),
-                            offset_y=int(t[k]["offset_y"]), pyramid_level=int(t[k]["pyramid_level"]), features=feats))
-        return out, tuple(bb)
+        return _pyramid_dicts(t, f), tuple(bb)
+
+    def extract_template_batch(self, bgrs, depths, masks, levels, mem=L.FL_MEM_HOST):
+        """fl_extract_template_batch: extract_template_pyramid for every view in one call.  masks: None, or one mask or
+        None per view.  mem=FL_MEM_HOST: numpy arrays; FL_MEM_DEVICE: device tensors (torch, anything with data_ptr()
+        and shape).  Returns one entry per view: (templates, bb), or None where the reference returns -1."""
+        from .bank import FEATURE_DTYPE, TEMPLATE_DTYPE
+        n = len(bgrs)
+        masks = [None] * n if masks is None else list(masks)
+        if mem == L.FL_MEM_HOST:
+            bgrs = [np.ascontiguousarray(b, np.uint8) for b in bgrs]
+            depths = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            masks = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in masks]
+
+            def addr(a):
+                return a.ctypes.data
+        else:
+            def addr(a):
+                return a.data_ptr()
+        h, w = depths[0].shape[:2]
+        bp = (C.c_void_p * n)(*[addr(b) for b in bgrs])
+        dp = (C.c_void_p * n)(*[addr(d) for d in depths])
+        mp = None if all(m is None for m in masks) else (C.c_void_p * n)(*[None if m is None else addr(m) for m in masks])
+        J = levels * 2
+        t = np.zeros(n * J, TEMPLATE_DTYPE)
+        f = np.zeros(n * J * 63, FEATURE_DTYPE)
+        bb = np.zeros(4 * n, np.int32)
+        st = np.zeros(n, np.int32)
+        self.check(self.lib.fl_extract_template_batch(self.h, n, bp, dp, mp, w, h, levels, mem, _ptr(t), _ptr(f), _ptr(bb), _ptr(st)))
+        return [None if st[v] != L.FL_OK else (_pyramid_dicts(t[v * J:(v + 1) * J], f), tuple(int(x) for x in bb[4 * v:4 * v + 4]))
+                for v in range(n)]
 
     def build_linear_memories(self, quantized, T):
         q = np.ascontiguousarray(quantized, np.uint8)

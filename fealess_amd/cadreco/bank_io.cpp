@@ -429,4 +429,44 @@ bool ReadPng16(const std::string &filename, std::vector<unsigned short> &pixels,
   return true;
 }
 
+// The mirror of ReadPng16: 16-bit greyscale, non-interlaced, one zlib IDAT, filter type 0 on every row, samples big-endian
+bool WritePng16(const std::string &filename, const unsigned short *px, int w, int h, std::string *err)
+{
+  auto fail = [&](const char *m) { if (err) *err = std::string(m) + ": " + filename; return false; };
+  if (!px || w <= 0 || h <= 0 || (long long)w * h > (64ll << 20)) return fail("bad image");
+  const size_t stride = (size_t)w * 2;
+  std::vector<unsigned char> raw((stride + 1) * (size_t)h);
+  for (int y = 0; y < h; ++y) {
+    unsigned char *r = &raw[(stride + 1) * (size_t)y];
+    r[0] = 0;
+    for (int x = 0; x < w; ++x) {
+      const unsigned short v = px[(size_t)y * w + x];
+      r[1 + 2 * x] = (unsigned char)(v >> 8);
+      r[2 + 2 * x] = (unsigned char)(v & 0xFF);
+    }
+  }
+  uLongf zlen = compressBound((uLong)raw.size());
+  std::vector<unsigned char> z(zlen);
+  if (compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) != Z_OK) return fail("deflate failed");
+  std::vector<unsigned char> out = {137, 80, 78, 71, 13, 10, 26, 10};
+  auto put32 = [&](unsigned v) { for (int s = 24; s >= 0; s -= 8) out.push_back((unsigned char)(v >> s)); };
+  auto chunk = [&](const char *type, const unsigned char *d, size_t len) {
+    put32((unsigned)len);
+    const size_t at = out.size();
+    out.insert(out.end(), type, type + 4);
+    if (len) out.insert(out.end(), d, d + len);
+    put32((unsigned)crc32(0L, &out[at], (uInt)(4 + len)));
+  };
+  const unsigned char ihdr[13] = {(unsigned char)(w >> 24), (unsigned char)(w >> 16), (unsigned char)(w >> 8), (unsigned char)w,
+                                  (unsigned char)(h >> 24), (unsigned char)(h >> 16), (unsigned char)(h >> 8), (unsigned char)h,
+                                  16, 0, 0, 0, 0};      // bit depth 16, colour type 0 (grey), deflate, filter 0, not interlaced
+  chunk("IHDR", ihdr, 13);
+  chunk("IDAT", z.data(), zlen);
+  chunk("IEND", nullptr, 0);
+  FILE *f = fopen(filename.c_str(), "wb");
+  if (!f) return fail("cannot open");
+  const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+  return (fclose(f) == 0 && ok) || fail("write failed");
+}
+
 }  // namespace fealess

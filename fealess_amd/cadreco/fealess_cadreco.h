@@ -128,6 +128,8 @@ bool ReadBankCache(const std::string &filename, DetectorFile &out, unsigned long
 bool ReadLinemodCached(const std::string &filename, DetectorFile &out, std::string *err, bool *from_cache);
 // imread(path, -1) for the 16-bit single-channel depth PNGs (obj_reco_lmicp.cpp:157)
 bool ReadPng16(const std::string &filename, std::vector<unsigned short> &pixels, int &w, int &h, std::string *err);
+// its mirror: 16-bit greyscale, non-interlaced, zlib (what imwrite gives a CV_16U image); false + err on failure
+bool WritePng16(const std::string &filename, const unsigned short *pixels, int w, int h, std::string *err);
 
 }  // namespace fealess
 
@@ -143,5 +145,20 @@ int CadRecoRecognitionBatch(CObjRecoCAD *handle, int n_frames, const TImageU *rg
 // frame and return the nonMaximumSuppression (ICP/NMS.cpp:6-40, th_obj_dist = nms_dist_mm) winners, best first, in
 // vtResult.  k = 1 restores the reference behaviour.
 int CadRecoSetMultiHypothesis(CObjRecoCAD *handle, int k, float nms_dist_mm);
+
+// Not in the reference, where Train() is a stub and a data directory comes from the test/linemod_train.cpp demo
+// (OpenCV, Detector::addTemplate per frame, writeLinemod): train one class on the handle's GPU, batched, and write the
+// directory AddObj() reads.  Views: bgr[v] (BGR8), depth_mm[v] (mm), all of one size; mask: NULL, or per view an
+// object mask whose pData may be NULL (no mask).  poses13: 13 floats per view; levels, T[levels]: the pyramid.
+// Writes <dir>/depth/<template_id>.png (the view's depth x 10 in 0.1 mm, saturating: Recognition's convertTo(CV_16U,
+// 0.1) gives back the view's millimetres) and then <dir>/linemod_templates.yml (ColorGradient + DepthNormal).
+// Template ids count the views that produced a template; template_of_view (optional) gets that id or -1 per view.
+// linemod_train names the PNGs by frame number while Recognition reads them by template id, so its directories are
+// only right when no view fails; here the PNGs follow the template ids.
+// Returns SUCCESS; ERROR_INVALID_PARAM (views of different sizes, a bad pointer or argument, no view yields a
+// template: nothing written); ERROR_OPEN_FILE_FAILED (a file cannot be written); ERROR_UNKNOW (no GPU, HIP error).
+int CadRecoTrainViews(CObjRecoCAD *handle, const string &dir, const string &class_id, int n_views, const TImageU *bgr,
+                      const TImageU16 *depth_mm, const TImageU *mask, const float *poses13, int levels, const int *T,
+                      std::vector<int> *template_of_view);
 
 #endif  // FEALESS_CADRECO_H

@@ -6,7 +6,10 @@
 #include "fealess_cadreco.h"
 #include "../../include/fealess_hip.h"
 
+#include <sys/stat.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <cstdio>
 #include <cstring>
 #include <sstream>
@@ -207,6 +210,8 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return first_rc;
   }
 
+  fl_context *Context() const { return m_ctx; }
+
   fl_recognition_params m_params;
   int m_topk = 1;            // > 1: multi-hypothesis mode (CadRecoSetMultiHypothesis)
   float m_nms_dist = 20.0f;  // th_obj_dist of nonMaximumSuppression, mm
@@ -256,8 +261,118 @@ int CadRecoSetMultiHypothesis(CObjRecoCAD *handle, int k, float nms_dist_mm)
   return 0;
 }
 
+int CadRecoTrainViews(CObjRecoCAD *handle, const string &dir, const string &class_id, int n_views, const TImageU *bgr,
+                      const TImageU16 *depth_mm, const TImageU *mask, const float *poses13, int levels, const int *T,
+                      std::vector<int> *template_of_view)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h || dir.empty() || n_views < 1 || !bgr || !depth_mm || !poses13 || !T || levels < 1 || levels > 4) return (int)ERROR_INVALID_PARAM;
+  for (int l = 0; l < levels; ++l)
+    if (T[l] < 1) return (int)ERROR_INVALID_PARAM;
+  const int w = bgr[0].nWidth, ht = bgr[0].nHeight;
+  std::vector<const uint8_t *> bp(n_views), mp(n_views, nullptr);
+  std::vector<const uint16_t *> dp(n_views);
+  bool any_mask = false;
+  for (int v = 0; v < n_views; ++v) {
+    if (!bgr[v].pData || !depth_mm[v].pData || bgr[v].nWidth != w || bgr[v].nHeight != ht || depth_mm[v].nWidth != w ||
+        depth_mm[v].nHeight != ht)
+      return (int)ERROR_INVALID_PARAM;
+    if (mask && mask[v].pData) {
+      if (mask[v].nWidth != w || mask[v].nHeight != ht) return (int)ERROR_INVALID_PARAM;
+      mp[v] = mask[v].pData;
+      any_mask = true;
+    }
+    bp[v] = bgr[v].pData;
+    dp[v] = depth_mm[v].pData;
+  }
+  if (!h->Context()) return (int)ERROR_UNKNOW;
+  // Detector::addTemplate for every view (linemod_train.cpp:30-91), all of them in one batched call
+  const int J = 2 * levels;
+  std::vector<fl_template> tl((size_t)n_views * J);
+  std::vector<fl_feature> fl((size_t)n_views * J * 63);
+  std::vector<int32_t> bb((size_t)n_views * 4), st(n_views);
+  const int rc = fl_extract_template_batch(h->Context(), n_views, bp.data(), dp.data(), any_mask ? mp.data() : nullptr, w, ht, levels,
+                                           FL_MEM_HOST, tl.data(), fl.data(), bb.data(), st.data());
+  if (rc == FL_ERR_INVALID) return (int)ERROR_INVALID_PARAM;
+  if (rc != FL_OK) {
+    fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(h->Context()));
+    return (int)ERROR_UNKNOW;
+  }
+  fealess::DetectorFile df;
+  df.pyramid_levels = levels;
+  df.T.assign(T, T + levels);
+  df.modalities = {"ColorGradient", "DepthNormal"};
+  df.classes.resize(1);
+  fealess::ObjectClass &c = df.classes[0];
+  c.class_id = class_id;
+  std::vector<int> tov(n_views, -1), view_of;
+  for (int v = 0; v < n_views; ++v) {
+    if (st[v] != FL_OK) continue;                                            // addTemplate returned -1: no template id
+    tov[v] = (int)c.template_pyramids.size();
+    view_of.push_back(v);
+    std::vector<fealess::Template> pyr(J);
+    for (int k = 0; k < J; ++k) {
+      const fl_template &t = tl[(size_t)v * J + k];
+      pyr[k].width = t.width;
+      pyr[k].height = t.height;
+      pyr[k].offset_x = t.offset_x;
+      pyr[k].offset_y = t.offset_y;
+      pyr[k].pyramid_level = t.pyramid_level;
+      for (int j = 0; j < t.feat_count; ++j) {
+        const fl_feature &f = fl[(size_t)t.feat_begin + j];
+        pyr[k].features.push_back(fealess::Feature{f.x, f.y, f.label});
+      }
+    }
+    c.template_pyramids.push_back(pyr);
+    c.poses.push_back(std::vector<float>(poses13 + (size_t)13 * v, poses13 + (size_t)13 * (v + 1)));
+  }
+  if (c.template_pyramids.empty()) return (int)ERROR_INVALID_PARAM;
+  // the renders first, the YAML last: AddObj never sees a template file whose depth images are still missing
+  const std::string ddir = dir + "/depth";
+  if ((mkdir(dir.c_str(), 0755) != 0 && errno != EEXIST) || (mkdir(ddir.c_str(), 0755) != 0 && errno != EEXIST))
+    return (int)ERROR_OPEN_FILE_FAILED;
+  std::vector<unsigned short> px((size_t)w * ht);
+  for (size_t id = 0; id < view_of.size(); ++id) {
+    const unsigned short *d = depth_mm[view_of[id]].pData;
+    for (size_t i = 0; i < px.size(); ++i) px[i] = (unsigned short)std::min(65535u, 10u * d[i]);   // 0.1 mm, saturating
+    std::ostringstream fn;
+    fn << ddir << "/" << id << ".png";                                       // by template id, as Recognition reads them
+    std::string err;
+    if (!fealess::WritePng16(fn.str(), px.data(), w, ht, &err)) return (int)ERROR_OPEN_FILE_FAILED;
+  }
+  const std::string yml = dir + "/linemod_templates.yml";
+  std::remove((yml + ".flbank").c_str());                                    // a stale cache could match the new file's size and mtime
+  if (!fealess::WriteLinemod(df, yml)) return (int)ERROR_OPEN_FILE_FAILED;
+  if (template_of_view) *template_of_view = tov;
+  return SUCCESS;
+}
+
 // ---- flat C shim so that the pytest harness (ctypes) can drive the C++ facade -------------------
 extern "C" {
+int cadreco_write_png16(const char *path, const unsigned short *px, int w, int h)
+{
+  std::string err;
+  return fealess::WritePng16(path, px, w, h, &err) ? 0 : -1;
+}
+// CadRecoTrainViews on host views of one size w x h_; mask: NULL or n pointers (each may be NULL); template_of_view: n ints
+// (may be NULL), written on success
+int cadreco_train_views(void *h, const char *dir, const char *class_id, int n, const unsigned char *const *bgr,
+                        const unsigned short *const *depth, const unsigned char *const *mask, int w, int h_, const float *poses13,
+                        int levels, const int *T, int *template_of_view)
+{
+  if (!dir || !class_id || n < 1 || !bgr || !depth) return (int)ERROR_INVALID_PARAM;
+  std::vector<TImageU> b(n), m(mask ? n : 0);
+  std::vector<TImageU16> d(n);
+  for (int i = 0; i < n; ++i) {
+    b[i] = TImageU{0.0, (unsigned char *)bgr[i], w, h_};
+    d[i] = TImageU16{0.0, (unsigned short *)depth[i], w, h_};
+    if (mask) m[i] = TImageU{0.0, (unsigned char *)mask[i], w, h_};
+  }
+  std::vector<int> tov;
+  const int rc = CadRecoTrainViews((CObjRecoCAD *)h, dir, class_id, n, b.data(), d.data(), mask ? m.data() : nullptr, poses13, levels, T, &tov);
+  if (rc == SUCCESS && template_of_view) std::copy(tov.begin(), tov.end(), template_of_view);
+  return rc;
+}
 int cadreco_set_multi_hypothesis(void *h, int k, float nms_dist_mm) { return CadRecoSetMultiHypothesis((CObjRecoCAD *)h, k, nms_dist_mm); }
 // Recognition() returning every result: poses16 receives min(*n_results, cap) 4x4 matrices
 int cadreco_recognition_all(void *h, const unsigned char *bgr, const unsigned short *depth, int w, int h_, double ts, int kw, int kh,

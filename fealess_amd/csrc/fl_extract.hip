@@ -3,20 +3,26 @@
 //   ColorGradientPyramid::extractTemplate (:461-513), DepthNormalPyramid::extractTemplate (:747-825),
 //   QuantizedPyramid::selectScatteredFeatures (:135-164), cropTemplates (:52-96), pyrDown (:434-453, :721-739).
 //
-// Offline path (one call per training view), so the kernels are simple; what matters is that the selected
-// features equal the reference's bit for bit (oracle/extract_oracle.c):
-//   k_color_candidates   border mask (mask - erode3x3(mask)), strong-gradient test, 64-bit sort keys
-//   k_depth_candidates   eroded (5x5) mask, exact chessboard distance to the nearest pixel of another label
+// Offline path, batched over training views: fl_extract_template_batch runs every stage once per chunk of up to
+// FL_EXTRACT_CHUNK_VIEWS views, with a grid dimension over the views or over the chunk's (view, level, modality) jobs;
+// fl_extract_template_pyramid is its n_views = 1 case.  What matters is that the selected features equal the
+// reference's bit for bit (oracle/extract_oracle.c):
+//   k_local_mask         border mask (mask - erode3x3(mask)) / 5x5-eroded mask, for the views that have a mask
+//   k_color_candidates   strong-gradient test, 64-bit sort keys appended to the job's key segment
+//   k_depth_candidates   exact chessboard distance to the nearest pixel of another label
 //                        (= cv::distanceTransform(DIST_C, 3) of the per-label images), per-label counts
 //   k_depth_keys         score / label_count -> sort keys
-//   k_bitonic_step/_local  bitonic sort of the keys (2048-key blocks in LDS, the wider steps in global memory):
-//                        (score desc, raster order asc) is exactly what std::stable_sort with Candidate::operator< yields
-//   k_select_scattered   the greedy selection, sequential in its result but not in its work: every candidate keeps its
-//                        squared distance to the nearest chosen feature, the walk to the next passing candidate is a
-//                        workgroup-wide min (1024 threads)
+//   k_pad_keys, k_bitonic_step/_local  bitonic sort of each job's keys as its own segment of next_pow2(candidates) keys
+//                        (2048-key blocks in LDS, the wider steps in global memory): (score desc, raster order asc) is
+//                        exactly what std::stable_sort with Candidate::operator< yields, whatever order the atomics
+//                        appended the candidates in
+//   k_select_scattered   the greedy selection, one 1024-thread workgroup per job and all jobs in one launch; sequential
+//                        in its result but not in its work: every candidate keeps its squared distance to the nearest
+//                        chosen feature, the walk to the next passing candidate is a workgroup-wide min
+// A chunk makes two host round trips whatever its size: the candidate counts (they size the sort) and the results.
 #include "fl_internal.h"
 #include <limits.h>
-#include <utility>
+#include <algorithm>
 #include <vector>
 
 namespace {
@@ -25,7 +31,20 @@ struct ExtractCounters {
   int n_cand;            // number of candidates
   int label_counts[8];   // depth modality
   int area;              // countNonZero(local_mask)
-  int n_out;             // features written (= num_features on success)
+  int n_out;             // features written (= num_features on success); -1: too few candidates
+};
+
+// One (view, level, modality) of a chunk, written on the host once the candidate counts are known.
+struct ExtractJob {
+  unsigned long long *keys;    // the job's key segment (n_pow2 keys once padded)
+  const uint8_t *labels;       // quantised image of the job's level and modality (the features' labels)
+  uint32_t *xy;                // selection scratch, n_cand entries each
+  int *mind2;
+  ExtractCounters *cnt;
+  fl_feature *out;             // 64 entries
+  int w, num_features, depth_mode, total_px;
+  int n_pow2;                  // sort segment length; 0: the view cannot yield a template, nothing to sort or select
+  int pad;
 };
 
 __device__ __forceinline__ int ex_label(int q)           // getLabel (linemod.cpp:15-30); -1 where the reference throws
@@ -43,33 +62,42 @@ __device__ __forceinline__ int ex_min_rect(const uint8_t *m, int w, int h, int x
   return v;
 }
 
+// The per-view kernels below find view z = blockIdx.z at base + z * vs (vs: bytes per view) and its counters at
+// cnt + z * cnt_stride.  has_mask[z] = 0: the view has no mask (the reference's empty cv::Mat).
+
 // local_mask of the two extractTemplate()s: iterations = 1 -> border of the mask (mask - erode(mask), :467-468),
 // iterations = 2 -> the mask eroded by a 5x5 rectangle (:752-755)
-__global__ __launch_bounds__(256) void k_local_mask(const uint8_t *__restrict__ mask, int w, int h, int iterations, int border,
-                                                    uint8_t *__restrict__ local)
+__global__ __launch_bounds__(256) void k_local_mask(const uint8_t *__restrict__ mask_, uint8_t *__restrict__ local_, size_t vs,
+                                                    const int *__restrict__ has_mask, int w, int h, int iterations, int border)
 {
+  const int z = blockIdx.z;
+  if (!has_mask[z]) return;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
+  const uint8_t *mask = mask_ + (size_t)z * vs;
   const size_t i = (size_t)y * w + x;
   const int e = ex_min_rect(mask, w, h, x, y, iterations);
   const int m = mask[i];
-  local[i] = (uint8_t)(border ? (m > e ? m - e : 0) : e);
+  local_[(size_t)z * vs + i] = (uint8_t)(border ? (m > e ? m - e : 0) : e);
 }
 
+// quantized / mag: the views' images at a pitch of w * h elements
 __global__ __launch_bounds__(256) void k_color_candidates(const uint8_t *__restrict__ quantized, const float *__restrict__ mag,
-                                                          const uint8_t *__restrict__ mask, int w, int h, float thr_sq,
-                                                          unsigned long long *__restrict__ keys, ExtractCounters *cnt)
+                                                          const uint8_t *__restrict__ local, size_t vs, const int *__restrict__ has_mask,
+                                                          int w, int h, float thr_sq, uint8_t *__restrict__ keys_,
+                                                          ExtractCounters *cnt_, int cnt_stride)
 {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
-  const size_t i = (size_t)y * w + x;
-  if (mask && !mask[i]) return;                            // `mask` is the precomputed local_mask here
-  const int q = quantized[i];
-  const float score = mag[i];
+  const int z = blockIdx.z;
+  const size_t i = (size_t)y * w + x, vo = (size_t)z * vs, io = (size_t)z * w * h + i;
+  if (has_mask[z] && !local[vo + i]) return;               // the precomputed local_mask
+  const int q = quantized[io];
+  const float score = mag[io];
   if (q > 0 && score > thr_sq) {
-    const int pos = atomicAdd(&cnt->n_cand, 1);
+    const int pos = atomicAdd(&cnt_[(size_t)z * cnt_stride].n_cand, 1);
     // descending score, then raster order: positive floats order like their bit patterns
-    keys[pos] = ((unsigned long long)(~__float_as_uint(score)) << 32) | (unsigned)i;
+    ((unsigned long long *)(keys_ + vo))[pos] = ((unsigned long long)(~__float_as_uint(score)) << 32) | (unsigned)i;
   }
 }
 
@@ -96,14 +124,19 @@ __device__ float ex_chessboard(const uint8_t *normal, const uint8_t *mask, int w
   return 8192.0f;
 }
 
-__global__ __launch_bounds__(256) void k_depth_candidates(const uint8_t *__restrict__ normal, const uint8_t *__restrict__ mask,
-                                                          int w, int h, int extract_threshold, int *__restrict__ raster,
-                                                          float *__restrict__ score, ExtractCounters *cnt)
+__global__ __launch_bounds__(256) void k_depth_candidates(const uint8_t *__restrict__ normal_, const uint8_t *__restrict__ local_,
+                                                          size_t vs, const int *__restrict__ has_mask, int w, int h,
+                                                          int extract_threshold, uint8_t *__restrict__ raster_,
+                                                          uint8_t *__restrict__ score_, ExtractCounters *cnt_, int cnt_stride)
 {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
-  const size_t i = (size_t)y * w + x;
-  const bool in_mask = !mask || mask[i] != 0;              // `mask` is the precomputed local_mask (5x5-eroded)
+  const int z = blockIdx.z;
+  const size_t i = (size_t)y * w + x, vo = (size_t)z * vs;
+  const uint8_t *normal = normal_ + vo;
+  const uint8_t *mask = has_mask[z] ? local_ + vo : nullptr;   // the precomputed local_mask (5x5-eroded)
+  ExtractCounters *cnt = cnt_ + (size_t)z * cnt_stride;
+  const bool in_mask = !mask || mask[i] != 0;
   if (mask && in_mask) atomicAdd(&cnt->area, 1);
   if (!in_mask) return;
   const int q = normal[i];
@@ -113,33 +146,47 @@ __global__ __launch_bounds__(256) void k_depth_candidates(const uint8_t *__restr
   const float d = ex_chessboard(normal, mask, w, h, x, y, 1 << label);
   if (d >= (float)extract_threshold) {
     const int pos = atomicAdd(&cnt->n_cand, 1);
-    raster[pos] = (int)i;
-    score[pos] = d;
+    ((int *)(raster_ + vo))[pos] = (int)i;
+    ((float *)(score_ + vo))[pos] = d;
     atomicAdd(&cnt->label_counts[label], 1);
   }
 }
 
-__global__ __launch_bounds__(256) void k_depth_keys(const uint8_t *__restrict__ normal, const int *__restrict__ raster,
-                                                    const float *__restrict__ score, const ExtractCounters *cnt,
-                                                    unsigned long long *__restrict__ keys)
+// grid-stride over the view's candidates: their count is only known on the device here
+__global__ __launch_bounds__(256) void k_depth_keys(const uint8_t *__restrict__ normal_, const uint8_t *__restrict__ raster_,
+                                                    const uint8_t *__restrict__ score_, size_t vs, const ExtractCounters *cnt_,
+                                                    int cnt_stride, uint8_t *__restrict__ keys_)
 {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= cnt->n_cand) return;
-  const int i = raster[k];
-  const float s = score[k] / (float)cnt->label_counts[ex_label(normal[i])];   // :806-810
-  keys[k] = ((unsigned long long)(~__float_as_uint(s)) << 32) | (unsigned)i;
+  const int z = blockIdx.z;
+  const size_t vo = (size_t)z * vs;
+  const ExtractCounters *cnt = cnt_ + (size_t)z * cnt_stride;
+  const uint8_t *normal = normal_ + vo;
+  const int *raster = (const int *)(raster_ + vo);
+  const float *score = (const float *)(score_ + vo);
+  unsigned long long *keys = (unsigned long long *)(keys_ + vo);
+  const int n = cnt->n_cand;
+  for (int k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
+    const int i = raster[k];
+    const float s = score[k] / (float)cnt->label_counts[ex_label(normal[i])];   // :806-810
+    keys[k] = ((unsigned long long)(~__float_as_uint(s)) << 32) | (unsigned)i;
+  }
 }
 
-__global__ __launch_bounds__(256) void k_pad_keys(unsigned long long *keys, const ExtractCounters *cnt, int n_pow2)
+// The sort kernels take blockIdx.y = job; a job's segment is keys[0 .. n_pow2).
+__global__ __launch_bounds__(256) void k_pad_keys(const ExtractJob *__restrict__ jobs)
 {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= cnt->n_cand && k < n_pow2) keys[k] = ~0ull;
+  const ExtractJob &jb = jobs[blockIdx.y];
+  const int n = jb.cnt->n_cand, np2 = jb.n_pow2;
+  for (int k = n + blockIdx.x * 256 + threadIdx.x; k < np2; k += gridDim.x * 256) jb.keys[k] = ~0ull;
 }
 
-__global__ __launch_bounds__(256) void k_bitonic_step(unsigned long long *keys, int n_pow2, int kk, int j)
+__global__ __launch_bounds__(256) void k_bitonic_step(const ExtractJob *__restrict__ jobs, int kk, int j)
 {
+  const ExtractJob &jb = jobs[blockIdx.y];
+  const int np2 = jb.n_pow2;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pow2) return;
+  if (kk > np2 || i >= np2) return;                        // a shorter segment has no stage kk
+  unsigned long long *keys = jb.keys;
   const int l = i ^ j;
   if (l > i) {
     const unsigned long long a = keys[i], b = keys[l];
@@ -149,13 +196,20 @@ __global__ __launch_bounds__(256) void k_bitonic_step(unsigned long long *keys, 
 }
 
 // The bitonic network's steps with partner distance j < SORT_CHUNK stay inside a SORT_CHUNK-key block: one workgroup
-// runs them back to back in LDS instead of one launch per step.  first_kk == 2: every stage up to SORT_CHUNK (a full
-// sort of each block, direction by the global index); otherwise the tail (j = SORT_CHUNK/2 .. 1) of stage kk.
+// runs them back to back in LDS instead of one launch per step.  first_kk == 2: every stage up to min(n_pow2, SORT_CHUNK)
+// (a full sort of each block, direction by the index in the segment); otherwise the tail (j = SORT_CHUNK/2 .. 1) of
+// stage kk = first_kk = last_kk, in the segments that have that stage.
 #define SORT_CHUNK 2048
-__global__ __launch_bounds__(SORT_CHUNK / 2) void k_bitonic_local(unsigned long long *keys, int n_pow2, int first_kk, int last_kk)
+__global__ __launch_bounds__(SORT_CHUNK / 2) void k_bitonic_local(const ExtractJob *__restrict__ jobs, int first_kk, int last_kk)
 {
   __shared__ unsigned long long sk[SORT_CHUNK];
+  const ExtractJob &jb = jobs[blockIdx.y];
+  const int n_pow2 = jb.n_pow2;
+  if (n_pow2 == 0 || (first_kk > 2 && last_kk > n_pow2)) return;
   const int chunk = min(n_pow2, SORT_CHUNK), base = blockIdx.x * chunk, t = threadIdx.x;
+  if (base >= n_pow2) return;                              // block-uniform
+  if (first_kk == 2) last_kk = chunk;
+  unsigned long long *keys = jb.keys;
   for (int e = t; e < chunk; e += SORT_CHUNK / 2) sk[e] = keys[base + e];
   __syncthreads();
   for (int kk = first_kk; kk <= last_kk; kk <<= 1) {
@@ -172,26 +226,31 @@ __global__ __launch_bounds__(SORT_CHUNK / 2) void k_bitonic_local(unsigned long 
   for (int e = t; e < chunk; e += SORT_CHUNK / 2) keys[base + e] = sk[e];
 }
 
-// selectScatteredFeatures (:135-164).  The reference re-tests every candidate against every chosen feature on every
-// pass (~candidates x features x passes distance tests, with the distance dropping by one per pass).  Here each
-// candidate carries mind2 = its squared distance to the nearest chosen feature so far, so `keep` is one compare,
-// an accepted feature is folded into mind2 with one test per candidate, and the sequential walk "next candidate
-// at or after i that passes" is a workgroup-wide min.  Same features in the same order.  Thread t owns candidates
-// t, t + 1024, ...: xy / mind2 (global scratch) are only ever touched by their owner, so no fences are needed.
+// selectScatteredFeatures (:135-164), one workgroup per job.  The reference re-tests every candidate against every
+// chosen feature on every pass (~candidates x features x passes distance tests, with the distance dropping by one per
+// pass).  Here each candidate carries mind2 = its squared distance to the nearest chosen feature so far, so `keep` is
+// one compare, an accepted feature is folded into mind2 with one test per candidate, and the sequential walk "next
+// candidate at or after i that passes" is a workgroup-wide min.  Same features in the same order.  Thread t owns
+// candidates t, t + 1024, ...: xy / mind2 (global scratch) are only ever touched by their owner, so no fences are needed.
 #define SEL_BS 1024
-__global__ __launch_bounds__(SEL_BS) void k_select_scattered(const unsigned long long *__restrict__ keys, const uint8_t *__restrict__ labels_img,
-                                                             int w, int num_features, int depth_mode, int total_px,
-                                                             ExtractCounters *cnt, fl_feature *__restrict__ out,
-                                                             uint32_t *__restrict__ xy, int *__restrict__ mind2)
+__global__ __launch_bounds__(SEL_BS) void k_select_scattered(const ExtractJob *__restrict__ jobs)
 {
   __shared__ int s_min[SEL_BS / 64];
+  const ExtractJob &jb = jobs[blockIdx.x];
   const int tid = threadIdx.x;
+  ExtractCounters *cnt = jb.cnt;
+  const unsigned long long *keys = jb.keys;
+  const int w = jb.w, num_features = jb.num_features, depth_mode = jb.depth_mode;
+  uint32_t *xy = jb.xy;
+  int *mind2 = jb.mind2;
   const int n = cnt->n_cand;
-  if (n < num_features || num_features > 1024) { if (tid == 0) cnt->n_out = -1; return; }   // "We require a certain number of features"
+  // "We require a certain number of features"; n_pow2 == 0: a job of the same view has too few
+  if (jb.n_pow2 == 0 || n < num_features || num_features > 1024) { if (tid == 0) cnt->n_out = -1; return; }
   float distance;
   if (depth_mode) {
-    const float area = cnt->area > 0 || depth_mode == 2 ? (float)cnt->area : (float)total_px;
-    distance = sqrtf(area) / sqrtf((float)num_features) + 1.5f;                  // :815-817
+    // countNonZero(local_mask) with a mask (depth_mode 2), the pixel count without (:815-817)
+    const float area = cnt->area > 0 || depth_mode == 2 ? (float)cnt->area : (float)jb.total_px;
+    distance = sqrtf(area) / sqrtf((float)num_features) + 1.5f;
   } else {
     distance = (float)(n / num_features + 1);                                    // :503-505
   }
@@ -234,9 +293,9 @@ __global__ __launch_bounds__(SEL_BS) void k_select_scattered(const unsigned long
     fx = raster % w;
     fy = raster / w;
     if (tid == 0) {
-      out[nf].x = fx;
-      out[nf].y = fy;
-      out[nf].label = ex_label(labels_img[raster]);
+      jb.out[nf].x = fx;
+      jb.out[nf].y = fy;
+      jb.out[nf].label = ex_label(jb.labels[raster]);
     }
     fold = true;
     ++nf;
@@ -252,53 +311,46 @@ __global__ __launch_bounds__(SEL_BS) void k_select_scattered(const unsigned long
 
 int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
-}  // namespace
+// A view's slab (offsets from the view's base, every array 256-byte aligned; px_l = (w0 >> l) * (h0 >> l)):
+//   colour A (3 px_0) | colour B (3 px_1) | depth (2 px_0) | local mask (px_0) | depth candidates' raster, score
+//   (4 px_0 each) | per level: mask, normals (px_l each) and per modality the key segment (8 next_pow2(px_l)) and the
+//   selection's xy, mind2 (4 px_l each).  The colour labels (px_l per level) and the magnitude (4 px_0) of the chunk's
+//   views sit in arrays of their own (k_color_quantize writes them at the pitch of one image).  include/fealess_hip.h
+//   states the total per view.
+struct ViewLayout {
+  size_t bgr0, bgr1, depth, local, raster, score;
+  size_t mask[FL_MAX_LEVELS], normal[FL_MAX_LEVELS];
+  size_t keys[FL_MAX_LEVELS][2], xy[FL_MAX_LEVELS][2], mind2[FL_MAX_LEVELS][2];
+  size_t bytes;
+};
 
-// One (level, modality): candidates -> sort -> select.  `feats` (device) receives num_features entries.
-static int extract_level(fl_context *ctx, int modality, const uint8_t *q_img, const float *mag, const uint8_t *mask, int w, int h,
-                         int num_features, float strong_threshold, int extract_threshold, unsigned long long *keys, int *raster,
-                         float *score, uint8_t *local, ExtractCounters *d_cnt, fl_feature *d_feats, int *ok)
+ViewLayout view_layout(int w0, int h0, int levels)
 {
-  FL_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(ExtractCounters), ctx->stream));
-  const dim3 grid((w + 63) / 64, (h + 3) / 4), blk(256);
-  if (mask) {
-    hipLaunchKernelGGL(k_local_mask, grid, blk, 0, ctx->stream, mask, w, h, modality == 0 ? 1 : 2, modality == 0 ? 1 : 0, local);
-    mask = local;
-  }
-  if (modality == 0) {
-    hipLaunchKernelGGL(k_color_candidates, grid, blk, 0, ctx->stream, q_img, mag, mask, w, h, strong_threshold * strong_threshold,
-                       keys, d_cnt);
-  } else {
-    hipLaunchKernelGGL(k_depth_candidates, grid, blk, 0, ctx->stream, q_img, mask, w, h, extract_threshold, raster, score, d_cnt);
-  }
-  FL_HIP(ctx, hipGetLastError());
-  ExtractCounters hc;
-  FL_HIP(ctx, hipMemcpyAsync(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream));
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *ok = hc.n_cand >= num_features;
-  if (!*ok) return FL_OK;
-  if (modality == 1) {
-    hipLaunchKernelGGL(k_depth_keys, dim3((hc.n_cand + 255) / 256), blk, 0, ctx->stream, q_img, raster, score, d_cnt, keys);
-    FL_HIP(ctx, hipGetLastError());
-  }
-  const int np2 = next_pow2(hc.n_cand);
-  hipLaunchKernelGGL(k_pad_keys, dim3((np2 + 255) / 256), blk, 0, ctx->stream, keys, d_cnt, np2);
-  {
-    const int chunk = np2 < SORT_CHUNK ? np2 : SORT_CHUNK, nblk = np2 / chunk;
-    hipLaunchKernelGGL(k_bitonic_local, dim3(nblk), dim3(SORT_CHUNK / 2), 0, ctx->stream, keys, np2, 2, chunk);
-    for (int kk = 2 * SORT_CHUNK; kk <= np2; kk <<= 1) {
-      for (int j = kk >> 1; j >= SORT_CHUNK; j >>= 1)
-        hipLaunchKernelGGL(k_bitonic_step, dim3((np2 + 255) / 256), blk, 0, ctx->stream, keys, np2, kk, j);
-      hipLaunchKernelGGL(k_bitonic_local, dim3(nblk), dim3(SORT_CHUNK / 2), 0, ctx->stream, keys, np2, kk, kk);
+  ViewLayout v;
+  size_t off = 0;
+  auto take = [&](size_t b) { size_t o = off; off += fl_align(b, 256); return o; };
+  const size_t px = (size_t)w0 * h0, px1 = (size_t)(w0 >> 1) * (h0 >> 1);
+  v.bgr0 = take(px * 3);
+  v.bgr1 = take(px1 * 3);
+  v.depth = take(px * 2);
+  v.local = take(px);
+  v.raster = take(px * 4);
+  v.score = take(px * 4);
+  for (int l = 0; l < levels; ++l) {
+    const size_t pl = (size_t)(w0 >> l) * (h0 >> l);
+    v.mask[l] = take(pl);
+    v.normal[l] = take(pl);
+    for (int m = 0; m < 2; ++m) {
+      v.keys[l][m] = take((size_t)next_pow2((int)pl) * 8);
+      v.xy[l][m] = take(pl * 4);
+      v.mind2[l][m] = take(pl * 4);
     }
   }
-  FL_HIP(ctx, hipGetLastError());
-  // raster / score are dead once the keys exist: reused as the selection's xy / mind2 scratch
-  hipLaunchKernelGGL(k_select_scattered, dim3(1), dim3(SEL_BS), 0, ctx->stream, keys, q_img, w, num_features,
-                     modality == 0 ? 0 : (mask ? 2 : 1), w * h, d_cnt, d_feats, (uint32_t *)raster, (int *)score);
-  FL_HIP(ctx, hipGetLastError());
-  return FL_OK;
+  v.bytes = off;
+  return v;
 }
+
+}  // namespace
 
 // cropTemplates (:52-96), host side
 static void crop_templates(fl_template *t, int n, fl_feature *f, int bb[4])
@@ -327,92 +379,188 @@ static void crop_templates(fl_template *t, int n, fl_feature *f, int bb[4])
   bb[0] = min_x; bb[1] = min_y; bb[2] = max_x - min_x; bb[3] = max_y - min_y;
 }
 
+// Views [v0, v0 + n) of a batch, n <= FL_EXTRACT_CHUNK_VIEWS: outputs at the batch's indices (feat_begin absolute).
+static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *bgr, const uint16_t *const *depth, const uint8_t *const *mask,
+                         int w0, int h0, int levels, int mem, fl_template *templates, fl_feature *features, int32_t *bb, int32_t *status)
+{
+  const int M = 2, J = levels * M;                         // jobs per view, index l * 2 + m
+  const ViewLayout lo = view_layout(w0, h0, levels);
+  const size_t vs = lo.bytes;
+  // device: view slabs | colour labels per level (n px_l) | magnitude (n 4 px_0) | then, also in pinned host memory at
+  // the same relative offsets: has_mask[n] | counters[n J] | features[n J 64] | jobs[n J]
+  size_t off = 0;
+  auto take = [&](size_t b) { size_t o = off; off += fl_align(b, 256); return o; };
+  const size_t px = (size_t)w0 * h0;
+  const size_t o_views = take(vs * n);
+  size_t o_quant[FL_MAX_LEVELS];
+  for (int l = 0; l < levels; ++l) o_quant[l] = take((size_t)n * (w0 >> l) * (h0 >> l));
+  const size_t o_mag = take(px * 4 * n), o_flags = take(sizeof(int) * n), o_cnt = take(sizeof(ExtractCounters) * n * J),
+               o_feats = take(sizeof(fl_feature) * 64 * n * J), o_jobs = take(sizeof(ExtractJob) * n * J);
+  void *sv = nullptr, *pv = nullptr;
+  int rc = fl_scratch(ctx, off, &sv);
+  if (rc) return rc;
+  if ((rc = fl_pinned(ctx, off - o_flags, &pv))) return rc;
+  uint8_t *s = (uint8_t *)sv, *vw = s + o_views;
+  auto pin = [&](size_t o) { return (uint8_t *)pv + (o - o_flags); };
+  int *d_flags = (int *)(s + o_flags), *h_flags = (int *)pin(o_flags);
+  ExtractCounters *d_cnt = (ExtractCounters *)(s + o_cnt), *h_cnt = (ExtractCounters *)pin(o_cnt);
+  fl_feature *d_feats = (fl_feature *)(s + o_feats), *h_feats = (fl_feature *)pin(o_feats);
+  ExtractJob *d_jobs = (ExtractJob *)(s + o_jobs), *h_jobs = (ExtractJob *)pin(o_jobs);
+
+  const hipMemcpyKind kind = mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  bool any_mask = false;
+  for (int v = 0; v < n; ++v) {
+    uint8_t *b = vw + (size_t)v * vs;
+    const uint8_t *mk = mask ? mask[v0 + v] : nullptr;
+    FL_HIP(ctx, hipMemcpyAsync(b + lo.bgr0, bgr[v0 + v], px * 3, kind, ctx->stream));
+    FL_HIP(ctx, hipMemcpyAsync(b + lo.depth, depth[v0 + v], px * 2, kind, ctx->stream));
+    if (mk) FL_HIP(ctx, hipMemcpyAsync(b + lo.mask[0], mk, px, kind, ctx->stream));
+    h_flags[v] = mk != nullptr;
+    any_mask = any_mask || mk;
+  }
+  FL_HIP(ctx, hipMemcpyAsync(d_flags, h_flags, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+  FL_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(ExtractCounters) * n * J, ctx->stream));
+  const dim3 blk(256);
+
+  // modality 0: ColorGradient(10, 63, 55) (:515-519); pyrDown :434-453.  The NN-halved mask pyramid made here is also
+  // modality 1's: it halves the same level-0 mask the same way (:721-739).
+  {
+    int w = w0, h = h0;
+    for (int l = 0; l < levels; ++l) {
+      const size_t img = (l & 1) ? lo.bgr1 : lo.bgr0;      // level l's colour image: A for even levels, B for odd ones
+      if (l > 0) {
+        if ((rc = fl_launch_pyrdown_bgr(ctx, vw + ((l & 1) ? lo.bgr0 : lo.bgr1), vs, vw + img, vs, n, w, h))) return rc;
+        if (any_mask && (rc = fl_launch_resize_nn_half(ctx, vw + lo.mask[l - 1], vs, vw + lo.mask[l], vs, n, w, h))) return rc;
+        w /= 2;
+        h /= 2;
+      }
+      if ((rc = fl_launch_quantized_orientations_mag(ctx, vw + img, vs, s + o_quant[l], (size_t)w * h, n, w, h, 10.0f, (float *)(s + o_mag))))
+        return rc;
+      const dim3 grid((w + 63) / 64, (h + 3) / 4, n);
+      if (any_mask) hipLaunchKernelGGL(k_local_mask, grid, blk, 0, ctx->stream, vw + lo.mask[l], vw + lo.local, vs, d_flags, w, h, 1, 1);
+      hipLaunchKernelGGL(k_color_candidates, grid, blk, 0, ctx->stream, s + o_quant[l], (const float *)(s + o_mag), vw + lo.local, vs, d_flags, w, h,
+                         55.0f * 55.0f, vw + lo.keys[l][0], d_cnt + l * M + 0, J);
+      FL_HIP(ctx, hipGetLastError());
+    }
+  }
+  // modality 1: DepthNormal(2000, 50, 63, 2) (:827-832)
+  {
+    int w = w0, h = h0;
+    if ((rc = fl_launch_quantized_normals(ctx, (const uint16_t *)(vw + lo.depth), vs, vw + lo.normal[0], vs, nullptr, 0, n, w, h, 2000, 50)))
+      return rc;
+    for (int l = 0; l < levels; ++l) {
+      if (l > 0) {
+        if ((rc = fl_launch_resize_nn_half(ctx, vw + lo.normal[l - 1], vs, vw + lo.normal[l], vs, n, w, h))) return rc;
+        w /= 2;
+        h /= 2;
+      }
+      const dim3 grid((w + 63) / 64, (h + 3) / 4, n);
+      if (any_mask) hipLaunchKernelGGL(k_local_mask, grid, blk, 0, ctx->stream, vw + lo.mask[l], vw + lo.local, vs, d_flags, w, h, 2, 0);
+      hipLaunchKernelGGL(k_depth_candidates, grid, blk, 0, ctx->stream, vw + lo.normal[l], vw + lo.local, vs, d_flags, w, h, 2 >> l,
+                         vw + lo.raster, vw + lo.score, d_cnt + l * M + 1, J);
+      // raster / score are reused by the next level, whose candidates queue behind these keys
+      const int kb = (int)std::min<size_t>(((size_t)w * h + 255) / 256, 64);
+      hipLaunchKernelGGL(k_depth_keys, dim3(kb, 1, n), blk, 0, ctx->stream, vw + lo.normal[l], vw + lo.raster, vw + lo.score, vs,
+                         d_cnt + l * M + 1, J, vw + lo.keys[l][1]);
+      FL_HIP(ctx, hipGetLastError());
+    }
+  }
+
+  // host round trip 1: every job's candidate count sizes its sort segment
+  FL_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(ExtractCounters) * n * J, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int max_np2 = 0;
+  for (int v = 0; v < n; ++v) {
+    bool view_ok = true;                                   // a view that cannot yield a template sorts nothing
+    for (int k = 0; k < J; ++k) view_ok = view_ok && h_cnt[v * J + k].n_cand >= (63 >> (k / M));
+    uint8_t *b = vw + (size_t)v * vs;
+    for (int k = 0; k < J; ++k) {
+      const int l = k / M, m = k % M;
+      ExtractJob &jb = h_jobs[v * J + k];
+      jb.keys = (unsigned long long *)(b + lo.keys[l][m]);
+      jb.labels = m == 0 ? s + o_quant[l] + (size_t)v * (w0 >> l) * (h0 >> l) : b + lo.normal[l];
+      jb.xy = (uint32_t *)(b + lo.xy[l][m]);
+      jb.mind2 = (int *)(b + lo.mind2[l][m]);
+      jb.cnt = d_cnt + v * J + k;
+      jb.out = d_feats + (size_t)64 * (v * J + k);
+      jb.w = w0 >> l;
+      jb.num_features = 63 >> l;
+      jb.depth_mode = m == 0 ? 0 : (h_flags[v] ? 2 : 1);
+      jb.total_px = (w0 >> l) * (h0 >> l);
+      jb.n_pow2 = view_ok ? next_pow2(h_cnt[v * J + k].n_cand) : 0;
+      jb.pad = 0;
+      max_np2 = std::max(max_np2, jb.n_pow2);
+    }
+  }
+  const int nj = n * J;
+  FL_HIP(ctx, hipMemcpyAsync(d_jobs, h_jobs, sizeof(ExtractJob) * nj, hipMemcpyHostToDevice, ctx->stream));
+  if (max_np2 > 0) {
+    hipLaunchKernelGGL(k_pad_keys, dim3(std::min((max_np2 + 255) / 256, 64), nj), blk, 0, ctx->stream, (const ExtractJob *)d_jobs);
+    hipLaunchKernelGGL(k_bitonic_local, dim3(max_np2 / std::min(max_np2, SORT_CHUNK), nj), dim3(SORT_CHUNK / 2), 0, ctx->stream,
+                       (const ExtractJob *)d_jobs, 2, SORT_CHUNK);
+    for (int kk = 2 * SORT_CHUNK; kk <= max_np2; kk <<= 1) {
+      for (int j = kk >> 1; j >= SORT_CHUNK; j >>= 1)
+        hipLaunchKernelGGL(k_bitonic_step, dim3(max_np2 / 256, nj), blk, 0, ctx->stream, (const ExtractJob *)d_jobs, kk, j);
+      hipLaunchKernelGGL(k_bitonic_local, dim3(max_np2 / SORT_CHUNK, nj), dim3(SORT_CHUNK / 2), 0, ctx->stream, (const ExtractJob *)d_jobs,
+                         kk, kk);
+    }
+    FL_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_select_scattered, dim3(nj), dim3(SEL_BS), 0, ctx->stream, (const ExtractJob *)d_jobs);
+  FL_HIP(ctx, hipGetLastError());
+
+  // host round trip 2: the counters (n_out) and the selected features
+  FL_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(ExtractCounters) * nj, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(h_feats, d_feats, sizeof(fl_feature) * 64 * nj, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int v = 0; v < n; ++v) {
+    const int gv = v0 + v;
+    bool ok = true;
+    for (int k = 0; k < J; ++k) ok = ok && h_cnt[v * J + k].n_out == (63 >> (k / M));
+    fl_template *t = templates + (size_t)gv * J;
+    for (int k = 0; k < J; ++k) {
+      t[k].width = t[k].height = -1;
+      t[k].offset_x = t[k].offset_y = 0;
+      t[k].pyramid_level = k / M;
+      t[k].feat_begin = 63 * (gv * J + k);
+      t[k].feat_count = ok ? 63 >> (k / M) : 0;
+      for (int j = 0; j < t[k].feat_count; ++j) features[t[k].feat_begin + j] = h_feats[(size_t)64 * (v * J + k) + j];
+    }
+    int box[4] = {0, 0, 0, 0};
+    if (ok) crop_templates(t, J, features, box);
+    for (int c = 0; c < 4; ++c) bb[4 * gv + c] = box[c];
+    status[gv] = ok ? FL_OK : FL_ERR_NO_TEMPLATE;
+  }
+  return FL_OK;
+}
+
+extern "C" int fl_extract_template_batch(fl_context *ctx, int n_views, const uint8_t *const *bgr, const uint16_t *const *depth,
+                                         const uint8_t *const *mask, int w0, int h0, int levels, int mem, fl_template *templates,
+                                         fl_feature *features, int32_t *bb, int32_t *status)
+{
+  if (!ctx || n_views < 1 || !bgr || !depth || !templates || !features || !bb || !status || w0 < 16 || h0 < 16 || levels < 1 ||
+      levels > FL_MAX_LEVELS)
+    return FL_ERR_INVALID;
+  if ((w0 >> (levels - 1)) < 8 || (h0 >> (levels - 1)) < 8) return fl_set_error(ctx, FL_ERR_INVALID, "image too small for %d levels", levels);
+  for (int v = 0; v < n_views; ++v)
+    if (!bgr[v] || !depth[v]) return fl_set_error(ctx, FL_ERR_INVALID, "view %d: null image", v);
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  for (int v0 = 0; v0 < n_views; v0 += FL_EXTRACT_CHUNK_VIEWS) {
+    const int rc = extract_chunk(ctx, v0, std::min(FL_EXTRACT_CHUNK_VIEWS, n_views - v0), bgr, depth, mask, w0, h0, levels, mem, templates,
+                                 features, bb, status);
+    if (rc) return rc;
+  }
+  return FL_OK;
+}
+
 extern "C" int fl_extract_template_pyramid(fl_context *ctx, const uint8_t *bgr, const uint16_t *depth, const uint8_t *mask, int w0,
                                            int h0, int levels, int mem, fl_template *templates, fl_feature *features, int bb[4])
 {
-  if (!ctx || !bgr || !depth || !templates || !features || w0 < 16 || h0 < 16 || levels < 1 || levels > FL_MAX_LEVELS)
-    return FL_ERR_INVALID;
-  if ((w0 >> (levels - 1)) < 8 || (h0 >> (levels - 1)) < 8) return fl_set_error(ctx, FL_ERR_INVALID, "image too small for %d levels", levels);
-  FL_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t px = (size_t)w0 * h0;
-  // scratch layout (bytes): bgr A | bgr B | depth | mask A | mask B | quant | normal A | normal B | mag | keys | raster | score | cnt | feats
-  size_t off = 0;
-  auto take = [&](size_t b) { size_t o = off; off += fl_align(b, 256); return o; };
-  const size_t o_bgr0 = take(px * 3), o_bgr1 = take(px * 3), o_depth = take(px * 2), o_m0 = take(px), o_m1 = take(px), o_q = take(px),
-               o_n0 = take(px), o_n1 = take(px), o_mag = take(px * 4), o_keys = take((size_t)next_pow2((int)px) * 8),
-               o_raster = take(px * 4), o_score = take(px * 4), o_local = take(px), o_cnt = take(sizeof(ExtractCounters)),
-               o_feats = take(sizeof(fl_feature) * 64 * 2 * FL_MAX_LEVELS);
-  void *sv = nullptr;
-  int rc = fl_scratch(ctx, off, &sv);
+  if (!bgr || !depth) return FL_ERR_INVALID;
+  int32_t box[4], st = FL_OK;
+  const int rc = fl_extract_template_batch(ctx, 1, &bgr, &depth, mask ? &mask : nullptr, w0, h0, levels, mem, templates, features, box, &st);
   if (rc) return rc;
-  uint8_t *s = (uint8_t *)sv;
-  const hipMemcpyKind kind = mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  FL_HIP(ctx, hipMemcpyAsync(s + o_bgr0, bgr, px * 3, kind, ctx->stream));
-  FL_HIP(ctx, hipMemcpyAsync(s + o_depth, depth, px * 2, kind, ctx->stream));
-  if (mask) FL_HIP(ctx, hipMemcpyAsync(s + o_m0, mask, px, kind, ctx->stream));
-  ExtractCounters *d_cnt = (ExtractCounters *)(s + o_cnt);
-  fl_feature *d_feats = (fl_feature *)(s + o_feats);
-  const int M = 2;
-  int all_ok = 1;
-  // modality 0: ColorGradient(10, 63, 55) (:515-519); pyrDown :434-453
-  {
-    int w = w0, h = h0, nf = 63;
-    uint8_t *src = s + o_bgr0, *nxt = s + o_bgr1, *mk = mask ? s + o_m0 : nullptr, *mk2 = s + o_m1;
-    for (int l = 0; l < levels && all_ok; ++l) {
-      if (l > 0) {
-        nf /= 2;
-        if ((rc = fl_launch_pyrdown_bgr(ctx, src, 0, nxt, 0, 1, w, h))) return rc;
-        std::swap(src, nxt);
-        if (mk) { if ((rc = fl_launch_resize_nn_half(ctx, mk, 0, mk2, 0, 1, w, h))) return rc; std::swap(mk, mk2); }
-        w /= 2;
-        h /= 2;
-      }
-      if ((rc = fl_launch_quantized_orientations_mag(ctx, src, 0, s + o_q, 0, 1, w, h, 10.0f, (float *)(s + o_mag)))) return rc;
-      int ok = 0;
-      if ((rc = extract_level(ctx, 0, s + o_q, (const float *)(s + o_mag), mk, w, h, nf, 55.0f, 0, (unsigned long long *)(s + o_keys),
-                              (int *)(s + o_raster), (float *)(s + o_score), s + o_local, d_cnt, d_feats + 64 * (l * M + 0), &ok)))
-        return rc;
-      all_ok = all_ok && ok;
-      fl_template &t = templates[l * M + 0];
-      t.width = t.height = -1; t.offset_x = t.offset_y = 0; t.pyramid_level = l; t.feat_begin = 63 * (l * M + 0); t.feat_count = ok ? nf : 0;
-    }
-  }
-  // modality 1: DepthNormal(2000, 50, 63, 2) (:827-832); pyrDown :721-739
-  if (all_ok) {
-    int w = w0, h = h0, nf = 63, ext = 2;
-    if (mask) FL_HIP(ctx, hipMemcpyAsync(s + o_m0, mask, px, kind, ctx->stream));       // level-0 mask again
-    uint8_t *nrm = s + o_n0, *nrm2 = s + o_n1, *mk = mask ? s + o_m0 : nullptr, *mk2 = s + o_m1;
-    if ((rc = fl_launch_quantized_normals(ctx, (const uint16_t *)(s + o_depth), 0, nrm, 0, s + o_q, 0, 1, w, h, 2000, 50))) return rc;
-    for (int l = 0; l < levels && all_ok; ++l) {
-      if (l > 0) {
-        nf /= 2;
-        ext /= 2;
-        if ((rc = fl_launch_resize_nn_half(ctx, nrm, 0, nrm2, 0, 1, w, h))) return rc;
-        std::swap(nrm, nrm2);
-        if (mk) { if ((rc = fl_launch_resize_nn_half(ctx, mk, 0, mk2, 0, 1, w, h))) return rc; std::swap(mk, mk2); }
-        w /= 2;
-        h /= 2;
-      }
-      int ok = 0;
-      if ((rc = extract_level(ctx, 1, nrm, nullptr, mk, w, h, nf, 0.f, ext, (unsigned long long *)(s + o_keys), (int *)(s + o_raster),
-                              (float *)(s + o_score), s + o_local, d_cnt, d_feats + 64 * (l * M + 1), &ok)))
-        return rc;
-      all_ok = all_ok && ok;
-      fl_template &t = templates[l * M + 1];
-      t.width = t.height = -1; t.offset_x = t.offset_y = 0; t.pyramid_level = l; t.feat_begin = 63 * (l * M + 1); t.feat_count = ok ? nf : 0;
-    }
-  }
-  if (!all_ok) {
-    FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return fl_set_error(ctx, FL_ERR_NO_TEMPLATE, "too few candidate features at some pyramid level (addTemplate returns -1)");
-  }
-  std::vector<fl_feature> hf((size_t)64 * M * levels);
-  FL_HIP(ctx, hipMemcpyAsync(hf.data(), d_feats, sizeof(fl_feature) * hf.size(), hipMemcpyDeviceToHost, ctx->stream));
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int k = 0; k < levels * M; ++k)
-    for (int j = 0; j < templates[k].feat_count; ++j) features[63 * k + j] = hf[(size_t)64 * k + j];
-  int box[4];
-  crop_templates(templates, levels * M, features, box);
+  if (st != FL_OK) return fl_set_error(ctx, FL_ERR_NO_TEMPLATE, "too few candidate features at some pyramid level (addTemplate returns -1)");
   if (bb) { bb[0] = box[0]; bb[1] = box[1]; bb[2] = box[2]; bb[3] = box[3]; }
   return FL_OK;
 }

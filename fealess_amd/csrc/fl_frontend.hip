@@ -120,6 +120,10 @@ __device__ __forceinline__ void cq_hrow(const uint8_t *__restrict__ src, int w, 
 #ifndef FL_CQ_WPE
 #define FL_CQ_WPE 6              // 80 VGPRs, no spills: 6 waves per SIMD (measured: 5 -> 6 gives -2 % front-end time, 7/8 spill)
 #endif
+// kMag (template extraction): frame z's squared gradient magnitude goes to mag_out + z * out_stride floats, i.e. the
+// magnitude images have the quantised images' pitch in elements.  The front-end of the recognition path launches
+// k_color_quantize<false>, whose mag_out is null there.
+template <bool kMag>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, FL_CQ_WPE))) void k_color_quantize(const uint8_t *__restrict__ bgr, size_t in_stride,
                                                         uint8_t *__restrict__ dst, size_t out_stride, int w, int h,
                                                         float threshold_sq, int nstrips, int nchunks,
@@ -228,8 +232,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, 
         if (maj) res = (uint8_t)(1u << ((__ffs((int)maj) - 4) >> 2));
       }
       out[(size_t)yo * w + x] = res;
-      // template extraction also wants the squared magnitude image (linemod.cpp:461-513); one frame only
-      if (mag_out) mag_out[(size_t)yo * w + x] = Mg[1];
+      // template extraction also wants the squared magnitude image (linemod.cpp:461-513)
+      if (kMag) mag_out[(size_t)blockIdx.z * out_stride + (size_t)yo * w + x] = Mg[1];
+      else if (mag_out) mag_out[(size_t)yo * w + x] = Mg[1];
     }
   }
 }
@@ -246,8 +251,12 @@ static int launch_color_quantize(fl_context *ctx, const uint8_t *bgr, size_t in_
 {
   const int nstrips = (w + CQ_COLS - 1) / CQ_COLS, nchunks = (h + CQ_CH - 1) / CQ_CH;
   dim3 grid((nstrips * nchunks + 3) / 4, 1, n_frames);
-  hipLaunchKernelGGL(k_color_quantize, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h,
-                     weak_threshold * weak_threshold, nstrips, nchunks, mag_out, tiles, tiles_stride);
+  if (mag_out)
+    hipLaunchKernelGGL(k_color_quantize<true>, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h,
+                       weak_threshold * weak_threshold, nstrips, nchunks, mag_out, tiles, tiles_stride);
+  else
+    hipLaunchKernelGGL(k_color_quantize<false>, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h,
+                       weak_threshold * weak_threshold, nstrips, nchunks, mag_out, tiles, tiles_stride);
   FL_HIP(ctx, hipGetLastError());
   return FL_OK;
 }

@@ -217,6 +217,25 @@ int  fl_pyrdown_bgr(fl_context *ctx, const uint8_t *src, int w, int h, uint8_t *
  * the reference returns -1.  The caller appends the pyramid to a class with fl_detector_add_class. */
 int  fl_extract_template_pyramid(fl_context *ctx, const uint8_t *bgr, const uint16_t *depth, const uint8_t *mask, int w0,
                                  int h0, int levels, int mem, fl_template *templates, fl_feature *features, int bb[4]);
+/* Detector::addTemplate for n_views views of w0 x h0, the same defaults and semantics as fl_extract_template_pyramid
+ * (which is this call with n_views = 1).  bgr[v] (w0*h0*3 u8), depth[v] (w0*h0 u16, mm): host or device memory as
+ * `mem` says.  mask: NULL (no view has a mask) or n_views pointers, each NULL (that view has none) or w0*h0 u8.
+ * Out (host):
+ *   templates[(v * levels + l) * 2 + m], feat_begin = 63 * that index (absolute in `features`)
+ *   features[63 * ((v * levels + l) * 2 + m) + j]
+ *   bb[4 * v .. 4 * v + 3] = {x, y, width, height}
+ *   status[v] = FL_OK, or FL_ERR_NO_TEMPLATE where addTemplate returns -1: then the view's templates have
+ *               feat_count = 0 and its bb = {0, 0, 0, 0}
+ * Returns FL_OK when the batch ran, even if some views failed; FL_ERR_INVALID (nothing written) for n_views < 1, a null
+ * array or image, or the sizes and levels fl_extract_template_pyramid refuses.
+ * The call works through the batch in chunks of FL_EXTRACT_CHUNK_VIEWS views, each stage launched once per chunk.  A
+ * chunk's device scratch (the context's, kept for later calls) is, per view and with px_l = (w0 >> l) * (h0 >> l):
+ *   18 px_0 + 3 px_1 + sum_l (19 px_l + 16 next_pow2(px_l)) bytes (each array rounded up to 256 bytes)
+ * -- 23.5 MB at 640x480 with two levels, 1.5 GB for a full chunk -- and 4 + 1768 levels bytes of pinned host memory. */
+#define FL_EXTRACT_CHUNK_VIEWS 64
+int  fl_extract_template_batch(fl_context *ctx, int n_views, const uint8_t *const *bgr, const uint16_t *const *depth,
+                               const uint8_t *const *mask, int w0, int h0, int levels, int mem, fl_template *templates,
+                               fl_feature *features, int32_t *bb, int32_t *status);
 /* cv::resize(src, dst, Size(dw, dh), 0, 0, INTER_LINEAR) as PrepareInputData applies it to frames
  * that are not 640 wide (obj_reco_lmicp.cpp:39-45, 229-249: TImage2Mat(..., true)); BGR8 and u16 */
 int  fl_resize_linear_bgr8(fl_context *ctx, const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh, int mem);
