@@ -56,6 +56,10 @@ class RecognitionParams(C.Structure):
                 ("dist_diff_thr", C.c_float), ("icp_mode", C.c_int32)]
 
 
+class RenderParams(C.Structure):
+    _fields_ = [("light", C.c_float * 3), ("ambient", C.c_float)]
+
+
 class StageTimes(C.Structure):
     _fields_ = [("frontend_ms", C.c_float), ("linmem_ms", C.c_float), ("scan_ms", C.c_float), ("refine_ms", C.c_float),
                 ("sort_ms", C.c_float), ("backproject_ms", C.c_float), ("icp_ms", C.c_float), ("total_ms", C.c_float),
@@ -63,6 +67,7 @@ class StageTimes(C.Structure):
                 ("lazy_frontend_ms", C.c_float), ("reserved0", C.c_float)]
 
 
+FL_RENDER_AMBIENT = 0.2    # include/fealess_hip.h: fl_render_views' ambient when no fl_render_params is given
 FL_TOPK_OVERFLOW = -2      # fl_export_topk_batch: template id of record 0 of a frame whose candidate buffers overflowed
 
 _P = C.c_void_p
@@ -97,6 +102,8 @@ SIGNATURES = {
     "fl_pyrdown_bgr": (_I, [_P, _P, _I, _I, _P, _I]),
     "fl_extract_template_pyramid": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, C.POINTER(_I)]),
     "fl_extract_template_batch": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "fl_render_views": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _P, C.POINTER(Intrinsics), C.POINTER(RenderParams), _I, _P, _P, _P, _P]),
+    "fl_view_sphere": (_I, [_I, _I, _P, _I, _I, _F, _P, _I, C.POINTER(_I)]),
     "fl_resize_linear_bgr8": (_I, [_P, _P, _I, _I, _P, _I, _I, _I]),
     "fl_resize_linear_u16": (_I, [_P, _P, _I, _I, _P, _I, _I, _I]),
     "fl_lm_label_stride": (C.c_size_t, [_I, _I, _I]),

@@ -159,6 +159,51 @@ class Context:
         return [None if st[v] != L.FL_OK else (_pyramid_dicts(t[v * J:(v + 1) * J], f), tuple(int(x) for x in bb[4 * v:4 * v + 4]))
                 for v in range(n)]
 
+    def render_views(self, vertices, triangles, poses13, K, w, h, normals=None, colors=None, light=None, ambient=None,
+                     mem=L.FL_MEM_HOST, out=None):
+        """fl_render_views: views of a triangle mesh (vertices (n, 3) mm, triangles (m, 3) 0-based) at poses13 (k, 13),
+        K = (fx, fy, cx, cy), w x h.  normals (n, 3) / colors (n, 3) u8 BGR: optional per-vertex.  light / ambient: None =
+        the library's defaults (a headlight and FL_RENDER_AMBIENT).  mem=FL_MEM_HOST: returns numpy (bgr (k, h, w, 3),
+        depth (k, h, w) u16 mm, mask (k, h, w) u8, tri (k, h, w) int32).  FL_MEM_DEVICE: `out` is a dict of device tensors
+        under some of the keys bgr / depth / mask / tri (contiguous, those shapes and dtypes); the work is queued on this
+        context's stream and `out` is returned."""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        p = np.ascontiguousarray(poses13, np.float32).reshape(-1, 13)
+        nv = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        cv = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        for a in (nv, cv):
+            if a is not None and len(a) != len(v):
+                raise ValueError("normals / colors need one row per vertex")
+        k = L.Intrinsics(w, h, *[float(x) for x in K])
+        prm = None
+        if light is not None or ambient is not None:
+            prm = L.RenderParams((C.c_float * 3)(*(light if light is not None else (0.0, 0.0, 1.0))),
+                                 L.FL_RENDER_AMBIENT if ambient is None else float(ambient))
+        n = len(p)
+        if mem == L.FL_MEM_HOST:
+            res = dict(bgr=np.empty((n, h, w, 3), np.uint8), depth=np.empty((n, h, w), np.uint16), mask=np.empty((n, h, w), np.uint8),
+                       tri=np.empty((n, h, w), np.int32))
+            ptrs = [_ptr(res[key]) for key in ("bgr", "depth", "mask", "tri")]
+        else:
+            res = dict(out or {})
+            # the kernel writes n * h * w pixels into each output: refuse a tensor that cannot hold them, before the call
+            shapes = dict(bgr=((n, h, w, 3), 1), depth=((n, h, w), 2), mask=((n, h, w), 1), tri=((n, h, w), 4))
+            for key, tns in res.items():
+                if key not in shapes:
+                    raise ValueError(f"render_views: unknown output {key!r}")
+                shape, size = shapes[key]
+                if (tns.device.type != "cuda" or tns.device.index != self.device or not tns.is_contiguous()
+                        or tns.element_size() != size or tuple(tns.shape) != shape):
+                    raise ValueError(f"render_views: out[{key!r}] must be a contiguous tensor on cuda:{self.device} of shape {shape} "
+                                     f"with {size}-byte elements")
+            ptrs = [C.c_void_p(res[key].data_ptr()) if key in res else None for key in ("bgr", "depth", "mask", "tri")]
+        self.check(self.lib.fl_render_views(self.h, _ptr(v), None if nv is None else _ptr(nv), None if cv is None else _ptr(cv), len(v),
+                                            _ptr(t), len(t), n, _ptr(p), C.byref(k), None if prm is None else C.byref(prm), mem, *ptrs))
+        if mem == L.FL_MEM_HOST:
+            return res["bgr"], res["depth"], res["mask"], res["tri"]
+        return res
+
     def build_linear_memories(self, quantized, T):
         q = np.ascontiguousarray(quantized, np.uint8)
         h, w = q.shape
@@ -561,6 +606,22 @@ class MgGroup:
         if self.h:
             self.lib.fl_mg_destroy(self.h)
             self.h = None
+
+
+def view_sphere(subdivisions, distances_mm, n_inplane=1, inplane_deg=0.0, upper_hemisphere=False):
+    """fl_view_sphere: camera poses around the object origin, (n, 13) float32 in the bank's pose layout."""
+    lib = L.load()
+    d = np.ascontiguousarray(np.atleast_1d(distances_mm), np.float32)
+    n = C.c_int()
+    args = (int(subdivisions), int(bool(upper_hemisphere)), _ptr(d), len(d), int(n_inplane), float(inplane_deg))
+    rc = lib.fl_view_sphere(*args, None, 0, C.byref(n))
+    if rc != L.FL_OK:
+        raise FealessError(rc, "fl_view_sphere: invalid arguments")
+    out = np.zeros((n.value, 13), np.float32)
+    rc = lib.fl_view_sphere(*args, _ptr(out), n.value, C.byref(n))
+    if rc != L.FL_OK:
+        raise FealessError(rc, "fl_view_sphere")
+    return out
 
 
 def merge_topk_batch(gathered, n_ranks, n_frames, k, cap):

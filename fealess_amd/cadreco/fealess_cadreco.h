@@ -131,6 +131,19 @@ bool ReadPng16(const std::string &filename, std::vector<unsigned short> &pixels,
 // its mirror: 16-bit greyscale, non-interlaced, zlib (what imwrite gives a CV_16U image); false + err on failure
 bool WritePng16(const std::string &filename, const unsigned short *pixels, int w, int h, std::string *err);
 
+// Wavefront OBJ (not in the reference, whose CModelMesh::Load(file, model_scale) goes through a mesh library,
+// test/model_mesh.cpp): v (extra components ignored), vn, and f in the forms i, i/j, i//k, i/j/k with 1-based or negative
+// (relative) indices; polygons are fan-triangulated; every other record is ignored.  Coordinates are multiplied by
+// `scale`.  Normals are kept only when every face corner has one: then each distinct (position, normal) pair becomes one
+// vertex, in order of first use; otherwise `normals` is empty and the positions keep their order.
+struct Mesh {
+  std::vector<float> vertices, normals;   // 3 floats per vertex (normals: empty, or one per vertex)
+  std::vector<int> triangles;             // 3 vertex indices per triangle, 0-based
+};
+// SUCCESS; ERROR_OPEN_FILE_FAILED (unreadable); ERROR_INVALID_PARAM (index 0 or out of range, a non-numeric token, a
+// face of fewer than three corners, no face, a scale that is not finite and > 0)
+int ReadObj(const std::string &path, float scale, Mesh &out, std::string *err);
+
 }  // namespace fealess
 
 // Extensions of the MI355X build (not in the reference): batch entry point on the same object.
@@ -156,9 +169,36 @@ int CadRecoSetMultiHypothesis(CObjRecoCAD *handle, int k, float nms_dist_mm);
 // linemod_train names the PNGs by frame number while Recognition reads them by template id, so its directories are
 // only right when no view fails; here the PNGs follow the template ids.
 // Returns SUCCESS; ERROR_INVALID_PARAM (views of different sizes, a bad pointer or argument, no view yields a
-// template: nothing written); ERROR_OPEN_FILE_FAILED (a file cannot be written); ERROR_UNKNOW (no GPU, HIP error).
+// template: nothing written); ERROR_OPEN_FILE_FAILED (a file cannot be written: what the call created is removed again);
+// ERROR_UNKNOW (no GPU, HIP error).
 int CadRecoTrainViews(CObjRecoCAD *handle, const string &dir, const string &class_id, int n_views, const TImageU *bgr,
                       const TImageU16 *depth_mm, const TImageU *mask, const float *poses13, int levels, const int *T,
                       std::vector<int> *template_of_view);
+
+// The view sphere of fl_view_sphere (include/fealess_hip.h): icosphere points (subdivisions 0..6, optionally z >= 0 only)
+// x distances_mm x n_inplane angles over [-inplane_deg, +inplane_deg], every camera looking at the object origin.
+struct CadRecoViewSphere {
+  int subdivisions = 2;
+  int upper_hemisphere = 1;
+  std::vector<float> distances_mm;
+  int n_inplane = 1;
+  float inplane_deg = 0.f;
+};
+// Not in the reference (its CObjRecoCAD::Train(..., TScanPackage, ...) is a stub and linemod_train reads views another
+// tool rendered): train one class from a CAD mesh on the handle's GPU.  Reads the OBJ (fealess::ReadObj, `scale` as
+// CModelMesh::Load's model_scale), renders every view of the sphere with fl_render_views at 640x480 and
+// K = 608 / 608 / 320 / 240 -- initInternalMat (ICP/common.cpp:358), the K detection() back-projects a template's depth
+// with (ICP/detection.cpp:35-36): any other K would give Recognition's ICP a wrongly scaled model cloud -- and writes the
+// directory CadRecoTrainViews writes (the render's mask is the view's object mask; template_pose = the view-sphere pose;
+// depth/<template_id>.png = the render x 10, saturating; linemod_templates.yml last).  Views go through in slabs of 64,
+// so host memory stays bounded.  template_of_view (optional): per view of the sphere, its template id or -1.
+// Returns SUCCESS; ERROR_OPEN_FILE_FAILED (unreadable OBJ, or a file cannot be written); ERROR_INVALID_PARAM (malformed
+// OBJ, bad arguments, no view yields a template); ERROR_UNKNOW (no GPU, HIP error).  On every error nothing is left
+// behind: an error once writing has begun (a file that cannot be written, a HIP error while the depths are rendered again)
+// removes the files and directories the call created (depth PNGs it replaced in an existing directory stay replaced).
+// The host path: views are rendered to host memory and extracted from there (the facade holds no device memory); the
+// Python route Context.render_views(mem=FL_MEM_DEVICE) -> extract_template_batch keeps them in HBM.
+int CadRecoTrainMesh(CObjRecoCAD *handle, const string &dir, const string &class_id, const string &obj_path, float scale,
+                     const CadRecoViewSphere &views, int levels, const int *T, std::vector<int> *template_of_view);
 
 #endif  // FEALESS_CADRECO_H

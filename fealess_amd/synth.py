@@ -113,6 +113,93 @@ def render(w, h, R_obj, t_obj, seed=0, plane_z=1200.0, noise=True, background=Tr
     return depth, bgr, mask
 
 
+def icosphere(subdivisions):
+    """Unit icosphere: the icosahedron with a vertex at each pole, each triangle split in four per subdivision with the
+    edge midpoints pushed onto the sphere.  Returns vertices (10 * 4^s + 2, 3) float64 and triangles (20 * 4^s, 3) int32,
+    wound counter-clockwise seen from outside."""
+    zr, rr = 1 / np.sqrt(5.0), 2 / np.sqrt(5.0)
+    a = 2 * np.pi * np.arange(5) / 5
+    v = [(0.0, 0.0, 1.0)] + [(rr * np.cos(x), rr * np.sin(x), zr) for x in a] + \
+        [(rr * np.cos(x + np.pi / 5), rr * np.sin(x + np.pi / 5), -zr) for x in a] + [(0.0, 0.0, -1.0)]
+    f = []
+    for k in range(5):
+        b, c, d, e = 1 + k, 1 + (k + 1) % 5, 6 + k, 6 + (k + 1) % 5
+        f += [(0, b, c), (b, d, c), (c, d, e), (11, e, d)]
+    v = [np.array(p) for p in v]
+    for _ in range(subdivisions):
+        mid = {}
+
+        def m(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in mid:
+                q = (v[i] + v[j]) / 2
+                v.append(q / np.linalg.norm(q))
+                mid[key] = len(v) - 1
+            return mid[key]
+        nf = []
+        for a_, b_, c_ in f:
+            ab, bc, ca = m(a_, b_), m(b_, c_), m(c_, a_)
+            nf += [(a_, ab, ca), (ab, b_, bc), (ca, bc, c_), (ab, bc, ca)]
+        f = nf
+    return np.array(v, np.float64), np.array(f, np.int32)
+
+
+def box_mesh(centre, half_sizes, first_index=0):
+    """An axis-aligned box as 12 triangles on 24 vertices (four per face, carrying the face normal), wound
+    counter-clockwise seen from outside.  Returns (vertices, normals, triangles) as lists; indices start at first_index."""
+    bv, bn, bt = [], [], []
+    for ax in range(3):
+        for sgn in (-1.0, 1.0):
+            u, w = (ax + 1) % 3, (ax + 2) % 3
+            nrm = np.zeros(3)
+            nrm[ax] = sgn
+            quad = []
+            for du, dw in ((-1, -1), (1, -1), (1, 1), (-1, 1)):
+                q = np.zeros(3)
+                q[ax], q[u], q[w] = sgn, du, dw
+                quad.append(centre + q * half_sizes)
+            if sgn < 0:                     # counter-clockwise seen from outside
+                quad = quad[::-1]
+            k = first_index + len(bv)
+            bv += quad
+            bn += [nrm] * 4
+            bt += [(k, k + 1, k + 2), (k, k + 2, k + 3)]
+    return bv, bn, bt
+
+
+def object_mesh(subdivisions=4):
+    """The object render() ray-casts, as a triangle mesh: the sphere (centre (-35, 0, 0), radius 60) from a subdivided
+    icosahedron with analytic vertex normals, and the box (centre (45, 0, 10), half sizes (55, 35, 25)) as 12 triangles on
+    24 vertices carrying their face normals; colours are render()'s two albedos (BGR), without its stripes.
+    Returns dict(vertices (n, 3) f32 mm, normals (n, 3) f32, colors (n, 3) u8, triangles (m, 3) int32); 5132
+    triangles at the default subdivision."""
+    sv, sf = icosphere(subdivisions)
+    verts = [sv * 60.0 + np.array([-35.0, 0.0, 0.0])]
+    norms = [sv]
+    cols = [np.tile(np.array([200, 120, 60], np.uint8), (len(sv), 1))]
+    tris = [sf]
+    bv, bn, bt = box_mesh(np.array([45.0, 0.0, 10.0]), np.array([55.0, 35.0, 25.0]), len(sv))
+    verts.append(np.array(bv))
+    norms.append(np.array(bn))
+    cols.append(np.tile(np.array([70, 160, 210], np.uint8), (24, 1)))
+    tris.append(np.array(bt, np.int32))
+    return dict(vertices=np.concatenate(verts).astype(np.float32), normals=np.concatenate(norms).astype(np.float32),
+                colors=np.concatenate(cols), triangles=np.concatenate(tris).astype(np.int32))
+
+
+def write_obj(path, mesh, with_normals=True):
+    """Write a mesh dict of object_mesh() as a Wavefront OBJ (v, optionally vn, and f with 1-based indices)."""
+    with open(path, "w") as fh:
+        for p in mesh["vertices"]:
+            fh.write("v %.9g %.9g %.9g\n" % tuple(p))
+        if with_normals:
+            for p in mesh["normals"]:
+                fh.write("vn %.9g %.9g %.9g\n" % tuple(p))
+        for t in mesh["triangles"] + 1:
+            fh.write(("f %d//%d %d//%d %d//%d\n" % (t[0], t[0], t[1], t[1], t[2], t[2])) if with_normals else
+                     ("f %d %d %d\n" % tuple(t)))
+
+
 def render_clutter(w, h, poses, seed=0, fx=FX, fy=FY, cx=CX, cy=CY):
     """A cluttered frame: every (R, t) of `poses` is an instance of the object (nearest surface wins per pixel), in front of
     a NON-planar background (a tilted, rippled wall 1000 - 1350 mm away with box-shaped steps) that carries a high-contrast

@@ -236,6 +236,50 @@ int  fl_extract_template_pyramid(fl_context *ctx, const uint8_t *bgr, const uint
 int  fl_extract_template_batch(fl_context *ctx, int n_views, const uint8_t *const *bgr, const uint16_t *const *depth,
                                const uint8_t *const *mask, int w0, int h0, int levels, int mem, fl_template *templates,
                                fl_feature *features, int32_t *bb, int32_t *status);
+/* ---- training views of a triangle mesh (no counterpart in the reference, which reads views another tool rendered:
+ * test/linemod_train.cpp:93-144, 180-255) ------------------------------------------------------------------------------
+ * fl_render_views: a batched z-buffer rasteriser.  Inputs (host memory): vertices n_vertices * 3 f32 (object frame, mm);
+ * normals n_vertices * 3 f32 or NULL (NULL: the face normal); colors n_vertices * 3 u8 BGR or NULL (NULL: FL_RENDER_GREY);
+ * triangles n_triangles * 3 int32, 0-based; poses13 n_views * 13 f32 in the bank's layout (row-major [R|t] object -> camera
+ * in mm; the 13th float is ignored, so one pose list feeds the renderer and template_pose); K->width x K->height is the
+ * image size.  Pixel (u, v) is sampled along d = ((u - cx) * (1/fx), (v - cy) * (1/fy), 1) in float32, as depthTo3dNoMask
+ * back-projects (ICP/depth_to_3d.cpp:103-121).  A triangle covers a pixel when that ray hits it at z > 0 (no clipping);
+ * edge-on triangles cover nothing; a pixel exactly on an edge shared by two same-facing triangles belongs to one of them
+ * (a top-left style tie rule); the nearest hit wins and equal depths go to the lower triangle index.
+ * Outputs (each may be NULL, not all four), views back to back, row-major: bgr h*w*3 u8 = rint(albedo * clamp(|n.l|,
+ * ambient, 1)) with albedo and normal interpolated perspective-correctly (the normal then normalised), 0 where nothing is
+ * hit; depth h*w u16 = rint(z) in mm, saturated at 65535, 0 where nothing is hit; mask h*w u8 255 / 0; tri h*w int32, the
+ * visible triangle or -1.  The arithmetic is float32 in the order written at the top of fealess_amd/csrc/fl_render.hip:
+ * results do not depend on the schedule.  params: light direction in the camera frame (the way the light travels) and
+ * ambient; NULL = a headlight (0, 0, 1) and FL_RENDER_AMBIENT.  mem: where the outputs are (host: the call synchronises;
+ * device: queued on the context's stream).
+ * FL_ERR_INVALID, nothing written: n_triangles or n_views < 1, n_vertices < 3, counts above FL_RENDER_MAX_PRIMS, an index
+ * outside [0, n_vertices), a size <= 0 or above FL_RENDER_MAX_DIM, a non-finite or non-positive fx / fy (or non-finite
+ * cx / cy), ambient outside [0, 1], a zero (or non-finite) light vector, a non-finite vertex / normal / pose, all outputs NULL.
+ * Views go through in chunks of FL_RENDER_CHUNK_VIEWS views, fewer when w*h*views would pass FL_RENDER_CHUNK_PIXELS.  A
+ * chunk's device scratch (the context's, kept for later calls): 8 bytes of depth key per pixel and view, plus 10 per pixel
+ * and view staging for host outputs, plus the mesh -- max(2^25, w*h) * 18 bytes of images at most (604 MB up to 2^25
+ * pixels per view, 1.2 GB for one 8192 x 8192 view; 64 views at 640x480: 157 MB of keys, 354 MB with host outputs). */
+typedef struct { float light[3]; float ambient; } fl_render_params;
+#define FL_RENDER_GREY 180            /* albedo of every channel when colors is NULL */
+#define FL_RENDER_AMBIENT 0.2f        /* ambient when params is NULL */
+#define FL_RENDER_MAX_DIM 8192
+#define FL_RENDER_MAX_PRIMS (1 << 26)
+#define FL_RENDER_CHUNK_VIEWS 64
+#define FL_RENDER_CHUNK_PIXELS (1 << 25)
+int  fl_render_views(fl_context *ctx, const float *vertices, const float *normals, const uint8_t *colors, int n_vertices,
+                     const int32_t *triangles, int n_triangles, int n_views, const float *poses13, const fl_intrinsics *K,
+                     const fl_render_params *params, int mem, uint8_t *bgr, uint16_t *depth, uint8_t *mask, int32_t *tri);
+/* Camera poses on a view sphere, host only (like fl_nms).  Points: the icosahedron with a vertex at each pole, subdivided
+ * `subdivisions` times (0..6: 10 * 4^s + 2 points, edge midpoints pushed onto the sphere); upper_hemisphere keeps the
+ * points with object-frame z >= 0.  For each point s, distance d (distances_mm, each > 0) and in-plane angle: a camera at
+ * d * s looking at the object origin, so t = (0, 0, d) and poses13[12] = d.  Image-up (camera -y) is object +z projected
+ * onto the image plane; within 1e-5 of the poles (|s.z| > 1 - 1e-5) it is object +y.  In-plane angles: n_inplane angles
+ * about the optical axis evenly spread over [-inplane_deg, +inplane_deg] (0 .. 180; one angle means 0), applied as
+ * R = Rz(angle) * R0.  Order: point, then distance, then angle.  *n_views = the count; cap = 0 only queries it (poses13
+ * may be NULL), otherwise cap must hold every view.  FL_ERR_INVALID (nothing written) for any other argument. */
+int  fl_view_sphere(int subdivisions, int upper_hemisphere, const float *distances_mm, int n_distances, int n_inplane,
+                    float inplane_deg, float *poses13, int cap, int *n_views);
 /* cv::resize(src, dst, Size(dw, dh), 0, 0, INTER_LINEAR) as PrepareInputData applies it to frames
  * that are not 640 wide (obj_reco_lmicp.cpp:39-45, 229-249: TImage2Mat(..., true)); BGR8 and u16 */
 int  fl_resize_linear_bgr8(fl_context *ctx, const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh, int mem);
