@@ -6,12 +6,12 @@
  * only as the checker / the timed CPU baseline.  The product path (fealess_amd/csrc) never
  * links, loads or calls it and has no CPU fallback.
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures for this path
- * (SURVEY.md section 4), and it cannot be built here (every hot-path TU needs OpenCV 3.x,
- * which is absent from the image and un-vendored).  This oracle is therefore a careful
- * restatement from the reference's sources, each function citing the file:line it follows,
- * plus the published OpenCV 3.x algorithms for the un-vendored calls (GaussianBlur, Sobel,
- * fastAtan2, pyrDown, medianBlur, JacobiSVD, FLANN exact NN) -- stated explicitly where used.
+ * PARITY: the LINEMOD half (spread .. Detector::match on quantized images, quantizedNormals, hysteresisGradient,
+ * cropTemplates) is pinned bit for bit to the reference's own compiled code: oracle/ref builds the reference's linemod.cpp
+ * against a container-only opencv2/ stand-in (tests/test_reference_cpu.py, tests/golden/reference_linemod.npz).  UNPINNED
+ * remain the un-vendored OpenCV 3.x calls (GaussianBlur, Sobel, fastAtan2, pyrDown, resize, erode, distanceTransform,
+ * JacobiSVD, FLANN exact NN), restated here from their published algorithms -- stated explicitly where used -- and with
+ * them the whole ICP half.  Every function cites the file:line of the reference it follows.
  *
  * All paths are relative to /root/reference.
  */
@@ -49,7 +49,7 @@ typedef struct {
 /* ---- LINEMOD scan stages --------------------------------------------------------------- */
 void orc_similarity_lut(uint8_t lut[256]);                                  /* linemod.cpp:970  */
 void orc_spread(const uint8_t *src, int w, int h, int T, uint8_t *dst);      /* linemod.cpp:950  */
-void orc_response_maps(const uint8_t *spread, int w, int h, uint8_t *maps8); /* linemod.cpp:979  */
+int  orc_response_maps(const uint8_t *spread, int w, int h, uint8_t *maps8); /* linemod.cpp:979; 0 / -1 on assert */
 /* linearize (linemod.cpp:1060): out is T*T rows of (w/T)*(h/T) bytes. returns 0 / -1 on assert */
 int  orc_linearize(const uint8_t *map, int w, int h, int T, uint8_t *out);
 size_t orc_lm_label_stride(int w, int h, int T);  /* bytes per label incl. zero pad (see .c) */
@@ -85,6 +85,8 @@ void orc_quantized_normals(const uint16_t *depth, int w, int h, int distance_thr
 /* quantizedOrientations + hysteresisGradient (linemod.cpp:230-385); magnitude may be NULL */
 void orc_quantized_orientations(const uint8_t *bgr, int w, int h, float weak_threshold,
                                 uint8_t *dst, float *magnitude);
+/* hysteresisGradient alone (linemod.cpp:307-385): threshold is compared with magnitude as given */
+void orc_hysteresis_gradient(const float *magnitude, const float *angle, int w, int h, float threshold, uint8_t *dst);
 void orc_pyrdown_bgr(const uint8_t *src, int w, int h, uint8_t *dst);       /* cv::pyrDown 8UC3 */
 void orc_resize_nn_half(const uint8_t *src, int w, int h, uint8_t *dst);    /* linemod.cpp:731  */
 void orc_gaussian7_bgr(const uint8_t *src, int w, int h, uint8_t *dst);

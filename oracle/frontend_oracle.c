@@ -72,14 +72,49 @@ float orc_fast_atan2(float y, float x)
   return a;
 }
 
-/* quantizedOrientations (linemod.cpp:230-305) + hysteresisGradient (:307-385) */
+/* hysteresisGradient (linemod.cpp:307-385): magnitude and angle (degrees) are w*h floats, threshold is compared with
+ * magnitude as given (the caller squares it, :304). */
+void orc_hysteresis_gradient(const float *magnitude, const float *angle, int w, int h, float threshold, uint8_t *dst)
+{
+  size_t n = (size_t)w * h;
+  uint8_t *qu = (uint8_t *)malloc(n);
+  for (size_t i = 0; i < n; ++i) {
+    /* angle.convertTo(CV_8U, 16.0/360.0) (:314): float multiply, round half to even, saturate */
+    float v = angle[i] * (float)(16.0 / 360.0);
+    long q = lrintf(v);
+    qu[i] = (uint8_t)(q < 0 ? 0 : (q > 255 ? 255 : q));
+  }
+  /* zero the border, fold 16 -> 8 bins in the interior (:316-335) */
+  for (int x = 0; x < w; ++x) { qu[x] = 0; qu[(size_t)(h - 1) * w + x] = 0; }
+  for (int y = 0; y < h; ++y) { qu[(size_t)y * w] = 0; qu[(size_t)y * w + w - 1] = 0; }
+  for (int y = 1; y < h - 1; ++y)
+    for (int x = 1; x < w - 1; ++x) qu[(size_t)y * w + x] &= 7;
+
+  memset(dst, 0, n);
+  for (int r = 1; r < h - 1; ++r)
+    for (int c = 1; c < w - 1; ++c) {
+      if (magnitude[(size_t)r * w + c] > threshold) {
+        int hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx) hist[qu[(size_t)(r + dy) * w + c + dx] & 7]++;
+        /* NB: border cells of qu are 0 and interior cells are < 8, so "& 7" above is a no-op guard */
+        int max_votes = 0, index = -1;
+        for (int i = 0; i < 8; ++i)
+          if (max_votes < hist[i]) { index = i; max_votes = hist[i]; }
+        if (max_votes >= 5) dst[(size_t)r * w + c] = (uint8_t)(1 << index);
+      }
+    }
+  free(qu);
+}
+
+/* quantizedOrientations (linemod.cpp:230-305), ending in hysteresisGradient */
 void orc_quantized_orientations(const uint8_t *bgr, int w, int h, float weak_threshold,
                                 uint8_t *dst, float *magnitude_out)
 {
   size_t n = (size_t)w * h;
   uint8_t *sm = (uint8_t *)malloc(n * 3);
   float *mag = (float *)malloc(sizeof(float) * n);
-  uint8_t *qu = (uint8_t *)malloc(n);
+  float *ag = (float *)malloc(sizeof(float) * n);
   orc_gaussian7_bgr(bgr, w, h, sm);
 
   for (int y = 0; y < h; ++y) {
@@ -103,38 +138,14 @@ void orc_quantized_orientations(const uint8_t *bgr, int w, int h, float weak_thr
       else if (mags[1] >= mags[0] && mags[1] >= mags[2]) { best_dx = dxs[1]; best_dy = dys[1]; best_mag = mags[1]; }
       else { best_dx = dxs[2]; best_dy = dys[2]; best_mag = mags[2]; }
       mag[(size_t)y * w + x] = (float)best_mag;
-      float ang = orc_fast_atan2((float)best_dy, (float)best_dx);       /* phase(dx, dy, ag, true) */
-      /* angle.convertTo(CV_8U, 16.0/360.0) (:314): float multiply, round half to even, saturate */
-      float v = ang * (float)(16.0 / 360.0);
-      long q = lrintf(v);
-      qu[(size_t)y * w + x] = (uint8_t)(q < 0 ? 0 : (q > 255 ? 255 : q));
+      ag[(size_t)y * w + x] = orc_fast_atan2((float)best_dy, (float)best_dx);   /* phase(dx, dy, ag, true) */
     }
   }
-  /* zero the border, fold 16 -> 8 bins in the interior (:316-335) */
-  for (int x = 0; x < w; ++x) { qu[x] = 0; qu[(size_t)(h - 1) * w + x] = 0; }
-  for (int y = 0; y < h; ++y) { qu[(size_t)y * w] = 0; qu[(size_t)y * w + w - 1] = 0; }
-  for (int y = 1; y < h - 1; ++y)
-    for (int x = 1; x < w - 1; ++x) qu[(size_t)y * w + x] &= 7;
-
-  float threshold = weak_threshold * weak_threshold;                   /* :304 */
-  memset(dst, 0, n);
-  for (int r = 1; r < h - 1; ++r)
-    for (int c = 1; c < w - 1; ++c) {
-      if (mag[(size_t)r * w + c] > threshold) {
-        int hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int dy = -1; dy <= 1; ++dy)
-          for (int dx = -1; dx <= 1; ++dx) hist[qu[(size_t)(r + dy) * w + c + dx] & 7]++;
-        /* NB: border cells of qu are 0 and interior cells are < 8, so "& 7" above is a no-op guard */
-        int max_votes = 0, index = -1;
-        for (int i = 0; i < 8; ++i)
-          if (max_votes < hist[i]) { index = i; max_votes = hist[i]; }
-        if (max_votes >= 5) dst[(size_t)r * w + c] = (uint8_t)(1 << index);
-      }
-    }
+  orc_hysteresis_gradient(mag, ag, w, h, weak_threshold * weak_threshold, dst);  /* :304 */
   if (magnitude_out) memcpy(magnitude_out, mag, sizeof(float) * n);
   free(sm);
   free(mag);
-  free(qu);
+  free(ag);
 }
 
 /* cv::pyrDown(src, dst, Size(w/2, h/2)) on CV_8UC3 (linemod.cpp:441-444): separable

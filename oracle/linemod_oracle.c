@@ -1,7 +1,7 @@
 /*
  * linemod_oracle.c -- ORACLE (test infrastructure, not product): CPU restatement of the online
  * matching half of cup_linemod::Detector (linemod/linemod.cpp:882-1577 of /root/reference).
- * PARITY UNPINNED (see fealess_oracle.h).  Plain C99, scalar fallbacks of the reference's
+ * Pinned bit for bit to the reference's compiled code (oracle/ref, see fealess_oracle.h).  Plain C99, scalar fallbacks of the reference's
  * SSE loops (the #else branches are the semantic definition).
  */
 #include "fealess_oracle.h"
@@ -44,9 +44,10 @@ void orc_spread(const uint8_t *src, int w, int h, int T, uint8_t *dst)
       }
 }
 
-/* computeResponseMaps (linemod.cpp:979-1048, scalar branch :1034-1046). maps8 = 8 * w*h. */
-void orc_response_maps(const uint8_t *spread, int w, int h, uint8_t *maps8)
+/* computeResponseMaps (linemod.cpp:979-1048, scalar branch :1034-1046). maps8 = 8 * w*h. returns 0 / -1 on assert */
+int orc_response_maps(const uint8_t *spread, int w, int h, uint8_t *maps8)
 {
+  if ((w * h) % 16 != 0) return -1;                   /* CV_Assert :981 */
   uint8_t lut[256];
   orc_similarity_lut(lut);
   size_t n = (size_t)w * h;
@@ -58,6 +59,7 @@ void orc_response_maps(const uint8_t *spread, int w, int h, uint8_t *maps8)
       m[i] = a > b ? a : b;
     }
   }
+  return 0;
 }
 
 /* linearize (linemod.cpp:1060-1088) */

@@ -4,12 +4,14 @@
 The reference ships no golden vectors, known-answer tests or fixtures for this path and cannot
 be built or run here (OpenCV 3.x is absent), so these vectors pin the oracle *restatement*
 against regressions and give the HIP path a data-only target that travels to the GPU box --
-they do NOT pin the oracle to the reference ("parity unpinned").
+they do NOT pin the oracle to the reference; reference_linemod.npz (--reference, below) does that for the LINEMOD half.
 Run:  python tests/golden/make_golden.py     (inputs are seeded; output is deterministic)
 
 `--reference DIR` instead records what the CPU tests compare against the reference's own sources, as data, so that the
 tests need no copy of the reference: the two tables of DIR/linemod (reference_tables.npz) and the layout table and linked
-symbols of a CadReco caller compiled against DIR/CadReco's headers (cadreco_reference_abi.txt; needs build() first).
+symbols of a CadReco caller compiled against DIR/CadReco's headers (cadreco_reference_abi.txt; needs build() first), and
+the outputs of DIR/linemod/linemod.cpp, compiled against the stand-in of oracle/ref, on the cases of tests/reference_cases.py
+(reference_linemod.npz).
 """
 import os
 import re
@@ -122,6 +124,30 @@ def reference_fixtures(ref):
                 "(tests/golden/make_golden.py --reference):\n# its layout table, then the library symbols it links\n")
         f.write("\n".join(layout + ["--symbols"] + syms) + "\n")
     print("reference fixtures:", len(layout), "layout rows,", len(syms), "symbols")
+    reference_linemod_fixture(ref)
+
+
+def reference_linemod_fixture(ref):
+    """Outputs of the reference's COMPILED linemod.cpp (oracle/ref, built here from `ref`) on the case list of
+    tests/reference_cases.py -> reference_linemod.npz.  Data only: a sha256 digest of every output and of every case's inputs
+    (the inputs are regenerated from seeds), and the match lists in full.  Both builds must agree before anything is written."""
+    import reference_cases as RC
+    import reference_py as R
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle", "ref")], env=dict(os.environ, FEALESS_REFERENCE_ROOT=os.path.abspath(ref)))
+    scalar, simd = RC.ReferenceBackend(R.lib(False)), RC.ReferenceBackend(R.lib(True))
+    rec = {}
+    for g, (cases, fn) in RC.groups().items():
+        for name, c in cases:
+            out = fn(scalar, c)
+            if RC.simd_takes(g, c):
+                assert RC.same(out, fn(simd, c)) is None, name
+            for k, v in out.items():
+                rec[f"{g}/{name}/{k}"] = v if k == "__in__" else RC.digest(v)
+                if k.startswith("matches_"):
+                    rec[f"{g}/{name}/{k}/full"] = v
+    path = os.path.join(HERE, "reference_linemod.npz")
+    np.savez_compressed(path, **rec)
+    print("reference linemod fixture:", len(rec), "entries,", os.path.getsize(path) // 1024, "KiB")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """ctypes binding of oracle/liboracle.so -- the CPU restatement of the reference hot path.
 
 TEST INFRASTRUCTURE.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
-import this module; the product (fealess_amd) never does.
+import this module; the product (fealess_amd) never does.  Its LINEMOD half is compared bit for bit with the reference's own
+compiled code through tests/reference_py.py, the twin of this module.
 """
 import ctypes as C
 import os
@@ -86,7 +87,8 @@ def spread(q, T):
 def response_maps(s):
     s = np.ascontiguousarray(s, np.uint8)
     out = np.zeros((8,) + s.shape, np.uint8)
-    lib().orc_response_maps(_p(s), s.shape[1], s.shape[0], _p(out))
+    if lib().orc_response_maps(_p(s), s.shape[1], s.shape[0], _p(out)):
+        raise AssertionError("reference CV_Assert")
     return out
 
 
@@ -421,3 +423,50 @@ def median5(img):
     out = np.zeros_like(m)
     lib().orc_median5(_p(m), m.shape[1], m.shape[0], _p(out))
     return out
+
+
+# ---- stage entry points that tests/reference_py.py mirrors one to one ----------------------------------------------------
+def linearize(response_map, T):
+    """(T*T, (w/T)*(h/T)) linear memories of one response map; AssertionError where the reference's CV_Assert refuses."""
+    m = np.ascontiguousarray(response_map, np.uint8)
+    h, w = m.shape
+    out = np.zeros((T * T, (w // T) * (h // T)), np.uint8)
+    if lib().orc_linearize(_p(m), w, h, T, _p(out)):
+        raise AssertionError("reference CV_Assert")
+    return out
+
+
+def similarity(lm8, templ, feats, w, h, T):
+    """lm8: (8, stride) from build_linear_memories; templ: one TEMPL_DTYPE record; feats: FEAT_DTYPE array."""
+    t = np.ascontiguousarray(np.atleast_1d(templ), TEMPL_DTYPE)
+    f = np.ascontiguousarray(feats, FEAT_DTYPE)
+    out = np.zeros((h // T, w // T), np.uint8)
+    if lib().orc_similarity(_p(lm8), _p(t), _p(f), w, h, T, _p(out)):
+        raise AssertionError("reference CV_Assert")
+    return out
+
+
+def similarity_local(lm8, templ, feats, w, h, T, cx, cy):
+    t = np.ascontiguousarray(np.atleast_1d(templ), TEMPL_DTYPE)
+    f = np.ascontiguousarray(feats, FEAT_DTYPE)
+    out = np.zeros((16, 16), np.uint8)
+    if lib().orc_similarity_local(_p(lm8), _p(t), _p(f), w, h, T, cx, cy, _p(out)):
+        raise AssertionError("reference CV_Assert")
+    return out
+
+
+def hysteresis_gradient(magnitude, angle, threshold):
+    mg = np.ascontiguousarray(magnitude, np.float32)
+    ag = np.ascontiguousarray(angle, np.float32)
+    out = np.zeros(mg.shape, np.uint8)
+    lib().orc_hysteresis_gradient(_p(mg), _p(ag), mg.shape[1], mg.shape[0], C.c_float(threshold), _p(out))
+    return out
+
+
+def crop_templates(templates, feats):
+    """cropTemplates on TEMPL_DTYPE / FEAT_DTYPE arrays: returns (templates, features, (x, y, w, h)), inputs untouched."""
+    t = np.array(templates, TEMPL_DTYPE)
+    f = np.array(feats, FEAT_DTYPE)
+    bb = (C.c_int * 4)()
+    lib().orc_crop_templates(_p(t), len(t), _p(f), bb)
+    return t, f, tuple(bb)

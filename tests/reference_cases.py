@@ -1,0 +1,625 @@
+"""The fixed, seeded case list on which the oracle, the HIP kernels and the reference's compiled code (tests/reference_py.py)
+are compared bit for bit, and the two back ends that compute a case: the oracle and a build of the compiled reference.
+
+One list serves three users, so that they cannot drift apart: tests/golden/make_golden.py --reference records the reference's
+outputs on it (tests/golden/reference_linemod.npz), tests/test_reference_cpu.py compares the oracle with the live libraries
+and with that record, tests/test_gpu_reference.py does the same for the kernels.  Every input is regenerated from its seed;
+the record holds a digest of every input, so a numpy whose generators drifted fails loudly instead of comparing other data.
+
+Where an input could make the reference's behaviour UNDEFINED, the input is built so that it cannot, and check_* asserts
+that property of the input (never of an output):
+  * similarity / similarityLocal read `positions` / 15 * W + 16 bytes from a feature's address; that must stay inside the
+    label's T*T x W*H Mat (in_mat).  Reads that leave it are quirk Q2: cases whose name starts with "q2_" are DEFINED BY THE
+    STAND-IN'S ALLOCATOR (zeroed guard), UB IN THE REFERENCE, and kept in a group of their own;
+  * quantizedNormals indexes NORMAL_LUT[20][20][20] with int(n * 10 + 10) / int(nz * 20 + 20): a unit normal with nz == 0
+    (zero depth or a singular system with a non-zero gradient) or a component that rounds to 1.0f indexes past the table
+    (normals_safe; unsafe pixels are pushed behind distance_threshold when the case is built);
+  * the SSE2 spread stores 16 bytes aligned at every row start, so the SIMD build takes widths that are multiples of 16;
+  * hysteresisGradient's one OpenCV call, convertTo(CV_8U, 16/360), agrees between a float and a double product on every
+    float in [0, 360] except two, which the angle pools leave out (angles_unambiguous);
+"""
+import hashlib
+
+import numpy as np
+
+from fealess_amd import synth
+from fealess_amd.bank import FEATURE_DTYPE, MATCH_DTYPE, TEMPLATE_DTYPE, TemplateBank
+
+
+def digest(a):
+    a = np.ascontiguousarray(a)
+    hsh = hashlib.sha256(f"{a.dtype.str}{a.shape}".encode())
+    hsh.update(a.tobytes())
+    return np.frombuffer(hsh.digest(), np.uint8).copy()
+
+
+def lm_stride(w, h, T):
+    """orc_lm_label_stride / fl_lm_label_stride: bytes per label of the padded linear-memory layout."""
+    W, H = w // T, h // T
+    return (T * T * W * H + W * H + 16 * W + 64 + 63) & ~63
+
+
+# ---- spread / response maps / linearize ------------------------------------------------------------------------------
+DENSITIES = (0.0, 0.03, 0.9)
+
+
+def spread_cases():
+    """(name, w, h, T, density, seed): any size; w % T and h % T non-zero wherever the width allows it."""
+    out = []
+    sizes = [(64, 37), (80, 45), (150, 50), (320, 61), (640, 43), (67, 33)]
+    for T in (2, 4, 5, 8, 16):
+        for i, (w, h) in enumerate(sizes):
+            for k, dens in enumerate(DENSITIES):
+                if w >= 320 and k != (i + T) % 3:
+                    continue                                # the large ones take one density each, all three over the list
+                out.append((f"spread_{w}x{h}_T{T}_d{k}", w, h, T, dens, 1000 + 37 * T + 3 * i + k))
+    return out
+
+
+def spread_input(case):
+    _, w, h, T, dens, seed = case
+    return synth.random_quantized(np.random.default_rng(seed), w, h, dens)
+
+
+def linearize_cases():
+    """(name, w, h, T, density, seed); sizes divisible by T, and the refusal of 80x45 with T = 8 (CV_Assert :1062)."""
+    sizes = {2: [(64, 48), (150, 50), (320, 240)], 4: [(64, 48), (80, 48), (320, 60)], 5: [(80, 45), (150, 50), (320, 240), (640, 480)],
+             8: [(64, 48), (80, 48), (320, 240), (640, 480)], 16: [(64, 48), (80, 48), (320, 240), (640, 480)]}
+    out = []
+    for T, ss in sizes.items():
+        for i, (w, h) in enumerate(ss):
+            k = (i + T) % 3
+            out.append((f"lm_{w}x{h}_T{T}_d{k}", w, h, T, DENSITIES[k], 2000 + 41 * T + i))
+    out.append(("lm_refused_80x45_T8", 80, 45, 8, 0.9, 2999))
+    return out
+
+
+# ---- similarity / similarityLocal / addSimilarities ------------------------------------------------------------------
+def _templ(width, height, feats, level=0):
+    t = np.zeros(1, TEMPLATE_DTYPE)
+    t["width"], t["height"], t["pyramid_level"], t["feat_count"] = width, height, level, len(feats)
+    f = np.zeros(len(feats), FEATURE_DTYPE)
+    if len(feats):
+        a = np.asarray(feats, np.int32).reshape(-1, 3)
+        f["x"], f["y"], f["label"] = a[:, 0], a[:, 1], a[:, 2]
+    return t, f
+
+
+def _rand_feats(rng, n, width, height):
+    return np.stack([rng.integers(0, width, n), rng.integers(0, height, n), rng.integers(0, 8, n)], 1).astype(np.int32)
+
+
+def in_mat(feats_xy, w, h, T, extent):
+    """Per in-image feature: does a read of `extent` bytes from its linear-memory address stay inside the label's Mat?"""
+    W, H = w // T, h // T
+    ok = []
+    for x, y in feats_xy:
+        if x < 0 or y < 0 or x >= w or y >= h:
+            continue
+        start = ((y % T) * T + x % T) * W * H + (y // T) * W + x // T
+        ok.append(start + max(extent, 0) <= T * T * W * H)
+    return ok
+
+
+def positions(w, h, T, width, height):
+    """template_positions of similarity() (linemod.cpp:1141-1155), C division truncating toward zero."""
+    W, H = w // T, h // T
+    wf, hf = int((width - 1) / T) + 1, int((height - 1) / T) + 1
+    return (H - hf) * W + (W - wf) + 1
+
+
+def similarity_cases():
+    """(name, w, h, T, density, seed, width, height, feats).  Names starting with q2_ read past the label's Mat."""
+    out = []
+    geo = [(320, 240, 8), (160, 120, 4), (160, 80, 5), (64, 48, 2), (640, 480, 5), (320, 240, 16)]
+    for gi, (w, h, T) in enumerate(geo):
+        for n in (1, 8, 63):
+            rng = np.random.default_rng(3000 + 10 * gi + n)
+            width, height = int(rng.integers(8, w // 3)), int(rng.integers(8, h // 3))
+            out.append((f"sim_{w}x{h}_T{T}_n{n}", w, h, T, 0.5, 3100 + gi, width, height, _rand_feats(rng, n, width, height)))
+    rng = np.random.default_rng(3500)
+    f = _rand_feats(rng, 20, 40, 40)
+    f[::4, 0] += 400                                        # outside the image: skipped (:1179)
+    f[1::4, 1] += 300
+    f[2::4, 0] -= 50
+    out.append(("sim_features_outside", 320, 240, 8, 0.5, 3501, 40, 40, f))
+    f = _rand_feats(rng, 12, 100, 100)
+    out.append(("sim_template_wider_than_image", 160, 120, 8, 0.5, 3502, 400, 60, f))     # span_x < 0
+    out.append(("sim_template_larger_than_image", 160, 120, 8, 0.5, 3503, 400, 300, f))   # positions < 0
+    out.append(("sim_uncropped_template", 160, 120, 8, 0.5, 3504, -1, -1, f[:3] // 16))   # (-2) / 8 == 0 in C
+    out.append(("sim_zero_size_template", 160, 120, 8, 0.5, 3505, 0, 0, np.array([[0, 0, 3]], np.int32)))
+    # Q1: a feature in the last column of its template: the positions of one image row run on into the next row
+    out.append(("sim_row_wrap", 160, 120, 8, 0.9, 3506, 64, 32, np.array([[63, 0, 1], [63, 31, 2], [0, 31, 5], [62, 17, 7]], np.int32)))
+    out.append(("sim_empty_image", 160, 120, 8, 0.0, 3507, 40, 40, _rand_feats(rng, 8, 40, 40)))
+    # Q2 (own group): features beyond the template's declared size in the LAST grid row (x % T == y % T == T - 1)
+    out.append(("q2_sim_last_grid_row", 160, 120, 8, 0.9, 3508, 16, 16, np.array([[159, 119, 1], [151, 111, 6], [7, 7, 2], [3, 3, 0]], np.int32)))
+    out.append(("q2_sim_y_equals_height", 160, 120, 8, 0.9, 3509, 16, 16, np.array([[15, 119, 1], [159, 16, 2], [9, 16, 0]], np.int32)))
+    return out
+
+
+def check_similarity_case(case):
+    name, w, h, T, _, _, width, height, feats = case
+    ok = in_mat(feats[:, :2].tolist(), w, h, T, positions(w, h, T, width, height))
+    assert (not all(ok)) if name.startswith("q2_") else all(ok), name
+
+
+def local_cases():
+    """(name, w, h, T, density, seed, feats, cx, cy): similarityLocal windows at the four corners, at centres that the
+    caller would have clamped, and inside.  Features that would read past the label's Mat are moved one row up unless the
+    case is in the Q2 group."""
+    out = []
+    for gi, (w, h, T) in enumerate([(320, 240, 5), (160, 120, 8), (80, 60, 4)]):
+        rng = np.random.default_rng(4000 + gi)
+        centres = {"tl": (0, 0), "tr": (w - 1, 0), "bl": (0, h - 1), "br": (w - 1, h - 1), "mid": (w // 2 + 1, h // 2 - 2),
+                   "clamp_lo": (8 * T, 8 * T), "clamp_hi": (w - 40 - 8 * T, h - 40 - 8 * T), "neg": (-37, -5)}
+        for ci, (cn, (cx, cy)) in enumerate(centres.items()):
+            n = (1, 8, 63)[(ci + gi) % 3]
+            for q2 in (False, True):
+                f = _rand_feats(np.random.default_rng(4100 + 10 * gi + ci), n, 40, 40)
+                if cn not in ("bl", "br") and q2:
+                    continue
+                ox, oy = (int(cx / T) - 8) * T, (int(cy / T) - 8) * T
+                if q2:
+                    f[0] = (w - 1 - ox, h - 1 - oy, 3)      # lands on the image's last pixel: last grid row, last cell
+                else:
+                    for _ in range(h):                      # move offenders up until their 16 rows fit
+                        bad = [i for i in range(n) if in_mat([(f[i, 0] + ox, f[i, 1] + oy)], w, h, T, 15 * (w // T) + 16) == [False]]
+                        if not bad:
+                            break
+                        f[bad, 1] -= 1
+                out.append((("q2_" if q2 else "") + f"loc_{w}x{h}_T{T}_{cn}_n{n}", w, h, T, 0.6, 4200 + gi, f, cx, cy))
+        out.append((f"loc_{w}x{h}_T{T}_empty", w, h, T, 0.0, 4300 + gi, _rand_feats(rng, 8, 40, 40), w // 2, h // 2))   # Q4 input
+    return out
+
+
+def check_local_case(case):
+    name, w, h, T, _, _, f, cx, cy = case
+    ox, oy = (int(cx / T) - 8) * T, (int(cy / T) - 8) * T
+    ok = in_mat([(int(x) + ox, int(y) + oy) for x, y in f[:, :2]], w, h, T, 15 * (w // T) + 16)
+    assert (not all(ok)) if name.startswith("q2_") else all(ok), name
+
+
+# ---- Detector::match on quantized images -----------------------------------------------------------------------------
+def _pyramid(rng, w0, h0, levels, M, density):
+    return [synth.random_quantized(rng, w0 >> l, h0 >> l, density) for l in range(levels) for _ in range(M)]
+
+
+def _count_bank(class_id, levels, M, counts, w, h, seed, bbox=48):
+    """One pyramid per entry of counts, every template of it with that many features (inside its declared size)."""
+    rng = np.random.default_rng(seed)
+    b = TemplateBank(class_id, levels, M)
+    for n in counts:
+        ox, oy = int(rng.integers(0, w - bbox)), int(rng.integers(0, h - bbox))
+        tl = []
+        for l in range(levels):
+            for _ in range(M):
+                s = max(bbox >> l, 2)
+                tl.append(dict(width=s, height=s, offset_x=ox >> l, offset_y=oy >> l, pyramid_level=l, features=_rand_feats(rng, n, s, s)))
+        b.add_pyramid(tl)
+    return b
+
+
+def match_cases():
+    """name -> dict(qs, w0, h0, T, banks (insertion order), thresholds, class_ids, min_matches).  Built lazily: call it."""
+    out = {}
+
+    def add(name, w0, h0, T, M, seed, density, classes, n, thresholds, class_ids=(), planted=0.3, bbox=64, min_matches=1, qs=None):
+        levels = len(T)
+        if qs is None:
+            qs = _pyramid(np.random.default_rng(seed), w0, h0, levels, M, density)
+        banks = [synth.make_bank(c, n, levels, M, w0, h0, seed=seed + 7 * i + 1, qs=qs, planted_frac=planted, bbox=bbox)
+                 for i, c in enumerate(classes)]
+        out[name] = dict(qs=qs, w0=w0, h0=h0, T=T, M=M, banks=banks, thresholds=thresholds, class_ids=tuple(class_ids),
+                         min_matches=min_matches)
+
+    add("match_1level_2mod", 320, 240, [8], 2, 5001, 0.05, ["obj"], 24, [70.0])
+    add("match_2level_2mod", 320, 240, [5, 8], 2, 5002, 0.05, ["obj"], 24, [60.0, 75.0])
+    add("match_3level_2mod", 640, 480, [5, 8, 4], 2, 5003, 0.05, ["obj"], 24, [0.0, 60.0])
+    add("match_2level_1mod_classes_out_of_order", 320, 240, [4, 8], 1, 5004, 0.3, ["zeta", "alpha", "mid"], 12, [65.0], bbox=96)
+    add("match_class_filter_duplicate_and_unknown", 320, 240, [4, 8], 1, 5004, 0.3, ["zeta", "alpha", "mid"], 12, [65.0],
+        class_ids=("mid", "nope", "mid"), bbox=96)
+    add("match_class_filter_unknown_only", 320, 240, [4, 8], 1, 5004, 0.3, ["zeta", "alpha", "mid"], 12, [65.0], class_ids=("nope",),
+        bbox=96, min_matches=0)
+    add("match_thresholds", 320, 240, [5, 8], 2, 5005, 0.3, ["obj"], 6, [-100.0, -30.0, 0.0, 50.0, 75.0, 100.0], bbox=32, min_matches=0)
+    add("match_more_than_2048", 320, 240, [8], 1, 5006, 0.9, ["obj"], 6, [-100.0], min_matches=2049)
+    # Q4: nothing at the fine level, so every refinement window is all zero and the argmax stays (-1, -1)
+    qs = _pyramid(np.random.default_rng(5007), 160, 120, 2, 1, 0.5)
+    qs[0][:] = 0
+    add("match_q4_empty_fine_level", 160, 120, [4, 5], 1, 5007, 0.5, ["obj"], 4, [-100.0, 0.0], bbox=32, qs=qs)
+    # many ties in similarity and template id: one pyramid repeated, few features
+    b = _count_bank("obj", 1, 1, [2, 2, 2, 2], 160, 120, 5008, bbox=16)
+    qs = _pyramid(np.random.default_rng(5008), 160, 120, 1, 1, 0.7)
+    out["match_many_ties"] = dict(qs=qs, w0=160, h0=120, T=[8], M=1, banks=[b], thresholds=[50.0, 99.0], class_ids=(), min_matches=1)
+    return out
+
+
+def sorted_banks(case):
+    return sorted(case["banks"], key=lambda b: b.class_id)
+
+
+def matched_banks(case):
+    """The banks Detector::match visits, each once, in std::map order, and their indices in that order."""
+    srt = sorted_banks(case)
+    keep = [i for i, b in enumerate(srt) if not case["class_ids"] or b.class_id in case["class_ids"]]
+    return [srt[i] for i in keep], keep
+
+
+def canonical(raw):
+    """The project's canonical order (similarity descending, template id ascending, then class, y, x) and then std::unique
+    with Match::operator== (x, y, similarity, class; NOT template id): adjacent repeats only."""
+    m = np.array(raw, MATCH_DTYPE)
+    if len(m) == 0:
+        return m
+    m = m[np.lexsort((m["x"], m["y"], m["class_idx"], m["template_id"], -m["similarity"]))]
+    keep = np.ones(len(m), bool)
+    last = 0
+    for i in range(1, len(m)):
+        a, b = m[last], m[i]
+        if a["x"] == b["x"] and a["y"] == b["y"] and a["similarity"] == b["similarity"] and a["class_idx"] == b["class_idx"]:
+            keep[i] = False
+        else:
+            last = i
+    return m[keep]
+
+
+def matches_equal(a, b):
+    return (len(a) == len(b) and all(np.array_equal(a[k], b[k]) for k in ("x", "y", "class_idx", "template_id"))
+            and np.array_equal(a["similarity"].view(np.uint32), b["similarity"].view(np.uint32)))
+
+
+# ---- quantizedNormals ------------------------------------------------------------------------------------------------
+NORMAL_THRESHOLDS = [(2000, 50), (2000, 400), (2000, 401), (65535, 5000), (65535, 65535), (2000, 1), (2000, 0), (2000, -3)]
+
+
+def normals_unsafe(depth, dist_thr, diff_thr):
+    """Pixels where the reference would index NORMAL_LUT outside [0, 20)^3: |nz| of the unit normal below 1e-3 with a
+    non-zero normal (then int(nz * 20 + 20) can be 20, and nx or ny can round to 1.0f).  Exact integer sums in int64, as the
+    reference's `long`; the float part only as a margin, in double."""
+    d = depth.astype(np.int64)
+    h, w = d.shape
+    r = 5
+    if h <= 2 * r + 1 or w <= 2 * r + 1:
+        return np.zeros((h, w), bool)
+    c = d[r:h - r - 1, r:w - r - 1]
+    A0 = np.zeros_like(c); A1 = np.zeros_like(c); A3 = np.zeros_like(c); b0 = np.zeros_like(c); b1 = np.zeros_like(c)
+    for j in (-r, 0, r):
+        for i in (-r, 0, r):
+            if i == 0 and j == 0:
+                continue
+            delta = d[r + j:h - r - 1 + j, r + i:w - r - 1 + i] - c
+            f = (np.abs(delta) < diff_thr).astype(np.int64)
+            A0 += f * i * i; A1 += f * i * j; A3 += f * j * j; b0 += f * i * delta; b1 += f * j * delta
+    det = A0 * A3 - A1 * A1
+    nx, ny, nz = (617 * (A3 * b0 - A1 * b1)).astype(np.float64), (617 * (-A1 * b0 + A0 * b1)).astype(np.float64), (-det * c).astype(np.float64)
+    norm = np.sqrt(nx * nx + ny * ny + nz * nz)
+    bad = (c < dist_thr) & (norm > 0) & (np.abs(nz) < 1e-3 * norm)
+    out = np.zeros((h, w), bool)
+    out[r:h - r - 1, r:w - r - 1] = bad
+    return out
+
+
+def _normals_base(kind, w, h, rng, dist_thr):
+    yy, xx = np.mgrid[0:h, 0:w]
+    if kind == "plane":
+        d = 600 + 1.7 * xx + 0.9 * yy + rng.integers(0, 3, (h, w))
+    elif kind == "steps":
+        d = 500 + 300 * rng.integers(0, 4, (h // 8 + 1, w // 8 + 1)).repeat(8, 0).repeat(8, 1)[:h, :w] + rng.integers(0, 20, (h, w))
+    elif kind == "zeros":
+        d = 700 + 0.5 * xx + 2.0 * yy + rng.integers(0, 4, (h, w))
+        d[rng.random((h, w)) < 0.03] = 0
+        d[h // 3:h // 3 + 7, w // 4:w // 4 + 9] = 0
+    elif kind == "around_threshold":
+        d = min(dist_thr, 65534) + rng.integers(-2, 2, (h, w)) + (xx // 6) % 3 - 1
+    elif kind == "rough":
+        d = rng.integers(0, 65536, (h, w))
+    elif kind == "deep":
+        d = 65535 - 3 * xx - 2 * yy - rng.integers(0, 30, (h, w))
+    return np.clip(d, 0, 65535).astype(np.uint16)
+
+
+def normals_cases():
+    """(name, kind, w, h, dist_thr, diff_thr, seed)."""
+    out = []
+    kinds = ["plane", "steps", "zeros", "around_threshold", "rough", "deep"]
+    for si, (w, h) in enumerate([(23, 17), (64, 48), (97, 61)]):
+        for ki, kind in enumerate(kinds):
+            for ti, (dt, ft) in enumerate(NORMAL_THRESHOLDS):
+                if kind == "deep" and dt < 65535:
+                    continue
+                if (si, ki) != (1, 2) and kind not in ("rough", "deep") and ti not in (0, (si + ki) % len(NORMAL_THRESHOLDS)):
+                    continue                                # every pair on zeros at 64x48, on rough and on deep; two elsewhere
+                out.append((f"normals_{kind}_{w}x{h}_{dt}_{ft}", kind, w, h, dt, ft, 6000 + 100 * si + 10 * ki + ti))
+    out.append(("normals_steps_640x480_2000_50", "steps", 640, 480, 2000, 50, 6900))
+    out.append(("normals_rough_640x480_65535_5000", "rough", 640, 480, 65535, 5000, 6901))
+    return out
+
+
+def normals_input(case):
+    _, kind, w, h, dt, ft, seed = case
+    d = _normals_base(kind, w, h, np.random.default_rng(seed), dt)
+    for _ in range(64):                                     # push unsafe pixels behind distance_threshold (their neighbours change: repeat)
+        bad = normals_unsafe(d, dt, ft)
+        if not bad.any():
+            return d
+        d[bad] = 65535
+    raise AssertionError(case[0])
+
+
+# ---- hysteresisGradient ----------------------------------------------------------------------------------------------
+AMBIGUOUS_ANGLES = np.array([123.749992, 213.749985], np.float32)     # float and double products round differently: left out
+
+
+def angles_unambiguous(angle):
+    a = np.asarray(angle, np.float32)
+    return bool(np.array_equal(np.rint(a.astype(np.float64) * (16.0 / 360.0)), np.rint(a * np.float32(16.0 / 360.0)).astype(np.float64)))
+
+
+def edge_angles():
+    """The 16 bin edges 11.25 + 22.5 k, their float neighbours, 348.75 .. 360 and 0: without the two ambiguous floats."""
+    e = (11.25 + 22.5 * np.arange(16)).astype(np.float32)
+    pool = np.concatenate([e, np.nextafter(e, np.float32(0)), np.nextafter(e, np.float32(400)),
+                           np.array([0.0, 348.75, 350.0, 355.5, 359.99997, 360.0], np.float32),
+                           (22.5 * np.arange(17)).astype(np.float32)])
+    return pool[~np.isin(pool, AMBIGUOUS_ANGLES)]
+
+
+def hysteresis_cases():
+    return [(f"hyst_{kind}_{w}x{h}", kind, w, h, 7000 + 10 * i + j) for i, (w, h) in enumerate([(23, 17), (64, 48), (97, 61), (3, 3), (640, 480)])
+            for j, kind in enumerate(["random", "blocks", "edges"])]
+
+
+def hysteresis_input(case):
+    """(magnitude, angle, threshold): magnitudes are integers as the reference's (sums of two squares), many equal to the
+    threshold; `blocks` and `edges` keep 4x4 blocks in one bin so that the 5-of-9 vote passes."""
+    _, kind, w, h, seed = case
+    rng = np.random.default_rng(seed)
+    thr = 100.0
+    mag = rng.choice(np.array([0, 99, 100, 101, 5000], np.float32), (h, w))
+    if kind == "random":
+        ang = rng.uniform(0, 360, (h, w)).astype(np.float32)
+    else:
+        pool = edge_angles() if kind == "edges" else (22.5 * rng.integers(0, 16, 64) + rng.uniform(-11, 11, 64)).astype(np.float32) % np.float32(360)
+        blocks = rng.integers(0, len(pool), (h // 4 + 1, w // 4 + 1)).repeat(4, 0).repeat(4, 1)[:h, :w]
+        noise = rng.random((h, w)) < 0.15
+        blocks[noise] = rng.integers(0, len(pool), int(noise.sum()))
+        ang = pool[blocks]
+    ang = np.ascontiguousarray(ang, np.float32)
+    ang[np.isin(ang, AMBIGUOUS_ANGLES)] = 0                 # a uniform draw could hit one of the two; the pools never hold them
+    return mag, np.ascontiguousarray(ang, np.float32), thr
+
+
+# ---- cropTemplates -------------------------------------------------------------------------
+def crop_cases():
+    """(name, templates, features): un-cropped pyramids (absolute features per level, offsets that differ per level)."""
+    out = []
+    for i, (levels, M, x0, y0) in enumerate([(1, 1, 10, 20), (2, 2, 101, 57), (3, 2, 33, 64), (2, 1, 0, 1), (3, 1, 255, 129)]):
+        rng = np.random.default_rng(9000 + i)
+        t = np.zeros(levels * M, TEMPLATE_DTYPE)
+        fs = []
+        for k in range(levels * M):
+            lv = k // M
+            n = int(rng.integers(1, 20))
+            f = np.zeros(n, FEATURE_DTYPE)
+            f["x"] = (x0 >> lv) + rng.integers(0, max(1, 90 >> lv), n)
+            f["y"] = (y0 >> lv) + rng.integers(0, max(1, 70 >> lv), n)
+            f["label"] = rng.integers(0, 8, n)
+            t[k]["width"] = t[k]["height"] = -1
+            t[k]["pyramid_level"], t[k]["feat_begin"], t[k]["feat_count"] = lv, sum(len(a) for a in fs), n
+            fs.append(f)
+        out.append((f"crop_L{levels}_M{M}_{x0}_{y0}", t, np.concatenate(fs)))
+    return out
+
+
+def check_crop_case(case):
+    _, t, f = case
+    assert len(f) > 0 and f["x"].min() >= 0 and f["y"].min() >= 0        # << of a negative int, min over nothing: undefined
+
+
+# ---- the two back ends ---------------------------------------------------------------------------------------------------
+class OracleBackend:
+    """oracle_py under the method names of reference_py.Ref."""
+
+    def __init__(self, O):
+        self.O = O
+        for k in ("spread", "response_maps", "linearize", "similarity", "similarity_local", "quantized_normals", "hysteresis_gradient",
+                  "crop_templates"):
+            setattr(self, k, getattr(O, k))
+
+    def build_linear_memories(self, q, T, stride):
+        out = self.O.build_linear_memories(q, T)
+        assert out.shape[1] == stride
+        return out
+
+    def total_similarity(self, lms, templs, w, h, T):
+        b = TemplateBank("obj", 1, len(templs))
+        b.add_pyramid([dict(width=int(t["width"][0]), height=int(t["height"][0]), offset_x=0, offset_y=0, pyramid_level=0,
+                            features=np.stack([f["x"], f["y"], f["label"]], 1)) for t, f in templs])
+        return self.O.total_similarity(lms, b, 0, w, h, T)
+
+    def match(self, case, threshold):
+        banks, keep = matched_banks(case)
+        if not banks:
+            return np.zeros(0, MATCH_DTYPE)
+        m, n = self.O.match_quantized(case["qs"], case["w0"], case["h0"], case["T"], banks, threshold)
+        assert n == len(m)
+        m = m.copy()
+        m["class_idx"] = np.array(keep, np.int32)[m["class_idx"]]
+        return m
+
+
+class ReferenceBackend:
+    """One build of the compiled reference (reference_py.Ref)."""
+
+    def __init__(self, R):
+        self.R = R
+        for k in ("spread", "response_maps", "linearize", "build_linear_memories", "similarity", "similarity_local", "quantized_normals",
+                  "hysteresis_gradient", "crop_templates"):
+            setattr(self, k, getattr(R, k))
+
+    def total_similarity(self, lms, templs, w, h, T):
+        return self.R.add_similarities([self.R.similarity(lm, t, f, w, h, T) for lm, (t, f) in zip(lms, templs)])
+
+    def match_lists(self, case, threshold):
+        """(final, raw) with class_idx mapped to the index in sorted class order."""
+        fin, raw = self.R.match_quantized(case["qs"], case["w0"], case["h0"], case["T"], case["banks"], threshold, case["class_ids"])
+        srt = [b.class_id for b in sorted_banks(case)]
+        remap = np.array([srt.index(b.class_id) for b in case["banks"]], np.int32)
+        fin, raw = fin.copy(), raw.copy()
+        fin["class_idx"], raw["class_idx"] = remap[fin["class_idx"]], remap[raw["class_idx"]]
+        return fin, raw
+
+    def match(self, case, threshold):
+        return canonical(self.match_lists(case, threshold)[1])
+
+
+# ---- one case on one back end ------------------------------------------------------------------------------------------
+def _with_inputs(out, *ins):
+    out["__in__"] = digest(np.concatenate([digest(a) for a in ins]))
+    return out
+
+
+def _refusable(out, key, fn):
+    try:
+        out[key] = fn()
+    except AssertionError:                                  # the reference's CV_Assert: both sides must refuse
+        out[key + "_refused"] = np.ones(1, np.uint8)
+
+
+def compute_spread(B, case):
+    q = spread_input(case)
+    out = {"spread": B.spread(q, case[3])}
+    _refusable(out, "maps", lambda: B.response_maps(out["spread"]))
+    return _with_inputs(out, q)
+
+
+def compute_lut(B, case=None):
+    s = np.arange(256, dtype=np.uint8).reshape(16, 16)      # all 256 spread bytes
+    return _with_inputs({"maps": B.response_maps(s)}, s)
+
+
+def linearize_input(case):
+    _, w, h, T, dens, seed = case
+    rng = np.random.default_rng(seed)
+    return synth.random_quantized(rng, w, h, dens), rng.integers(0, 5, (h, w)).astype(np.uint8)
+
+
+def compute_linearize(B, case):
+    _, w, h, T, dens, seed = case
+    q, m = linearize_input(case)
+    out = {}
+    _refusable(out, "lin", lambda: B.linearize(m, T))
+    _refusable(out, "lm", lambda: B.build_linear_memories(q, T, lm_stride(w, h, T)))
+    return _with_inputs(out, q, m)
+
+
+def _sim_lm(B, w, h, T, dens, seed):
+    q = synth.random_quantized(np.random.default_rng(seed), w, h, dens)
+    return q, B.build_linear_memories(q, T, lm_stride(w, h, T))
+
+
+def compute_similarity(B, case):
+    name, w, h, T, dens, seed, width, height, feats = case
+    q, lm = _sim_lm(B, w, h, T, dens, seed)
+    t, f = _templ(width, height, feats)
+    return _with_inputs({"sim": B.similarity(lm, t, f, w, h, T)}, q, t, f)
+
+
+def compute_local(B, case):
+    name, w, h, T, dens, seed, feats, cx, cy = case
+    q, lm = _sim_lm(B, w, h, T, dens, seed)
+    t, f = _templ(40, 40, feats)
+    return _with_inputs({"loc": B.similarity_local(lm, t, f, w, h, T, cx, cy)}, q, t, f, np.array([cx, cy]))
+
+
+def total_cases():
+    """(name, first, second): two non-Q2 similarity cases of one geometry; totals with one and with two modalities."""
+    cs = [c for c in similarity_cases() if c[0].startswith("sim_") and c[0].split("_n")[-1] in ("1", "8", "63")]
+    return [(f"total_{a[0][4:]}_{b[0].split('_')[-1]}", a, b) for a, b in zip(cs, cs[1:]) if a[1:4] == b[1:4]]
+
+
+def compute_total(B, case):
+    _, a, b = case
+    w, h, T = a[1:4]
+    qa, lma = _sim_lm(B, w, h, T, a[4], a[5])
+    qb, lmb = _sim_lm(B, w, h, T, 0.3, b[5] + 50)
+    ta, tb = _templ(a[6], a[7], a[8]), _templ(b[6], b[7], b[8])
+    out = {"one": B.total_similarity([lma], [ta], w, h, T), "two": B.total_similarity([lma, lmb], [ta, tb], w, h, T)}
+    return _with_inputs(out, qa, qb, *ta, *tb)
+
+
+def coarse_templates(bank, p):
+    """[(template record, its features)] of pyramid p at the coarsest level, one per modality."""
+    t, f, _ = bank.arrays()
+    L, M = bank.levels, bank.modalities
+    out = []
+    for m in range(M):
+        hdr = t[(p * L + L - 1) * M + m:(p * L + L - 1) * M + m + 1].copy()
+        fr = f[int(hdr["feat_begin"][0]):int(hdr["feat_begin"][0]) + int(hdr["feat_count"][0])].copy()
+        hdr["feat_begin"] = 0
+        out.append((hdr, fr))
+    return out
+
+
+def compute_match(B, case):
+    """The canonical match list per threshold, and the u16 total similarity map of every pyramid at the coarsest level
+    (classes in std::map order)."""
+    L, M, T = len(case["T"]), case["M"], case["T"][-1]
+    wl, hl = case["w0"] >> (L - 1), case["h0"] >> (L - 1)
+    out = {f"matches_{thr:g}": B.match(case, thr) for thr in case["thresholds"]}
+    lms = [B.build_linear_memories(case["qs"][(L - 1) * M + m], T, lm_stride(wl, hl, T)) for m in range(M)]
+    out["sims"] = np.stack([B.total_similarity(lms, coarse_templates(b, p), wl, hl, T) for b in sorted_banks(case) for p in range(b.n_pyramids)])
+    ins = list(case["qs"])
+    for b in case["banks"]:
+        ins += list(b.arrays()[:2])
+    return _with_inputs(out, *ins)
+
+
+def compute_normals(B, case):
+    d = normals_input(case)
+    return _with_inputs({"qn": B.quantized_normals(d, case[4], case[5])}, d)
+
+
+def compute_hysteresis(B, case):
+    mag, ang, thr = hysteresis_input(case)
+    return _with_inputs({"q": B.hysteresis_gradient(mag, ang, thr)}, mag, ang)
+
+
+def compute_crop(B, case):
+    _, t, f = case
+    to, fo, bb = B.crop_templates(t, f)
+    return _with_inputs({"templates": to, "features": fo, "bb": np.array(bb, np.int32)}, t, f)
+
+
+def groups():
+    """group -> (list of (name, case), compute).  The whole case list, in one place."""
+    mc = match_cases()
+    return {
+        "spread": ([(c[0], c) for c in spread_cases()], compute_spread),
+        "lut": ([("lut_all_256_bytes", None)], compute_lut),
+        "linearize": ([(c[0], c) for c in linearize_cases()], compute_linearize),
+        "similarity": ([(c[0], c) for c in similarity_cases()], compute_similarity),
+        "local": ([(c[0], c) for c in local_cases()], compute_local),
+        "total": ([(c[0], c) for c in total_cases()], compute_total),
+        "match": ([(k, v) for k, v in mc.items()], compute_match),
+        "normals": ([(c[0], c) for c in normals_cases()], compute_normals),
+        "hysteresis": ([(c[0], c) for c in hysteresis_cases()], compute_hysteresis),
+        "crop": ([(c[0], c) for c in crop_cases()], compute_crop),
+    }
+
+
+def simd_takes(group, case):
+    """The SIMD build's spread needs w % 16 == 0 (aligned 16-byte stores at every row start): decided by the case alone."""
+    if group in ("spread", "linearize"):
+        return case[1] % 16 == 0
+    return True
+
+
+def same(a, b):
+    """Two output dicts agree bit for bit; returns the first key that does not, or None."""
+    if sorted(a) != sorted(b):
+        return f"keys {sorted(a)} != {sorted(b)}"
+    for k in a:
+        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
+        if x.dtype != y.dtype or x.shape != y.shape or x.tobytes() != y.tobytes():
+            return k
+    return None

@@ -1,0 +1,160 @@
+"""GPU parity with the REFERENCE ITSELF, bit for bit: the HIP kernels against the outputs recorded from the reference's compiled
+linemod.cpp (tests/golden/reference_linemod.npz; always run) and against the compiled reference live (oracle/_ref/, which
+travels with the tree; tests/reference_py.require decides what its absence means), on seeded cases placed on the kernels'
+dispatch edges as fl_linemod.hip states them.  Neither part reads a reference source tree.
+"""
+import numpy as np
+import pytest
+
+import reference_cases as RC
+import reference_py as R
+from fealess_amd import api, synth
+from util import golden
+
+pytestmark = pytest.mark.gpu
+GROUPS = RC.groups()
+
+
+def _detector(ctx, case):
+    det = api.Detector(ctx, case["M"], case["T"])
+    for b in case["banks"]:
+        det.add_class(b)
+    det.finalize(case["w0"], case["h0"])
+    det.set_class_filter(case["class_ids"])
+    return det
+
+
+# ---- against the recorded reference ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [n for n, c in GROUPS["linearize"][0]])
+def test_linear_memories_equal_recorded_reference(ctx, name):
+    """The reference's CV_Asserts (rows * cols % 16, linemod.cpp:981; rows, cols % T, :1062-1063) are part of the record:
+    where it refused, the kernel's entry point must refuse too."""
+    case = dict(GROUPS["linearize"][0])[name]
+    rec = golden("reference_linemod.npz")
+    q, _ = RC.linearize_input(case)
+    if f"linearize/{name}/lm_refused" in rec.files:
+        with pytest.raises(api.FealessError) as e:
+            ctx.build_linear_memories(q, case[3])
+        assert e.value.code == -3
+        return
+    got = ctx.build_linear_memories(q, case[3])
+    assert np.array_equal(RC.digest(got), rec[f"linearize/{name}/lm"])
+
+
+@pytest.mark.parametrize("name", list(RC.match_cases()))
+def test_match_and_similarity_maps_equal_recorded_reference(ctx, name):
+    case = RC.match_cases()[name]
+    rec = golden("reference_linemod.npz")
+    det = _detector(ctx, case)
+    for thr in case["thresholds"]:
+        exp = rec[f"match/{name}/matches_{thr:g}/full"]
+        got, n = det.match_quantized(case["qs"], thr, cap=1 << 18)
+        assert n == len(exp), (thr, n, len(exp))
+        assert RC.matches_equal(got, exp), thr
+    if len(case["banks"]) == 1:        # fl_similarity_maps indexes the pyramids of the whole detector; one class: no ordering to assume
+        assert np.array_equal(RC.digest(det.similarity_maps(0, case["banks"][0].n_pyramids)), rec[f"match/{name}/sims"])
+    det.close()
+
+
+@pytest.mark.parametrize("name", [c[0] for c in RC.normals_cases()])
+def test_quantized_normals_equal_recorded_reference(ctx, name):
+    case = dict(GROUPS["normals"][0])[name]
+    rec = golden("reference_linemod.npz")
+    got = ctx.quantized_normals(RC.normals_input(case), case[4], case[5])
+    assert np.array_equal(RC.digest(got), rec[f"normals/{name}/qn"])
+
+
+# ---- against the compiled reference, live, on the dispatch edges -------------------------------------------------------
+# fl_launch_build_lm takes k_build_lm when w % 4 == 0 and W % 4 == 0 and 2 <= T <= 8 and the strip of k*T rows fits:
+# lds = 2 * (k*T + T-1) * (w+16) + 2048, k from 6 down while lds > 60 KiB, refused above 64 KiB even at k = 1.
+LM_EDGES = [(150, 80, 5),      # w % 4 != 0                                   -> generic
+            (80, 48, 8),       # w % 4 == 0, W = 10: W % 4 != 0               -> generic
+            (96, 48, 8),       # W = 12                                       -> k_build_lm, k = 6
+            (64, 48, 16),      # T > 8                                        -> generic
+            (64, 48, 2),       # T = 2, the lower bound                       -> k_build_lm
+            (512, 64, 8),      # 2*55*528+2048 = 60128 <= 61440: still k = 6
+            (544, 64, 8),      # 2*55*560+2048 = 63648 > 61440: k drops to 5
+            (2080, 64, 8),     # only k = 1 fits: 2*15*2096+2048 = 64928 <= 65536
+            (2560, 64, 8)]     # 2*15*2576+2048 = 79328 > 64 KiB: not even k = 1 -> generic although w % 4 == W % 4 == 0
+
+
+@pytest.mark.parametrize("w,h,T", LM_EDGES)
+@pytest.mark.parametrize("density", [0.05, 0.9])
+def test_linear_memories_equal_live_reference_on_dispatch_edges(ctx, w, h, T, density):
+    ref = R.require(False)
+    q = synth.random_quantized(np.random.default_rng(w * 31 + T), w, h, density)
+    got = ctx.build_linear_memories(q, T)
+    assert np.array_equal(got, ref.build_linear_memories(q, T, got.shape[1]))
+
+
+def _edge_case(w0, h0, T, M, counts, seed, density, bbox):
+    levels = len(T)
+    qs = RC._pyramid(np.random.default_rng(seed), w0, h0, levels, M, density)
+    planted = synth.make_bank("obj", 6, levels, M, w0, h0, seed=seed + 1, qs=qs, planted_frac=0.5, bbox=bbox)
+    counted = RC._count_bank("cnt", levels, M, counts, w0, h0, seed + 2, bbox=bbox)
+    return dict(qs=qs, w0=w0, h0=h0, T=T, M=M, banks=[planted, counted], class_ids=(), thresholds=[])
+
+
+# k_scan chunks the W*H positions by 1024 and pads the features to groups of 8; k_refine clamps its 16x16 window at the
+# borders; k_spread takes strips of k = 4 rows of T while 2*(k*T+T-1)*(w+16) <= 60 KiB (w = 1280, T = 5: k drops to 3) and
+# needs w % 4 == 0 (650: generic, and 325 % 4 != 0 sends level 1 to the generic linear-memory kernel)
+SCAN_EDGES = [("wh_992", 256, 248, [8], 1), ("wh_1024", 256, 256, [8], 1), ("wh_1056", 256, 264, [8], 2),
+              ("refine_T5_T8", 320, 240, [5, 8], 2), ("refine_T4_T8", 320, 240, [4, 8], 1), ("three_levels", 640, 480, [5, 8, 4], 2),
+              ("spread_k_drops_1280", 1280, 720, [5, 8], 1), ("spread_generic_650", 650, 480, [5, 5], 1)]
+
+
+@pytest.mark.parametrize("name,w0,h0,T,M", SCAN_EDGES)
+def test_match_equals_live_reference_on_scan_and_refine_edges(ctx, name, w0, h0, T, M):
+    ref = RC.ReferenceBackend(R.require(False))
+    case = _edge_case(w0, h0, T, M, [1, 7, 8, 9, 63], 11000 + w0 + h0, 0.25, 48)
+    det = _detector(ctx, case)
+    seen = 0
+    for thr in (-100.0, 40.0, 70.0):
+        exp = ref.match(case, thr)
+        for prune, mid in ((1, 0), (1, 0xFF), (0, 0)):
+            ctx.set_option("scan_prune", prune)
+            ctx.set_option("scan_prune_mid", mid)
+            try:
+                got, n = det.match_quantized(case["qs"], thr, cap=1 << 20)
+            finally:
+                ctx.set_option("scan_prune", 1)
+                ctx.set_option("scan_prune_mid", 0)
+            assert n == len(exp), (thr, prune, mid, n, len(exp))
+            assert RC.matches_equal(got, exp), (thr, prune, mid)
+        seen += len(exp)
+    assert seen > 0
+    det.close()
+
+
+@pytest.mark.parametrize("n_live", [0, 1, 2047, 2048, 2049])
+def test_sort_unique_equals_live_reference_at_exact_list_sizes(ctx, n_live):
+    """k_sort_unique around its switch from the LDS to the HBM bitonic path (2048 live matches).  n_live isolated pixels of
+    one label at multiples of T, one 1-feature template of that label, threshold 70 (raw score 4 > 3): exactly n_live matches, all tied in
+    similarity and template id."""
+    ref = RC.ReferenceBackend(R.require(False))
+    q = np.zeros((480, 640), np.uint8)
+    cells = np.random.default_rng(12100 + n_live).permutation(80 * 60)[:n_live]
+    q[(cells // 80) * 8, (cells % 80) * 8] = 1 << 3
+    bank = RC.TemplateBank("obj", 1, 1)
+    bank.add_pyramid([dict(width=1, height=1, offset_x=0, offset_y=0, pyramid_level=0, features=np.array([[0, 0, 3]], np.int32))])
+    case = dict(qs=[q], w0=640, h0=480, T=[8], M=1, banks=[bank], class_ids=(), thresholds=[])
+    exp = ref.match(case, 70.0)
+    assert len(exp) == n_live
+    det = _detector(ctx, case)
+    got, n = det.match_quantized([q], 70.0, cap=1 << 16)
+    assert n == n_live and RC.matches_equal(got, exp)
+    det.close()
+
+
+def test_sort_unique_equals_live_reference_above_20000(ctx):
+    """The HBM bitonic path well above the switch, with many ties: 2- to 5-feature templates on a dense image."""
+    ref = RC.ReferenceBackend(R.require(False))
+    qs = RC._pyramid(np.random.default_rng(12000), 640, 480, 1, 1, 0.6)
+    bank = RC._count_bank("obj", 1, 1, [2, 2, 3, 2, 5, 2], 640, 480, 12001, bbox=24)
+    case = dict(qs=qs, w0=640, h0=480, T=[8], M=1, banks=[bank], class_ids=(), thresholds=[])
+    exp = ref.match(case, 75.0)
+    assert len(exp) > 20000
+    det = _detector(ctx, case)
+    got, n = det.match_quantized(qs, 75.0, cap=1 << 20)
+    assert n == len(exp) and RC.matches_equal(got, exp)
+    det.close()
