@@ -56,6 +56,15 @@ class RecognitionParams(C.Structure):
                 ("dist_diff_thr", C.c_float), ("icp_mode", C.c_int32)]
 
 
+class InstanceParams(C.Structure):
+    _fields_ = [("max_instances", C.c_int32), ("min_dist_px", C.c_int32), ("hyp_per_instance", C.c_int32)]
+
+
+class InstanceResult(C.Structure):
+    _fields_ = [("reco", RecognitionResult), ("rank", C.c_int32), ("n_members", C.c_int32), ("n_refined", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("light", C.c_float * 3), ("ambient", C.c_float)]
 
@@ -64,7 +73,7 @@ class StageTimes(C.Structure):
     _fields_ = [("frontend_ms", C.c_float), ("linmem_ms", C.c_float), ("scan_ms", C.c_float), ("refine_ms", C.c_float),
                 ("sort_ms", C.c_float), ("backproject_ms", C.c_float), ("icp_ms", C.c_float), ("total_ms", C.c_float),
                 ("icp_iters_total", C.c_int32), ("icp_launches", C.c_int32), ("scan_algorithmic_bytes", C.c_double),
-                ("lazy_frontend_ms", C.c_float), ("reserved0", C.c_float)]
+                ("lazy_frontend_ms", C.c_float), ("group_ms", C.c_float)]
 
 
 FL_RENDER_AMBIENT = 0.2    # include/fealess_hip.h: fl_render_views' ambient when no fl_render_params is given
@@ -130,6 +139,9 @@ SIGNATURES = {
     "fl_recognize_topk": (_I, [_P, _P, _P, _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams), _I, _P, C.POINTER(_I)]),
     "fl_recognize_batch_topk": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams), _I, _P,
                                      C.POINTER(_I)]),
+    "fl_group_matches": (_I, [_P, _P, _I, _I, C.POINTER(InstanceParams), _P, _P, _P]),
+    "fl_recognize_batch_instances": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams),
+                                          C.POINTER(InstanceParams), _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "fl_nms": (_I, [_P, _I, _F, C.POINTER(_I), C.POINTER(_I)]),
     "fl_export_topk": (_I, [_P, _I, _I, _I, _P]),
     "fl_merge_topk": (_I, [_P, _I, _P, _I]),
@@ -141,6 +153,19 @@ SIGNATURES = {
     "fl_last_stage_times": (_I, [_P, C.POINTER(StageTimes)]),
     "fl_frame_counters": (_I, [_P, _I, C.POINTER(C.c_int32)]),
 }
+
+# development / test aids the library exports without declaring them in the header (fl_internal.h)
+DEV_SIGNATURES = {
+    "fl_dev_detector_create_host": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_P)]),
+    "fl_dev_group_jobs": (_I, [_P, _P, _I, C.POINTER(InstanceParams), _P, _P, _P, _P, _P]),
+}
+
+
+def dev(lib, name):
+    fn = getattr(lib, name)
+    fn.restype, fn.argtypes = DEV_SIGNATURES[name]
+    return fn
+
 
 class MgResult(C.Structure):         # include/fealess_mg.h fl_mg_result
     _fields_ = [("status", C.c_int32), ("found", C.c_int32), ("best", Match), ("pose", C.c_float * 16)]

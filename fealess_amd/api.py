@@ -286,10 +286,28 @@ def recognition_result_to_dict(r):
                 pose=np.array(r.pose, np.float32).reshape(4, 4), det=detection_result_to_dict(r.det))
 
 
+class _HostOnlyContext:
+    """What a host-only Detector needs of a Context: the library and the error text of the detector's own context."""
+
+    def __init__(self):
+        self.lib = L.load()
+        self.h = None
+
+    def check(self, rc):
+        if rc != L.FL_OK:
+            raise FealessError(rc, self.lib.fl_last_error(self.h).decode(errors="replace") if self.h else "")
+
+
+def _host_only_detector(modalities, T_pyramid):
+    """Test aid (fl_dev_detector_create_host, not part of the ABI): a Detector that holds its bank on the host only.  It needs
+    no GPU, cannot be finalized and serves the host-only entry points (group_matches with FL_MEM_HOST)."""
+    return Detector(_HostOnlyContext(), modalities, T_pyramid, _host_only=True)
+
+
 class Detector:
     """cup_linemod::Detector resident on one GPU (linemod.hpp:292-412)."""
 
-    def __init__(self, ctx, modalities, T_pyramid):
+    def __init__(self, ctx, modalities, T_pyramid, _host_only=False):
         self.ctx = ctx
         self.lib = ctx.lib
         self.M = modalities
@@ -297,7 +315,11 @@ class Detector:
         self.L = len(self.T)
         h = C.c_void_p()
         arr = (C.c_int * self.L)(*self.T)
-        ctx.check(self.lib.fl_detector_create(ctx.h, modalities, self.L, arr, C.byref(h)))
+        if _host_only:
+            ctx.check(L.dev(self.lib, "fl_dev_detector_create_host")(modalities, self.L, arr, C.byref(h)))
+            ctx.h = C.c_void_p(self.lib.fl_detector_get_context(h))
+        else:
+            ctx.check(self.lib.fl_detector_create(ctx.h, modalities, self.L, arr, C.byref(h)))
         self.h = h
         self.banks = []
         self.w0 = self.h0 = 0
@@ -485,6 +507,51 @@ class Detector:
         cnt = (C.c_int * n)()
         self.ctx.check(self.lib.fl_recognize_batch_topk(self.h, n, bp, dp, L.FL_MEM_HOST, C.byref(kk), C.byref(p), k, res, cnt))
         return [[recognition_result_to_dict(res[f * k + r]) for r in range(cnt[f])] for f in range(n)]
+
+    def group_matches(self, matches, max_instances, min_dist_px, hyp_per_instance=1, mem=L.FL_MEM_HOST, n=None, group_of=None,
+                      group_size=None, n_groups=None):
+        """fl_group_matches: the multi-instance grouping alone.  Host: `matches` is a MATCH_DTYPE array; returns
+        (group_of, group_size, n_groups).  Device (mem=FL_MEM_DEVICE): matches, group_of, group_size and n_groups are device
+        pointers and n the number of matches; queued on the context's stream, returns None."""
+        ip = L.InstanceParams(max_instances, min_dist_px, hyp_per_instance)
+        if mem == L.FL_MEM_DEVICE:
+            self.ctx.check(self.lib.fl_group_matches(self.h, C.c_void_p(matches), n, mem, C.byref(ip), C.c_void_p(group_of),
+                                                     C.c_void_p(group_size), C.c_void_p(n_groups)))
+            return None
+        m = np.ascontiguousarray(matches, MATCH_DTYPE)
+        gof = np.full(max(1, len(m)), -9, np.int32)
+        gsize = np.full(max(1, max_instances), -9, np.int32)
+        ng = C.c_int32(-9)
+        self.ctx.check(self.lib.fl_group_matches(self.h, _ptr(m), len(m), mem, C.byref(ip), _ptr(gof), _ptr(gsize), C.byref(ng)))
+        return gof[:len(m)], gsize, ng.value
+
+    def recognize_batch_instances(self, bgrs, depths, K, max_instances, min_dist_px, hyp_per_instance, threshold=75.0, icp_it_thr=10,
+                                  dist_mean_thr=0.5, dist_diff_thr=0.01, mode=L.FL_ICP_PARITY, mem=L.FL_MEM_HOST, with_dropped=False):
+        """fl_recognize_batch_instances: every instance in each frame.  Host arrays in (or, with mem=FL_MEM_DEVICE, lists of
+        device pointers); a list per frame of result dicts (recognition_result_to_dict plus rank, n_members, n_refined), in
+        group order.  with_dropped: also the per-frame counts of matches that found no group."""
+        if mem == L.FL_MEM_HOST:
+            bs = [np.ascontiguousarray(b, np.uint8) for b in bgrs]
+            ds = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            bptrs, dptrs = [b.ctypes.data for b in bs], [d.ctypes.data for d in ds]
+        else:
+            bptrs, dptrs = bgrs, depths
+        n = len(bptrs)
+        bp = (C.c_void_p * n)(*bptrs)
+        dp = (C.c_void_p * n)(*dptrs)
+        kk = L.Intrinsics(self.w0, self.h0, *K)
+        p = self._params(threshold, icp_it_thr, dist_mean_thr, dist_diff_thr, mode)
+        ip = L.InstanceParams(max_instances, min_dist_px, hyp_per_instance)
+        G = max(1, max_instances)
+        res = (L.InstanceResult * (n * G))()
+        cnt = (C.c_int32 * n)()
+        drop = (C.c_int32 * n)()
+        self.ctx.check(self.lib.fl_recognize_batch_instances(self.h, n, bp, dp, mem, C.byref(kk), C.byref(p), C.byref(ip), res, cnt, drop))
+        out = []
+        for f in range(n):
+            out.append([dict(recognition_result_to_dict(res[f * G + g].reco), rank=int(res[f * G + g].rank),
+                             n_members=int(res[f * G + g].n_members), n_refined=int(res[f * G + g].n_refined)) for g in range(cnt[f])])
+        return (out, [int(v) for v in drop]) if with_dropped else out
 
     def nms(self, n, th_obj_dist):
         """nonMaximumSuppression (ICP/NMS.cpp:6-40) over the first n hypotheses of the last recognize_topk call."""

@@ -159,6 +159,15 @@ int CadRecoRecognitionBatch(CObjRecoCAD *handle, int n_frames, const TImageU *rg
 // vtResult.  k = 1 restores the reference behaviour.
 int CadRecoSetMultiHypothesis(CObjRecoCAD *handle, int k, float nms_dist_mm);
 
+// Opt-in, not in the reference: every instance in the frame.  The match list is grouped in image space on the device
+// (box centres closer than min_dist_px to a group's first match, same class; at most max_instances groups, 1..64), the
+// first hyp_per_instance (1..64) members of each group are refined in one ICP launch, and nonMaximumSuppression's rule
+// (ICP/NMS.cpp:6-40) picks one of them per group (fl_recognize_batch_instances, include/fealess_hip.h).  Recognition() and
+// CadRecoRecognitionBatch then return one TObjRecoResult per instance, in group order (the group of matches[0] first).
+// max_instances = 1 with hyp_per_instance = 1 restores the reference behaviour.  This mode and CadRecoSetMultiHypothesis
+// exclude each other: setting one clears the other.
+int CadRecoSetMultiInstance(CObjRecoCAD *handle, int max_instances, int min_dist_px, int hyp_per_instance);
+
 // Not in the reference, where Train() is a stub and a data directory comes from the test/linemod_train.cpp demo
 // (OpenCV, Detector::addTemplate per frame, writeLinemod): train one class on the handle's GPU, batched, and write the
 // directory AddObj() reads.  Views: bgr[v] (BGR8), depth_mm[v] (mm), all of one size; mask: NULL, or per view an

@@ -131,9 +131,10 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     std::vector<std::vector<uint8_t> > zb;
     std::vector<std::vector<uint16_t> > zd;
     const bool zoom = K.nWidth != w;
-    // the single-hypothesis path zooms on the device (fl_recognize_batch_zoom); only the multi-hypothesis extension still
-    // takes the zoomed frames through host vectors
-    if (zoom && m_topk > 1) {
+    // the single-hypothesis path zooms on the device (fl_recognize_batch_zoom); only the multi-hypothesis and multi-instance
+    // extensions still take the zoomed frames through host vectors
+    const bool multi_instance = m_instances.max_instances > 1 || m_instances.hyp_per_instance > 1;
+    if (zoom && (m_topk > 1 || multi_instance)) {
       zb.resize(n);
       zd.resize(n);
       for (int i = 0; i < n; ++i) {
@@ -189,6 +190,31 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
       }
       return 0;
     }
+    if (multi_instance) {
+      // opt-in extension (CadRecoSetMultiInstance): the match list grouped on the device, a few members of each group
+      // refined, one result per group in group order
+      const int G = m_instances.max_instances;
+      std::vector<fl_instance_result> res((size_t)n * G);
+      std::vector<int32_t> cnt(n), dropped(n);
+      if (fl_recognize_batch_instances(m_det, n, bp.data(), dp.data(), FL_MEM_HOST, &k, &m_params, &m_instances, res.data(), cnt.data(),
+                                       dropped.data()) != FL_OK) {
+        fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
+        return (int)ERROR_INVALID_PARAM;
+      }
+      for (int i = 0; i < n; ++i) {
+        if (frame_rc) (*frame_rc)[i] = 0;
+        for (int g = 0; g < cnt[i]; ++g) {
+          const fl_recognition_result &h = res[(size_t)i * G + g].reco;
+          if (h.status != FL_OK && h.status != FL_ERR_ASSERT) return (int)ERROR_INVALID_PARAM;
+          if (!h.found) continue;
+          TObjRecoResult o;
+          o.strObjTag = m_class_ids[h.best.class_idx];
+          memcpy(o.tWorld2Cam, h.pose, sizeof(o.tWorld2Cam));
+          out[i].push_back(o);
+        }
+      }
+      return 0;
+    }
     std::vector<fl_recognition_result> res(n);
     const int rc = zoom ? fl_recognize_batch_zoom(m_det, n, bp.data(), dp.data(), K.nWidth, K.nHeight, FL_MEM_HOST, &k, &m_params, res.data())
                         : fl_recognize_batch(m_det, n, bp.data(), dp.data(), FL_MEM_HOST, &k, &m_params, res.data());
@@ -216,6 +242,7 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
   fl_recognition_params m_params;
   int m_topk = 1;            // > 1: multi-hypothesis mode (CadRecoSetMultiHypothesis)
   float m_nms_dist = 20.0f;  // th_obj_dist of nonMaximumSuppression, mm
+  fl_instance_params m_instances = {1, 48, 1};   // max_instances or hyp_per_instance > 1: multi-instance mode (CadRecoSetMultiInstance)
 
  private:
   fl_context *m_ctx = nullptr;
@@ -259,6 +286,19 @@ int CadRecoSetMultiHypothesis(CObjRecoCAD *handle, int k, float nms_dist_mm)
   if (!h || k < 1 || k > 1024 || !(nms_dist_mm >= 0.f)) return (int)ERROR_INVALID_PARAM;
   h->m_topk = k;
   h->m_nms_dist = nms_dist_mm;
+  h->m_instances.max_instances = h->m_instances.hyp_per_instance = 1;      // the two modes exclude each other
+  return 0;
+}
+
+int CadRecoSetMultiInstance(CObjRecoCAD *handle, int max_instances, int min_dist_px, int hyp_per_instance)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h || max_instances < 1 || max_instances > 64 || min_dist_px < 1 || min_dist_px > (1 << 30) || hyp_per_instance < 1 || hyp_per_instance > 64)
+    return (int)ERROR_INVALID_PARAM;
+  h->m_instances.max_instances = max_instances;
+  h->m_instances.min_dist_px = min_dist_px;
+  h->m_instances.hyp_per_instance = hyp_per_instance;
+  h->m_topk = 1;                                                             // the two modes exclude each other
   return 0;
 }
 
@@ -547,6 +587,10 @@ int cadreco_train_mesh(void *h, const char *dir, const char *class_id, const cha
   return rc;
 }
 int cadreco_set_multi_hypothesis(void *h, int k, float nms_dist_mm) { return CadRecoSetMultiHypothesis((CObjRecoCAD *)h, k, nms_dist_mm); }
+int cadreco_set_multi_instance(void *h, int max_instances, int min_dist_px, int hyp_per_instance)
+{
+  return CadRecoSetMultiInstance((CObjRecoCAD *)h, max_instances, min_dist_px, hyp_per_instance);
+}
 // Recognition() returning every result: poses16 receives min(*n_results, cap) 4x4 matrices
 int cadreco_recognition_all(void *h, const unsigned char *bgr, const unsigned short *depth, int w, int h_, double ts, int kw, int kh,
                             double fx, double fy, double cx, double cy, int *n_results, float *poses16, int cap)

@@ -136,6 +136,7 @@ extern "C" int fl_context_get_option(const fl_context *ctx, const char *name, lo
 // context that still has detectors only marks it; the last fl_detector_destroy releases it.
 static void context_release(fl_context *ctx)
 {
+  if (ctx->device < 0) { delete ctx; return; }           // a host-only detector's context (fl_dev_detector_create_host): no device state
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
@@ -249,12 +250,14 @@ static void free_device_tables(fl_detector *det)
 extern "C" void fl_detector_destroy(fl_detector *det)
 {
   if (!det) return;
-  (void)hipSetDevice(det->ctx->device);
-  (void)hipStreamSynchronize(det->ctx->stream);
-  free_device_tables(det);
-  for (auto &c : det->classes)
-    if (c.d_depths) (void)hipFree(c.d_depths);
   fl_context *ctx = det->ctx;
+  if (ctx->device >= 0) {                                // a host-only detector never had device state
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    free_device_tables(det);
+    for (auto &c : det->classes)
+      if (c.d_depths) (void)hipFree(c.d_depths);
+  }
   delete det;
   if (--ctx->detectors == 0 && ctx->destroy_pending) context_release(ctx);
 }
@@ -300,6 +303,7 @@ extern "C" int fl_detector_set_model_depths(fl_detector *det, int class_idx, int
 {
   if (!det || !depth_01mm || w <= 0 || h <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_STATE, "a host-only detector holds no depth renders");
   if (class_idx < 0 || class_idx >= (int)det->classes.size()) return fl_set_error(ctx, FL_ERR_INVALID, "class_idx");
   FlClass &c = det->classes[class_idx];
   if (first < 0 || count < 0 || first + count > c.n_pyramids) return fl_set_error(ctx, FL_ERR_INVALID, "pyramid range");
@@ -456,6 +460,7 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
 {
   if (!det || w0 <= 0 || h0 <= 0 || max_batch <= 0) return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_STATE, "a host-only detector cannot be finalized");
   FL_HIP(ctx, hipSetDevice(ctx->device));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_device_tables(det);

@@ -208,7 +208,9 @@ static inline void fl_batch_record(fl_detector *det, int n, const uint16_t *dept
   det->batch = FlBatch{n, depth, depth_stride, match_only};
 }
 
-// argument checks shared by entry points that return the same codes for them
+// argument checks shared by entry points that return the same codes for them.  The `finalized` check is also what keeps a
+// host-only detector (fl_dev_detector_create_host, context device = -1) away from every HIP call: it can never be finalized,
+// and every entry point that takes a detector tests `finalized` -- here or on its own -- before its first device call.
 static inline int fl_check_frames(fl_detector *det, int n_frames)     // finalized (FL_ERR_STATE), n_frames <= max_batch (FL_ERR_INVALID)
 {
   if (!det->finalized) return fl_set_error(det->ctx, FL_ERR_STATE, "fl_detector_finalize first");
@@ -236,6 +238,45 @@ int fl_launch_spread(fl_context *ctx, const uint8_t *quant, size_t quant_stride,
                      size_t spread_stride, int n_frames, int w, int h, int T);
 int fl_launch_match_core(fl_detector *det, int n_frames, float threshold);
 int fl_launch_lazy_level(fl_detector *det, int n_frames, int level);   // frontend: colour quantisation + spreads of the marked tiles
+// Multi-instance grouping (fl_group_matches, fl_recognize_batch_instances): one workgroup per frame groups that frame's
+// match list.  The list is `matches[0 .. n)` (frame_ws == nullptr, one frame) or the sorted list the match stage left in
+// each frame workspace.  Per frame f: group_of + f * group_of_stride (one int per match, also the kernel's working storage
+// for lists longer than FL_GROUP_LDS_MAX), group_size[f * G .. + G), info[f * 4 .. + 4) = {groups, matches without a group,
+// FL_ERR_OVERFLOW if the frame's candidate buffers overflowed (then nothing is grouped) else 0, matches}.  With jobs != nullptr:
+// jobs[(f * G + g) * h + r] = member r of group g (frame = -1 where absent) and job_idx[same] = its index in the list (-1).
+#define FL_GROUP_MAX 64            // groups per frame: one lane of a wave each
+#define FL_GROUP_HYP_MAX 64        // members refined per group
+#define FL_GROUP_LDS_MAX 16384     // matches whose group ids the kernel keeps in LDS (one byte each)
+struct FlGroupArgs {
+  const fl_match *matches;
+  int n;
+  const uint8_t *frame_ws;
+  size_t frame_stride, off_count, off_match;
+  const FlPyrInfo *pyr;
+  const int *class_first;
+  int n_classes, n_pyr;
+  int G, h;
+  long long r2, r;                 // (2 * min_dist_px)^2 and 2 * min_dist_px
+  int32_t *group_of;
+  size_t group_of_stride;
+  int32_t *group_size, *info;
+  FlRefineJob *jobs;
+  int32_t *job_idx;
+  int write_group_of;              // 0: group_of is written only where it is the working storage (n > FL_GROUP_LDS_MAX; else it may be null)
+};
+int fl_launch_group_matches(fl_detector *det, int n_frames, const FlGroupArgs &a);
+bool fl_instance_params_ok(const fl_instance_params *ip);   // the ranges include/fealess_hip.h states (the one check of both entry points)
+#define FL_INSTANCE_PARAMS_TEXT "fl_instance_params: max_instances 1..64, min_dist_px 1..2^30, hyp_per_instance 1..64"
+FlGroupArgs fl_group_args(const fl_detector *det, const fl_instance_params *ip);   // the detector's tables and the parameters; the rest zero
+// Development / test aids, exported but not part of the ABI (no header declares them).
+// A detector that holds its bank on the host only, on a context without a device (device = -1: no HIP call is ever made for
+// it): for the entry points that never touch the device (fl_group_matches with FL_MEM_HOST).  It cannot be finalized
+// (FL_ERR_STATE); fl_detector_destroy releases it and its context.
+extern "C" int fl_dev_detector_create_host(int modalities, int levels, const int *T_at_level, fl_detector **out);
+// k_group_matches on one caller-supplied device list WITH the job list: jobs[g * h + r] (FlRefineJob, frame 0 or -1) and
+// job_idx[g * h + r], info[4]; every pointer is device memory, queued on the context's stream.
+extern "C" int fl_dev_group_jobs(fl_detector *det, const fl_match *matches, int n, const fl_instance_params *ip, int32_t *group_of,
+                                 int32_t *group_size, int32_t *info, void *jobs, int32_t *job_idx);
 // frontend
 int fl_launch_quantized_orientations(fl_context *ctx, const uint8_t *bgr, size_t in_stride,
                                      uint8_t *dst, size_t out_stride, int n_frames, int w, int h,

@@ -419,6 +419,138 @@ extern "C" int fl_recognize_batch_topk(fl_detector *det, int n_frames, const uin
   }
 }
 
+// ---- multi-instance recognition (include/fealess_hip.h): match -> group -> one ICP launch -> pick, all on the device ----
+// What the pick kernel leaves for the one copy to the host: results[n_frames * G], then n_instances, n_dropped and status
+// (FL_ERR_OVERFLOW: the frame's candidate buffers overflowed and nothing was grouped), n_frames ints each.
+static size_t instances_out_bytes(int n_frames, int G) { return sizeof(fl_instance_result) * (size_t)n_frames * G + sizeof(int32_t) * 3 * (size_t)n_frames; }
+
+// One thread per (frame, group): nonMaximumSuppression's choice among the group's refined members (see the header).
+__global__ __launch_bounds__(64) void k_pick_instances(const fl_recognition_result *__restrict__ res, const int32_t *__restrict__ job_idx,
+                                                       const int32_t *__restrict__ group_size, const int32_t *__restrict__ info, int n_frames,
+                                                       int G, int h, fl_instance_result *__restrict__ out)
+{
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n_frames * G) return;
+  const int f = t / G, g = t - f * G;
+  const int32_t *fi = info + 4 * (size_t)f;
+  if (g == 0) {
+    int32_t *tail = (int32_t *)(out + (size_t)n_frames * G);
+    tail[f] = fi[0];
+    tail[n_frames + f] = fi[1];
+    tail[2 * n_frames + f] = fi[2];
+  }
+  if (g >= fi[0]) return;                                  // the slot stays zeroed
+  const size_t first = (size_t)t * h;
+  int o = -1, size_th = 0, n_refined = 0;
+  for (int r = 0; r < h && job_idx[first + r] >= 0; ++r) {
+    ++n_refined;
+    const fl_recognition_result &c = res[first + r];
+    if (!c.found) continue;
+    if (o < 0) { o = r; size_th = (int)((double)(float)c.det.n_points * 0.85); }     // NMS.cpp:13, the double product fl_nms takes
+    else if (c.det.n_points > size_th && c.det.icp.dist_mean < res[first + o].det.icp.dist_mean) o = r;
+  }
+  if (o < 0) o = 0;                                        // no member was found: the leader, found = 0
+  fl_instance_result v;
+  v.reco = res[first + o];
+  v.reco.n_matches = fi[3];
+  v.rank = job_idx[first + o];
+  v.n_members = group_size[t];
+  v.n_refined = n_refined;
+  v.reserved = 0;
+  out[t] = v;
+}
+
+static int recognize_batch_instances_once(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth, int mem,
+                                          const fl_intrinsics *K, const fl_recognition_params *params, const fl_instance_params *ip,
+                                          fl_instance_result *results, int32_t *n_instances, int32_t *n_dropped)
+{
+  if (!det || !bgr || n_frames <= 0 || !K || !params || !ip || !results || !n_instances || !n_dropped) return FL_ERR_INVALID;
+  fl_context *ctx = det->ctx;
+  if (det->M != 2) return fl_set_error(ctx, FL_ERR_INVALID, "needs the colour + depth modalities");
+  if (!fl_instance_params_ok(ip)) return fl_set_error(ctx, FL_ERR_INVALID, FL_INSTANCE_PARAMS_TEXT);
+  int rc = fl_check_frames(det, n_frames);
+  if (rc) return rc;
+  // Everything that can refuse or fail without the batch comes BEFORE the batch is queued: a return between stage_and_match
+  // and input_done would leave the input buffer's read event unrecorded.
+  const int G = ip->max_instances, h = ip->hyp_per_instance;
+  const size_t jobs = (size_t)n_frames * G * h, ws_one = fl_align(fl_icp_ws_bytes(det->n_pts_max), 256);
+  const size_t icp_bytes = ws_one * jobs, out_bytes = instances_out_bytes(n_frames, G);
+  if (jobs > (1u << 20) || icp_bytes > ((size_t)96 << 30))
+    return fl_set_error(ctx, FL_ERR_INVALID, "%d frames x %d instances x %d hypotheses need %zu MB of ICP workspaces", n_frames, G, h, icp_bytes >> 20);
+  // one scratch block: ICP workspaces, their results, the job list and its list indices, sizes, counters, output -- and the
+  // group ids only where the kernel needs them as working storage (lists longer than FL_GROUP_LDS_MAX)
+  const bool need_gof = det->cap > FL_GROUP_LDS_MAX;
+  size_t off = icp_bytes;
+  auto take = [&](size_t bytes) { const size_t o = off; off = fl_align(off + bytes, 256); return o; };
+  const size_t o_res = take(sizeof(fl_recognition_result) * jobs), o_jobs = take(sizeof(FlRefineJob) * jobs), o_idx = take(sizeof(int32_t) * jobs);
+  const size_t o_gof = take(need_gof ? sizeof(int32_t) * (size_t)det->cap * n_frames : 0), o_size = take(sizeof(int32_t) * (size_t)n_frames * G);
+  const size_t o_info = take(sizeof(int32_t) * 4 * (size_t)n_frames), o_out = take(out_bytes);
+  void *sv = nullptr, *hv = nullptr;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = fl_scratch(ctx, off, &sv)) || (rc = fl_pinned(ctx, out_bytes, &hv))) return rc;
+  uint8_t *s = (uint8_t *)sv;
+  const uint16_t *depth_base = nullptr;
+  size_t depth_stride = 0;
+  int host_buf = -1;
+  if ((rc = stage_and_match(det, n_frames, bgr, depth, mem, K, params->matching_threshold, &depth_base, &depth_stride, &host_buf))) return rc;
+  fl_recognition_result *d_res = (fl_recognition_result *)(s + o_res);
+  FL_HIP(ctx, hipMemsetAsync(d_res, 0, sizeof(fl_recognition_result) * jobs, ctx->stream));
+  FL_HIP(ctx, hipMemsetAsync(s + o_out, 0, out_bytes, ctx->stream));
+  FL_HIP(ctx, hipEventRecord(det->ev[16], ctx->stream));
+  FlGroupArgs a = fl_group_args(det, ip);
+  a.n = det->cap;
+  a.frame_ws = det->d_ws;
+  a.frame_stride = det->ws_stride;
+  a.off_count = det->off_count;
+  a.off_match = det->off_match;
+  a.group_of = need_gof ? (int32_t *)(s + o_gof) : nullptr;
+  a.group_of_stride = need_gof ? (size_t)det->cap : 0;
+  a.group_size = (int32_t *)(s + o_size);
+  a.info = (int32_t *)(s + o_info);
+  a.jobs = (FlRefineJob *)(s + o_jobs);
+  a.job_idx = (int32_t *)(s + o_idx);
+  if ((rc = fl_launch_group_matches(det, n_frames, a))) return rc;
+  FL_HIP(ctx, hipEventRecord(det->ev[17], ctx->stream));
+  if ((rc = fl_launch_detection(det, (int)jobs, K, params, depth_base, depth_stride, s, ws_one, 1, a.jobs, d_res, false))) return rc;
+  if ((rc = input_done(det, host_buf))) return rc;
+  FL_HIP(ctx, hipEventRecord(det->ev[18], ctx->stream));
+  hipLaunchKernelGGL(k_pick_instances, dim3((n_frames * G + 63) / 64), dim3(64), 0, ctx->stream, d_res, a.job_idx, a.group_size, a.info, n_frames, G, h,
+                     (fl_instance_result *)(s + o_out));
+  FL_HIP(ctx, hipGetLastError());
+  FL_HIP(ctx, hipEventRecord(det->ev[6], ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(hv, s + o_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const fl_instance_result *h_res = (const fl_instance_result *)hv;
+  const int32_t *tail = (const int32_t *)(h_res + (size_t)n_frames * G);
+  for (int f = 0; f < n_frames; ++f)
+    if (tail[2 * n_frames + f] == FL_ERR_OVERFLOW) return fl_set_error(ctx, FL_ERR_OVERFLOW, "frame %d: more than %d candidates", f, det->cap);
+  memcpy(results, h_res, sizeof(fl_instance_result) * (size_t)n_frames * G);
+  memcpy(n_instances, tail, sizeof(int32_t) * (size_t)n_frames);
+  memcpy(n_dropped, tail + n_frames, sizeof(int32_t) * (size_t)n_frames);
+  // stage times: the ICP stage of this call is grouping + ICP + pick; group_ms is the two new kernels' part of it
+  fl_update_stage_times(det, n_frames, nullptr);
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, det->ev[16], det->ev[17]) == hipSuccess) det->times.group_ms = ms;
+  if (hipEventElapsedTime(&ms, det->ev[18], det->ev[6]) == hipSuccess) det->times.group_ms += ms;
+  for (int f = 0; f < n_frames; ++f)
+    for (int g = 0; g < n_instances[f]; ++g) {
+      const fl_recognition_result &r = results[(size_t)f * G + g].reco;
+      det->times.icp_iters_total += r.found ? r.det.icp.iters : 0;        // of the picked hypotheses
+    }
+  return FL_OK;
+}
+
+extern "C" int fl_recognize_batch_instances(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth,
+                                            int mem, const fl_intrinsics *K, const fl_recognition_params *params,
+                                            const fl_instance_params *ip, fl_instance_result *results, int32_t *n_instances,
+                                            int32_t *n_dropped)
+{
+  for (int attempt = 0;; ++attempt) {
+    int rc = recognize_batch_instances_once(det, n_frames, bgr, depth, mem, K, params, ip, results, n_instances, n_dropped);
+    if (!fl_grow_after_overflow(det, n_frames, attempt, &rc)) return rc;
+  }
+}
+
 // nonMaximumSuppression (ICP/NMS.cpp:6-40) over refined hypotheses, in list order.  winners[g] = index of the
 // hypothesis that represents group g; returns the number of groups in *n_winners.  Host-only arithmetic.
 extern "C" int fl_nms(const fl_recognition_result *objs, int n, float th_obj_dist, int *winners, int *n_winners)

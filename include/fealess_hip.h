@@ -179,7 +179,7 @@ int  fl_detector_set_model_depths(fl_detector *det, int class_idx, int first, in
 int  fl_detector_finalize(fl_detector *det, int w0, int h0, int max_batch, int max_candidates);
 /* max_candidates: per-frame capacity of the coarse-candidate / match buffers.  > 0 (or 0 = 65536): an INITIAL size -- a frame
  * that needs more makes the synchronous entry points (fl_match_quantized / _frame / _frame_masked, fl_recognize_batch /
- * _batch_zoom / _topk / _batch_topk) grow the buffers and run again, because the reference's vectors are unbounded
+ * _batch_zoom / _topk / _batch_topk / _batch_instances) grow the buffers and run again, because the reference's vectors are unbounded
  * (linemod.cpp:1490-1504, 1575); the queued ones (fl_recognize_submit / fl_match_batch_submit) cannot replay a batch and
  * report FL_ERR_OVERFLOW in that frame's status (the other frames keep their results).  < 0: a hard cap of
  * -max_candidates, FL_ERR_OVERFLOW beyond it. */
@@ -377,6 +377,54 @@ int  fl_recognize_batch_topk(fl_detector *det, int n_frames, const uint8_t *cons
 /* nonMaximumSuppression (ICP/NMS.cpp:6-40) over refined hypotheses in list order: winners[g] = index of the
  * hypothesis representing group g (translation closer than th_obj_dist to the group's current best). Host only. */
 int  fl_nms(const fl_recognition_result *objs, int n, float th_obj_dist, int *winners, int *n_winners);
+/* ---- multi-instance recognition: group the match list on the device, refine a few members of each group ----------
+ * The sorted match list is not spread over the objects in a frame: every instance contributes a run of near-ties
+ * (neighbouring positions, neighbouring views), so the first k matches may all belong to one object.  The entry points
+ * below group a frame's list in image space BEFORE the refinement and refine only the first few members of each group.
+ *
+ * Grouping -- greedy over the list in its sorted order, all in integers: for match i with template pyramid g, the doubled
+ * centre of the rectangle Recognition() crops (templates[0], obj_reco_lmicp.cpp:129-132) is
+ *   c2 = (2 x + width0(g), 2 y + height0(g)).
+ * Match i joins the FIRST group in creation order whose leader has the same class_idx and
+ *   (c2x - leader.c2x)^2 + (c2y - leader.c2y)^2 < (2 min_dist_px)^2          (64-bit, strict)
+ * -- distances are taken to the leader only -- or else founds a new group while fewer than max_instances exist, or else
+ * is dropped (group -1).  Members keep list order inside their group.
+ * Refinement -- the first hyp_per_instance members of each group, each exactly as fl_refine_matches refines a match.
+ * Pick -- nonMaximumSuppression's choice (ICP/NMS.cpp:6-40, as fl_nms states it) among a group's refined members with
+ * found = 1, in list order: o = the first of them, size_th = (int)((float)n_points[o] * 0.85); a later member j replaces
+ * o when n_points[j] > size_th && dist_mean[j] < dist_mean[o].  A group without a found member reports its leader
+ * (found = 0).  Groups are reported in creation order, which is the order fl_nms reports its winners in. */
+typedef struct {
+  int32_t max_instances;               /* 1..64: groups per frame                         */
+  int32_t min_dist_px;                 /* 1..2^30: group radius, pixels of the w0 x h0 frame */
+  int32_t hyp_per_instance;            /* 1..64: members refined per group                */
+} fl_instance_params;
+typedef struct {
+  fl_recognition_result reco;          /* the picked hypothesis; reco.n_matches = the frame's */
+  int32_t rank;                        /* its index in the frame's match list */
+  int32_t n_members, n_refined, reserved;
+} fl_instance_result;
+/* The grouping alone, on a caller-supplied list of n >= 0 matches (class-local template ids of THIS detector):
+ * group_of[i] = group of match i or -1, group_size[g] for g < ip->max_instances (0 beyond *n_groups), *n_groups.
+ * FL_MEM_HOST: host arrays, computed on the host from the classes added so far (no device work, the detector need not be
+ * finalized); a match whose class or template is not on the detector: FL_ERR_INVALID, nothing written.
+ * FL_MEM_DEVICE: matches, group_of, group_size and n_groups (one int) are device memory; the grouping kernel is queued on
+ * the context's stream (finalized detector, no synchronisation); there a match that is not on the detector gets -1. */
+int  fl_group_matches(fl_detector *det, const fl_match *matches, int n, int mem, const fl_instance_params *ip,
+                      int32_t *group_of, int32_t *group_size, int32_t *n_groups);
+/* Recognition() returning every instance in the frame: front-end and Detector::match of the batch, the grouping kernel
+ * (one workgroup per frame), ONE ICP launch over n_frames * max_instances * hyp_per_instance jobs (the absent ones exit at
+ * once), the pick kernel, one copy to the host -- nothing touches the host in between.  results[f * max_instances + g]
+ * for g < n_instances[f] (the rest zeroed); n_dropped[f] = matches of frame f that found no group.  Needs both
+ * modalities.  A frame without matches has n_instances = 0.  With {1, any, 1} results[f].reco is what fl_recognize_batch
+ * returns.  The ICP workspaces come from the context's scratch, one per job SLOT -- n_frames * max_instances *
+ * hyp_per_instance of them, absent jobs included, each about 86 bytes per pixel of the largest template rectangle (2.2 MB at
+ * 160 x 160) -- and the call is refused with FL_ERR_INVALID beyond 2^20 slots or 96 GB: at {8, ., 4} and 160 x 160 templates that
+ * is about 1300 frames per call; larger batches go through in several calls. */
+int  fl_recognize_batch_instances(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth,
+                                  int mem, const fl_intrinsics *K, const fl_recognition_params *params,
+                                  const fl_instance_params *ip, fl_instance_result *results, int32_t *n_instances,
+                                  int32_t *n_dropped);
 /* After fl_match_frame / fl_recognize_submit: copy frame `frame`'s first k sorted matches into a
  * device buffer (k * sizeof(fl_match) bytes, padded with template_id = -1) for an RCCL
  * all-gather by the caller; template ids are offset by template_id_base (the shard's first
@@ -432,7 +480,7 @@ typedef struct {
   float lazy_frontend_ms;   /* fl_recognize_*: colour quantisation + spread of the finer levels, computed after the scan
                                and only in the tiles the candidates touch (0 when FL_EAGER_FRONTEND=1: then part of
                                frontend_ms / linmem_ms).  refine_ms excludes it. */
-  float reserved0;
+  float group_ms;          /* fl_recognize_batch_instances: the grouping and the pick kernel (icp_ms includes them) */
 } fl_stage_times;
 int  fl_last_stage_times(fl_detector *det, fl_stage_times *out);
 
