@@ -69,6 +69,16 @@ class RenderParams(C.Structure):
     _fields_ = [("light", C.c_float * 3), ("ambient", C.c_float)]
 
 
+class TrackParams(C.Structure):
+    _fields_ = [("margin_px", C.c_int32), ("passes", C.c_int32), ("icp_it_thr", C.c_int32), ("dist_mean_thr", C.c_float),
+                ("dist_diff_thr", C.c_float), ("icp_mode", C.c_int32), ("max_dist_mean", C.c_float), ("min_px_ratio", C.c_float)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("tracked", C.c_int32), ("rect_model", C.c_int32 * 4), ("rect_ref", C.c_int32 * 4),
+                ("pose", C.c_float * 16), ("det", DetectionResult)]
+
+
 class StageTimes(C.Structure):
     _fields_ = [("frontend_ms", C.c_float), ("linmem_ms", C.c_float), ("scan_ms", C.c_float), ("refine_ms", C.c_float),
                 ("sort_ms", C.c_float), ("backproject_ms", C.c_float), ("icp_ms", C.c_float), ("total_ms", C.c_float),
@@ -77,6 +87,7 @@ class StageTimes(C.Structure):
 
 
 FL_RENDER_AMBIENT = 0.2    # include/fealess_hip.h: fl_render_views' ambient when no fl_render_params is given
+FL_TRACK_MAX_PASSES = 4    # include/fealess_hip.h: fl_track_params.passes
 FL_TOPK_OVERFLOW = -2      # fl_export_topk_batch: template id of record 0 of a frame whose candidate buffers overflowed
 
 _P = C.c_void_p
@@ -142,6 +153,9 @@ SIGNATURES = {
     "fl_group_matches": (_I, [_P, _P, _I, _I, C.POINTER(InstanceParams), _P, _P, _P]),
     "fl_recognize_batch_instances": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams),
                                           C.POINTER(InstanceParams), _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "fl_tracker_create": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "fl_tracker_destroy": (None, [_P]),
+    "fl_track_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams), _P]),
     "fl_nms": (_I, [_P, _I, _F, C.POINTER(_I), C.POINTER(_I)]),
     "fl_export_topk": (_I, [_P, _I, _I, _I, _P]),
     "fl_merge_topk": (_I, [_P, _I, _P, _I]),
@@ -158,6 +172,8 @@ SIGNATURES = {
 DEV_SIGNATURES = {
     "fl_dev_detector_create_host": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_P)]),
     "fl_dev_group_jobs": (_I, [_P, _P, _I, C.POINTER(InstanceParams), _P, _P, _P, _P, _P]),
+    "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
 }
 
 

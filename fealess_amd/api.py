@@ -18,6 +18,10 @@ _ICP_DT = np.dtype([("R", "<f4", 9), ("T", "<f4", 3), ("dist_mean", "<f4"), ("px
 _DET_DT = np.dtype([("R_final", "<f4", 9), ("T_final", "<f4", 3), ("icp", _ICP_DT), ("n_points", "<i4"), ("status", "<i4")])
 RESULT_DTYPE = np.dtype([("status", "<i4"), ("found", "<i4"), ("n_matches", "<i4"), ("best", MATCH_DTYPE), ("pose", "<f4", 16), ("det", _DET_DT)])
 assert RESULT_DTYPE.itemsize == C.sizeof(L.RecognitionResult)
+# numpy view of fl_track_result
+TRACK_DTYPE = np.dtype([("status", "<i4"), ("tracked", "<i4"), ("rect_model", "<i4", 4), ("rect_ref", "<i4", 4), ("pose", "<f4", 16),
+                        ("det", _DET_DT)])
+assert TRACK_DTYPE.itemsize == C.sizeof(L.TrackResult)
 
 
 class FealessError(RuntimeError):
@@ -713,3 +717,83 @@ def merge_topk(records, cap):
     if n < 0:
         raise FealessError(n, "fl_merge_topk")
     return out[:n]
+
+
+class Tracker:
+    """fl_tracker: follows objects from frame to frame against their CAD mesh (render at the previous pose, crop, detection()
+    from that pose).  Owns its device memory: the mesh, max_frames depth frames of w x h, max_tracks renders and ICP workspaces
+    for crops of up to max_crop_px pixels."""
+
+    def __init__(self, ctx, vertices, triangles, w, h, max_frames, max_tracks, max_crop_px):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        self.w, self.h, self.max_frames, self.max_tracks, self.max_crop_px = w, h, max_frames, max_tracks, max_crop_px
+        h_ = C.c_void_p()
+        ctx.check(self.lib.fl_tracker_create(ctx.h, _ptr(v), len(v), _ptr(t), len(t), w, h, max_frames, max_tracks, max_crop_px, C.byref(h_)))
+        self.handle = h_
+
+    def track(self, depths, frame_of_track, poses13, K, **params):
+        """One step of every track (fl_track_batch).  depths: the frames, (h, w) u16 numpy arrays in mm, or device tensors
+        (anything with data_ptr(): all of one kind); frame_of_track: the frame each track looks at; poses13: (n_tracks, 13)
+        or (n_tracks, 4, 4) poses to start from; K = (fx, fy, cx, cy) of the scene camera.  params: the fields of
+        fl_track_params (margin_px, passes, icp_it_thr, dist_mean_thr, dist_diff_thr, icp_mode, max_dist_mean, min_px_ratio);
+        none given = the library's defaults.  Returns a TRACK_DTYPE array, one record per track; feed its poses back in
+        (poses13_of) for the next frame."""
+        depths = list(depths)
+        device = len(depths) > 0 and hasattr(depths[0], "data_ptr")
+        if device:
+            for d in depths:
+                if d.numel() != self.w * self.h or d.element_size() != 2 or not d.is_contiguous():
+                    raise ValueError(f"Tracker.track: device frames must be contiguous {self.h} x {self.w} 16-bit tensors")
+            ptrs = [d.data_ptr() for d in depths]
+        else:
+            depths = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            for d in depths:
+                if d.shape != (self.h, self.w):
+                    raise ValueError(f"Tracker.track: frames must be {self.h} x {self.w}")
+            ptrs = [d.ctypes.data for d in depths]
+        n = len(ptrs)
+        dp = (C.c_void_p * max(1, n))(*ptrs)
+        fof = np.ascontiguousarray(frame_of_track, np.int32).ravel()
+        p = np.asarray(poses13, np.float32)
+        if p.ndim == 3 and p.shape[1:] == (4, 4):
+            p = np.concatenate([p[:, :3, :].reshape(-1, 12), np.zeros((len(p), 1), np.float32)], 1)
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 13)
+        if len(p) != len(fof):
+            raise ValueError("Tracker.track: one pose per track")
+        prm = None
+        if params:
+            unknown = set(params) - {f[0] for f in L.TrackParams._fields_}
+            if unknown:
+                raise TypeError(f"Tracker.track: unknown parameters {sorted(unknown)}")
+            d = dict(margin_px=12, passes=1, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01, icp_mode=L.FL_ICP_POINT_TO_PLANE,
+                     max_dist_mean=0.0, min_px_ratio=0.0)
+            d.update(params)
+            prm = L.TrackParams(**d)
+        k = L.Intrinsics(self.w, self.h, *[float(x) for x in K])
+        out = np.zeros(max(1, len(fof)), TRACK_DTYPE)
+        self.ctx.check(self.lib.fl_track_batch(self.handle, n, dp, L.FL_MEM_DEVICE if device else L.FL_MEM_HOST, len(fof), _ptr(fof), _ptr(p),
+                                               C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
+        return out[:len(fof)]
+
+    def stage_ms(self):
+        """DEVELOPMENT ONLY (fl_dev_tracker_stage_ms, not part of the C ABI): device time of the last track() by stage, summed
+        over its passes: dict(copy, render, rects, icp, finish) in ms."""
+        out = (C.c_float * 5)()
+        self.ctx.check(L.dev(self.lib, "fl_dev_tracker_stage_ms")(self.handle, out))
+        return dict(zip(("copy", "render", "rects", "icp", "finish"), [float(v) for v in out]))
+
+    def close(self):
+        if self.handle:
+            self.lib.fl_tracker_destroy(self.handle)
+            self.handle = None
+
+
+def poses13_of(track_results):
+    """The (n, 13) pose array that feeds a TRACK_DTYPE result array back into Tracker.track."""
+    r = np.atleast_1d(track_results)
+    out = np.zeros((len(r), 13), np.float32)
+    out[:, :12] = r["pose"][:, :12]
+    return out

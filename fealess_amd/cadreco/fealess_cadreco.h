@@ -210,4 +210,23 @@ struct CadRecoViewSphere {
 int CadRecoTrainMesh(CObjRecoCAD *handle, const string &dir, const string &class_id, const string &obj_path, float scale,
                      const CadRecoViewSphere &views, int levels, const int *T, std::vector<int> *template_of_view);
 
+// ---- tracking between recognitions (not in the reference, which links a KCF box tracker it never calls:
+// test/linemod_acq.cpp:108-150) -------------------------------------------------------------------------------------------
+// Recognition() costs a front-end, a scan of the whole bank and a 20-iteration ICP per frame.  Between recognitions an object
+// can be FOLLOWED instead: render the CAD mesh at the previous frame's pose, crop both depth images around the render and
+// run detection() from that pose (fl_track_batch, include/fealess_hip.h: point-to-plane ICP, one pass, the library's defaults).
+// CadRecoSetTrackingMesh reads the OBJ (fealess::ReadObj -- the file and scale CadRecoTrainMesh trained from) and uploads it;
+// a second call replaces the mesh.  SUCCESS; ReadObj's codes; ERROR_INVALID_PARAM (mesh limits); ERROR_UNKNOW (no GPU, HIP).
+// CadRecoTrack: vtResult comes in as the previous frame's results (from Recognition or from CadRecoTrack) and goes out
+// updated; (*tracked)[i] (optional) = 1 where entry i was followed, 0 where it was lost -- out of view, too few points, a crop
+// of more than FEALESS_TRACK_MAX_CROP_PX pixels -- and then the entry keeps its pose: call Recognition again.  The depth frame
+// must be 640 x 480 (the image of the model camera 608 / 608 / 320 / 240 that detection() assumes for the render); K is the
+// frame's camera.  ERROR_INVALID_PARAM: no mesh set, another frame size, an invalid image, more than
+// FEALESS_TRACK_MAX_OBJECTS entries.  An empty vtResult is SUCCESS.
+#define FEALESS_TRACK_MAX_OBJECTS 16
+#define FEALESS_TRACK_MAX_CROP_PX (320 * 240)
+int CadRecoSetTrackingMesh(CObjRecoCAD *handle, const string &obj_path, float scale);
+int CadRecoTrack(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult,
+                 vector<int> *tracked);
+
 #endif  // FEALESS_CADRECO_H

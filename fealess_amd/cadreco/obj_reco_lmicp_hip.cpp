@@ -16,6 +16,7 @@
 #include <sstream>
 
 #define PROC_IMG_WIDTH 640      // obj_reco_lmicp.cpp:6
+#define TRACK_IMG_HEIGHT 480    // with PROC_IMG_WIDTH: the image the model camera (608 / 608 / 320 / 240) belongs to
 
 namespace {
 int check_image_u8(const TImageU &t) { return t.dTimestamp >= 0 && t.nHeight > 0 && t.nWidth > 0 && t.pData; }     // CheckTImage :32-36
@@ -36,6 +37,7 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
   }
   ~CObjRecoLmICPHip() override
   {
+    if (m_tracker) fl_tracker_destroy(m_tracker);
     if (m_det) fl_detector_destroy(m_det);
     if (m_ctx) fl_context_destroy(m_ctx);
   }
@@ -239,6 +241,52 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
 
   fl_context *Context() const { return m_ctx; }
 
+  // CadRecoSetTrackingMesh: the mesh goes to the device once; a second call replaces the tracker
+  int SetTrackingMesh(const fealess::Mesh &mesh)
+  {
+    if (!m_ctx) return (int)ERROR_UNKNOW;
+    fl_tracker *trk = nullptr;
+    const int rc = fl_tracker_create(m_ctx, mesh.vertices.data(), (int)(mesh.vertices.size() / 3), mesh.triangles.data(),
+                                     (int)(mesh.triangles.size() / 3), PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, 1, FEALESS_TRACK_MAX_OBJECTS,
+                                     FEALESS_TRACK_MAX_CROP_PX, &trk);
+    if (rc == FL_ERR_INVALID) return (int)ERROR_INVALID_PARAM;
+    if (rc != FL_OK) {
+      fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
+      return (int)ERROR_UNKNOW;
+    }
+    if (m_tracker) fl_tracker_destroy(m_tracker);
+    m_tracker = trk;
+    return SUCCESS;
+  }
+
+  // CadRecoTrack: one fl_track_batch over the previous frame's results, library defaults (point-to-plane, one pass)
+  int Track(const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult, vector<int> *tracked)
+  {
+    if (tracked) tracked->assign(vtResult.size(), 0);
+    if (!m_ctx || !m_tracker || !check_image_u16(tDepth) || tDepth.nWidth != PROC_IMG_WIDTH || tDepth.nHeight != TRACK_IMG_HEIGHT ||
+        (int)vtResult.size() > FEALESS_TRACK_MAX_OBJECTS)
+      return (int)ERROR_INVALID_PARAM;
+    const int n = (int)vtResult.size();
+    if (n == 0) return SUCCESS;
+    std::vector<float> poses((size_t)n * 13, 0.f);
+    std::vector<int32_t> frame_of(n, 0);
+    for (int i = 0; i < n; ++i) memcpy(poses.data() + (size_t)13 * i, vtResult[i].tWorld2Cam, 12 * sizeof(float));
+    const fl_intrinsics k = {PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, K.dFx, K.dFy, K.dCx, K.dCy};
+    const uint16_t *frame = tDepth.pData;
+    std::vector<fl_track_result> res(n);
+    const int rc = fl_track_batch(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), &k, nullptr, res.data());
+    if (rc != FL_OK) {
+      fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
+      return rc == FL_ERR_INVALID ? (int)ERROR_INVALID_PARAM : (int)ERROR_UNKNOW;
+    }
+    for (int i = 0; i < n; ++i) {
+      if (!res[i].tracked) continue;                                          // lost: the entry keeps its pose
+      memcpy(vtResult[i].tWorld2Cam, res[i].pose, sizeof(vtResult[i].tWorld2Cam));
+      if (tracked) (*tracked)[i] = 1;
+    }
+    return SUCCESS;
+  }
+
   fl_recognition_params m_params;
   int m_topk = 1;            // > 1: multi-hypothesis mode (CadRecoSetMultiHypothesis)
   float m_nms_dist = 20.0f;  // th_obj_dist of nonMaximumSuppression, mm
@@ -250,6 +298,7 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
   std::vector<std::string> m_class_ids;
   std::string m_path;
   int m_w = 0, m_h = 0, m_batch = 1;
+  fl_tracker *m_tracker = nullptr;   // CadRecoSetTrackingMesh
 };
 
 // ---- factory (CadReco/obj_reco_temp.cpp:6-35) -------------------------------------------------
@@ -525,8 +574,53 @@ int CadRecoTrainMesh(CObjRecoCAD *handle, const string &dir, const string &class
   }, template_of_view);
 }
 
+int CadRecoSetTrackingMesh(CObjRecoCAD *handle, const string &obj_path, float scale)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h) return (int)ERROR_INVALID_PARAM;
+  fealess::Mesh mesh;
+  std::string err;
+  const int rc = fealess::ReadObj(obj_path, scale, mesh, &err);
+  if (rc != SUCCESS) {
+    fprintf(stderr, "[cadreco] %s\n", err.c_str());
+    return rc;
+  }
+  return h->SetTrackingMesh(mesh);
+}
+
+int CadRecoTrack(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult,
+                 vector<int> *tracked)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h) return (int)ERROR_INVALID_PARAM;
+  return h->Track(tDepth, K, vtResult, tracked);
+}
+
 // ---- flat C shim so that the pytest harness (ctypes) can drive the C++ facade -------------------
 extern "C" {
+int cadreco_set_tracking_mesh(void *h, const char *obj_path, float scale)
+{
+  if (!obj_path) return (int)ERROR_INVALID_PARAM;
+  return CadRecoSetTrackingMesh((CObjRecoCAD *)h, obj_path, scale);
+}
+// CadRecoTrack on n results: poses16 (n 4x4 matrices) goes in as the previous poses and comes out updated; tracked: n ints
+int cadreco_track(void *h, const unsigned short *depth, int w, int h_, double ts, double fx, double fy, double cx, double cy, int n,
+                  float *poses16, int *tracked)
+{
+  if (n < 0 || (n > 0 && (!poses16 || !tracked))) return (int)ERROR_INVALID_PARAM;
+  TImageU16 d = {ts, (unsigned short *)depth, w, h_};
+  TCamIntrinsicParam K;
+  K.nWidth = w; K.nHeight = h_; K.dFx = fx; K.dFy = fy; K.dCx = cx; K.dCy = cy;
+  std::vector<TObjRecoResult> res(n);
+  for (int i = 0; i < n; ++i) memcpy(res[i].tWorld2Cam, poses16 + 16 * i, 16 * sizeof(float));
+  std::vector<int> trk;
+  const int rc = CadRecoTrack((CObjRecoCAD *)h, d, K, res, &trk);
+  for (int i = 0; i < n; ++i) {
+    memcpy(poses16 + 16 * i, res[i].tWorld2Cam, 16 * sizeof(float));
+    tracked[i] = i < (int)trk.size() ? trk[i] : 0;
+  }
+  return rc;
+}
 int cadreco_write_png16(const char *path, const unsigned short *px, int w, int h)
 {
   std::string err;

@@ -2865,38 +2865,47 @@ int fl_launch_detection(fl_detector *det, int n_jobs, const fl_intrinsics *K, co
                         size_t depth_stride, uint8_t *ws, size_t ws_stride, int ranks, const FlRefineJob *d_jobs,
                         fl_recognition_result *d_results, bool longest_first)
 {
-  fl_context *ctx = det->ctx;
-  IcpArgs a = icp_args(ws, det->n_pts_max, p->icp_it_thr, p->dist_mean_thr, p->dist_diff_thr, p->icp_mode);
+  const FlDetectionTables t = {det->w0, det->h0, det->n_pts_max, det->d_ws, det->ws_stride, det->off_count, det->off_match, det->d_pyr,
+                               det->d_class_first, det->d_poses, det->d_depth_ptrs, det->d_icp_order, det->max_batch};
+  return fl_launch_detection_tables(det->ctx, t, n_jobs, K, p, depth, depth_stride, ws, ws_stride, ranks, d_jobs, d_results, longest_first);
+}
+
+// The same launch on tables the caller names (a detector's, above, or a tracker's: fl_track.hip).
+int fl_launch_detection_tables(fl_context *ctx, const FlDetectionTables &t, int n_jobs, const fl_intrinsics *K, const fl_recognition_params *p,
+                               const uint16_t *depth, size_t depth_stride, uint8_t *ws, size_t ws_stride, int ranks, const FlRefineJob *d_jobs,
+                               fl_recognition_result *d_results, bool longest_first)
+{
+  IcpArgs a = icp_args(ws, t.n_pts_max, p->icp_it_thr, p->dist_mean_thr, p->dist_diff_thr, p->icp_mode);
   a.ws_stride = ws_stride;
-  a.w = det->w0;
-  a.h = det->h0;
+  a.w = t.w;
+  a.h = t.h;
   a.fx = (float)K->fx;
   a.fy = (float)K->fy;
   a.cx = (float)K->cx;
   a.cy = (float)K->cy;
   a.job.kind = 0;
-  a.frame_ws = det->d_ws;
-  a.frame_stride = det->ws_stride;
+  a.frame_ws = t.frame_ws;
+  a.frame_stride = t.frame_stride;
   a.ranks = ranks;
   a.scene_base = depth;
   a.scene_stride = depth_stride;
-  a.off_count = det->off_count;
-  a.off_match = det->off_match;
-  a.pyr = det->d_pyr;
-  a.class_first = det->d_class_first;
-  a.poses = det->d_poses;
-  a.depth_ptrs = det->d_depth_ptrs;
+  a.off_count = t.off_count;
+  a.off_match = t.off_match;
+  a.pyr = t.pyr;
+  a.class_first = t.class_first;
+  a.poses = t.poses;
+  a.depth_ptrs = t.depth_ptrs;
   a.results = d_results;
   a.jobs = d_jobs;
-  if (longest_first && n_jobs > 4 * ctx->cus && n_jobs <= ICP_ORDER_MAX && det->d_icp_order && ctx->opt.icp_order != 0) {
-    int *d_size = det->d_icp_order + det->max_batch;
+  if (longest_first && n_jobs > 4 * ctx->cus && n_jobs <= ICP_ORDER_MAX && t.icp_order && ctx->opt.icp_order != 0) {
+    int *d_size = t.icp_order + t.order_cap;
     hipLaunchKernelGGL(k_icp_count, dim3(n_jobs), dim3(256), 0, ctx->stream, a, d_size);
     int m = 1;
     while (m < n_jobs) m <<= 1;
     hipLaunchKernelGGL(k_icp_order, dim3(1), dim3(1024), sizeof(unsigned long long) * (size_t)m, ctx->stream, (const int *)d_size, n_jobs,
-                       det->d_icp_order);
+                       t.icp_order);
     FL_HIP(ctx, hipGetLastError());
-    a.order = det->d_icp_order;
+    a.order = t.icp_order;
   }
   return icp_launch(ctx, n_jobs, a);
 }

@@ -303,3 +303,30 @@ int fl_icp_prepare(fl_detector *det);      // fl_detector_finalize: job-order bu
 int fl_launch_detection(fl_detector *det, int n_jobs, const fl_intrinsics *K, const fl_recognition_params *p, const uint16_t *depth,
                         size_t depth_stride, uint8_t *ws, size_t ws_stride, int ranks, const FlRefineJob *d_jobs,
                         fl_recognition_result *d_results, bool longest_first);
+// The device arrays the recognition branch of the ICP kernel reads, whoever owns them: a detector's (fl_launch_detection
+// fills this from the detector) or a tracker's (fl_track.hip, which always goes through the job list: frame_ws stays null).
+struct FlDetectionTables {
+  int w, h, n_pts_max;                   // frame size; capacity in points of one ICP workspace
+  const uint8_t *frame_ws;               // frame workspaces holding the match lists (jobs without a job list)
+  size_t frame_stride, off_count, off_match;
+  const FlPyrInfo *pyr;
+  const int *class_first;
+  const float *poses;
+  const uint16_t *const *depth_ptrs;
+  int *icp_order;                        // 2 * order_cap ints for the longest-first order, or null
+  int order_cap;
+};
+int fl_launch_detection_tables(fl_context *ctx, const FlDetectionTables &t, int n_jobs, const fl_intrinsics *K, const fl_recognition_params *p,
+                               const uint16_t *depth, size_t depth_stride, uint8_t *ws, size_t ws_stride, int ranks, const FlRefineJob *d_jobs,
+                               fl_recognition_result *d_results, bool longest_first);
+// render
+// fl_render_views' checks of a host mesh (FL_ERR_INVALID with `who` in the text), and its launch part for one chunk of at most
+// fl_render_chunk_views(w, h) views on arrays that are already on the device: clears the chunk's depth keys (8 bytes per
+// pixel and view), rasterises, resolves into the outputs that are not null (views back to back).  light: unit vector.
+struct FlRenderMesh { const float *vtx, *nrm; const uint8_t *col; const int32_t *tri; int n_t; };
+int fl_render_check_mesh(fl_context *ctx, const char *who, const float *vertices, const float *normals, int n_vertices,
+                         const int32_t *triangles, int n_triangles);
+int fl_render_chunk_views(int w, int h);
+int fl_launch_render_chunk(fl_context *ctx, const FlRenderMesh &mesh, const float *d_poses13, int n_views, int w, int h, float fx, float fy,
+                           float cx, float cy, const float light[3], float ambient, unsigned long long *keys, uint8_t *bgr, uint16_t *depth,
+                           uint8_t *mask, int32_t *tri);

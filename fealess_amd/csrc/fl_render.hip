@@ -217,10 +217,53 @@ bool finite_all(const float *p, size_t n)
 }  // namespace
 
 // views per chunk: FL_RENDER_CHUNK_VIEWS, fewer when their pixels would pass FL_RENDER_CHUNK_PIXELS
-static int render_chunk_views(int w, int h)
+int fl_render_chunk_views(int w, int h)
 {
   const long long px = (long long)w * h;
   return (int)std::max(1LL, std::min((long long)FL_RENDER_CHUNK_VIEWS, (long long)FL_RENDER_CHUNK_PIXELS / px));
+}
+
+int fl_render_check_mesh(fl_context *ctx, const char *who, const float *vertices, const float *normals, int n_vertices,
+                         const int32_t *triangles, int n_triangles)
+{
+  if (!vertices || !triangles || n_vertices < 3 || n_triangles < 1 || n_vertices > FL_RENDER_MAX_PRIMS || n_triangles > FL_RENDER_MAX_PRIMS)
+    return fl_set_error(ctx, FL_ERR_INVALID, "%s: null input or counts out of range", who);
+  const size_t nv3 = (size_t)n_vertices * 3, nt3 = (size_t)n_triangles * 3;
+  for (size_t i = 0; i < nt3; ++i)
+    if (triangles[i] < 0 || triangles[i] >= n_vertices)
+      return fl_set_error(ctx, FL_ERR_INVALID, "%s: triangle %zu has vertex index %d outside [0, %d)", who, i / 3, triangles[i], n_vertices);
+  if (!finite_all(vertices, nv3) || (normals && !finite_all(normals, nv3)))
+    return fl_set_error(ctx, FL_ERR_INVALID, "%s: non-finite vertex or normal", who);
+  return FL_OK;
+}
+
+// One chunk of views on device arrays: clear the keys, k_raster, k_resolve (queued on the context's stream).
+int fl_launch_render_chunk(fl_context *ctx, const FlRenderMesh &mesh, const float *d_poses13, int n_views, int w, int h, float fx, float fy,
+                           float cx, float cy, const float light[3], float ambient, unsigned long long *keys, uint8_t *bgr, uint16_t *depth,
+                           uint8_t *mask, int32_t *tri)
+{
+  RenderArgs a;
+  a.vtx = mesh.vtx;
+  a.nrm = mesh.nrm;
+  a.col = mesh.col;
+  a.tri = mesh.tri;
+  a.pose = d_poses13;
+  a.n_t = mesh.n_t;
+  a.w = w;
+  a.h = h;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+  a.ifx = 1.0f / fx;
+  a.ify = 1.0f / fy;
+  a.lx = light[0]; a.ly = light[1]; a.lz = light[2];
+  a.ambient = ambient;
+  const size_t cpx = (size_t)n_views * w * h;
+  FL_HIP(ctx, hipMemsetAsync(keys, 0xFF, cpx * 8, ctx->stream));
+  hipLaunchKernelGGL(k_raster, dim3((mesh.n_t + RB / FL_WAVE - 1) / (RB / FL_WAVE), n_views), dim3(RB), 0, ctx->stream, a, keys);
+  FL_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_resolve, dim3((unsigned)((cpx + 255) / 256)), dim3(256), 0, ctx->stream, a, (const unsigned long long *)keys,
+                     (long long)cpx, bgr, depth, mask, tri);
+  FL_HIP(ctx, hipGetLastError());
+  return FL_OK;
 }
 
 extern "C" int fl_render_views(fl_context *ctx, const float *vertices, const float *normals, const uint8_t *colors, int n_vertices,
@@ -248,16 +291,14 @@ extern "C" int fl_render_views(fl_context *ctx, const float *vertices, const flo
   if (!(ambient >= 0.f && ambient <= 1.f) || !(l2 > 0.f) || !std::isfinite(l2))
     return fl_set_error(ctx, FL_ERR_INVALID, "fl_render_views: ambient outside [0, 1] or a zero / non-finite light vector");
   const size_t nv3 = (size_t)n_vertices * 3, nt3 = (size_t)n_triangles * 3;
-  for (size_t i = 0; i < nt3; ++i)
-    if (triangles[i] < 0 || triangles[i] >= n_vertices)
-      return fl_set_error(ctx, FL_ERR_INVALID, "fl_render_views: triangle %zu has vertex index %d outside [0, %d)", i / 3, triangles[i], n_vertices);
-  if (!finite_all(vertices, nv3) || (normals && !finite_all(normals, nv3)) || !finite_all(poses13, (size_t)n_views * 13))
-    return fl_set_error(ctx, FL_ERR_INVALID, "fl_render_views: non-finite vertex, normal or pose");
+  int rc = fl_render_check_mesh(ctx, "fl_render_views", vertices, normals, n_vertices, triangles, n_triangles);
+  if (rc) return rc;
+  if (!finite_all(poses13, (size_t)n_views * 13)) return fl_set_error(ctx, FL_ERR_INVALID, "fl_render_views: non-finite pose");
   const float ll = sqrtf(l2);
 
   FL_HIP(ctx, hipSetDevice(ctx->device));
   const size_t px = (size_t)w * h;
-  const int cv = render_chunk_views(w, h);
+  const int cv = fl_render_chunk_views(w, h);
   // scratch: mesh | poses of a chunk | keys of a chunk | (host outputs) staging of a chunk
   size_t off = 0;
   auto take = [&](size_t b) { size_t o = off; off += fl_align(b, 256); return o; };
@@ -266,7 +307,7 @@ extern "C" int fl_render_views(fl_context *ctx, const float *vertices, const flo
   const size_t o_bgr = take(mem == FL_MEM_HOST && bgr ? (size_t)cv * px * 3 : 0), o_dep = take(mem == FL_MEM_HOST && depth ? (size_t)cv * px * 2 : 0),
                o_msk = take(mem == FL_MEM_HOST && mask ? (size_t)cv * px : 0), o_idx = take(mem == FL_MEM_HOST && tri ? (size_t)cv * px * 4 : 0);
   void *sv = nullptr;
-  int rc = fl_scratch(ctx, off, &sv);
+  rc = fl_scratch(ctx, off, &sv);
   if (rc) return rc;
   uint8_t *s = (uint8_t *)sv;
   FL_HIP(ctx, hipMemcpyAsync(s + o_vtx, vertices, nv3 * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -274,20 +315,9 @@ extern "C" int fl_render_views(fl_context *ctx, const float *vertices, const flo
   if (colors) FL_HIP(ctx, hipMemcpyAsync(s + o_col, colors, nv3, hipMemcpyHostToDevice, ctx->stream));
   FL_HIP(ctx, hipMemcpyAsync(s + o_tri, triangles, nt3 * 4, hipMemcpyHostToDevice, ctx->stream));
 
-  RenderArgs a;
-  a.vtx = (const float *)(s + o_vtx);
-  a.nrm = normals ? (const float *)(s + o_nrm) : nullptr;
-  a.col = colors ? s + o_col : nullptr;
-  a.tri = (const int32_t *)(s + o_tri);
-  a.pose = (const float *)(s + o_pose);
-  a.n_t = n_triangles;
-  a.w = w;
-  a.h = h;
-  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
-  a.ifx = 1.0f / fx;
-  a.ify = 1.0f / fy;
-  a.lx = light[0] / ll; a.ly = light[1] / ll; a.lz = light[2] / ll;
-  a.ambient = ambient;
+  const FlRenderMesh mesh = {(const float *)(s + o_vtx), normals ? (const float *)(s + o_nrm) : nullptr, colors ? s + o_col : nullptr,
+                             (const int32_t *)(s + o_tri), n_triangles};
+  const float lu[3] = {light[0] / ll, light[1] / ll, light[2] / ll};
   unsigned long long *keys = (unsigned long long *)(s + o_keys);
   const bool host = mem == FL_MEM_HOST;
   for (int v0 = 0; v0 < n_views; v0 += cv) {
@@ -295,16 +325,11 @@ extern "C" int fl_render_views(fl_context *ctx, const float *vertices, const flo
     const size_t cpx = (size_t)n * px, g0 = (size_t)v0 * px;
     // the pose upload reuses the chunk's slot: stream-ordered behind the previous chunk's kernels
     FL_HIP(ctx, hipMemcpyAsync(s + o_pose, poses13 + (size_t)13 * v0, (size_t)n * 13 * 4, hipMemcpyHostToDevice, ctx->stream));
-    FL_HIP(ctx, hipMemsetAsync(keys, 0xFF, cpx * 8, ctx->stream));
-    hipLaunchKernelGGL(k_raster, dim3((n_triangles + RB / FL_WAVE - 1) / (RB / FL_WAVE), n), dim3(RB), 0, ctx->stream, a, keys);
-    FL_HIP(ctx, hipGetLastError());
     uint8_t *ob = bgr ? (host ? s + o_bgr : bgr + 3 * g0) : nullptr;
     uint16_t *od = depth ? (host ? (uint16_t *)(s + o_dep) : depth + g0) : nullptr;
     uint8_t *om = mask ? (host ? s + o_msk : mask + g0) : nullptr;
     int32_t *ot = tri ? (host ? (int32_t *)(s + o_idx) : tri + g0) : nullptr;
-    hipLaunchKernelGGL(k_resolve, dim3((unsigned)((cpx + 255) / 256)), dim3(256), 0, ctx->stream, a, (const unsigned long long *)keys,
-                       (long long)cpx, ob, od, om, ot);
-    FL_HIP(ctx, hipGetLastError());
+    if ((rc = fl_launch_render_chunk(ctx, mesh, (const float *)(s + o_pose), n, w, h, fx, fy, cx, cy, lu, ambient, keys, ob, od, om, ot))) return rc;
     if (host) {
       if (bgr) FL_HIP(ctx, hipMemcpyAsync(bgr + 3 * g0, ob, cpx * 3, hipMemcpyDeviceToHost, ctx->stream));
       if (depth) FL_HIP(ctx, hipMemcpyAsync(depth + g0, od, cpx * 2, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,0 +1,456 @@
+// fl_track.hip -- 6-DoF model-based tracking (fl_tracker_create / fl_track_batch, include/fealess_hip.h): the batched z-buffer
+// rasteriser of fl_render.hip and the ICP workgroup per job of fl_icp.hip, joined on the device.  No counterpart in the
+// reference, which links a 2-D KCF box tracker it never calls (test/linemod_acq.cpp:108-150).
+//
+// One pass of a call, all on the context's stream:
+//   fl_launch_render_chunk   the mesh at every track's pose, depth only, K = 608 / 608 / 320 / 240 (the K crop_clouds
+//                            back-projects a model image with, fl_icp.hip; ICP/detection.cpp:35-36)
+//   k_track_rects            one workgroup per track: bounding box of the render, the rectangle rule, the render x 10 inside
+//                            rect_model, and the records the ICP kernel's job-list path reads for slot t: pyr[t], depth_ptrs[t],
+//                            jobs[t] (the pose is already at poses[13 t]); frame = -1 for a slot that has nothing to refine
+//   fl_launch_detection_tables   k_icp_pipeline over the n_tracks slots, through its job list: class_first = {0}, so slot t's
+//                            "template" is g = t
+//   k_track_finish           one thread per track: the lost rule, the result record, the pose of the next pass
+// The rectangle rule is stated in integers in include/fealess_hip.h and in numpy in tests/track_model.py; the shift is fp64,
+// one IEEE operation per operator (the Makefile's -ffp-contract=off: hipcc would contract a * b + c otherwise).
+#include "fl_internal.h"
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+
+namespace {
+
+constexpr int TB = 256;                         // k_track_rects: threads per track
+constexpr int TRACK_EVENTS = 2 + 4 * FL_TRACK_MAX_PASSES;
+constexpr double MODEL_F = 608.0, MODEL_CX = 320.0, MODEL_CY = 240.0;   // initInternalMat (ICP/common.cpp:358)
+constexpr double SHIFT_MAX = 1048576.0;         // 2^20: a shift beyond it cannot leave a pixel of an 8192-pixel image in view
+
+struct TrackArgs {
+  int n_tracks, w, h, margin, max_crop_px;
+  double fx, fy, cx, cy;                        // the scene camera
+  uint16_t *render;                             // n_tracks images of w * h, views back to back
+  const int32_t *frame_of;
+  float *poses;                                 // n_tracks * 13: the pose each pass starts from
+  const float *poses_in;                        // n_tracks * 13: the poses the call came in with
+  int32_t *lost;                                // per track: 1 once it is not tracked
+  FlPyrInfo *pyr;
+  const uint16_t **depth_ptrs;
+  FlRefineJob *jobs;
+  const fl_recognition_result *res;
+  fl_track_result *out;
+  float max_dist_mean, min_px_ratio;
+};
+
+__device__ __forceinline__ void bbox_add(int idx, int w, int &x0, int &x1, int &y0, int &y1)
+{
+  const int y = idx / w, x = idx - y * w;
+  x0 = min(x0, x); x1 = max(x1, x);
+  y0 = min(y0, y); y1 = max(y1, y);
+}
+
+__device__ __forceinline__ void pose_to_4x4(const float *p13, float *m)
+{
+  for (int k = 0; k < 12; ++k) m[k] = p13[k];
+  m[12] = m[13] = m[14] = 0.f;
+  m[15] = 1.f;
+}
+
+__global__ __launch_bounds__(TB) void k_track_rects(TrackArgs a)
+{
+  __shared__ int red[4][TB / FL_WAVE];
+  __shared__ int rect[5];                       // rect_model after the clip, and whether the slot runs
+  const int t = blockIdx.x, tid = threadIdx.x;
+  if (a.lost[t]) {                              // not tracked in an earlier pass: the slot exits at once (uniform per workgroup)
+    if (tid == 0) a.jobs[t].frame = -1;
+    return;
+  }
+  const int px = a.w * a.h;                     // <= FL_RENDER_MAX_DIM^2, fits an int
+  uint16_t *img = a.render + (size_t)t * px;
+  int x0 = a.w, x1 = -1, y0 = a.h, y1 = -1;
+  if ((px & 7) == 0) {                          // every image starts on a 16-byte boundary: eight pixels per load
+    // one workgroup reads a whole image, so the loop is bound by the latency of its loads: four of them in flight per thread
+    const uint4 *v4 = (const uint4 *)img;
+    const int n8 = px / 8;
+    for (int i0 = tid; i0 < n8; i0 += 4 * TB) {
+      uint4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * TB;
+        v[u] = i < n8 ? v4[i] : make_uint4(0u, 0u, 0u, 0u);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if ((v[u].x | v[u].y | v[u].z | v[u].w) == 0u) continue;
+        const int i = i0 + u * TB;
+        const unsigned wd[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+        for (int k = 0; k < 4; ++k) {
+          if (wd[k] & 0xffffu) bbox_add(8 * i + 2 * k, a.w, x0, x1, y0, y1);
+          if (wd[k] >> 16) bbox_add(8 * i + 2 * k + 1, a.w, x0, x1, y0, y1);
+        }
+      }
+    }
+  } else {
+    for (int i = tid; i < px; i += TB)
+      if (img[i]) bbox_add(i, a.w, x0, x1, y0, y1);
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    x0 = min(x0, __shfl_xor(x0, s, FL_WAVE)); x1 = max(x1, __shfl_xor(x1, s, FL_WAVE));
+    y0 = min(y0, __shfl_xor(y0, s, FL_WAVE)); y1 = max(y1, __shfl_xor(y1, s, FL_WAVE));
+  }
+  if ((tid & (FL_WAVE - 1)) == 0) {
+    const int wv = tid / FL_WAVE;
+    red[0][wv] = x0; red[1][wv] = x1; red[2][wv] = y0; red[3][wv] = y1;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int wv = 0; wv < TB / FL_WAVE; ++wv) {
+      x0 = min(x0, red[0][wv]); x1 = max(x1, red[1][wv]);
+      y0 = min(y0, red[2][wv]); y1 = max(y1, red[3][wv]);
+    }
+    int rm[4] = {0, 0, 0, 0}, rr[4] = {0, 0, 0, 0};
+    int status = FL_OK;
+    bool run = x1 >= x0;                        // an empty render: out of view
+    if (run) {
+      const int mx0 = max(x0 - a.margin, 0), my0 = max(y0 - a.margin, 0);
+      const int mx1 = min(x1 + a.margin, a.w - 1), my1 = min(y1 + a.margin, a.h - 1);
+      const float *p = a.poses + 13 * (size_t)t;
+      const double tx = (double)p[3], ty = (double)p[7], tz = (double)p[11];
+      const double sx = (a.fx - MODEL_F) * (tx / tz) + (a.cx - MODEL_CX), sy = (a.fy - MODEL_F) * (ty / tz) + (a.cy - MODEL_CY);
+      run = fabs(sx) <= SHIFT_MAX && fabs(sy) <= SHIFT_MAX;    // false for NaN too
+      if (run) {
+        const int dx = (int)rint(sx), dy = (int)rint(sy);
+        const int cx0 = max(mx0 + dx, 0), cy0 = max(my0 + dy, 0), cx1 = min(mx1 + dx, a.w - 1), cy1 = min(my1 + dy, a.h - 1);
+        run = cx1 >= cx0 && cy1 >= cy0;
+        if (run) {
+          rr[0] = cx0; rr[1] = cy0; rr[2] = cx1 - cx0 + 1; rr[3] = cy1 - cy0 + 1;
+          rm[0] = cx0 - dx; rm[1] = cy0 - dy; rm[2] = rr[2]; rm[3] = rr[3];
+          if ((long long)rm[2] * rm[3] > a.max_crop_px) { status = FL_ERR_OVERFLOW; run = false; }
+        }
+      }
+    }
+    fl_track_result *o = a.out + t;
+    o->status = status;
+    for (int k = 0; k < 4; ++k) { o->rect_model[k] = rm[k]; o->rect_ref[k] = rr[k]; rect[k] = rm[k]; }
+    rect[4] = run ? 1 : 0;
+    FlPyrInfo pi;
+    pi.class_idx = 0; pi.template_id = t;
+    pi.off_x0 = rm[0]; pi.off_y0 = rm[1]; pi.width0 = rm[2]; pi.height0 = rm[3];
+    pi.depth_slot = t; pi.pad = 0;
+    a.pyr[t] = pi;
+    a.depth_ptrs[t] = img;
+    FlRefineJob j;
+    j.frame = run ? a.frame_of[t] : -1;
+    j.match.x = rr[0]; j.match.y = rr[1]; j.match.similarity = 0.f; j.match.class_idx = 0; j.match.template_id = t;
+    a.jobs[t] = j;
+  }
+  __syncthreads();
+  if (!rect[4]) return;
+  // millimetres -> 0.1 mm inside rect_model, saturating (what the recognition branch of the ICP kernel reads)
+  const int rx = rect[0], ry = rect[1], rw = rect[2], n = rw * rect[3];
+  for (int i = tid; i < n; i += TB) {
+    const int y = i / rw, x = i - y * rw;
+    uint16_t *q = img + (size_t)(ry + y) * a.w + rx + x;
+    const unsigned v = 10u * (unsigned)*q;
+    *q = (uint16_t)(v > 65535u ? 65535u : v);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_track_finish(TrackArgs a)
+{
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= a.n_tracks || a.lost[t]) return;     // lost earlier: the record of the pass that lost it stands
+  fl_track_result *o = a.out + t;
+  bool lost = a.jobs[t].frame < 0;              // nothing to refine: out of view or too large a crop (status says which)
+  if (!lost) {
+    const fl_recognition_result &r = a.res[t];
+    o->det = r.det;
+    if (r.status != FL_OK) o->status = r.status;
+    const fl_icp_result &ic = r.det.icp;
+    lost = r.status != FL_OK || !r.found || ic.dist_mean < 0.f || (a.max_dist_mean > 0.f && ic.dist_mean > a.max_dist_mean) ||
+           (a.min_px_ratio > 0.f && ic.px_ratio < a.min_px_ratio);
+    if (!lost) {
+      for (int k = 0; k < 16; ++k) o->pose[k] = r.pose[k];
+      float *p = a.poses + 13 * (size_t)t;      // the next pass starts here
+      for (int k = 0; k < 12; ++k) p[k] = r.pose[k];
+      o->tracked = 1;
+      return;
+    }
+  } else {
+    memset(&o->det, 0, sizeof(o->det));
+  }
+  a.lost[t] = 1;
+  o->tracked = 0;
+  pose_to_4x4(a.poses_in + 13 * (size_t)t, o->pose);
+}
+
+bool finite_all(const float *p, size_t n)
+{
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+}  // namespace
+
+struct fl_tracker {
+  fl_context *ctx = nullptr;
+  bool owns_ctx = false;                        // fl_dev_tracker_create_host: a context without a device, released with the tracker
+  int w = 0, h = 0, max_frames = 0, max_tracks = 0, max_crop_px = 0, n_t = 0;
+  int chunk = 0;                                // views per render launch
+  uint8_t *d_mem = nullptr;                     // the one device allocation
+  const float *d_vtx = nullptr;
+  const int32_t *d_tri = nullptr;
+  uint8_t *d_frames = nullptr;
+  size_t frame_stride = 0;
+  uint16_t *d_render = nullptr;
+  unsigned long long *d_keys = nullptr;
+  uint8_t *d_icp = nullptr;
+  size_t ws_one = 0;
+  float *d_poses = nullptr, *d_poses_in = nullptr;
+  int32_t *d_frame_of = nullptr, *d_lost = nullptr, *d_class_first = nullptr;
+  FlPyrInfo *d_pyr = nullptr;
+  const uint16_t **d_depth_ptrs = nullptr;
+  FlRefineJob *d_jobs = nullptr;
+  fl_recognition_result *d_res = nullptr;
+  fl_track_result *d_out = nullptr;
+  uint8_t *h_stage = nullptr;                   // pinned: poses | frame_of | results
+  hipEvent_t ev[TRACK_EVENTS] = {nullptr};      // 0: start, 1: inputs on the device, then per pass render / rects / ICP / finish
+  int last_passes = 0;
+};
+
+static const fl_track_params k_track_defaults = {12, 1, 10, 0.5f, 0.01f, FL_ICP_POINT_TO_PLANE, 0.f, 0.f};
+
+// the argument checks of fl_tracker_create that concern the sizes (shared with fl_dev_tracker_create_host)
+static int tracker_sizes_ok(fl_context *ctx, int w, int h, int max_frames, int max_tracks, int max_crop_px)
+{
+  if (w < 1 || h < 1 || w > FL_RENDER_MAX_DIM || h > FL_RENDER_MAX_DIM)
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_tracker_create: image size %dx%d outside 1..%d", w, h, FL_RENDER_MAX_DIM);
+  if (max_frames < 1 || max_tracks < 1 || max_frames > FL_TRACK_MAX_TRACKS || max_tracks > FL_TRACK_MAX_TRACKS)
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_tracker_create: max_frames %d / max_tracks %d outside 1..%d", max_frames, max_tracks, FL_TRACK_MAX_TRACKS);
+  const long long px = (long long)w * h;
+  if (max_crop_px < 1 || max_crop_px > px || max_crop_px > FL_TRACK_MAX_CROP_PX)
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_tracker_create: max_crop_px %d outside [1, min(w * h, %d)]", max_crop_px, FL_TRACK_MAX_CROP_PX);
+  if (fl_align(fl_icp_ws_bytes(max_crop_px), 256) * (size_t)max_tracks > ((size_t)96 << 30))
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_tracker_create: %d ICP workspaces of %d pixels pass 96 GB", max_tracks, max_crop_px);
+  return FL_OK;
+}
+
+extern "C" void fl_tracker_destroy(fl_tracker *trk)
+{
+  if (!trk) return;
+  if (trk->ctx->device >= 0) {
+    (void)hipSetDevice(trk->ctx->device);
+    (void)hipStreamSynchronize(trk->ctx->stream);
+    for (hipEvent_t e : trk->ev)
+      if (e) (void)hipEventDestroy(e);
+    if (trk->d_mem) (void)hipFree(trk->d_mem);
+    if (trk->h_stage) (void)hipHostFree(trk->h_stage);
+  }
+  if (trk->owns_ctx) delete trk->ctx;
+  delete trk;
+}
+
+static size_t stage_bytes(int max_tracks)
+{
+  return fl_align((size_t)max_tracks * 13 * 4, 256) + fl_align((size_t)max_tracks * 4, 256) + sizeof(fl_track_result) * (size_t)max_tracks;
+}
+
+extern "C" int fl_tracker_create(fl_context *ctx, const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
+                                 int w, int h, int max_frames, int max_tracks, int max_crop_px, fl_tracker **out)
+{
+  if (!ctx || !out) return FL_ERR_INVALID;
+  int rc = fl_render_check_mesh(ctx, "fl_tracker_create", vertices, nullptr, n_vertices, triangles, n_triangles);
+  if (rc || (rc = tracker_sizes_ok(ctx, w, h, max_frames, max_tracks, max_crop_px))) return rc;
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_tracker_create: the context has no device");
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  fl_tracker *trk = new fl_tracker();
+  trk->ctx = ctx;
+  trk->w = w; trk->h = h;
+  trk->max_frames = max_frames; trk->max_tracks = max_tracks; trk->max_crop_px = max_crop_px;
+  trk->n_t = n_triangles;
+  trk->chunk = std::min(max_tracks, fl_render_chunk_views(w, h));
+  const size_t px = (size_t)w * h, nv3 = (size_t)n_vertices * 3, nt3 = (size_t)n_triangles * 3, T = (size_t)max_tracks;
+  trk->frame_stride = fl_align(px * 2, 256);
+  trk->ws_one = fl_align(fl_icp_ws_bytes(max_crop_px), 256);
+  size_t off = 0;
+  auto take = [&](size_t b) { const size_t o = off; off += fl_align(b, 256); return o; };
+  const size_t o_vtx = take(nv3 * 4), o_tri = take(nt3 * 4), o_frames = take(trk->frame_stride * max_frames), o_render = take(T * px * 2),
+               o_keys = take((size_t)trk->chunk * px * 8), o_icp = take(trk->ws_one * T), o_poses = take(T * 13 * 4), o_pin = take(T * 13 * 4),
+               o_fof = take(T * 4), o_lost = take(T * 4), o_cf = take(4), o_pyr = take(T * sizeof(FlPyrInfo)), o_dp = take(T * sizeof(void *)),
+               o_jobs = take(T * sizeof(FlRefineJob)), o_res = take(T * sizeof(fl_recognition_result)), o_out = take(T * sizeof(fl_track_result));
+  auto fail = [&](hipError_t e, const char *what) {
+    fl_set_error(ctx, FL_ERR_HIP, "fl_tracker_create: %s -> %s", what, hipGetErrorString(e));
+    fl_tracker_destroy(trk);
+    return FL_ERR_HIP;
+  };
+  hipError_t e;
+  if ((e = hipMalloc((void **)&trk->d_mem, off)) != hipSuccess) { trk->d_mem = nullptr; return fail(e, "hipMalloc"); }
+  if ((e = hipHostMalloc((void **)&trk->h_stage, stage_bytes(max_tracks), hipHostMallocDefault)) != hipSuccess) { trk->h_stage = nullptr; return fail(e, "hipHostMalloc"); }
+  for (hipEvent_t &v : trk->ev)
+    if ((e = hipEventCreate(&v)) != hipSuccess) { v = nullptr; return fail(e, "hipEventCreate"); }
+  uint8_t *m = trk->d_mem;
+  trk->d_vtx = (const float *)(m + o_vtx);
+  trk->d_tri = (const int32_t *)(m + o_tri);
+  trk->d_frames = m + o_frames;
+  trk->d_render = (uint16_t *)(m + o_render);
+  trk->d_keys = (unsigned long long *)(m + o_keys);
+  trk->d_icp = m + o_icp;
+  trk->d_poses = (float *)(m + o_poses);
+  trk->d_poses_in = (float *)(m + o_pin);
+  trk->d_frame_of = (int32_t *)(m + o_fof);
+  trk->d_lost = (int32_t *)(m + o_lost);
+  trk->d_class_first = (int32_t *)(m + o_cf);
+  trk->d_pyr = (FlPyrInfo *)(m + o_pyr);
+  trk->d_depth_ptrs = (const uint16_t **)(m + o_dp);
+  trk->d_jobs = (FlRefineJob *)(m + o_jobs);
+  trk->d_res = (fl_recognition_result *)(m + o_res);
+  trk->d_out = (fl_track_result *)(m + o_out);
+  // the mesh, once; the one class every slot's "template" belongs to starts at g = 0
+  if ((e = hipMemcpyAsync(m + o_vtx, vertices, nv3 * 4, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(m + o_tri, triangles, nt3 * 4, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+      (e = hipMemsetAsync(m + o_cf, 0, 4, ctx->stream)) != hipSuccess || (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
+    return fail(e, "mesh upload");
+  *out = trk;
+  return FL_OK;
+}
+
+// Development / test aid, exported but not part of the ABI: a tracker without a device (its own context, device = -1), for the
+// argument checks of fl_track_batch, which come before its first HIP call.  fl_tracker_destroy releases both.
+extern "C" int fl_dev_tracker_create_host(int w, int h, int max_frames, int max_tracks, int max_crop_px, fl_tracker **out)
+{
+  if (!out) return FL_ERR_INVALID;
+  fl_context *ctx = new fl_context();
+  ctx->device = -1;
+  if (tracker_sizes_ok(ctx, w, h, max_frames, max_tracks, max_crop_px)) { delete ctx; return FL_ERR_INVALID; }
+  fl_tracker *trk = new fl_tracker();
+  trk->ctx = ctx;
+  trk->owns_ctx = true;
+  trk->w = w; trk->h = h;
+  trk->max_frames = max_frames; trk->max_tracks = max_tracks; trk->max_crop_px = max_crop_px;
+  *out = trk;
+  return FL_OK;
+}
+
+// device time of the last fl_track_batch by stage, summed over its passes: {copy, render, rects, ICP, finish} in ms
+extern "C" int fl_dev_tracker_stage_ms(fl_tracker *trk, float out[5])
+{
+  if (!trk || !out || trk->last_passes < 1) return FL_ERR_INVALID;
+  for (int k = 0; k < 5; ++k) out[k] = 0.f;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, trk->ev[0], trk->ev[1]) != hipSuccess) return FL_ERR_HIP;
+  out[0] = ms;
+  for (int p = 0; p < trk->last_passes; ++p)
+    for (int k = 0; k < 4; ++k) {
+      if (hipEventElapsedTime(&ms, trk->ev[1 + 4 * p + k], trk->ev[2 + 4 * p + k]) != hipSuccess) return FL_ERR_HIP;
+      out[1 + k] += ms;
+    }
+  return FL_OK;
+}
+
+extern "C" int fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
+                              const int32_t *frame_of_track, const float *poses13, const fl_intrinsics *K, const fl_track_params *params,
+                              fl_track_result *results)
+{
+  if (!trk) return FL_ERR_INVALID;
+  fl_context *ctx = trk->ctx;
+  if (!depth || !frame_of_track || !poses13 || !K || !results) return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: null pointer");
+  if (mem != FL_MEM_HOST && mem != FL_MEM_DEVICE) return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: bad mem %d", mem);
+  if (n_frames < 1 || n_frames > trk->max_frames || n_tracks < 1 || n_tracks > trk->max_tracks)
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: n_frames %d outside 1..%d or n_tracks %d outside 1..%d", n_frames, trk->max_frames,
+                        n_tracks, trk->max_tracks);
+  for (int i = 0; i < n_frames; ++i)
+    if (!depth[i]) return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: depth[%d] is null", i);
+  for (int t = 0; t < n_tracks; ++t)
+    if (frame_of_track[t] < 0 || frame_of_track[t] >= n_frames)
+      return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: frame_of_track[%d] = %d outside [0, %d)", t, frame_of_track[t], n_frames);
+  for (int t = 0; t < n_tracks; ++t)
+    if (!finite_all(poses13 + (size_t)13 * t, 12)) return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: non-finite pose of track %d", t);
+  if (K->width != trk->w || K->height != trk->h)
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: intrinsics are %dx%d, tracker created for %dx%d", K->width, K->height, trk->w, trk->h);
+  if (!(std::isfinite(K->fx) && K->fx > 0 && std::isfinite(K->fy) && K->fy > 0 && std::isfinite(K->cx) && std::isfinite(K->cy)))
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_batch: fx, fy must be finite and > 0, cx, cy finite");
+  const fl_track_params P = params ? *params : k_track_defaults;
+  if (P.passes < 1 || P.passes > FL_TRACK_MAX_PASSES || P.margin_px < 0 || P.margin_px > FL_RENDER_MAX_DIM || P.icp_it_thr < 0 ||
+      !std::isfinite(P.dist_mean_thr) || !std::isfinite(P.dist_diff_thr) || !std::isfinite(P.max_dist_mean) || !std::isfinite(P.min_px_ratio) ||
+      (P.icp_mode != FL_ICP_PARITY && P.icp_mode != FL_ICP_FAST && P.icp_mode != FL_ICP_POINT_TO_PLANE))
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_params: passes 1..%d, margin_px 0..%d, icp_it_thr >= 0, finite thresholds, a known icp_mode",
+                        FL_TRACK_MAX_PASSES, FL_RENDER_MAX_DIM);
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_track_batch: the tracker has no device");
+
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t px = (size_t)trk->w * trk->h, T = (size_t)n_tracks;
+  hipStream_t st = ctx->stream;
+  FL_HIP(ctx, hipEventRecord(trk->ev[0], st));
+  // 1. frames into their slots, poses and frame indices to the device (through the pinned block)
+  for (int i = 0; i < n_frames; ++i)
+    FL_HIP(ctx, hipMemcpyAsync(trk->d_frames + trk->frame_stride * i, depth[i], px * 2,
+                               mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  float *h_poses = (float *)trk->h_stage;
+  int32_t *h_fof = (int32_t *)(trk->h_stage + fl_align((size_t)trk->max_tracks * 13 * 4, 256));
+  fl_track_result *h_out = (fl_track_result *)((uint8_t *)h_fof + fl_align((size_t)trk->max_tracks * 4, 256));
+  memcpy(h_poses, poses13, T * 13 * 4);
+  memcpy(h_fof, frame_of_track, T * 4);
+  FL_HIP(ctx, hipMemcpyAsync(trk->d_poses_in, h_poses, T * 13 * 4, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(trk->d_poses, trk->d_poses_in, T * 13 * 4, hipMemcpyDeviceToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(trk->d_frame_of, h_fof, T * 4, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemsetAsync(trk->d_lost, 0, T * 4, st));
+  FL_HIP(ctx, hipMemsetAsync(trk->d_out, 0, T * sizeof(fl_track_result), st));
+  FL_HIP(ctx, hipEventRecord(trk->ev[1], st));
+
+  TrackArgs a;
+  a.n_tracks = n_tracks;
+  a.w = trk->w; a.h = trk->h;
+  a.margin = P.margin_px;
+  a.max_crop_px = trk->max_crop_px;
+  a.fx = K->fx; a.fy = K->fy; a.cx = K->cx; a.cy = K->cy;
+  a.render = trk->d_render;
+  a.frame_of = trk->d_frame_of;
+  a.poses = trk->d_poses;
+  a.poses_in = trk->d_poses_in;
+  a.lost = trk->d_lost;
+  a.pyr = trk->d_pyr;
+  a.depth_ptrs = trk->d_depth_ptrs;
+  a.jobs = trk->d_jobs;
+  a.res = trk->d_res;
+  a.out = trk->d_out;
+  a.max_dist_mean = P.max_dist_mean;
+  a.min_px_ratio = P.min_px_ratio;
+  const FlRenderMesh mesh = {trk->d_vtx, nullptr, nullptr, trk->d_tri, trk->n_t};
+  const float headlight[3] = {0.f, 0.f, 1.f};
+  const FlDetectionTables tab = {trk->w, trk->h, trk->max_crop_px, nullptr, 0, 0, 0, trk->d_pyr, trk->d_class_first, trk->d_poses,
+                                 trk->d_depth_ptrs, nullptr, 0};
+  const fl_recognition_params rp = {0.f, P.icp_it_thr, P.dist_mean_thr, P.dist_diff_thr, P.icp_mode};
+  int rc;
+  for (int pass = 0; pass < P.passes; ++pass) {
+    hipEvent_t *ev = trk->ev + 2 + 4 * pass;
+    // 2. the render, at the model K whatever the scene's K is
+    for (int v0 = 0; v0 < n_tracks; v0 += trk->chunk) {
+      const int n = std::min(trk->chunk, n_tracks - v0);
+      if ((rc = fl_launch_render_chunk(ctx, mesh, trk->d_poses + (size_t)13 * v0, n, trk->w, trk->h, (float)MODEL_F, (float)MODEL_F, (float)MODEL_CX,
+                                       (float)MODEL_CY, headlight, FL_RENDER_AMBIENT, trk->d_keys, nullptr, trk->d_render + (size_t)v0 * px, nullptr,
+                                       nullptr)))
+        return rc;
+    }
+    FL_HIP(ctx, hipEventRecord(ev[0], st));
+    // 3. rectangles, the render in 0.1 mm, the job records
+    hipLaunchKernelGGL(k_track_rects, dim3(n_tracks), dim3(TB), 0, st, a);
+    FL_HIP(ctx, hipGetLastError());
+    FL_HIP(ctx, hipEventRecord(ev[1], st));
+    // 4. one ICP launch over the slots (a slot whose job has frame = -1 leaves its zeroed result alone)
+    FL_HIP(ctx, hipMemsetAsync(trk->d_res, 0, T * sizeof(fl_recognition_result), st));
+    if ((rc = fl_launch_detection_tables(ctx, tab, n_tracks, K, &rp, (const uint16_t *)trk->d_frames, trk->frame_stride, trk->d_icp, trk->ws_one, 1,
+                                         trk->d_jobs, trk->d_res, false)))
+      return rc;
+    FL_HIP(ctx, hipEventRecord(ev[2], st));
+    // 5. lost rule, result records, the next pass's poses
+    hipLaunchKernelGGL(k_track_finish, dim3((n_tracks + 63) / 64), dim3(64), 0, st, a);
+    FL_HIP(ctx, hipGetLastError());
+    FL_HIP(ctx, hipEventRecord(ev[3], st));
+  }
+  // 6. one copy, one wait
+  FL_HIP(ctx, hipMemcpyAsync(h_out, trk->d_out, T * sizeof(fl_track_result), hipMemcpyDeviceToHost, st));
+  FL_HIP(ctx, hipStreamSynchronize(st));
+  memcpy(results, h_out, T * sizeof(fl_track_result));
+  trk->last_passes = P.passes;
+  return FL_OK;
+}

@@ -425,6 +425,76 @@ int  fl_recognize_batch_instances(fl_detector *det, int n_frames, const uint8_t 
                                   int mem, const fl_intrinsics *K, const fl_recognition_params *params,
                                   const fl_instance_params *ip, fl_instance_result *results, int32_t *n_instances,
                                   int32_t *n_dropped);
+/* ---- tracking: follow recognised objects from frame to frame against the CAD mesh (no counterpart in the reference,
+ * which ships a 2-D KCF box tracker it never wired in: test/linemod_acq.cpp:108-150) ------------------------------------
+ * A track is one (object pose, depth frame) pair.  One step of one track: render the mesh at the track's pose, crop both
+ * depth images around the render, run detection() (ICP/detection.cpp:11-254) with r_match, t_match = that pose, take the
+ * composed pose.  No LINEMOD front-end, no scan, no template bank.  Several tracks may name one frame, many frames may be
+ * tracked in one call; time stepping is the caller's loop (feed results[t].pose back in as poses13).
+ *
+ * fl_tracker_create uploads the mesh (as fl_render_views takes it: vertices n * 3 f32 in mm, triangles 0-based) and
+ * allocates every device buffer once -- max_frames frame slots of w * h u16, max_tracks render images, the rasteriser's
+ * depth keys for one chunk of views, max_tracks ICP workspaces for crops of up to max_crop_px pixels (about 86 bytes per
+ * pixel), the small per-track arrays; fl_track_batch allocates nothing.  FL_ERR_INVALID: null pointers, the mesh limits
+ * of fl_render_views, w or h outside 1..FL_RENDER_MAX_DIM, max_frames or max_tracks outside 1..FL_TRACK_MAX_TRACKS,
+ * max_crop_px outside [1, min(w * h, FL_TRACK_MAX_CROP_PX)] (the crop sizes the ICP's organised search is exact for without
+ * its slow paths), more than 96 GB of ICP workspaces.  A tracker does not keep its context alive: destroy it before the context.
+ *
+ * fl_track_batch: depth[i], i < n_frames, are w * h u16 in mm, host or device memory as `mem` says; frame_of_track[t] and
+ * poses13 (the bank's layout, row-major [R|t] object -> camera in mm, the 13th float ignored) are host memory, as is
+ * results.  params == NULL: the defaults below.  K is the SCENE camera (K->width x K->height must be w x h).  Everything
+ * is queued on the context's stream and the call waits once, at the end.  Per pass:
+ *   render   the mesh at every track's pose, depth only, at w x h with K = 608 / 608 / 320 / 240 whatever the scene's K is:
+ *            detection() back-projects the model image with exactly that K (initInternalMat, ICP/common.cpp:358;
+ *            ICP/detection.cpp:35-36), so the model cloud is metrically right for any scene camera.
+ *   rects    (integers) [x0, x1] x [y0, y1] = the bounding box of the render's non-zero pixels; grown by margin_px on every
+ *            side and clamped to the image = rect_model {x, y, w, h}.  rect_ref = rect_model shifted by
+ *              dx = (int)rint((fx - 608) * (tx / tz) + (cx - 320)),  dy = (int)rint((fy - 608) * (ty / tz) + (cy - 240))
+ *            (fp64, one IEEE operation per operator, (tx, ty, tz) = the pose's translation; 0 when the scene K is the model
+ *            K; a shift that is not finite or beyond 2^20 pixels counts as out of view), then clipped to the image, and the
+ *            same clip applied to rect_model, so both keep one size and their alignment.  The render's depths inside
+ *            rect_model are multiplied by 10 (saturating at 65535): the recognition branch of the ICP reads model images in
+ *            0.1 mm through rint(d * 0.1f), which gives back the millimetres for every depth <= 6553 mm.
+ *   ICP      one launch over the n_tracks slots, exactly the refinement fl_refine_matches runs.
+ *   finish   a track is LOST when detection() found nothing (fewer than 3 paired points: icp.dist_mean < 0) or one of the two
+ *            optional gates says so; otherwise pose = detection()'s composition, R = R_icp R_in, T = R_icp (t_in + (c_ref -
+ *            c_mod)) + T_icp, which is also the next pass's input.  Passes never touch the host.
+ * A track whose render is empty (behind the camera, out of view) or whose rectangles clip to nothing: tracked = 0, status
+ * FL_OK, rects and det zero.  A track whose crop has more than max_crop_px pixels: tracked = 0, status FL_ERR_OVERFLOW, the
+ * rects reported.  A track that is not tracked in some pass stays so in the later passes and reports the pose it came in
+ * with; the other tracks are not affected.  Returns FL_OK when the batch ran, whatever the tracks' fates.
+ * FL_ERR_INVALID, nothing written: null pointers, n_frames outside 1..max_frames, n_tracks outside 1..max_tracks, a
+ * frame_of_track outside [0, n_frames), a non-finite pose or K, fx or fy <= 0, K's size not w x h, passes outside 1..4,
+ * margin_px outside 0..FL_RENDER_MAX_DIM, icp_it_thr < 0, a non-finite threshold, an unknown icp_mode or mem.
+ * Limit: both crops have the same pixel size, so a scene camera whose focal length is far from 608 sees the object at
+ * another pixel size than the render and the paired compaction of detection() pairs the wrong pixels; the reference's own
+ * Recognition() has the same limit (its templates' renders are at 608 too). */
+typedef struct fl_tracker fl_tracker;
+typedef struct {
+  int32_t margin_px;                   /* crop = the render's bounding box grown by this on every side; default 12 */
+  int32_t passes;                      /* render + ICP repeated, pass p+1 starting from pass p's pose; 1..4; default 1 */
+  int32_t icp_it_thr;                  /* as fl_recognition_params; default 10 */
+  float   dist_mean_thr, dist_diff_thr;   /* defaults 0.5, 0.01 */
+  int32_t icp_mode;                    /* default FL_ICP_POINT_TO_PLANE */
+  float   max_dist_mean;               /* > 0: a result with icp.dist_mean above it is "lost"; <= 0: no test */
+  float   min_px_ratio;                /* > 0: a result with icp.px_ratio below it is "lost"; <= 0: no test */
+} fl_track_params;
+typedef struct {
+  int32_t status;                      /* FL_OK; FL_ERR_OVERFLOW: the crop has more pixels than max_crop_px */
+  int32_t tracked;                     /* 1: pose is the new pose; 0: lost, pose = the input pose */
+  int32_t rect_model[4], rect_ref[4];  /* of the last pass that ran */
+  float   pose[16];                    /* row-major 4x4 like fl_recognition_result::pose */
+  fl_detection_result det;             /* of the last pass that ran */
+} fl_track_result;
+#define FL_TRACK_MAX_TRACKS (1 << 16)
+#define FL_TRACK_MAX_CROP_PX ((1 << 24) - 4)
+#define FL_TRACK_MAX_PASSES 4
+int  fl_tracker_create(fl_context *ctx, const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
+                       int w, int h, int max_frames, int max_tracks, int max_crop_px, fl_tracker **out);
+void fl_tracker_destroy(fl_tracker *trk);
+int  fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
+                    int n_tracks, const int32_t *frame_of_track, const float *poses13,
+                    const fl_intrinsics *K, const fl_track_params *params, fl_track_result *results);
 /* After fl_match_frame / fl_recognize_submit: copy frame `frame`'s first k sorted matches into a
  * device buffer (k * sizeof(fl_match) bytes, padded with template_id = -1) for an RCCL
  * all-gather by the caller; template ids are offset by template_id_base (the shard's first
