@@ -147,6 +147,7 @@ SIGNATURES = {
     "fl_recognize_submit": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics),
                                  C.POINTER(RecognitionParams)]),
     "fl_recognize_collect": (_I, [_P, _I, _P]),
+    "fl_recognize_collect_previous": (_I, [_P, _I, _P]),
     "fl_recognize_topk": (_I, [_P, _P, _P, _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams), _I, _P, C.POINTER(_I)]),
     "fl_recognize_batch_topk": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams), _I, _P,
                                      C.POINTER(_I)]),

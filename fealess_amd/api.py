@@ -584,6 +584,13 @@ class Detector:
         self.ctx.check(self.lib.fl_recognize_collect(self.h, n, res))
         return res
 
+    def recognize_collect_previous(self, n):
+        """The results of the batch submitted before the latest recognize_submit_*, waiting for that batch only: with
+        submit(i + 1); collect_previous(i) two batches stay in flight.  FL_ERR_STATE when there is no such batch."""
+        res = (L.RecognitionResult * n)()
+        self.ctx.check(self.lib.fl_recognize_collect_previous(self.h, n, res))
+        return res
+
     def frame_counters(self, frame):
         """fl_frame_counters: (coarse candidates, matches after sort/unique, overflow flag, marked level-0 tiles or -1)."""
         out = (C.c_int32 * 4)()

@@ -20,8 +20,11 @@ int fl_set_error(fl_context *ctx, int code, const char *fmt, ...)
   return code;
 }
 
+// (the single-shot entry points all come through here or fl_pinned before they queue work: ctx->stream first waits for
+// whatever a pipelined fl_recognize_submit left on the ICP stream)
 int fl_scratch(fl_context *ctx, size_t bytes, void **out)
 {
+  if (int rc = fl_context_join(ctx)) return rc;
   if (bytes > ctx->scratch_bytes) {
     if (ctx->scratch) {
       FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -39,6 +42,7 @@ int fl_scratch(fl_context *ctx, size_t bytes, void **out)
 
 int fl_pinned(fl_context *ctx, size_t bytes, void **out)
 {
+  if (int rc = fl_context_join(ctx)) return rc;
   if (bytes > ctx->pinned_bytes) {
     if (ctx->pinned) {
       FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -51,6 +55,43 @@ int fl_pinned(fl_context *ctx, size_t bytes, void **out)
     ctx->pinned_bytes = nb;
   }
   *out = ctx->pinned;
+  return FL_OK;
+}
+
+int fl_context_join(fl_context *ctx)
+{
+  if (!ctx->icp_pending) return FL_OK;
+  ctx->icp_pending = false;
+  FL_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_icp_tail, 0));
+  return FL_OK;
+}
+
+int fl_context_sync_all(fl_context *ctx)
+{
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->icp_stream) FL_HIP(ctx, hipStreamSynchronize(ctx->icp_stream));
+  ctx->icp_pending = false;
+  return FL_OK;
+}
+
+// pipeline_icp 1: the ICP stream at the default priority; 2 / 3: at the highest / lowest the device offers.  A stream keeps
+// the priority it was created with, so a changed option value replaces the stream once its work has finished.
+int fl_icp_stream(fl_context *ctx, hipStream_t *out)
+{
+  const long mode = ctx->opt.pipeline_icp;
+  if (ctx->icp_stream && ctx->icp_stream_mode != mode) {
+    FL_HIP(ctx, hipStreamSynchronize(ctx->icp_stream));
+    FL_HIP(ctx, hipStreamDestroy(ctx->icp_stream));
+    ctx->icp_stream = nullptr;
+  }
+  if (!ctx->icp_stream) {
+    int least = 0, greatest = 0;
+    FL_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    FL_HIP(ctx, hipStreamCreateWithPriority(&ctx->icp_stream, hipStreamNonBlocking, mode == 2 ? greatest : (mode == 3 ? least : 0)));
+    ctx->icp_stream_mode = mode;
+  }
+  if (!ctx->ev_icp_tail) FL_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_icp_tail, hipEventDisableTiming));
+  *out = ctx->icp_stream;
   return FL_OK;
 }
 
@@ -68,6 +109,7 @@ static const FlOptionName fl_option_names[] = {
   {"eager_frontend", "FL_EAGER_FRONTEND", &fl_context::Options::eager_frontend, false, 0, 1},
   {"dev_poison", "FL_DEV_POISON", &fl_context::Options::dev_poison, false, 0, 1},
   {"ws_pad", "FL_DEV_WS_PAD", &fl_context::Options::ws_pad, false, 0, 16l << 20},
+  {"pipeline_icp", "FL_PIPELINE_ICP", &fl_context::Options::pipeline_icp, false, 0, 3},
 };
 
 // A value outside an option's range is refused rather than taken for "default": a forced kernel variant with a mistyped
@@ -138,7 +180,9 @@ static void context_release(fl_context *ctx)
 {
   if (ctx->device < 0) { delete ctx; return; }           // a host-only detector's context (fl_dev_detector_create_host): no device state
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
+  (void)fl_context_sync_all(ctx);
+  if (ctx->icp_stream) (void)hipStreamDestroy(ctx->icp_stream);
+  if (ctx->ev_icp_tail) (void)hipEventDestroy(ctx->ev_icp_tail);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -157,7 +201,7 @@ extern "C" const char *fl_last_error(const fl_context *ctx) { return ctx ? ctx->
 extern "C" int fl_context_set_stream(fl_context *ctx, void *hip_stream)
 {
   if (!ctx) return FL_ERR_INVALID;
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (int rc = fl_context_sync_all(ctx)) return rc;
   ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
   return FL_OK;
 }
@@ -166,8 +210,7 @@ extern "C" int fl_context_synchronize(fl_context *ctx)
 {
   if (!ctx) return FL_ERR_INVALID;
   FL_HIP(ctx, hipSetDevice(ctx->device));
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FL_OK;
+  return fl_context_sync_all(ctx);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -233,6 +276,13 @@ static void free_device_tables(fl_detector *det)
   det->h_results = nullptr;
   for (auto &e : det->ev)
     if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  for (int b = 0; b < 2; ++b) {
+    if (det->ev_done[b]) { (void)hipEventDestroy(det->ev_done[b]); det->ev_done[b] = nullptr; }
+    if (det->ev_set_read[b]) { (void)hipEventDestroy(det->ev_set_read[b]); det->ev_set_read[b] = nullptr; }
+    det->set_busy[b] = false;
+  }
+  det->prev_n = 0;
+  det->latest_open = false;
   if (det->d_jobs) { (void)hipFree(det->d_jobs); det->d_jobs = nullptr; }
   if (det->d_icp_order) { (void)hipFree(det->d_icp_order); det->d_icp_order = nullptr; }
   det->selected_frames = 0;
@@ -253,7 +303,7 @@ extern "C" void fl_detector_destroy(fl_detector *det)
   fl_context *ctx = det->ctx;
   if (ctx->device >= 0) {                                // a host-only detector never had device state
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)fl_context_sync_all(ctx);
     free_device_tables(det);
     for (auto &c : det->classes)
       if (c.d_depths) (void)hipFree(c.d_depths);
@@ -308,6 +358,7 @@ extern "C" int fl_detector_set_model_depths(fl_detector *det, int class_idx, int
   FlClass &c = det->classes[class_idx];
   if (first < 0 || count < 0 || first + count > c.n_pyramids) return fl_set_error(ctx, FL_ERR_INVALID, "pyramid range");
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;     // an ICP stage in flight reads the renders
   size_t per = (size_t)w * h * sizeof(uint16_t);
   if (!c.d_depths) {
     FL_HIP(ctx, hipMalloc((void **)&c.d_depths, per * (size_t)c.n_pyramids));
@@ -402,6 +453,13 @@ static int layout_workspace(fl_detector *det, int cap)
   det->off_match = take((size_t)cap * sizeof(fl_match));
   det->n_pts_max = det->max_tw * det->max_th;
   det->off_icp = take(fl_icp_ws_bytes(det->n_pts_max));
+  // the second set of what the ICP stage reads (see fl_internal.h); off_count / off_match keep naming the current set
+  det->off_count_set[0] = det->off_count;
+  det->off_match_set[0] = det->off_match;
+  det->off_count_set[1] = take(256);
+  det->off_match_set[1] = take((size_t)cap * sizeof(fl_match));
+  det->off_count = det->off_count_set[det->set];
+  det->off_match = det->off_match_set[det->set];
   det->ws_stride = fl_align(off, 4096);
   det->cap = cap;
   if (ctx->opt.ws_pad > 0) det->ws_stride += fl_align((size_t)ctx->opt.ws_pad, 4096);   // dev aid: stride sensitivity
@@ -429,7 +487,8 @@ int fl_grow_candidates(fl_detector *det, int needed)
   long long want = det->cap;
   while (want < needed || want <= det->cap) want <<= 1;
   if (want > (1ll << 28)) return fl_set_error(ctx, FL_ERR_OVERFLOW, "%d candidates in one frame", needed);
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (int rc = fl_context_sync_all(ctx)) return rc;         // both streams: ICP reads the match lists and writes its workspaces
+  (void)fl_pipeline_join(det);
   const int old_cap = det->cap;
   fl_batch_forget(det);                                  // the frame workspaces are about to be freed
   (void)hipFree(det->d_ws);
@@ -462,7 +521,7 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
   fl_context *ctx = det->ctx;
   if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_STATE, "a host-only detector cannot be finalized");
   FL_HIP(ctx, hipSetDevice(ctx->device));
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (int rc = fl_context_sync_all(ctx)) return rc;
   free_device_tables(det);
   det->finalized = false;
   fl_batch_forget(det);
@@ -634,9 +693,13 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
   if ((rc = layout_workspace(det, cap))) return rc;
   if ((rc = fl_icp_prepare(det))) return rc;
   FL_HIP(ctx, hipMalloc((void **)&det->d_results, sizeof(fl_recognition_result) * (size_t)max_batch));
-  FL_HIP(ctx, hipHostMalloc((void **)&det->h_results, sizeof(fl_recognition_result) * (size_t)max_batch,
+  FL_HIP(ctx, hipHostMalloc((void **)&det->h_results, sizeof(fl_recognition_result) * 2 * (size_t)max_batch,
                             hipHostMallocDefault));
   for (auto &e : det->ev) FL_HIP(ctx, hipEventCreate(&e));
+  for (int b = 0; b < 2; ++b) {
+    FL_HIP(ctx, hipEventCreateWithFlags(&det->ev_done[b], hipEventDisableTiming));
+    FL_HIP(ctx, hipEventCreateWithFlags(&det->ev_set_read[b], hipEventDisableTiming));
+  }
   det->finalized = true;
   return FL_OK;
 }

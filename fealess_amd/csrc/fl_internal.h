@@ -13,6 +13,13 @@ struct fl_context {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
+  // Pipelined recognition (fl_recognize_submit, option pipeline_icp): the ICP stage of a batch runs on this second
+  // non-blocking stream while the next batch's LINEMOD stages run on `stream`.  Created on first use with the priority the
+  // option asks for.  ev_icp_tail is recorded after the last work queued on it; icp_pending: `stream` has not waited for it yet.
+  hipStream_t icp_stream = nullptr;
+  long icp_stream_mode = 0;     // the pipeline_icp value icp_stream was created for
+  hipEvent_t ev_icp_tail = nullptr;
+  bool icp_pending = false;
   char err[512] = {0};
   // scratch for the single-shot stage entry points (grown on demand)
   void *scratch = nullptr;
@@ -33,6 +40,10 @@ struct fl_context {
     long eager_frontend = 0;    // FL_EAGER_FRONTEND: finer pyramid levels in full before the scan (read by fl_detector_finalize)
     long dev_poison = 0;        // FL_DEV_POISON: fill what the lazy path leaves uncomputed with 0xFF (read by fl_detector_finalize)
     long ws_pad = 0;            // FL_DEV_WS_PAD: extra bytes of frame workspace stride (read by fl_detector_finalize)
+    long pipeline_icp = 3;      // FL_PIPELINE_ICP: 0 = fl_recognize_submit queues everything on one stream; 1 = a batch's ICP stage on a
+                                // second stream beside the next batch's LINEMOD stages; 2 / 3 = the same with that stream at the
+                                // highest / lowest priority the device offers (3 measured best: the short LINEMOD kernels get the
+                                // slots the long ICP launch frees, profiles/README.md)
   } opt;
   int detectors = 0;            // live fl_detector objects on this context
   bool destroy_pending = false; // fl_context_destroy was called while detectors were alive: the last one releases the context
@@ -41,6 +52,9 @@ struct fl_context {
 int fl_set_error(fl_context *ctx, int code, const char *fmt, ...);
 int fl_scratch(fl_context *ctx, size_t bytes, void **out);
 int fl_pinned(fl_context *ctx, size_t bytes, void **out);
+int fl_context_join(fl_context *ctx);        // ctx->stream waits for everything queued on the ICP stream (no host wait)
+int fl_context_sync_all(fl_context *ctx);    // the host waits for both streams
+int fl_icp_stream(fl_context *ctx, hipStream_t *out);   // the ICP stream for the current pipeline_icp value, created on first use
 
 #define FL_HIP(ctx, call)                                                                  \
   do {                                                                                     \
@@ -163,6 +177,15 @@ struct fl_detector {
   size_t ws_stride = 0;
   size_t off_bgr = 0, off_depth = 0, off_cand = 0, off_count = 0, off_keys = 0, off_match = 0;
   size_t off_icp = 0, off_tmp = 0;
+  // What the ICP stage reads of a frame workspace -- the counters and the sorted match list -- exists twice, so that the
+  // match stage of batch i+1 can fill one set while ICP(i) still reads the other (pipelined fl_recognize_submit).
+  // off_count / off_match always name the set of the batch last queued: every reader of "the last batch" uses them as before.
+  // ev_set_read[s] is recorded on the ICP stream after the ICP stage that reads set s; set_busy[s]: ctx->stream has not waited
+  // for it yet, which it does before the match stage next zeroes the set's counters.
+  size_t off_count_set[2] = {0, 0}, off_match_set[2] = {0, 0};
+  int set = 0;
+  hipEvent_t ev_set_read[2] = {nullptr, nullptr};
+  bool set_busy[2] = {false, false};
   // Lazy fine levels (fl_recognize_*): the finer levels are only ever read by k_refine, around the candidates the
   // coarse scan produced.  Their colour quantisation and spread images are therefore computed after the scan and
   // only in the 60x60-pixel tiles the candidates' 16x16 patches can touch (k_mark_tiles).  Two bitmaps per frame
@@ -194,15 +217,32 @@ struct fl_detector {
 
   // results
   fl_recognition_result *d_results = nullptr;   // max_batch
-  fl_recognition_result *h_results = nullptr;   // pinned
+  fl_recognition_result *h_results = nullptr;   // pinned, 2 * max_batch: fl_recognize_submit alternates between the halves
+  // fl_recognize_submit / _collect / _collect_previous: half h_flip holds the latest submitted batch, the other half the one
+  // before it while prev_n > 0 (its frame count; 0: none, collected, or another entry point ran since).  ev_done[b] is
+  // recorded after the copy into half b.  latest_open: the latest call was a fl_recognize_submit not collected yet.
+  int h_flip = 0, prev_n = 0;
+  bool latest_open = false;
+  hipEvent_t ev_done[2] = {nullptr, nullptr};
+  int icp_ev = 5;                        // the event that starts icp_ms: 5, or 7 where fl_recognize_submit recorded it before its ICP launch
   // timing
-  hipEvent_t ev[FL_NUM_EVENTS] = {nullptr};   // 0..6 stage boundaries, 8 + 2l / 9 + 2l around the lazy work of fine level l
+  hipEvent_t ev[FL_NUM_EVENTS] = {nullptr};   // 0..6 stage boundaries, 7 start of the ICP launches (fl_recognize_submit), 8 + 2l / 9 + 2l around the lazy work of fine level l
   fl_stage_times times;
   bool have_times = false;
   double scan_bytes_per_frame = 0;       // SURVEY 8(d) B_tmpl summed over the bank
 };
 
 static inline void fl_batch_forget(fl_detector *det) { det->batch = FlBatch(); }
+// Before an entry point other than fl_recognize_submit forgets the batch or queues work on ctx->stream: that stream waits
+// for the ICP stage a pipelined fl_recognize_submit may still have in flight on the ICP stream (it writes d_results and the
+// frames' ICP workspaces and reads the match lists), and the batch before the latest is no longer there to collect.
+static inline int fl_pipeline_join(fl_detector *det)
+{
+  det->prev_n = 0;
+  det->latest_open = false;
+  det->set_busy[0] = det->set_busy[1] = false;
+  return fl_context_join(det->ctx);
+}
 static inline void fl_batch_record(fl_detector *det, int n, const uint16_t *depth, size_t depth_stride, bool match_only)
 {
   det->batch = FlBatch{n, depth, depth_stride, match_only};

@@ -969,6 +969,11 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
 int fl_launch_match_core(fl_detector *det, int n_frames, float threshold)
 {
   fl_context *ctx = det->ctx;
+  // the ICP stage that last read this set of counters and match lists (two batches ago, on the ICP stream) comes first
+  if (det->set_busy[det->set]) {
+    det->set_busy[det->set] = false;
+    FL_HIP(ctx, hipStreamWaitEvent(ctx->stream, det->ev_set_read[det->set], 0));
+  }
   // zero the per-frame counters
   FL_HIP(ctx, hipMemset2DAsync(det->d_ws + det->off_count, det->ws_stride, 0, 16, n_frames, ctx->stream));
   for (int l = 0; l < det->L; ++l) {
@@ -1035,7 +1040,8 @@ extern "C" int fl_detector_grow_candidates(fl_detector *det, int n_frames, int *
     return fl_set_error(ctx, FL_ERR_STATE, "n_frames %d > the %d frames of the last batch", n_frames, det->batch.n);
   FL_HIP(ctx, hipSetDevice(ctx->device));
   int needed = 0;
-  int rc = fl_overflow_needed(det, n_frames, &needed);
+  int rc = fl_pipeline_join(det);
+  if (rc == FL_OK) rc = fl_overflow_needed(det, n_frames, &needed);
   if (rc == FL_OK && needed > 0) rc = fl_grow_candidates(det, needed);
   if (new_cap) *new_cap = det->cap;
   return rc;
@@ -1049,6 +1055,7 @@ extern "C" int fl_match_quantized(fl_detector *det, const uint8_t *const *quanti
   if (int rc = fl_check_frames(det, 1)) return rc;
   FL_HIP(ctx, hipSetDevice(ctx->device));
   for (int attempt = 0;; ++attempt) {
+    if (int rc = fl_pipeline_join(det)) return rc;
     fl_batch_forget(det);
     for (int l = 0; l < det->L; ++l)
       for (int m = 0; m < det->M; ++m) {
@@ -1105,6 +1112,7 @@ static int match_frame_masked_once(fl_detector *det, const uint8_t *bgr, const u
   int rc = fl_check_frames(det, 1);
   if (rc) return rc;
   if (det->M == 2 && !depth) return fl_set_error(ctx, FL_ERR_INVALID, "sources.size() != modalities.size() (linemod.cpp:1364)");
+  if ((rc = fl_pipeline_join(det))) return rc;
   fl_batch_forget(det);
   if ((rc = fl_upload_frame0(det, bgr, depth, mem))) return rc;
   det->have_times = false;
@@ -1169,6 +1177,7 @@ extern "C" int fl_match_batch_collect(fl_detector *det, int frame, fl_match *out
   fl_context *ctx = det->ctx;
   if (!det->finalized || frame < 0 || frame >= det->batch.n) return fl_set_error(ctx, FL_ERR_STATE, "no such frame in the last batch");
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   fl_update_stage_times(det, det->batch.n, nullptr);
   return read_matches(det, frame, out, cap, n_total);
@@ -1184,7 +1193,8 @@ extern "C" int fl_similarity_maps(fl_detector *det, int first, int count, uint16
   const FlLevelGeom &g = det->geom[det->L - 1];
   size_t bytes = (size_t)count * g.WH * sizeof(uint16_t);
   void *d = nullptr;
-  int rc = fl_scratch(ctx, bytes, &d);
+  int rc = fl_pipeline_join(det);          // frame 0's counters are rewritten below
+  if (rc == FL_OK) rc = fl_scratch(ctx, bytes, &d);
   if (rc) return rc;
   FL_HIP(ctx, hipMemsetAsync(d, 0, bytes, ctx->stream));
   // re-run the scan on frame 0's resident linear memories with the debug tap on; threshold 200%
@@ -1212,6 +1222,7 @@ extern "C" int fl_frame_counters(fl_detector *det, int frame, int32_t out[4])
   fl_context *ctx = det->ctx;
   if (!det->finalized || frame < 0 || frame >= det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "frame");
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;
   FL_HIP(ctx, hipMemcpyAsync(out, det->d_ws + (size_t)frame * det->ws_stride + det->off_count, 16, hipMemcpyDeviceToHost, ctx->stream));
   uint32_t bm[2 * FL_TILE_WORDS];
   const bool lazy = det->lazy && det->L > 1 && frame < det->batch.n;
@@ -1335,6 +1346,7 @@ extern "C" int fl_export_topk(fl_detector *det, int frame, int k, int template_i
   fl_context *ctx = det->ctx;
   if (!det->finalized || frame < 0 || frame >= det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "frame");
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;
   hipLaunchKernelGGL(k_export_topk, dim3(1), dim3(256), 0, ctx->stream, det->d_ws + (size_t)frame * det->ws_stride,
                      det->off_count, det->off_match, k, template_id_base, (fl_match *)dev_out);
   FL_HIP(ctx, hipGetLastError());
@@ -1366,6 +1378,7 @@ extern "C" int fl_export_topk_batch(fl_detector *det, int n_frames, int k, int t
   if (!det->finalized || n_frames > det->max_batch) return fl_set_error(ctx, FL_ERR_INVALID, "n_frames");
   if (n_frames > det->batch.n) return fl_set_error(ctx, FL_ERR_STATE, "%d frames asked for, the last batch had %d", n_frames, det->batch.n);
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;
   hipLaunchKernelGGL(k_export_topk_batch, dim3(n_frames), dim3(64), 0, ctx->stream, det->d_ws, det->ws_stride, det->off_count,
                      det->off_match, k, template_id_base, (fl_match *)dev_out);
   FL_HIP(ctx, hipGetLastError());
@@ -1420,6 +1433,7 @@ extern "C" int fl_select_best_batch(fl_detector *det, const void *dev_gathered, 
     return fl_set_error(ctx, FL_ERR_INVALID, "template-sharded refinement: one class per detector, tid_count = its %d pyramids",
                         det->classes.empty() ? 0 : det->classes[0].n_pyramids);
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;
   if (!det->d_jobs) FL_HIP(ctx, hipMalloc((void **)&det->d_jobs, sizeof(FlRefineJob) * (size_t)det->max_batch));
   hipLaunchKernelGGL(k_select_best, dim3((n_frames + 63) / 64), dim3(64), 0, ctx->stream, (const fl_match *)dev_gathered, n_ranks,
                      n_frames, k, tid_first, tid_count, (fl_match *)dev_best, det->d_jobs);

@@ -1,9 +1,22 @@
 // fl_pipeline.hip -- CObjRecoLmICP::Recognition (CadReco/obj_reco_lmicp.cpp:86-204) for a batch
 // of frames: quantise -> linear memories -> scan -> refine -> sort/unique -> (device-side
-// hand-over of matches[0]) -> crop back-projection -> ICP -> 4x4 pose, queued back to back on
-// one HIP stream with no host synchronisation in between.  Every kernel is launched over the
-// whole batch (grid.z / grid.y / one workgroup per frame), so the launch count per batch is
-// constant (about a dozen) whatever the number of frames.
+// hand-over of matches[0]) -> crop back-projection -> ICP -> 4x4 pose, queued with no host
+// synchronisation in between.  Every kernel is launched over the whole batch (grid.z / grid.y /
+// one workgroup per frame), so the launch count per batch is constant (about a dozen) whatever
+// the number of frames.
+//
+// fl_recognize_submit queues a batch as two stages on two streams (option pipeline_icp, see
+// fl_internal.h): staging, front-end, match, refine and sort on the context's stream, then --
+// after an event recorded behind the sort -- the ICP stage and the copy of the results on the
+// context's ICP stream.  The ICP stage reads only the frame's counters and sorted match list, the
+// caller's depth frames and the bank, and the frame workspaces hold the counters and the list
+// twice, so the LINEMOD stages of batch i+1 run beside the ICP launch of batch i and fill the
+// tails of its occupancy-bound launch.  Batch i+2's match stage waits for ICP(i) before it zeroes
+// the set ICP(i) read.  One stream carries everything, in the order above, when pipeline_icp is 0,
+// when the caller set a stream of their own (synchronising that stream must finish the work), or
+// when device frames had to be gathered into the frame workspaces (ICP reads the depth there).
+// Every other entry point first makes the context's stream wait for the ICP stream
+// (fl_pipeline_join / fl_context_join).
 #include "fl_internal.h"
 #include <cmath>
 #include <vector>
@@ -23,9 +36,10 @@ static bool uniform_stride(const void *const *ptrs, int n, size_t min_bytes, siz
 
 // argument checks, frame staging, front-end and Detector::match of a batch, which it records (refinable when depth frames were
 // given); the depth frames' device location comes back (K == nullptr: Detector::match only, no intrinsics to check)
+// pipelined != nullptr (fl_recognize_submit): the caller may run the ICP stage on the ICP stream; *pipelined says whether it is to
 static int stage_and_match(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth, int mem,
                            const fl_intrinsics *K, float threshold, const uint16_t **depth_base_out,
-                           size_t *depth_stride_out, int *host_buf_out)
+                           size_t *depth_stride_out, int *host_buf_out, bool *pipelined = nullptr)
 {
   int host_buf = -1;     // the input buffer the batch was uploaded to (host frames), released by input_done()
   if (!det || !bgr || n_frames <= 0) return FL_ERR_INVALID;
@@ -38,15 +52,27 @@ static int stage_and_match(fl_detector *det, int n_frames, const uint8_t *const 
   for (int i = 0; i < n_frames; ++i)
     if (!bgr[i] || (det->M == 2 && !depth[i])) return fl_set_error(ctx, FL_ERR_INVALID, "frame %d: null pData (CheckTImage)", i);
   FL_HIP(ctx, hipSetDevice(ctx->device));
-  fl_batch_forget(det);
 
   const size_t bgr_bytes = (size_t)det->w0 * det->h0 * 3, depth_bytes = (size_t)det->w0 * det->h0 * 2;
   const uint8_t *bgr_base = det->d_ws + det->off_bgr;
   const uint16_t *depth_base = (const uint16_t *)(det->d_ws + det->off_depth);
   size_t bgr_stride = det->ws_stride, depth_stride = det->ws_stride;
   size_t s1 = 0, s2 = 0;
-  if (mem == FL_MEM_DEVICE && uniform_stride((const void *const *)bgr, n_frames, bgr_bytes, &s1) &&
-      (det->M < 2 || (uniform_stride((const void *const *)depth, n_frames, depth_bytes, &s2) && s2 % 2 == 0))) {
+  const bool in_place = mem == FL_MEM_DEVICE && uniform_stride((const void *const *)bgr, n_frames, bgr_bytes, &s1) &&
+                        (det->M < 2 || (uniform_stride((const void *const *)depth, n_frames, depth_bytes, &s2) && s2 % 2 == 0));
+  // two stages on two streams, or today's one-stream order (see the header comment)
+  const bool two_streams = pipelined && ctx->opt.pipeline_icp != 0 && ctx->stream == ctx->own_stream && (in_place || mem == FL_MEM_HOST);
+  if (pipelined) *pipelined = two_streams;
+  if (two_streams) {                       // this batch's match stage fills the set the ICP stage in flight does not read
+    det->set ^= 1;
+    det->off_count = det->off_count_set[det->set];
+    det->off_match = det->off_match_set[det->set];
+  } else if ((rc = pipelined ? fl_context_join(ctx) : fl_pipeline_join(det))) {
+    return rc;
+  }
+  fl_batch_forget(det);
+  det->icp_ev = 5;
+  if (in_place) {
     // frames already in HBM at a regular pitch: read them in place
     bgr_base = bgr[0];
     bgr_stride = s1;
@@ -120,7 +146,9 @@ void fl_update_stage_times(fl_detector *det, int n_frames, const fl_recognition_
     t.refine_ms -= t.lazy_frontend_ms;
   }
   t.sort_ms = el(4, 5);
-  t.icp_ms = det->batch.match_only ? 0.f : el(5, 6);
+  // from the event before the ICP launches to the one after them; total_ms spans the batch's first and last event, which for
+  // a pipelined batch includes its ICP stage's wait for the ICP stage of the batch before
+  t.icp_ms = det->batch.match_only ? 0.f : el(det->icp_ev, 6);
   t.total_ms = el(0, 6);
   t.backproject_ms = 0;                 // fused into the per-frame ICP workgroup
   t.icp_launches = det->batch.match_only ? 0 : 1;
@@ -140,6 +168,14 @@ static int input_done(fl_detector *det, int host_buf)
   return FL_OK;
 }
 
+// ctx->stream names the ICP stream for the lifetime of this object: the launchers take their stream from that field
+struct FlStreamScope {
+  fl_context *ctx;
+  hipStream_t saved;
+  FlStreamScope(fl_context *c, hipStream_t s) : ctx(c), saved(c->stream) { c->stream = s; }
+  ~FlStreamScope() { ctx->stream = saved; }
+};
+
 extern "C" int fl_recognize_submit(fl_detector *det, int n_frames, const uint8_t *const *bgr,
                                    const uint16_t *const *depth, int mem, const fl_intrinsics *K,
                                    const fl_recognition_params *params)
@@ -147,18 +183,43 @@ extern "C" int fl_recognize_submit(fl_detector *det, int n_frames, const uint8_t
   const uint16_t *depth_base = nullptr;
   size_t depth_stride = 0;
   int host_buf = -1;
+  bool pipelined = false;
   if (!K || !params) return FL_ERR_INVALID;
-  int rc = stage_and_match(det, n_frames, bgr, depth, mem, K, params->matching_threshold, &depth_base, &depth_stride, &host_buf);
+  // the batch before this one stays collectable (fl_recognize_collect_previous) if it was a fl_recognize_submit nobody collected
+  const int prev_n = det && det->latest_open ? det->batch.n : 0;
+  if (det) { det->prev_n = 0; det->latest_open = false; }
+  int rc = stage_and_match(det, n_frames, bgr, depth, mem, K, params->matching_threshold, &depth_base, &depth_stride, &host_buf, &pipelined);
   if (rc) return rc;
   fl_context *ctx = det->ctx;
-  FL_HIP(ctx, hipMemsetAsync(det->d_results, 0, sizeof(fl_recognition_result) * (size_t)n_frames, ctx->stream));
-  rc = fl_launch_detection(det, n_frames, K, params, depth_base, depth_stride, det->d_ws + det->off_icp, det->ws_stride, 1, nullptr,
-                           det->d_results, true);
-  if (rc) return rc;
-  if ((rc = input_done(det, host_buf))) return rc;
-  FL_HIP(ctx, hipEventRecord(det->ev[6], ctx->stream));
-  FL_HIP(ctx, hipMemcpyAsync(det->h_results, det->d_results, sizeof(fl_recognition_result) * (size_t)n_frames,
-                             hipMemcpyDeviceToHost, ctx->stream));
+  const int hb = det->h_flip ^ 1;          // the half of h_results the batch before this one did not use
+  fl_recognition_result *h_res = det->h_results + (size_t)hb * det->max_batch;
+  {
+    hipStream_t icp = ctx->stream;
+    if (pipelined) {
+      if ((rc = fl_icp_stream(ctx, &icp))) return rc;
+      FL_HIP(ctx, hipStreamWaitEvent(icp, det->ev[5], 0));      // recorded behind the sort
+    }
+    FlStreamScope scope(ctx, icp);
+    FL_HIP(ctx, hipMemsetAsync(det->d_results, 0, sizeof(fl_recognition_result) * (size_t)n_frames, ctx->stream));
+    FL_HIP(ctx, hipEventRecord(det->ev[7], ctx->stream));      // icp_ms starts here: behind the wait for the ICP stage before
+    det->icp_ev = 7;
+    rc = fl_launch_detection(det, n_frames, K, params, depth_base, depth_stride, det->d_ws + det->off_icp, det->ws_stride, 1, nullptr,
+                             det->d_results, true);
+    if (rc) return rc;
+    if ((rc = input_done(det, host_buf))) return rc;
+    FL_HIP(ctx, hipEventRecord(det->ev[6], ctx->stream));
+    FL_HIP(ctx, hipMemcpyAsync(h_res, det->d_results, sizeof(fl_recognition_result) * (size_t)n_frames, hipMemcpyDeviceToHost, ctx->stream));
+    FL_HIP(ctx, hipEventRecord(det->ev_done[hb], ctx->stream));
+    if (pipelined) {
+      FL_HIP(ctx, hipEventRecord(det->ev_set_read[det->set], ctx->stream));
+      det->set_busy[det->set] = true;
+      FL_HIP(ctx, hipEventRecord(ctx->ev_icp_tail, ctx->stream));
+      ctx->icp_pending = true;
+    }
+  }
+  det->h_flip = hb;
+  det->prev_n = prev_n;
+  det->latest_open = true;
   return FL_OK;
 }
 
@@ -184,9 +245,27 @@ extern "C" int fl_recognize_collect(fl_detector *det, int n_frames, fl_recogniti
   fl_context *ctx = det->ctx;
   if (!det->finalized || n_frames > det->batch.n) return fl_set_error(ctx, FL_ERR_STATE, "nothing submitted");
   FL_HIP(ctx, hipSetDevice(ctx->device));
-  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(results, det->h_results, sizeof(fl_recognition_result) * (size_t)n_frames);
+  if (int rc = fl_context_sync_all(ctx)) return rc;        // the latest batch: both streams
+  memcpy(results, det->h_results + (size_t)det->h_flip * det->max_batch, sizeof(fl_recognition_result) * (size_t)n_frames);
   fl_update_stage_times(det, n_frames, results);
+  det->latest_open = false;
+  return FL_OK;
+}
+
+// The results of the batch submitted BEFORE the latest fl_recognize_submit, while the latest is still in flight: waits for
+// that batch's completion event only and leaves the stage times alone.
+extern "C" int fl_recognize_collect_previous(fl_detector *det, int n_frames, fl_recognition_result *results)
+{
+  if (!det || !results || n_frames <= 0) return FL_ERR_INVALID;
+  fl_context *ctx = det->ctx;
+  if (!det->finalized || det->prev_n < 1)
+    return fl_set_error(ctx, FL_ERR_STATE, "no uncollected batch before the latest fl_recognize_submit (or another call ran in between)");
+  if (n_frames > det->prev_n) return fl_set_error(ctx, FL_ERR_STATE, "%d frames asked for, the batch before the latest had %d", n_frames, det->prev_n);
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  const int hb = det->h_flip ^ 1;
+  FL_HIP(ctx, hipEventSynchronize(det->ev_done[hb]));
+  memcpy(results, det->h_results + (size_t)hb * det->max_batch, sizeof(fl_recognition_result) * (size_t)n_frames);
+  det->prev_n = 0;
   return FL_OK;
 }
 
@@ -219,6 +298,7 @@ extern "C" int fl_recognize_batch_zoom(fl_detector *det, int n_frames, const uin
   for (int i = 0; i < n_frames; ++i)
     if (!bgr[i] || !depth[i]) return fl_set_error(ctx, FL_ERR_INVALID, "frame %d: null pData (CheckTImage)", i);
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;
   fl_batch_forget(det);                  // d_zoom may hold the last batch's depth frames
   const int w = det->w0, h = det->h0;
   const size_t zb = fl_align((size_t)w * h * 3, 256), zf = zb + fl_align((size_t)w * h * 2, 256);
@@ -278,7 +358,7 @@ extern "C" int fl_refine_matches(fl_detector *det, int n_jobs, const int32_t *fr
   }
   FL_HIP(ctx, hipSetDevice(ctx->device));
   void *sv = nullptr;
-  if ((rc = fl_scratch(ctx, sizeof(FlRefineJob) * (size_t)n_jobs, &sv))) return rc;
+  if ((rc = fl_pipeline_join(det)) || (rc = fl_scratch(ctx, sizeof(FlRefineJob) * (size_t)n_jobs, &sv))) return rc;
   FL_HIP(ctx, hipMemcpyAsync(sv, jobs.data(), sizeof(FlRefineJob) * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
   FL_HIP(ctx, hipMemsetAsync(det->d_results, 0, sizeof(fl_recognition_result) * (size_t)n_jobs, ctx->stream));
   det->have_times = false;
@@ -318,6 +398,7 @@ extern "C" int fl_refine_selected(fl_detector *det, int n_frames, const fl_intri
     depth_stride = det->batch.depth_stride;
   }
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_pipeline_join(det)) return rc;
   FL_HIP(ctx, hipMemsetAsync(det->d_results, 0, sizeof(fl_recognition_result) * (size_t)n_frames, ctx->stream));
   det->have_times = false;
   int rc = fl_launch_detection(det, n_frames, K, params, depth_base, depth_stride, det->d_ws + det->off_icp, det->ws_stride, 1, det->d_jobs,
@@ -339,6 +420,7 @@ static int recognize_topk_once(fl_detector *det, const uint8_t *bgr, const uint1
   if (rc) return rc;
   if (det->M != 2) return fl_set_error(ctx, FL_ERR_INVALID, "needs the colour + depth modalities");
   if ((rc = fl_check_intrinsics(det, K))) return rc;
+  if ((rc = fl_pipeline_join(det))) return rc;
   fl_batch_forget(det);
   if ((rc = fl_upload_frame0(det, bgr, depth, mem))) return rc;
   det->have_times = false;

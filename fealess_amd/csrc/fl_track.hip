@@ -378,6 +378,7 @@ extern "C" int fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *con
   if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_track_batch: the tracker has no device");
 
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = fl_context_join(ctx)) return rc;    // a detector's pipelined ICP stage on this context comes first
   const size_t px = (size_t)trk->w * trk->h, T = (size_t)n_tracks;
   hipStream_t st = ctx->stream;
   FL_HIP(ctx, hipEventRecord(trk->ev[0], st));

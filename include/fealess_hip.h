@@ -143,14 +143,16 @@ fl_context *fl_detector_get_context(fl_detector *det);
  * checks the pruning bound; -1 = built-in), "icp_wide" (-1 = by batch size; 0 / 1 force the 256- / 1024-thread ICP workgroup),
  * "icp_occ" (0 = by batch size; 4 / 5 force the 256-thread kernel built for that many workgroups per CU), "icp_order" (1 = ICP
  * jobs dealt longest first; 0 = frame order), "icp_wg_per_cu" (0 = as many 256-thread ICP workgroups per CU as fit; 1 .. 3 = at
- * most that many, the rest of the CU left to the kernels of other streams), and -- sampled by fl_detector_finalize -- "eager_frontend" (1 = finer pyramid
+ * most that many, the rest of the CU left to the kernels of other streams), "pipeline_icp" (3; how fl_recognize_submit queues a batch: 0 = every
+ * stage on the context's stream; 1 = the ICP stage on a second stream of the context, beside the next batch's LINEMOD stages; 2 / 3 =
+ * the same with that stream at the highest / lowest priority of hipDeviceGetStreamPriorityRange), and -- sampled by fl_detector_finalize -- "eager_frontend" (1 = finer pyramid
  * levels in full before the scan, the reference's order), "dev_poison" (1 = what the lazy path leaves uncomputed is filled
  * with 0xFF), "ws_pad" (extra bytes of frame-workspace stride).  Their INITIAL values are read once from the environment
  * when the context is created (FL_SCAN_PRUNE, FL_SCAN_PRUNE_MID (hex), FL_ICP_WIDE, FL_ICP_OCC, FL_ICP_ORDER, FL_ICP_WG_PER_CU,
- * FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
+ * FL_PIPELINE_ICP, FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
  * process later on changes nothing.  Unknown names: FL_ERR_INVALID.
  * Accepted values: scan_prune, icp_order, eager_frontend, dev_poison {0, 1}; scan_prune_mid -1 .. 0xFF; icp_wide {-1, 0, 1};
- * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
+ * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; pipeline_icp 0 .. 3; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
  * FL_ERR_INVALID and leaves the option as it was; an environment value outside its range keeps the built-in default. */
 int  fl_context_set_option(fl_context *ctx, const char *name, long value);
 int  fl_context_get_option(const fl_context *ctx, const char *name, long *value);
@@ -355,12 +357,25 @@ int  fl_recognize_batch(fl_detector *det, int n_frames, const uint8_t *const *bg
 int  fl_recognize_batch_zoom(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth,
                              int src_w, int src_h, int mem, const fl_intrinsics *K, const fl_recognition_params *params,
                              fl_recognition_result *results);
-/* same, but only queues the work on the context's stream; fl_recognize_collect() waits and
- * copies the results out.  Lets the caller overlap two contexts / batches. */
+/* same, but only queues the work; fl_recognize_collect() waits and copies the results out.  Lets the caller overlap two
+ * contexts / batches.
+ * Two batches are in flight inside one detector: the LINEMOD stages (staging, front-end, match, refine, sort) are queued on the
+ * context's stream and the ICP stage, with the copy of the results, on a second stream the context owns, so the LINEMOD
+ * stages of batch i+1 run beside the ICP launch of batch i (option "pipeline_icp").  fl_context_synchronize and
+ * fl_recognize_collect wait for both streams, and every other entry point orders itself behind both.  Everything is queued on
+ * ONE stream, in order, when the caller gave the context a stream (fl_context_set_stream: synchronising that stream finishes
+ * the work), when device frames lie at irregular addresses, or with pipeline_icp = 0.  Results are the same either way.
+ * fl_recognize_collect returns the LATEST submitted batch.  fl_recognize_collect_previous returns the batch submitted BEFORE
+ * the latest fl_recognize_submit and waits only for that batch, so that
+ *     submit(0); for i in 1..: submit(i); collect_previous(i-1); ...; collect(last)
+ * keeps two batches in flight and still hands every batch's results over.  It returns FL_ERR_STATE when there is no such
+ * batch: fewer than two submits, the batch already collected (by either call), or any other entry point of the detector
+ * called since that batch was submitted.  It leaves the stage times as they are. */
 int  fl_recognize_submit(fl_detector *det, int n_frames, const uint8_t *const *bgr,
                          const uint16_t *const *depth, int mem, const fl_intrinsics *K,
                          const fl_recognition_params *params);
 int  fl_recognize_collect(fl_detector *det, int n_frames, fl_recognition_result *results);
+int  fl_recognize_collect_previous(fl_detector *det, int n_frames, fl_recognition_result *results);
 
 /* ---- multi-GPU support: top-k records for the all-gather ------------------------------------ */
 /* Multi-hypothesis recognition (the pipeline ICP/NMS.cpp + obj_data.h sketch): the refinement of
@@ -542,7 +557,9 @@ int  fl_refine_selected(fl_detector *det, int n_frames, const fl_intrinsics *K, 
  * (host memory) */
 int  fl_frame_counters(fl_detector *det, int frame, int32_t out[4]);
 
-/* per-stage device time (ms) of the last fl_recognize_* call, by stage index; for bench.py */
+/* per-stage device time (ms) of the last fl_recognize_* call, by stage index; for bench.py.  icp_ms starts at the first ICP
+ * launch.  total_ms spans the batch's first to its last event: for a batch whose ICP stage ran on the second stream it
+ * includes that stage's wait for the ICP stage of the batch before it. */
 typedef struct {
   float frontend_ms, linmem_ms, scan_ms, refine_ms, sort_ms, backproject_ms, icp_ms, total_ms;
   int32_t icp_iters_total, icp_launches;

@@ -2,7 +2,8 @@
 """dev: TWO pipelines on one GPU -- two contexts (a HIP stream each) with a detector each, half of the frames each, their
 steps submitted alternately, so that one pipeline's LINEMOD stages run beside the other's ICP launch.  The ICP launch normally
 fills every CU's registers (4 workgroups x 128 VGPRs x 4 waves); option icp_wg_per_cu caps it so that the other stream's
-kernels find room.  usage: two_pipelines.py <frames per pipeline> <icp_wg_per_cu, 0 = uncapped> [steps]"""
+kernels find room.  (The library now overlaps the two stages inside ONE detector: fl_recognize_submit, option pipeline_icp.)
+usage: two_pipelines.py <frames per pipeline> <icp_wg_per_cu, 0 = uncapped> [steps]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
