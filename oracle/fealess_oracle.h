@@ -143,6 +143,18 @@ typedef struct {
 int  orc_icp(const float *ref, int n_ref, const float *model, int n_model,
              int icp_it_thr, float dist_mean_thr, float dist_diff_thr,
              int accum64, int use_kdtree, orc_icp_result *res, float *trace, int trace_cap);
+/* The helpers of icpCloudToCloud_Ex as entry points, in the reference's float32 arithmetic: getMean (ICP.cpp:8-25),
+ * getL2distClouds (:68-111; ref must hold at least n_model points; returns the inlier ratio), copyPoints (:48-65),
+ * transformPoints (:28-45; in_place != 0 is transformPoints(pts, pts, ..), else a fresh destination in which invalid
+ * points are zero) and PointsCorresponding on a prebuilt index (:193-279; returns the pair count, the pairs packed). */
+void  orc_get_mean(const float *pts, int n, float out[3]);
+float orc_l2dist_clouds(const float *model, int n_model, const float *ref, float dist_thr, float *dist_mean);
+void  orc_copy_points(const float *src, int n, float *dst);
+void  orc_transform_points(const float *src, int n, const float R[9], const float T[3], float *dst, int in_place);
+int   orc_points_corresponding(const float *ref, int n_ref, const float *model, int n_model, float dist_thr, int use_kdtree,
+                               float *cor_ref, float *cor_model);
+/* queries with two or more reference points at exactly the smallest float32 squared distance (by exhaustion) */
+int   orc_nn_tie_count(const float *ref, int n_ref, const float *q, int n_q);
 /* cv::SVD::compute on a 3x3 float matrix (OpenCV JacobiSVDImpl_<float> restated). A = U diag(W) Vt */
 void orc_svd3(const float A[9], float W[3], float U[9], float Vt[9]);
 /* detection() (ICP/detection.cpp:11-254, live lines) on two full-frame u16 depth images (mm). */

@@ -5,8 +5,17 @@
  * (ICP/detection.cpp:11-254, live lines), icpCloudToCloud_Ex and helpers (ICP/ICP.cpp:8-111,
  * 193-279,617-809) and CObjRecoLmICP::Recognition (CadReco/obj_reco_lmicp.cpp:86-204).
  *
- * PARITY UNPINNED.  cv::SVD (OpenCV JacobiSVDImpl_<float>) and the FLANN KDTreeSingleIndex
- * exact 1-NN are un-vendored third-party code, restated from their published algorithms.
+ * PARITY: the reference's own text is PINNED.  oracle/ref/icp_harness.cpp compiles ICP.cpp,
+ * common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp against a container-only opencv2/
+ * stand-in, and tests/test_reference_cpu.py compares this file with that library and with its
+ * recorded outputs (tests/golden/reference_icp.npz) bit for bit, accum64 = 0, both searches:
+ * control flow, operand order, which sum runs over which vector, which threshold meets which
+ * distance, after every prefix of the iteration count.  Recognition() is not compiled there.
+ * UNPINNED is the third-party arithmetic the reference only calls, restated here from the
+ * published algorithms: cv::SVD (OpenCV JacobiSVDImpl_<float>; the compiled reference is linked
+ * with orc_svd3 below), cv::gemm's double accumulators for vt.t() * u.t(), the Matx product order,
+ * cv::norm's double accumulation, convertTo's float(v) * float(1/1000.0), and FLANN's
+ * KDTreeSingleIndex exact 1-NN (exact ties go to the lowest index here; FLANN leaves them open).
  * Build with -ffp-contract=off: each float expression is one IEEE binary32 operation per
  * operator, in the order written (the reference is built for baseline x86-64: no FMA).
  */
@@ -292,6 +301,112 @@ static int all_finite(const float *v, int n)
   return 1;
 }
 
+/* getMean (ICP.cpp:8-25): every point counts, valid or not; sequential float32 sums */
+static void get_mean32(const float *pts, int n, float c[3])
+{
+  c[0] = c[1] = c[2] = 0.0f;
+  for (int i = 0; i < n; ++i) { c[0] += pts[3 * i]; c[1] += pts[3 * i + 1]; c[2] += pts[3 * i + 2]; }
+  if (n > 0) for (int k = 0; k < 3; ++k) c[k] /= (float)n;
+}
+
+/* copyPoints (ICP.cpp:48-65): dst.resize() zero-fills, invalid points stay Vec3f() = 0 */
+static void copy_points(const float *src, int n, float *dst)
+{
+  memset(dst, 0, sizeof(float) * 3 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+    if (vec_valid(src + 3 * i)) memcpy(dst + 3 * i, src + 3 * i, 12);
+}
+
+/* transformPoints(pts, pts, R, T) (ICP.cpp:28-45): in place, invalid points untouched */
+static void transform_points(float *pts, int n, const float *R, const float *T)
+{
+  for (int i = 0; i < n; ++i) {
+    float *p = pts + 3 * i;
+    if (!vec_valid(p)) continue;
+    float o[3];
+    mat_vec(R, p, o);
+    p[0] = o[0] + T[0];
+    p[1] = o[1] + T[1];
+    p[2] = o[2] + T[2];
+  }
+}
+
+/* PointsCorresponding on a prebuilt index (ICP.cpp:193-279): the SQUARED distance against dist_thr; returns the pairs */
+static int points_corresponding(const float *ref, int n_ref, const float *model, int n_model, const kd_tree *tree,
+                                float dist_thr, float *cor_ref, float *cor_model)
+{
+  int nc = 0;
+  for (int i = 0; i < n_model; ++i) {
+    int idx = -1;
+    float d = INFINITY;
+    if (tree) { kd_search(tree, 0, model + 3 * i, &idx, &d); if (idx < 0) d = NAN; }
+    else nn_brute(ref, n_ref, model + 3 * i, &idx, &d);
+    if (d <= dist_thr) {
+      memcpy(cor_model + 3 * nc, model + 3 * i, 12);
+      memcpy(cor_ref + 3 * nc, ref + 3 * idx, 12);
+      ++nc;
+    }
+  }
+  return nc;
+}
+
+static void kd_make(kd_tree *tree, const float *ref, int n_ref)
+{
+  memset(tree, 0, sizeof(*tree));
+  tree->cap = 2 * (n_ref / 8 + 2);
+  tree->nodes = (kd_node *)malloc(sizeof(kd_node) * tree->cap);
+  tree->perm = (int *)malloc(sizeof(int) * (n_ref > 0 ? n_ref : 1));
+  tree->pts = ref;
+  for (int i = 0; i < n_ref; ++i) tree->perm[i] = i;
+  kd_build(tree, 0, n_ref);
+}
+
+/* the helpers above as entry points, float32 mode, for the comparison with the reference's compiled functions */
+void orc_get_mean(const float *pts, int n, float out[3]) { get_mean32(pts, n, out); }
+float orc_l2dist_clouds(const float *model, int n_model, const float *ref, float dist_thr, float *dist_mean)
+{
+  return l2dist_clouds(model, ref, n_model, dist_mean, dist_thr, 0);
+}
+void orc_copy_points(const float *src, int n, float *dst) { copy_points(src, n, dst); }
+/* in_place == 0: transformPoints into a fresh vector, where invalid points are left at zero */
+void orc_transform_points(const float *src, int n, const float R[9], const float T[3], float *dst, int in_place)
+{
+  if (in_place) memcpy(dst, src, sizeof(float) * 3 * (size_t)n);
+  else copy_points(src, n, dst);
+  /* after copy_points an invalid source point is (0, 0, 0), which is valid: it must stay untouched all the same */
+  for (int i = 0; i < n; ++i) {
+    if (!vec_valid(src + 3 * i)) continue;
+    transform_points(dst + 3 * i, 1, R, T);
+  }
+}
+int orc_points_corresponding(const float *ref, int n_ref, const float *model, int n_model, float dist_thr, int use_kdtree,
+                             float *cor_ref, float *cor_model)
+{
+  kd_tree tree;
+  memset(&tree, 0, sizeof(tree));
+  if (use_kdtree && n_ref > 0) kd_make(&tree, ref, n_ref);
+  int n = points_corresponding(ref, n_ref, model, n_model, use_kdtree && n_ref > 0 ? &tree : NULL, dist_thr, cor_ref, cor_model);
+  free(tree.nodes);
+  free(tree.perm);
+  return n;
+}
+
+/* How many of the n_q queries have two or more reference points at exactly the smallest float32 squared distance: the
+ * searches whose answer FLANN leaves unspecified.  By exhaustion (the tests assert that their inputs have none). */
+int orc_nn_tie_count(const float *ref, int n_ref, const float *q, int n_q)
+{
+  int ties = 0;
+  for (int i = 0; i < n_q; ++i) {
+    int idx = -1, same = 0;
+    float d = INFINITY;
+    nn_brute(ref, n_ref, q + 3 * i, &idx, &d);
+    if (idx < 0) continue;
+    for (int j = 0; j < n_ref; ++j) same += d2f(q + 3 * i, ref + 3 * j) == d;
+    ties += same > 1;
+  }
+  return ties;
+}
+
 /* icpCloudToCloud_Ex (ICP.cpp:617-809) */
 int orc_icp(const float *ref, int n_ref, const float *model, int n_model,
             int icp_it_thr, float dist_mean_thr, float dist_diff_thr,
@@ -304,19 +419,11 @@ int orc_icp(const float *ref, int n_ref, const float *model, int n_model,
 
   kd_tree tree;
   memset(&tree, 0, sizeof(tree));
-  if (use_kdtree) {
-    tree.cap = 2 * (n_ref / 8 + 2);
-    tree.nodes = (kd_node *)malloc(sizeof(kd_node) * tree.cap);
-    tree.perm = (int *)malloc(sizeof(int) * n_ref);
-    tree.pts = ref;
-    for (int i = 0; i < n_ref; ++i) tree.perm[i] = i;
-    kd_build(&tree, 0, n_ref);
-  }
+  if (use_kdtree) kd_make(&tree, ref, n_ref);
 
   /* copyPoints(pts_model, pts_model_tmp) (:666-667): invalid points stay Vec3f() = 0 */
-  float *mt = (float *)calloc((size_t)n_model * 3, sizeof(float));
-  for (int i = 0; i < n_model; ++i)
-    if (vec_valid(model + 3 * i)) memcpy(mt + 3 * i, model + 3 * i, 12);
+  float *mt = (float *)malloc(sizeof(float) * 3 * (size_t)n_model);
+  copy_points(model, n_model, mt);
   float *cm = (float *)malloc(sizeof(float) * 3 * (size_t)n_model);
   float *cr = (float *)malloc(sizeof(float) * 3 * (size_t)n_ref);
 
@@ -328,37 +435,21 @@ int orc_icp(const float *ref, int n_ref, const float *model, int n_model,
     ++iter;
     int ncm = 0, ncr = 0;
     if (iter == 1) {                                     /* :700-704 */
-      memset(cm, 0, sizeof(float) * 3 * (size_t)n_model);
-      memset(cr, 0, sizeof(float) * 3 * (size_t)n_ref);
-      for (int i = 0; i < n_model; ++i)
-        if (vec_valid(mt + 3 * i)) memcpy(cm + 3 * i, mt + 3 * i, 12);
-      for (int i = 0; i < n_ref; ++i)
-        if (vec_valid(ref + 3 * i)) memcpy(cr + 3 * i, ref + 3 * i, 12);
+      copy_points(mt, n_model, cm);
+      copy_points(ref, n_ref, cr);
       ncm = n_model;
       ncr = n_ref;
     } else {                                             /* PointsCorresponding :193-279 */
       float thr = 3 * dist_mean;                         /* squared distance vs 3*mean (Q9) */
-      for (int i = 0; i < n_model; ++i) {
-        int idx = -1;
-        float d = INFINITY;
-        if (use_kdtree) { kd_search(&tree, 0, mt + 3 * i, &idx, &d); if (idx < 0) d = NAN; }
-        else nn_brute(ref, n_ref, mt + 3 * i, &idx, &d);
-        if (d <= thr) {
-          memcpy(cm + 3 * ncm, mt + 3 * i, 12);
-          memcpy(cr + 3 * ncr, ref + 3 * idx, 12);
-          ++ncm;
-          ++ncr;
-        }
-      }
+      ncm = ncr = points_corresponding(ref, n_ref, mt, n_model, use_kdtree ? &tree : NULL, thr, cr, cm);
     }
     n_corr_last = ncm;
     if (ncr < 3 || ncm < 3) { iter = icp_it_thr; continue; }                     /* :711-715 */
 
     float mc[3] = {0, 0, 0}, rc[3] = {0, 0, 0}, C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (!accum64) {
-      for (int i = 0; i < ncm; ++i) { mc[0] += cm[3 * i]; mc[1] += cm[3 * i + 1]; mc[2] += cm[3 * i + 2]; }   /* getMean :8-25 */
-      for (int i = 0; i < ncr; ++i) { rc[0] += cr[3 * i]; rc[1] += cr[3 * i + 1]; rc[2] += cr[3 * i + 2]; }
-      for (int k = 0; k < 3; ++k) { mc[k] /= (float)ncm; rc[k] /= (float)ncr; }
+      get_mean32(cm, ncm, mc);                                                      /* getMean :8-25 */
+      get_mean32(cr, ncr, rc);
       for (int i = 0; i < ncm; ++i)                                                 /* :731-735 */
         for (int a = 0; a < 3; ++a)
           for (int b = 0; b < 3; ++b) C[a * 3 + b] += cm[3 * i + a] * cr[3 * i + b];
@@ -395,15 +486,7 @@ int orc_icp(const float *ref, int n_ref, const float *model, int n_model,
     }
     if (!all_finite(Ropt, 9) || !all_finite(Topt, 3)) continue;                     /* :748-749 */
 
-    for (int i = 0; i < n_model; ++i) {                  /* transformPoints in place :28-45, :756 */
-      float *p = mt + 3 * i;
-      if (!vec_valid(p)) continue;
-      float o[3];
-      mat_vec(Ropt, p, o);
-      p[0] = o[0] + Topt[0];
-      p[1] = o[1] + Topt[1];
-      p[2] = o[2] + Topt[2];
-    }
+    transform_points(mt, n_model, Ropt, Topt);          /* transformPoints in place :28-45, :756 */
     dist_diff = dist_mean;                                                          /* :778-780 */
     float thr = 3 * dist_mean;
     px = l2dist_clouds(mt, ref, n_model, &dist_mean, thr, accum64);
@@ -467,9 +550,8 @@ int orc_detection(const uint16_t *model_depth, const uint16_t *scene_depth, int 
   res->n_points = np;
   float mc[3] = {0, 0, 0}, rc[3] = {0, 0, 0};                                      /* getMean x2 :165-166 */
   if (!accum64) {
-    for (int i = 0; i < np; ++i) for (int k = 0; k < 3; ++k) { mc[k] += pts_mod[3 * i + k]; }
-    for (int i = 0; i < np; ++i) for (int k = 0; k < 3; ++k) { rc[k] += pts_ref[3 * i + k]; }
-    if (np > 0) for (int k = 0; k < 3; ++k) { mc[k] /= (float)np; rc[k] /= (float)np; }
+    get_mean32(pts_mod, np, mc);
+    get_mean32(pts_ref, np, rc);
   } else {
     double m64[3] = {0, 0, 0}, r64[3] = {0, 0, 0};
     for (int i = 0; i < np; ++i) for (int k = 0; k < 3; ++k) { m64[k] += pts_mod[3 * i + k]; r64[k] += pts_ref[3 * i + k]; }
@@ -477,16 +559,8 @@ int orc_detection(const uint16_t *model_depth, const uint16_t *scene_depth, int 
   }
   float t_tmp[3], t_init[3];
   for (int k = 0; k < 3; ++k) { t_tmp[k] = rc[k] - mc[k]; t_init[k] = t_tmp[k] + t_match[k]; }   /* :177,:199 */
-  for (int i = 0; i < np; ++i) {                                                   /* transformPoints(I, t_tmp) :206 */
-    float *p = pts_mod + 3 * i;
-    if (!vec_valid(p)) continue;
-    static const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    float o[3];
-    mat_vec(I, p, o);
-    p[0] = o[0] + t_tmp[0];
-    p[1] = o[1] + t_tmp[1];
-    p[2] = o[2] + t_tmp[2];
-  }
+  static const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  transform_points(pts_mod, np, I, t_tmp);                                         /* transformPoints(I, t_tmp) :206 */
   orc_icp(pts_ref, np, pts_mod, np, icp_it_thr, dist_mean_thr, dist_diff_thr, accum64, use_kdtree,
           &res->icp, NULL, 0);                                                     /* :228 */
   float Rt[3];

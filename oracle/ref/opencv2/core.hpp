@@ -1,5 +1,6 @@
 // Container-only stand-in of <opencv2/core.hpp>, written from scratch for ONE purpose: to compile the reference's
-// linemod/linemod.cpp unchanged (oracle/ref/ref_harness.cpp includes it by include path at build time) on a machine
+// linemod/linemod.cpp and its ICP sources (ICP.cpp, common.cpp, depth_to_3d.cpp, detection.cpp, NMS.cpp) unchanged
+// (oracle/ref/ref_harness.cpp and oracle/ref/icp_harness.cpp include them by include path at build time) on a machine
 // without OpenCV, so that the oracle and the HIP kernels can be compared with the reference's own compiled arithmetic.
 // TEST INFRASTRUCTURE ONLY; nothing here is part of the product, and nothing here is copied from OpenCV or the reference.
 //
@@ -27,6 +28,16 @@
 //    roundings for those stays UNPINNED; this stand-in does not re-implement OpenCV arithmetic a second time and call it
 //    a reference.
 //
+//  * FOR THE ICP SOURCES (oracle/ref/icp_harness.cpp lists, item by item, which of these is OpenCV's header text restated
+//    and which is a choice of ours): Vec<T,n> and Matx<T,m,n> with the element-wise operators and the products of
+//    OpenCV's matx.hpp (s = 0; s += a(i,k) * b(k,j), in T); Mat_<T> with ROIs, element access and iterators that walk a
+//    ROI row by row; Rect_<T>; _InputArray / _OutputArray over a Mat; cv::norm (squares accumulated in double), cv::add
+//    on Vec, cv::checkRange (every element finite), Mat == scalar, setTo(value, mask) on CV_32FC1, getTickCount, and
+//    the conversions CV_16U -> CV_32F with a scale (float(v) * float(alpha)), CV_64F -> CV_32F and same-type copies;
+//    Mat * Mat on CV_32FC1 (double accumulators, as cv::gemm) and Mat::t().  cv::SVD::compute is declared here and
+//    defined by icp_harness.cpp on the oracle's orc_svd3.  The Mat expression arithmetic of depthTo3d_from_uvz, merge,
+//    split, reshape, resize(n), Mat(std::vector), Rodrigues and the window functions are declared only.
+//
 //  * THE ALLOCATOR zero-fills every buffer and puts a zeroed guard of two rows plus 4 KiB after it.  The reference reads
 //    past the last grid row of a linear memory (quirk Q2): undefined behaviour there, deterministic here, with the value
 //    the project already defined for it (reads 0).
@@ -39,6 +50,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <limits>
 #include <memory>
 #include <stdexcept>
@@ -67,6 +79,10 @@
 
 typedef unsigned char uchar;
 typedef unsigned short ushort;
+#include <stdint.h>
+typedef int64_t int64;
+
+#define CV_MAJOR_VERSION 3
 
 #define CV_8U 0
 #define CV_8S 1
@@ -82,6 +98,11 @@ typedef unsigned short ushort;
 #define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
 #define CV_16UC1 CV_MAKETYPE(CV_16U, 1)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
+#define CV_16UC3 CV_MAKETYPE(CV_16U, 3)
+#define CV_16SC1 CV_MAKETYPE(CV_16S, 1)
+#define CV_32FC2 CV_MAKETYPE(CV_32F, 2)
+#define CV_32FC3 CV_MAKETYPE(CV_32F, 3)
+#define CV_64FC1 CV_MAKETYPE(CV_64F, 1)
 
 #define CV_CPU_SSE2 3
 #define CV_CPU_SSE3 4
@@ -95,9 +116,20 @@ typedef unsigned short ushort;
     std::abort();                                                                                           \
   } while (0)
 
+inline int cvIsNaN(double v) { return std::isnan(v) ? 1 : 0; }
+
 namespace cv {
 
 typedef std::string String;
+
+// What the reference's ICP loop does not return but the stand-in sees it do (oracle/ref/icp_harness.cpp derives the
+// loop's final `iter` from them): searches of the cvflann index, and checkRange calls on a 3x3 matrix.
+struct FealessRefCounters { long knn_searches, check_range_3x3; };
+inline FealessRefCounters &fealess_ref_counters()
+{
+  static FealessRefCounters c = {0, 0};
+  return c;
+}
 
 class Exception : public std::runtime_error {
  public:
@@ -135,11 +167,12 @@ struct Point {
   Point() : x(0), y(0) {}
   Point(int x_, int y_) : x(x_), y(y_) {}
 };
-struct Rect {
-  int x, y, width, height;
-  Rect() : x(0), y(0), width(0), height(0) {}
-  Rect(int x_, int y_, int w, int h) : x(x_), y(y_), width(w), height(h) {}
+template <typename T> struct Rect_ {
+  T x, y, width, height;
+  Rect_() : x(0), y(0), width(0), height(0) {}
+  Rect_(T x_, T y_, T w, T h) : x(x_), y(y_), width(w), height(h) {}
 };
+typedef Rect_<int> Rect;
 struct Vec3b {
   uchar val[3];
   Vec3b() { val[0] = val[1] = val[2] = 0; }
@@ -154,15 +187,180 @@ struct Scalar {
 
 enum BorderTypes { BORDER_CONSTANT = 0, BORDER_REPLICATE = 1, BORDER_REFLECT = 2, BORDER_REFLECT_101 = 4, BORDER_DEFAULT = 4 };
 
+// ---- Matx / Vec: small fixed-size matrices, as OpenCV's matx.hpp states them ----------------------------------------------
+// Default construction zeroes; a product is `s = 0; s += a(i,k) * b(k,j)` in T, k ascending; the element-wise operators
+// are one T operation per element.
+template <typename T, int m, int n> class Matx {
+ public:
+  enum { rows = m, cols = n, channels = m * n };
+  T val[m * n];
+  Matx() { for (int i = 0; i < m * n; ++i) val[i] = T(0); }
+  Matx(T v0, T v1) { static_assert(m * n >= 2, "Matx"); zero(); val[0] = v0; val[1] = v1; }
+  Matx(T v0, T v1, T v2) { static_assert(m * n >= 3, "Matx"); zero(); val[0] = v0; val[1] = v1; val[2] = v2; }
+  Matx(T v0, T v1, T v2, T v3, T v4, T v5, T v6, T v7, T v8)
+  {
+    static_assert(m * n >= 9, "Matx");
+    zero();
+    val[0] = v0; val[1] = v1; val[2] = v2; val[3] = v3; val[4] = v4; val[5] = v5; val[6] = v6; val[7] = v7; val[8] = v8;
+  }
+  static Matx eye()
+  {
+    Matx M;
+    for (int i = 0; i < (m < n ? m : n); ++i) M(i, i) = T(1);
+    return M;
+  }
+  T &operator()(int i, int j) { return val[i * n + j]; }
+  const T &operator()(int i, int j) const { return val[i * n + j]; }
+  T &operator()(int i) { return val[i]; }
+  const T &operator()(int i) const { return val[i]; }
+  Matx<T, n, m> t() const
+  {
+    Matx<T, n, m> r;
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < n; ++j) r(j, i) = (*this)(i, j);
+    return r;
+  }
+
+ private:
+  void zero() { for (int i = 0; i < m * n; ++i) val[i] = T(0); }
+};
+
+template <typename T, int cn> class Vec : public Matx<T, cn, 1> {
+ public:
+  Vec() {}
+  Vec(T v0, T v1) : Matx<T, cn, 1>(v0, v1) {}
+  Vec(T v0, T v1, T v2) : Matx<T, cn, 1>(v0, v1, v2) {}
+  Vec(const Matx<T, cn, 1> &a) : Matx<T, cn, 1>(a) {}
+  T &operator[](int i) { return this->val[i]; }
+  const T &operator[](int i) const { return this->val[i]; }
+};
+typedef Vec<float, 2> Vec2f;
+typedef Vec<float, 3> Vec3f;
+typedef Vec<double, 3> Vec3d;
+typedef Matx<float, 3, 3> Matx33f;
+typedef Matx<double, 3, 3> Matx33d;
+
+template <typename T, int m, int n> inline Matx<T, m, n> &operator+=(Matx<T, m, n> &a, const Matx<T, m, n> &b)
+{
+  for (int i = 0; i < m * n; ++i) a.val[i] = a.val[i] + b.val[i];
+  return a;
+}
+template <typename T, int m, int n> inline Matx<T, m, n> &operator-=(Matx<T, m, n> &a, const Matx<T, m, n> &b)
+{
+  for (int i = 0; i < m * n; ++i) a.val[i] = a.val[i] - b.val[i];
+  return a;
+}
+template <typename T, int m, int n> inline Matx<T, m, n> operator-(const Matx<T, m, n> &a)
+{
+  Matx<T, m, n> r;
+  for (int i = 0; i < m * n; ++i) r.val[i] = -a.val[i];
+  return r;
+}
+template <typename T, int cn> inline Vec<T, cn> operator+(const Vec<T, cn> &a, const Vec<T, cn> &b)
+{
+  Vec<T, cn> r;
+  for (int i = 0; i < cn; ++i) r.val[i] = a.val[i] + b.val[i];
+  return r;
+}
+template <typename T, int cn> inline Vec<T, cn> operator-(const Vec<T, cn> &a, const Vec<T, cn> &b)
+{
+  Vec<T, cn> r;
+  for (int i = 0; i < cn; ++i) r.val[i] = a.val[i] - b.val[i];
+  return r;
+}
+// Vec *= int multiplies in T (matx.hpp: saturate_cast<T>(a[i] * alpha), the int promoted to T)
+template <typename T, int cn> inline Vec<T, cn> &operator*=(Vec<T, cn> &a, int alpha)
+{
+  for (int i = 0; i < cn; ++i) a.val[i] = a.val[i] * (T)alpha;
+  return a;
+}
+template <typename T, int m, int l, int n> inline Matx<T, m, n> operator*(const Matx<T, m, l> &a, const Matx<T, l, n> &b)
+{
+  Matx<T, m, n> r;
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < n; ++j) {
+      T s = 0;
+      for (int k = 0; k < l; ++k) s += a(i, k) * b(k, j);
+      r(i, j) = s;
+    }
+  return r;
+}
+template <typename T, int m, int n> inline Vec<T, m> operator*(const Matx<T, m, n> &a, const Vec<T, n> &b)
+{
+  return Vec<T, m>(a * static_cast<const Matx<T, n, 1> &>(b));
+}
+// cv::norm of a Matx: the squares accumulated in double in element order, the root in double
+template <typename T, int m, int n> inline double norm(const Matx<T, m, n> &a)
+{
+  double s = 0;
+  for (int i = 0; i < m * n; ++i) s += (double)a.val[i] * a.val[i];
+  return std::sqrt(s);
+}
+template <typename T, int cn> inline void add(const Vec<T, cn> &a, const Vec<T, cn> &b, Vec<T, cn> &c) { c = a + b; }
+// cv::checkRange with its default bounds (-DBL_MAX, DBL_MAX): every element finite
+template <typename T, int m, int n> inline bool checkRange(const Matx<T, m, n> &a)
+{
+  if (m == 3 && n == 3) ++fealess_ref_counters().check_range_3x3;
+  for (int i = 0; i < m * n; ++i)
+    if (!std::isfinite(a.val[i])) return false;
+  return true;
+}
+
+template <typename T> struct DataType;
+template <> struct DataType<uchar> { enum { depth = CV_8U, type = CV_8UC1 }; };
+template <> struct DataType<ushort> { enum { depth = CV_16U, type = CV_16UC1 }; };
+template <> struct DataType<short> { enum { depth = CV_16S, type = CV_16SC1 }; };
+template <> struct DataType<int> { enum { depth = CV_32S, type = CV_MAKETYPE(CV_32S, 1) }; };
+template <> struct DataType<float> { enum { depth = CV_32F, type = CV_32FC1 }; };
+template <> struct DataType<double> { enum { depth = CV_64F, type = CV_64FC1 }; };
+template <typename T, int cn> struct DataType<Vec<T, cn> > { enum { depth = DataType<T>::depth, type = CV_MAKETYPE(DataType<T>::depth, cn) }; };
+
+class Mat;
+template <typename T> class MatConstIterator_;
+template <typename T> class MatIterator_;
+// Mat::size: callable (m.size()) and comparable (a.size == b.size)
+struct MSize {
+  const Mat *m;
+  explicit MSize(const Mat *m_) : m(m_) {}
+  inline Size operator()() const;
+  inline bool operator==(const MSize &o) const;
+  bool operator!=(const MSize &o) const { return !(*this == o); }
+};
+
 class Mat {
  public:
   int rows, cols;
   uchar *data;
   size_t step;  // bytes per row
+  MSize size;
 
-  Mat() : rows(0), cols(0), data(NULL), step(0), type_(0) {}
-  Mat(int r, int c, int type) : rows(0), cols(0), data(NULL), step(0), type_(0) { create(r, c, type); }
-  Mat(Size s, int type) : rows(0), cols(0), data(NULL), step(0), type_(0) { create(s.height, s.width, type); }
+  Mat() : rows(0), cols(0), data(NULL), step(0), size(this), type_(0) {}
+  Mat(int r, int c, int type) : rows(0), cols(0), data(NULL), step(0), size(this), type_(0) { create(r, c, type); }
+  Mat(Size s, int type) : rows(0), cols(0), data(NULL), step(0), size(this), type_(0) { create(s.height, s.width, type); }
+  Mat(const Mat &m) : rows(m.rows), cols(m.cols), data(m.data), step(m.step), size(this), type_(m.type_), buf_(m.buf_) {}
+  Mat &operator=(const Mat &m)
+  {
+    assignFrom(m);
+    return *this;
+  }
+  template <typename T, int m, int n> explicit Mat(const Matx<T, m, n> &M) : rows(0), cols(0), data(NULL), step(0), size(this), type_(0)
+  {
+    create(m, n, DataType<T>::type);
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < n; ++j) ptr<T>(i)[j] = M(i, j);
+  }
+  template <typename T> explicit Mat(const std::vector<T> &) : rows(0), cols(0), data(NULL), step(0), size(this), type_(0)
+  {
+    FEALESS_REF_UNPINNED("Mat(std::vector)");
+  }
+  template <typename T, int m, int n> operator Matx<T, m, n>() const
+  {
+    CV_Assert(rows == m && cols == n && type_ == (int)DataType<T>::type);
+    Matx<T, m, n> M;
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < n; ++j) M(i, j) = ptr<T>(i)[j];
+    return M;
+  }
 
   static size_t depthSize(int type)
   {
@@ -175,7 +373,6 @@ class Mat {
   size_t elemSize1() const { return depthSize(type_); }
   size_t elemSize() const { return depthSize(type_) * CV_MAT_CN(type_); }
   size_t step1() const { return step / elemSize1(); }
-  Size size() const { return Size(cols, rows); }
   size_t total() const { return (size_t)rows * cols; }
   bool empty() const { return data == NULL || rows == 0 || cols == 0; }
 
@@ -210,9 +407,17 @@ class Mat {
   const uchar *ptr(int r = 0) const { return data + step * (size_t)r; }
   template <typename T> T &at(int r, int c) { return ptr<T>(r)[c]; }
   template <typename T> const T &at(int r, int c) const { return ptr<T>(r)[c]; }
+  template <typename T> T *ptr(int r, int c) { return ptr<T>(r) + c; }
+  template <typename T> const T *ptr(int r, int c) const { return ptr<T>(r) + c; }
+  template <typename T> inline MatIterator_<T> begin();
+  template <typename T> inline MatIterator_<T> end();
+  template <typename T> inline MatConstIterator_<T> begin() const;
+  template <typename T> inline MatConstIterator_<T> end() const;
 
+  // a ROI that leaves the matrix is refused, as cv::Mat's constructor asserts
   Mat operator()(const Rect &roi) const
   {
+    CV_Assert(0 <= roi.x && 0 <= roi.width && roi.x + roi.width <= cols && 0 <= roi.y && 0 <= roi.height && roi.y + roi.height <= rows);
     Mat m(*this);
     m.data = data + step * (size_t)roi.y + elemSize() * (size_t)roi.x;
     m.rows = roi.height;
@@ -245,16 +450,36 @@ class Mat {
   }
   Mat &setTo(const Scalar &v, const Mat &mask = Mat())
   {
-    CV_Assert(type_ == CV_8UC1);
+    CV_Assert(type_ == CV_8UC1 || type_ == CV_32FC1);
+    CV_Assert(mask.empty() || (mask.rows == rows && mask.cols == cols && mask.type() == CV_8UC1));
     for (int r = 0; r < rows; ++r)
       for (int c = 0; c < cols; ++c)
-        if (mask.empty() || mask.ptr(r)[c]) ptr(r)[c] = (uchar)v.val[0];
+        if (mask.empty() || mask.ptr(r)[c]) {
+          if (type_ == CV_8UC1) ptr(r)[c] = (uchar)v.val[0];
+          else ptr<float>(r)[c] = (float)v.val[0];
+        }
     return *this;
   }
-  // defined for CV_8U -> CV_16U (alpha 1) and CV_32F -> CV_8U (any alpha), beta 0, one channel (see the header comment);
-  // any other conversion is OpenCV's
+  // defined for CV_8U -> CV_16U (alpha 1) and CV_32F -> CV_8U (any alpha), beta 0, one channel (see the header comment),
+  // and for what the ICP sources convert: a copy (same depth, alpha 1), CV_64F -> CV_32F (alpha 1) and CV_16U -> CV_32F
+  // with a scale, float(v) * float(alpha): the scale narrowed to the destination's type before the product, which is
+  // what a cv::Mat::convertTo to CV_32F does.  Any other conversion is OpenCV's
   void convertTo(Mat &dst, int rtype, double alpha = 1, double beta = 0) const
   {
+    const int ddepth = CV_MAT_DEPTH(rtype), cn = channels();
+    if (beta == 0 && !empty() && ((ddepth == depth() && alpha == 1) || (depth() == CV_64F && ddepth == CV_32F && alpha == 1) ||
+                                  (depth() == CV_16U && ddepth == CV_32F))) {
+      Mat src(*this);                                      // dst may be *this
+      dst.create(src.rows, src.cols, CV_MAKETYPE(ddepth, cn));
+      const float a = (float)alpha;
+      for (int r = 0; r < src.rows; ++r)
+        for (int c = 0; c < src.cols * cn; ++c) {
+          if (ddepth == src.depth()) std::memmove(dst.ptr(r) + src.elemSize1() * c, src.ptr(r) + src.elemSize1() * c, src.elemSize1());
+          else if (src.depth() == CV_64F) dst.ptr<float>(r)[c] = (float)src.ptr<double>(r)[c];
+          else dst.ptr<float>(r)[c] = (float)src.ptr<ushort>(r)[c] * a;
+        }
+      return;
+    }
     if (depth() == CV_32F && channels() == 1 && CV_MAT_DEPTH(rtype) == CV_8U && beta == 0) {
       Mat out(rows, cols, CV_8UC1);  // not dst.create(): dst may be *this
       for (int r = 0; r < rows; ++r)
@@ -273,39 +498,203 @@ class Mat {
   }
   // header copy that keeps the static type of a Mat_<T> target
   void assignFrom(const Mat &m) { rows = m.rows; cols = m.cols; data = m.data; step = m.step; type_ = m.type_; buf_ = m.buf_; }
+  // the transpose of a one-channel CV_32F matrix (a copy: nothing to round)
+  Mat t() const
+  {
+    if (type_ != CV_32FC1) FEALESS_REF_UNPINNED("Mat::t (other than CV_32FC1)");
+    Mat o(cols, rows, type_);
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) o.ptr<float>(c)[r] = ptr<float>(r)[c];
+    return o;
+  }
+  Mat mul(const Mat &) const { FEALESS_REF_UNPINNED("Mat::mul"); }
+  void resize(size_t) { FEALESS_REF_UNPINNED("Mat::resize"); }
+  Mat reshape(int, int) const { FEALESS_REF_UNPINNED("Mat::reshape"); }
+  inline void copyTo(const class _OutputArray &dst) const;
 
  protected:
   int type_;
   std::shared_ptr<void> buf_;
 };
 
+inline Size MSize::operator()() const { return Size(m->cols, m->rows); }
+inline bool MSize::operator==(const MSize &o) const { return m->rows == o.m->rows && m->cols == o.m->cols; }
+
+// Iterators over a Mat or a ROI of one: row by row, each row left to right, as cv::MatConstIterator_
+template <typename T> class MatConstIterator_ {
+ public:
+  MatConstIterator_() : m_(NULL), r_(0), c_(0) {}
+  MatConstIterator_(const Mat *m, bool at_end) : m_(m), r_(at_end || m->cols == 0 ? m->rows : 0), c_(0) {}
+  const T &operator*() const { return m_->template ptr<T>(r_)[c_]; }
+  MatConstIterator_ &operator++()
+  {
+    if (++c_ >= m_->cols) { c_ = 0; ++r_; }
+    return *this;
+  }
+  bool operator==(const MatConstIterator_ &o) const { return r_ == o.r_ && c_ == o.c_; }
+  bool operator!=(const MatConstIterator_ &o) const { return !(*this == o); }
+
+ protected:
+  const Mat *m_;
+  int r_, c_;
+};
+template <typename T> class MatIterator_ : public MatConstIterator_<T> {
+ public:
+  MatIterator_() {}
+  MatIterator_(Mat *m, bool at_end) : MatConstIterator_<T>(m, at_end) {}
+  T &operator*() const { return const_cast<T &>(MatConstIterator_<T>::operator*()); }
+  MatIterator_ &operator++()
+  {
+    MatConstIterator_<T>::operator++();
+    return *this;
+  }
+};
+template <typename T> inline MatIterator_<T> Mat::begin() { return MatIterator_<T>(this, false); }
+template <typename T> inline MatIterator_<T> Mat::end() { return MatIterator_<T>(this, true); }
+template <typename T> inline MatConstIterator_<T> Mat::begin() const { return MatConstIterator_<T>(this, false); }
+template <typename T> inline MatConstIterator_<T> Mat::end() const { return MatConstIterator_<T>(this, true); }
+
+// A Mat whose element type is fixed: an empty one already has it, and a Mat of another depth is converted on the way in
 template <typename T> class Mat_ : public Mat {
  public:
-  Mat_() : Mat() {}
+  typedef MatIterator_<T> iterator;
+  typedef MatConstIterator_<T> const_iterator;
+  Mat_() : Mat() { type_ = DataType<T>::type; }
+  Mat_(int r, int c) : Mat(r, c, DataType<T>::type) {}
+  Mat_(int r, int c, const T &v) : Mat(r, c, DataType<T>::type)
+  {
+    for (int i = 0; i < r; ++i)
+      for (int j = 0; j < c; ++j) (*this)(i, j) = v;
+  }
+  explicit Mat_(Size s) : Mat(s.height, s.width, DataType<T>::type) {}
+  Mat_(const Mat &m) : Mat() { type_ = DataType<T>::type; *this = m; }
+  Mat_(const Mat_ &m) : Mat(m) {}
+  Mat_ &operator=(const Mat_ &m)
+  {
+    assignFrom(m);
+    return *this;
+  }
+  Mat_ &operator=(const Mat &m)
+  {
+    if (m.type() == (int)DataType<T>::type) assignFrom(m);
+    else if (m.empty()) { Mat e; assignFrom(e); type_ = DataType<T>::type; }
+    else if (m.channels() == CV_MAT_CN((int)DataType<T>::type)) m.convertTo(*this, DataType<T>::type);
+    else FEALESS_REF_UNPINNED("Mat_ = Mat with another channel count");
+    return *this;
+  }
   T &operator()(int r, int c) { return this->template ptr<T>(r)[c]; }
   const T &operator()(int r, int c) const { return this->template ptr<T>(r)[c]; }
+  // one index: into a single row or a single column
+  T &operator()(int i) { return rows == 1 ? (*this)(0, i) : (*this)(i / cols, i % cols); }
+  const T &operator()(int i) const { return rows == 1 ? (*this)(0, i) : (*this)(i / cols, i % cols); }
+  T *operator[](int r) { return this->template ptr<T>(r); }
+  const T *operator[](int r) const { return this->template ptr<T>(r); }
+  Mat_ operator()(const Rect &roi) const { return Mat_(Mat::operator()(roi)); }
+  iterator begin() { return Mat::begin<T>(); }
+  iterator end() { return Mat::end<T>(); }
+  const_iterator begin() const { return Mat::begin<T>(); }
+  const_iterator end() const { return Mat::end<T>(); }
 };
 
-// noArray() or a std::vector<Mat> to be filled: all that Detector::match asks of its optional output
-class _OutputArray {
+// An argument that is a Mat (or nothing); as an output also a std::vector<Mat> to be filled, which is all that
+// Detector::match asks of its optional output
+class _InputArray {
  public:
-  _OutputArray() : vec_(NULL) {}
-  _OutputArray(std::vector<Mat> &v) : vec_(&v) {}
-  bool needed() const { return vec_ != NULL; }
-  void create(int r, int c, int /*type*/) const { if (vec_) vec_->resize((size_t)r * c); }
+  _InputArray() : in_(NULL) {}
+  _InputArray(const Mat &m) : in_(&m) {}
+  Mat getMat() const { return in_ ? *in_ : Mat(); }
+
+ protected:
+  const Mat *in_;
+};
+class _OutputArray : public _InputArray {
+ public:
+  _OutputArray() : vec_(NULL), out_(NULL) {}
+  _OutputArray(std::vector<Mat> &v) : vec_(&v), out_(NULL) {}
+  _OutputArray(Mat &m) : _InputArray(m), vec_(NULL), out_(&m) {}
+  _OutputArray(const Mat &m) : _InputArray(m), vec_(NULL), out_(const_cast<Mat *>(&m)) {}
+  bool needed() const { return vec_ != NULL || out_ != NULL; }
+  void create(int r, int c, int type) const
+  {
+    if (vec_) vec_->resize((size_t)r * c);
+    else if (out_) out_->create(r, c, type);
+  }
+  void create(Size s, int type) const { create(s.height, s.width, type); }
   Mat &getMatRef(int i) const { return (*vec_)[i]; }
 
  private:
   std::vector<Mat> *vec_;
+  Mat *out_;
 };
+typedef const _InputArray &InputArray;
 typedef const _OutputArray &OutputArray;
 typedef const _OutputArray &OutputArrayOfArrays;
-typedef const _OutputArray &InputArray;
 inline const _OutputArray &noArray()
 {
   static const _OutputArray none;
   return none;
 }
+inline void Mat::copyTo(const _OutputArray &) const { FEALESS_REF_UNPINNED("Mat::copyTo(OutputArray)"); }
+
+// ---- defined for the ICP sources -----------------------------------------------------------------------------------
+// Mat * Mat on one-channel CV_32F: cv::gemm keeps double accumulators for float matrices, k ascending
+inline Mat operator*(const Mat &a, const Mat &b)
+{
+  if (a.type() != CV_32FC1 || b.type() != CV_32FC1 || a.cols != b.rows) FEALESS_REF_UNPINNED("Mat * Mat (other than CV_32FC1)");
+  Mat o(a.rows, b.cols, CV_32FC1);
+  for (int i = 0; i < a.rows; ++i)
+    for (int j = 0; j < b.cols; ++j) {
+      double s = 0;
+      for (int k = 0; k < a.cols; ++k) s += (double)a.ptr<float>(i)[k] * (double)b.ptr<float>(k)[j];
+      o.ptr<float>(i)[j] = (float)s;
+    }
+  return o;
+}
+// Mat == value on CV_16UC1: 255 where equal, 0 elsewhere
+inline Mat operator==(const Mat &a, double v)
+{
+  if (a.type() != CV_16UC1) FEALESS_REF_UNPINNED("Mat == scalar (other than CV_16UC1)");
+  Mat o(a.rows, a.cols, CV_8UC1);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) o.ptr(r)[c] = (double)a.ptr<ushort>(r)[c] == v ? 255 : 0;
+  return o;
+}
+// cv::norm(a, b), NORM_L2, of two CV_32F matrices of one shape: the differences taken in double, their squares
+// accumulated in double in element order (the oracle's statement of it; OpenCV's own order of the subtraction and the
+// widening is not pinned, and the tests keep to coordinates on which the two agree)
+inline double norm(const Mat &a, const Mat &b)
+{
+  if (a.depth() != CV_32F || a.type() != b.type() || a.rows != b.rows || a.cols != b.cols) FEALESS_REF_UNPINNED("norm(Mat, Mat) (other than CV_32F)");
+  double s = 0;
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols * a.channels(); ++c) {
+      const double d = (double)a.ptr<float>(r)[c] - (double)b.ptr<float>(r)[c];
+      s += d * d;
+    }
+  return std::sqrt(s);
+}
+inline int64 getTickCount()
+{
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (int64)ts.tv_sec * 1000000000 + ts.tv_nsec;
+}
+inline double getTickFrequency() { return 1e9; }
+// defined by oracle/ref/icp_harness.cpp on the oracle's orc_svd3 (OpenCV's JacobiSVD restated there: unpinned)
+struct SVD {
+  static void compute(const Matx33f &src, Mat &w, Mat &u, Mat &vt);
+};
+
+// ---- declared only: the Mat expression arithmetic of depthTo3d_from_uvz and what else the dead paths name -----------------
+inline Mat operator+(const Mat &, const Mat &) { FEALESS_REF_UNPINNED("Mat + Mat"); }
+inline Mat operator+(const Mat &, double) { FEALESS_REF_UNPINNED("Mat + scalar"); }
+inline Mat operator-(const Mat &, double) { FEALESS_REF_UNPINNED("Mat - scalar"); }
+inline Mat operator*(const Mat &, double) { FEALESS_REF_UNPINNED("Mat * scalar"); }
+inline Mat operator*(double, const Mat &) { FEALESS_REF_UNPINNED("scalar * Mat"); }
+inline Mat operator/(const Mat &, double) { FEALESS_REF_UNPINNED("Mat / scalar"); }
+inline Mat operator|(const Mat &, const Mat &) { FEALESS_REF_UNPINNED("Mat | Mat"); }
+inline void merge(const std::vector<Mat> &, Mat &) { FEALESS_REF_UNPINNED("merge"); }
+inline void split(const Mat &, std::vector<Mat> &) { FEALESS_REF_UNPINNED("split"); }
 
 // ---- declared only: persistence ---------------------------------------------------------------------------------
 class FileNode;

@@ -4,21 +4,26 @@
 The reference ships no golden vectors, known-answer tests or fixtures for this path and cannot
 be built or run here (OpenCV 3.x is absent), so these vectors pin the oracle *restatement*
 against regressions and give the HIP path a data-only target that travels to the GPU box --
-they do NOT pin the oracle to the reference; reference_linemod.npz (--reference, below) does that for the LINEMOD half.
+they do NOT pin the oracle to the reference; reference_linemod.npz and reference_icp.npz (--reference, below) do that for the
+LINEMOD half and for the ICP half.
 Run:  python tests/golden/make_golden.py     (inputs are seeded; output is deterministic)
 
 `--reference DIR` instead records what the CPU tests compare against the reference's own sources, as data, so that the
 tests need no copy of the reference: the two tables of DIR/linemod (reference_tables.npz) and the layout table and linked
 symbols of a CadReco caller compiled against DIR/CadReco's headers (cadreco_reference_abi.txt; needs build() first), and
 the outputs of DIR/linemod/linemod.cpp, compiled against the stand-in of oracle/ref, on the cases of tests/reference_cases.py
-(reference_linemod.npz).
+(reference_linemod.npz), and those of DIR/ICP's ICP.cpp, common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp, compiled the same
+way, on the ICP cases of that module (reference_icp.npz: results only, written with fixed time stamps so that a second run gives
+the same bytes).
 """
+import io
 import os
 import re
 import shutil
 import subprocess
 import sys
 import tempfile
+import zipfile
 
 import numpy as np
 
@@ -125,6 +130,7 @@ def reference_fixtures(ref):
         f.write("\n".join(layout + ["--symbols"] + syms) + "\n")
     print("reference fixtures:", len(layout), "layout rows,", len(syms), "symbols")
     reference_linemod_fixture(ref)
+    reference_icp_fixture(ref)
 
 
 def reference_linemod_fixture(ref):
@@ -148,6 +154,36 @@ def reference_linemod_fixture(ref):
     path = os.path.join(HERE, "reference_linemod.npz")
     np.savez_compressed(path, **rec)
     print("reference linemod fixture:", len(rec), "entries,", os.path.getsize(path) // 1024, "KiB")
+
+
+def save_npz_reproducibly(path, arrays):
+    """np.savez_compressed with the members in sorted order and a fixed time stamp: the same arrays give the same bytes."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[k]), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def reference_icp_fixture(ref):
+    """Outputs of the reference's COMPILED ICP sources (oracle/ref/icp_harness.cpp, built here from `ref`) on the ICP case
+    list of tests/reference_cases.py -> reference_icp.npz.  Results only: a digest of every case's inputs (regenerated from
+    seeds), the float results as bit patterns, the ints, and a digest in place of every large array, one member per case
+    (RC.recorded)."""
+    import reference_cases as RC
+    import reference_py as R
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle", "ref")], env=dict(os.environ, FEALESS_REFERENCE_ROOT=os.path.abspath(ref)))
+    B = RC.ReferenceIcpBackend(R.icp_lib())
+    rec = {}
+    for g, (cases, fn) in RC.icp_groups().items():
+        for name, c in cases:
+            rec[f"{g}/{name}"] = RC.recorded(fn(B, c))
+    path = os.path.join(HERE, "reference_icp.npz")
+    save_npz_reproducibly(path, rec)
+    print("reference icp fixture:", len(rec), "entries,", os.path.getsize(path) // 1024, "KiB")
 
 
 if __name__ == "__main__":

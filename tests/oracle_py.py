@@ -1,8 +1,8 @@
 """ctypes binding of oracle/liboracle.so -- the CPU restatement of the reference hot path.
 
 TEST INFRASTRUCTURE.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
-import this module; the product (fealess_amd) never does.  Its LINEMOD half is compared bit for bit with the reference's own
-compiled code through tests/reference_py.py, the twin of this module.
+import this module; the product (fealess_amd) never does.  Its LINEMOD half and its ICP half are compared bit for bit with the
+reference's own compiled code through tests/reference_py.py, the twin of this module.
 """
 import ctypes as C
 import os
@@ -470,3 +470,67 @@ def crop_templates(templates, feats):
     bb = (C.c_int * 4)()
     lib().orc_crop_templates(_p(t), len(t), _p(f), bb)
     return t, f, tuple(bb)
+
+
+# ---- ICP helpers and NMS under the signatures tests/reference_py.RefIcp mirrors one to one ------------------------------------
+def _cloud(a):
+    return np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+
+
+def get_mean(pts):
+    pts = _cloud(pts)
+    out = np.zeros(3, np.float32)
+    lib().orc_get_mean(_p(pts), len(pts), _p(out))
+    return out
+
+
+def l2dist_clouds(model, ref, dist_thr=np.finfo(np.float32).max):
+    """getL2distClouds: (inlier ratio, dist_mean) as float32."""
+    model, ref = _cloud(model), _cloud(ref)
+    assert len(ref) >= len(model)
+    lib().orc_l2dist_clouds.restype = C.c_float
+    dm = C.c_float(0)
+    ratio = lib().orc_l2dist_clouds(_p(model), len(model), _p(ref), C.c_float(dist_thr), C.byref(dm))
+    return np.float32(ratio), np.float32(dm.value)
+
+
+def copy_points(src):
+    src = _cloud(src)
+    out = np.full_like(src, 7.0)
+    lib().orc_copy_points(_p(src), len(src), _p(out))
+    return out
+
+
+def transform_points(src, R, T, in_place):
+    src = _cloud(src)
+    out = np.full_like(src, 7.0)
+    R, T = np.ascontiguousarray(R, np.float32), np.ascontiguousarray(T, np.float32)
+    lib().orc_transform_points(_p(src), len(src), _p(R), _p(T), _p(out), int(in_place))
+    return out
+
+
+def points_corresponding(ref, model, dist_thr, use_kdtree=True):
+    """PointsCorresponding on a prebuilt index: (cor_ref, cor_model)."""
+    ref, model = _cloud(ref), _cloud(model)
+    cr, cm = np.zeros_like(model), np.zeros_like(model)
+    n = lib().orc_points_corresponding(_p(ref), len(ref), _p(model), len(model), C.c_float(dist_thr), int(use_kdtree), _p(cr), _p(cm))
+    return cr[:n].copy(), cm[:n].copy()
+
+
+def nn_tie_count(ref, queries):
+    """Queries with two or more reference points at exactly the smallest float32 squared distance."""
+    ref, q = _cloud(ref), _cloud(queries)
+    return int(lib().orc_nn_tie_count(_p(ref), len(ref), _p(q), len(q)))
+
+
+def nms(t, n_points, icp_dist, th_obj_dist):
+    """nonMaximumSuppression over objects given by their translation, model point count and ICP distance: the winners."""
+    n = len(n_points)
+    res = (OrcRecognitionResult * max(1, n))()
+    for i in range(n):
+        res[i].det.T_final[:] = [float(v) for v in np.asarray(t, np.float32).reshape(-1, 3)[i]]
+        res[i].det.n_points = int(n_points[i])
+        res[i].det.icp.dist_mean = float(icp_dist[i])
+    win = (C.c_int * max(1, n))()
+    nw = lib().orc_nms(res, n, C.c_float(th_obj_dist), win)
+    return [int(win[i]) for i in range(nw)]

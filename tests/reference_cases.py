@@ -17,7 +17,20 @@ that property of the input (never of an output):
   * the SSE2 spread stores 16 bytes aligned at every row start, so the SIMD build takes widths that are multiples of 16;
   * hysteresisGradient's one OpenCV call, convertTo(CV_8U, 16/360), agrees between a float and a double product on every
     float in [0, 360] except two, which the angle pools leave out (angles_unambiguous);
+  * icpCloudToCloud_Ex walks the ref iterator past its end when the model has more points than the reference cloud
+    (getL2distClouds, the covariance loop): no case has n_model > n_ref (check_icp_case);
+  * which of two reference points at exactly the same float32 squared distance FLANN returns is unspecified: no case has
+    such a tie at any search the loop performs (nn_ties, by exhaustion over the iterations actually run), except the cases
+    whose name starts with "tie_", which are DEFINED BY THE STAND-IN'S RULE (lowest index), UNSPECIFIED IN FLANN, and kept
+    in a group of their own like q2_;
+  * detection()'s two crops must have one size and lie inside the frame (the second is the reference's own CV_Assert, Q10,
+    and is recorded as a refusal); cv::norm(t_i, t_j) in nonMaximumSuppression is taken on small integers, where the order
+    of the subtraction and the widening to double cannot matter.
+
+The ICP half (icp_groups) follows the same pattern on tests/golden/reference_icp.npz: that record holds digests of the inputs
+and RESULTS ONLY (float bit patterns as uint32, ints, digests of the clouds depthTo3d returns), no cloud and no image.
 """
+import functools
 import hashlib
 
 import numpy as np
@@ -623,3 +636,419 @@ def same(a, b):
         if x.dtype != y.dtype or x.shape != y.shape or x.tobytes() != y.tobytes():
             return k
     return None
+
+
+# ======================================================================================================================
+# The ICP half: icpCloudToCloud_Ex and its helpers, detection(), depthTo3d, nonMaximumSuppression
+# ======================================================================================================================
+FLT_MAX = float(np.finfo(np.float32).max)
+RUN_ALL = (0.0, -3.0e38)                                    # every iteration runs; the suite's other two: (0.3, 0.01), (0.5, 0.01)
+EDGE_INDICES = (0, 63, 64, 255, 256, -1)                    # first / last lane of a wave, of a 256-thread workgroup, last point
+
+
+def fbits(a):
+    """float32 -> uint32 bit patterns; every NaN as the one quiet NaN (a NaN's sign and payload carry no meaning)."""
+    a = np.ascontiguousarray(a, np.float32)
+    out = a.view(np.uint32).copy()
+    out[np.isnan(a)] = 0x7FC00000
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _object_pool(seed, n, noise):
+    rng = np.random.default_rng(seed)
+    R, t = synth.object_pose(tz=650.0)
+    depth, _, mask = synth.render(640, 480, R, t, seed=seed, noise=True, background=False)
+    ys, xs = np.nonzero(mask)
+    sel = rng.choice(len(ys), size=min(n, len(ys)), replace=False)
+    sel.sort()
+    z = depth[ys[sel], xs[sel]].astype(np.float32)
+    ref = np.stack([(xs[sel] - 320.0) / 608.0 * z, (ys[sel] - 240.0) / 608.0 * z, z], 1).astype(np.float32)
+    dR = synth.rot_z(0.02) @ synth.rot_x(-0.015) @ synth.rot_y(0.01)
+    c = ref.mean(0)
+    model = ((ref - c) @ dR.T + c + np.array([1.5, -2.0, 1.0])).astype(np.float32)
+    model += rng.normal(0, noise, model.shape).astype(np.float32)
+    return ref, model
+
+
+def object_clouds(seed, n=6000, noise=0.3):
+    """A paired cloud: reference = points on the synthetic object, model = rigidly perturbed copy (the clouds of
+    tests/test_gpu_icp.py)."""
+    ref, model = _object_pool(seed, n, noise)
+    return ref.copy(), model.copy()
+
+
+def _shuffled(seed, n):
+    """n pairs of the object clouds in random order: both ends of the arrays are inliers, not the object's outline."""
+    ref, model = object_clouds(1 + seed % 4, 1500)             # four renders serve every case; the seed picks and orders the points
+    p = np.random.default_rng(seed + 1000).permutation(len(ref))[:n]
+    return ref[p].copy(), model[p].copy()
+
+
+def _invalidate(a, n):
+    """z > 900 and z = NaN at the edge indices; and the bound itself: z = 900 is valid, the next float is not."""
+    for k, i in enumerate(EDGE_INDICES):
+        if i < n:
+            a[i, 2] = np.float32(950.0 + k) if k % 2 == 0 else np.float32(np.nan)
+    a[n // 2, 2] = np.float32(900.0)
+    a[n // 2 + 1, 2] = np.nextafter(np.float32(900.0), np.float32(1000.0))
+
+
+def icp_cases():
+    """(name, kind, n_model, n_ref, seed, icp_it_thr, dist_mean_thr, dist_diff_thr)."""
+    out = []
+    sizes = [3, 4, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 1500]
+    for i, n in enumerate(sizes):
+        out.append((f"icp_clean_{n}", "clean", n, n, 100 + i, 8, *RUN_ALL))
+    out.append(("icp_clean_257_1025", "clean", 257, 1025, 120, 8, *RUN_ALL))
+    out.append(("icp_clean_1024_1500", "clean", 1024, 1500, 121, 8, *RUN_ALL))
+    out.append(("icp_refused_2_2", "clean", 2, 2, 122, 8, *RUN_ALL))
+    for i, n in enumerate((65, 257, 1025)):
+        for kind in ("invalid_model", "invalid_ref", "invalid_both", "nan_valid_model", "nan_valid_ref", "far", "all_invalid_model", "all_invalid_ref"):
+            out.append((f"icp_{kind}_{n}", kind, n, n, 200 + 10 * i + len(kind), 3 if kind.startswith("all_invalid") else 8, *RUN_ALL))
+        out.append((f"icp_identical_{n}", "identical", n, n, 300 + i, 8, 0.0, 0.01))
+        out.append((f"icp_growing_{n}", "growing", n, n, 310 + i, 8, 0.0, 0.0))     # the reference's default thresholds: only a rise ends it
+        for it in (0, 1, 2):
+            out.append((f"icp_clean_{n}_it{it}", "clean", n, n, 320 + i, it, *RUN_ALL))
+        for a, b in ((0.3, 0.01), (0.5, 0.01)):
+            out.append((f"icp_clean_{n}_thr{a:g}", "clean", n, n, 330 + i, 8, a, b))
+        out.append((f"tie_icp_duplicate_ref_{n}", "tie", n, n, 340 + i, 8, *RUN_ALL))
+    return out
+
+
+def icp_input(case):
+    """(ref, model) float32 clouds of a case."""
+    _, kind, nm, nr, seed, *_ = case
+    ref, model = _shuffled(seed, max(nm, nr))
+    model = model[:nm].copy()
+    rng = np.random.default_rng(seed + 5)
+    if kind in ("invalid_model", "invalid_both"):
+        _invalidate(model, nm)
+    if kind in ("invalid_ref", "invalid_both"):
+        _invalidate(ref[::-1] if kind == "invalid_both" else ref, nr)     # both: the mirrored indices, so that pairs lose one side each
+    if kind == "nan_valid_model":
+        model[1] = (np.nan, np.nan, 500.0)                    # "valid" (z <= 900) and poisons the first centroid
+    if kind == "nan_valid_ref":
+        ref[1] = (np.nan, np.nan, 500.0)
+    if kind == "far":
+        # sparse points in a 600 mm cube, every model point 8 to 12 mm from its partner: after the first pass the squared
+        # distances (~100) are above 3 * dist_mean (~30), so fewer than 3 pairs survive
+        ref = np.stack([rng.uniform(-300, 300, nr), rng.uniform(-300, 300, nr), rng.uniform(300, 800, nr)], 1).astype(np.float32)
+        d = rng.normal(size=(nm, 3))
+        d *= (rng.uniform(8, 12, nm) / np.linalg.norm(d, axis=1))[:, None]
+        model = (ref[:nm] + d).astype(np.float32)
+    if kind == "all_invalid_model":                           # copyPoints turns every point into (0, 0, 0), which is valid
+        model[:, 2] = np.float32(950.0)
+    if kind == "all_invalid_ref":                             # the reference cloud is used as it is: counter == 0, FLT_MAX
+        ref[:, 2] = np.float32(950.0)
+    if kind == "identical":
+        model = ref[:nm].copy()
+    if kind == "growing":
+        # model point i lies on reference point i + 1 of the cloud sorted by x.  The first pass trusts the pairing by index
+        # and shifts the model towards its partners; the nearest-neighbour passes pull it back onto the points it lies on, so
+        # the mean distance of the index pairs, which is what the loop watches, goes up again
+        pool = object_clouds(1 + seed % 4, 1500)[0]
+        pool = pool[np.argsort(pool[:, 0], kind="stable")][::len(pool) // (nr + 1)][:nr + 1]
+        ref = pool[:nr].copy()
+        model = (pool[1:nm + 1] + rng.normal(0, 0.05, (nm, 3))).astype(np.float32)
+    if kind == "tie":
+        ref[nr // 3] = ref[nr // 7]                          # two reference points at one place: every search near them ties
+    return np.ascontiguousarray(ref, np.float32), np.ascontiguousarray(model, np.float32)
+
+
+def nn_ties(O, ref, model, it, dist_mean_thr, dist_diff_thr):
+    """How many searches of the loop (over the iterations actually run, from the oracle's brute-force trace) find two
+    reference points at exactly the smallest float32 squared distance of a model point."""
+    ref, model = np.ascontiguousarray(ref, np.float32), np.ascontiguousarray(model, np.float32)
+    if len(model) < 3 or len(ref) < 3 or it < 1:
+        return 0
+    r = O.icp(ref, model, it, dist_mean_thr, dist_diff_thr, accum64=False, use_kdtree=False, trace=True)
+    state = O.copy_points(model)
+    ties = 0
+    for row in r["trace"]:
+        if np.isnan(row[0]):                                  # the pass never reached the SVD: the loop had ended
+            break
+        Ropt, Topt = row[11:20], row[20:23]
+        if np.isfinite(Ropt).all() and np.isfinite(Topt).all():
+            state = O.transform_points(state, Ropt, Topt, in_place=True)
+        ties += O.nn_tie_count(ref, state)
+    return ties
+
+
+def check_icp_case(O, case):
+    name, kind, nm, nr, seed, it, a, b = case
+    ref, model = icp_input(case)
+    assert len(ref) == nr and len(model) == nm and nm <= nr, name
+    ties = nn_ties(O, ref, model, it, a, b)
+    assert (ties > 0) if name.startswith("tie_") else (ties == 0), (name, ties)
+    # the cases that are there for one path of the loop take it (the oracle's reading; the comparison decides if it is right)
+    r = O.icp(ref, model, it, a, b, use_kdtree=False)
+    if kind == "far":
+        assert r["iters"] == it and r["n_corr_last"] < 3, (name, r["iters"], r["n_corr_last"])
+    if kind == "identical":
+        assert r["iters"] == 0 and r["dist_mean"] == 0, name
+    if kind == "growing":
+        dm = [O.icp(ref, model, i, *RUN_ALL, use_kdtree=False)["dist_mean"] for i in range(it + 1)]
+        assert 0 < r["iters"] < it and dm[r["iters"]] > dm[r["iters"] - 1], (name, r["iters"], dm)
+    if kind == "all_invalid_ref":
+        assert O.icp(ref, model, 0, a, b)["dist_mean"] == np.float32(FLT_MAX), name
+
+
+def _icp_state(r):
+    return np.concatenate([fbits(r["R"]).ravel(), fbits(r["T"]), fbits([r["dist_mean"], r["px_ratio"]])])
+
+
+def compute_icp(B, case):
+    """The result of every prefix icp_it_thr = 0 .. N (the prefix runs are the per-iteration trace): R, T, dist_mean and
+    px_ratio as bit patterns, and `iter` on exit."""
+    name, kind, nm, nr, seed, it, a, b = case
+    ref, model = icp_input(case)
+    runs = [B.icp(ref, model, i, a, b) for i in range(it + 1)]
+    out = {"states": np.stack([_icp_state(r) for r in runs]), "iters": np.array([r["iters"] for r in runs], np.int32)}
+    return _with_inputs(out, ref, model, np.array([it]), np.array([a, b], np.float32))
+
+
+# ---- the helpers of the loop, one by one -----------------------------------------------------------------------------
+def helper_cases():
+    return [(f"helpers_{kind}_{n}", kind, n, 400 + i) for i, n in enumerate((4, 65, 257, 1025)) for kind in ("clean", "invalid_both", "nan_valid_model")]
+
+
+def compute_helpers(B, case):
+    name, kind, n, seed = case
+    ref, model = icp_input((name, kind, n, n, seed, 0, 0.0, 0.0))
+    R = (synth.rot_z(0.3) @ synth.rot_x(-0.2)).astype(np.float32)
+    T = np.array([3.5, -20.25, 100.125], np.float32)          # lifts some z above 900: they turn invalid
+    out = {"mean_model": fbits(B.get_mean(model)), "mean_ref": fbits(B.get_mean(ref)), "copy": fbits(B.copy_points(model)),
+           "transform_fresh": fbits(B.transform_points(model, R, T, False)), "transform_in_place": fbits(B.transform_points(model, R, T, True))}
+    moved = B.transform_points(B.copy_points(model), R, T, True)
+    for k, thr in (("all", FLT_MAX), ("3", 3.0), ("none", -1.0)):
+        ratio, dm = B.l2dist_clouds(model, ref, thr)
+        out["l2_" + k] = fbits([ratio, dm])
+    out["l2_short_model"] = fbits(B.l2dist_clouds(model[:n // 2], ref))
+    for k, thr in (("all", FLT_MAX), ("9", 9.0), ("none", -1.0)):   # the threshold meets SQUARED distances here
+        cr, cm = B.points_corresponding(ref, model, thr)
+        out["pairs_" + k] = np.concatenate([fbits(cr).ravel(), fbits(cm).ravel()])
+        out["n_pairs_" + k] = np.array([len(cm)], np.int32)
+    return _with_inputs(out, ref, model)
+
+
+# ---- detection() -----------------------------------------------------------------------------------------------------
+DET_W, DET_H = 176, 56                                      # a frame that just holds the largest crop and room to place it
+MODEL_K = (608.0, 608.0, 320.0, 240.0)                      # initInternalMat: the model's intrinsics are fixed
+SCENE_K = (571.3, 569.9, 91.25, 26.5)
+
+
+def _det_surface(rng, dx, dy):
+    yy, xx = np.mgrid[0:DET_H, 0:DET_W].astype(np.float64)
+    z = 600 + 40 * np.sin((xx - dx) / 17.0) + 30 * np.cos((yy - dy) / 9.0) + 0.5 * (xx - dx) + rng.normal(0, 0.6, (DET_H, DET_W))
+    return np.clip(np.rint(z), 1, 65535).astype(np.uint16)
+
+
+def detection_cases():
+    """(name, seed, rect_model, rect_ref, K, holes, icp_it_thr, dist_mean_thr, dist_diff_thr, rotated)."""
+    out = []
+    crops = [(63, 3), (64, 4), (65, 5), (130, 41), (64, 41), (65, 3), (130, 4), (63, 5)]
+    for i, (cw, ch) in enumerate(crops):
+        rm = (3 + i, 2 + i % 3, cw, ch)
+        rr = (DET_W - cw, DET_H - ch, cw, ch) if i % 2 == 0 else (7 + 2 * i, 1 + i % 4, cw, ch)   # even: flush right and bottom
+        K = SCENE_K if i % 3 else MODEL_K
+        thr = (8, *RUN_ALL) if i % 2 == 0 else (10, 0.5, 0.01)
+        out.append((f"det_{cw}x{ch}", 500 + i, rm, rr, K, "some", *thr, i % 2 == 1))
+    out.append(("det_model_flush_130x41", 520, (DET_W - 130, DET_H - 41, 130, 41), (0, 0, 130, 41), SCENE_K, "some", 8, *RUN_ALL, True))
+    out.append(("det_no_holes_65x5", 521, (10, 10, 65, 5), (20, 30, 65, 5), MODEL_K, "none", 8, *RUN_ALL, False))
+    out.append(("det_two_valid_pairs_64x4", 522, (5, 5, 64, 4), (30, 40, 64, 4), SCENE_K, "all_but_2", 8, *RUN_ALL, True))
+    out.append(("det_no_valid_pair_63x3", 523, (5, 5, 63, 3), (30, 40, 63, 3), SCENE_K, "all", 8, *RUN_ALL, True))
+    out.append(("det_refused_rect_leaves_frame", 524, (DET_W - 64, 5, 65, 5), (30, 40, 65, 5), SCENE_K, "some", 8, *RUN_ALL, False))
+    return out
+
+
+def detection_input(case):
+    """(model_depth, scene_depth, r_match, t_match): u16 frames in mm with holes (0) and pixels beyond 900 mm."""
+    name, seed, rm, rr, K, holes, it, a, b, rotated = case
+    rng = np.random.default_rng(seed)
+    model = _det_surface(rng, 0.0, 0.0)
+    scene = _det_surface(rng, rr[0] - rm[0] + 1.5, rr[1] - rm[1] - 0.5)     # the crops see nearly the same piece of surface
+    if holes == "some":
+        for img in (model, scene):
+            img[rng.random(img.shape) < 0.04] = 0
+            img[rng.random(img.shape) < 0.03] = rng.integers(901, 3000)
+            img[rng.random(img.shape) < 0.01] = 900               # float(900) * float(1/1000.0) * 1000 = 900.00006: beyond the bound
+    elif holes in ("all", "all_but_2"):
+        keep = [(1, 2), (2, 40)] if holes == "all_but_2" else []
+        crop = scene[rr[1]:rr[1] + rr[3], rr[0]:rr[0] + rr[2]]
+        saved = [crop[y, x] for y, x in keep]
+        crop[:] = 0
+        crop[::2, ::3] = 2000
+        for (y, x), v in zip(keep, saved):
+            crop[y, x] = v
+    r_match = (synth.rot_z(0.4) @ synth.rot_y(-0.3) @ synth.rot_x(0.2)).astype(np.float32) if rotated else np.eye(3, dtype=np.float32)
+    t_match = np.array([12.5, -7.25, 640.0], np.float32) if rotated else np.array([1.0, 2.0, 3.0], np.float32)
+    return model, scene, r_match, t_match
+
+
+def detection_clouds(O, case):
+    """The two clouds detection() hands to icpCloudToCloud_Ex, from the oracle's pieces (for check_detection_case only)."""
+    name, seed, rm, rr, K, *_ = case
+    model, scene, _, _ = detection_input(case)
+    with np.errstate(invalid="ignore"):
+        p_ref = (O.depth_to_3d(scene, *K) * np.float32(1000))[rr[1]:rr[1] + rr[3], rr[0]:rr[0] + rr[2]].reshape(-1, 3)
+        p_mod = (O.depth_to_3d(model, *MODEL_K) * np.float32(1000))[rm[1]:rm[1] + rm[3], rm[0]:rm[0] + rm[2]].reshape(-1, 3)
+        ok = (p_ref[:, 2] <= 900) & (p_mod[:, 2] <= 900)
+    p_ref, p_mod = np.ascontiguousarray(p_ref[ok]), np.ascontiguousarray(p_mod[ok])
+    if len(p_ref):
+        p_mod = O.transform_points(p_mod, np.eye(3, dtype=np.float32), O.get_mean(p_ref) - O.get_mean(p_mod), True)
+    return p_ref, p_mod
+
+
+def check_detection_case(O, case):
+    name, seed, rm, rr, K, holes, it, a, b, rotated = case
+    assert rm[2:] == rr[2:], name                              # one crop size: matToVec walks both crops with one loop
+    inside = all(0 <= r[0] and 0 <= r[1] and r[0] + r[2] <= DET_W and r[1] + r[3] <= DET_H for r in (rm, rr))
+    assert inside != name.startswith("det_refused"), name
+    if not inside:
+        return
+    p_ref, p_mod = detection_clouds(O, case)
+    model, scene, r_match, t_match = detection_input(case)
+    assert O.detection(model, scene, K, rm, rr, it, a, b, r_match, t_match)["n_points"] == len(p_ref), name
+    assert (len(p_ref) < 3) == (holes in ("all", "all_but_2")), (name, len(p_ref))
+    assert nn_ties(O, p_ref, p_mod, it, a, b) == 0, name
+
+
+def compute_detection(B, case):
+    name, seed, rm, rr, K, holes, it, a, b, rotated = case
+    model, scene, r_match, t_match = detection_input(case)
+    out = {}
+    try:
+        r = B.detection(model, scene, K, rm, rr, it, a, b, r_match, t_match)
+        out["pose"] = np.concatenate([fbits(r["R_final"]).ravel(), fbits(r["T_final"]), _icp_state(r["icp"])])
+        out["counts"] = np.array([r["n_points"], r["icp"]["iters"]], np.int32)
+    except AssertionError:                                  # the reference's CV_Assert on the ROI: both sides must refuse
+        out["refused"] = np.ones(1, np.uint8)
+    return _with_inputs(out, model, scene, r_match, t_match, np.array(rm + rr), np.array(K), np.array([it]), np.array([a, b], np.float32))
+
+
+# ---- cup_d2pc::depthTo3d ---------------------------------------------------------------------------------------------
+def depth3d_cases():
+    """(name, w, h, K, seed)."""
+    return [(f"d3d_{w}x{h}_{'K' if k else 'Kint'}", w, h, (SCENE_K if k else MODEL_K), 600 + 10 * i + j)
+            for i, w in enumerate((63, 64, 65, 130)) for j, h in enumerate((3, 4, 5)) for k in (0, 1) if k == (i + j) % 2 or (w, h) == (65, 5)]
+
+
+def depth3d_input(case):
+    _, w, h, K, seed = case
+    rng = np.random.default_rng(seed)
+    d = rng.integers(0, 65536, (h, w)).astype(np.uint16)
+    d[rng.random((h, w)) < 0.2] = 0
+    d.ravel()[[0, 1, 2, w - 1, w * h - 1]] = (0, 1, 65535, 65535, 1)
+    return d
+
+
+def compute_depth3d(B, case):
+    d = depth3d_input(case)
+    return _with_inputs({"points": fbits(B.depth_to_3d(d, *case[3]))}, d, np.array(case[3]))
+
+
+# ---- nonMaximumSuppression -------------------------------------------------------------------------------------------
+def nms_cases():
+    """(name, t [n, 3], n_points [n], icp_dist [n], th_obj_dist).  Translations are small integers, so that every distance
+    is exact in whatever order cv::norm forms it."""
+    f = np.float32
+    five_t = [(0, 0, 600), (30, 40, 600), (0, 0, 651), (300, 0, 600), (330, 40, 600)]          # |t1-t0| = 50, |t2-t0| = 51, |t4-t3| = 50
+    out = [("nms_none", np.zeros((0, 3), f), [], [], 60.0), ("nms_one", [(1, 2, 3)], [100], [0.5], 60.0)]
+    out.append(("nms_five_both_sides_of_50", five_t, [100, 100, 100, 100, 100], [0.9, 0.5, 0.1, 0.4, 0.6], 50.5))
+    out.append(("nms_five_at_the_distance", five_t, [100, 100, 100, 100, 100], [0.9, 0.5, 0.1, 0.4, 0.6], 50.0))   # `<`: 50 is not near
+    out.append(("nms_five_all_near", five_t, [100, 100, 100, 100, 100], [0.9, 0.5, 0.1, 0.4, 0.6], 1000.0))
+    # the 0.85 rule: more than int(float(n) * 0.85) points, 85 of 100 and 17 of 21 (17.85 truncates); `>` decides
+    out.append(("nms_size_rule_100", [(0, 0, 600)] * 4, [100, 85, 86, 84], [0.9, 0.1, 0.5, 0.05], 10.0))
+    out.append(("nms_size_rule_21", [(0, 0, 600)] * 4, [21, 17, 18, 16], [0.9, 0.1, 0.5, 0.05], 10.0))
+    out.append(("nms_equal_icp_dist", [(0, 0, 600), (1, 0, 600), (0, 1, 600)], [50, 50, 50], [0.5, 0.5, 0.25], 10.0))
+    # the winner so far decides who is near, its opener's size decides the 0.85 rule
+    out.append(("nms_winner_moves", [(0, 0, 600), (40, 0, 600), (80, 0, 600), (120, 0, 600)], [100, 90, 50, 99], [0.9, 0.5, 0.1, 0.2], 45.0))
+    return [(n, np.asarray(t, f).reshape(-1, 3), np.asarray(p, np.int32), np.asarray(d, f), th) for n, t, p, d, th in out]
+
+
+def check_nms_case(case):
+    name, t, npts, dist, th = case
+    assert np.array_equal(t, np.rint(t)) and np.abs(t).max(initial=0) < 4096, name   # sums of squares exact in float32 and in double
+
+
+def compute_nms(B, case):
+    name, t, npts, dist, th = case
+    return _with_inputs({"winners": np.array(B.nms(t, npts, dist, th), np.int32)}, t, npts, dist, np.array([th], np.float32))
+
+
+def recorded(out):
+    """What tests/golden/reference_icp.npz keeps of one case's outputs, as one uint8 array: per key in sorted order the array
+    itself while it is small (poses, counts, winners) or its digest beyond 256 elements (clouds, pair lists), behind a table
+    of their byte lengths.  One array per case keeps the file small: the container's cost is per member."""
+    parts = []
+    for k in sorted(out):
+        v = np.ascontiguousarray(out[k])
+        parts.append((v if v.size <= 256 else digest(v)).tobytes())
+    table = np.array([len(parts)] + [len(p) for p in parts], np.uint32).tobytes()
+    return np.frombuffer(table + b"".join(parts), np.uint8).copy()
+
+
+def same_as_record(out, rec, group, name):
+    """The outputs of one case against the record; returns the first key that differs, or None."""
+    a, b = recorded(out), rec[f"{group}/{name}"]
+    if a.tobytes() == b.tobytes():
+        return None
+    n = int(b[:4].view(np.uint32)[0])
+    if n != len(out):
+        return f"{len(out)} outputs, {n} recorded"
+    lens = b[4:4 + 4 * n].view(np.uint32)
+    pos = 4 + 4 * n
+    for k, ln in zip(sorted(out), lens):
+        v = np.ascontiguousarray(out[k])
+        if (v if v.size <= 256 else digest(v)).tobytes() != b[pos:pos + int(ln)].tobytes():
+            return k
+        pos += int(ln)
+    return "layout"
+
+
+class OracleIcpBackend:
+    """oracle_py in the reference's float32 arithmetic (accum64 = False), on its kd-tree or its brute-force search."""
+
+    def __init__(self, O, use_kdtree):
+        self.O, self.kd = O, use_kdtree
+        for k in ("get_mean", "l2dist_clouds", "copy_points", "transform_points", "depth_to_3d", "nms"):
+            setattr(self, k, getattr(O, k))
+
+    def icp(self, ref, model, it, a, b):
+        return self.O.icp(ref, model, it, a, b, accum64=False, use_kdtree=self.kd)
+
+    def points_corresponding(self, ref, model, thr):
+        return self.O.points_corresponding(ref, model, thr, use_kdtree=self.kd)
+
+    def detection(self, model, scene, K, rm, rr, it, a, b, r_match, t_match):
+        r = self.O.detection(model, scene, K, rm, rr, it, a, b, r_match, t_match, accum64=False, use_kdtree=self.kd)
+        if r["rc"]:
+            raise AssertionError("reference CV_Assert")
+        return r
+
+
+class ReferenceIcpBackend:
+    """The compiled ICP sources of the reference (reference_py.RefIcp)."""
+
+    def __init__(self, R):
+        for k in ("icp", "get_mean", "l2dist_clouds", "copy_points", "transform_points", "points_corresponding", "depth_to_3d", "nms"):
+            setattr(self, k, getattr(R, k))
+        self.R = R
+
+    def detection(self, *args):
+        r = self.R.detection(*args)
+        if r["rc"]:
+            raise AssertionError("reference CV_Assert")
+        return r
+
+
+def icp_groups():
+    """group -> (list of (name, case), compute): the case list of the ICP half, in one place."""
+    return {
+        "icp": ([(c[0], c) for c in icp_cases()], compute_icp),
+        "helpers": ([(c[0], c) for c in helper_cases()], compute_helpers),
+        "detection": ([(c[0], c) for c in detection_cases()], compute_detection),
+        "depth3d": ([(c[0], c) for c in depth3d_cases()], compute_depth3d),
+        "nms": ([(c[0], c) for c in nms_cases()], compute_nms),
+    }

@@ -1,5 +1,6 @@
-"""ctypes binding of oracle/_ref/libfealess_ref{,_simd}.so -- the reference's own linemod.cpp, compiled against the
-container-only opencv2/ stand-in of oracle/ref/ (the twin of tests/oracle_py.py, entry point for entry point).
+"""ctypes binding of oracle/_ref/libfealess_ref{,_simd}.so -- the reference's own linemod.cpp -- and of
+oracle/_ref/libfealess_ref_icp.so -- its ICP sources (ICP.cpp, common.cpp, depth_to_3d.cpp, detection.cpp, NMS.cpp) --, both compiled
+against the container-only opencv2/ stand-in of oracle/ref/ (the twin of tests/oracle_py.py, entry point for entry point).
 
 TEST INFRASTRUCTURE.  The libraries are built by `make -C oracle/ref` (which __graft_entry__.build() runs when a reference
 tree is there) and never committed; a machine without the reference tree receives them ready built or does without.
@@ -9,7 +10,7 @@ import os
 
 import numpy as np
 
-from oracle_py import FEAT_DTYPE, MATCH_DTYPE, TEMPL_DTYPE, OrcBank, _banks, _p
+from oracle_py import FEAT_DTYPE, MATCH_DTYPE, TEMPL_DTYPE, OrcBank, OrcDetectionResult, OrcIcpResult, _banks, _cloud, _icp_dict, _p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
@@ -136,6 +137,89 @@ class Ref:
             raise AssertionError("reference CV_Assert")
 
 
+ICP_LIB_PATH = os.path.join(REF_DIR, "libfealess_ref_icp.so")
+
+
+class RefIcp:
+    """The loaded build of the reference's ICP sources, under the names and result layouts of oracle_py."""
+
+    def __init__(self):
+        self.l = C.CDLL(ICP_LIB_PATH)
+        self.l.ref_l2dist_clouds.restype = C.c_float
+
+    def icp(self, ref, model, icp_it_thr=4, dist_mean_thr=0.0, dist_diff_thr=0.0):
+        """As oracle_py.icp; n_corr_last is not observable in the reference (-1)."""
+        ref, model = _cloud(ref), _cloud(model)
+        res = OrcIcpResult()
+        rc = self.l.ref_icp(_p(ref), len(ref), _p(model), len(model), icp_it_thr, C.c_float(dist_mean_thr), C.c_float(dist_diff_thr),
+                            C.byref(res))
+        d = _icp_dict(res)
+        d["rc"] = rc
+        return d
+
+    def get_mean(self, pts):
+        pts = _cloud(pts)
+        out = np.zeros(3, np.float32)
+        self.l.ref_get_mean(_p(pts), len(pts), _p(out))
+        return out
+
+    def l2dist_clouds(self, model, ref, dist_thr=np.finfo(np.float32).max):
+        model, ref = _cloud(model), _cloud(ref)
+        assert len(ref) >= len(model)
+        dm = C.c_float(0)
+        ratio = self.l.ref_l2dist_clouds(_p(model), len(model), _p(ref), len(ref), C.c_float(dist_thr), C.byref(dm))
+        return np.float32(ratio), np.float32(dm.value)
+
+    def copy_points(self, src):
+        src = _cloud(src)
+        out = np.full_like(src, 7.0)
+        self.l.ref_copy_points(_p(src), len(src), _p(out))
+        return out
+
+    def transform_points(self, src, R, T, in_place):
+        src = _cloud(src)
+        out = np.full_like(src, 7.0)
+        R, T = np.ascontiguousarray(R, np.float32), np.ascontiguousarray(T, np.float32)
+        self.l.ref_transform_points(_p(src), len(src), _p(R), _p(T), _p(out), int(in_place))
+        return out
+
+    def points_corresponding(self, ref, model, dist_thr, use_kdtree=True):
+        ref, model = _cloud(ref), _cloud(model)
+        cr, cm = np.zeros_like(model), np.zeros_like(model)
+        n = self.l.ref_points_corresponding(_p(ref), len(ref), _p(model), len(model), C.c_float(dist_thr), _p(cr), _p(cm))
+        return cr[:n].copy(), cm[:n].copy()
+
+    def depth_to_3d(self, depth, fx, fy, cx, cy):
+        d = np.ascontiguousarray(depth, np.uint16)
+        out = np.zeros(d.shape + (3,), np.float32)
+        if self.l.ref_depth_to_3d(_p(d), d.shape[1], d.shape[0], C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), _p(out)):
+            raise AssertionError("reference CV_Assert")
+        return out
+
+    def detection(self, model_depth_mm, scene_depth_mm, K, rect_model, rect_ref, icp_it_thr, dist_mean_thr, dist_diff_thr, r_match, t_match):
+        md = np.ascontiguousarray(model_depth_mm, np.uint16)
+        sd = np.ascontiguousarray(scene_depth_mm, np.uint16)
+        h, w = sd.shape
+        rm = (C.c_int * 4)(*[int(v) for v in rect_model])
+        rr = (C.c_int * 4)(*[int(v) for v in rect_ref])
+        rmat = (C.c_float * 9)(*np.asarray(r_match, np.float32).ravel())
+        tvec = (C.c_float * 3)(*np.asarray(t_match, np.float32).ravel())
+        res = OrcDetectionResult()
+        rc = self.l.ref_detection(_p(md), _p(sd), w, h, C.c_double(K[0]), C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]), rm, rr,
+                                  icp_it_thr, C.c_float(dist_mean_thr), C.c_float(dist_diff_thr), rmat, tvec, C.byref(res))
+        return dict(rc=rc, R_final=np.array(res.R_final, np.float32).reshape(3, 3), T_final=np.array(res.T_final, np.float32),
+                    icp=_icp_dict(res.icp), n_points=int(res.n_points))
+
+    def nms(self, t, n_points, icp_dist, th_obj_dist):
+        n = len(n_points)
+        t = np.ascontiguousarray(np.asarray(t, np.float32).reshape(-1, 3))
+        npts = np.ascontiguousarray(n_points, np.int32)
+        dist = np.ascontiguousarray(icp_dist, np.float32)
+        win = np.zeros(max(1, n), np.int32)
+        nw = self.l.ref_nms(_p(t), _p(npts), _p(dist), n, C.c_float(th_obj_dist), _p(win))
+        return [int(v) for v in win[:nw]]
+
+
 _libs = {}
 
 
@@ -146,14 +230,30 @@ def lib(simd=False):
     return _libs[simd]
 
 
+def icp_lib():
+    """The loaded build of the ICP sources; OSError when it is not built."""
+    if "icp" not in _libs:
+        _libs["icp"] = RefIcp()
+    return _libs["icp"]
+
+
+def _require(path, load):
+    import pytest
+    if os.path.exists(path):
+        return load()
+    if not reference_present():
+        pytest.skip(f"{os.path.relpath(path, ROOT)} is not built and there is no reference tree at "
+                    f"{reference_root()} to build it from")
+    pytest.fail(f"{os.path.relpath(path, ROOT)} is missing although the reference tree is at {reference_root()}: "
+                "build first (python -c 'import __graft_entry__ as g; g.build()' or make -C oracle/ref)")
+
+
 def require(simd=False):
     """lib(simd) for a test.  A missing library means: skip where there is no reference tree to build it from, fail where
     there is one (the build was forgotten)."""
-    import pytest
-    if os.path.exists(lib_path(simd)):
-        return lib(simd)
-    if not reference_present():
-        pytest.skip(f"{os.path.relpath(lib_path(simd), ROOT)} is not built and there is no reference tree at "
-                    f"{reference_root()} to build it from")
-    pytest.fail(f"{os.path.relpath(lib_path(simd), ROOT)} is missing although the reference tree is at {reference_root()}: "
-                "build first (python -c 'import __graft_entry__ as g; g.build()' or make -C oracle/ref)")
+    return _require(lib_path(simd), lambda: lib(simd))
+
+
+def require_icp():
+    """icp_lib() for a test, with require()'s meaning of a missing library."""
+    return _require(ICP_LIB_PATH, icp_lib)

@@ -13,27 +13,11 @@ from fealess_amd import api, synth
 from fealess_amd import _lib as L
 
 import util
+from reference_cases import object_clouds as _clouds     # the paired object clouds, shared with the reference case list
 
 pytestmark = pytest.mark.gpu
 
 POSE_TOL = 1e-4          # north_star: "within 1e-4 on ICP's final 4x4 pose"
-
-
-def _clouds(seed, n=6000, noise=0.3):
-    """A paired cloud: reference = points on the synthetic object, model = rigidly perturbed copy."""
-    rng = np.random.default_rng(seed)
-    R, t = synth.object_pose(tz=650.0)
-    depth, _, mask = synth.render(640, 480, R, t, seed=seed, noise=True, background=False)
-    ys, xs = np.nonzero(mask)
-    sel = rng.choice(len(ys), size=min(n, len(ys)), replace=False)
-    sel.sort()
-    z = depth[ys[sel], xs[sel]].astype(np.float32)
-    ref = np.stack([(xs[sel] - 320.0) / 608.0 * z, (ys[sel] - 240.0) / 608.0 * z, z], 1).astype(np.float32)
-    dR = synth.rot_z(0.02) @ synth.rot_x(-0.015) @ synth.rot_y(0.01)
-    c = ref.mean(0)
-    model = ((ref - c) @ dR.T + c + np.array([1.5, -2.0, 1.0])).astype(np.float32)
-    model += rng.normal(0, noise, model.shape).astype(np.float32)
-    return ref, model
 
 
 def _bits(a):

@@ -2,17 +2,27 @@
 linemod.cpp (tests/golden/reference_linemod.npz; always run) and against the compiled reference live (oracle/_ref/, which
 travels with the tree; tests/reference_py.require decides what its absence means), on seeded cases placed on the kernels'
 dispatch edges as fl_linemod.hip states them.  Neither part reads a reference source tree.
+
+The ICP half the same way (tests/golden/reference_icp.npz and oracle/_ref/libfealess_ref_icp.so, the reference's compiled ICP.cpp,
+common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp): FL_ICP_PARITY under every build of the ICP kernels that test_gpu_icp.py's
+`width` fixture selects, on cloud sizes on the wave and workgroup strides of those builds; ctx.detection, ctx.depth_to_3d and
+fl_nms.  Every comparison is equality of bit patterns or of ints.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import reference_cases as RC
 import reference_py as R
+from fealess_amd import _lib as L
 from fealess_amd import api, synth
+from test_gpu_icp import width  # noqa: F401  (the fixture that forces each build of the ICP kernels in turn)
 from util import golden
 
 pytestmark = pytest.mark.gpu
 GROUPS = RC.groups()
+ICP_GROUPS = RC.icp_groups()
 
 
 def _detector(ctx, case):
@@ -158,3 +168,76 @@ def test_sort_unique_equals_live_reference_above_20000(ctx):
     got, n = det.match_quantized(qs, 75.0, cap=1 << 20)
     assert n == len(exp) and RC.matches_equal(got, exp)
     det.close()
+
+
+# ---- the ICP half --------------------------------------------------------------------------------------------------------
+class KernelIcpBackend:
+    """The HIP entry points under the method names of reference_cases.ReferenceIcpBackend, in FL_ICP_PARITY."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.depth_to_3d = ctx.depth_to_3d
+
+    def icp(self, ref, model, it, a, b):
+        return self.ctx.icp_cloud_to_cloud_ex(ref, model, it, a, b, L.FL_ICP_PARITY)
+
+    def detection(self, model, scene, K, rm, rr, it, a, b, r_match, t_match):
+        try:
+            return self.ctx.detection(model, scene, K, rm, rr, it, a, b, r_match, t_match, L.FL_ICP_PARITY)
+        except api.FealessError as e:
+            assert e.code == -3                             # FL_ERR_ASSERT: the reference's CV_Assert on the ROI
+            raise AssertionError("reference CV_Assert")
+
+    def nms(self, t, n_points, icp_dist, th_obj_dist):
+        n = len(n_points)
+        objs = (L.RecognitionResult * max(1, n))()
+        for i in range(n):
+            objs[i].det.T_final[:] = [float(v) for v in t[i]]
+            objs[i].det.n_points = int(n_points[i])
+            objs[i].det.icp.dist_mean = float(icp_dist[i])
+        win = (C.c_int * max(1, n))()
+        nw = C.c_int(0)
+        self.ctx.check(self.ctx.lib.fl_nms(objs, n, th_obj_dist, win, C.byref(nw)))
+        return [int(win[i]) for i in range(nw.value)]
+
+
+def _icp_case(group, name):
+    cases, fn = ICP_GROUPS[group]
+    return dict(cases)[name], fn
+
+
+def _names(group):
+    return [n for n, _ in ICP_GROUPS[group][0]]
+
+
+@pytest.mark.parametrize("name", _names("icp"))
+def test_icp_parity_equals_recorded_reference(ctx, width, name):
+    """R, T, dist_mean and px_ratio of every prefix icp_it_thr = 0 .. N, and `iter` on exit, under each build."""
+    case, fn = _icp_case("icp", name)
+    diff = RC.same_as_record(fn(KernelIcpBackend(ctx), case), golden("reference_icp.npz"), "icp", name)
+    assert diff is None, (name, width, diff)
+
+
+@pytest.mark.parametrize("name", _names("detection"))
+def test_detection_equals_recorded_reference(ctx, width, name):
+    """R_final, T_final, the ICP result inside, n_points and `iter`; a crop that leaves the frame is refused on both sides."""
+    case, fn = _icp_case("detection", name)
+    diff = RC.same_as_record(fn(KernelIcpBackend(ctx), case), golden("reference_icp.npz"), "detection", name)
+    assert diff is None, (name, width, diff)
+
+
+@pytest.mark.parametrize("group,name", [(g, n) for g in ("depth3d", "nms") for n in _names(g)])
+def test_depth_to_3d_and_nms_equal_recorded_reference(ctx, group, name):
+    case, fn = _icp_case(group, name)
+    diff = RC.same_as_record(fn(KernelIcpBackend(ctx), case), golden("reference_icp.npz"), group, name)
+    assert diff is None, (name, diff)
+
+
+@pytest.mark.parametrize("group", ["icp", "detection", "depth3d", "nms"])
+def test_icp_half_equals_live_reference(ctx, group):
+    """The same cases against the compiled reference itself, under the build the library picks for one job."""
+    ref = RC.ReferenceIcpBackend(R.require_icp())
+    cases, fn = ICP_GROUPS[group]
+    for name, case in cases:
+        diff = RC.same(fn(KernelIcpBackend(ctx), case), fn(ref, case))
+        assert diff is None, (name, diff)

@@ -6,6 +6,13 @@ No case is dropped at run time: what a build cannot take (the SSE2 spread needs 
 the tests are collected, and inputs that would make the reference's behaviour undefined are built so that they cannot.  Quirk
 Q2 (reads past the last grid row of a linear memory) is DEFINED BY THE STAND-IN'S ALLOCATOR, UB IN THE REFERENCE: its cases
 (names starting with q2_) are a group of their own in every list below.
+
+The ICP half the same way: the oracle in the reference's float32 arithmetic (accum64 = False), on its kd-tree and on its
+brute-force search, against the reference's compiled ICP.cpp, common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp
+(oracle/_ref/libfealess_ref_icp.so) and against tests/golden/reference_icp.npz.  Every comparison is equality of bit patterns
+or of ints: R, T, dist_mean and px_ratio of every prefix icp_it_thr = 0 .. N (the prefixes are the per-iteration states), `iter`
+on exit, n_points, the helpers' clouds and pair lists, the back-projected clouds, the NMS winners.  Exact nearest-neighbour ties
+(names starting with tie_) are DEFINED BY THE STAND-IN'S RULE (lowest index), UNSPECIFIED IN FLANN, and a group of their own.
 """
 import numpy as np
 import pytest
@@ -18,6 +25,9 @@ GROUPS = RC.groups()
 LIVE = [pytest.param(simd, g, name, id=f"{'simd' if simd else 'scalar'}-{name}") for simd in (False, True)
         for g, (cases, _) in GROUPS.items() for name, c in cases if not simd or RC.simd_takes(g, c)]
 ALL = [pytest.param(g, name, id=name) for g, (cases, _) in GROUPS.items() for name, _ in cases]
+ICP_GROUPS = RC.icp_groups()
+ICP_ALL = [pytest.param(kd, g, name, id=f"{'kdtree' if kd else 'brute'}-{name}") for kd in (True, False)
+           for g, (cases, _) in ICP_GROUPS.items() for name, _ in cases]
 
 
 def _case(g, name):
@@ -46,6 +56,31 @@ def test_oracle_equals_recorded_reference(oracle, group, name):
             assert RC.matches_equal(v, rec[f"{group}/{name}/{k}/full"]), (name, k)
 
 
+def _icp_case(g, name):
+    cases, fn = ICP_GROUPS[g]
+    return dict(cases)[name], fn
+
+
+@pytest.mark.parametrize("use_kdtree,group,name", ICP_ALL)
+def test_icp_oracle_equals_compiled_reference(oracle, use_kdtree, group, name):
+    case, fn = _icp_case(group, name)
+    ref = RC.ReferenceIcpBackend(R.require_icp())
+    a, b = fn(RC.OracleIcpBackend(oracle, use_kdtree), case), fn(ref, case)
+    assert RC.same(a, b) is None, (name, RC.same(a, b))
+
+
+@pytest.mark.parametrize("use_kdtree,group,name", ICP_ALL)
+def test_icp_oracle_equals_recorded_reference(oracle, use_kdtree, group, name):
+    case, fn = _icp_case(group, name)
+    out = fn(RC.OracleIcpBackend(oracle, use_kdtree), case)
+    assert RC.same_as_record(out, golden("reference_icp.npz"), group, name) is None, (name, RC.same_as_record(out, golden("reference_icp.npz"), group, name))
+
+
+def test_icp_record_holds_exactly_the_case_list():
+    rec = golden("reference_icp.npz")
+    assert sorted(rec.files) == sorted(f"{g}/{name}" for g, (cases, _) in ICP_GROUPS.items() for name, _ in cases)
+
+
 @pytest.mark.parametrize("group", ["spread", "lut", "linearize", "similarity", "local", "total", "match"])
 def test_scalar_and_simd_builds_agree(group):
     """The functions with SSE branches, on every case both builds take."""
@@ -59,8 +94,8 @@ def test_scalar_and_simd_builds_agree(group):
     assert n > 0
 
 
-def test_inputs_keep_the_reference_defined():
-    """The properties of the INPUTS that keep the reference's behaviour defined (and Q2 cases in their own group)."""
+def test_inputs_keep_the_reference_defined(oracle):
+    """The properties of the INPUTS that keep the reference's behaviour defined (and Q2 and tie_ cases in their own groups)."""
     for c in RC.similarity_cases():
         RC.check_similarity_case(c)
     for c in RC.local_cases():
@@ -75,6 +110,18 @@ def test_inputs_keep_the_reference_defined():
         RC.check_crop_case(c)
     for g in ("spread", "linearize"):
         assert any(not RC.simd_takes(g, c) for _, c in GROUPS[g][0]) and any(RC.simd_takes(g, c) for _, c in GROUPS[g][0])
+    # the ICP half: n_model <= n_ref, no exact nearest-neighbour tie at any search the loop performs outside the tie_ group,
+    # crops of one size inside the frame (or the recorded refusal), NMS distances exact in any order of evaluation
+    for c in RC.icp_cases():
+        RC.check_icp_case(oracle, c)
+    assert sum(c[0].startswith("tie_") for c in RC.icp_cases()) >= 2
+    for c in RC.detection_cases():
+        RC.check_detection_case(oracle, c)
+    for c in RC.nms_cases():
+        RC.check_nms_case(c)
+    for c in RC.depth3d_cases():
+        d = RC.depth3d_input(c)
+        assert d.shape == (c[2], c[1]) and {0, 1, 65535} <= set(d.ravel().tolist()), c[0]
 
 
 @pytest.mark.parametrize("simd", [False, True], ids=["scalar", "simd"])
