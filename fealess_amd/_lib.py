@@ -86,6 +86,12 @@ class StageTimes(C.Structure):
                 ("lazy_frontend_ms", C.c_float), ("group_ms", C.c_float)]
 
 
+class DevSelectJob(C.Structure):       # fl_internal.h fl_dev_select_job
+    _fields_ = [("w", C.c_int32), ("total_px", C.c_int32), ("num_features", C.c_int32), ("depth_mode", C.c_int32),
+                ("area", C.c_int32), ("n_cand", C.c_int32), ("raster", C.c_void_p), ("score", C.c_void_p), ("labels", C.c_void_p),
+                ("n_out", C.c_void_p), ("features", C.c_void_p), ("sorted_keys", C.c_void_p)]
+
+
 FL_RENDER_AMBIENT = 0.2    # include/fealess_hip.h: fl_render_views' ambient when no fl_render_params is given
 FL_TRACK_MAX_PASSES = 4    # include/fealess_hip.h: fl_track_params.passes
 FL_TOPK_OVERFLOW = -2      # fl_export_topk_batch: template id of record 0 of a frame whose candidate buffers overflowed
@@ -173,6 +179,7 @@ SIGNATURES = {
 DEV_SIGNATURES = {
     "fl_dev_detector_create_host": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_P)]),
     "fl_dev_group_jobs": (_I, [_P, _P, _I, C.POINTER(InstanceParams), _P, _P, _P, _P, _P]),
+    "fl_dev_extract_select": (_I, [_P, _I, _P]),
     "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
 }

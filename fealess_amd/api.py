@@ -163,6 +163,29 @@ class Context:
         return [None if st[v] != L.FL_OK else (_pyramid_dicts(t[v * J:(v + 1) * J], f), tuple(int(x) for x in bb[4 * v:4 * v + 4]))
                 for v in range(n)]
 
+    def dev_extract_select(self, jobs, fill=-7):
+        """DEVELOPMENT ONLY (fl_dev_extract_select, not part of the C ABI): extraction's sort and scattered selection on
+        candidate lists, all jobs in one call.  jobs: dicts with w, h, num_features, depth_mode, area, raster (int32, in
+        arrival order), score (float32), labels ((h, w) uint8).  Returns per job (n_out, features (64, 3) int32 with
+        `fill` wherever the kernel wrote nothing, sorted keys (uint64, `fill` as uint64 if the job was not sorted))."""
+        n = len(jobs)
+        arr = (L.DevSelectJob * n)()
+        keep = []
+        for k, j in enumerate(jobs):
+            raster = np.ascontiguousarray(j["raster"], np.int32)
+            score = np.ascontiguousarray(j["score"], np.float32)
+            labels = np.ascontiguousarray(j["labels"], np.uint8)
+            assert len(raster) == len(score) and labels.shape == (j["h"], j["w"])
+            n_out = np.full(1, fill, np.int32)
+            feats = np.full((64, 3), fill, np.int32)
+            keys = np.full(max(len(raster), 1), np.int64(fill).astype(np.uint64), np.uint64)
+            keep.append((raster, score, labels, n_out, feats, keys))
+            arr[k] = L.DevSelectJob(j["w"], j["w"] * j["h"], j["num_features"], j["depth_mode"], j["area"], len(raster),
+                                    raster.ctypes.data, score.ctypes.data, labels.ctypes.data, n_out.ctypes.data,
+                                    feats.ctypes.data, keys.ctypes.data)
+        self.check(L.dev(self.lib, "fl_dev_extract_select")(self.h, n, arr))
+        return [(int(k[3][0]), k[4], k[5][:len(k[0])]) for k in keep]
+
     def render_views(self, vertices, triangles, poses13, K, w, h, normals=None, colors=None, light=None, ambient=None,
                      mem=L.FL_MEM_HOST, out=None):
         """fl_render_views: views of a triangle mesh (vertices (n, 3) mm, triangles (m, 3) 0-based) at poses13 (k, 13),

@@ -22,6 +22,7 @@
 // A chunk makes two host round trips whatever its size: the candidate counts (they size the sort) and the results.
 #include "fl_internal.h"
 #include <limits.h>
+#include <string.h>
 #include <algorithm>
 #include <vector>
 
@@ -50,6 +51,13 @@ struct ExtractJob {
 __device__ __forceinline__ int ex_label(int q)           // getLabel (linemod.cpp:15-30); -1 where the reference throws
 {
   return (q != 0 && (q & (q - 1)) == 0 && q < 256) ? (31 - __clz(q)) : -1;
+}
+
+// A candidate's sort key: descending score, then raster order (positive floats order like their bit patterns).  The one
+// expression behind k_color_candidates, k_depth_keys and fl_dev_extract_select.
+__host__ __device__ __forceinline__ unsigned long long ex_pack_key(float score, int raster)
+{
+  return ((unsigned long long)(~__builtin_bit_cast(unsigned, score)) << 32) | (unsigned)raster;
 }
 
 __device__ __forceinline__ int ex_min_rect(const uint8_t *m, int w, int h, int x, int y, int r)   // cv::erode, BORDER_REPLICATE
@@ -96,8 +104,7 @@ __global__ __launch_bounds__(256) void k_color_candidates(const uint8_t *__restr
   const float score = mag[io];
   if (q > 0 && score > thr_sq) {
     const int pos = atomicAdd(&cnt_[(size_t)z * cnt_stride].n_cand, 1);
-    // descending score, then raster order: positive floats order like their bit patterns
-    ((unsigned long long *)(keys_ + vo))[pos] = ((unsigned long long)(~__float_as_uint(score)) << 32) | (unsigned)i;
+    ((unsigned long long *)(keys_ + vo))[pos] = ex_pack_key(score, (int)i);
   }
 }
 
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(256) void k_depth_keys(const uint8_t *__restrict__ 
   for (int k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
     const int i = raster[k];
     const float s = score[k] / (float)cnt->label_counts[ex_label(normal[i])];   // :806-810
-    keys[k] = ((unsigned long long)(~__float_as_uint(s)) << 32) | (unsigned)i;
+    keys[k] = ex_pack_key(s, i);
   }
 }
 
@@ -379,6 +386,28 @@ static void crop_templates(fl_template *t, int n, fl_feature *f, int bb[4])
   bb[0] = min_x; bb[1] = min_y; bb[2] = max_x - min_x; bb[3] = max_y - min_y;
 }
 
+// The launches behind the job list: every job's keys[0 .. n_cand) padded to n_pow2 keys and sorted as its own segment,
+// then the selection.  max_np2: the largest n_pow2 of the nj jobs (0: nothing to sort).
+static int launch_sort_select(fl_context *ctx, const ExtractJob *d_jobs, int nj, int max_np2)
+{
+  const dim3 blk(256);
+  if (max_np2 > 0) {
+    hipLaunchKernelGGL(k_pad_keys, dim3(std::min((max_np2 + 255) / 256, 64), nj), blk, 0, ctx->stream, d_jobs);
+    hipLaunchKernelGGL(k_bitonic_local, dim3(max_np2 / std::min(max_np2, SORT_CHUNK), nj), dim3(SORT_CHUNK / 2), 0, ctx->stream,
+                       d_jobs, 2, SORT_CHUNK);
+    for (int kk = 2 * SORT_CHUNK; kk <= max_np2; kk <<= 1) {
+      for (int j = kk >> 1; j >= SORT_CHUNK; j >>= 1)
+        hipLaunchKernelGGL(k_bitonic_step, dim3(max_np2 / 256, nj), blk, 0, ctx->stream, d_jobs, kk, j);
+      hipLaunchKernelGGL(k_bitonic_local, dim3(max_np2 / SORT_CHUNK, nj), dim3(SORT_CHUNK / 2), 0, ctx->stream, d_jobs,
+                         kk, kk);
+    }
+    FL_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_select_scattered, dim3(nj), dim3(SEL_BS), 0, ctx->stream, d_jobs);
+  FL_HIP(ctx, hipGetLastError());
+  return FL_OK;
+}
+
 // Views [v0, v0 + n) of a batch, n <= FL_EXTRACT_CHUNK_VIEWS: outputs at the batch's indices (feat_begin absolute).
 static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *bgr, const uint16_t *const *depth, const uint8_t *const *mask,
                          int w0, int h0, int levels, int mem, fl_template *templates, fl_feature *features, int32_t *bb, int32_t *status)
@@ -494,20 +523,7 @@ static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *b
   }
   const int nj = n * J;
   FL_HIP(ctx, hipMemcpyAsync(d_jobs, h_jobs, sizeof(ExtractJob) * nj, hipMemcpyHostToDevice, ctx->stream));
-  if (max_np2 > 0) {
-    hipLaunchKernelGGL(k_pad_keys, dim3(std::min((max_np2 + 255) / 256, 64), nj), blk, 0, ctx->stream, (const ExtractJob *)d_jobs);
-    hipLaunchKernelGGL(k_bitonic_local, dim3(max_np2 / std::min(max_np2, SORT_CHUNK), nj), dim3(SORT_CHUNK / 2), 0, ctx->stream,
-                       (const ExtractJob *)d_jobs, 2, SORT_CHUNK);
-    for (int kk = 2 * SORT_CHUNK; kk <= max_np2; kk <<= 1) {
-      for (int j = kk >> 1; j >= SORT_CHUNK; j >>= 1)
-        hipLaunchKernelGGL(k_bitonic_step, dim3(max_np2 / 256, nj), blk, 0, ctx->stream, (const ExtractJob *)d_jobs, kk, j);
-      hipLaunchKernelGGL(k_bitonic_local, dim3(max_np2 / SORT_CHUNK, nj), dim3(SORT_CHUNK / 2), 0, ctx->stream, (const ExtractJob *)d_jobs,
-                         kk, kk);
-    }
-    FL_HIP(ctx, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_select_scattered, dim3(nj), dim3(SEL_BS), 0, ctx->stream, (const ExtractJob *)d_jobs);
-  FL_HIP(ctx, hipGetLastError());
+  if ((rc = launch_sort_select(ctx, d_jobs, nj, max_np2))) return rc;
 
   // host round trip 2: the counters (n_out) and the selected features
   FL_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(ExtractCounters) * nj, hipMemcpyDeviceToHost, ctx->stream));
@@ -562,5 +578,89 @@ extern "C" int fl_extract_template_pyramid(fl_context *ctx, const uint8_t *bgr, 
   if (rc) return rc;
   if (st != FL_OK) return fl_set_error(ctx, FL_ERR_NO_TEMPLATE, "too few candidate features at some pyramid level (addTemplate returns -1)");
   if (bb) { bb[0] = box[0]; bb[1] = box[1]; bb[2] = box[2]; bb[3] = box[3]; }
+  return FL_OK;
+}
+
+// see fl_internal.h
+extern "C" int fl_dev_extract_select(fl_context *ctx, int n_jobs, const fl_dev_select_job *jobs)
+{
+  if (!ctx || n_jobs < 1 || n_jobs > 4096 || !jobs) return FL_ERR_INVALID;
+  for (int k = 0; k < n_jobs; ++k) {
+    const fl_dev_select_job &j = jobs[k];
+    if (!j.labels || !j.n_out || !j.features || !j.sorted_keys || j.n_cand < 0 || j.n_cand > (1 << 24) || (j.n_cand > 0 && (!j.raster || !j.score)))
+      return FL_ERR_INVALID;
+    if (j.num_features < 1 || j.num_features > FL_MAX_FEATURES || j.depth_mode < 0 || j.depth_mode > 2 || j.area < 0) return FL_ERR_INVALID;
+    // the selection packs a candidate's x and y into 16 bits each
+    if (j.w < 1 || j.w > 65536 || j.total_px < j.w || j.total_px % j.w || j.total_px / j.w > 65536) return FL_ERR_INVALID;
+    // A depth job's start distance is fractional and never reaches 0: fewer than num_features distinct pixels would
+    // never finish, in the reference as here.  A colour job's distance reaches 0, where a repeated pixel passes.
+    std::vector<bool> seen(j.depth_mode ? (size_t)j.total_px : 0);
+    for (int c = 0; c < j.n_cand; ++c) {
+      if (j.raster[c] < 0 || j.raster[c] >= j.total_px || !(j.score[c] > 0.0f)) return FL_ERR_INVALID;   // keys order positive scores only
+      if (j.depth_mode) {
+        if (seen[j.raster[c]]) return FL_ERR_INVALID;
+        seen[j.raster[c]] = true;
+      }
+    }
+  }
+  // device, mirrored in pinned host memory: per job keys (next_pow2(n_cand)) | labels, then counters | features | jobs;
+  // device only: per job xy | mind2
+  size_t off = 0;
+  auto take = [&](size_t b) { size_t o = off; off += fl_align(b, 256); return o; };
+  std::vector<size_t> o_keys(n_jobs), o_labels(n_jobs), o_xy(n_jobs), o_mind2(n_jobs);
+  for (int k = 0; k < n_jobs; ++k) {
+    o_keys[k] = take((size_t)next_pow2(std::max(jobs[k].n_cand, 1)) * 8);
+    o_labels[k] = take((size_t)jobs[k].total_px);
+  }
+  const size_t o_cnt = take(sizeof(ExtractCounters) * n_jobs), o_feats = take(sizeof(fl_feature) * 64 * n_jobs),
+               o_jobs = take(sizeof(ExtractJob) * n_jobs), mirrored = off;
+  for (int k = 0; k < n_jobs; ++k) {
+    o_xy[k] = take((size_t)jobs[k].n_cand * 4);
+    o_mind2[k] = take((size_t)jobs[k].n_cand * 4);
+  }
+  void *sv = nullptr, *pv = nullptr;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = fl_scratch(ctx, off, &sv);
+  if (rc) return rc;
+  if ((rc = fl_pinned(ctx, mirrored, &pv))) return rc;
+  uint8_t *s = (uint8_t *)sv, *p = (uint8_t *)pv;
+  ExtractCounters *h_cnt = (ExtractCounters *)(p + o_cnt);
+  fl_feature *h_feats = (fl_feature *)(p + o_feats);
+  ExtractJob *h_jobs = (ExtractJob *)(p + o_jobs);
+  int max_np2 = 0;
+  for (int k = 0; k < n_jobs; ++k) {
+    const fl_dev_select_job &j = jobs[k];
+    unsigned long long *keys = (unsigned long long *)(p + o_keys[k]);
+    for (int c = 0; c < j.n_cand; ++c) keys[c] = ex_pack_key(j.score[c], j.raster[c]);
+    memcpy(p + o_labels[k], j.labels, (size_t)j.total_px);
+    memset(&h_cnt[k], 0, sizeof(ExtractCounters));
+    h_cnt[k].n_cand = j.n_cand;
+    h_cnt[k].area = j.area;
+    memcpy(h_feats + (size_t)64 * k, j.features, sizeof(fl_feature) * 64);   // what the kernel does not write comes back as it went in
+    ExtractJob &jb = h_jobs[k];
+    jb.keys = (unsigned long long *)(s + o_keys[k]);
+    jb.labels = s + o_labels[k];
+    jb.xy = (uint32_t *)(s + o_xy[k]);
+    jb.mind2 = (int *)(s + o_mind2[k]);
+    jb.cnt = (ExtractCounters *)(s + o_cnt) + k;
+    jb.out = (fl_feature *)(s + o_feats) + (size_t)64 * k;
+    jb.w = j.w;
+    jb.num_features = j.num_features;
+    jb.depth_mode = j.depth_mode;
+    jb.total_px = j.total_px;
+    jb.n_pow2 = j.n_cand >= j.num_features ? next_pow2(j.n_cand) : 0;
+    jb.pad = 0;
+    max_np2 = std::max(max_np2, jb.n_pow2);
+  }
+  FL_HIP(ctx, hipMemcpyAsync(s, p, mirrored, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = launch_sort_select(ctx, (const ExtractJob *)(s + o_jobs), n_jobs, max_np2))) return rc;
+  FL_HIP(ctx, hipMemcpyAsync(p, s, o_jobs, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < n_jobs; ++k) {
+    const fl_dev_select_job &j = jobs[k];
+    *j.n_out = h_cnt[k].n_out;
+    memcpy(j.features, h_feats + (size_t)64 * k, sizeof(fl_feature) * 64);
+    if (h_jobs[k].n_pow2 > 0) memcpy(j.sorted_keys, p + o_keys[k], (size_t)j.n_cand * 8);
+  }
   return FL_OK;
 }

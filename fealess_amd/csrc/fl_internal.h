@@ -317,6 +317,26 @@ extern "C" int fl_dev_detector_create_host(int modalities, int levels, const int
 // job_idx[g * h + r], info[4]; every pointer is device memory, queued on the context's stream.
 extern "C" int fl_dev_group_jobs(fl_detector *det, const fl_match *matches, int n, const fl_instance_params *ip, int32_t *group_of,
                                  int32_t *group_size, int32_t *info, void *jobs, int32_t *job_idx);
+// The sort and the selection of template extraction (fl_extract.hip) on caller-supplied candidate lists, all jobs in one
+// call through the launch sequence fl_extract_template_batch uses.  Everything is host memory.  Per job: the candidates as
+// (raster, score > 0) pairs in the order given (the keys are packed in that order), the w x (total_px / w) image the
+// features' labels are read from, num_features 1..63, depth_mode 0 (colour distance) / 1 (depth, total_px) / 2 (depth, area).
+// A job with n_cand >= num_features is sorted and selected, any other is handed to the kernels as a job that cannot yield a
+// template.  Out: n_out (num_features, or -1); features[64], uploaded as given and read back, so that what the kernel
+// does not write returns unchanged; sorted_keys[n_cand], the job's sorted key segment, written only for a job that was sorted.
+// FL_ERR_INVALID with nothing launched or written: null pointers, n_jobs < 1, num_features outside 1..63, n_cand < 0,
+// a raster outside [0, total_px), a score that is not positive, a repeated raster in a depth job (its
+// fractional distance never reaches 0, so too few distinct pixels would never finish), w or total_px / w beyond 65536.
+struct fl_dev_select_job {
+  int32_t w, total_px, num_features, depth_mode, area, n_cand;
+  const int32_t *raster;
+  const float *score;
+  const uint8_t *labels;
+  int32_t *n_out;
+  fl_feature *features;
+  unsigned long long *sorted_keys;
+};
+extern "C" int fl_dev_extract_select(fl_context *ctx, int n_jobs, const fl_dev_select_job *jobs);
 // frontend
 int fl_launch_quantized_orientations(fl_context *ctx, const uint8_t *bgr, size_t in_stride,
                                      uint8_t *dst, size_t out_stride, int n_frames, int w, int h,

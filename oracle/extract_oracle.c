@@ -121,6 +121,20 @@ static void select_scattered(const cand_t *c, int n, int num_features, float dis
   }
 }
 
+/* The sort and the selection alone, on a caller-supplied candidate list in arrival order: std::stable_sort with
+ * Candidate::operator<, then selectScatteredFeatures with the caller's start distance.  returns 1 / 0 (n < num_features) */
+int orc_select_scattered_list(const int *x, const int *y, const int *label, const float *score, int n, int num_features,
+                              float distance, orc_feature *out)
+{
+  if (n < num_features) return 0;
+  cand_t *c = (cand_t *)malloc(sizeof(cand_t) * (size_t)(n > 0 ? n : 1));
+  for (int i = 0; i < n; ++i) { c[i].x = x[i]; c[i].y = y[i]; c[i].label = label[i]; c[i].score = score[i]; c[i].order = i; }
+  qsort(c, (size_t)n, sizeof(cand_t), cmp_cand);
+  select_scattered(c, n, num_features, distance, out);
+  free(c);
+  return 1;
+}
+
 /* ColorGradientPyramid::extractTemplate (:461-513).  quantized = the 3x3-voted one-hot image, magnitude = the
  * squared gradient magnitude (both from quantizedOrientations), mask optional.  returns 1 / 0 (too few candidates) */
 int orc_extract_template_color(const uint8_t *quantized, const float *magnitude, const uint8_t *mask, int w, int h,

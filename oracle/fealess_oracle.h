@@ -118,6 +118,8 @@ int  orc_extract_template_color(const uint8_t *quantized, const float *magnitude
                                 float strong_threshold, int num_features, orc_feature *out);    /* linemod.cpp:461-513 */
 int  orc_extract_template_depth(const uint8_t *normal, const uint8_t *mask, int w, int h, int extract_threshold,
                                 int num_features, orc_feature *out);                            /* linemod.cpp:747-825 */
+int  orc_select_scattered_list(const int *x, const int *y, const int *label, const float *score, int n, int num_features,
+                               float distance, orc_feature *out);                               /* linemod.cpp:135-164 on a list */
 void orc_crop_templates(orc_template *t, int n, orc_feature *feats, int bb[4]);                 /* linemod.cpp:52-96 */
 /* Detector::addTemplate (linemod.cpp:1579-1615), default modalities; templates[levels*2] ordered [l*2+m], feature
  * slot of template k = feats + 63*k; returns 0 / -1 */

@@ -226,6 +226,16 @@ def extract_template_depth(normal, mask, extract_threshold, num_features):
     return out if ok else None
 
 
+def select_scattered_list(x, y, label, score, num_features, distance):
+    """stable sort by Candidate::operator< + selectScatteredFeatures on a candidate list in arrival order; None when the
+    list is shorter than num_features."""
+    x, y, label = (np.ascontiguousarray(a, np.int32) for a in (x, y, label))
+    score = np.ascontiguousarray(score, np.float32)
+    out = np.zeros(num_features, FEAT_DTYPE)
+    ok = lib().orc_select_scattered_list(_p(x), _p(y), _p(label), _p(score), len(x), num_features, C.c_float(distance), _p(out))
+    return out if ok else None
+
+
 def quantized_orientations_mag(bgr, weak_threshold=10.0):
     b = np.ascontiguousarray(bgr, np.uint8)
     out = np.zeros(b.shape[:2], np.uint8)
