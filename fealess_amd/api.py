@@ -186,6 +186,31 @@ class Context:
         self.check(L.dev(self.lib, "fl_dev_extract_select")(self.h, n, arr))
         return [(int(k[3][0]), k[4], k[5][:len(k[0])]) for k in keep]
 
+    def dev_front_images(self, bgrs, depths, levels):
+        """DEVELOPMENT ONLY (fl_dev_front_images, not part of the C ABI): the launches of an eager batch's front-end on frames
+        of any size, also those no detector can be finalized for.  Returns per frame a list over the levels of dicts with the
+        quantised colour image `q0`, the quantised normals `q1` and, from level 1 on, the colour image `bgr`."""
+        n = len(bgrs)
+        b = np.ascontiguousarray(np.stack(bgrs), np.uint8)
+        d = np.ascontiguousarray(np.stack(depths), np.uint16)
+        h, w = d.shape[1:]
+        sizes = [(w >> l, h >> l) for l in range(levels)]
+        per = sum(lw * lh * (5 if l else 2) for l, (lw, lh) in enumerate(sizes))
+        out = np.zeros(n * per, np.uint8)
+        self.check(L.dev(self.lib, "fl_dev_front_images")(self.h, _ptr(b), _ptr(d), n, w, h, levels, _ptr(out), out.nbytes))
+        frames, o = [], 0
+        for _ in range(n):
+            lv = []
+            for l, (lw, lh) in enumerate(sizes):
+                px = lw * lh
+                e = dict(q0=out[o:o + px].reshape(lh, lw), q1=out[o + px:o + 2 * px].reshape(lh, lw))
+                if l:
+                    e["bgr"] = out[o + 2 * px:o + 5 * px].reshape(lh, lw, 3)
+                o += (5 if l else 2) * px
+                lv.append(e)
+            frames.append(lv)
+        return frames
+
     def render_views(self, vertices, triangles, poses13, K, w, h, normals=None, colors=None, light=None, ambient=None,
                      mem=L.FL_MEM_HOST, out=None):
         """fl_render_views: views of a triangle mesh (vertices (n, 3) mm, triangles (m, 3) 0-based) at poses13 (k, 13),

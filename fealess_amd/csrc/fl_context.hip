@@ -97,7 +97,8 @@ int fl_icp_stream(fl_context *ctx, hipStream_t *out)
 
 extern "C" int fl_abi_version(void) { return FL_ABI_VERSION; }
 
-// name, environment variable, field, environment value in hex, accepted values lo .. hi (icp_occ: 0, 4 or 5)
+// name, environment variable, field, environment value in hex, accepted values lo .. hi (icp_occ: 0, 4 or 5;
+// frontend_chunk_rows: multiples of 60)
 struct FlOptionName { const char *name, *env; long fl_context::Options::*field; bool hex; long lo, hi; };
 static const FlOptionName fl_option_names[] = {
   {"scan_prune", "FL_SCAN_PRUNE", &fl_context::Options::scan_prune, false, 0, 1},
@@ -110,6 +111,7 @@ static const FlOptionName fl_option_names[] = {
   {"dev_poison", "FL_DEV_POISON", &fl_context::Options::dev_poison, false, 0, 1},
   {"ws_pad", "FL_DEV_WS_PAD", &fl_context::Options::ws_pad, false, 0, 16l << 20},
   {"pipeline_icp", "FL_PIPELINE_ICP", &fl_context::Options::pipeline_icp, false, 0, 3},
+  {"frontend_chunk_rows", "FL_FRONTEND_CHUNK_ROWS", &fl_context::Options::frontend_chunk_rows, false, 0, 60 * 1024},
 };
 
 // A value outside an option's range is refused rather than taken for "default": a forced kernel variant with a mistyped
@@ -117,6 +119,7 @@ static const FlOptionName fl_option_names[] = {
 static bool fl_option_valid(const FlOptionName &o, long v)
 {
   if (v < o.lo || v > o.hi) return false;
+  if (o.field == &fl_context::Options::frontend_chunk_rows) return v % 60 == 0;
   return o.field != &fl_context::Options::icp_occ || v == 0 || v >= 4;
 }
 

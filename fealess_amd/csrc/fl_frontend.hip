@@ -6,10 +6,13 @@
 //                      16-bin quantise -> 3x3 majority vote, fused in registers (sliding window per
 //                      column, wave shuffles for x+-1): the BGR image is read from HBM once and only
 //                      the one-hot byte image is written.
-//   k_pyrdown_bgr      cv::pyrDown [1 4 6 4 1]^2, (acc+128)>>8, REFLECT_101
+//   k_pyrdown_pairs    cv::pyrDown [1 4 6 4 1]^2, (acc+128)>>8, REFLECT_101, border pairs included (k_pyrdown_general:
+//                      sizes the pair kernel does not take)
 //   k_depth_quantize   bilateral 8-neighbour LSQ normal (int64) + NORMAL_LUT + exact 5x5 median of the
-//                      one-hot codes (replicated border), fused in registers like k_color_quantize
-//   k_resize_nn_half   src(2y, 2x)
+//                      one-hot codes (replicated border), fused in registers like k_color_quantize; at even sizes it
+//                      also writes the half-size image src(2y, 2x) of the next pyramid level
+//   k_resize_nn_half   src(2y, 2x) for the levels after that, and for level 1 at other sizes
+// Both quantisers walk chunks of rows whose height a whole-image launch picks from the batch size (fl_eager_chunk_rows).
 //
 // The integer stages are exact; the float stages restate OpenCV 3.x's arithmetic operator by
 // operator (built with -ffp-contract=off; IEEE divide/sqrt are hipcc's default), so they equal
@@ -55,11 +58,14 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
 
 // ------------------------------------------------------------------------------------------
 // k_color_quantize: one wavefront owns a strip of 64 adjacent image columns (60 outputs plus two
-// halo columns on each side) and walks CQ_CH output rows downwards with the whole filter chain in
+// halo columns on each side) and walks chunk_rows output rows downwards with the whole filter chain in
 // registers: a 7-row ring of horizontal-blur sums per channel, 3-row rings of the smoothed pixel
 // (packed B|G<<8|R<<16) and of the 16-bin code for x-1, x, x+1 -- horizontal neighbours come from
 // wave shuffles, vertical ones from the rings.  No LDS, no barriers; every source byte is fetched
 // once per strip (plus the 4-column / 10-row halo) through two wide loads per row and lane.
+// chunk_rows is CQ_CH for a tiled (lazy) launch, whose chunks are the tile rows; a whole-image launch takes 120-row chunks
+// where the batch still fills the device with them (fl_eager_chunk_rows): every chunk recomputes 10 blur rows, 4 smoothed
+// rows and 2 Sobel rows of halo for its first output row.
 #define CQ_COLS 60
 #define CQ_CH 60
 
@@ -126,7 +132,7 @@ __device__ __forceinline__ void cq_hrow(const uint8_t *__restrict__ src, int w, 
 template <bool kMag>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, FL_CQ_WPE))) void k_color_quantize(const uint8_t *__restrict__ bgr, size_t in_stride,
                                                         uint8_t *__restrict__ dst, size_t out_stride, int w, int h,
-                                                        float threshold_sq, int nstrips, int nchunks,
+                                                        float threshold_sq, int nstrips, int nchunks, int chunk_rows,
                                                         float *__restrict__ mag_out, const uint32_t *__restrict__ tiles,
                                                         size_t tiles_stride)
 {
@@ -149,7 +155,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, 
   // a sample requested outside the image is the sample at the clamped position -- for the blur's own
   // taps and for Sobel's BORDER_REPLICATE on the *smoothed* image alike (linemod.cpp:247-249)
   const int xc = clampi(x, 0, w - 1);
-  const int y0 = max(chunk * CQ_CH, row_lo), y1 = min(min(h, chunk * CQ_CH + CQ_CH), row_hi + 1);
+  const int y0 = max(chunk * chunk_rows, row_lo), y1 = min(min(h, chunk * chunk_rows + chunk_rows), row_hi + 1);
   const bool interior = __all(xc >= 3 && xc <= w - 5);
 
   int H[7][3];
@@ -245,18 +251,44 @@ int fl_launch_quantized_orientations(fl_context *ctx, const uint8_t *bgr, size_t
   return fl_launch_quantized_orientations_mag(ctx, bgr, in_stride, dst, out_stride, n_frames, w, h, weak_threshold, nullptr);
 }
 
+// Chunk height of a whole-image (eager) quantiser launch: 120 rows where the launch then still has FL_CHUNK_FILL times the
+// waves the device holds at once, else 60 (so the small-batch launches are what they were).  Measured at 4096 VGA frames
+// (profiles/README.md): 120 rows beat 60; 240 rows and whole images, which leave the level-1 colour launch 4 and 2 rounds of
+// long waves, were slower again and are not chosen.  Option frontend_chunk_rows != 0 forces a height.
+#define FL_CHUNK_FILL 4
+template <typename K>
+static long waves_per_cu(K kernel, long *cache)
+{
+  if (*cache == 0) {
+    int blocks = 0;
+    *cache = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, 256, 0) == hipSuccess && blocks > 0 ? 4l * blocks : 32;
+  }
+  return *cache;
+}
+static int fl_eager_chunk_rows(const fl_context *ctx, long per_cu, int nstrips, int n_frames, int h)
+{
+  if (ctx->opt.frontend_chunk_rows) return (int)ctx->opt.frontend_chunk_rows;
+  const long need = (long)FL_CHUNK_FILL * ctx->cus * per_cu;
+  return h > 60 && (long)nstrips * n_frames * ((h + 119) / 120) >= need ? 120 : 60;
+}
+
 static_assert(CQ_COLS == FL_TILE && CQ_CH == FL_TILE, "the lazy tile grid is k_color_quantize's work decomposition");
 static int launch_color_quantize(fl_context *ctx, const uint8_t *bgr, size_t in_stride, uint8_t *dst, size_t out_stride, int n_frames,
                                  int w, int h, float weak_threshold, float *mag_out, const uint32_t *tiles, size_t tiles_stride)
 {
-  const int nstrips = (w + CQ_COLS - 1) / CQ_COLS, nchunks = (h + CQ_CH - 1) / CQ_CH;
+  static long per_cu[2] = {0, 0};
+  const int nstrips = (w + CQ_COLS - 1) / CQ_COLS;
+  const int rows = tiles ? CQ_CH
+                         : fl_eager_chunk_rows(ctx, mag_out ? waves_per_cu(k_color_quantize<true>, &per_cu[1]) : waves_per_cu(k_color_quantize<false>, &per_cu[0]),
+                                               nstrips, n_frames, h);
+  const int nchunks = (h + rows - 1) / rows;
   dim3 grid((nstrips * nchunks + 3) / 4, 1, n_frames);
   if (mag_out)
     hipLaunchKernelGGL(k_color_quantize<true>, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h,
-                       weak_threshold * weak_threshold, nstrips, nchunks, mag_out, tiles, tiles_stride);
+                       weak_threshold * weak_threshold, nstrips, nchunks, rows, mag_out, tiles, tiles_stride);
   else
     hipLaunchKernelGGL(k_color_quantize<false>, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h,
-                       weak_threshold * weak_threshold, nstrips, nchunks, mag_out, tiles, tiles_stride);
+                       weak_threshold * weak_threshold, nstrips, nchunks, rows, mag_out, tiles, tiles_stride);
   FL_HIP(ctx, hipGetLastError());
   return FL_OK;
 }
@@ -271,11 +303,14 @@ int fl_launch_quantized_orientations_mag(fl_context *ctx, const uint8_t *bgr, si
 // cv::pyrDown.  The stage is bound by vector-memory instructions, whose cost on gfx950 depends on alignment and lane
 // stride much more than on width (tools/probes/ldwidth.hip: a 16-byte load costs ~30 cycles per wave when 4-byte
 // aligned, ~70 at byte alignment or a 6-byte lane stride; a byte load at stride 5 ~25).  So:
-//   k_pyrdown_pairs   interior: one thread makes TWO adjacent output pixels; their 7 source pixels are 21 bytes
+//   k_pyrdown_pairs   one thread makes TWO adjacent output pixels; their 7 source pixels are 21 bytes
 //                     inside the 4-byte aligned 24-byte window starting at 12 x' - 8 -> one 16-byte + one 8-byte
-//                     aligned load per source row, three 2-byte stores per thread
-//   k_pyrdown_general any pixel, REFLECT_101 taps fetched one by one: the two border pixel pairs of every row
-//                     (second, tiny grid) and whole images that are too small for the pair kernel
+//                     aligned load per source row, three 2-byte stores per thread.  The first and the last pair of a
+//                     row load at shifted, in-range addresses of the same alignment and rebuild their reflected
+//                     window with a few selects (a second launch of one thread per border pixel, 75 byte loads each,
+//                     used to take a third of this kernel's time)
+//   k_pyrdown_general any pixel, REFLECT_101 taps fetched one by one: whole images the pair kernel does not take
+//                     (dw < 8, odd w or dw)
 __device__ __forceinline__ void pyrdown_general_px(const uint8_t *__restrict__ src, int w, int h, int x, int y, uint8_t *o)
 {
   const int k[5] = {1, 4, 6, 4, 1};
@@ -301,23 +336,12 @@ __device__ __forceinline__ void pyrdown_general_px(const uint8_t *__restrict__ s
   o[2] = (uint8_t)((acc2 + 128) >> 8);
 }
 
-// border_only = 0: every pixel; 1: the pixels of the first and of the last pair of each row (x in {0, 1, dw-2, dw-1})
 __global__ __launch_bounds__(256) void k_pyrdown_general(const uint8_t *__restrict__ src_, size_t in_stride,
-                                                         uint8_t *__restrict__ dst_, size_t out_stride, int w, int h, int border_only)
+                                                         uint8_t *__restrict__ dst_, size_t out_stride, int w, int h)
 {
   const int dw = w / 2, dh = h / 2;
-  int x, y;
-  if (border_only) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    y = t >> 2;
-    const int c = t & 3;
-    x = c < 2 ? c : dw - 4 + c;
-    if (y >= dh) return;
-  } else {
-    x = blockIdx.x * 32 + (threadIdx.x & 31);
-    y = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= dw || y >= dh) return;
-  }
+  const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (x >= dw || y >= dh) return;
   const uint8_t *src = src_ + (size_t)blockIdx.z * in_stride;
   uint8_t *dst = dst_ + (size_t)blockIdx.z * out_stride;
   pyrdown_general_px(src, w, h, x, y, dst + ((size_t)y * dw + x) * 3);
@@ -332,20 +356,45 @@ __global__ __launch_bounds__(256) void k_pyrdown_general(const uint8_t *__restri
 __global__ __launch_bounds__(256) void k_pyrdown_pairs(const uint8_t *__restrict__ src_, size_t in_stride,
                                                        uint8_t *__restrict__ dst_, size_t out_stride, int w, int h)
 {
-  const int dw = w / 2, dh = h / 2;
-  const int xp = blockIdx.x * 64 + (threadIdx.x & 63) + 1;                    // pair index >= 1
+  const int dw = w / 2, dh = h / 2, np = dw / 2;          // np pairs per output row, dealt evenly over the row's waves
+  const int per = (np + (int)gridDim.x - 1) / (int)gridDim.x, lane = threadIdx.x & 63;
+  const int xp = blockIdx.x * per + lane;
   const int y0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * PD_ROWS;
-  if (xp > dw / 2 - 2 || y0 >= dh) return;                // the last pair (and an odd last pixel) belong to the border grid
+  if (lane >= per || xp >= np || y0 >= dh) return;
   const uint8_t *src = src_ + (size_t)blockIdx.z * in_stride;
   uint8_t *dst = dst_ + (size_t)blockIdx.z * out_stride;
+  // The first and the last pair of a row (w is even here) have taps outside the row.  They load in-range bytes instead and
+  // rebuild the REFLECT_101 window in registers, in the waves that hold them (wave-uniform tests), with selects:
+  //   first: source pixels -2, -1 are pixels 2, 1.  Row bytes 0..15 go to window bytes 8..23, bytes 2..7 are put together
+  //          from pixels 2 and 1 (row bytes 6..8 and 3..5).
+  //   last:  source pixel w is pixel w - 2, i.e. window bytes 20..22 repeat bytes 14..16; the 8-byte load would end 4 bytes
+  //          past the row, so it starts 4 bytes earlier and only its upper half is used.
+  const bool first = xp == 0, last = xp == np - 1;
+  const bool wave_first = blockIdx.x == 0, wave_last = blockIdx.x == gridDim.x - 1;
+  const int off16 = first ? 0 : 12 * xp - 8, off8 = first ? 16 : (last ? 12 * xp + 4 : 12 * xp + 8);
   // horizontal [1 4 6 4 1] sums of one source row for this lane's two output pixels (taps 0..4 and 2..6 of the seven source
   // pixels 4 xp - 2 .. 4 xp + 4; bytes 12 xp - 8 .. 12 xp + 15 hold them from byte 2 on)
   auto hrow = [&](int r, int (&o)[6]) {
     const int yy = reflect101(r, h);
     uint32_t wd[6];
-    const uint8_t *p = src + (size_t)yy * w * 3 + 12 * xp - 8;
-    __builtin_memcpy(wd, p, 16);
-    __builtin_memcpy(wd + 4, p + 16, 8);
+    const uint8_t *p = src + (size_t)yy * w * 3;
+    __builtin_memcpy(wd, p + off16, 16);
+    __builtin_memcpy(wd + 4, p + off8, 8);
+    if (wave_first) {
+      const uint32_t mix = (wd[2] & 0xFFu) | ((wd[0] >> 24) << 8) | (wd[1] << 16);
+      const uint32_t n0 = wd[1], n2 = wd[0], n3 = wd[1], n4 = wd[2], n5 = wd[3];
+      wd[0] = first ? n0 : wd[0];
+      wd[1] = first ? mix : wd[1];
+      wd[2] = first ? n2 : wd[2];
+      wd[3] = first ? n3 : wd[3];
+      wd[4] = first ? n4 : wd[4];
+      wd[5] = first ? n5 : wd[5];
+    }
+    if (wave_last) {
+      const uint32_t hi = wd[5];
+      wd[4] = last ? hi : wd[4];
+      wd[5] = last ? ((wd[3] >> 16) | (hi << 16)) : wd[5];
+    }
 #define SB(b) ((int)((wd[(b) >> 2] >> (8 * ((b) & 3))) & 0xFFu))
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -384,16 +433,15 @@ int fl_launch_pyrdown_bgr(fl_context *ctx, const uint8_t *src, size_t in_stride,
                           int n_frames, int w, int h)
 {
   const int dw = w / 2, dh = h / 2;
-  // the pair kernel stores 16-bit words: rows and frames of the output must start at even addresses
-  const bool pairs_ok = dw >= 8 && (dw & 1) == 0 && ((3 * dw) & 1) == 0 && (out_stride & 1) == 0 && (((size_t)dst) & 1) == 0;
+  // the pair kernel stores 16-bit words: rows and frames of the output must start at even addresses; its last pair
+  // reflects at an even w (an odd w has one more source column: the general kernel)
+  const bool pairs_ok = dw >= 8 && (w & 1) == 0 && (dw & 1) == 0 && ((3 * dw) & 1) == 0 && (out_stride & 1) == 0 && (((size_t)dst) & 1) == 0;
   if (!pairs_ok) {
     dim3 grid((dw + 31) / 32, (dh + 7) / 8, n_frames);
-    hipLaunchKernelGGL(k_pyrdown_general, grid, dim3(256), 0, ctx->stream, src, in_stride, dst, out_stride, w, h, 0);
+    hipLaunchKernelGGL(k_pyrdown_general, grid, dim3(256), 0, ctx->stream, src, in_stride, dst, out_stride, w, h);
   } else {
-    dim3 grid((dw / 2 - 2 + 63) / 64, (dh + 4 * PD_ROWS - 1) / (4 * PD_ROWS), n_frames);             // pairs 1 .. dw/2 - 2
+    dim3 grid((dw / 2 + 63) / 64, (dh + 4 * PD_ROWS - 1) / (4 * PD_ROWS), n_frames);
     hipLaunchKernelGGL(k_pyrdown_pairs, grid, dim3(256), 0, ctx->stream, src, in_stride, dst, out_stride, w, h);
-    dim3 gridb((4 * dh + 255) / 256, 1, n_frames);
-    hipLaunchKernelGGL(k_pyrdown_general, gridb, dim3(256), 0, ctx->stream, src, in_stride, dst, out_stride, w, h, 1);
   }
   FL_HIP(ctx, hipGetLastError());
   return FL_OK;
@@ -435,7 +483,8 @@ static int ensure_normal_lut(fl_context *ctx)
 //
 // k_depth_quantize: quantizedNormals (linemod.cpp:595-683) fused with the medianBlur(5) that ends
 // it (:684).  Same execution shape as k_color_quantize: a wavefront owns 64 adjacent columns (60
-// outputs + 2 halo columns per side), walks DQ_CH output rows and keeps the last five rows in registers.
+// outputs + 2 halo columns per side), walks chunk_rows output rows (fl_eager_chunk_rows: the first output row of a chunk
+// costs four more rows of normals) and keeps the last five rows in registers.
 // The codes are 0 or one-hot, i.e. 9 classes ordered like their byte values, and the exact 5x5 median is
 // the first class whose CUMULATIVE count reaches 13.  A pixel of class c therefore contributes the
 // pattern "1 in every 4-bit field i >= c" (fields 0..7; class 8's own field would always hold 25 and is
@@ -443,8 +492,10 @@ static int ensure_normal_lut(fl_context *ctx)
 // whole-wave DPP shifts, 3 + 2 columns are added in 4-bit fields (<= 15, <= 10), and the ">= 13" test runs on
 // the even / odd fields widened to bytes (sum + 115 sets bit 7).  The flags are monotone in the class, so
 // median class = 8 - popcount.  The un-medianed normal image never exists in memory.
+// dst1 (null: none) is the next pyramid level's image, cv::resize INTER_NEAREST to half size, for even w and h: the lane
+// that stores pixel (yo, x) with both even stores the same byte to dst1(yo / 2, x / 2) -- a separate pass would read the
+// whole level-0 image back for it.
 #define DQ_COLS 60
-#define DQ_CH 60
 
 __device__ __forceinline__ unsigned dq_pattern(unsigned cls) { return cls >= 8u ? 0u : 0x11111111u << (4u * cls); }
 
@@ -511,7 +562,8 @@ __device__ __forceinline__ unsigned dq_normal_pattern(const uint16_t *__restrict
 __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restrict__ depth_, size_t in_stride,
                                                         uint8_t *__restrict__ dst_, size_t out_stride, int w, int h,
                                                         int distance_threshold, int difference_threshold, int nstrips,
-                                                        int nchunks)
+                                                        int nchunks, int chunk_rows, uint8_t *__restrict__ dst1_,
+                                                        size_t out1_stride)
 {
   __shared__ uint8_t s_lut[400];                           // NORMAL_LUT's 20x20 face: a per-lane lookup every row
   for (int k = threadIdx.x; k < 400; k += 256) s_lut[k] = c_normal_lut[k];
@@ -522,9 +574,10 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restri
   const int strip = item % nstrips, chunk = item / nstrips;
   const uint16_t *depth = depth_ + (size_t)blockIdx.z * in_stride;
   uint8_t *dst = dst_ + (size_t)blockIdx.z * out_stride;
+  uint8_t *dst1 = dst1_ ? dst1_ + (size_t)blockIdx.z * out1_stride : nullptr;
   const int x = strip * DQ_COLS + lane - 2;
   const int xc = clampi(x, 0, w - 1);                      // medianBlur replicates the border
-  const int y0 = chunk * DQ_CH, y1 = min(h, y0 + DQ_CH);
+  const int y0 = chunk * chunk_rows, y1 = min(h, y0 + chunk_rows);
   unsigned p0 = 0, p1 = 0, p2 = 0, p3 = 0, p4 = 0;         // cumulative-count patterns of the last five rows, p0 newest
   int center = -1;
   unsigned pat = 0;
@@ -543,22 +596,28 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restri
     const unsigned to = ((s3 >> 4) & 0x0F0F0F0Fu) + ((s2 >> 4) & 0x0F0F0F0Fu) + 0x73737373u;
     const int idx = 8 - __popc((te & 0x80808080u) | ((to & 0x80808080u) >> 1));
     const int yo = yv - 2;
-    if (lane >= 2 && lane < 2 + DQ_COLS && x < w) dst[__umul24((unsigned)yo, (unsigned)w) + (unsigned)x] = idx ? (uint8_t)(1u << (idx - 1)) : 0;
+    if (lane >= 2 && lane < 2 + DQ_COLS && x < w) {
+      const uint8_t v = idx ? (uint8_t)(1u << (idx - 1)) : 0;
+      dst[__umul24((unsigned)yo, (unsigned)w) + (unsigned)x] = v;
+      if (dst1 && !((yo | x) & 1)) dst1[__umul24((unsigned)yo >> 1, (unsigned)w >> 1) + ((unsigned)x >> 1)] = v;
+    }
   }
 }
 
 int fl_launch_quantized_normals(fl_context *ctx, const uint16_t *depth, size_t in_stride, uint8_t *dst,
-                                size_t out_stride, uint8_t *tmp, size_t tmp_stride, int n_frames, int w, int h,
+                                size_t out_stride, uint8_t *dst1, size_t out1_stride, int n_frames, int w, int h,
                                 int distance_threshold, int difference_threshold)
 {
+  static long per_cu = 0;
   int rc = ensure_normal_lut(ctx);
   if (rc) return rc;
-  (void)tmp;
-  (void)tmp_stride;
-  const int nstrips = (w + DQ_COLS - 1) / DQ_COLS, nchunks = (h + DQ_CH - 1) / DQ_CH;
+  if (dst1 && ((w | h) & 1)) return fl_set_error(ctx, FL_ERR_INVALID, "fused half-size normals need even sizes, got %dx%d", w, h);
+  const int nstrips = (w + DQ_COLS - 1) / DQ_COLS;
+  const int rows = fl_eager_chunk_rows(ctx, waves_per_cu(k_depth_quantize, &per_cu), nstrips, n_frames, h);
+  const int nchunks = (h + rows - 1) / rows;
   dim3 grid((nstrips * nchunks + 3) / 4, 1, n_frames);
   hipLaunchKernelGGL(k_depth_quantize, grid, dim3(256), 0, ctx->stream, depth, in_stride / sizeof(uint16_t), dst, out_stride,
-                     w, h, distance_threshold, difference_threshold, nstrips, nchunks);
+                     w, h, distance_threshold, difference_threshold, nstrips, nchunks, rows, dst1, out1_stride);
   FL_HIP(ctx, hipGetLastError());
   return FL_OK;
 }
@@ -594,12 +653,16 @@ __global__ __launch_bounds__(256) void k_resize_nn_half(const uint8_t *__restric
   dst[(size_t)y * dw + x] = src[(size_t)sy * w + sx];
 }
 
+// even sizes: 1 / ((w/2) / w) == 2 exactly, so the source pixel is (2y, 2x); w % 8 == 0 keeps the 8-byte loads aligned
+static bool resize_nn_half_fast(const uint8_t *src, size_t in_stride, const uint8_t *dst, size_t out_stride, int w, int h)
+{
+  return (w % 8) == 0 && (h % 2) == 0 && ((in_stride | out_stride) & 7) == 0 && ((((size_t)src) | ((size_t)dst)) & 7) == 0;
+}
+
 int fl_launch_resize_nn_half(fl_context *ctx, const uint8_t *src, size_t in_stride, uint8_t *dst, size_t out_stride,
                              int n_frames, int w, int h)
 {
-  // even sizes: 1 / ((w/2) / w) == 2 exactly, so the source pixel is (2y, 2x); w % 8 == 0 keeps the 8-byte loads aligned
-  const bool fast = (w % 8) == 0 && (h % 2) == 0 && ((in_stride | out_stride) & 7) == 0 && ((((size_t)src) | ((size_t)dst)) & 7) == 0;
-  if (fast) {
+  if (resize_nn_half_fast(src, in_stride, dst, out_stride, w, h)) {
     dim3 grid((w / 8 + 63) / 64, (h / 2 + 3) / 4, n_frames);
     hipLaunchKernelGGL(k_resize_nn_half4, grid, dim3(256), 0, ctx->stream, src, in_stride, dst, out_stride, w, h);
   } else {
@@ -611,43 +674,124 @@ int fl_launch_resize_nn_half(fl_context *ctx, const uint8_t *src, size_t in_stri
 }
 
 // ------------------------------------------------------------------------------------------
-// Modality::process + pyrDown + quantize for every level (linemod.cpp:1369-1416) of n_frames frames
-// resident in the detector workspace.  Default modality parameters (linemod.cpp:515-519, 827-832).
+// Modality::process + pyrDown + quantize for every level (linemod.cpp:1369-1416) of n_frames frames.  Default modality
+// parameters (linemod.cpp:515-519, 827-832).  The images of level l are frame-strided arrays: the colour image (level 0: the
+// input), the quantised colour image and, with a depth modality, the quantised normals.  Level 1's normals come out of the
+// depth quantiser itself where the half-size rule is src(2y, 2x) (the sizes resize_nn_half_fast takes); deeper levels and other
+// sizes take k_resize_nn_half*.  first_color_level: colour levels below it are left to the lazy path.
+struct FlFrontImages {
+  int L, M;
+  int w[FL_MAX_LEVELS], h[FL_MAX_LEVELS];
+  uint8_t *bgr[FL_MAX_LEVELS], *qcolor[FL_MAX_LEVELS], *qdepth[FL_MAX_LEVELS];
+  size_t stride;
+};
+static int launch_front_images(fl_context *ctx, const FlFrontImages &im, int n_frames, const uint8_t *bgr, size_t bgr_stride,
+                               const uint16_t *depth, size_t depth_stride, int first_color_level)
+{
+  int rc;
+  bool fused1 = false;
+  for (int l = 0; l < im.L; ++l) {
+    if (l > 0) {
+      rc = fl_launch_pyrdown_bgr(ctx, l == 1 ? bgr : im.bgr[l - 1], l == 1 ? bgr_stride : im.stride, im.bgr[l], im.stride, n_frames,
+                                 im.w[l - 1], im.h[l - 1]);
+      if (rc) return rc;
+      if (im.M > 1 && !(l == 1 && fused1)) {
+        rc = fl_launch_resize_nn_half(ctx, im.qdepth[l - 1], im.stride, im.qdepth[l], im.stride, n_frames, im.w[l - 1], im.h[l - 1]);
+        if (rc) return rc;
+      }
+    } else if (im.M > 1) {
+      fused1 = im.L > 1 && resize_nn_half_fast(im.qdepth[0], im.stride, im.qdepth[1], im.stride, im.w[0], im.h[0]);
+      rc = fl_launch_quantized_normals(ctx, depth, depth_stride, im.qdepth[0], im.stride, fused1 ? im.qdepth[1] : nullptr, im.stride,
+                                       n_frames, im.w[0], im.h[0], 2000, 50);
+      if (rc) return rc;
+    }
+    if (l < first_color_level) continue;
+    rc = fl_launch_quantized_orientations(ctx, l == 0 ? bgr : im.bgr[l], l == 0 ? bgr_stride : im.stride, im.qcolor[l], im.stride,
+                                          n_frames, im.w[l], im.h[l], 10.0f);
+    if (rc) return rc;
+  }
+  return FL_OK;
+}
+
 int fl_launch_frontend(fl_detector *det, int n_frames, const uint8_t *bgr, size_t bgr_stride, const uint16_t *depth,
                        size_t depth_stride, bool allow_lazy)
 {
   fl_context *ctx = det->ctx;
-  int rc;
   // Lazy fine levels: everything that feeds the coarsest level (colour pyramid, depth quantisation and its NN
   // pyramid, the coarsest colour quantisation) runs here; the colour quantisation of the finer levels waits for the
   // scan's candidates (fl_launch_lazy_level).
   det->lazy = allow_lazy && det->lazy_capable && !det->eager_env;
   det->lazy_bgr = bgr;
   det->lazy_bgr_stride = bgr_stride;
+  FlFrontImages im;
+  im.L = det->L;
+  im.M = det->M;
+  im.stride = det->ws_stride;
   for (int l = 0; l < det->L; ++l) {
     const FlLevelGeom &g = det->geom[l];
-    if (l > 0) {
-      const FlLevelGeom &p = det->geom[l - 1];
-      rc = fl_launch_pyrdown_bgr(ctx, l == 1 ? bgr : det->d_ws + p.bgr_off, l == 1 ? bgr_stride : det->ws_stride,
-                                 det->d_ws + g.bgr_off, det->ws_stride, n_frames, p.w, p.h);
-      if (rc) return rc;
-      if (det->M > 1) {
-        rc = fl_launch_resize_nn_half(ctx, det->d_ws + p.quant_off[1], det->ws_stride, det->d_ws + g.quant_off[1],
-                                      det->ws_stride, n_frames, p.w, p.h);
-        if (rc) return rc;
-      }
-    } else if (det->M > 1) {
-      rc = fl_launch_quantized_normals(ctx, depth, depth_stride,
-                                       det->d_ws + g.quant_off[1], det->ws_stride, det->d_ws + det->off_tmp,
-                                       det->ws_stride, n_frames, g.w, g.h, 2000, 50);
-      if (rc) return rc;
-    }
-    if (det->lazy && l < det->L - 1) continue;
-    rc = fl_launch_quantized_orientations(ctx, l == 0 ? bgr : det->d_ws + g.bgr_off, l == 0 ? bgr_stride : det->ws_stride,
-                                          det->d_ws + g.quant_off[0], det->ws_stride, n_frames, g.w, g.h, 10.0f);
-    if (rc) return rc;
+    im.w[l] = g.w;
+    im.h[l] = g.h;
+    im.bgr[l] = det->d_ws + g.bgr_off;
+    im.qcolor[l] = det->d_ws + g.quant_off[0];
+    im.qdepth[l] = det->d_ws + g.quant_off[1];
   }
+  int rc = launch_front_images(ctx, im, n_frames, bgr, bgr_stride, depth, depth_stride, det->lazy ? det->L - 1 : 0);
+  if (rc) return rc;
   if (det->have_times) FL_HIP(ctx, hipEventRecord(det->ev[1], ctx->stream));
+  return FL_OK;
+}
+
+// Development / test aid (not part of the ABI): launch_front_images -- the launches fl_launch_frontend queues for an eager
+// batch with both modalities -- on n_frames host frames of ANY size, also those no detector can be finalized for (LINEMOD's
+// own asserts on T and rows * cols do not concern the front-end).  out: per frame, level after level, the quantised colour
+// image, the quantised normals and (level >= 1) the colour image, (5 or 2) * w_l * h_l bytes per level with w_l = w >> l.
+extern "C" int fl_dev_front_images(fl_context *ctx, const uint8_t *bgr, const uint16_t *depth, int n_frames, int w, int h, int levels,
+                                   uint8_t *out, size_t out_bytes)
+{
+  if (!ctx || !bgr || !depth || !out || n_frames < 1 || levels < 1 || levels > FL_MAX_LEVELS || w < 3 || h < 3 || (w >> (levels - 1)) < 3 ||
+      (h >> (levels - 1)) < 3)
+    return FL_ERR_INVALID;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  FlFrontImages im;
+  im.L = levels;
+  im.M = 2;
+  size_t off = 0;
+  for (int l = 0; l < levels; ++l) {
+    im.w[l] = w >> l;
+    im.h[l] = h >> l;
+    const size_t px = (size_t)im.w[l] * im.h[l];
+    im.qcolor[l] = (uint8_t *)off;
+    im.qdepth[l] = (uint8_t *)(off + fl_align(px, 256));
+    im.bgr[l] = (uint8_t *)(off + 2 * fl_align(px, 256));
+    off += 2 * fl_align(px, 256) + (l ? fl_align(3 * px, 256) : 0);
+  }
+  const size_t packed = off, fb = (size_t)w * h * 3, fd = (size_t)w * h * 2, in_b = fl_align(fb * n_frames, 256);
+  size_t need = 0;
+  for (int l = 0; l < levels; ++l) need += (size_t)im.w[l] * im.h[l] * (l ? 5 : 2);
+  if (out_bytes < need * n_frames) return fl_set_error(ctx, FL_ERR_INVALID, "fl_dev_front_images: out holds %zu bytes, %zu needed", out_bytes, need * n_frames);
+  void *s = nullptr;
+  int rc = fl_scratch(ctx, in_b + fl_align(fd * n_frames, 256) + packed * n_frames, &s);
+  if (rc) return rc;
+  uint8_t *d_bgr = (uint8_t *)s, *d_depth = d_bgr + in_b, *d_im = d_depth + fl_align(fd * n_frames, 256);
+  im.stride = packed;
+  for (int l = 0; l < levels; ++l) {
+    im.qcolor[l] = d_im + (size_t)im.qcolor[l];
+    im.qdepth[l] = d_im + (size_t)im.qdepth[l];
+    im.bgr[l] = d_im + (size_t)im.bgr[l];
+  }
+  FL_HIP(ctx, hipMemcpyAsync(d_bgr, bgr, fb * n_frames, hipMemcpyHostToDevice, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(d_depth, depth, fd * n_frames, hipMemcpyHostToDevice, ctx->stream));
+  FL_HIP(ctx, hipMemsetAsync(d_im, 0xFF, packed * n_frames, ctx->stream));      // never a quantised byte: an unwritten pixel shows
+  if ((rc = launch_front_images(ctx, im, n_frames, d_bgr, fb, (const uint16_t *)d_depth, fd, 0))) return rc;
+  for (int f = 0; f < n_frames; ++f)
+    for (int l = 0; l < levels; ++l) {
+      const size_t px = (size_t)im.w[l] * im.h[l];
+      FL_HIP(ctx, hipMemcpyAsync(out, im.qcolor[l] + f * packed, px, hipMemcpyDeviceToHost, ctx->stream));
+      FL_HIP(ctx, hipMemcpyAsync(out + px, im.qdepth[l] + f * packed, px, hipMemcpyDeviceToHost, ctx->stream));
+      if (l) FL_HIP(ctx, hipMemcpyAsync(out + 2 * px, im.bgr[l] + f * packed, 3 * px, hipMemcpyDeviceToHost, ctx->stream));
+      out += (l ? 5 : 2) * px;
+    }
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return FL_OK;
 }
 
@@ -721,8 +865,8 @@ extern "C" int fl_quantized_normals(fl_context *ctx, const uint16_t *depth, int 
 {
   if (!ctx || !depth || !dst || w <= 0 || h <= 0) return FL_ERR_INVALID;
   return run_stage(ctx, depth, (size_t)w * h * 2, dst, (size_t)w * h, (size_t)w * h, mem,
-                   [&](const uint8_t *i, uint8_t *o, uint8_t *t) {
-                     return fl_launch_quantized_normals(ctx, (const uint16_t *)i, 0, o, 0, t, 0, 1, w, h,
+                   [&](const uint8_t *i, uint8_t *o, uint8_t *) {
+                     return fl_launch_quantized_normals(ctx, (const uint16_t *)i, 0, o, 0, nullptr, 0, 1, w, h,
                                                         distance_threshold, difference_threshold);
                    });
 }

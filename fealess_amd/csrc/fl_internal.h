@@ -44,6 +44,8 @@ struct fl_context {
                                 // second stream beside the next batch's LINEMOD stages; 2 / 3 = the same with that stream at the
                                 // highest / lowest priority the device offers (3 measured best: the short LINEMOD kernels get the
                                 // slots the long ICP launch frees, profiles/README.md)
+    long frontend_chunk_rows = 0;   // FL_FRONTEND_CHUNK_ROWS: output rows a wave of the whole-image quantiser launches walks; 0 = 120 where
+                                // the launch still fills the device several times over, else 60; a multiple of 60 is used as given
   } opt;
   int detectors = 0;            // live fl_detector objects on this context
   bool destroy_pending = false; // fl_context_destroy was called while detectors were alive: the last one releases the context
@@ -341,8 +343,9 @@ extern "C" int fl_dev_extract_select(fl_context *ctx, int n_jobs, const fl_dev_s
 int fl_launch_quantized_orientations(fl_context *ctx, const uint8_t *bgr, size_t in_stride,
                                      uint8_t *dst, size_t out_stride, int n_frames, int w, int h,
                                      float weak_threshold);
+// dst1 (null: none): the half-size NN image of the normals, written by the same kernel (even w and h only)
 int fl_launch_quantized_normals(fl_context *ctx, const uint16_t *depth, size_t in_stride,
-                                uint8_t *dst, size_t out_stride, uint8_t *tmp, size_t tmp_stride,
+                                uint8_t *dst, size_t out_stride, uint8_t *dst1, size_t out1_stride,
                                 int n_frames, int w, int h, int distance_threshold,
                                 int difference_threshold);
 int fl_launch_pyrdown_bgr(fl_context *ctx, const uint8_t *src, size_t in_stride, uint8_t *dst,
