@@ -23,21 +23,10 @@
 // chain producers get 4x the lanes, the next iteration's search runs underneath the dist_mean chain ("Search ahead of the
 // distance chain" in icp_run), and a frame's latency drops to about what its two sequential chains cost.
 //
-// Nearest neighbours: the reference's FLANN kd-tree (exact 1-NN, eps 0) is replaced by a uniform
-// x/y cell grid over the static reference cloud built once per frame; a query only visits the
-// cells within sqrt(3*dist_mean) because farther neighbours are discarded anyway
-// (PointsCorresponding keeps d^2 <= 3*dist_mean, ICP.cpp:268,708).  Distances use L2_Simple's
-// float expression ((dx*dx + dy*dy) + dz*dz); ties go to the lowest index.
-//
-// Organised search (the recognition / detection() pipeline, where both clouds are back-projected crops).  The grid, its
-// CSR headers and their gathers are not needed there: the reference cloud is kept as an IMAGE (crop pixel -> 12-byte point,
-// a point at infinity where the pixel was dropped; a point is named by its pixel), and the reference points within distance r of a query
-// q can only come from the pixels its ball projects to -- u in [fx (qx -+ r) / (qz +- r)], likewise v -- a window of a
-// few pixels.  Queries are taken in 16x4-pixel tile order (a permutation built once per frame), so the 64 queries of a
-// wave share a compact union window; the wave stages that window into its share of the (idle) chain tiles in LDS with a
-// handful of coalesced loads and every lane enumerates its own window from LDS.  When the union does not fit (the first
-// iterations, where sqrt(3 dist_mean) is several pixels) the same enumeration reads the image from L2 instead.
-// fl_icp() (caller-supplied clouds, no image structure) keeps the grid search.
+// Where things are.  This file: workspace and LDS layout, the float32 chains (chain_tile, chain_deferred), l2dist_phase, the pose solvers,
+// icp_run (the algorithm: A1 search, A2 sums, solve, distances), crop_clouds / build_tile_order, the kernels, the host entries and, in one
+// block at the end, the dev / test entries.  fl_icp_search.h (included here only): what the searches are made of -- loads, bnd[], the grid
+// and its search, the reference image, wave reductions, windows -- and the organised searches org_search / org_search_pipe themselves.
 // Built with -ffp-contract=off: one IEEE binary32/64 operation per operator.
 #include "fl_internal.h"
 #include <float.h>
@@ -59,13 +48,29 @@
 #define CH_STAMP(v) { const long long now_ = clock64(); v += now_ - c_last; c_last = now_; }
 #define CH_STAMP_END(k) { if (threadIdx.x == 0) { S.hist[k] += (unsigned)(c_add >> 4); S.hist[(k) + 1] += (unsigned)(c_bar >> 4); } }
 #define PR_STAMP_BARRIER(k, every) { const long long b0_ = clock64(); tile_barrier(); if (threadIdx.x == 64) S.hist[k] += (unsigned)(((clock64() - b0_) * (every)) >> 4); }
+// search step: cycles of a wave's step segments, summed into S.stime[k] when the search ends; ST_ARRIVED: the two values are in
+// their registers (the stamp that follows includes the wait for them)
+#define ST_STAMP_BEGIN long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_last = clock64()
+#define ST_STAMP(k) { const long long now_ = clock64(); st_acc[k] += now_ - st_last; st_last = now_; }
+#define ST_ARRIVED(a, b) asm volatile("" :: "v"(a), "v"(b));
+#define ST_STAMP_END { if ((threadIdx.x & 63) == 0) for (int k = 0; k < 5; ++k) atomicAdd(&S.stime[k], (unsigned long long)st_acc[k]); }
 #else
 #define TSTAMP(k) do { } while (0)
 #define CH_STAMP_BEGIN
 #define CH_STAMP(v) { }
 #define CH_STAMP_END(k) { }
 #define PR_STAMP_BARRIER(k, every) tile_barrier()
+#define ST_STAMP_BEGIN
+#define ST_STAMP(k) { }
+#define ST_ARRIVED(a, b)
+#define ST_STAMP_END
 #endif
+// the barrier between the tiles of a chain phase: this wave's LDS writes complete, then a raw s_barrier (why: phase A2 in icp_run)
+__device__ __forceinline__ void tile_barrier()
+{
+  __builtin_amdgcn_s_waitcnt(0xC07F);                      // s_waitcnt lgkmcnt(0)
+  __builtin_amdgcn_s_barrier();
+}
 #define ICP_PARITY_WPE 4          // waves per SIMD the default 256-thread recognition kernel is compiled for (4 -> 128 VGPRs, 5 -> 96; a
                                   // second instance for 5 is always built, see k_icp_pipeline).  ICP us per frame, one box: mid-round
                                   // 5 @ 1280 frames 11.65, 4 @ 2048 10.4 (the 96-VGPR build spilled in the search loop); after the scan
@@ -245,6 +250,8 @@ __device__ __forceinline__ int cvt_i32_sat(float f)
   asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(f));
   return r;
 }
+
+#include "fl_icp_search.h"
 
 // ---- block-level helpers (every thread of the workgroup must call) ---------------------------
 template <class SH>
@@ -546,487 +553,11 @@ __device__ __forceinline__ float chain_deferred(const float *__restrict__ dterm,
     float *dst = buf[b & 1];
     *(float4 *)(dst + 4 * lane) = c0;
     *(float4 *)(dst + 256 + 4 * lane) = c1;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handover();
     if (lane == 0) acc = chain_tile<NBUF>(dst, cnt, acc);
     acc = uniform_f(acc);
   }
   return acc;                                            // every lane holds the sum
-}
-
-// uniform base + 32-bit unsigned byte offset: one VGPR per address (global_load ... v_off, s[base]) instead of a
-// sign-extended 64-bit pointer pair -- the search keeps 24 addresses in flight
-template <typename T>
-__device__ __forceinline__ T ld_u32(const T *__restrict__ base, int idx)
-{
-  return *(const T *)((const char *)base + (size_t)((unsigned)idx * (unsigned)sizeof(T)));
-}
-
-// one 12-byte load (global_load_dwordx3) for a point instead of three dword loads: the phases are bound by the
-// number of vector-memory instructions as much as by anything else
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 ld3_u32(const float *__restrict__ base, int i)
-{
-  F3 v;
-  unsigned i3;                                           // 12 i as (2 i + i) << 2: the compiler folds the C form back into a quarter-rate v_mul_lo_u32
-  asm("v_lshl_add_u32 %0, %1, 1, %1" : "=v"(i3) : "v"(i));
-  __builtin_memcpy(&v, (const char *)base + (size_t)(i3 << 2), 12);
-  return v;
-}
-
-// bnd[] is only ever an UPPER bound (a wider search radius visits more pixels, the neighbour found is the same), so it is kept
-// as the top 16 bits of its float32 pattern, rounded UP: 8 of the ~155 bytes the kernel moves per point and iteration.
-// Saturating: a finite value rounds up to at most +inf (0x7F80), and ANY NaN payload is stored as the canonical 0x7FC0 -- "no
-// bound" -- instead of carrying into the exponent or the sign (0x7FFFxxxx + 0xFFFF would wrap to 0x8000 = a bound of -0).
-// bnd values are non-negative by construction (distances and sums of distances).
-typedef uint16_t bnd_t;
-// (three instructions: every pattern at or above the canonical NaN -- the negative ones included -- is clamped to it first;
-// the NaNs below it round up to a NaN no larger than it; FLT_MAX rounds up to +inf)
-__host__ __device__ __forceinline__ uint16_t bnd_pack(unsigned bits)
-{
-  return (uint16_t)(((bits < 0x7FC00000u ? bits : 0x7FC00000u) + 0xFFFFu) >> 16);
-}
-extern "C" unsigned fl_dev_bnd_pack(unsigned bits) { return bnd_pack(bits); }      // for tests/test_abi_cpu.py (host arithmetic, no GPU)
-__device__ __forceinline__ float bnd_ld(const bnd_t *__restrict__ b, int i) { return __uint_as_float((unsigned)ld_u32(b, i) << 16); }
-__device__ __forceinline__ void bnd_st(bnd_t *b, int i, float v) { b[i] = bnd_pack(__float_as_uint(v)); }
-
-// An UPPER bound of sqrt(x) for the search-radius bookkeeping (bnd[]): the hardware's 1-ulp v_sqrt_f32 inflated past
-// its error (and past a flushed denormal) instead of the ~15-instruction correctly rounded sqrtf.  Any over-estimate
-// only widens the visited area; the nearest neighbour found is the same.
-__device__ __forceinline__ float sqrt_upper(float x) { return __builtin_amdgcn_sqrtf(x) * 1.000001f + 1.1e-19f; }
-
-// A searchable reference point is a float4 (index bits, X, Y, Z): the index comes FIRST so that the 64-bit key
-// (index low, d2 high) can be formed in the two registers the load put the index and X into -- X is dead once dx is
-// computed -- without a register move per candidate.
-__device__ __forceinline__ float4 nn_point(float x, float y, float z, int index) { return make_float4(__int_as_float(index), x, y, z); }
-__device__ __forceinline__ int nn_point_index(const float4 &p) { return __float_as_int(p.x); }
-#define NN_OVERRUN 3                // readable points behind the last position of a staged window / of the reference image
-#define NN_IDX_NONE 0x7fffffff      // index stored with a dropped pixel of the reference image (real indices are below it)
-
-// ---- uniform x/y grid over the reference cloud --------------------------------------------------
-__device__ __forceinline__ int cell_of(float v, float vmin, float inv_c, int G)
-{
-  float t = floorf((v - vmin) * inv_c);
-  int c = t < 0.f ? 0 : (t > (float)(G - 1) ? G - 1 : (int)t);
-  return c;
-}
-
-template <class SH>
-__device__ __forceinline__ void build_grid(SH &S, const float *ref, int n_ref, float4 *sref, int *cell_start, int *cell_cur,
-                           int ncell_max)
-{
-  constexpr int BS = SH::BS, NW = SH::NW;
-  // bounding box of the finite points
-  float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
-  for (int i = threadIdx.x; i < n_ref; i += BS) {
-    const F3 p3 = ld3_u32(ref, i);
-    const float x = p3.x, y = p3.y, z = p3.z;
-    if (isfinite(x) && isfinite(y) && isfinite(z)) {
-      xmin = fminf(xmin, x);
-      xmax = fmaxf(xmax, x);
-      ymin = fminf(ymin, y);
-      ymax = fmaxf(ymax, y);
-    }
-  }
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    xmin = fminf(xmin, __shfl_xor(xmin, s, 64));
-    xmax = fmaxf(xmax, __shfl_xor(xmax, s, 64));
-    ymin = fminf(ymin, __shfl_xor(ymin, s, 64));
-    ymax = fmaxf(ymax, __shfl_xor(ymax, s, 64));
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    const int wv = threadIdx.x >> 6;
-    S.fred[0][wv] = xmin;
-    S.fred[1][wv] = xmax;
-    S.fred[2][wv] = ymin;
-    S.fred[3][wv] = ymax;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < NW; ++i) {
-      xmin = fminf(xmin, S.fred[0][i]);
-      xmax = fmaxf(xmax, S.fred[1][i]);
-      ymin = fminf(ymin, S.fred[2][i]);
-      ymax = fmaxf(ymax, S.fred[3][i]);
-    }
-    if (!(xmax >= xmin)) { xmin = xmax = 0.f; ymin = ymax = 0.f; }
-    const float dx = xmax - xmin, dy = ymax - ymin;
-    float c = sqrtf((dx * dy) / (float)(n_ref > 0 ? n_ref : 1));   // about one point per cell on a dense surface
-    // scale-free guards: a (nearly) collinear cloud gets cells of extent / sqrt(n); coincident points one cell
-    const float ext = fmaxf(dx, dy);
-    if (!(c > ext * 1e-4f)) c = ext / sqrtf((float)(n_ref > 0 ? n_ref : 1));
-    if (!(c > 0.f) || !isfinite(c)) c = 1.0f;
-    int GX, GY;
-    for (;;) {
-      GX = (int)(dx / c) + 1;
-      GY = (int)(dy / c) + 1;
-      if ((long long)GX * GY <= ncell_max) break;
-      c *= 1.5f;
-    }
-    S.xmin = xmin;
-    S.ymin = ymin;
-    S.inv_c = 1.0f / c;
-    S.GX = GX;
-    S.GY = GY;
-  }
-  __syncthreads();
-  const int ncell = S.GX * S.GY;
-  for (int i = threadIdx.x; i < ncell; i += BS) cell_cur[i] = 0;
-  __syncthreads();
-  for (int i = threadIdx.x; i < n_ref; i += BS) {
-    const F3 p3 = ld3_u32(ref, i);
-    const float x = p3.x, y = p3.y, z = p3.z;
-    if (isfinite(x) && isfinite(y) && isfinite(z))
-      atomicAdd(&cell_cur[cell_of(y, S.ymin, S.inv_c, S.GY) * S.GX + cell_of(x, S.xmin, S.inv_c, S.GX)], 1);
-  }
-  __syncthreads();
-  // exclusive scan of the counts -> cell_start (and cell_cur, the scatter cursors): four consecutive cells per thread,
-  // a shuffle scan inside the wave, the wave totals through a double-buffered LDS slot -- one barrier per 4*BS cells
-  {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int run = 0, step = 0;
-    for (int base = 0; base < ncell; base += 4 * BS, ++step) {
-      const int i0 = base + 4 * threadIdx.x;
-      int c[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) c[u] = i0 + u < ncell ? cell_cur[i0 + u] : 0;
-      const int mine = (c[0] + c[1]) + (c[2] + c[3]);
-      int inc = mine;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-      }
-      int *slot = S.iscan2[step & 1];
-      if (lane == 63) slot[wv] = inc;
-      __syncthreads();
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { const int t = slot[w]; before += w < wv ? t : 0; total += t; }
-      int ex = run + before + inc - mine;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (i0 + u < ncell) { cell_start[i0 + u] = ex; cell_cur[i0 + u] = ex; }
-        ex += c[u];
-      }
-      run += total;
-    }
-    if (threadIdx.x == 0) { cell_start[ncell] = run; S.nsorted = run; }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n_ref; i += BS) {
-    const F3 p3 = ld3_u32(ref, i);
-    const float x = p3.x, y = p3.y, z = p3.z;
-    if (isfinite(x) && isfinite(y) && isfinite(z)) {
-      const int slot = atomicAdd(&cell_cur[cell_of(y, S.ymin, S.inv_c, S.GY) * S.GX + cell_of(x, S.xmin, S.inv_c, S.GX)], 1);
-      sref[slot] = nn_point(x, y, z, i);
-    }
-  }
-  __syncthreads();
-}
-
-// ---- exact nearest neighbours within a window -------------------------------------------------------
-// the grid parameters as wave-uniform scalars (SGPRs): read from LDS they would each cost a VGPR in the search loop
-struct NnGrid {
-  float xmin, ymin, inv_c;
-  int GX, GY, nsorted;
-};
-template <class SH>
-__device__ __forceinline__ NnGrid nn_grid(const SH &S)
-{
-  NnGrid g;
-  g.xmin = uniform_f(S.xmin);
-  g.ymin = uniform_f(S.ymin);
-  g.inv_c = uniform_f(S.inv_c);
-  g.GX = __builtin_amdgcn_readfirstlane(S.GX);
-  g.GY = __builtin_amdgcn_readfirstlane(S.GY);
-  g.nsorted = __builtin_amdgcn_readfirstlane(S.nsorted);
-  return g;
-}
-
-// the radius every reference point within distance `lim` of the query lies within, inflated past the float rounding of
-// d2, of the coordinate differences and of the bound's own arithmetic (orders of magnitude below the relative margins)
-__device__ __forceinline__ float nn_radius(float qx, float qy, float qz, float lim)
-{
-  return lim * 1.0001f + 2e-6f * (fabsf(qx) + fabsf(qy) + fabsf(qz)) + 1e-30f;
-}
-
-// (d2, index) packed as d2's bit pattern (non-negative floats order like unsigned integers) in the high word and the
-// reference index in the low word: one 64-bit unsigned minimum implements "smaller distance, ties to the lower
-// index" exactly.
-#define NN_KEY_NONE 0xFFFFFFFFFFFFFFFFull
-__device__ __forceinline__ unsigned long long nn_key(float qx, float qy, float qz, const float4 &p)
-{
-  const float dx = qx - p.y, dy = qy - p.z, dz = qz - p.w;
-  float d = dx * dx;                                     // cvflann::L2_Simple<float>
-  d += dy * dy;
-  d += dz * dz;
-  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(p.x);
-}
-#define NN_CONSIDER(P) { const unsigned long long key_ = nn_key(qx, qy, qz, (P)); best = key_ < best ? key_ : best; }
-// a key whose index is NN_IDX_NONE (a dropped pixel: d2 = inf) or NN_KEY_NONE itself means "nothing found"
-#define NN_UNPACK(best, bi, bd)                                            \
-  {                                                                        \
-    const unsigned lo_ = (unsigned)((best) & 0xFFFFFFFFull);               \
-    const bool found_ = lo_ < (unsigned)NN_IDX_NONE;                       \
-    *(bi) = found_ ? (int)lo_ : -1;                                        \
-    *(bd) = found_ ? __uint_as_float((unsigned)((best) >> 32)) : NAN;      \
-  }
-
-// ---- grid search (fl_icp: caller-supplied clouds) -------------------------------------------------------
-// exact 1-NN among the points of the cell rows [cy0, cy1] x [cx0, cx1]; the grid and the sorted cloud are L2-resident
-__device__ __forceinline__ void nn_search_grid(const NnGrid &S, const float4 *__restrict__ sref,
-                                               const int *__restrict__ cell_start, float qx, float qy, float qz, float r,
-                                               int *bi, float *bd)
-{
-  unsigned long long best = NN_KEY_NONE;
-  const int last = S.nsorted - 1;
-  if (last < 0) { NN_UNPACK(best, bi, bd) return; }
-  int cx0 = 0, cx1 = S.GX - 1, cy0 = 0, cy1 = S.GY - 1;
-  if (isfinite(r)) {
-    cx0 = cell_of(qx - r, S.xmin, S.inv_c, S.GX);
-    cx1 = cell_of(qx + r, S.xmin, S.inv_c, S.GX);
-    cy0 = cell_of(qy - r, S.ymin, S.inv_c, S.GY);
-    cy1 = cell_of(qy + r, S.ymin, S.inv_c, S.GY);
-  }
-  // The search is latency-bound and a wave pays for its slowest lane, so round trips are what counts:
-  // the headers of 4 grid rows (8 loads) are fetched together, then the candidates of all 4 row segments
-  // are enumerated as ONE flat list, ICP_NB per round trip -- a lane needs ceil(total / NB) rounds however the
-  // candidates are spread over the rows.  Slots past the end of the list are NOT masked: they read points that
-  // follow the last row segment (clamped to the cloud), and looking at extra reference points never changes the
-  // answer -- the minimum over a superset that still contains every point within the search radius is the same
-  // nearest neighbour, ties to the lowest index included.
-  for (int cy = cy0; cy <= cy1; cy += 4) {
-    int rb[4], re[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int cyu = min(cy + u, cy1);
-      rb[u] = ld_u32(cell_start, cyu * S.GX + cx0);      // cells of a row are contiguous
-      re[u] = ld_u32(cell_start, cyu * S.GX + cx1 + 1);
-    }
-#pragma unroll
-    for (int u = 1; u < 4; ++u)
-      if (cy + u > cy1) re[u] = rb[u];                  // predicated: keeps rb/re in registers
-    // flat index k -> slot k + adj[u] for pre[u] <= k < pre[u + 1]
-    const int pre1 = re[0] - rb[0], pre2 = pre1 + (re[1] - rb[1]), pre3 = pre2 + (re[2] - rb[2]);
-    const int tot = pre3 + (re[3] - rb[3]);
-    const int adj0 = rb[0], adj1 = rb[1] - pre1, adj2 = rb[2] - pre2, adj3 = rb[3] - pre3;
-    for (int base = 0; base < tot; base += ICP_NB) {
-      float4 p[ICP_NB];
-#pragma unroll
-      for (int v = 0; v < ICP_NB; ++v) {
-        const int k = base + v;
-        int adj = k >= pre1 ? adj1 : adj0;
-        adj = k >= pre2 ? adj2 : adj;
-        adj = k >= pre3 ? adj3 : adj;
-        p[v] = ld_u32(sref, min(k + adj, last));
-      }
-#pragma unroll
-      for (int v = 0; v < ICP_NB; ++v) NN_CONSIDER(p[v])
-    }
-  }
-  NN_UNPACK(best, bi, bd)
-}
-
-// ---- organised search (recognition / detection: the reference cloud is a back-projected crop) ------------
-// The reference cloud of the organised search is an IMAGE of 12-byte points (crop pixel p -> X, Y, Z; +inf where the paired
-// compaction dropped the pixel) followed by an image of their indices.  The search identifies a reference point by its PIXEL
-// (nn[] holds pixel positions there; ties between equal distances go to the lower pixel, which is the lower index: the
-// compaction is row-major), so the staged records need no index from memory -- 12 instead of 16 bytes per staged point, of a
-// kernel that is bound by the bytes it moves -- and phase A2 gathers the partner from the image instead of from ref[].
-// idximg is read once per frame (tile order) and by the point-to-plane mode (normals are stored by index).
-__host__ __device__ __forceinline__ size_t org_idximg_offset(int pixels) { return (size_t)12 * (size_t)(pixels + 4); }
-struct OrgGeom {
-  int cw, ch;            // crop size: rimg[v * cw + u] holds the point of crop pixel (u, v)
-  float offu, offv;      // scene pixel of crop pixel (0, 0) minus the principal point
-  float fx, fy;
-  float cwm, chm;        // (float)(cw - 1), (float)(ch - 1)
-  int sx0, sy0;          // scene pixel of crop pixel (0, 0)
-  float cx, cy, inv_fx, inv_fy;   // as crop_clouds uses them: (float)K.cx, 1.0f / (float)K.fx ...
-};
-// The reference point of crop pixel (u, v) from its depth factor zsf, by crop_clouds' own expression (depth_to_3d.cpp:119,132 +
-// scale_mat_vec3f): bit for bit what the 12-byte image holds.  A dropped pixel (zsf = NaN) gives a NaN point, whose distance
-// is NaN: its key orders behind every real one.
-// (suf, svf): the SCENE pixel as floats, (float)(g.sx0 + u) and (float)(g.sy0 + v)
-__device__ __forceinline__ F3 org_point_f(const OrgGeom &g, float suf, float svf, float zsf)
-{
-  F3 p;
-  p.x = (((suf - g.cx) * g.inv_fx) * zsf) * 1000;
-  p.y = (((svf - g.cy) * g.inv_fy) * zsf) * 1000;
-  p.z = zsf * 1000;
-  return p;
-}
-__device__ __forceinline__ F3 org_point(const OrgGeom &g, int u, int v, float zsf)
-{
-  return org_point_f(g, (float)(g.sx0 + u), (float)(g.sy0 + v), zsf);
-}
-// whole-wave minimum / maximum of an int by DPP (row_shr 1, 2, 4, 8, row_bcast 15 / 31), returned as a wave-uniform value
-#define FL_DPP_RED(OP, IDENT)                                                                                 \
-  v = OP(v, __builtin_amdgcn_update_dpp((int)(IDENT), v, 0x111, 0xF, 0xF, false));                            \
-  v = OP(v, __builtin_amdgcn_update_dpp((int)(IDENT), v, 0x112, 0xF, 0xF, false));                            \
-  v = OP(v, __builtin_amdgcn_update_dpp((int)(IDENT), v, 0x114, 0xF, 0xF, false));                            \
-  v = OP(v, __builtin_amdgcn_update_dpp((int)(IDENT), v, 0x118, 0xF, 0xF, false));                            \
-  v = OP(v, __builtin_amdgcn_update_dpp((int)(IDENT), v, 0x142, 0xA, 0xF, false));                            \
-  v = OP(v, __builtin_amdgcn_update_dpp((int)(IDENT), v, 0x143, 0xC, 0xF, false));                            \
-  return __builtin_amdgcn_readlane(v, 63);
-__device__ __forceinline__ int wave_min_i(int v) { FL_DPP_RED(min, 0x7fffffff) }
-__device__ __forceinline__ int wave_max_i(int v) { FL_DPP_RED(max, (int)0x80000000) }
-
-// N whole-wave maxima at once (a minimum is the maximum of the negated values): the DPP steps of the N reductions are
-// interleaved, so the wait states a DPP read needs after the VALU write of its source are filled by the other reductions'
-// steps instead of s_nop -- six serial reductions cost 6 x (6 + 6 nops + 2) issue slots, five interleaved ones 5 x 7
-template <int N>
-__device__ __forceinline__ void wave_max_multi(int (&v)[N])
-{
-#define FL_DPP_STEP(CTRL, RMASK)                                                                                       \
-  _Pragma("unroll") for (int k_ = 0; k_ < N; ++k_)                                                                     \
-    v[k_] = max(v[k_], __builtin_amdgcn_update_dpp((int)0x80000000, v[k_], CTRL, RMASK, 0xF, false));
-  FL_DPP_STEP(0x111, 0xF)
-  FL_DPP_STEP(0x112, 0xF)
-  FL_DPP_STEP(0x114, 0xF)
-  FL_DPP_STEP(0x118, 0xF)
-  FL_DPP_STEP(0x142, 0xA)
-  FL_DPP_STEP(0x143, 0xC)
-#undef FL_DPP_STEP
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = __builtin_amdgcn_readlane(v[k], 63);
-}
-
-// Six whole-wave maxima with gfx950's lane-swap instructions: v_permlane32_swap exchanges the upper half of one register with
-// the lower half of another, so ONE maximum of the swapped pair folds the two halves of BOTH values (value A's partials now live
-// in lanes 0-31, value B's in 32-63); v_permlane16_swap does the same for 16-lane rows.  Four values folded into the four rows
-// of one register and two into the halves of another need 4 + 5 DPP steps in all where six separate reductions need 36:
-// 19 vector instructions instead of 36 (+ their wait states) per search step.
-__device__ __forceinline__ void wave_max6(int (&v)[6])
-{
-  auto fold32 = [](int a, int b) {                         // lanes 0-31: max over a's halves, lanes 32-63: over b's
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false);
-    return max((int)r[0], (int)r[1]);
-  };
-  const int m01 = fold32(v[0], v[1]), m23 = fold32(v[2], v[3]);
-  int m45 = fold32(v[4], v[5]);
-  const auto q = __builtin_amdgcn_permlane16_swap((unsigned)m01, (unsigned)m23, false, false);
-  int n = max((int)q[0], (int)q[1]);                        // rows 0..3: v[0], v[2], v[1], v[3] (16 partials each)
-#define FL_DPP_STEP2(CTRL)                                                                                             \
-  n = max(n, __builtin_amdgcn_update_dpp((int)0x80000000, n, CTRL, 0xF, 0xF, false));                                  \
-  m45 = max(m45, __builtin_amdgcn_update_dpp((int)0x80000000, m45, CTRL, 0xF, 0xF, false));
-  FL_DPP_STEP2(0x111)
-  FL_DPP_STEP2(0x112)
-  FL_DPP_STEP2(0x114)
-  FL_DPP_STEP2(0x118)
-#undef FL_DPP_STEP2
-  m45 = max(m45, __builtin_amdgcn_update_dpp((int)0x80000000, m45, 0x142, 0xA, 0xF, false));   // row_bcast:15 into rows 1, 3
-  v[0] = __builtin_amdgcn_readlane(n, 15);
-  v[2] = __builtin_amdgcn_readlane(n, 31);
-  v[1] = __builtin_amdgcn_readlane(n, 47);
-  v[3] = __builtin_amdgcn_readlane(n, 63);
-  v[4] = __builtin_amdgcn_readlane(m45, 31);
-  v[5] = __builtin_amdgcn_readlane(m45, 63);
-}
-// dev / tests: both reductions on one wavefront of inputs (tests/test_gpu_icp.py checks them against each other and numpy)
-__global__ void k_dev_wave_max6(const int *in, int *out)
-{
-  int a[6], b[6];
-  for (int k = 0; k < 6; ++k) a[k] = b[k] = in[k * 64 + threadIdx.x];
-  wave_max6(a);
-  wave_max_multi(b);
-  if (threadIdx.x == 0)
-    for (int k = 0; k < 6; ++k) { out[k] = a[k]; out[6 + k] = b[k]; }
-}
-
-// host entry for the test: 6 x 64 ints in, 6 (wave_max6) + 6 (wave_max_multi) out; plain HIP calls on the null stream
-extern "C" int fl_dev_wave_max6(const int *in_host, int *out_host)
-{
-  int *d_in = nullptr, *d_out = nullptr;
-  if (hipMalloc(&d_in, 6 * 64 * sizeof(int)) != hipSuccess || hipMalloc(&d_out, 12 * sizeof(int)) != hipSuccess) { (void)hipFree(d_in); return FL_ERR_HIP; }
-  bool ok = hipMemcpy(d_in, in_host, 6 * 64 * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_dev_wave_max6, dim3(1), dim3(64), 0, 0, d_in, d_out);
-    ok = hipGetLastError() == hipSuccess && hipMemcpy(out_host, d_out, 12 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
-  return ok ? FL_OK : FL_ERR_HIP;
-}
-
-// The crop pixels whose points can lie within distance r of q: a point (X, Y, Z) of pixel (su, sv) satisfies
-// su - cx = X fx / Z up to float rounding (it was generated as X = ((su - cx) / fx) Z), and |X - qx|, |Z - qz| <= r.
-// The 0.01-pixel slop is an order of magnitude above that rounding (5e-7 relative on |su - cx| <= 2000 pixels).  An empty window has u_lo > u_hi.
-// (the constants folded -- cul / cuh = offu +- slop, cvl / cvh = offv +- slop, wave-uniform -- and the clamping left to the
-// saturating float -> int conversion; returns whether the window holds a pixel)
-// Branch-free form of org_window2 for the pipelined step: every lane computes the projection (a lane whose radius is not finite
-// or reaches Z <= 1 computes garbage and selects the whole crop, a lane that is not queryable selects nothing), so that a step
-// has no exec-mask regions in front of its reductions.  Same windows.
-__device__ __forceinline__ bool org_window2_flat(const OrgGeom &g, float cul, float cuh, float cvl, float cvh, float qx, float qy, float qz, float r,
-                                                 bool queryable, int &u_lo, int &u_hi, int &v_lo, int &v_hi)
-{
-  const float zlo = qz - r, zhi = qz + r;
-  const bool narrow = isfinite(r) && zlo > 1.0f;         // otherwise the whole crop (valid points have 0 < Z <= 900)
-  const float ilo = __builtin_amdgcn_rcpf(zlo), ihi = __builtin_amdgcn_rcpf(zhi);
-  const float xlo = qx - r, xhi = qx + r, ylo = qy - r, yhi = qy + r;
-  const int iul = cvt_i32_sat(ceilf((xlo * (xlo < 0.f ? ilo : ihi)) * g.fx - cul));
-  const int iuh = cvt_i32_sat(floorf((xhi * (xhi > 0.f ? ilo : ihi)) * g.fx - cuh));
-  const int ivl = cvt_i32_sat(ceilf((ylo * (ylo < 0.f ? ilo : ihi)) * g.fy - cvl));
-  const int ivh = cvt_i32_sat(floorf((yhi * (yhi > 0.f ? ilo : ihi)) * g.fy - cvh));
-  u_lo = narrow ? max(iul, 0) : 0;
-  u_hi = narrow ? min(iuh, g.cw - 1) : g.cw - 1;
-  v_lo = narrow ? max(ivl, 0) : 0;
-  v_hi = narrow ? min(ivh, g.ch - 1) : g.ch - 1;
-  return queryable & (u_lo <= u_hi) & (v_lo <= v_hi);
-}
-__device__ __forceinline__ bool org_window2(const OrgGeom &g, float cul, float cuh, float cvl, float cvh, float qx, float qy, float qz, float r,
-                                            int &u_lo, int &u_hi, int &v_lo, int &v_hi)
-{
-  u_lo = 0; u_hi = g.cw - 1; v_lo = 0; v_hi = g.ch - 1;
-  const float zlo = qz - r, zhi = qz + r;
-  if (isfinite(r) && zlo > 1.0f) {                       // otherwise the whole crop (valid points have 0 < Z <= 900)
-    const float ilo = __builtin_amdgcn_rcpf(zlo), ihi = __builtin_amdgcn_rcpf(zhi);
-    const float xlo = qx - r, xhi = qx + r, ylo = qy - r, yhi = qy + r;
-    const int iul = cvt_i32_sat(ceilf((xlo * (xlo < 0.f ? ilo : ihi)) * g.fx - cul));
-    const int iuh = cvt_i32_sat(floorf((xhi * (xhi > 0.f ? ilo : ihi)) * g.fx - cuh));
-    const int ivl = cvt_i32_sat(ceilf((ylo * (ylo < 0.f ? ilo : ihi)) * g.fy - cvl));
-    const int ivh = cvt_i32_sat(floorf((yhi * (yhi > 0.f ? ilo : ihi)) * g.fy - cvh));
-    u_lo = max(iul, 0);
-    u_hi = min(iuh, g.cw - 1);
-    v_lo = max(ivl, 0);
-    v_hi = min(ivh, g.ch - 1);
-  }
-  return u_lo <= u_hi && v_lo <= v_hi;
-}
-
-// every lane's window enumerated in lockstep, maxh rows of maxw positions, ICP_NBQ positions per batch (lanes with a
-// smaller window re-read their own last column / row: duplicates do not change a minimum);
-// fetch((v - ov) * RS + (u - ou)) returns the point of crop pixel (u, v)
-template <typename F>
-__device__ __forceinline__ unsigned long long org_scan(F fetch, int RS, int ou, int ov, float qx, float qy, float qz, int u_lo, int u_hi,
-                                                       int v_lo, int v_hi, int maxw, int maxh)
-{
-  constexpr int NBQ = ICP_NBQ;
-  unsigned long long best = NN_KEY_NONE;
-  const int wl = u_hi - u_lo, hl = v_hi - v_lo;
-  const int b0 = (v_lo - ov) * RS + (u_lo - ou);
-  // A batch is NBQ CONSECUTIVE positions from a clamped start (one address and immediate offsets instead of a clamp and
-  // an address per position).  A window narrower than NBQ reads up to NBQ - 1 = NN_OVERRUN positions past its right edge:
-  // the next pixels of the row, the start of the next row, or -- behind the last row -- the points the caller keeps there
-  // (copies of the last staged point / points at infinity behind the image).  All of them are reference points of this
-  // frame or points at infinity, and looking at more reference points never changes the nearest one.
-  static_assert(NBQ - 1 <= NN_OVERRUN, "the overrun guard behind the staged window / the image is NN_OVERRUN points");
-  const int wlc = max(wl - (NBQ - 1), 0);
-  for (int dv = 0; dv < maxh; ++dv) {
-    const int rb = b0 + min(dv, hl) * RS;
-    for (int du = 0; du < maxw; du += NBQ) {               // one batch at a time: the other waves of the SIMD cover the LDS latency
-      float4 cur[NBQ];
-      const int bb = rb + min(du, wlc);
-#pragma unroll
-      for (int e = 0; e < NBQ; ++e) cur[e] = fetch(bb + e);
-#pragma unroll
-      for (int e = 0; e < NBQ; ++e) NN_CONSIDER(cur[e])
-    }
-  }
-  return best;
 }
 
 // ---- getL2distClouds (ICP.cpp:68-111) over the index-paired clouds, optionally fused with the
@@ -1118,12 +649,6 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
     if (parity) dbuf(t)[slot] = term;                     // non-inliers add an exact +0.0f
     if (DEFER && i < n) dterm[i] = term;
   };
-  auto tile_barrier = [&]() {
-    if (parity) {
-      __builtin_amdgcn_s_waitcnt(0xC07F);                  // s_waitcnt lgkmcnt(0)
-      __builtin_amdgcn_s_barrier();
-    }
-  };
   // tile t (block t of KB tiles) is complete in LDS: the chain wave adds it (every lane of the wave enters)
   auto chain_step = [&](int t) {
     const int first = KB == 1 || t == 0 ? t : (t - 1) * KB + 1, last = KB == 1 || t == 0 ? t : t * KB;   // the block's tiles
@@ -1136,9 +661,9 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
   const int nblocks = KB == 1 ? ntiles : (ntiles > 0 ? (ntiles - 1 + KB - 1) / KB + 1 : 0);
   const int nbar = KB == 1 ? ntiles : (ntiles > 0 ? (ntiles - 1) / KB + 1 : 0);
   auto block_barrier = [&](int t) {                       // behind tile t: the barrier that closes a block
-    if (KB == 1 || t % KB == 0) tile_barrier();
+    if (parity && (KB == 1 || t % KB == 0)) tile_barrier();
   };
-  const bool chain_wave = __builtin_amdgcn_readfirstlane(clane) >= 0;
+  const bool chain_wave = parity && __builtin_amdgcn_readfirstlane(clane) >= 0;
   if (chain_wave) {
     // the chain wave's own loop (see the A2 phase): one barrier per tile like the producers' below
     CH_STAMP_BEGIN;
@@ -1163,7 +688,7 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
         block_barrier(t + 1);
       }
     }
-  } else {
+  } else if (parity) {
     for (int t = 0; t < nbar; ++t) tile_barrier();         // a wave that neither chains nor produces (1024-thread workgroup)
   }
   __syncthreads();                                         // the phase's stores (mod, bnd, dterm) are visible to the workgroup
@@ -1205,6 +730,98 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
   return 0.0f;
 }
 
+// ---- the pose solvers of an iteration and the pose accumulation (one thread, from the sums in S.sums / S.dsum[0]) ----
+// R_optimal, T_optimal from the 9 products and the two centroids' sums (ICP.cpp:737-748); S.ok = checkRange
+template <int MODE, class SH>
+__device__ __forceinline__ void solve_rigid(SH &S, int ncm, int ncr)
+{
+  float C[9], mc[3], rc[3];
+  if (MODE == FL_ICP_PARITY) {
+    for (int k = 0; k < 9; ++k) C[k] = S.sums[k];
+    for (int k = 0; k < 3; ++k) { mc[k] = S.sums[9 + k] / (float)ncm; rc[k] = S.sums[12 + k] / (float)ncr; }   // getMean :19-24
+  } else {
+    for (int k = 0; k < 9; ++k) C[k] = (float)S.dsum[0][k];
+    for (int k = 0; k < 3; ++k) { mc[k] = (float)(S.dsum[0][9 + k] / ncm); rc[k] = (float)(S.dsum[0][12 + k] / ncr); }
+  }
+  float u[9], vt[9];
+  svd3(C, u, vt);                                    // :742
+  for (int i = 0; i < 3; ++i)                        // R_optimal = Mat(vt.t() * u.t()) :744 (gemm: double acc)
+    for (int j = 0; j < 3; ++j) {
+      double s = 0;
+      for (int k = 0; k < 3; ++k) s += (double)vt[k * 3 + i] * (double)u[j * 3 + k];
+      S.Ropt[i * 3 + j] = (float)s;
+    }
+  float Rm[3];
+  mat_vec(S.Ropt, mc, Rm);
+  for (int k = 0; k < 3; ++k) S.Topt[k] = rc[k] - Rm[k];                      // :747
+  S.ok = finite_all(S.Ropt, 9) && finite_all(S.Topt, 3);                      // checkRange :748
+}
+// FL_ICP_POINT_TO_PLANE: the 6x6 normal equations (21 + 6 sums) by Cholesky, the rotation by Rodrigues; S.ok = solvable and finite
+template <class SH>
+__device__ __forceinline__ void solve_point_to_plane(SH &S)
+{
+  double A[6][6], x[6], tr = 0.0;
+  int q = 0;
+  for (int a = 0; a < 6; ++a)
+    for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = S.dsum[0][q++];
+  for (int a = 0; a < 6; ++a) { x[a] = -S.dsum[0][21 + a]; tr += A[a][a]; }
+  bool ok = tr > 0.0 && tr < 1.0e300;
+  for (int a = 0; a < 6; ++a) A[a][a] += 1.0e-12 * tr;          // keeps a barely constrained direction finite
+  for (int c = 0; c < 6 && ok; ++c) {                            // Cholesky A = L L^T (lower triangle in place)
+    double d = A[c][c];
+    for (int k = 0; k < c; ++k) d -= A[c][k] * A[c][k];
+    if (!(d > 1.0e-13 * tr)) { ok = false; break; }              // a direction the pairs do not constrain
+    d = sqrt(d);
+    A[c][c] = d;
+    for (int r = c + 1; r < 6; ++r) {
+      double v = A[r][c];
+      for (int k = 0; k < c; ++k) v -= A[r][k] * A[c][k];
+      A[r][c] = v / d;
+    }
+  }
+  if (ok) {
+    for (int r = 0; r < 6; ++r) {                                // L y = b
+      double v = x[r];
+      for (int k = 0; k < r; ++k) v -= A[r][k] * x[k];
+      x[r] = v / A[r][r];
+    }
+    for (int r = 5; r >= 0; --r) {                               // L^T x = y
+      double v = x[r];
+      for (int k = r + 1; k < 6; ++k) v -= A[k][r] * x[k];
+      x[r] = v / A[r][r];
+    }
+    // Rodrigues: R = I + (sin t / t) K + ((1 - cos t) / t^2) K^2, K = [omega]x
+    const double wx = x[0], wy = x[1], wz = x[2], t2 = wx * wx + wy * wy + wz * wz, t = sqrt(t2);
+    const double sa = t > 1.0e-9 ? sin(t) / t : 1.0 - t2 / 6.0, sb = t > 1.0e-9 ? (1.0 - cos(t)) / t2 : 0.5 - t2 / 24.0;
+    const double Kx[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double k2 = 0;
+        for (int k = 0; k < 3; ++k) k2 += Kx[i * 3 + k] * Kx[k * 3 + j];
+        S.Ropt[i * 3 + j] = (float)((i == j ? 1.0 : 0.0) + sa * Kx[i * 3 + j] + sb * k2);
+      }
+    for (int k = 0; k < 3; ++k) S.Topt[k] = (float)x[3 + k];
+  }
+  S.ok = ok && finite_all(S.Ropt, 9) && finite_all(S.Topt, 3);
+}
+// T = Ropt T + Topt, R = Ropt R (:793-797)
+template <class SH>
+__device__ __forceinline__ void pose_accumulate(SH &S)
+{
+  float RT[3];
+  mat_vec(S.Ropt, S.T, RT);
+  for (int k = 0; k < 3; ++k) S.T[k] = RT[k] + S.Topt[k];
+  mat_mat(S.Ropt, S.R, S.R);
+}
+// the result of a run that cannot start (:633-638)
+__device__ __forceinline__ void icp_result_none(fl_icp_result *res)
+{
+  for (int i = 0; i < 9; ++i) res->R[i] = 0.f;
+  for (int i = 0; i < 3; ++i) res->T[i] = 0.f;
+  res->dist_mean = -1.0f; res->px_ratio = 0.f;
+  res->iters = 0; res->n_corr_last = 0;
+}
+
 // ---- icpCloudToCloud_Ex (ICP.cpp:617-809) --------------------------------------------------------
 // ORG: the reference cloud is also available as the image `og` describes (sref = image of points + image of indices, perm = tile order), see
 // "Organised search" at the top; otherwise the grid is built here and searched.
@@ -1244,14 +861,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   }
   __syncthreads();
   if (n_model < 3 || n_ref < 3 || n_ref < n_model) {    // :633-638 (n_ref < n_model: reference reads OOB)
-    if (threadIdx.x == 0) {
-      for (int i = 0; i < 9; ++i) res->R[i] = 0.f;
-      for (int i = 0; i < 3; ++i) res->T[i] = 0.f;
-      res->dist_mean = -1.0f;
-      res->px_ratio = 0.f;
-      res->iters = 0;
-      res->n_corr_last = 0;
-    }
+    if (threadIdx.x == 0) icp_result_none(res);
     __syncthreads();
     return;
   }
@@ -1281,419 +891,8 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   bool have_nn = false;                                  // nn[] / nd[] hold the neighbours of the current model cloud
   float old_mean = 0.0f;                                 // dist_mean before the pending distances (pending == 2)
 
-  // ---- organised search: PointsCorresponding (:193-279) for every model point, exact 1-NN within min(bnd[i], r_lim) ----
-  // 64 queries of one (or two adjacent) 16x4-pixel tiles per wave and step: window, staging, scan.  Steps are claimed from a
-  // workgroup counter (S.a1_next, reset by the caller) where a wave joins late (SPEC), four steps ahead of the one being
-  // scanned, so that the loads of the next steps (perm -> mod, bnd) are in flight; otherwise wave w takes steps w, w + NW, ...
-  // found(active, i, qx, qy, qz, j, d): j = -1, d = NaN when no reference point lies within the radius.
-  // Around the distance scan of a step (which is what the step is for: 4 rows x 46 instructions per batch of four
-  // positions) round 2 spent as many instructions again; what is left of that:
-  //  * the union rectangle is staged in whole passes of 64 points, as many as it needs (a compile-time count per case), the
-  //    point of a slot by a reciprocal multiply: no division, no per-pass predicate, no separate guard points (measured:
-  //    rows padded to 16 / 32 / 64 points need no address arithmetic at all, but nine steps in ten are 14 - 29 pixels wide
-  //    and would stage twice the points: 26.8 against 25.4 ms per 2560 frames, profiles/README.md);
-  //  * the five wave reductions (union rectangle, tallest lane window) are interleaved (wave_max_multi), the batches per
-  //    row come from two ballots;
-  //  * the window arithmetic has its constants folded and leaves the clamping to the saturating float -> int conversion.
-  auto org_search = [&](const float r_lim, const bool poll_stop, auto &&found) {
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    static_assert(sizeof(S.prod) + sizeof(S.dtile) + sizeof(S.stage_pad) >= (size_t)NW * ICP_STAGE_CAP * 16, "the chain tiles (idle during the search) hold every wave's staged rows");
-    static_assert(offsetof(SH, stage_pad) == offsetof(SH, dtile) + sizeof(S.dtile), "prod, dtile and stage_pad are one contiguous region");
-    static_assert(offsetof(SH, dtile) == offsetof(SH, prod) + sizeof(S.prod), "prod and dtile are one contiguous region");
-    float4 *stage = (float4 *)&S.prod[0][0][0] + wv * ICP_STAGE_CAP;
-    const float *rimg = (const float *)sref;
-    // (the 1024-thread kernel keeps the 12-byte image: a frame alone on its CU waits for the rebuilt points -- 2.92 against 2.67 ms
-    // per 8 frames -- where four workgroups per CU gain from the bytes: 32.9 against 34.2 ms per 4096)
-    constexpr bool ZIMG = MODE == FL_ICP_PARITY && NW < 8;
-    const float *zimg = (const float *)(wsb + L.zimg);
-    const int last_s = n_model - 1;
-    const float cul = uniform_f(og.offu + 0.01f), cuh = uniform_f(og.offu - 0.01f), cvl = uniform_f(og.offv + 0.01f), cvh = uniform_f(og.offv - 0.01f);
-    constexpr int stride = NW * 64;
-    int static_next = wv * 64 + 4 * stride;
-    auto claim = [&](int count) {                          // `count` queries off the workgroup's list (wave-uniform result)
-      int v = 0;
-      if (lane == 0) v = atomicAdd(&S.a1_next, count);
-      return __builtin_amdgcn_readfirstlane(v);
-    };
-    auto next_step = [&]() {
-      if (SPEC) return claim(64);
-      const int v = static_next;
-      static_next += stride;
-      return v;
-    };
-    const int sdist = SPEC ? 64 : stride;
-    int sb0 = SPEC ? claim(256) : wv * 64, sb1 = sb0 + sdist, sb2 = sb0 + 2 * sdist, sb3 = sb0 + 3 * sdist;
-    int i_c = ld_u32(perm, min(sb0 + lane, last_s));
-    int i_n = ld_u32(perm, min(sb1 + lane, last_s));
-    int i_nn = ld_u32(perm, min(sb2 + lane, last_s));
-    F3 q_c = ld3_u32(mod, i_c), q_n = ld3_u32(mod, i_n);
-    float b_c = bnd_ld(bnd, i_c), b_n = bnd_ld(bnd, i_n);
-    // A step's results are handed to found() (which stores them) at the head of the NEXT step, in front of that step's
-    // staging loads: vmcnt counts loads and stores in one in-order queue, so stores issued at the end of a step were what the
-    // wait at the head of the next one waited for (20 % of the phase); issued here, the wait that follows them is the one
-    // for the staging loads, which covers them for free.
-    bool pend = false, p_active = false;
-    int p_i = 0, p_j = -1;
-    float p_qx = 0.f, p_qy = 0.f, p_qz = 0.f, p_d = NAN;
-#ifdef FL_ICP_PHASES
-    long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_last = clock64();
-#define ST_STAMP(k) { const long long now_ = clock64(); st_acc[k] += now_ - st_last; st_last = now_; }
-#else
-#define ST_STAMP(k) { }
-#endif
-    while (sb0 < n_model) {
-      if (poll_stop && *(volatile int *)&S.stop) break;
-      const int sb4 = next_step();
-      const int i = i_c;
-      const float qx = q_c.x, qy = q_c.y, qz = q_c.z;
-#ifdef FL_ICP_PHASES
-      asm volatile("" :: "v"(qx), "v"(b_c));             // the query and its bound have arrived
-#endif
-      ST_STAMP(0)
-      if (pend) { found(p_active, p_i, p_qx, p_qy, p_qz, p_j, p_d); pend = false; }
-      const bool active = sb0 + lane < n_model;
-      const bool queryable = active && r_lim >= 0.f && isfinite(qx) && isfinite(qy) && isfinite(qz);
-      // ---- this lane's window, the union rectangle, the tallest window ----
-      int u_lo = 1, u_hi = 0, v_lo = 1, v_hi = 0;
-      bool some = false;
-      if (queryable) some = org_window2(og, cul, cuh, cvl, cvh, qx, qy, qz, nn_radius(qx, qy, qz, fminf(b_c, r_lim)), u_lo, u_hi, v_lo, v_hi);   // NaN bnd -> r_lim
-      const int big = 0x3fffffff;
-      int red[5] = {some ? -u_lo : -big, some ? u_hi : -1, some ? -v_lo : -big, some ? v_hi : -1, some ? v_hi - v_lo + 1 : 0};
-      wave_max_multi(red);
-      const int U0 = -red[0], U1 = red[1], V0 = -red[2], V1 = red[3], maxh = red[4];
-      const bool any = U1 >= U0;                            // wave-uniform: some lane has a window
-      ST_STAMP(1)
-      // the loads of the step after next (the next one's are in flight)
-      const F3 q_nn = ld3_u32(mod, i_nn);
-      const float b_nn = bnd_ld(bnd, i_nn);
-      const int i_nnn = ld_u32(perm, min(sb3 + lane, last_s));
-      int j = -1;
-      float d = NAN;
-      if (any) {
-        if (!some) { u_lo = u_hi = U0; v_lo = v_hi = V0; }     // lanes without a window look at one point of the union: a real
-                                                             // reference point beyond their radius, which the gate drops
-        const int wl = u_hi - u_lo, hl = v_hi - v_lo;
-        // 4-wide batches per row of the widest lane window: 1 or 2 by ballot, beyond that by a reduction (first iterations)
-        int nbw = 1;
-        if (__ballot(wl > 3) != 0ull) nbw = __ballot(wl > 7) == 0ull ? 2 : (wave_max_i(wl) >> 2) + 1;
-        const int W = U1 - U0 + 1, H = V1 - V0 + 1, area = W * H;
-        // The union rectangle is staged row by row at its own width: LDS slot k = lane + 64 p holds its point (k / W, k % W).
-        // Whole passes of 64 slots are staged, enough for the rectangle and the 3 slots a 4-wide batch may run past its last
-        // row; slots past the rectangle hold further points of the image (or the points at infinity behind it), which is
-        // all a scan may ever look at: a real reference point of this frame or infinity never changes the nearest one.
-        const int npneed = (area + 3 + 63) >> 6, npass = npneed <= 2 ? 2 : (npneed <= 4 ? npneed : 6);
-        const bool staged = npneed <= 6;
-#ifdef FL_ICP_PHASES
-        if (lane == 0) {
-          atomicAdd((unsigned long long *)&S.tacc[8], 1ull);
-          atomicAdd((unsigned long long *)&S.tacc[9], (unsigned long long)(4 * nbw * maxh));
-          atomicAdd((unsigned long long *)&S.tacc[10], staged ? 0ull : 1ull);
-          atomicAdd((unsigned long long *)&S.tacc[11], (unsigned long long)(staged ? npass * 64 : 0));
-          if (S.iter <= 3) atomicAdd((unsigned long long *)&S.tacc[12], (unsigned long long)(4 * nbw * maxh));
-          const int wcl = W <= 13 ? 0 : (W <= 29 ? 1 : (W <= 61 ? 2 : 3)), hcl = H <= 5 ? 0 : (H <= 10 ? 1 : (H <= 20 ? 2 : 3));
-          atomicAdd(&S.hist[wcl * 4 + hcl], 1u);
-          atomicAdd(&S.hist[16 + min(maxh, 6) - 1], 1u);   // (bins 22..24 and 26..28 carry the chain phases' stamps)
-        }
-#endif
-        unsigned long long best = NN_KEY_NONE;
-        if (staged) {
-          // k / W by reciprocal: (k + 0.5) / W stays 0.5 / W away from the integers, three orders of magnitude more than the
-          // error of v_rcp_f32 and the product (k < 448)
-          const float invW = uniform_f(__builtin_amdgcn_rcpf((float)W));
-          const int base = (int)__umul24((unsigned)V0, (unsigned)og.cw) + U0, last_pt = og.cw * og.ch + NN_OVERRUN - 1;
-          auto stage_passes = [&](auto np_) {
-            constexpr int NP = decltype(np_)::value;
-            float4 R[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-              const int row = (int)(((float)(lane + 64 * p) + 0.5f) * invW), col = lane + 64 * p - row * W;
-              const int pos = min((int)__umul24((unsigned)row, (unsigned)og.cw) + col + base, last_pt);
-              if (ZIMG) {
-                // 4 bytes per staged point instead of 12: the pixel's depth factor; its point rebuilt by crop_clouds' expression
-                // (pixel (U0 + col, V0 + row); a slot clamped to the guard behind the image reads NaN whatever its pixel)
-                const float zf = ld_u32(zimg, pos);
-                const F3 pt = org_point(og, U0 + col, V0 + row, zf);
-                R[p] = nn_point(pt.x, pt.y, pt.z, zf != zf ? NN_IDX_NONE : pos);
-              } else {
-                const F3 pt = ld3_u32(rimg, pos);
-                R[p] = nn_point(pt.x, pt.y, pt.z, pt.x == INFINITY ? NN_IDX_NONE : pos);
-              }
-            }
-#pragma unroll
-            for (int p = 0; p < NP; ++p) stage[lane + 64 * p] = R[p];
-          };
-          if (npass == 3) stage_passes(std::integral_constant<int, 3>());
-          else if (npass == 4) stage_passes(std::integral_constant<int, 4>());
-          else if (npass == 2) stage_passes(std::integral_constant<int, 2>());
-          else stage_passes(std::integral_constant<int, 6>());
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          ST_STAMP(2)
-          // scan: maxh rows (a lane with fewer re-reads its last one) of nbw batches of 4 consecutive points (a window narrower
-          // than 4 reads on into the next points of its row, of the next row, or of the slots behind the rectangle)
-          static_assert(ICP_NBQ == 4 && NN_OVERRUN == 3, "the staged scan is written for 4-wide batches (cur[4], wl - 3, area + 3): "
-                                                            "build org_scan's ICP_NBQ variants only with this path rewritten to match");
-          const float4 *row0 = stage + (v_lo - V0) * W + (u_lo - U0);
-          if (nbw == 1) {                                      // every lane's window is at most 4 wide: one batch per row
-            for (int dv = 0; dv < maxh; ++dv) {
-              const float4 *bp = row0 + min(dv, hl) * W;
-              float4 cur[4];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) cur[e] = bp[e];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) NN_CONSIDER(cur[e])
-            }
-          } else {
-            const int wlc = max(wl - 3, 0);
-            for (int dv = 0; dv < maxh; ++dv) {
-              const float4 *rowp = row0 + min(dv, hl) * W;
-              for (int du = 0; du < 4 * nbw; du += 4) {
-                const float4 *bp = rowp + min(du, wlc);
-                float4 cur[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) cur[e] = bp[e];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) NN_CONSIDER(cur[e])
-              }
-            }
-          }
-        } else {
-          best = org_scan([&](int idx) { const F3 pt = ld3_u32(rimg, idx); return nn_point(pt.x, pt.y, pt.z, pt.x == INFINITY ? NN_IDX_NONE : idx); },
-                          og.cw, 0, 0, qx, qy, qz, u_lo, u_hi, v_lo, v_hi, 4 * nbw, maxh);
-        }
-        if (queryable) NN_UNPACK(best, &j, &d)
-#ifdef FL_ICP_PHASES
-        asm volatile("" :: "v"(j), "v"(d));
-#endif
-        ST_STAMP(3)
-      }
-      pend = true; p_active = active; p_i = i; p_qx = qx; p_qy = qy; p_qz = qz; p_j = j; p_d = d;
-      i_c = i_n; q_c = q_n; b_c = b_n;
-      i_n = i_nn; q_n = q_nn; b_n = b_nn;
-      i_nn = i_nnn;
-      sb0 = sb1; sb1 = sb2; sb2 = sb3; sb3 = sb4;
-      ST_STAMP(4)
-    }
-    if (pend) found(p_active, p_i, p_qx, p_qy, p_qz, p_j, p_d);
-#ifdef FL_ICP_PHASES
-    if (lane == 0)
-      for (int k = 0; k < 5; ++k) atomicAdd(&S.stime[k], (unsigned long long)st_acc[k]);
-#endif
-#undef ST_STAMP
-  };
-  // (Measured in round 3 and not kept, profiles/README.md: the same search software-pipelined over its steps -- the next
-  // step's rectangle fetched by LDS-DMA while this one is scanned -- shortens the search phase by a fifth and lengthens the
-  // chain phases by as much; the rectangle staged as 2-byte depths with the points rebuilt in registers, an eighth of the
-  // staged bytes, is slower still: the conversion sits on the step's critical path.)
-  // ---- the same search with the staging one step ahead (256-thread parity kernel) -------------------------------------------
-  // With the 4-byte image a step's staged data is a handful of dwords per lane, so the NEXT step can be prepared -- its
-  // windows, its union rectangle, its staging loads issued -- before this step is scanned: the loads' round trip (a third of a
-  // step) runs underneath the scan instead of in front of it.  Two prepared-step states trade roles by unrolling the loop
-  // twice (never by moves: see the chain phases).  A state issues its loads in wave-uniform pairs of passes (the
-  // first version always issued ICP_PIPE_NP, slots past the rectangle reading the guard behind the image, for fear that a branch
-  // between issue and use would make the compiler drain the queue: it does not -- the wait in front of the first use is
-  // counted for the shortest path -- and with the column-major tiles seven steps in ten need only two passes).  Same windows,
-  // same candidates, same keys: bit-identical to org_search.
-#define ICP_PIPE_NP 6
-
-  // Slot s = lane + 64 p of a staged W-wide rectangle -> its row and column and the crop position base + row * cw + col, in
-  // float32: every value is an integer below 2^24 (small_crop), so each product, fma and sum is exact, at full rate, where the
-  // integer forms cost two quarter-rate multiplies per slot (v_mul_lo_u32, v_mad_u64_u32).
-  struct SlotPos { float row, col, pos; };
-  const float cwf = (float)og.cw;
-  const bool small_crop = (long long)og.cw * og.ch + NN_OVERRUN < (1 << 24);
-  auto slot_pos = [&](float slotf, float Wf, float invW, float basef) {
-    SlotPos r;
-    r.row = __builtin_truncf((slotf + 0.5f) * invW);
-    r.col = __builtin_fmaf(-r.row, Wf, slotf);
-    r.pos = __builtin_fmaf(r.row, cwf, r.col + basef);
-    return r;
-  };
-  struct Prep {
-    int i;                                   // the lane's query (model index) and point
-    float qx, qy, qz;
-    bool active, queryable;
-    int u_lo, u_hi, v_lo, v_hi;              // its window (one pixel of the union if it has none)
-    int U0, V0, W, maxh, nbw, npass;         // wave-uniform: union rectangle, tallest window, batches per row, passes
-    bool w3;                                 // no lane window is wider than 3 pixels: batches of 3 positions
-#ifdef FL_ICP_PHASES
-    int wlmax;
-#endif
-    bool any, staged;
-    float z[ICP_PIPE_NP];                    // depth factors of the staged slots lane + 64 p (in flight until finish)
-  };
-  auto org_search_pipe = [&](const float r_lim, auto &&found) {
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    float4 *stage = (float4 *)&S.prod[0][0][0] + wv * ICP_STAGE_CAP;
-    const float *rimg = (const float *)sref;
-    const float *zimg = (const float *)(wsb + L.zimg);
-    const int last_s = n_model - 1, last_pt = og.cw * og.ch + NN_OVERRUN - 1;
-    const float lanef = (float)lane;
-    const float cul = uniform_f(og.offu + 0.01f), cuh = uniform_f(og.offu - 0.01f), cvl = uniform_f(og.offv + 0.01f), cvh = uniform_f(og.offv - 0.01f);
-    constexpr int stride = NW * 64;
-    // windows, union and staging loads of the step whose queries start at sb
-    auto prepare = [&](Prep &P, int sb, int i, const F3 &q, float b) {
-      P.i = i; P.qx = q.x; P.qy = q.y; P.qz = q.z;
-      P.active = sb + lane < n_model;
-      P.queryable = P.active && r_lim >= 0.f && isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
-      int u_lo, u_hi, v_lo, v_hi;
-      const bool some = org_window2_flat(og, cul, cuh, cvl, cvh, q.x, q.y, q.z, nn_radius(q.x, q.y, q.z, fminf(b, r_lim)), P.queryable,
-                                         u_lo, u_hi, v_lo, v_hi);
-      // union rectangle, tallest and widest lane window (a lane without a window: one pixel of the union, width 0).  A lane
-      // without a window contributes the crop's far corners -- neutral among real windows, and a step in which NO lane has one
-      // still gets a pixel of the crop as its "union" without a single wave-uniform select (each costs four scalar instructions)
-      int red[6] = {some ? -u_lo : 1 - og.cw, some ? u_hi : 0, some ? -v_lo : 1 - og.ch, some ? v_hi : 0, some ? v_hi - v_lo + 1 : 0,
-                    some ? u_hi - u_lo : 0};
-      wave_max6(red);
-      const int U0 = -red[0], U1 = red[1], V0 = -red[2], V1 = red[3];
-      P.maxh = red[4];
-      P.any = red[4] > 0;                                        // some lane has a window
-      if (!some) { u_lo = u_hi = U0; v_lo = v_hi = V0; }
-      P.u_lo = u_lo; P.u_hi = u_hi; P.v_lo = v_lo; P.v_hi = v_hi;
-      P.nbw = (red[5] >> 2) + 1;                                 // batches of four positions per row: 1 up to width 3, 2 up to 7, ...
-      P.w3 = red[5] <= 2;
-#ifdef FL_ICP_PHASES
-      P.wlmax = red[5];
-#endif
-      const int W = max(U1 - U0 + 1, 1), H = max(V1 - V0 + 1, 1), area = W * H;
-      const int npneed = (area + 3 + 63) >> 6;
-      P.npass = npneed <= 2 ? 2 : npneed;
-      P.staged = P.any && npneed <= ICP_PIPE_NP && small_crop;
-      P.U0 = U0; P.V0 = V0; P.W = W;
-      const float Wf = (float)W, invW = uniform_f(__builtin_amdgcn_rcpf(Wf));
-      const float basef = (float)((int)__umul24((unsigned)P.V0, (unsigned)og.cw) + P.U0);
-      // two passes always, the others in pairs where the rectangle needs them (wave-uniform: with the column-major tiles seven
-      // steps in ten need two)
-      auto ldz = [&](int p) {
-        const SlotPos sp = slot_pos(lanef + (float)(64 * p), Wf, invW, basef);
-        P.z[p] = ld_u32(zimg, P.staged ? min((int)sp.pos, last_pt) : last_pt);
-      };
-      ldz(0);
-      ldz(1);
-      if (P.staged && P.npass > 2) { ldz(2); ldz(3); }
-      if (P.staged && P.npass > 4) { ldz(4); ldz(5); }
-    };
-    // the step itself: rebuild and stage its rectangle, scan, unpack
-    auto finish = [&](const Prep &P, int &j, float &d) {
-      j = -1;
-      d = NAN;
-      if (!P.any) return;
-      const float qx = P.qx, qy = P.qy, qz = P.qz;
-      const int u_lo = P.u_lo, u_hi = P.u_hi, v_lo = P.v_lo, v_hi = P.v_hi, W = P.W, U0 = P.U0, V0 = P.V0, maxh = P.maxh, nbw = P.nbw;
-      const int wl = u_hi - u_lo, hl = v_hi - v_lo;
-#ifdef FL_ICP_PHASES
-      {                                                    // dev: steps, scanned / staged positions, what the lanes' own windows hold
-        int own = P.queryable ? (wl + 1) * (hl + 1) : 0;
-        for (int sft = 32; sft >= 1; sft >>= 1) own += __shfl_xor(own, sft, 64);
-        if (lane == 0) {
-          atomicAdd((unsigned long long *)&S.tacc[8], 1ull);
-          atomicAdd((unsigned long long *)&S.tacc[9], (unsigned long long)((P.w3 ? 3 : 4 * nbw) * maxh));
-          atomicAdd((unsigned long long *)&S.tacc[10], P.staged ? 0ull : 1ull);
-          atomicAdd((unsigned long long *)&S.tacc[11], (unsigned long long)(P.staged ? P.npass * 64 : 0));
-          atomicAdd((unsigned long long *)&S.tacc[12], (unsigned long long)own);     // summed over the 64 lanes
-          atomicAdd(&S.hist[16 + min(maxh, 6) - 1], 1u);   // (bins 22..24 and 26..28 carry the chain phases' stamps)
-          atomicAdd(&S.hist[5 + min(nbw, 3) - 1], 1u);     // bins 5..7: 1, 2, 3+ batches per row
-          atomicAdd(&S.hist[8 + min(P.npass, 4) - 2], 1u); // bins 8..10: 2, 3, 4+ staged passes
-          atomicAdd(&S.stime[min(P.wlmax, 4)], 1ull);      // widest lane window of the step: 1, 2, 3, 4, 5+ pixels
-        }
-      }
-#endif
-      unsigned long long best = NN_KEY_NONE;
-      if (P.staged) {
-        const float Wf = (float)W, invW = uniform_f(__builtin_amdgcn_rcpf(Wf));
-        const float basef = (float)((int)__umul24((unsigned)V0, (unsigned)og.cw) + U0);
-        const float suf = (float)(og.sx0 + U0), svf = (float)(og.sy0 + V0);   // scene pixel of the rectangle's corner
-        auto put = [&](int p) {
-          const SlotPos sp = slot_pos(lanef + (float)(64 * p), Wf, invW, basef);
-          const float zf = P.z[p];
-          const F3 pt = org_point_f(og, suf + sp.col, svf + sp.row, zf);
-          stage[lane + 64 * p] = nn_point(pt.x, pt.y, pt.z, zf != zf ? NN_IDX_NONE : min((int)sp.pos, last_pt));
-        };
-        put(0);
-        put(1);
-        if (P.npass > 2) put(2);
-        if (P.npass > 3) put(3);
-        if (P.npass > 4) { put(4); put(5); }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const float4 *row0 = stage + __mul24(v_lo - V0, W) + (u_lo - U0);
-        if (P.w3) {                                        // (nearly half of the steps: a quarter of their scan saved)
-          for (int dv = 0; dv < maxh; ++dv) {
-            const float4 *bp = row0 + __mul24(min(dv, hl), W);
-            float4 cur[3];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) cur[e] = bp[e];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) NN_CONSIDER(cur[e])
-          }
-        } else if (nbw == 1) {
-          for (int dv = 0; dv < maxh; ++dv) {
-            const float4 *bp = row0 + __mul24(min(dv, hl), W);
-            float4 cur[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) cur[e] = bp[e];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) NN_CONSIDER(cur[e])
-          }
-        } else {
-          const int wlc = max(wl - 3, 0);
-          for (int dv = 0; dv < maxh; ++dv) {
-            const float4 *rowp = row0 + __mul24(min(dv, hl), W);
-            for (int du = 0; du < 4 * nbw; du += 4) {
-              const float4 *bp = rowp + min(du, wlc);
-              float4 cur[4];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) cur[e] = bp[e];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) NN_CONSIDER(cur[e])
-            }
-          }
-        }
-      } else {
-        best = org_scan([&](int idx) { const F3 pt = ld3_u32(rimg, idx); return nn_point(pt.x, pt.y, pt.z, pt.x == INFINITY ? NN_IDX_NONE : idx); },
-                        og.cw, 0, 0, qx, qy, qz, u_lo, u_hi, v_lo, v_hi, 4 * nbw, maxh);
-      }
-      if (P.queryable) NN_UNPACK(best, &j, &d)
-    };
-    int sb0 = wv * 64, sb1 = sb0 + stride, sb2 = sb0 + 2 * stride, sb3 = sb0 + 3 * stride;
-    if (!(sb0 < n_model)) return;
-    int i_c = ld_u32(perm, min(sb0 + lane, last_s));
-    int i_n = ld_u32(perm, min(sb1 + lane, last_s));
-    int i_nn = ld_u32(perm, min(sb2 + lane, last_s));
-    F3 q_c = ld3_u32(mod, i_c), q_n = ld3_u32(mod, i_n);
-    float b_c = bnd_ld(bnd, i_c), b_n = bnd_ld(bnd, i_n);
-    Prep A, B;
-    prepare(A, sb0, i_c, q_c, b_c);
-    bool pend = false, p_active = false;
-    int p_i = 0, p_j = -1;
-    float p_qx = 0.f, p_qy = 0.f, p_qz = 0.f, p_d = NAN;
-    // one step: the results of the step before are stored, the queries of the step after next requested, the NEXT step prepared
-    // (its loads issued), then THIS step finished
-#define ICP_PIPE_STEP(CUR, NXT)                                                                                        \
-    {                                                                                                                  \
-      if (pend) { found(p_active, p_i, p_qx, p_qy, p_qz, p_j, p_d); pend = false; }                                    \
-      const F3 q_nn = ld3_u32(mod, i_nn);                                                                              \
-      const float b_nn = bnd_ld(bnd, i_nn);                                                                            \
-      const int i_nnn = ld_u32(perm, min(sb3 + lane, last_s));                                                         \
-      prepare(NXT, sb1, i_n, q_n, b_n);                                                                                \
-      int j_; float d_;                                                                                                \
-      finish(CUR, j_, d_);                                                                                             \
-      pend = true; p_active = CUR.active; p_i = CUR.i; p_qx = CUR.qx; p_qy = CUR.qy; p_qz = CUR.qz; p_j = j_; p_d = d_; \
-      i_n = i_nn; q_n = q_nn; b_n = b_nn; i_nn = i_nnn;                                                                \
-      sb0 = sb1; sb1 = sb2; sb2 = sb3; sb3 += stride;                                                                  \
-    }
-    for (;;) {
-      ICP_PIPE_STEP(A, B)
-      if (!(sb0 < n_model)) break;
-      ICP_PIPE_STEP(B, A)
-      if (!(sb0 < n_model)) break;
-    }
-#undef ICP_PIPE_STEP
-    if (pend) found(p_active, p_i, p_qx, p_qy, p_qz, p_j, p_d);
-  };
-#define ORG_SEARCH org_search
+  // what the organised searches read (fl_icp_search.h); the pairs they find go to the `found` callables below
+  const OrgSearchCtx ctx = org_search_ctx(mod, bnd, perm, (const float *)sref, (const float *)(wsb + L.zimg), n_model, og);
   // the deferred dist_mean chain of the pending distances (chain wave), then -- every wave -- the search for the next iteration
   auto chain_and_search = [&](const int pend, const bool want, const float r_lim, const float old_mean_) {
     if (pend && threadIdx.x < 64) {
@@ -1706,10 +905,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
         S.px = counter > 0 ? (float)inl / (float)counter : 0.0f;
         if (pend == 2) {
           S.dist_diff = old_mean_ - new_mean;
-          float RT[3];                                   // :793-797
-          mat_vec(S.Ropt, S.T, RT);
-          for (int k = 0; k < 3; ++k) S.T[k] = RT[k] + S.Topt[k];
-          mat_mat(S.Ropt, S.R, S.R);
+          pose_accumulate(S);
         }
         S.dist_mean = new_mean;
         const bool go = (new_mean > dmt) && (S.dist_diff > ddt) && (S.iter < it_thr);       // :684, as the loop head will find it
@@ -1717,7 +913,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       }
     }
     if (want)
-      ORG_SEARCH(r_lim, true, [&](bool active, int i, float, float, float, int j, float d) {
+      org_search<SH, SPEC>(S, ctx, r_lim, true, [&](bool active, int i, float, float, float, int j, float d) {
         if (active) {
           nn[i] = j;
           nd[i] = d;
@@ -1725,7 +921,6 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
         }
       });
   };
-
 
   for (;;) {
     if (SPEC) {
@@ -1753,7 +948,6 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     const float thr = uniform_f(S.thr);
     const int rows = iter == 1 ? n_ref : n_model;
     constexpr bool parity = MODE == FL_ICP_PARITY;
-    constexpr int mode = MODE;
     int kept = 0;
     const bool index_pairs = iter == 1 && !plane;       // :700-704
     // fast and point-to-plane: per-thread partials.  The thread's ~60 terms are summed in float32 (27 registers
@@ -1793,23 +987,20 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       // last time plus the motion since; initially the index pair) bounds the search radius, so a converging
       // cloud visits only a handful of candidates per point; the result is still the exact 1-NN.
       const float r_thr = uniform_f(sqrtf(thr));
-      if (ORG) {
-        constexpr bool PIPE = MODE == FL_ICP_PARITY && NW < 8;
-        auto on_found = [&](bool active, int i, float qx, float qy, float qz, int j, float d) {
-            const bool keep = d <= thr;                       // dists[i][0] <= dist_thr (:268)
-            if (active) {
-              nn[i] = keep ? j : -1;
-              if (j >= 0) bnd_st(bnd, i, sqrt_upper(d));             // else: the old partner is still within the old bound
-            }
-            if (keep) {
-              ++kept;
-              if (!parity) { const F3 rv = ld3_u32(jsrc, j); pair_sums(qx, qy, qz, rv.x, rv.y, rv.z, j); }
-            }
-          };
-        if (!SPEC) {
-          if (PIPE) org_search_pipe(r_thr, on_found);
-          else ORG_SEARCH(r_thr, false, on_found);
+      auto on_found = [&](bool active, int i, float qx, float qy, float qz, int j, float d) {
+        const bool keep = d <= thr;                       // dists[i][0] <= dist_thr (:268)
+        if (active) {
+          nn[i] = keep ? j : -1;
+          if (j >= 0) bnd_st(bnd, i, sqrt_upper(d));      // else: the old partner is still within the old bound
         }
+        if (keep) {
+          ++kept;
+          if (!parity) { const F3 rv = ld3_u32(jsrc, j); pair_sums(qx, qy, qz, rv.x, rv.y, rv.z, j); }
+        }
+      };
+      if (ORG) {
+        if (MODE == FL_ICP_PARITY && NW < 8) org_search_pipe(S, ctx, r_thr, on_found);   // the 256-thread parity kernel
+        else org_search<SH, SPEC>(S, ctx, r_thr, false, on_found);
       } else {
         const NnGrid G = nn_grid(S);
         int i = threadIdx.x;
@@ -1823,13 +1014,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
           float d = NAN;
           if (thr >= 0.f && isfinite(qx) && isfinite(qy) && isfinite(qz))
             nn_search_grid(G, sref, cell_start, qx, qy, qz, nn_radius(qx, qy, qz, fminf(qb, r_thr)), &j, &d);
-          const bool keep = d <= thr;                       // dists[i][0] <= dist_thr (:268)
-          nn[i] = keep ? j : -1;
-          if (j >= 0) bnd_st(bnd, i, sqrt_upper(d));               // else: the old partner is still within qb
-          if (keep) {
-            ++kept;
-            if (!parity) { const F3 rv = ld3_u32(ref, j); pair_sums(qx, qy, qz, rv.x, rv.y, rv.z, j); }
-          }
+          on_found(true, i, qx, qy, qz, j, d);
           qx = nqx; qy = nqy; qz = nqz; qb = nqb;
         }
       }
@@ -1887,7 +1072,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
           // multiplies): exact for every pixel index (the estimate is off by at most one below 2^24 pixels; beyond: divide)
           const int jj = max(w.j, 0);
           int vv, uu;
-          if (small_crop) {
+          if (ctx.small_crop) {
             vv = (int)(((float)jj + 0.5f) * inv_cw);
             uu = jj - __mul24(vv, og.cw);
             if (uu < 0) { --vv; uu += og.cw; } else if (uu >= og.cw) { ++vv; uu -= og.cw; }
@@ -1905,10 +1090,6 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
           for (int b = 0; b < 3; ++b) tile[a * 3 + b][slot] = mm[a] * rr[b];   // (*it_s) * (*it_ref).t()
 #pragma unroll
         for (int q = 0; q < 3; ++q) { tile[9 + q][slot] = mm[q]; tile[12 + q][slot] = rr[q]; }
-      };
-      auto tile_barrier = [&]() {                          // LDS writes of this wave complete, then the workgroup barrier
-        __builtin_amdgcn_s_waitcnt(0xC07F);                // s_waitcnt lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();
       };
       const bool chain_wave = __builtin_amdgcn_readfirstlane(clane) >= 0;
       if (chain_wave) {
@@ -2000,7 +1181,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       __syncthreads();
       continue;
     }
-    if (mode == FL_ICP_PARITY) {
+    if (MODE == FL_ICP_PARITY) {
       if (clane >= 0 && clane < 15) S.sums[clane] = acc;
       __syncthreads();
     } else {
@@ -2009,74 +1190,9 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       for (int k = 0; k < NSUM; ++k) dd[k] = (double)ds[k];
       block_sum_double<NSUM>(S, dd);
     }
-    if (plane) {
-      if (threadIdx.x == 0) {
-        double A[6][6], x[6], tr = 0.0;
-        int q = 0;
-        for (int a = 0; a < 6; ++a)
-          for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = S.dsum[0][q++];
-        for (int a = 0; a < 6; ++a) { x[a] = -S.dsum[0][21 + a]; tr += A[a][a]; }
-        bool ok = tr > 0.0 && tr < 1.0e300;
-        for (int a = 0; a < 6; ++a) A[a][a] += 1.0e-12 * tr;          // keeps a barely constrained direction finite
-        for (int c = 0; c < 6 && ok; ++c) {                            // Cholesky A = L L^T (lower triangle in place)
-          double d = A[c][c];
-          for (int k = 0; k < c; ++k) d -= A[c][k] * A[c][k];
-          if (!(d > 1.0e-13 * tr)) { ok = false; break; }              // a direction the pairs do not constrain
-          d = sqrt(d);
-          A[c][c] = d;
-          for (int r = c + 1; r < 6; ++r) {
-            double v = A[r][c];
-            for (int k = 0; k < c; ++k) v -= A[r][k] * A[c][k];
-            A[r][c] = v / d;
-          }
-        }
-        if (ok) {
-          for (int r = 0; r < 6; ++r) {                                // L y = b
-            double v = x[r];
-            for (int k = 0; k < r; ++k) v -= A[r][k] * x[k];
-            x[r] = v / A[r][r];
-          }
-          for (int r = 5; r >= 0; --r) {                               // L^T x = y
-            double v = x[r];
-            for (int k = r + 1; k < 6; ++k) v -= A[k][r] * x[k];
-            x[r] = v / A[r][r];
-          }
-          // Rodrigues: R = I + (sin t / t) K + ((1 - cos t) / t^2) K^2, K = [omega]x
-          const double wx = x[0], wy = x[1], wz = x[2], t2 = wx * wx + wy * wy + wz * wz, t = sqrt(t2);
-          const double sa = t > 1.0e-9 ? sin(t) / t : 1.0 - t2 / 6.0, sb = t > 1.0e-9 ? (1.0 - cos(t)) / t2 : 0.5 - t2 / 24.0;
-          const double Kx[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-          for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-              double k2 = 0;
-              for (int k = 0; k < 3; ++k) k2 += Kx[i * 3 + k] * Kx[k * 3 + j];
-              S.Ropt[i * 3 + j] = (float)((i == j ? 1.0 : 0.0) + sa * Kx[i * 3 + j] + sb * k2);
-            }
-          for (int k = 0; k < 3; ++k) S.Topt[k] = (float)x[3 + k];
-        }
-        S.ok = ok && finite_all(S.Ropt, 9) && finite_all(S.Topt, 3);
-      }
-    } else
     if (threadIdx.x == 0) {
-      float C[9], mc[3], rc[3];
-      if (mode == FL_ICP_PARITY) {
-        for (int k = 0; k < 9; ++k) C[k] = S.sums[k];
-        for (int k = 0; k < 3; ++k) { mc[k] = S.sums[9 + k] / (float)ncm; rc[k] = S.sums[12 + k] / (float)ncr; }   // getMean :19-24
-      } else {
-        for (int k = 0; k < 9; ++k) C[k] = (float)S.dsum[0][k];
-        for (int k = 0; k < 3; ++k) { mc[k] = (float)(S.dsum[0][9 + k] / ncm); rc[k] = (float)(S.dsum[0][12 + k] / ncr); }
-      }
-      float u[9], vt[9];
-      svd3(C, u, vt);                                    // :742
-      for (int i = 0; i < 3; ++i)                        // R_optimal = Mat(vt.t() * u.t()) :744 (gemm: double acc)
-        for (int j = 0; j < 3; ++j) {
-          double s = 0;
-          for (int k = 0; k < 3; ++k) s += (double)vt[k * 3 + i] * (double)u[j * 3 + k];
-          S.Ropt[i * 3 + j] = (float)s;
-        }
-      float Rm[3];
-      mat_vec(S.Ropt, mc, Rm);
-      for (int k = 0; k < 3; ++k) S.Topt[k] = rc[k] - Rm[k];                      // :747
-      S.ok = finite_all(S.Ropt, 9) && finite_all(S.Topt, 3);                      // checkRange :748
+      if (plane) solve_point_to_plane(S);
+      else solve_rigid<MODE>(S, ncm, ncr);
     }
     __syncthreads();
     TSTAMP(4);
@@ -2095,10 +1211,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     }
     if (threadIdx.x == 0) {
       S.dist_diff = old_mean - S.dist_mean;
-      float RT[3];                                       // :793-797
-      mat_vec(S.Ropt, S.T, RT);
-      for (int k = 0; k < 3; ++k) S.T[k] = RT[k] + S.Topt[k];
-      mat_mat(S.Ropt, S.R, S.R);
+      pose_accumulate(S);
     }
     __syncthreads();
   }
@@ -2154,46 +1267,6 @@ __device__ __forceinline__ void scene_normal(const uint16_t *__restrict__ scene,
   const float len = sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
   if (!(len > 0.f)) return;
   n[0] = c[0] / len; n[1] = c[1] / len; n[2] = c[2] / len;
-}
-
-// dev / tests: scene_normal at n pixels (xy[2 k], xy[2 k + 1]) of a w x h depth image (tests/test_gpu_icp.py checks it against
-// the fp64 restatement in tests/p2plane_model.py)
-__global__ void k_dev_scene_normals(const uint16_t *depth, int w, int h, float fx, float fy, float cx, float cy, const int *xy, int n,
-                                    float *out)
-{
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  float nv[3];
-  scene_normal(depth, w, h, xy[2 * k], xy[2 * k + 1], fx, fy, cx, cy, nv);
-  out[3 * k] = nv[0]; out[3 * k + 1] = nv[1]; out[3 * k + 2] = nv[2];
-}
-
-// host entry for the test: pixels outside the image are refused (scene_normal's window test assumes 0 <= x < w, 0 <= y < h);
-// plain HIP calls on the null stream.  The image is followed by one spare row of zeros, so that a window rule that is off by
-// one reads a zero inside the allocation and the test reports a wrong normal.
-extern "C" int fl_dev_scene_normals(const uint16_t *depth_host, int w, int h, float fx, float fy, float cx, float cy, const int *xy_host,
-                                    int n, float *out_host)
-{
-  if (w <= 0 || h <= 0 || n <= 0 || (long long)w * (h + 1) > (1ll << 28)) return FL_ERR_INVALID;
-  for (int k = 0; k < n; ++k)
-    if (xy_host[2 * k] < 0 || xy_host[2 * k] >= w || xy_host[2 * k + 1] < 0 || xy_host[2 * k + 1] >= h) return FL_ERR_INVALID;
-  const size_t img = sizeof(uint16_t) * (size_t)w * h, pad = sizeof(uint16_t) * (size_t)w;
-  uint16_t *d_depth = nullptr;
-  int *d_xy = nullptr;
-  float *d_out = nullptr;
-  bool ok = hipMalloc(&d_depth, img + pad) == hipSuccess && hipMalloc(&d_xy, 2 * sizeof(int) * (size_t)n) == hipSuccess &&
-            hipMalloc(&d_out, 3 * sizeof(float) * (size_t)n) == hipSuccess;
-  ok = ok && hipMemcpy(d_depth, depth_host, img, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemset((uint8_t *)d_depth + img, 0, pad) == hipSuccess &&
-       hipMemcpy(d_xy, xy_host, 2 * sizeof(int) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_dev_scene_normals, dim3((n + 255) / 256), dim3(256), 0, 0, d_depth, w, h, fx, fy, cx, cy, d_xy, n, d_out);
-    ok = hipGetLastError() == hipSuccess && hipMemcpy(out_host, d_out, 3 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  (void)hipFree(d_depth);
-  (void)hipFree(d_xy);
-  (void)hipFree(d_out);
-  return ok ? FL_OK : FL_ERR_HIP;
 }
 
 template <class SH>
@@ -2352,7 +1425,7 @@ __global__ __launch_bounds__(BS) void k_icp_clouds(IcpArgs a)
   SH &S = *(SH *)icp_smem;
   const IcpWsLayout L = icp_layout(a.n_max);
   uint8_t *wsb = a.ws + (size_t)blockIdx.x * a.ws_stride;
-  const OrgGeom none = {0, 0, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0, 0.f, 0.f, 0.f, 0.f};
+  const OrgGeom none = {};
   if (threadIdx.x == 0) S.cw = 0;                         // the chain wave (IcpSharedT::cw)
   __syncthreads();
   icp_run<MODE, false>(S, wsb, L, a.job.n_ref, a.job.n_model, a.it_thr, a.dmt, a.ddt, &a.results[blockIdx.x].det.icp, none);
@@ -2451,7 +1524,6 @@ void k_icp_pipeline(IcpArgs a)
   // wave-uniform values read from LDS are VGPRs unless told otherwise: the search loop keeps them in SGPRs
   const OrgGeom og = {__builtin_amdgcn_readfirstlane(S.rect_r[2]), __builtin_amdgcn_readfirstlane(S.rect_r[3]),
                       uniform_f((float)S.rect_r[0] - a.cx), uniform_f((float)S.rect_r[1] - a.cy), a.fx, a.fy,
-                      uniform_f((float)(S.rect_r[2] - 1)), uniform_f((float)(S.rect_r[3] - 1)),
                       __builtin_amdgcn_readfirstlane(S.rect_r[0]), __builtin_amdgcn_readfirstlane(S.rect_r[1]), a.cx, a.cy,
                       uniform_f(1.0f / a.fx), uniform_f(1.0f / a.fy)};
   build_tile_order(S, (const int *)((const uint8_t *)rimg + org_idximg_offset(og.cw * og.ch)), og.cw, og.ch, np, (int *)(wsb + L.perm));
@@ -2737,6 +1809,12 @@ static IcpArgs icp_args(uint8_t *ws, int n_max, int it_thr, float dmt, float ddt
   a.mode = mode;
   return a;
 }
+// the scene's frame size and intrinsics (kinds 0, 1)
+static void icp_set_camera(IcpArgs &a, int w, int h, const fl_intrinsics *K)
+{
+  a.w = w; a.h = h;
+  a.fx = (float)K->fx; a.fy = (float)K->fy; a.cx = (float)K->cx; a.cy = (float)K->cy;
+}
 
 // one job (kinds 1, 2) with its result slot at a.results: launch it and read the result back
 static int icp_run_one(fl_context *ctx, const IcpArgs &a, fl_recognition_result *out)
@@ -2822,12 +1900,7 @@ extern "C" int fl_detection(fl_context *ctx, const uint16_t *model_depth, const 
   }
   FL_HIP(ctx, hipMemsetAsync(dres, 0, sizeof(*dres), ctx->stream));
   IcpArgs a = icp_args(wsb, n_max, icp_it_thr, dist_mean_thr, dist_diff_thr, icp_mode);
-  a.w = w;
-  a.h = h;
-  a.fx = (float)K->fx;
-  a.fy = (float)K->fy;
-  a.cx = (float)K->cx;
-  a.cy = (float)K->cy;
+  icp_set_camera(a, w, h, K);
   a.job.kind = 1;
   for (int k = 0; k < 4; ++k) { a.job.rect_model[k] = rect_model[k]; a.job.rect_ref[k] = rect_ref[k]; }
   for (int k = 0; k < 9; ++k) a.job.r_match[k] = r_match[k];
@@ -2877,12 +1950,7 @@ int fl_launch_detection_tables(fl_context *ctx, const FlDetectionTables &t, int 
 {
   IcpArgs a = icp_args(ws, t.n_pts_max, p->icp_it_thr, p->dist_mean_thr, p->dist_diff_thr, p->icp_mode);
   a.ws_stride = ws_stride;
-  a.w = t.w;
-  a.h = t.h;
-  a.fx = (float)K->fx;
-  a.fy = (float)K->fy;
-  a.cx = (float)K->cx;
-  a.cy = (float)K->cy;
+  icp_set_camera(a, t.w, t.h, K);
   a.job.kind = 0;
   a.frame_ws = t.frame_ws;
   a.frame_stride = t.frame_stride;
@@ -2908,4 +1976,72 @@ int fl_launch_detection_tables(fl_context *ctx, const FlDetectionTables &t, int 
     a.order = t.icp_order;
   }
   return icp_launch(ctx, n_jobs, a);
+}
+
+// ---- dev / test entries ----
+extern "C" unsigned fl_dev_bnd_pack(unsigned bits) { return bnd_pack(bits); }      // for tests/test_abi_cpu.py (host arithmetic, no GPU)
+// dev / tests: both reductions on one wavefront of inputs (tests/test_gpu_icp.py checks them against each other and numpy)
+__global__ void k_dev_wave_max6(const int *in, int *out)
+{
+  int a[6], b[6];
+  for (int k = 0; k < 6; ++k) a[k] = b[k] = in[k * 64 + threadIdx.x];
+  wave_max6(a);
+  wave_max_multi(b);
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 6; ++k) { out[k] = a[k]; out[6 + k] = b[k]; }
+}
+
+// host entry for the test: 6 x 64 ints in, 6 (wave_max6) + 6 (wave_max_multi) out; plain HIP calls on the null stream
+extern "C" int fl_dev_wave_max6(const int *in_host, int *out_host)
+{
+  int *d_in = nullptr, *d_out = nullptr;
+  if (hipMalloc(&d_in, 6 * 64 * sizeof(int)) != hipSuccess || hipMalloc(&d_out, 12 * sizeof(int)) != hipSuccess) { (void)hipFree(d_in); return FL_ERR_HIP; }
+  bool ok = hipMemcpy(d_in, in_host, 6 * 64 * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_dev_wave_max6, dim3(1), dim3(64), 0, 0, d_in, d_out);
+    ok = hipGetLastError() == hipSuccess && hipMemcpy(out_host, d_out, 12 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  (void)hipFree(d_in);
+  (void)hipFree(d_out);
+  return ok ? FL_OK : FL_ERR_HIP;
+}
+
+// dev / tests: scene_normal at n pixels (xy[2 k], xy[2 k + 1]) of a w x h depth image (tests/test_gpu_icp.py checks it against
+// the fp64 restatement in tests/p2plane_model.py)
+__global__ void k_dev_scene_normals(const uint16_t *depth, int w, int h, float fx, float fy, float cx, float cy, const int *xy, int n,
+                                    float *out)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  float nv[3];
+  scene_normal(depth, w, h, xy[2 * k], xy[2 * k + 1], fx, fy, cx, cy, nv);
+  out[3 * k] = nv[0]; out[3 * k + 1] = nv[1]; out[3 * k + 2] = nv[2];
+}
+
+// host entry for the test: pixels outside the image are refused (scene_normal's window test assumes 0 <= x < w, 0 <= y < h);
+// plain HIP calls on the null stream.  The image is followed by one spare row of zeros, so that a window rule that is off by
+// one reads a zero inside the allocation and the test reports a wrong normal.
+extern "C" int fl_dev_scene_normals(const uint16_t *depth_host, int w, int h, float fx, float fy, float cx, float cy, const int *xy_host,
+                                    int n, float *out_host)
+{
+  if (w <= 0 || h <= 0 || n <= 0 || (long long)w * (h + 1) > (1ll << 28)) return FL_ERR_INVALID;
+  for (int k = 0; k < n; ++k)
+    if (xy_host[2 * k] < 0 || xy_host[2 * k] >= w || xy_host[2 * k + 1] < 0 || xy_host[2 * k + 1] >= h) return FL_ERR_INVALID;
+  const size_t img = sizeof(uint16_t) * (size_t)w * h, pad = sizeof(uint16_t) * (size_t)w;
+  uint16_t *d_depth = nullptr;
+  int *d_xy = nullptr;
+  float *d_out = nullptr;
+  bool ok = hipMalloc(&d_depth, img + pad) == hipSuccess && hipMalloc(&d_xy, 2 * sizeof(int) * (size_t)n) == hipSuccess &&
+            hipMalloc(&d_out, 3 * sizeof(float) * (size_t)n) == hipSuccess;
+  ok = ok && hipMemcpy(d_depth, depth_host, img, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemset((uint8_t *)d_depth + img, 0, pad) == hipSuccess &&
+       hipMemcpy(d_xy, xy_host, 2 * sizeof(int) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_dev_scene_normals, dim3((n + 255) / 256), dim3(256), 0, 0, d_depth, w, h, fx, fy, cx, cy, d_xy, n, d_out);
+    ok = hipGetLastError() == hipSuccess && hipMemcpy(out_host, d_out, 3 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  (void)hipFree(d_depth);
+  (void)hipFree(d_xy);
+  (void)hipFree(d_out);
+  return ok ? FL_OK : FL_ERR_HIP;
 }
