@@ -40,17 +40,14 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
   const float p3 = -0.3258083974640975f * (float)(180 / 3.14159265358979323846);
   const float p5 = 0.1555786518463281f * (float)(180 / 3.14159265358979323846);
   const float p7 = -0.04432655554792128f * (float)(180 / 3.14159265358979323846);
-  float ax = fabsf(x), ay = fabsf(y);
-  float a, c, c2;
-  if (ax >= ay) {
-    c = ay / (ax + (float)DBL_EPSILON);
-    c2 = c * c;
-    a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-  } else {
-    c = ax / (ay + (float)DBL_EPSILON);
-    c2 = c * c;
-    a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-  }
+  const float ax = fabsf(x), ay = fabsf(y);
+  // ax >= ay: c = ay / (ax + eps), a = poly(c); else c = ax / (ay + eps), a = 90 - poly(c) -- the same operations on swapped
+  // operands, so one division and one polynomial serve both (as two branches a wave with lanes of both kinds ran each in turn)
+  const bool steep = !(ax >= ay);
+  const float c = (steep ? ax : ay) / ((steep ? ay : ax) + (float)DBL_EPSILON);
+  const float c2 = c * c;
+  const float poly = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+  float a = steep ? 90.f - poly : poly;
   if (x < 0) a = 180.f - a;
   if (y < 0) a = 360.f - a;
   return a;
@@ -73,17 +70,99 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
 // ds_bpermute + index arithmetic of __shfl_up / __shfl_down; lane 0 / lane 63 keep their own value, as those do.
 __device__ __forceinline__ unsigned wave_from_prev(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xF, 0xF, false); }
 __device__ __forceinline__ unsigned wave_from_next(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130, 0xF, 0xF, false); }
+// the same where lane 0 / lane 63 may receive anything (0): no copy of v into the destination first
+__device__ __forceinline__ unsigned wave_from_prev0(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true); }
+__device__ __forceinline__ unsigned wave_from_next0(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, true); }
 
-__device__ __forceinline__ void cq_hrow(const uint8_t *__restrict__ src, int w, int h, int row, int xc, bool interior,
+// The 7-pixel window of a lane, fetched as 4-byte aligned dwords (a 16-byte load costs 28-32 cycles per wave-instruction at
+// 4-byte alignment and 70-76 at byte alignment or a 3-byte lane stride: tools/probes/ldwidth.hip).
+// The window starts at pixel first = clamp(xc - 3, 0, w - 7), i.e. it lies inside the row for every lane of an image at
+// least 7 wide; its 21 bytes begin row_mis + 3 * first bytes behind the row's address rounded down to a multiple of 4
+// (row_mis: the row address's low two bits).  Whatever that sum's low two bits are, the 21 bytes lie inside the six aligned
+// dwords from *off on, the first of which holds the window's first byte and the last of which its byte 20 - shift: no dword
+// without a byte of the window is read, so nothing in front of a frame's first row or behind its last one is touched.
+// *shift is what v_alignbyte_b32 takes to move the window to byte 0.
+__host__ __device__ __forceinline__ void cq_window_addr(uint32_t row_mis, int w, int xc, uint32_t *off, uint32_t *shift, int *first)
+{
+  const int f = xc - 3 < 0 ? 0 : (xc - 3 > w - 7 ? w - 7 : xc - 3);
+  const uint32_t o = row_mis + 3u * (uint32_t)f;
+  *off = o & ~3u;
+  *shift = o & 3u;
+  *first = f;
+}
+
+// ({hi, lo} >> 8 * (s & 3)), low dword: v_alignbyte_b32
+__host__ __device__ __forceinline__ uint32_t cq_alignbyte(uint32_t hi, uint32_t lo, uint32_t s)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_alignbyte(hi, lo, s);
+#else
+  return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (s & 3u)));
+#endif
+}
+
+// wd[0..5]: bytes 3 t + ch of it are tap t (column clamp(xc + t - 3, 0, w - 1), BORDER_REPLICATE) of channel ch; bytes 21..23
+// are not defined.  row4 is the row's address rounded down to a multiple of 4.  Two loads in every lane.  The lanes within 3
+// columns of an image edge (and the ones beside the image, whose xc is the edge column) have dpx = xc - 3 - first != 0: their
+// taps are the window moved by dpx pixels with the edge pixel repeated.  The waves that hold such lanes (any_left / any_right,
+// wave-uniform) rebuild it: the edge pixel's three bytes continue the window as a 12-byte pattern of period 3 on that side, and
+// every lane takes its six dwords out of that stream at byte 12 + 3 dpx (left) or 3 dpx (right) -- a select per bit of the dword
+// index and an alignbyte; lanes with dpx == 0 keep their window.
+__host__ __device__ __forceinline__ void cq_window(const uint8_t *__restrict__ row4, uint32_t row_mis, int w, int xc, bool any_left,
+                                                   bool any_right, uint32_t *wd)
+{
+  uint32_t off, shift;
+  int first;
+  cq_window_addr(row_mis, w, xc, &off, &shift, &first);
+  const int dpx = xc - 3 - first;
+  uint32_t d[6];
+  const uint8_t *q = (const uint8_t *)__builtin_assume_aligned(row4 + off, 4);
+  __builtin_memcpy(d, q, 16);
+  __builtin_memcpy(d + 4, q + 16, 8);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) wd[k] = cq_alignbyte(d[k + 1], d[k], shift);
+  wd[5] = cq_alignbyte(d[5], d[5], shift);                // byte 20 of the window arrives; 21..23 carry no tap
+  // (the selects are written out on named values: over arrays the compiler turns them into indexed loads from scratch)
+#define CQ_TAKE(e0, e1, e2, e3, e4, e5, e6, e7, e8)                                                                                 \
+  {                                                                                                                                 \
+    const bool b0 = (dw & 1u) != 0u, b1 = (dw & 2u) != 0u;                                                                          \
+    const uint32_t t0 = b0 ? e1 : e0, t1 = b0 ? e2 : e1, t2 = b0 ? e3 : e2, t3 = b0 ? e4 : e3, t4 = b0 ? e5 : e4, t5 = b0 ? e6 : e5, \
+                   t6 = b0 ? e7 : e6, t7 = b0 ? e8 : e7;                                                                            \
+    const uint32_t g0 = b1 ? t2 : t0, g1 = b1 ? t3 : t1, g2 = b1 ? t4 : t2, g3 = b1 ? t5 : t3, g4 = b1 ? t6 : t4, g5 = b1 ? t7 : t5; \
+    wd[0] = cq_alignbyte(g1, g0, s);                                                                                                \
+    wd[1] = cq_alignbyte(g2, g1, s);                                                                                                \
+    wd[2] = cq_alignbyte(g3, g2, s);                                                                                                \
+    wd[3] = cq_alignbyte(g4, g3, s);                                                                                                \
+    wd[4] = cq_alignbyte(g5, g4, s);                                                                                                \
+    wd[5] = cq_alignbyte(g5, g5, s);                                                                                                \
+  }
+  if (any_left) {
+    const uint32_t s = dpx < 0 ? (uint32_t)-dpx : 0u, dw = 3u - s;         // stream byte 12 - 3 s = dword 3 - s, byte s
+    const uint32_t p = wd[0] & 0xFFFFFFu;                                  // pixel 0: B | G << 8 | R << 16
+    // stream bytes 0..11: B G R B | G R B G | R B G R, then the window
+    CQ_TAKE((p | (p << 24)), ((p >> 8) | (p << 16)), ((p >> 16) | (p << 8)), wd[0], wd[1], wd[2], wd[3], wd[4], wd[5])
+  }
+  if (any_right) {
+    const uint32_t n = dpx > 0 ? 3u * (uint32_t)dpx : 0u, dw = n >> 2, s = n & 3u;     // stream byte 3 dpx = dword dw, byte s
+    const uint32_t p = (wd[4] >> 16) | ((wd[5] & 0xFFu) << 16);            // pixel 6 (bytes 18..20)
+    // the window, whose bytes 20..31 become R B G R | B G R B | G R B G (the ninth dword is read by no lane: dw <= 2)
+    CQ_TAKE(wd[0], wd[1], wd[2], wd[3], wd[4], ((p >> 16) | (p << 8)), (p | (p << 24)), ((p >> 8) | (p << 16)), 0u)
+  }
+#undef CQ_TAKE
+}
+
+// Horizontal [8 28 56 72 56 28 8] sums of a row's three channels at column xc.  kNarrow (w < 8): a tap at a time.
+template <bool kNarrow>
+__device__ __forceinline__ void cq_hrow(const uint8_t *__restrict__ src, int w, int h, int row, int xc, bool any_left, bool any_right,
                                         int *h3)
 {
   const int kk[7] = {8, 28, 56, 72, 56, 28, 8};
-  const uint8_t *p = src + (size_t)clampi(row, 0, h - 1) * w * 3;
+  const uint8_t *p = src + (size_t)clampi(row, 0, h - 1) * (size_t)(w * 3);          // wave-uniform: scalar arithmetic
   int a0 = 0, a1 = 0, a2 = 0;
-  if (interior) {          // wave-uniform: no tap of any lane is clamped and 24 bytes are readable
+  if (!kNarrow) {
+    const uint32_t mis = (uint32_t)(uintptr_t)p & 3u;
     uint32_t wd[6];
-    __builtin_memcpy(wd, p + 3 * (xc - 3), 16);
-    __builtin_memcpy(wd + 4, p + 3 * (xc - 3) + 16, 8);
+    cq_window(p - mis, mis, w, xc, any_left, any_right, wd);
     // the 7 taps of a channel sit at bytes 3 t + ch of the 24-byte window: per dword one v_dot4_u32_u8 against a constant
     // word that holds the tap weights at this channel's byte positions (0 elsewhere) -- 6 dot products per channel instead of
     // 7 byte extractions + 7 multiply-adds; integer arithmetic, the same sums (<= 255 * 256)
@@ -97,7 +176,7 @@ __device__ __forceinline__ void cq_hrow(const uint8_t *__restrict__ src, int w, 
 #pragma unroll
         for (int t = 0; t < 7; ++t)
           if (((3 * t + ch) >> 2) == k) wk |= (unsigned)kk[t] << (8 * ((3 * t + ch) & 3));
-        acc[ch] = __builtin_amdgcn_udot4(wd[k], wk, acc[ch], false);
+        if (wk != 0u) acc[ch] = __builtin_amdgcn_udot4(wd[k], wk, acc[ch], false);     // (dword 5 holds a tap of channel 2 only)
       }
     a0 = (int)acc[0]; a1 = (int)acc[1]; a2 = (int)acc[2];
 #else
@@ -123,20 +202,38 @@ __device__ __forceinline__ void cq_hrow(const uint8_t *__restrict__ src, int w, 
   h3[2] = a2;
 }
 
+// for tests/test_cq_window_cpu.py (host arithmetic, no GPU): the window addressing, and the taps cq_window makes of a row
+extern "C" void fl_dev_cq_window_addr(unsigned row_mis, int w, int xc, unsigned *off, unsigned *shift, int *first)
+{
+  cq_window_addr(row_mis, w, xc, off, shift, first);
+}
+extern "C" void fl_dev_cq_window_taps(const uint8_t *row4, unsigned row_mis, int w, int xc, int any_left, int any_right, uint8_t *taps21)
+{
+  uint32_t wd[6];
+  cq_window(row4, row_mis, w, xc, any_left != 0, any_right != 0, wd);
+  for (int b = 0; b < 21; ++b) taps21[b] = (uint8_t)(wd[b >> 2] >> (8 * (b & 3)));
+}
+
 #ifndef FL_CQ_WPE
-#define FL_CQ_WPE 6              // 80 VGPRs, no spills: 6 waves per SIMD (measured: 5 -> 6 gives -2 % front-end time, 7/8 spill)
+#define FL_CQ_WPE 6              // 6 waves per SIMD (measured: 5 -> 6 gives -2 % front-end time).  The kernel now holds 58 VGPRs: 7 and 8
+                                 // fit without spills and were measured at 0 / -0.09 ms (level 1 / tiled level 0), profiles/README.md
 #endif
 // kMag (template extraction): frame z's squared gradient magnitude goes to mag_out + z * out_stride floats, i.e. the
 // magnitude images have the quantised images' pitch in elements.  The front-end of the recognition path launches
 // k_color_quantize<false>, whose mag_out is null there.
-template <bool kMag>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, FL_CQ_WPE))) void k_color_quantize(const uint8_t *__restrict__ bgr, size_t in_stride,
+// The 7-row ring trades roles by unrolling: seven steps make the loop body, step P writes the new source row into slot P and
+// reads the window from slot P + 1 on, so no row is moved.  Virtual rows above the image's first row and below its last one
+// have the window of that row (the window does not advance there): those steps, at most two at either end, push the
+// smoothed pixels of the step before into the 3-row rings again.
+template <bool kMag, bool kNarrow>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kNarrow ? 6 : FL_CQ_WPE, kNarrow ? 6 : FL_CQ_WPE))) void k_color_quantize(const uint8_t *__restrict__ bgr, size_t in_stride,
                                                         uint8_t *__restrict__ dst, size_t out_stride, int w, int h,
                                                         float threshold_sq, int nstrips, int nchunks, int chunk_rows,
                                                         float *__restrict__ mag_out, const uint32_t *__restrict__ tiles,
                                                         size_t tiles_stride)
 {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // the wave index is the same in all 64 lanes: as a scalar it keeps the strip, the rows and the row addresses on the scalar unit
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + wave;
   if (item >= nstrips * nchunks) return;
   const int strip = item % nstrips, chunk = item / nstrips;
@@ -156,42 +253,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, 
   // taps and for Sobel's BORDER_REPLICATE on the *smoothed* image alike (linemod.cpp:247-249)
   const int xc = clampi(x, 0, w - 1);
   const int y0 = max(chunk * chunk_rows, row_lo), y1 = min(min(h, chunk * chunk_rows + chunk_rows), row_hi + 1);
-  const bool interior = __all(xc >= 3 && xc <= w - 5);
+  if (y0 >= y1) return;                                  // no row to write
+  // the waves that hold lanes within 3 columns of an image edge (lane 0 is column strip * CQ_COLS - 2, lane 63 + 61)
+  const bool any_left = strip == 0, any_right = strip * CQ_COLS + 61 > w - 4;
 
   int H[7][3];
-  int center = clampi(y0 - 2, 0, h - 1);
+  {
+    const int center = clampi(y0 - 2, 0, h - 1);
 #pragma unroll
-  for (int i = 0; i < 7; ++i) cq_hrow(src, w, h, center + i - 3, xc, interior, H[i]);
+    for (int i = 0; i < 7; ++i) cq_hrow<kNarrow>(src, w, h, center + i - 3, xc, any_left, any_right, H[i]);
+  }
   uint32_t Sl[3] = {0, 0, 0}, Sc[3] = {0, 0, 0}, Sr[3] = {0, 0, 0};
   uint32_t Qp[3] = {0, 0, 0};
   float Mg[3] = {0.f, 0.f, 0.f};
-  for (int yv = y0 - 2; yv <= y1 + 1; ++yv) {
-    const int c = clampi(yv, 0, h - 1);
-    if (c != center) {                                 // advance the 7-row window by one source row
+  // vertical pass over the window whose first row is in slot p + the single rounding of the 8-bit GaussianBlur:
+  // (acc + 2^15) >> 16.  H <= 255 * 256, so every product fits 24 bits: __umul24 is a full-rate multiply where the generic
+  // 32-bit one runs at quarter rate; the kernel is symmetric, so 4 multiplies per channel instead of 7.  The smoothed pixel
+  // (B | G << 8 | R << 16) and its neighbours' enter the 3-row rings.
+  auto smooth = [&](int p) __attribute__((always_inline)) {
+    uint32_t vv[3];
 #pragma unroll
-      for (int i = 0; i < 6; ++i) { H[i][0] = H[i + 1][0]; H[i][1] = H[i + 1][1]; H[i][2] = H[i + 1][2]; }
-      cq_hrow(src, w, h, c + 3, xc, interior, H[6]);
-      center = c;
-    }
-    // vertical pass + the single rounding of the 8-bit GaussianBlur: (acc + 2^15) >> 16
-    // H <= 255 * 256, so every product fits 24 bits: __umul24 is a full-rate multiply where the generic 32-bit one
-    // runs at quarter rate; the kernel is symmetric, so 4 multiplies per channel instead of 7
-    int v0, v1, v2;
-    {
-      int vv[3];
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch)
-        vv[ch] = (int)(__umul24(8u, (unsigned)(H[0][ch] + H[6][ch])) + __umul24(28u, (unsigned)(H[1][ch] + H[5][ch])) +
-                       __umul24(56u, (unsigned)(H[2][ch] + H[4][ch])) + __umul24(72u, (unsigned)H[3][ch]));
-      v0 = vv[0]; v1 = vv[1]; v2 = vv[2];
-    }
-    const uint32_t S = (uint32_t)((v0 + (1 << 15)) >> 16) | ((uint32_t)((v1 + (1 << 15)) >> 16) << 8) |
-                       ((uint32_t)((v2 + (1 << 15)) >> 16) << 16);
-    const uint32_t L = wave_from_prev(S), R = wave_from_next(S);
+    for (int ch = 0; ch < 3; ++ch)
+      vv[ch] = __umul24(8u, (unsigned)(H[p % 7][ch] + H[(p + 6) % 7][ch])) + __umul24(28u, (unsigned)(H[(p + 1) % 7][ch] + H[(p + 5) % 7][ch])) +
+               __umul24(56u, (unsigned)(H[(p + 2) % 7][ch] + H[(p + 4) % 7][ch])) + __umul24(72u, (unsigned)H[(p + 3) % 7][ch]);
+    const uint32_t S = (uint32_t)(((int)vv[0] + (1 << 15)) >> 16) | ((uint32_t)(((int)vv[1] + (1 << 15)) >> 16) << 8) |
+                       ((uint32_t)(((int)vv[2] + (1 << 15)) >> 16) << 16);
+    // lanes 0 and 63 have no such neighbour: what they get reaches their own label only, which feeds the votes of lanes 0, 1
+    // and 62, 63 -- halo lanes that store nothing
+    const uint32_t L = wave_from_prev0(S), R = wave_from_next0(S);
     Sl[0] = Sl[1]; Sl[1] = Sl[2]; Sl[2] = L;
     Sc[0] = Sc[1]; Sc[1] = Sc[2]; Sc[2] = S;
     Sr[0] = Sr[1]; Sr[1] = Sr[2]; Sr[2] = R;
-    if (yv < y0) continue;                             // wave-uniform
+  };
+  auto again = [&]() __attribute__((always_inline)) {     // a virtual row outside the image: the smoothed row of the step before
+    Sl[0] = Sl[1]; Sl[1] = Sl[2];
+    Sc[0] = Sc[1]; Sc[1] = Sc[2];
+    Sr[0] = Sr[1]; Sr[1] = Sr[2];
+  };
+  // what follows the smoothed row of virtual row yv: Sobel at yv - 1, the vote and the store at yv - 2
+  auto finish = [&](int yv) __attribute__((always_inline)) {
+    if (yv < y0) return;                               // wave-uniform
     // Sobel 3x3 at row ys = yv - 1 (rings hold virtual rows ys-1, ys, ys+1), strongest channel,
     // fastAtan2, 16 bins (:248-303, :314)
     const int ys = yv - 1;
@@ -222,10 +323,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, 
     // counter word of its own label, the row sum x-1, x, x+1 is formed once and kept for three rows
     const uint32_t q = inside ? (uint32_t)(qi & 7) : 0u;
     const uint32_t oh = 1u << (4 * q);
-    const uint32_t ohl = wave_from_prev(oh), ohr = wave_from_next(oh);
+    const uint32_t ohl = wave_from_prev0(oh), ohr = wave_from_next0(oh);
     Qp[0] = Qp[1]; Qp[1] = Qp[2]; Qp[2] = oh + ohl + ohr;
     Mg[0] = Mg[1]; Mg[1] = Mg[2]; Mg[2] = (float)bmag;
-    if (yv < y0 + 2) continue;
+    if (yv < y0 + 2) return;
     // 3x3 majority vote at row yo = yv - 2 (:337-384)
     const int yo = yv - 2;
     if (lane >= 2 && lane < 2 + CQ_COLS && x < w && yo < y1) {
@@ -242,6 +343,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_CQ_WPE, 
       if (kMag) mag_out[(size_t)blockIdx.z * out_stride + (size_t)yo * w + x] = Mg[1];
       else if (mag_out) mag_out[(size_t)yo * w + x] = Mg[1];
     }
+  };
+
+  // virtual rows y0 - 2 .. y1 + 1.  The first one has the window that was just loaded; rows <= 0 keep it; rows 1 .. h - 1 take
+  // one new source row each; rows >= h keep the last window.
+  const int ylast = y1 + 1, yadv = min(ylast, h - 1);
+  int yv = y0 - 2;
+  smooth(0);                                             // yv < y0: nothing follows
+  for (++yv; yv <= min(ylast, 0); ++yv) {
+    again();
+    finish(yv);
+  }
+  for (;;) {
+#pragma unroll
+    for (int P = 0; P < 7; ++P) {
+      if (yv > yadv) goto below;
+      cq_hrow<kNarrow>(src, w, h, yv + 3, xc, any_left, any_right, H[P]);
+      smooth(P + 1);
+      finish(yv);
+      ++yv;
+    }
+  }
+below:
+  for (; yv <= ylast; ++yv) {
+    again();
+    finish(yv);
   }
 }
 
@@ -276,19 +402,23 @@ static_assert(CQ_COLS == FL_TILE && CQ_CH == FL_TILE, "the lazy tile grid is k_c
 static int launch_color_quantize(fl_context *ctx, const uint8_t *bgr, size_t in_stride, uint8_t *dst, size_t out_stride, int n_frames,
                                  int w, int h, float weak_threshold, float *mag_out, const uint32_t *tiles, size_t tiles_stride)
 {
-  static long per_cu[2] = {0, 0};
+  static long per_cu[4] = {0, 0, 0, 0};
   const int nstrips = (w + CQ_COLS - 1) / CQ_COLS;
-  const int rows = tiles ? CQ_CH
-                         : fl_eager_chunk_rows(ctx, mag_out ? waves_per_cu(k_color_quantize<true>, &per_cu[1]) : waves_per_cu(k_color_quantize<false>, &per_cu[0]),
-                                               nstrips, n_frames, h);
-  const int nchunks = (h + rows - 1) / rows;
-  dim3 grid((nstrips * nchunks + 3) / 4, 1, n_frames);
-  if (mag_out)
-    hipLaunchKernelGGL(k_color_quantize<true>, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h,
-                       weak_threshold * weak_threshold, nstrips, nchunks, rows, mag_out, tiles, tiles_stride);
-  else
-    hipLaunchKernelGGL(k_color_quantize<false>, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h,
-                       weak_threshold * weak_threshold, nstrips, nchunks, rows, mag_out, tiles, tiles_stride);
+  const bool narrow = w < 8;                             // no 7-pixel window inside a row to load: a tap at a time
+  auto launch = [&](auto kernel, long *cache) {
+    const int rows = tiles ? CQ_CH : fl_eager_chunk_rows(ctx, waves_per_cu(kernel, cache), nstrips, n_frames, h);
+    const int nchunks = (h + rows - 1) / rows;
+    dim3 grid((nstrips * nchunks + 3) / 4, 1, n_frames);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, bgr, in_stride, dst, out_stride, w, h, weak_threshold * weak_threshold,
+                       nstrips, nchunks, rows, mag_out, tiles, tiles_stride);
+  };
+  if (mag_out) {
+    if (narrow) launch(k_color_quantize<true, true>, &per_cu[3]);
+    else launch(k_color_quantize<true, false>, &per_cu[1]);
+  } else {
+    if (narrow) launch(k_color_quantize<false, true>, &per_cu[2]);
+    else launch(k_color_quantize<false, false>, &per_cu[0]);
+  }
   FL_HIP(ctx, hipGetLastError());
   return FL_OK;
 }
