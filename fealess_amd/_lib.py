@@ -185,6 +185,7 @@ DEV_SIGNATURES = {
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_cq_window_addr": (None, [C.c_uint, _I, _I, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_I)]),
     "fl_dev_cq_window_taps": (None, [_P, C.c_uint, _I, _I, _I, _I, _P]),
+    "fl_dev_scan_items": (_I, [_P, _I, _I, _I, C.c_uint, _P, _I, _P, _I, _P]),
 }
 
 

@@ -98,7 +98,7 @@ int fl_icp_stream(fl_context *ctx, hipStream_t *out)
 extern "C" int fl_abi_version(void) { return FL_ABI_VERSION; }
 
 // name, environment variable, field, environment value in hex, accepted values lo .. hi (icp_occ: 0, 4 or 5;
-// frontend_chunk_rows: multiples of 60)
+// frontend_chunk_rows: multiples of 60; scan_run: 0 = automatic)
 struct FlOptionName { const char *name, *env; long fl_context::Options::*field; bool hex; long lo, hi; };
 static const FlOptionName fl_option_names[] = {
   {"scan_prune", "FL_SCAN_PRUNE", &fl_context::Options::scan_prune, false, 0, 1},
@@ -112,6 +112,7 @@ static const FlOptionName fl_option_names[] = {
   {"ws_pad", "FL_DEV_WS_PAD", &fl_context::Options::ws_pad, false, 0, 16l << 20},
   {"pipeline_icp", "FL_PIPELINE_ICP", &fl_context::Options::pipeline_icp, false, 0, 3},
   {"frontend_chunk_rows", "FL_FRONTEND_CHUNK_ROWS", &fl_context::Options::frontend_chunk_rows, false, 0, 60 * 1024},
+  {"scan_run", "FL_SCAN_RUN", &fl_context::Options::scan_run, false, 0, 64},
 };
 
 // A value outside an option's range is refused rather than taken for "default": a forced kernel variant with a mistyped
@@ -250,7 +251,6 @@ extern "C" int fl_detector_create(fl_context *ctx, int modalities, int levels, c
 
 static void free_device_tables(fl_detector *det)
 {
-  (void)hipFree(det->d_scan_hdr);
   (void)hipFree(det->d_scan_items);
   (void)hipFree(det->d_scan_off);
   (void)hipFree(det->d_fine_hdr);
@@ -258,21 +258,21 @@ static void free_device_tables(fl_detector *det)
   (void)hipFree(det->d_pyr);
   (void)hipFree(det->d_poses);
   (void)hipFree(det->d_class_first);
-  (void)hipFree(det->d_pyr_enabled);
+  (void)hipFree(det->d_item_enabled);
   (void)hipFree((void *)det->d_depth_ptrs);
   (void)hipFree(det->d_ws);
   (void)hipFree(det->d_results);
   if (det->h_results) (void)hipHostFree(det->h_results);
-  det->d_scan_hdr = nullptr;
   det->d_scan_items = nullptr;
   det->n_scan_items = 0;
+  det->scan_item_g.clear();
   det->d_scan_off = nullptr;
   det->d_fine_hdr = nullptr;
   det->d_fine_feat = nullptr;
   det->d_pyr = nullptr;
   det->d_poses = nullptr;
   det->d_class_first = nullptr;
-  det->d_pyr_enabled = nullptr;
+  det->d_item_enabled = nullptr;
   det->d_depth_ptrs = nullptr;
   det->d_ws = nullptr;
   det->d_results = nullptr;
@@ -394,6 +394,59 @@ static int upload(fl_context *ctx, const std::vector<T> &v, T **out)
   return FL_OK;
 }
 
+// k_scan's work list: one item per (pyramid, chunk of 1024 coarse positions) -- only the chunks some modality's
+// template_positions reach (a 160-pixel template at VGA level 1 has P = 831 of 1200 cells: its second chunk is empty).
+// scan_off gains FL_SCAN_OFF_PAD zero offsets: the kernel requests the next group of eight while it adds the current one,
+// behind a bank's last group too.
+void fl_build_scan_items(const std::vector<FlScanHdr> &hdr, int n_pyr, int M, int WH, uint32_t zero_off, std::vector<uint32_t> &scan_off,
+                         std::vector<FlScanItem> &items)
+{
+  const int nchunks = (WH + 1023) / 1024;
+  scan_off.insert(scan_off.end(), FL_SCAN_OFF_PAD, zero_off);
+  items.clear();
+  for (int g = 0; g < n_pyr; ++g) {
+    int pmax = 0, nf_all = 0;
+    for (int m = 0; m < M; ++m) {
+      pmax = std::max(pmax, (int)hdr[(size_t)g * M + m].P);
+      nf_all += hdr[(size_t)g * M + m].nf;
+    }
+    for (int c = 0; c < nchunks && (c == 0 || c * 1024 < pmax); ++c) {    // chunk 0 always: the debug tap zero-fills through it
+      FlScanItem it;
+      it.g = g;
+      it.chunk_nf = (uint32_t)c | ((uint32_t)nf_all << 16);
+      for (int m = 0; m < FL_MAX_MODALITIES; ++m) {
+        const FlScanHdr h = m < M ? hdr[(size_t)g * M + m] : FlScanHdr{0, 0, 0, 0};
+        it.mod[m].P = h.P;
+        it.mod[m].off_begin = h.off_begin;
+        it.mod[m].npad_nf = (uint32_t)h.n_pad | ((uint32_t)h.nf << 16);
+      }
+      const FlScanHdr h0 = hdr[(size_t)g * M];
+      for (int u = 0; u < 8; ++u) it.off0[u] = h0.n_pad > 0 ? scan_off[(size_t)h0.off_begin + u] : zero_off;
+      items.push_back(it);
+    }
+  }
+}
+
+// fl_build_scan_items on caller-supplied headers (hdr: n_pyr * M entries of {P, off_begin, n_pad, nf}) and offsets, for
+// tests/test_scan_items_cpu.py: items_out receives up to cap_items records of 16 words, offs_out the padded offset table
+// (n_offs + FL_SCAN_OFF_PAD entries).  Returns the number of items, or FL_ERR_INVALID.  Host arithmetic, no GPU.
+extern "C" int fl_dev_scan_items(const int32_t *hdr, int n_pyr, int M, int WH, uint32_t zero_off, const uint32_t *offs, int n_offs,
+                                 uint32_t *items_out, int cap_items, uint32_t *offs_out)
+{
+  if (!hdr || !offs || !items_out || !offs_out || n_pyr < 0 || M < 1 || M > FL_MAX_MODALITIES || WH < 1 || n_offs < 0) return FL_ERR_INVALID;
+  std::vector<FlScanHdr> h((size_t)n_pyr * M);
+  for (size_t i = 0; i < h.size(); ++i) {
+    h[i] = FlScanHdr{hdr[4 * i], hdr[4 * i + 1], hdr[4 * i + 2], hdr[4 * i + 3]};
+    if (h[i].n_pad < 0 || h[i].n_pad % 8 || h[i].off_begin < 0 || (long)h[i].off_begin + h[i].n_pad > n_offs) return FL_ERR_INVALID;
+  }
+  std::vector<uint32_t> so(offs, offs + n_offs);
+  std::vector<FlScanItem> items;
+  fl_build_scan_items(h, n_pyr, M, WH, zero_off, so, items);
+  for (size_t i = 0; i < items.size() && (int)i < cap_items; ++i) memcpy(items_out + 16 * i, &items[i], sizeof(FlScanItem));
+  memcpy(offs_out, so.data(), so.size() * sizeof(uint32_t));
+  return (int)items.size();
+}
+
 // Detector::match's class_ids (linemod.cpp:1418-1434): empty = every class; otherwise only the listed classes
 // that exist are matched (unknown ids are ignored, repeats change nothing after sort + unique).
 int fl_apply_class_filter(fl_detector *det)
@@ -405,9 +458,13 @@ int fl_apply_class_filter(fl_detector *det)
     for (size_t k = 0; k < det->class_filter.size(); ++k) on = on || det->class_filter[k] == det->classes[ci].id;
     en.insert(en.end(), (size_t)det->classes[ci].n_pyramids, on ? 1 : 0);
   }
-  if (en.empty()) return FL_OK;
-  if (!det->d_pyr_enabled) FL_HIP(ctx, hipMalloc((void **)&det->d_pyr_enabled, en.size()));
-  FL_HIP(ctx, hipMemcpyAsync(det->d_pyr_enabled, en.data(), en.size(), hipMemcpyHostToDevice, ctx->stream));
+  // k_scan reads the flag of a work item, not of a pyramid, as a byte of an aligned dword on the scalar side: it is
+  // requested together with the item's record instead of behind it
+  if (det->scan_item_g.empty()) return FL_OK;            // before fl_detector_finalize: it applies the filter
+  std::vector<uint8_t> item_en(fl_align(det->scan_item_g.size(), 4), 0);
+  for (size_t i = 0; i < det->scan_item_g.size(); ++i) item_en[i] = en[(size_t)det->scan_item_g[i]];
+  if (!det->d_item_enabled) FL_HIP(ctx, hipMalloc((void **)&det->d_item_enabled, item_en.size()));
+  FL_HIP(ctx, hipMemcpyAsync(det->d_item_enabled, item_en.data(), item_en.size(), hipMemcpyHostToDevice, ctx->stream));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return FL_OK;
 }
@@ -661,18 +718,12 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
   det->scan_bytes_per_frame = scan_bytes;
 
   int rc;
-  if ((rc = upload(ctx, scan_hdr, &det->d_scan_hdr))) return rc;
   {
-    // k_scan's work list: one wave per (pyramid, chunk of 1024 coarse positions) -- only the chunks some modality's
-    // template_positions reach (a 160-pixel template at VGA level 1 has P = 831 of 1200 cells: its second chunk is empty)
-    std::vector<int2> items;
-    const int nchunks = (det->geom[L - 1].WH + 1023) / 1024;
-    for (int g = 0; g < g_idx; ++g) {
-      int pmax = 0;
-      for (int m = 0; m < M; ++m) pmax = std::max(pmax, (int)scan_hdr[(size_t)g * M + m].P);
-      for (int c = 0; c < nchunks && (c == 0 || c * 1024 < pmax); ++c) items.push_back(make_int2(g, c));   // chunk 0 always: the debug tap zero-fills through it
-    }
+    std::vector<FlScanItem> items;
+    fl_build_scan_items(scan_hdr, g_idx, M, det->geom[L - 1].WH, det->geom[L - 1].zero_off, scan_off, items);
     det->n_scan_items = (int)items.size();
+    det->scan_item_g.clear();
+    for (const FlScanItem &it : items) det->scan_item_g.push_back(it.g);
     if ((rc = upload(ctx, items, &det->d_scan_items))) return rc;
   }
   if ((rc = upload(ctx, scan_off, &det->d_scan_off))) return rc;

@@ -46,6 +46,8 @@ struct fl_context {
                                 // slots the long ICP launch frees, profiles/README.md)
     long frontend_chunk_rows = 0;   // FL_FRONTEND_CHUNK_ROWS: output rows a wave of the whole-image quantiser launches walks; 0 = 120 where
                                 // the launch still fills the device several times over, else 60; a multiple of 60 is used as given
+    long scan_run = 0;          // FL_SCAN_RUN: work items a wave of k_scan walks; 0 = FL_SCAN_RUN_AUTO where the launch still fills the
+                                // device several times over, else a shorter run (fl_scan_run); 1 .. 64 is used as given
   } opt;
   int detectors = 0;            // live fl_detector objects on this context
   bool destroy_pending = false; // fl_context_destroy was called while detectors were alive: the last one releases the context
@@ -80,6 +82,25 @@ struct FlScanHdr {       // one per (pyramid g, modality m) at the coarsest leve
   int32_t n_pad;         // entries, padded to a multiple of 8 with the zero offset
   int32_t nf;            // templ.features.size() (counts skipped features too)
 };
+// k_scan's work item: everything a wave needs of a (pyramid, 1024-position chunk) before its first vector load, in 64
+// bytes: one dword per lane of a single load, the first group's offsets in the lanes a later group's offsets arrive in.  Built by fl_build_scan_items from the FlScanHdr entries: it depends on the bank and the
+// geometry only.
+struct FlScanItem {
+  uint32_t off0[8];      // the first 8-offset group of modality 0 (the zero offset where it has none)
+  int32_t g;             // pyramid
+  uint32_t chunk_nf;     // chunk | (features of all modalities << 16)
+  struct {
+    int32_t P;           // FlScanHdr::P
+    int32_t off_begin;   // FlScanHdr::off_begin
+    uint32_t npad_nf;    // FlScanHdr::n_pad | (FlScanHdr::nf << 16)
+  } mod[FL_MAX_MODALITIES];
+};
+static_assert(sizeof(FlScanItem) == 64 && FL_MAX_MODALITIES == 2, "a dword per lane of a 16-lane load");
+#define FL_SCAN_OFF_PAD 8   // entries behind the last group of the offset table: k_scan requests a group ahead of the one it adds
+// The work list of a bank: one item per (pyramid, chunk some modality's template_positions reach; chunk 0 always), pyramid
+// major.  Appends FL_SCAN_OFF_PAD zero offsets to scan_off.  Host code only (tests/test_scan_items_cpu.py: fl_dev_scan_items).
+void fl_build_scan_items(const std::vector<FlScanHdr> &hdr, int n_pyr, int M, int WH, uint32_t zero_off, std::vector<uint32_t> &scan_off,
+                         std::vector<FlScanItem> &items);
 struct FlFineFeat {      // one per feature at the finer levels (12 bytes)
   int16_t x, y;          // template-relative position
   int16_t qx, qy;        // floor(x / T), floor(y / T)
@@ -159,15 +180,15 @@ struct fl_detector {
   FlLevelGeom geom[FL_MAX_LEVELS];
 
   // device tables
-  FlScanHdr *d_scan_hdr = nullptr;       // n_pyr * M
-  int2 *d_scan_items = nullptr;          // (pyramid g, 1024-position chunk) pairs that have positions to scan: k_scan's work list
+  FlScanItem *d_scan_items = nullptr;    // (pyramid g, 1024-position chunk) pairs that have positions to scan: k_scan's work list
   int n_scan_items = 0;
-  uint32_t *d_scan_off = nullptr;
+  std::vector<int32_t> scan_item_g;      // the items' pyramids on the host (fl_apply_class_filter)
+  uint32_t *d_scan_off = nullptr;        // every (pyramid, modality)'s offsets, padded to groups of 8, + FL_SCAN_OFF_PAD
   FlFineHdr *d_fine_hdr = nullptr;       // n_pyr * (L-1) * M, index (g*(L-1)+l)*M+m
   FlFineFeat *d_fine_feat = nullptr;
   FlPyrInfo *d_pyr = nullptr;            // n_pyr
   int *d_class_first = nullptr;          // first global pyramid index of each class
-  uint8_t *d_pyr_enabled = nullptr;      // n_pyr: 0 = its class is excluded by the class filter of match()
+  uint8_t *d_item_enabled = nullptr;     // per work item, padded to whole dwords: 0 = its pyramid's class is excluded by the class filter of match()
   std::vector<std::string> class_filter; // empty = all classes (Detector::match's class_ids)
   float *d_poses = nullptr;              // n_pyr * 13 (zeros when absent)
   const uint16_t **d_depth_ptrs = nullptr; // n_pyr pointers to model depth (0.1mm) or null

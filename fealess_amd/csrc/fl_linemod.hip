@@ -288,7 +288,7 @@ int fl_launch_build_lm(fl_context *ctx, const uint8_t *quant, size_t quant_strid
 }
 
 // ------------------------------------------------------------------------------------------
-// k_scan: one wavefront per (pyramid, 1024-position chunk, frame).  Lane i owns 16 consecutive
+// k_scan: one wavefront per run of (pyramid, 1024-position chunk) work items of a frame.  Lane i owns 16 consecutive
 // positions and keeps their u8 partial sums packed in four 32-bit registers per modality:
 // with <= 63 features of response <= 4 a byte never carries (63*4 = 252, linemod.cpp:1133-1137),
 // so one 32-bit add sums four positions.  Feature offsets are wave-uniform (scalar loads), padded
@@ -297,22 +297,31 @@ int fl_launch_build_lm(fl_context *ctx, const uint8_t *quant, size_t quant_strid
 // templates and are served from L2; the feature tables are the only per-template HBM stream.
 // Between the modalities and after every 8 features a wave whose positions can no longer reach the coarse threshold stops
 // (exact: see `prune` in the kernel); the reference adds every feature of every template everywhere (linemod.cpp:1471-1481).
+//
+// With pruning most items end after 16 of up to 126 features, and what such an item costs is not its bytes but the chain
+// of dependent memory round trips in front of them.  So everything an item needs before its first vector load is one
+// 64-byte record (FlScanItem, built at finalize: it depends on the bank and the geometry only) with the first eight
+// offsets inline; the class filter's flag is a byte per ITEM, requested with the record; a wave walks `run` items
+// (ScanArgs::run, fl_scan_run) and requests the next item's record and flag before it works on the current one; and
+// inside an item the next group's eight offsets -- the next modality's first group behind a modality's last -- are
+// requested before the current group's vector loads are waited for.  An early-pruned item then costs the two vector
+// round trips of its two groups; the record, the flag and the offsets arrive underneath them.
 struct ScanArgs {
-  const FlScanHdr *hdr;
-  const int2 *items;         // work list: (pyramid, chunk)
+  const FlScanItem *items;   // work list: one record per (pyramid, chunk)
   int n_items;
-  const uint32_t *offs;
-  const uint8_t *enabled;    // per pyramid: class selected by match()'s class_ids (linemod.cpp:1418-1434)
+  const uint32_t *offs;      // FL_SCAN_OFF_PAD entries behind the last group
+  const uint8_t *enabled;    // per work item, whole dwords: class selected by match()'s class_ids (linemod.cpp:1418-1434)
   uint8_t *ws;               // frame workspace base
   size_t ws_stride;
   size_t lm_off[FL_MAX_MODALITIES];
   size_t off_count, off_cand;
-  int n_pyr, M, nchunks, W, WH, T, cap;
+  int M, W, WH, T, cap;
   int bpf, n_frames;         // blocks per frame, frames in this launch
+  int run, wave_step, item_step;   // wave w of a frame walks the items w * wave_step + i * item_step, i < run
   float threshold;
   int prune;                 // stop a (template, chunk) between modalities once no position can reach the threshold (exact)
   unsigned prune_mid;        // ... and inside a modality after the 8-feature groups whose bit is set (same bound, same exactness)
-  uint16_t *dbg;             // optional raw u16 maps of pyramids [dbg_first, dbg_first+dbg_count)
+  uint16_t *dbg;             // optional raw u16 maps of pyramids [dbg_first, dbg_first+dbg_count); null: dbg_count = 0
   int dbg_first, dbg_count;
 };
 
@@ -330,15 +339,34 @@ __device__ __forceinline__ uint4 ld16(const uint8_t *p)
   __builtin_memcpy(&v, p, 16);     // global_load_dwordx4, any byte alignment (unaligned access mode)
   return v;
 }
+// a wave-uniform load of memory no kernel in flight writes: s_load_dword whatever stores the loop holds
+#define FL_CONST_AS __attribute__((address_space(4)))
+__device__ __forceinline__ uint32_t sload1(const void *p) { return *(const FL_CONST_AS uint32_t *)(uintptr_t)p; }
+// What the loop keeps in flight for later -- the next item's record and flag, the next group's offsets -- travels in ONE vector
+// register each, a dword per lane, and is taken apart with v_readlane when its turn comes: sixteen and eight scalar registers
+// held across an item were more than the scalar file has beside the group in work (the compiler then issued a group's loads
+// one at a time).  Vector loads return in order, so the wait for a group's own loads covers the request issued before them.
+__device__ __forceinline__ uint32_t rl(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
 #ifndef FL_SCAN_PRUNE_MID
 #define FL_SCAN_PRUNE_MID 0x7Fu   // 8-feature groups after which a modality checks the bound (every one but the last: the check
                                   // after 16 features is the one that pays -- chunks without colour edges stop there)
 #endif
-#ifndef FL_SCAN_WPE
-#define FL_SCAN_WPE 5             // waves per SIMD; measured after the DPP change (ms per 1280 frames x 360 templates): 3: 2.32, 4: 1.95, 5: 1.71, 6: 1.77, 8: 2.17
+#ifndef FL_SCAN_OFFSETS_AHEAD
+#define FL_SCAN_OFFSETS_AHEAD 1   // 0 (comparison builds): every group fetches its own offsets first, a second round trip per group
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_SCAN_WPE, FL_SCAN_WPE))) void k_scan(ScanArgs a)
+// Waves per SIMD.  Without pruning the kernel is bound by the rate of its vector loads and five waves are the optimum (measured
+// after the DPP change, ms per 1280 frames x 360 templates: 3: 2.32, 4: 1.95, 5: 1.71, 6: 1.77, 8: 2.17).  With pruning an item is
+// two or three round trips and little else, the launch is bound by how many of them are in flight, and six beat five
+// (profiles/README.md): the same code built twice, the launch picks by ScanArgs::prune.
+#ifndef FL_SCAN_WPE
+#define FL_SCAN_WPE 5
+#endif
+#ifndef FL_SCAN_WPE_PRUNED
+#define FL_SCAN_WPE_PRUNED 6
+#endif
+template <int WPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_scan(ScanArgs a)
 {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // XCD-aware block mapping: workgroups are dealt round-robin over the 8 XCDs, each with its own
@@ -348,136 +376,195 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FL_SCAN_WPE
   const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
   const int frame = xcd + 8 * (q / a.bpf);
   if (frame >= a.n_frames) return;
-  const int item = __builtin_amdgcn_readfirstlane((q % a.bpf) * 4 + wave);
-  if (item >= a.n_items) return;
-  const int2 gc = a.items[item];
-  const int g = __builtin_amdgcn_readfirstlane(gc.x), chunk = __builtin_amdgcn_readfirstlane(gc.y);
-  if (!a.enabled[g]) return;                             // wave-uniform: matchClass is not called for this class
-  uint8_t *ws = a.ws + (size_t)frame * a.ws_stride;
-  const int j0 = chunk * 1024 + lane * 16;
+  int it = __builtin_amdgcn_readfirstlane(((q % a.bpf) * 4 + wave) * a.wave_step);
+  if (it >= a.n_items) return;
+  // lanes 0..15: the dwords of item `idx`'s record; the others: the dword that holds its class-filter flag
+  const int l7 = lane & 7;
+  auto request_item = [&](int idx) {
+    const uint32_t *p = lane < 16 ? (const uint32_t *)(a.items + idx) + lane : (const uint32_t *)(a.enabled + (idx & ~3));
+    return *p;
+  };
+  uint32_t rec = request_item(it);
+  const uint8_t *lm[FL_MAX_MODALITIES];                  // the frame's linear memories
+  for (int m = 0; m < FL_MAX_MODALITIES; ++m) lm[m] = a.ws + (size_t)frame * a.ws_stride + a.lm_off[m];
+  const float thr100 = a.threshold / 100.f;
+  const unsigned lane_off = (unsigned)lane * 16u;
+  const int dbg_first = a.dbg_first;
+  const unsigned dbg_count = (unsigned)a.dbg_count;
+  // What only an item with candidates or a tapped one needs is read from the kernel arguments when it is needed: in scalar
+  // registers for the whole loop it would crowd out the offsets and records the loop keeps in flight.
+  const FL_CONST_AS ScanArgs *ka = (const FL_CONST_AS ScanArgs *)__builtin_amdgcn_kernarg_segment_ptr();
 
-  uint32_t tot[16];
+  // One work item.  `return` = on to the wave's next item; every per-item value starts from zero in here.
+  auto scan_item = [&](const uint32_t r) {
+    const int g = (int)rl(r, 8), chunk = (int)(rl(r, 9) & 0xFFFFu), nf_all = (int)(rl(r, 9) >> 16);
+    const int rP[FL_MAX_MODALITIES] = {(int)rl(r, 10), (int)rl(r, 13)}, rB[FL_MAX_MODALITIES] = {(int)rl(r, 11), (int)rl(r, 14)};
+    const uint32_t rN[FL_MAX_MODALITIES] = {rl(r, 12), rl(r, 15)};
+    const int j0 = chunk * 1024 + lane * 16;
+
+    uint32_t tot[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) tot[i] = 0;
-  // Exact pruning between modalities: a feature adds at most 4 to a position (SIMILARITY_LUT's largest entry), so once the
-  // largest total of this wave's 1024 positions plus 4 x (the features of the modalities still to come) cannot exceed the
-  // coarse threshold, no position of the chunk can become a candidate (`raw > raw_threshold`, linemod.cpp:1490-1492) and the
-  // rest of the template's additions have no observable effect: the wave stops.  The colour modality comes first and is
-  // sparse (gradients only on edges), so on most (template, chunk) pairs the depth modality -- half of the scan's loads -- is
-  // never read.  The same bound is checked inside a modality after the 8-feature groups a.prune_mid names (chunks without
-  // colour edges stop after 16 features).  Not when the raw maps are tapped (fl_similarity_maps), and FL_SCAN_PRUNE=0
-  // switches it off (a.prune).
-  int nf_all = 0;
-  for (int m = 0; m < a.M; ++m) nf_all += a.hdr[g * a.M + m].nf;
-  const int prune_threshold = (int)(2 * nf_all + (a.threshold / 100.f) * (2 * nf_all) + 0.5f);   // = raw_threshold below
-  const bool prune = a.prune && !(a.dbg && g >= a.dbg_first && g < a.dbg_first + a.dbg_count);
-  int nf = 0;
-  for (int m = 0; m < a.M; ++m) {
-    const FlScanHdr h = a.hdr[g * a.M + m];
-    uint32_t mx_tot = 0;                                 // the lane's largest total of the modalities done
-    if (prune && m > 0) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mx_tot = max(mx_tot, tot[i]);
-      if (__ballot((int)mx_tot + 4 * (nf_all - nf) > prune_threshold) == 0ull) return;    // wave-uniform
-    }
+    for (int i = 0; i < 16; ++i) tot[i] = 0;
+    // Exact pruning between modalities: a feature adds at most 4 to a position (SIMILARITY_LUT's largest entry), so once the
+    // largest total of this wave's 1024 positions plus 4 x (the features of the modalities still to come) cannot exceed the
+    // coarse threshold, no position of the chunk can become a candidate (`raw > raw_threshold`, linemod.cpp:1490-1492) and the
+    // rest of the template's additions have no observable effect: the item ends.  The colour modality comes first and is
+    // sparse (gradients only on edges), so on most (template, chunk) pairs the depth modality -- half of the scan's loads -- is
+    // never read.  The same bound is checked inside a modality after the 8-feature groups a.prune_mid names (chunks without
+    // colour edges stop after 16 features).  Not when the raw maps are tapped (fl_similarity_maps), and FL_SCAN_PRUNE=0
+    // switches it off (a.prune).
+    const int prune_threshold = (int)(2 * nf_all + thr100 * (2 * nf_all) + 0.5f);   // = raw_threshold below
+    const bool tapped = (unsigned)(g - dbg_first) < dbg_count;
+    const bool prune = a.prune && !tapped;
     const unsigned mid = prune ? a.prune_mid : 0u;
-    nf += h.nf;
-    if (chunk * 1024 >= h.P) continue;                  // wave-uniform; lanes past P load along (masked below): the
-                                                       // next lane's first dword is this lane's bytes 16..19
-    const uint8_t *lm_u = ws + a.lm_off[m] + chunk * 1024;   // lane 0's bytes: wave-uniform
-    const unsigned lane_off = (unsigned)lane * 16u;
-    // descriptor over the frame's linear memories from 4 bytes below this chunk on (scalar offsets stay positive)
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(lm_u - 4), 0, 0x7FFFFFFF, 0x00020000);
-    uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    const uint32_t *offs = a.offs + h.off_begin;
-    // A feature's 16 bytes start at an arbitrary byte.  A byte-aligned 16-byte load costs ~2.4x a 4-byte aligned one
-    // on gfx950 (tools/probes/ldwidth.hip) and this loop is bound by exactly those loads, so each feature is fetched as
-    // an aligned 16 + 4 bytes and shifted into place with four v_alignbyte (the misalignment is wave-uniform).
-    // The extra 4 bytes are the next lane's first dword: one DPP wave shift instead of a second vector load; lane 63's
-    // come from a wave-uniform address, i.e. a scalar load.
-    const unsigned lm_mis = (unsigned)(size_t)lm_u & 3u;  // same for every lane (lane * 16): keep it a scalar
-    // Only the lanes whose 16 positions start below template_positions have anything to add (P = 831 of the 1024 positions
-    // of a chunk for a 160-pixel template at VGA level 1: 52 of 64 lanes); one more lane stays on because its first dword is
-    // the previous lane's bytes 16..19.  The condition is a contiguous lane range, i.e. one EXEC mask around the whole loop --
-    // not a select per load (measured in round 1: that serialised the eight loads in flight) -- and the masked lanes' loads
-    // are simply not issued: 19 % less L2 traffic.
-    const int lanes_on = min(64, ((h.P - chunk * 1024 + 15) >> 4) + 1);
-    const bool on = lane < lanes_on;
-    for (int k = 0; k < h.n_pad; k += 8) {
-      if (on) {
-      uint4 v[8];
-      uint32_t e[8];
-      unsigned mis[8];
+    // the group of eight offsets in flight (lanes 0..7) and where in a.offs it is from: the record brings modality 0's first
+    uint32_t ov = r;
+    int o_at = (rN[0] & 0xFFFFu) ? rB[0] : -1;
+    int nf = 0;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const unsigned off = offs[k + u];
-        mis[u] = (lm_mis + off) & 3u;
-        // buffer_load ... v_lane_off, s[rsrc], s_feature_off offen: the lane's byte offset is one loop-invariant VGPR and the
-        // feature's offset a scalar operand -- no per-lane 64-bit address arithmetic (it was 2 of the 10 VALU instructions
-        // per feature)
-        const u32x4 ld = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, off - mis[u] + 4u, 0);   // 4-byte aligned
-        v[u] = make_uint4(ld.x, ld.y, ld.z, ld.w);
-        const uint32_t tail = *(const uint32_t *)__builtin_assume_aligned(lm_u + off - mis[u] + 1024, 4);
-        e[u] = (uint32_t)__builtin_amdgcn_update_dpp((int)tail, (int)v[u].x, 0x130, 0xF, 0xF, false);   // wave_shl:1
-      }
+    for (int m = 0; m < FL_MAX_MODALITIES; ++m) {
+      if (m >= a.M) break;
+      const int P = rP[m], off_begin = rB[m], n_pad = (int)(rN[m] & 0xFFFFu), h_nf = (int)(rN[m] >> 16);
+      uint32_t mx_tot = 0;                                 // the lane's largest total of the modalities done
+      if (prune && m > 0) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        a0 += __builtin_amdgcn_alignbyte(v[u].y, v[u].x, mis[u]);
-        a1 += __builtin_amdgcn_alignbyte(v[u].z, v[u].y, mis[u]);
-        a2 += __builtin_amdgcn_alignbyte(v[u].w, v[u].z, mis[u]);
-        a3 += __builtin_amdgcn_alignbyte(e[u], v[u].w, mis[u]);
+        for (int i = 0; i < 16; ++i) mx_tot = max(mx_tot, tot[i]);
+        if (__ballot((int)mx_tot + 4 * (nf_all - nf) > prune_threshold) == 0ull) return;    // wave-uniform
       }
+      nf += h_nf;
+      if (chunk * 1024 >= P) continue;                    // wave-uniform; lanes past P load along (masked below): the
+                                                         // next lane's first dword is this lane's bytes 16..19
+      const uint8_t *lm_u = lm[m] + chunk * 1024;         // lane 0's bytes: wave-uniform
+      // descriptor over the frame's linear memories from 4 bytes below this chunk on (scalar offsets stay positive)
+      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(lm_u - 4), 0, 0x7FFFFFFF, 0x00020000);
+      uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+      // A feature's 16 bytes start at an arbitrary byte.  A byte-aligned 16-byte load costs ~2.4x a 4-byte aligned one
+      // on gfx950 (tools/probes/ldwidth.hip) and this loop is bound by exactly those loads, so each feature is fetched as
+      // an aligned 16 + 4 bytes and shifted into place with four v_alignbyte (the misalignment is wave-uniform).
+      // The extra 4 bytes are the next lane's first dword: one DPP wave shift instead of a second vector load; lane 63's
+      // come from a wave-uniform address, i.e. a scalar load.
+      const unsigned lm_mis = (unsigned)(size_t)lm_u & 3u;  // same for every lane (lane * 16): keep it a scalar
+      // Only the lanes whose 16 positions start below template_positions have anything to add (P = 831 of the 1024 positions
+      // of a chunk for a 160-pixel template at VGA level 1: 52 of 64 lanes); one more lane stays on because its first dword is
+      // the previous lane's bytes 16..19.  The condition is a contiguous lane range, i.e. one EXEC mask around the whole loop --
+      // not a select per load (measured in round 1: that serialised the eight loads in flight) -- and the masked lanes' loads
+      // are simply not issued: 19 % less L2 traffic.
+      const int lanes_on = min(64, ((P - chunk * 1024 + 15) >> 4) + 1);
+      const bool on = lane < lanes_on;
+      // behind this modality's last group the next modality's first is requested (whether or not that one then runs)
+      const int next_begin = rB[m + 1 < FL_MAX_MODALITIES ? m + 1 : m];
+      for (int k = 0; k < n_pad; k += 8) {
+        const int at = off_begin + k;
+        if (o_at != at) ov = a.offs[at + l7];              // rare: the modality before this one added nothing in this chunk
+        // The group after this one, requested before this group's vector loads are waited for: a group costs one memory
+        // round trip, not two.  Past a bank's last group this reads the table's FL_SCAN_OFF_PAD entries; an offset beyond
+        // n_pad is never turned into a load.
+        const int nxt_at = k + 8 < n_pad ? at + 8 : next_begin;
+        const uint32_t nxt = a.offs[nxt_at + l7];
+        uint32_t o[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) o[u] = rl(ov, u);
+        if (on) {
+        uint4 v[8];
+        uint32_t e[8];
+        unsigned mis_all = 0;                              // the eight misalignments, four bits each: one scalar register
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const unsigned off = o[u];
+          const unsigned mis_u = (lm_mis + off) & 3u;
+          mis_all |= mis_u << (4 * u);
+          // buffer_load ... v_lane_off, s[rsrc], s_feature_off offen: the lane's byte offset is one loop-invariant VGPR and the
+          // feature's offset a scalar operand -- no per-lane 64-bit address arithmetic (it was 2 of the 10 VALU instructions
+          // per feature)
+          const u32x4 ld = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, off - mis_u + 4u, 0);   // 4-byte aligned
+          v[u] = make_uint4(ld.x, ld.y, ld.z, ld.w);
+          const uint32_t tail = sload1(lm_u + off - mis_u + 1024);
+          e[u] = (uint32_t)__builtin_amdgcn_update_dpp((int)tail, (int)v[u].x, 0x130, 0xF, 0xF, false);   // wave_shl:1
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const unsigned mis_u = (mis_all >> (4 * u)) & 3u;
+          a0 += __builtin_amdgcn_alignbyte(v[u].y, v[u].x, mis_u);
+          a1 += __builtin_amdgcn_alignbyte(v[u].z, v[u].y, mis_u);
+          a2 += __builtin_amdgcn_alignbyte(v[u].w, v[u].z, mis_u);
+          a3 += __builtin_amdgcn_alignbyte(e[u], v[u].w, mis_u);
+        }
+        asm volatile("" :: "v"(nxt));                      // (keeps the request above in front of this group's loads)
+        }
+        ov = nxt;
+        o_at = FL_SCAN_OFFSETS_AHEAD ? nxt_at : -1;
+        if ((mid >> (k >> 3)) & 1u) {                      // wave-uniform
+          // the same bound inside the modality: the lane's largest byte so far on top of its largest finished total
+          // (an over-estimate of its largest partial total, so nothing reachable is ever dropped)
+          const u16x2 b0 = pk_bytes_max(a0), b1 = pk_bytes_max(a1), b2 = pk_bytes_max(a2), b3 = pk_bytes_max(a3);
+          const u16x2 bm = __builtin_elementwise_max(__builtin_elementwise_max(b0, b1), __builtin_elementwise_max(b2, b3));
+          const int part = (int)max(bm.x, bm.y);
+          const int left = nf_all - nf + max(0, h_nf - (k + 8));
+          // (every lane votes: one past this modality's template_positions adds nothing here, its bound is simply generous --
+          // it may still collect from a modality whose template_positions reach further)
+          if (__ballot((int)mx_tot + part + 4 * left > prune_threshold) == 0ull) return;          // wave-uniform
+        }
       }
-      if ((mid >> (k >> 3)) & 1u) {                      // wave-uniform
-        // the same bound inside the modality: the lane's largest byte so far on top of its largest finished total
-        // (an over-estimate of its largest partial total, so nothing reachable is ever dropped)
-        const u16x2 b0 = pk_bytes_max(a0), b1 = pk_bytes_max(a1), b2 = pk_bytes_max(a2), b3 = pk_bytes_max(a3);
-        const u16x2 bm = __builtin_elementwise_max(__builtin_elementwise_max(b0, b1), __builtin_elementwise_max(b2, b3));
-        const int part = (int)max(bm.x, bm.y);
-        const int left = nf_all - nf + max(0, h.nf - (k + 8));
-        // (every lane votes: one past this modality's template_positions adds nothing here, its bound is simply generous --
-        // it may still collect from a modality whose template_positions reach further)
-        if (__ballot((int)mx_tot + part + 4 * left > prune_threshold) == 0ull) return;          // wave-uniform
+      const uint32_t acc[4] = {a0, a1, a2, a3};
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        uint32_t byte = (acc[i >> 2] >> ((i & 3) * 8)) & 0xFFu;
+        tot[i] += (j0 + i < P) ? byte : 0u;          // cells >= template_positions stay 0 (:1160)
       }
     }
-    const uint32_t acc[4] = {a0, a1, a2, a3};
+    if (tapped) {
+      const FL_CONST_AS ScanArgs *kr = ka;
+      asm volatile("" : "+s"(kr));
+      const int WH = kr->WH;
+      uint16_t *d = kr->dbg + ((size_t)frame * dbg_count + (g - dbg_first)) * WH;
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (j0 + i < WH) d[j0 + i] = (uint16_t)tot[i];
+    }
+    // coarse threshold (linemod.cpp:1483-1506), float expression evaluated as written
+    const int raw_threshold = (int)(2 * nf + thr100 * (2 * nf) + 0.5f);
+    uint32_t mx = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mx = max(mx, tot[i]);
+    if ((int)mx <= raw_threshold) return;
+    const FL_CONST_AS ScanArgs *kr = ka;
+    asm volatile("" : "+s"(kr));
+    const int W = kr->W, WH = kr->WH, T = kr->T, cap = kr->cap;
+    uint8_t *ws = kr->ws + (size_t)frame * kr->ws_stride;
+    int *count = (int *)(ws + kr->off_count);
+    FlCand *cand = (FlCand *)(ws + kr->off_cand);
+    const int offset = T / 2 + (T % 2 - 1);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      uint32_t byte = (acc[i >> 2] >> ((i & 3) * 8)) & 0xFFu;
-      tot[i] += (j0 + i < h.P) ? byte : 0u;        // cells >= template_positions stay 0 (:1160)
-    }
-  }
-  if (a.dbg && g >= a.dbg_first && g < a.dbg_first + a.dbg_count) {
-    uint16_t *d = a.dbg + ((size_t)frame * a.dbg_count + (g - a.dbg_first)) * a.WH;
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (j0 + i < a.WH) d[j0 + i] = (uint16_t)tot[i];
-  }
-  // coarse threshold (linemod.cpp:1483-1506), float expression evaluated as written
-  const int raw_threshold = (int)(2 * nf + (a.threshold / 100.f) * (2 * nf) + 0.5f);
-  uint32_t mx = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) mx = max(mx, tot[i]);
-  if ((int)mx <= raw_threshold) return;
-  int *count = (int *)(ws + a.off_count);
-  FlCand *cand = (FlCand *)(ws + a.off_cand);
-  const int offset = a.T / 2 + (a.T % 2 - 1);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int raw = (int)tot[i];
-    const int j = j0 + i;
-    if (raw > raw_threshold && j < a.WH) {
-      const int r = j / a.W, c = j - r * a.W;
-      const int idx = atomicAdd(count, 1);
-      if (idx < a.cap) {
-        FlCand cd;
-        cd.x = c * a.T + offset;
-        cd.y = r * a.T + offset;
-        cd.g = g;
-        cd.sim = (raw * 100.f) / (4 * nf) + 0.5f;                               // :1502
-        cand[idx] = cd;
+      const int raw = (int)tot[i];
+      const int j = j0 + i;
+      if (raw > raw_threshold && j < WH) {
+        const int rr = j / W, c = j - rr * W;
+        const int idx = atomicAdd(count, 1);
+        if (idx < cap) {
+          FlCand cd;
+          cd.x = c * T + offset;
+          cd.y = rr * T + offset;
+          cd.g = g;
+          cd.sim = (raw * 100.f) / (4 * nf) + 0.5f;                               // :1502
+          cand[idx] = cd;
+        }
       }
     }
+  };
+
+  const int it_end = min(a.n_items, it + a.run * a.item_step);
+  for (;;) {
+    const uint32_t cur = rec;
+    const bool cur_on = ((rl(cur, 16) >> ((it & 3) * 8)) & 0xFFu) != 0;   // wave-uniform: matchClass is not called for a class left out
+    // the next item's record and flag are requested before this item's loads (behind the last item: its own again)
+    const int nx = it + a.item_step;
+    const bool more = nx < it_end;
+    const int nxc = more ? nx : it;
+    rec = request_item(nxc);
+    if (cur_on) scan_item(cur);
+    if (!more) break;
+    it = nx;
   }
 }
 
@@ -870,6 +957,25 @@ __global__ __launch_bounds__(1024) void k_sort_unique(SortArgs a)
 }
 
 // ------------------------------------------------------------------------------------------
+// Work items a wave of k_scan walks: FL_SCAN_RUN_AUTO where the launch then still has FL_SCAN_FILL times the waves the device
+// holds at once, else half of that, and so on down to 1 (so the small-batch launches are what they were: one frame of 2000
+// templates is 2000 items for 1024 SIMDs).  Option scan_run != 0 forces a length.
+#ifndef FL_SCAN_RUN_AUTO
+#define FL_SCAN_RUN_AUTO 8
+#endif
+#ifndef FL_SCAN_STRIDED
+#define FL_SCAN_STRIDED 1
+#endif
+#define FL_SCAN_FILL 4
+static int fl_scan_run(const fl_context *ctx, int items, int n_frames)
+{
+  if (ctx->opt.scan_run) return (int)ctx->opt.scan_run;
+  const long need = (long)FL_SCAN_FILL * ctx->cus * 4 * (ctx->opt.scan_prune ? FL_SCAN_WPE_PRUNED : FL_SCAN_WPE);
+  int run = FL_SCAN_RUN_AUTO;
+  while (run > 1 && (long)n_frames * ((items + run - 1) / run) < need) run /= 2;
+  return run;
+}
+
 static int launch_scan_refine_sort(fl_detector *det, int n_frames, float threshold, uint16_t *dbg, int dbg_first,
                                    int dbg_count)
 {
@@ -878,17 +984,14 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
   {
     const FlLevelGeom &g = det->geom[L - 1];
     ScanArgs a;
-    a.hdr = det->d_scan_hdr;
     a.offs = det->d_scan_off;
-    a.enabled = det->d_pyr_enabled;
+    a.enabled = det->d_item_enabled;
     a.ws = det->d_ws;
     a.ws_stride = det->ws_stride;
     for (int m = 0; m < FL_MAX_MODALITIES; ++m) a.lm_off[m] = g.lm_off[m < M ? m : 0];
     a.off_count = det->off_count;
     a.off_cand = det->off_cand;
-    a.n_pyr = det->n_pyr;
     a.M = M;
-    a.nchunks = (g.WH + 1023) / 1024;
     a.W = g.W;
     a.WH = g.WH;
     a.T = g.T;
@@ -898,15 +1001,25 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
     a.prune_mid = ctx->opt.scan_prune_mid >= 0 ? (unsigned)ctx->opt.scan_prune_mid : FL_SCAN_PRUNE_MID;
     a.dbg = dbg;
     a.dbg_first = dbg_first;
-    a.dbg_count = dbg_count;
+    a.dbg_count = dbg ? dbg_count : 0;
     a.items = det->d_scan_items;
     a.n_items = det->n_scan_items;
     const int items = det->n_scan_items;
     if (items > 0) {
-      a.bpf = (items + 3) / 4;
+      a.run = fl_scan_run(ctx, items, n_frames);
+      const int waves = (items + a.run - 1) / a.run;      // per frame
+      a.bpf = (waves + 3) / 4;
+#if FL_SCAN_STRIDED
+      a.wave_step = 1;                                    // wave w: items w, w + 4 bpf, ...: the trained views, which lead the bank
+      a.item_step = a.bpf * 4;                            // and never prune, are spread over the frame's waves
+#else
+      a.wave_step = a.run;
+      a.item_step = 1;
+#endif
       a.n_frames = n_frames;
       dim3 grid((unsigned)(a.bpf * ((n_frames + 7) / 8) * 8));
-      hipLaunchKernelGGL(k_scan, grid, dim3(256), 0, ctx->stream, a);
+      if (a.prune) hipLaunchKernelGGL(k_scan<FL_SCAN_WPE_PRUNED>, grid, dim3(256), 0, ctx->stream, a);
+      else hipLaunchKernelGGL(k_scan<FL_SCAN_WPE>, grid, dim3(256), 0, ctx->stream, a);
       FL_HIP(ctx, hipGetLastError());
     }
   }
