@@ -79,6 +79,16 @@ class TrackResult(C.Structure):
                 ("pose", C.c_float * 16), ("det", DetectionResult)]
 
 
+class VerifyParams(C.Structure):
+    _fields_ = [("tau_mm", C.c_int32), ("min_model_px", C.c_int32), ("min_inlier_ratio", C.c_float), ("max_behind_ratio", C.c_float)]
+
+
+class VerifyResult(C.Structure):       # 64 bytes
+    _fields_ = [("status", C.c_int32), ("accepted", C.c_int32), ("best", C.c_int32), ("rect", C.c_int32 * 4), ("n_model", C.c_int32),
+                ("n_missing", C.c_int32), ("n_inlier", C.c_int32), ("n_front", C.c_int32), ("n_behind", C.c_int32),
+                ("sum_abs_inlier", C.c_int64), ("inlier_ratio", C.c_float), ("behind_ratio", C.c_float)]
+
+
 class StageTimes(C.Structure):
     _fields_ = [("frontend_ms", C.c_float), ("linmem_ms", C.c_float), ("scan_ms", C.c_float), ("refine_ms", C.c_float),
                 ("sort_ms", C.c_float), ("backproject_ms", C.c_float), ("icp_ms", C.c_float), ("total_ms", C.c_float),
@@ -163,6 +173,7 @@ SIGNATURES = {
     "fl_tracker_create": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_tracker_destroy": (None, [_P]),
     "fl_track_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams), _P]),
+    "fl_verify_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(VerifyParams), _P]),
     "fl_nms": (_I, [_P, _I, _F, C.POINTER(_I), C.POINTER(_I)]),
     "fl_export_topk": (_I, [_P, _I, _I, _I, _P]),
     "fl_merge_topk": (_I, [_P, _I, _P, _I]),
@@ -183,6 +194,7 @@ DEV_SIGNATURES = {
     "fl_dev_front_images": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t]),
     "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
+    "fl_dev_tracker_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_cq_window_addr": (None, [C.c_uint, _I, _I, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_I)]),
     "fl_dev_cq_window_taps": (None, [_P, C.c_uint, _I, _I, _I, _I, _P]),
     "fl_dev_scan_items": (_I, [_P, _I, _I, _I, C.c_uint, _P, _I, _P, _I, _P]),

@@ -22,6 +22,11 @@ assert RESULT_DTYPE.itemsize == C.sizeof(L.RecognitionResult)
 TRACK_DTYPE = np.dtype([("status", "<i4"), ("tracked", "<i4"), ("rect_model", "<i4", 4), ("rect_ref", "<i4", 4), ("pose", "<f4", 16),
                         ("det", _DET_DT)])
 assert TRACK_DTYPE.itemsize == C.sizeof(L.TrackResult)
+# numpy view of fl_verify_result
+VERIFY_DTYPE = np.dtype([("status", "<i4"), ("accepted", "<i4"), ("best", "<i4"), ("rect", "<i4", 4), ("n_model", "<i4"), ("n_missing", "<i4"),
+                         ("n_inlier", "<i4"), ("n_front", "<i4"), ("n_behind", "<i4"), ("sum_abs_inlier", "<i8"), ("inlier_ratio", "<f4"),
+                         ("behind_ratio", "<f4")])
+assert VERIFY_DTYPE.itemsize == C.sizeof(L.VerifyResult) == 64
 
 
 class FealessError(RuntimeError):
@@ -774,6 +779,14 @@ def merge_topk(records, cap):
     return out[:n]
 
 
+def _poses13(poses):
+    """(n, 13) float32 from (n, 13) or (n, 4, 4) poses."""
+    p = np.asarray(poses, np.float32)
+    if p.ndim == 3 and p.shape[1:] == (4, 4):
+        p = np.concatenate([p[:, :3, :].reshape(-1, 12), np.zeros((len(p), 1), np.float32)], 1)
+    return np.ascontiguousarray(p, np.float32).reshape(-1, 13)
+
+
 class Tracker:
     """fl_tracker: follows objects from frame to frame against their CAD mesh (render at the previous pose, crop, detection()
     from that pose).  Owns its device memory: the mesh, max_frames depth frames of w x h, max_tracks renders and ICP workspaces
@@ -789,6 +802,26 @@ class Tracker:
         ctx.check(self.lib.fl_tracker_create(ctx.h, _ptr(v), len(v), _ptr(t), len(t), w, h, max_frames, max_tracks, max_crop_px, C.byref(h_)))
         self.handle = h_
 
+    def _frames(self, depths, who):
+        """(n, pointer array, device?) of a list of frames: (h, w) u16 numpy arrays, or device tensors, all of one kind.  The
+        pointer array's owner keeps the (possibly converted) frames alive through its _frames attribute."""
+        depths = list(depths)
+        device = len(depths) > 0 and hasattr(depths[0], "data_ptr")
+        if device:
+            for d in depths:
+                if d.numel() != self.w * self.h or d.element_size() != 2 or not d.is_contiguous():
+                    raise ValueError(f"{who}: device frames must be contiguous {self.h} x {self.w} 16-bit tensors")
+            ptrs = [d.data_ptr() for d in depths]
+        else:
+            depths = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            for d in depths:
+                if d.shape != (self.h, self.w):
+                    raise ValueError(f"{who}: frames must be {self.h} x {self.w}")
+            ptrs = [d.ctypes.data for d in depths]
+        dp = (C.c_void_p * max(1, len(ptrs)))(*ptrs)
+        dp._frames = depths
+        return len(ptrs), dp, device
+
     def track(self, depths, frame_of_track, poses13, K, **params):
         """One step of every track (fl_track_batch).  depths: the frames, (h, w) u16 numpy arrays in mm, or device tensors
         (anything with data_ptr(): all of one kind); frame_of_track: the frame each track looks at; poses13: (n_tracks, 13)
@@ -796,26 +829,9 @@ class Tracker:
         fl_track_params (margin_px, passes, icp_it_thr, dist_mean_thr, dist_diff_thr, icp_mode, max_dist_mean, min_px_ratio);
         none given = the library's defaults.  Returns a TRACK_DTYPE array, one record per track; feed its poses back in
         (poses13_of) for the next frame."""
-        depths = list(depths)
-        device = len(depths) > 0 and hasattr(depths[0], "data_ptr")
-        if device:
-            for d in depths:
-                if d.numel() != self.w * self.h or d.element_size() != 2 or not d.is_contiguous():
-                    raise ValueError(f"Tracker.track: device frames must be contiguous {self.h} x {self.w} 16-bit tensors")
-            ptrs = [d.data_ptr() for d in depths]
-        else:
-            depths = [np.ascontiguousarray(d, np.uint16) for d in depths]
-            for d in depths:
-                if d.shape != (self.h, self.w):
-                    raise ValueError(f"Tracker.track: frames must be {self.h} x {self.w}")
-            ptrs = [d.ctypes.data for d in depths]
-        n = len(ptrs)
-        dp = (C.c_void_p * max(1, n))(*ptrs)
+        n, dp, device = self._frames(depths, "Tracker.track")
         fof = np.ascontiguousarray(frame_of_track, np.int32).ravel()
-        p = np.asarray(poses13, np.float32)
-        if p.ndim == 3 and p.shape[1:] == (4, 4):
-            p = np.concatenate([p[:, :3, :].reshape(-1, 12), np.zeros((len(p), 1), np.float32)], 1)
-        p = np.ascontiguousarray(p, np.float32).reshape(-1, 13)
+        p = _poses13(poses13)
         if len(p) != len(fof):
             raise ValueError("Tracker.track: one pose per track")
         prm = None
@@ -832,6 +848,46 @@ class Tracker:
         self.ctx.check(self.lib.fl_track_batch(self.handle, n, dp, L.FL_MEM_DEVICE if device else L.FL_MEM_HOST, len(fof), _ptr(fof), _ptr(p),
                                                C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
         return out[:len(fof)]
+
+    def verify(self, depths, frame_of_pose, poses, K, group_first=None, **params):
+        """Hypothesis verification (fl_verify_batch): the mesh rendered at every pose with the scene camera K = (fx, fy, cx, cy)
+        and laid over the pose's depth frame.  depths, frame_of_pose and poses ((n, 13) or (n, 4, 4): the `pose` fields of
+        recognize_instances / track results feed straight in) are as track() takes them.  group_first: None (every pose is its
+        own group, best = accepted) or n_groups + 1 non-decreasing indices from 0 to n; one pose per group at most comes back
+        with best = 1.  params: the fields of fl_verify_params (tau_mm, min_model_px, min_inlier_ratio, max_behind_ratio); none
+        given = the library's defaults.  Returns a VERIFY_DTYPE array, one record per pose."""
+        n, dp, device = self._frames(depths, "Tracker.verify")
+        fof = np.ascontiguousarray(frame_of_pose, np.int32).ravel()
+        p = _poses13(poses)
+        if len(p) != len(fof):
+            raise ValueError("Tracker.verify: one pose per frame index")
+        gf, n_groups = None, 0
+        if group_first is not None:
+            gf = np.ascontiguousarray(group_first, np.int32).ravel()
+            if len(gf) < 2:
+                raise ValueError("Tracker.verify: group_first has n_groups + 1 entries")
+            n_groups = len(gf) - 1
+        prm = None
+        if params:
+            unknown = set(params) - {f[0] for f in L.VerifyParams._fields_}
+            if unknown:
+                raise TypeError(f"Tracker.verify: unknown parameters {sorted(unknown)}")
+            d = dict(tau_mm=10, min_model_px=1, min_inlier_ratio=0.0, max_behind_ratio=0.0)
+            d.update(params)
+            prm = L.VerifyParams(**d)
+        k = L.Intrinsics(self.w, self.h, *[float(x) for x in K])
+        out = np.zeros(max(1, len(fof)), VERIFY_DTYPE)
+        self.ctx.check(self.lib.fl_verify_batch(self.handle, n, dp, L.FL_MEM_DEVICE if device else L.FL_MEM_HOST, len(fof), _ptr(fof), _ptr(p),
+                                                n_groups, None if gf is None else _ptr(gf), C.byref(k), None if prm is None else C.byref(prm),
+                                                _ptr(out)))
+        return out[:len(fof)]
+
+    def verify_ms(self):
+        """DEVELOPMENT ONLY (fl_dev_tracker_verify_ms, not part of the C ABI): device time of the last verify() by stage:
+        dict(copy, render, score, finish) in ms."""
+        out = (C.c_float * 4)()
+        self.ctx.check(L.dev(self.lib, "fl_dev_tracker_verify_ms")(self.handle, out))
+        return dict(zip(("copy", "render", "score", "finish"), [float(v) for v in out]))
 
     def stage_ms(self):
         """DEVELOPMENT ONLY (fl_dev_tracker_stage_ms, not part of the C ABI): device time of the last track() by stage, summed

@@ -229,4 +229,20 @@ int CadRecoSetTrackingMesh(CObjRecoCAD *handle, const string &obj_path, float sc
 int CadRecoTrack(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult,
                  vector<int> *tracked);
 
+// ---- verification: is an object where its result says it is? ---------------------------------------------------------------
+// CadRecoVerify renders the mesh of CadRecoSetTrackingMesh at every entry's tWorld2Cam with the frame's camera K and lays the
+// render over the depth frame (fl_verify_batch, include/fealess_hip.h, which states the per-pixel rule).  Per entry: the
+// rendered pixels (n_model), how many of them the frame supports within tau_mm (n_inlier), has no depth for (n_missing), shows
+// something nearer at -- an occluder, which is allowed -- (n_front), or sees THROUGH the object at, which is impossible
+// (n_behind), and the two ratios n_inlier / n_model and n_behind / n_model.  accepted = 1 when anything was rendered (the
+// library's default gates); callers put their own thresholds on the ratios.  vtResult is not changed; *out gets one record per
+// entry.  The same limits and error codes as CadRecoTrack; tau_mm outside 0..65535 (as an integer): ERROR_INVALID_PARAM.
+struct CadRecoVerifyResult {
+  int accepted;
+  int n_model, n_missing, n_inlier, n_front, n_behind;
+  float inlier_ratio, behind_ratio;
+};
+int CadRecoVerify(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult,
+                  float tau_mm, vector<CadRecoVerifyResult> *out);
+
 #endif  // FEALESS_CADRECO_H

@@ -287,6 +287,35 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return SUCCESS;
   }
 
+  // CadRecoVerify: one fl_verify_batch over the entries, every pose its own group, the library's default gates
+  int Verify(const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult, float tau_mm,
+             vector<CadRecoVerifyResult> *out)
+  {
+    if (out) out->clear();
+    if (!out || !m_ctx || !m_tracker || !check_image_u16(tDepth) || tDepth.nWidth != PROC_IMG_WIDTH || tDepth.nHeight != TRACK_IMG_HEIGHT ||
+        (int)vtResult.size() > FEALESS_TRACK_MAX_OBJECTS || !(tau_mm >= 0.f && tau_mm < 65536.f))
+      return (int)ERROR_INVALID_PARAM;
+    const int n = (int)vtResult.size();
+    if (n == 0) return SUCCESS;
+    std::vector<float> poses((size_t)n * 13, 0.f);
+    std::vector<int32_t> frame_of(n, 0);
+    for (int i = 0; i < n; ++i) memcpy(poses.data() + (size_t)13 * i, vtResult[i].tWorld2Cam, 12 * sizeof(float));
+    const fl_intrinsics k = {PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, K.dFx, K.dFy, K.dCx, K.dCy};
+    const uint16_t *frame = tDepth.pData;
+    const fl_verify_params prm = {(int32_t)tau_mm, 1, 0.f, 0.f};
+    std::vector<fl_verify_result> res(n);
+    const int rc = fl_verify_batch(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), 0, nullptr, &k, &prm, res.data());
+    if (rc != FL_OK) {
+      fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
+      return rc == FL_ERR_INVALID ? (int)ERROR_INVALID_PARAM : (int)ERROR_UNKNOW;
+    }
+    out->resize(n);
+    for (int i = 0; i < n; ++i)
+      (*out)[i] = CadRecoVerifyResult{res[i].accepted, res[i].n_model, res[i].n_missing, res[i].n_inlier, res[i].n_front, res[i].n_behind,
+                                      res[i].inlier_ratio, res[i].behind_ratio};
+    return SUCCESS;
+  }
+
   fl_recognition_params m_params;
   int m_topk = 1;            // > 1: multi-hypothesis mode (CadRecoSetMultiHypothesis)
   float m_nms_dist = 20.0f;  // th_obj_dist of nonMaximumSuppression, mm
@@ -596,8 +625,31 @@ int CadRecoTrack(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrins
   return h->Track(tDepth, K, vtResult, tracked);
 }
 
+int CadRecoVerify(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult,
+                  float tau_mm, vector<CadRecoVerifyResult> *out)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h) return (int)ERROR_INVALID_PARAM;
+  return h->Verify(tDepth, K, vtResult, tau_mm, out);
+}
+
 // ---- flat C shim so that the pytest harness (ctypes) can drive the C++ facade -------------------
 extern "C" {
+// CadRecoVerify on n poses (n 4x4 matrices); out: n CadRecoVerifyResult records (8 x 4 bytes each)
+int cadreco_verify(void *h, const unsigned short *depth, int w, int h_, double ts, double fx, double fy, double cx, double cy, int n,
+                   const float *poses16, float tau_mm, void *out)
+{
+  if (n < 0 || (n > 0 && (!poses16 || !out))) return (int)ERROR_INVALID_PARAM;
+  TImageU16 d = {ts, (unsigned short *)depth, w, h_};
+  TCamIntrinsicParam K;
+  K.nWidth = w; K.nHeight = h_; K.dFx = fx; K.dFy = fy; K.dCx = cx; K.dCy = cy;
+  std::vector<TObjRecoResult> res(n);
+  for (int i = 0; i < n; ++i) memcpy(res[i].tWorld2Cam, poses16 + 16 * i, 16 * sizeof(float));
+  std::vector<CadRecoVerifyResult> v;
+  const int rc = CadRecoVerify((CObjRecoCAD *)h, d, K, res, tau_mm, &v);
+  if (rc == SUCCESS && !v.empty()) memcpy(out, v.data(), v.size() * sizeof(CadRecoVerifyResult));
+  return rc;
+}
 int cadreco_set_tracking_mesh(void *h, const char *obj_path, float scale)
 {
   if (!obj_path) return (int)ERROR_INVALID_PARAM;

@@ -513,6 +513,56 @@ void fl_tracker_destroy(fl_tracker *trk);
 int  fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
                     int n_tracks, const int32_t *frame_of_track, const float *poses13,
                     const fl_intrinsics *K, const fl_track_params *params, fl_track_result *results);
+/* ---- verification: is the object where a pose says it is?  (No counterpart in the reference, whose check is visual.) -----
+ * The ICP's dist_mean and px_ratio are measured over the point pairs the ICP kept: they say how well the kept points fit,
+ * not whether the object is there.  fl_verify_batch renders the tracker's mesh at every pose and lays the render over the
+ * pose's depth frame, pixel by pixel.  depth, mem, frame_of_pose, poses13 and K are as fl_track_batch takes them; results
+ * (n_poses records) is host memory; params == NULL: the defaults below.  Everything is queued on the context's stream (after
+ * a detector's pipelined ICP stage on that context) and the call waits once, at the end; it allocates nothing.  It writes the
+ * tracker's frame slots and render images, as fl_track_batch does: the caller serialises the two, as everything on a context.
+ *   render   the mesh at every pose, depth only, at w x h with the SCENE camera (float)K->fx, (float)K->fy, (float)K->cx,
+ *            (float)K->cy -- not the model camera fl_track_batch renders with: here a render pixel and the frame pixel
+ *            under it are one ray, so there is no rectangle shift and no assumption about the image size.
+ *   score    (integers) per pixel, r = the render and s = the frame in mm: r == 0 is not counted.  Otherwise the pixel
+ *            counts in n_model and, with d = (int)s - (int)r, in exactly one of
+ *              n_missing  s == 0              the frame has no depth there
+ *              n_inlier   |d| <= tau_mm       supported; |d| is added to sum_abs_inlier
+ *              n_front    d < -tau_mm         the scene is nearer: something stands in front of the object, which may be
+ *              n_behind   d >  tau_mm         the camera sees through the object, which may not be
+ *            so n_model == n_missing + n_inlier + n_front + n_behind.  rect = {x0, y0, x1 - x0 + 1, y1 - y0 + 1} of the
+ *            inclusive bounding box [x0, x1] x [y0, y1] of the r != 0 pixels.
+ *   finish   inlier_ratio = (float)n_inlier / (float)n_model, behind_ratio = (float)n_behind / (float)n_model, one float32
+ *            division each, both 0 when n_model == 0.  accepted = 1 when n_model >= min_model_px and (min_inlier_ratio <= 0
+ *            or inlier_ratio >= min_inlier_ratio) and (max_behind_ratio <= 0 or behind_ratio <= max_behind_ratio), else 0.
+ *            An empty render (out of view, behind the camera): status FL_OK, accepted 0, rect, counts and ratios zero.
+ *   pick     group g is the poses group_first[g] .. group_first[g + 1] - 1 (group_first: n_groups + 1 entries, host memory,
+ *            non-decreasing, group_first[0] == 0, group_first[n_groups] == n_poses; a group may be empty and its members may
+ *            look at different frames).  best = 1 for at most one pose of a group: among the accepted ones the pose with
+ *            the largest n_inlier / n_model, compared exactly -- a beats b when (int64)n_inlier_a * n_model_b >
+ *            (int64)n_inlier_b * n_model_a -- and a tie goes to the lower index; a group without an accepted pose has no
+ *            best.  group_first == NULL (n_groups is ignored): every pose is its own group, best = accepted.
+ * Returns FL_OK when the batch ran, whatever the poses' fates; status is FL_OK in every record then.
+ * FL_ERR_INVALID, nothing written: null pointers, n_frames outside 1..max_frames, n_poses outside 1..max_tracks, a
+ * frame_of_pose outside [0, n_frames), a non-finite pose or K, fx or fy <= 0 (as doubles or as floats), K's size not w x h,
+ * with group_first: n_groups outside 1..max_tracks or a group_first that breaks the rules above, tau_mm outside 0..65535,
+ * min_model_px < 1, a non-finite threshold, an unknown mem.  These checks precede the first HIP call. */
+typedef struct {
+  int32_t tau_mm;                      /* inlier band in mm, 0..65535; default 10 */
+  int32_t min_model_px;                /* accepted only if n_model >= this; >= 1; default 1 */
+  float   min_inlier_ratio;            /* > 0: accepted only if inlier_ratio >= it; <= 0: no test (default 0) */
+  float   max_behind_ratio;            /* > 0: accepted only if behind_ratio <= it; <= 0: no test (default 0) */
+} fl_verify_params;
+typedef struct {
+  int32_t status, accepted, best;
+  int32_t rect[4];                     /* x, y, w, h of the render's non-zero pixels; zeros when empty */
+  int32_t n_model, n_missing, n_inlier, n_front, n_behind;
+  int64_t sum_abs_inlier;              /* sum of |scene - render| in mm over the inliers */
+  float   inlier_ratio, behind_ratio;
+} fl_verify_result;                    /* 64 bytes */
+int  fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
+                     int n_poses, const int32_t *frame_of_pose, const float *poses13,
+                     int n_groups, const int32_t *group_first, const fl_intrinsics *K,
+                     const fl_verify_params *params, fl_verify_result *results);
 /* After fl_match_frame / fl_recognize_submit: copy frame `frame`'s first k sorted matches into a
  * device buffer (k * sizeof(fl_match) bytes, padded with template_id = -1) for an RCCL
  * all-gather by the caller; template ids are offset by template_id_base (the shard's first
