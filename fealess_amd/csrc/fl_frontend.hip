@@ -20,6 +20,7 @@
 // "parity unpinned" at this boundary.
 #include "fl_internal.h"
 #include <float.h>
+#include <type_traits>
 
 #ifndef FL_CQ_DOT4
 #define FL_CQ_DOT4 1               // horizontal blur taps by v_dot4_u32_u8 against constant weight words
@@ -614,7 +615,13 @@ static int ensure_normal_lut(fl_context *ctx)
 // k_depth_quantize: quantizedNormals (linemod.cpp:595-683) fused with the medianBlur(5) that ends
 // it (:684).  Same execution shape as k_color_quantize: a wavefront owns 64 adjacent columns (60
 // outputs + 2 halo columns per side), walks chunk_rows output rows (fl_eager_chunk_rows: the first output row of a chunk
-// costs four more rows of normals) and keeps the last five rows in registers.
+// costs four more rows of normals) and keeps the last five rows of patterns in registers.
+// The depth taps come from a register ring: a lane holds the depth at its columns x - 5, x, x + 5 for the rows c - 5 .. c + 5
+// of its current row c (33 registers), so a step loads one row at three columns instead of three rows at three columns, and
+// the ring's slots trade roles over a loop body of eleven steps (k_color_quantize's seven-row ring does the same).  Strip,
+// chunk, rows and the row addresses of depth, dst and dst1 are scalar and advance by scalar additions; loads and stores take
+// a scalar base and a 32-bit lane offset.  Measured (profiles/README.md): 5.63 -> 4.98 ms per 4096 VGA frames, most of it
+// from the scalar addresses; the row-ahead and packed rings were slower than this one.
 // The codes are 0 or one-hot, i.e. 9 classes ordered like their byte values, and the exact 5x5 median is
 // the first class whose CUMULATIVE count reaches 13.  A pixel of class c therefore contributes the
 // pattern "1 in every 4-bit field i >= c" (fields 0..7; class 8's own field would always hold 25 and is
@@ -629,19 +636,18 @@ static int ensure_normal_lut(fl_context *ctx)
 
 __device__ __forceinline__ unsigned dq_pattern(unsigned cls) { return cls >= 8u ? 0u : 0x11111111u << (4u * cls); }
 
-__device__ __forceinline__ unsigned dq_normal_pattern(const uint16_t *__restrict__ depth, int w, int h, int y, int x,
-                                                      int distance_threshold, int difference_threshold, const uint8_t *lut)
+// The normal of one pixel from values: its depth d and the eight ring neighbours n0..n7, in the order (-,-) (0,-) (+,-) (-,0)
+// (+,0) (-,+) (0,+) (+,+).  interior: y >= 5 && y < h - 6 && x >= 5 && x < w - 6 (loop bounds :619, :624); of a lane that is not
+// interior, or whose d is not below distance_threshold, nothing is looked at (its taps are clamped into the image and mean
+// nothing).
+__device__ __forceinline__ unsigned dq_normal_pattern(bool interior, int d, int n0, int n1, int n2, int n3, int n4, int n5, int n6,
+                                                      int n7, int distance_threshold, int difference_threshold, const uint8_t *lut)
 {
-  const int r = 5;
-  if (!(y >= r && y < h - r - 1 && x >= r && x < w - r - 1)) return dq_pattern(0);   // loop bounds :619, :624
-  const uint16_t *p = depth + (__umul24((unsigned)y, (unsigned)w) + (unsigned)x);   // (rows, columns < 2^24: the full-rate multiply)
-  const int d = p[0];
+  if (!interior) return dq_pattern(0);
   if (!(d < distance_threshold)) return dq_pattern(0);
   const int t = difference_threshold;
   const unsigned span = t > 0 ? (unsigned)(2 * t - 1) : 0u;   // t <= 0 admits nothing
-  // neighbours 0..7: (-,-) (0,-) (+,-) (-,0) (+,0) (-,+) (0,+) (+,+)
-  const int e0 = (int)p[-r - r * w] - d, e1 = (int)p[0 - r * w] - d, e2 = (int)p[+r - r * w] - d, e3 = (int)p[-r] - d,
-            e4 = (int)p[+r] - d, e5 = (int)p[-r + r * w] - d, e6 = (int)p[0 + r * w] - d, e7 = (int)p[+r + r * w] - d;
+  const int e0 = n0 - d, e1 = n1 - d, e2 = n2 - d, e3 = n3 - d, e4 = n4 - d, e5 = n5 - d, e6 = n6 - d, e7 = n7 - d;
   // |e| < t  <=>  (unsigned)(e + t - 1) < 2t - 1                                                    :569
   const bool g0 = (unsigned)(e0 + t - 1) < span, g1 = (unsigned)(e1 + t - 1) < span,
              g2 = (unsigned)(e2 + t - 1) < span, g3 = (unsigned)(e3 + t - 1) < span,
@@ -689,6 +695,8 @@ __device__ __forceinline__ unsigned dq_normal_pattern(const uint16_t *__restrict
   return dq_pattern(v ? (unsigned)(32 - __clz(v)) : 0u);   // 0 -> class 0, 1<<k -> class k+1 (ascending in value)
 }
 
+#define DQ_RING 11                                         // depth rows c - 5 .. c + 5 of the current row of normals c
+
 __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restrict__ depth_, size_t in_stride,
                                                         uint8_t *__restrict__ dst_, size_t out_stride, int w, int h,
                                                         int distance_threshold, int difference_threshold, int nstrips,
@@ -698,7 +706,8 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restri
   __shared__ uint8_t s_lut[400];                           // NORMAL_LUT's 20x20 face: a per-lane lookup every row
   for (int k = threadIdx.x; k < 400; k += 256) s_lut[k] = c_normal_lut[k];
   __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // the wave index is the same in all 64 lanes: as a scalar it keeps the strip, the rows and the row addresses on the scalar unit
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + wave;
   if (item >= nstrips * nchunks) return;
   const int strip = item % nstrips, chunk = item / nstrips;
@@ -708,17 +717,35 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restri
   const int x = strip * DQ_COLS + lane - 2;
   const int xc = clampi(x, 0, w - 1);                      // medianBlur replicates the border
   const int y0 = chunk * chunk_rows, y1 = min(h, y0 + chunk_rows);
+  // The lane's 32-bit byte offsets from a row's scalar address: the three tap columns, clamped into the row (a clamped one
+  // belongs to a pixel that is not interior), and its pixel in dst and dst1.  lane_off's empty asm keeps an offset a 32-bit value
+  // where it is used: widened to 64 bits once, ahead of the loop, it turns every access into a 64-bit vector addition
+  // instead of the instruction's scalar-base form.
+  unsigned ol = 2u * (unsigned)max(xc - 5, 0), oc = 2u * (unsigned)xc, orr = 2u * (unsigned)min(xc + 5, w - 1);
+  unsigned ox = (unsigned)x, ox1 = (unsigned)x >> 1;
+  auto lane_off = [](unsigned &off) __attribute__((always_inline)) { asm volatile("" : "+v"(off)); return off; };
+  auto tap = [&](const char *rowp, unsigned &off) __attribute__((always_inline)) { return (int)*(const uint16_t *)(rowp + lane_off(off)); };
+  const bool xin = xc >= 5 && xc < w - 6;
+  const bool writes = lane >= 2 && lane < 2 + DQ_COLS && x < w;
+  const int cs = max(y0 - 2, 0), ce = min(y1 + 1, h - 1);  // the rows of normals this chunk's medians take
+  const size_t row_bytes = 2 * (size_t)w;
+  int RL[DQ_RING], RC[DQ_RING], RR[DQ_RING];               // columns xc - 5, xc, xc + 5; in step P row c + j is in slot (P + 5 + j) % DQ_RING
+  // prologue: rows cs - 5 .. cs + 4, clamped into the image, into slots 0 .. 9
+#pragma unroll
+  for (int i = 0; i < DQ_RING - 1; ++i) {
+    const char *rowp = (const char *)depth + (size_t)clampi(cs + i - 5, 0, h - 1) * row_bytes;
+    RL[i] = tap(rowp, ol);
+    RC[i] = tap(rowp, oc);
+    RR[i] = tap(rowp, orr);
+  }
+  const char *ldp = (const char *)depth + (size_t)min(cs + 5, h - 1) * row_bytes;    // the row the first step loads
+  uint8_t *orow = dst + (size_t)y0 * (size_t)w;            // the output rows' addresses: scalar, advanced by additions
+  uint8_t *orow1 = dst1 ? dst1 + (size_t)(y0 >> 1) * (size_t)(w >> 1) : nullptr;
   unsigned p0 = 0, p1 = 0, p2 = 0, p3 = 0, p4 = 0;         // cumulative-count patterns of the last five rows, p0 newest
-  int center = -1;
-  unsigned pat = 0;
-  for (int yv = y0 - 2; yv <= y1 + 1; ++yv) {
-    const int c = clampi(yv, 0, h - 1);
-    if (c != center) {                                     // wave-uniform
-      pat = dq_normal_pattern(depth, w, h, c, xc, distance_threshold, difference_threshold, s_lut);
-      center = c;
-    }
-    p4 = p3; p3 = p2; p2 = p1; p1 = p0; p0 = pat;
-    if (yv < y0 + 2) continue;
+  auto push = [&](unsigned pat) __attribute__((always_inline)) { p4 = p3; p3 = p2; p2 = p1; p1 = p0; p0 = pat; };
+  // the median and the stores at row yo = yv - 2
+  auto finish = [&](int yv) __attribute__((always_inline)) {
+    if (yv < y0 + 2) return;                               // wave-uniform
     const unsigned col = p0 + p1 + p2 + p3 + p4;           // fields <= 5
     const unsigned a1 = wave_from_next(col), b1 = wave_from_prev(col), a2 = wave_from_next(a1), b2 = wave_from_prev(b1);
     const unsigned s3 = col + a1 + b1, s2 = a2 + b2;       // fields <= 15, <= 10
@@ -726,11 +753,41 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restri
     const unsigned to = ((s3 >> 4) & 0x0F0F0F0Fu) + ((s2 >> 4) & 0x0F0F0F0Fu) + 0x73737373u;
     const int idx = 8 - __popc((te & 0x80808080u) | ((to & 0x80808080u) >> 1));
     const int yo = yv - 2;
-    if (lane >= 2 && lane < 2 + DQ_COLS && x < w) {
+    if (writes) {
       const uint8_t v = idx ? (uint8_t)(1u << (idx - 1)) : 0;
-      dst[__umul24((unsigned)yo, (unsigned)w) + (unsigned)x] = v;
-      if (dst1 && !((yo | x) & 1)) dst1[__umul24((unsigned)yo >> 1, (unsigned)w >> 1) + ((unsigned)x >> 1)] = v;
+      orow[lane_off(ox)] = v;
+      if (orow1 && !((yo | x) & 1)) orow1[lane_off(ox1)] = v;
     }
+    orow += w;
+    if (orow1 && (yo & 1)) orow1 += w >> 1;
+  };
+  // Virtual rows y0 - 2 .. y1 + 1.  Rows < 0 and >= h repeat rows 0 and h - 1, which are never interior: they push
+  // dq_pattern(0) and leave the depth ring alone.  Rows cs .. ce take one step each: step P of the unrolled body loads row c + 5
+  // (clamped) into slot P + 10, which row c - 6 has left, and computes with slots P, P + 5, P + 10 (rows c - 5, c, c + 5), so
+  // no slot is moved.
+  int yv = y0 - 2;
+  for (; yv < 0; ++yv) push(dq_pattern(0));                // nothing follows: yv < y0 + 2
+  auto step = [&](auto phase) __attribute__((always_inline)) {
+    constexpr int P = decltype(phase)::value, A = P % DQ_RING, C = (P + 5) % DQ_RING, B = (P + 10) % DQ_RING;
+    RL[B] = tap(ldp, ol);
+    RC[B] = tap(ldp, oc);
+    RR[B] = tap(ldp, orr);
+    if (yv + 5 < h - 1) ldp += row_bytes;                  // scalar
+    push(dq_normal_pattern(xin && yv >= 5 && yv < h - 6, RC[C], RL[A], RC[A], RR[A], RL[C], RR[C], RL[B], RC[B], RR[B],
+                           distance_threshold, difference_threshold, s_lut));
+    finish(yv);
+    ++yv;
+  };
+#define DQ_STEP(P)                                                                                                                  \
+  if (yv > ce) break;                                                                                                               \
+  step(std::integral_constant<int, P>());
+  for (;;) {
+    DQ_STEP(0) DQ_STEP(1) DQ_STEP(2) DQ_STEP(3) DQ_STEP(4) DQ_STEP(5) DQ_STEP(6) DQ_STEP(7) DQ_STEP(8) DQ_STEP(9) DQ_STEP(10)
+  }
+#undef DQ_STEP
+  for (; yv <= y1 + 1; ++yv) {
+    push(dq_pattern(0));
+    finish(yv);
   }
 }
 
