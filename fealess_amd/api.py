@@ -398,8 +398,8 @@ class Detector:
     def finalize(self, w0, h0, max_batch=1, max_candidates=0):
         # model depth renders first (class order = sorted class ids)
         for ci, b in enumerate(self.banks):
-            # render i belongs to pyramid i (bank.py); pyramids without one (None / behind the list's end) keep an empty
-            # render and cannot be refined.  One upload per run of consecutive renders.
+            # render i belongs to pyramid i (bank.py); pyramids without one (None / behind the list's end) get none and
+            # cannot be refined (FL_ERR_STATE in the result).  One upload per run of consecutive renders.
             i, n = 0, len(b.model_depths)
             while i < n:
                 if b.model_depths[i] is None:

@@ -363,15 +363,29 @@ extern "C" int fl_detector_set_model_depths(fl_detector *det, int class_idx, int
   FL_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = fl_pipeline_join(det)) return rc;     // an ICP stage in flight reads the renders
   size_t per = (size_t)w * h * sizeof(uint16_t);
+  // the finalized tables hold a pointer per pyramid that has a render: renders that arrive later join them below, and
+  // have to be frame-sized like the ones fl_detector_finalize checked
+  if (det->finalized && (w != det->w0 || h != det->h0))
+    return fl_set_error(ctx, FL_ERR_INVALID, "model depth renders must be %dx%d like the frames", det->w0, det->h0);
   if (!c.d_depths) {
     FL_HIP(ctx, hipMalloc((void **)&c.d_depths, per * (size_t)c.n_pyramids));
     FL_HIP(ctx, hipMemsetAsync(c.d_depths, 0, per * (size_t)c.n_pyramids, ctx->stream));
+    c.has_depth.assign((size_t)c.n_pyramids, 0);
     c.dw = w;
     c.dh = h;
   } else if (c.dw != w || c.dh != h)
     return fl_set_error(ctx, FL_ERR_INVALID, "model depth size changed");
   FL_HIP(ctx, hipMemcpyAsync((uint8_t *)c.d_depths + per * (size_t)first, depth_01mm, per * (size_t)count,
                              mem == FL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+  std::vector<const uint16_t *> ptrs;
+  for (int p = first; p < first + count; ++p) {
+    c.has_depth[(size_t)p] = 1;
+    ptrs.push_back(c.d_depths + (size_t)p * w * h);
+  }
+  if (det->finalized && det->d_depth_ptrs && count > 0) {
+    FL_HIP(ctx, hipMemcpyAsync(det->d_depth_ptrs + c.first_g + first, ptrs.data(), sizeof(ptrs[0]) * (size_t)count, hipMemcpyHostToDevice,
+                               ctx->stream));
+  }
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return FL_OK;
 }
@@ -647,13 +661,14 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
       pi.off_y0 = tp[0].offset_y;
       pi.width0 = tp[0].width;
       pi.height0 = tp[0].height;
-      pi.depth_slot = c.d_depths ? p : -1;
+      const bool has_depth = c.d_depths && c.has_depth[(size_t)p];
+      pi.depth_slot = has_depth ? p : -1;
       pi.pad = 0;
       pyr.push_back(pi);
       det->max_tw = std::max(det->max_tw, std::min(tp[0].width, w0));
       det->max_th = std::max(det->max_th, std::min(tp[0].height, h0));
       for (int k = 0; k < 13; ++k) poses.push_back(c.poses.empty() ? 0.f : c.poses[(size_t)p * 13 + k]);
-      depth_ptrs.push_back(c.d_depths ? c.d_depths + (size_t)p * c.dw * c.dh : nullptr);
+      depth_ptrs.push_back(has_depth ? c.d_depths + (size_t)p * c.dw * c.dh : nullptr);
       // coarsest level: scan tables (similarity(), linemod.cpp:1130-1214)
       {
         const FlLevelGeom &g = det->geom[L - 1];

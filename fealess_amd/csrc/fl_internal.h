@@ -154,6 +154,8 @@ struct FlClass {
   std::vector<float> poses;              // n_pyramids*13 or empty
   int first_g = 0;                       // set at finalize
   uint16_t *d_depths = nullptr;          // n_pyramids * dw*dh u16 (0.1 mm) or null
+  std::vector<uint8_t> has_depth;        // per pyramid: a render was uploaded (empty while d_depths is null).  The others are
+                                         // a missing depth/<id>.png: FL_ERR_STATE when refined, not an all-zero render
   int dw = 0, dh = 0;
 };
 

@@ -175,7 +175,10 @@ int  fl_detector_add_class(fl_detector *det, const char *class_id, int n_pyramid
                            int n_features, const float *poses13);
 /* The per-template depth renders CObjRecoLmICP reads from <dir>/depth/<template_id>.png on
  * every frame (obj_reco_lmicp.cpp:156-157): uploaded once, w*h u16 in 0.1 mm each, for the
- * pyramids [first, first+count) of class class_idx.  src may be host or device memory. */
+ * pyramids [first, first+count) of class class_idx.  src may be host or device memory.
+ * class_idx is the class's place in std::map order of the ids added SO FAR: a class added later may sort in front of it.
+ * A pyramid that never got a render is a missing depth/<id>.png: refining a match of it reports FL_ERR_STATE in that
+ * result's status (found = 0), whether or not other pyramids of its class have renders. */
 int  fl_detector_set_model_depths(fl_detector *det, int class_idx, int first, int count,
                                   const uint16_t *depth_01mm, int w, int h, int mem);
 /* Freeze the bank for frames of w0 x h0 and at most max_batch frames per call; uploads the

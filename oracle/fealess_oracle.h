@@ -187,6 +187,13 @@ int  orc_recognition(const uint8_t *bgr, const uint16_t *depth, int w, int h,
                      const float *poses13, const uint16_t *const *model_depths_01mm,
                      float threshold, int icp_it_thr, float dist_mean_thr, float dist_diff_thr,
                      int accum64, int use_kdtree, orc_recognition_result *res);
+/* The part of Recognition() behind the choice of the match (obj_reco_lmicp.cpp:111-197) for a match the caller names:
+ * bank, poses13 and model_depths_01mm belong to the match's class and match->template_id indexes them; match->class_idx is
+ * copied to res->best untouched and res->n_matches stays 0.  Returns 0, or what detection() refuses (then found = 0). */
+int  orc_recognition_refine(const orc_match *match, const uint16_t *depth, int w, int h, double fx, double fy, double cx, double cy,
+                            const orc_bank *bank, const float *poses13, const uint16_t *const *model_depths_01mm,
+                            int icp_it_thr, float dist_mean_thr, float dist_diff_thr, int accum64, int use_kdtree,
+                            orc_recognition_result *res);
 /* stage times (ms) of the calling thread's last orc_recognition at the reference's own timer points:
  * [0] "Time of linemod" (CadReco/obj_reco_lmicp.cpp:88,124-125), [1] "Time of ICP" (:126,201-202) */
 void orc_last_stage_ms(double out[2]);

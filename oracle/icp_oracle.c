@@ -622,6 +622,23 @@ static int recognition_refine(const orc_match best, const uint16_t *depth, int w
   return 0;
 }
 
+/* recognition_refine for a match the CALLER names (a match of a list over several classes, whose refinement depends on the
+ * match's own class only): bank, poses13 and model_depths_01mm are those of the match's class, match->template_id indexes
+ * them, match->class_idx is copied to res->best as it is.  res->n_matches stays 0.  A refinement that fails (Q10: the crop
+ * leaves the image) gives found = 0, as in orc_recognition_topk; the return value is recognition_refine's. */
+int orc_recognition_refine(const orc_match *match, const uint16_t *depth, int w, int h, double fx, double fy, double cx, double cy,
+                           const orc_bank *bank, const float *poses13, const uint16_t *const *model_depths_01mm,
+                           int icp_it_thr, float dist_mean_thr, float dist_diff_thr, int accum64, int use_kdtree,
+                           orc_recognition_result *res)
+{
+  memset(res, 0, sizeof(*res));
+  if (match->template_id < 0 || match->template_id >= bank->n_pyramids) return -1;
+  const int rc = recognition_refine(*match, depth, w, h, fx, fy, cx, cy, bank, poses13, model_depths_01mm, icp_it_thr, dist_mean_thr,
+                                    dist_diff_thr, accum64, use_kdtree, res);
+  if (rc) res->found = 0;
+  return rc;
+}
+
 int orc_recognition(const uint8_t *bgr, const uint16_t *depth, int w, int h,
                     double fx, double fy, double cx, double cy,
                     int levels, const int *T_at_level, const orc_bank *bank,

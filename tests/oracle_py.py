@@ -357,7 +357,8 @@ def recognition(bgr, depth, K, T_pyramid, bank, threshold=75.0, icp_it_thr=10, d
     T = (C.c_int * levels)(*T_pyramid)
     arr, keep = _banks([bank])
     t, f, p = keep[0]
-    zero = np.zeros((h, w), np.uint16)    # pyramids without a depth render (bank.py): an empty render, as the product uploads
+    zero = np.zeros((h, w), np.uint16)    # pyramids without a depth render (bank.py): an empty render here; the product reports
+                                          # FL_ERR_STATE for them, and refine_match / recognition_banks say no_render
     mds = [zero if m is None else np.ascontiguousarray(m, np.uint16) for m in bank.model_depths]
     mds = mds + [zero] * (bank.n_pyramids - len(mds))
     mptr = (C.c_void_p * len(mds))(*[m.ctypes.data for m in mds])
@@ -403,7 +404,8 @@ def recognition_topk(bgr, depth, K, T_pyramid, bank, k, threshold=75.0, icp_it_t
     T = (C.c_int * levels)(*T_pyramid)
     arr, keep = _banks([bank])
     t, f, p = keep[0]
-    zero = np.zeros((h, w), np.uint16)    # pyramids without a depth render (bank.py): an empty render, as the product uploads
+    zero = np.zeros((h, w), np.uint16)    # pyramids without a depth render (bank.py): an empty render here; the product reports
+                                          # FL_ERR_STATE for them, and refine_match / recognition_banks say no_render
     mds = [zero if m is None else np.ascontiguousarray(m, np.uint16) for m in bank.model_depths]
     mds = mds + [zero] * (bank.n_pyramids - len(mds))
     mptr = (C.c_void_p * len(mds))(*[m.ctypes.data for m in mds])
@@ -418,6 +420,70 @@ def recognition_topk(bgr, depth, K, T_pyramid, bank, k, threshold=75.0, icp_it_t
         return out
     win = (C.c_int * max(1, n))()
     nw = lib().orc_nms(res, n, C.c_float(nms_dist), win)
+    return out, [int(win[i]) for i in range(nw)]
+
+
+def _refine_into(res, depth, K, bank, match, icp_it_thr, dist_mean_thr, dist_diff_thr, accum64):
+    """orc_recognition_refine of `match` (template_id local to `bank`) into the OrcRecognitionResult `res`.  Returns False,
+    with res zero but for `best`, where the pyramid has no depth render: the reference finds no depth/<id>.png to read."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    h, w = d.shape
+    tid = int(match["template_id"])
+    m = OrcMatch(int(match["x"]), int(match["y"]), float(match["similarity"]), int(match["class_idx"]), tid)
+    if not 0 <= tid < bank.n_pyramids:
+        raise IndexError("template %d is not in bank %r" % (tid, bank.class_id))
+    md = bank.model_depths[tid] if tid < len(bank.model_depths) else None
+    if md is None:
+        C.memset(C.byref(res), 0, C.sizeof(res))
+        res.best = m
+        return False
+    md = np.ascontiguousarray(md, np.uint16)
+    assert md.shape == (h, w)
+    arr, keep = _banks([bank])
+    p = keep[0][2]
+    mptr = (C.c_void_p * bank.n_pyramids)()          # recognition_refine reads the named pyramid's render only
+    mptr[tid] = md.ctypes.data
+    lib().orc_recognition_refine(C.byref(m), _p(d), w, h, C.c_double(K[0]), C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]),
+                                 C.byref(arr[0]), _p(p), mptr, icp_it_thr, C.c_float(dist_mean_thr), C.c_float(dist_diff_thr),
+                                 int(accum64), 1, C.byref(res))
+    return True
+
+
+def refine_match(depth, K, bank, match, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01, accum64=False, n_matches=0):
+    """The part of Recognition() behind the choice of the match, for a match the caller names: `match` is a MATCH_DTYPE
+    record (or a dict with its fields) whose template_id is local to `bank`, the bank of its class; class_idx is carried
+    along untouched.  A result dict as recognition_topk's, plus no_render: True (and found = 0) where the pyramid has no
+    depth render, which the reference cannot refine."""
+    res = OrcRecognitionResult()
+    ok = _refine_into(res, depth, K, bank, match, icp_it_thr, dist_mean_thr, dist_diff_thr, accum64)
+    res.n_matches = n_matches
+    return dict(_reco_dict(res), no_render=not ok)
+
+
+def recognition_banks(bgr, depth, K, T_pyramid, banks, k, threshold=75.0, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01,
+                      nms_dist=None, accum64=False, class_ids=()):
+    """Recognition() over several classes on one detector: Detector::match over `banks` in the order of their class ids
+    (std::map order), restricted to class_ids when that is not empty (a set; unknown ids match nothing, linemod.cpp:1418-1434),
+    then refine_match of the first k matches.  class_idx is the index in the FULL sorted list whatever the filter.  A list of
+    result dicts (n_matches = the length of the whole match list); with nms_dist also orc_nms's winners among them."""
+    full = sorted(banks, key=lambda b: b.class_id)
+    sel = [i for i, b in enumerate(full) if not class_ids or b.class_id in set(class_ids)]
+    if sel:
+        m, n_total = match_images(bgr, depth, T_pyramid, [full[i] for i in sel], threshold)
+    else:
+        m, n_total = np.zeros(0, MATCH_DTYPE), 0
+    m = m[:k].copy()
+    m["class_idx"] = np.asarray(sel, np.int32)[m["class_idx"]] if len(m) else m["class_idx"]
+    res = (OrcRecognitionResult * max(1, len(m)))()
+    out = []
+    for r in range(len(m)):
+        ok = _refine_into(res[r], depth, K, full[int(m["class_idx"][r])], m[r], icp_it_thr, dist_mean_thr, dist_diff_thr, accum64)
+        res[r].n_matches = n_total
+        out.append(dict(_reco_dict(res[r]), no_render=not ok))
+    if nms_dist is None:
+        return out
+    win = (C.c_int * max(1, len(m)))()
+    nw = lib().orc_nms(res, len(m), C.c_float(nms_dist), win)
     return out, [int(win[i]) for i in range(nw)]
 
 

@@ -134,9 +134,11 @@ def write_png16(path, img):
 
 
 def write_linemod_yaml(path, bank, T, modalities=("ColorGradient", "DepthNormal")):
-    """OpenCV FileStorage YAML 1.0 as cup_linemod's writeLinemod lays it out (linemod_if.cpp:49-63)."""
-    t, f, p = bank.arrays()
-    LM = bank.levels * bank.modalities
+    """OpenCV FileStorage YAML 1.0 as cup_linemod's writeLinemod lays it out (linemod_if.cpp:49-63).  bank: one TemplateBank, or
+    a list of them (one class each, the same levels and modalities), written in the order given."""
+    banks = list(bank) if isinstance(bank, (list, tuple)) else [bank]
+    bank = banks[0]
+    assert all((b.levels, b.modalities) == (bank.levels, bank.modalities) for b in banks)
     o = ["%YAML:1.0", "---", f"pyramid_levels: {bank.levels}", "T: [ " + ", ".join(str(v) for v in T) + " ]", "modalities:"]
     for m in modalities[:bank.modalities]:
         if m == "ColorGradient":
@@ -144,21 +146,25 @@ def write_linemod_yaml(path, bank, T, modalities=("ColorGradient", "DepthNormal"
         else:
             o += ["   -", "      type: DepthNormal", "      distance_threshold: 2000", "      difference_threshold: 50",
                   "      num_features: 63", "      extract_threshold: 2"]
-    o += ["classes:", "   -", f'      class_id: "{bank.class_id}"',
-          "      modalities: [ " + ", ".join(modalities[:bank.modalities]) + " ]", f"      pyramid_levels: {bank.levels}",
-          "      template_pyramids:"]
-    for i in range(bank.n_pyramids):
-        pose = [repr(float(v)).rstrip("0") if "." in repr(float(v)) else repr(float(v)) for v in p[i]]
-        o += ["         -", f"            template_id: {i}",
-              "            template_pose: [ " + ", ".join(pose[:7]) + ",", "               " + ", ".join(pose[7:]) + " ]",
-              "            templates:"]
-        for k in range(LM):
-            hdr = t[i * LM + k]
-            o += ["               -", f"                  width: {hdr['width']}", f"                  height: {hdr['height']}",
-                  f"                  offset_x: {hdr['offset_x']}", f"                  offset_y: {hdr['offset_y']}",
-                  f"                  pyramid_level: {hdr['pyramid_level']}", "                  features:"]
-            for fr in f[hdr["feat_begin"]:hdr["feat_begin"] + hdr["feat_count"]]:
-                o.append(f"                     - [ {fr['x']}, {fr['y']}, {fr['label']} ]")
+    o += ["classes:"]
+    for bank in banks:
+        t, f, p = bank.arrays()
+        LM = bank.levels * bank.modalities
+        o += ["   -", f'      class_id: "{bank.class_id}"',
+              "      modalities: [ " + ", ".join(modalities[:bank.modalities]) + " ]", f"      pyramid_levels: {bank.levels}",
+              "      template_pyramids:"]
+        for i in range(bank.n_pyramids):
+            pose = [repr(float(v)).rstrip("0") if "." in repr(float(v)) else repr(float(v)) for v in p[i]]
+            o += ["         -", f"            template_id: {i}",
+                  "            template_pose: [ " + ", ".join(pose[:7]) + ",", "               " + ", ".join(pose[7:]) + " ]",
+                  "            templates:"]
+            for k in range(LM):
+                hdr = t[i * LM + k]
+                o += ["               -", f"                  width: {hdr['width']}", f"                  height: {hdr['height']}",
+                      f"                  offset_x: {hdr['offset_x']}", f"                  offset_y: {hdr['offset_y']}",
+                      f"                  pyramid_level: {hdr['pyramid_level']}", "                  features:"]
+                for fr in f[hdr["feat_begin"]:hdr["feat_begin"] + hdr["feat_count"]]:
+                    o.append(f"                     - [ {fr['x']}, {fr['y']}, {fr['label']} ]")
     with open(path, "w") as fh:
         fh.write("\n".join(o) + "\n")
 
