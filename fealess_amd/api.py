@@ -787,6 +787,23 @@ def _poses13(poses):
     return np.ascontiguousarray(p, np.float32).reshape(-1, 13)
 
 
+# what a field holds when only some keywords are given: the library's own defaults (k_track_defaults, k_verify_defaults)
+_TRACK_DEFAULTS = dict(margin_px=12, passes=1, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01, icp_mode=L.FL_ICP_POINT_TO_PLANE,
+                       max_dist_mean=0.0, min_px_ratio=0.0)
+_VERIFY_DEFAULTS = dict(tau_mm=10, min_model_px=1, min_inlier_ratio=0.0, max_behind_ratio=0.0)
+
+
+def _params_struct(who, struct, defaults, params):
+    """A parameter struct from keyword arguments, the fields not named from `defaults`; None (the library's defaults) when no
+    keyword is given.  TypeError for a keyword that is no field of the struct."""
+    if not params:
+        return None
+    unknown = set(params) - {f[0] for f in struct._fields_}
+    if unknown:
+        raise TypeError(f"{who}: unknown parameters {sorted(unknown)}")
+    return struct(**dict(defaults, **params))
+
+
 class Tracker:
     """fl_tracker: follows objects from frame to frame against their CAD mesh (render at the previous pose, crop, detection()
     from that pose).  Owns its device memory: the mesh, max_frames depth frames of w x h, max_tracks renders and ICP workspaces
@@ -822,6 +839,17 @@ class Tracker:
         dp._frames = depths
         return len(ptrs), dp, device
 
+    def _batch(self, who, what, depths, frame_of, poses, K, dtype):
+        """What track() and verify() hand the library alike: (n_frames, frame pointers, mem, n, frame_of, poses13) to pass on as
+        they are, then the Intrinsics and the zeroed output array."""
+        n_frames, dp, device = self._frames(depths, who)
+        fof = np.ascontiguousarray(frame_of, np.int32).ravel()
+        p = _poses13(poses)
+        if len(p) != len(fof):
+            raise ValueError(f"{who}: one pose per {what}")
+        k = L.Intrinsics(self.w, self.h, *[float(x) for x in K])
+        return (n_frames, dp, L.FL_MEM_DEVICE if device else L.FL_MEM_HOST, len(fof), fof, p), k, np.zeros(max(1, len(fof)), dtype)
+
     def track(self, depths, frame_of_track, poses13, K, **params):
         """One step of every track (fl_track_batch).  depths: the frames, (h, w) u16 numpy arrays in mm, or device tensors
         (anything with data_ptr(): all of one kind); frame_of_track: the frame each track looks at; poses13: (n_tracks, 13)
@@ -829,25 +857,11 @@ class Tracker:
         fl_track_params (margin_px, passes, icp_it_thr, dist_mean_thr, dist_diff_thr, icp_mode, max_dist_mean, min_px_ratio);
         none given = the library's defaults.  Returns a TRACK_DTYPE array, one record per track; feed its poses back in
         (poses13_of) for the next frame."""
-        n, dp, device = self._frames(depths, "Tracker.track")
-        fof = np.ascontiguousarray(frame_of_track, np.int32).ravel()
-        p = _poses13(poses13)
-        if len(p) != len(fof):
-            raise ValueError("Tracker.track: one pose per track")
-        prm = None
-        if params:
-            unknown = set(params) - {f[0] for f in L.TrackParams._fields_}
-            if unknown:
-                raise TypeError(f"Tracker.track: unknown parameters {sorted(unknown)}")
-            d = dict(margin_px=12, passes=1, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01, icp_mode=L.FL_ICP_POINT_TO_PLANE,
-                     max_dist_mean=0.0, min_px_ratio=0.0)
-            d.update(params)
-            prm = L.TrackParams(**d)
-        k = L.Intrinsics(self.w, self.h, *[float(x) for x in K])
-        out = np.zeros(max(1, len(fof)), TRACK_DTYPE)
-        self.ctx.check(self.lib.fl_track_batch(self.handle, n, dp, L.FL_MEM_DEVICE if device else L.FL_MEM_HOST, len(fof), _ptr(fof), _ptr(p),
-                                               C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
-        return out[:len(fof)]
+        (n_frames, dp, mem, n, fof, p), k, out = self._batch("Tracker.track", "track", depths, frame_of_track, poses13, K, TRACK_DTYPE)
+        prm = _params_struct("Tracker.track", L.TrackParams, _TRACK_DEFAULTS, params)
+        self.ctx.check(self.lib.fl_track_batch(self.handle, n_frames, dp, mem, n, _ptr(fof), _ptr(p), C.byref(k),
+                                               None if prm is None else C.byref(prm), _ptr(out)))
+        return out[:n]
 
     def verify(self, depths, frame_of_pose, poses, K, group_first=None, **params):
         """Hypothesis verification (fl_verify_batch): the mesh rendered at every pose with the scene camera K = (fx, fy, cx, cy)
@@ -856,31 +870,16 @@ class Tracker:
         own group, best = accepted) or n_groups + 1 non-decreasing indices from 0 to n; one pose per group at most comes back
         with best = 1.  params: the fields of fl_verify_params (tau_mm, min_model_px, min_inlier_ratio, max_behind_ratio); none
         given = the library's defaults.  Returns a VERIFY_DTYPE array, one record per pose."""
-        n, dp, device = self._frames(depths, "Tracker.verify")
-        fof = np.ascontiguousarray(frame_of_pose, np.int32).ravel()
-        p = _poses13(poses)
-        if len(p) != len(fof):
-            raise ValueError("Tracker.verify: one pose per frame index")
-        gf, n_groups = None, 0
+        (n_frames, dp, mem, n, fof, p), k, out = self._batch("Tracker.verify", "frame index", depths, frame_of_pose, poses, K, VERIFY_DTYPE)
+        gf = None
         if group_first is not None:
             gf = np.ascontiguousarray(group_first, np.int32).ravel()
             if len(gf) < 2:
                 raise ValueError("Tracker.verify: group_first has n_groups + 1 entries")
-            n_groups = len(gf) - 1
-        prm = None
-        if params:
-            unknown = set(params) - {f[0] for f in L.VerifyParams._fields_}
-            if unknown:
-                raise TypeError(f"Tracker.verify: unknown parameters {sorted(unknown)}")
-            d = dict(tau_mm=10, min_model_px=1, min_inlier_ratio=0.0, max_behind_ratio=0.0)
-            d.update(params)
-            prm = L.VerifyParams(**d)
-        k = L.Intrinsics(self.w, self.h, *[float(x) for x in K])
-        out = np.zeros(max(1, len(fof)), VERIFY_DTYPE)
-        self.ctx.check(self.lib.fl_verify_batch(self.handle, n, dp, L.FL_MEM_DEVICE if device else L.FL_MEM_HOST, len(fof), _ptr(fof), _ptr(p),
-                                                n_groups, None if gf is None else _ptr(gf), C.byref(k), None if prm is None else C.byref(prm),
-                                                _ptr(out)))
-        return out[:len(fof)]
+        prm = _params_struct("Tracker.verify", L.VerifyParams, _VERIFY_DEFAULTS, params)
+        self.ctx.check(self.lib.fl_verify_batch(self.handle, n_frames, dp, mem, n, _ptr(fof), _ptr(p), 0 if gf is None else len(gf) - 1,
+                                                None if gf is None else _ptr(gf), C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
+        return out[:n]
 
     def verify_ms(self):
         """DEVELOPMENT ONLY (fl_dev_tracker_verify_ms, not part of the C ABI): device time of the last verify() by stage:

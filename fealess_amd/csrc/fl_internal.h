@@ -1,6 +1,7 @@
 // fl_internal.h -- shared host-side state of libfealess_hip.so (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -69,6 +70,12 @@ int fl_icp_stream(fl_context *ctx, hipStream_t *out);   // the ICP stream for th
   } while (0)
 
 static inline size_t fl_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline bool fl_finite_all(const float *p, size_t n)   // host arrays: meshes, poses
+{
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
 
 // ---- device-side table entries ------------------------------------------------------------
 // Offset of a feature's linear memory relative to the (level, modality) LM base of a frame.

@@ -207,13 +207,6 @@ __global__ __launch_bounds__(256) void k_resolve(RenderArgs a, const unsigned lo
   }
 }
 
-bool finite_all(const float *p, size_t n)
-{
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 // views per chunk: FL_RENDER_CHUNK_VIEWS, fewer when their pixels would pass FL_RENDER_CHUNK_PIXELS
@@ -232,7 +225,7 @@ int fl_render_check_mesh(fl_context *ctx, const char *who, const float *vertices
   for (size_t i = 0; i < nt3; ++i)
     if (triangles[i] < 0 || triangles[i] >= n_vertices)
       return fl_set_error(ctx, FL_ERR_INVALID, "%s: triangle %zu has vertex index %d outside [0, %d)", who, i / 3, triangles[i], n_vertices);
-  if (!finite_all(vertices, nv3) || (normals && !finite_all(normals, nv3)))
+  if (!fl_finite_all(vertices, nv3) || (normals && !fl_finite_all(normals, nv3)))
     return fl_set_error(ctx, FL_ERR_INVALID, "%s: non-finite vertex or normal", who);
   return FL_OK;
 }
@@ -293,7 +286,7 @@ extern "C" int fl_render_views(fl_context *ctx, const float *vertices, const flo
   const size_t nv3 = (size_t)n_vertices * 3, nt3 = (size_t)n_triangles * 3;
   int rc = fl_render_check_mesh(ctx, "fl_render_views", vertices, normals, n_vertices, triangles, n_triangles);
   if (rc) return rc;
-  if (!finite_all(poses13, (size_t)n_views * 13)) return fl_set_error(ctx, FL_ERR_INVALID, "fl_render_views: non-finite pose");
+  if (!fl_finite_all(poses13, (size_t)n_views * 13)) return fl_set_error(ctx, FL_ERR_INVALID, "fl_render_views: non-finite pose");
   const float ll = sqrtf(l2);
 
   FL_HIP(ctx, hipSetDevice(ctx->device));

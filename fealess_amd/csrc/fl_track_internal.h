@@ -1,0 +1,90 @@
+// fl_track_internal.h -- what the tracker's entry points share (fl_track.hip: fl_track_batch, fl_verify.hip: fl_verify_batch;
+// not part of the ABI): the tracker, the layout of its pinned block, and the steps of a call, which fl_track.hip defines.
+#pragma once
+#include "fl_internal.h"
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+
+constexpr int FL_TRACK_EVENTS = 2 + 4 * FL_TRACK_MAX_PASSES;   // start, inputs on the device, then per pass render / rects / ICP / finish
+constexpr int FL_VERIFY_EVENTS = 5;                            // start, inputs on the device, render, score, finish and pick
+constexpr size_t FL_VERIFY_ACC_BYTES = 48;                     // sizeof(FlVerifyAcc), which fl_verify.hip defines and asserts
+
+// p = base + off (base null: a sizing pass, p is left alone); off moves on by bytes rounded up to 256
+template <class T>
+inline void fl_carve(T *&p, uint8_t *base, size_t &off, size_t bytes)
+{
+  if (base) p = (T *)(base + off);
+  off += fl_align(bytes, 256);
+}
+
+// The pinned block a call's inputs leave through and its records come back through, and the one statement of its layout:
+// max_tracks poses of 13 floats | frame indices | records (of fl_track_batch or of fl_verify_batch) | max_tracks + 1 group starts
+struct FlTrackStage { float *poses; int32_t *frame_of; uint8_t *results; int32_t *group_first; };
+inline size_t fl_track_stage(FlTrackStage &s, uint8_t *base, int max_tracks)   // returns the bytes; base null: nothing else
+{
+  const size_t T = (size_t)max_tracks;
+  size_t off = 0;
+  fl_carve(s.poses, base, off, T * 13 * 4);
+  fl_carve(s.frame_of, base, off, T * 4);
+  fl_carve(s.results, base, off, T * std::max(sizeof(fl_track_result), sizeof(fl_verify_result)));
+  fl_carve(s.group_first, base, off, (T + 1) * 4);
+  return off;
+}
+
+struct fl_tracker {
+  fl_context *ctx = nullptr;
+  bool owns_ctx = false;                        // fl_dev_tracker_create_host: a context without a device, released with the tracker
+  int w = 0, h = 0, max_frames = 0, max_tracks = 0, max_crop_px = 0, n_t = 0;
+  int chunk = 0;                                // views per render launch
+  uint8_t *d_mem = nullptr;                     // the one device allocation (carve_device, fl_track.hip)
+  const float *d_vtx = nullptr;
+  const int32_t *d_tri = nullptr;
+  uint8_t *d_frames = nullptr;
+  size_t frame_stride = 0;
+  uint16_t *d_render = nullptr;
+  unsigned long long *d_keys = nullptr;
+  uint8_t *d_icp = nullptr;
+  size_t ws_one = 0;
+  float *d_poses = nullptr, *d_poses_in = nullptr;
+  int32_t *d_frame_of = nullptr, *d_lost = nullptr, *d_class_first = nullptr;
+  FlPyrInfo *d_pyr = nullptr;
+  const uint16_t **d_depth_ptrs = nullptr;
+  FlRefineJob *d_jobs = nullptr;
+  fl_recognition_result *d_res = nullptr;
+  fl_track_result *d_out = nullptr;
+  uint8_t *d_vacc = nullptr;                    // FL_VERIFY_ACC_BYTES per pose: fl_verify.hip's accumulators
+  fl_verify_result *d_vres = nullptr;
+  int32_t *d_group_first = nullptr;             // max_tracks + 1 entries
+  uint8_t *h_stage = nullptr;                   // the one pinned allocation
+  FlTrackStage stage = {};                      // its parts
+  hipEvent_t ev[FL_TRACK_EVENTS + FL_VERIFY_EVENTS] = {nullptr};   // fl_track_batch's, then fl_verify_batch's
+  int last_passes = 0;                          // of the last fl_track_batch; 0: none yet
+  bool verified = false;                        // an fl_verify_batch has completed
+};
+
+// The steps of a call, in the order an entry point takes them.
+// 1. The checks both entry points make, `who` in the text: null pointers (`results` is only tested for null), mem, n_frames and n
+// against the tracker's limits, a null frame, frame_of outside [0, n_frames), a non-finite pose (floats 0..11), K's size against
+// the tracker's, fx, fy finite and > 0 and cx, cy finite AS DOUBLES.  fl_verify_batch then asks the same of them as floats, which
+// is what it hands the rasteriser; fl_track_batch renders at the model camera and reads K in fp64: that one difference is meant.
+// FL_ERR_INVALID or FL_OK, no HIP call.  The entry point's own checks follow, and the device check (FL_ERR_NO_DEVICE) after all.
+int fl_tracker_check_call(fl_tracker *trk, const char *who, int n_frames, const uint16_t *const *depth, int mem, int n, const int32_t *frame_of,
+                          const float *poses13, const fl_intrinsics *K, const void *results);
+// 2. hipSetDevice, the context's streams joined, ev_start, the frames into their slots, then poses13 and frame_of through the
+// pinned block into d_poses and d_frame_of.  poses_keep (null: none): a second device array the poses pass through on their way
+// to d_poses and stay in.
+int fl_tracker_stage(fl_tracker *trk, hipEvent_t ev_start, int n_frames, const uint16_t *const *depth, int mem, int n, const int32_t *frame_of,
+                     const float *poses13, float *poses_keep);
+// 3. the mesh at the first n poses of d_poses, depth only, into d_render, a chunk of views per launch
+int fl_tracker_render(fl_tracker *trk, int n, float fx, float fy, float cx, float cy);
+// 4. bytes of records from d_records to the caller through the pinned block: one copy, one wait for the stream
+int fl_tracker_results(fl_tracker *trk, const void *d_records, size_t bytes, void *results);
+
+// a pixel index into the bounding box of a w-wide image (k_track_rects, k_verify_score)
+__device__ __forceinline__ void bbox_add(int idx, int w, int &x0, int &x1, int &y0, int &y1)
+{
+  const int y = idx / w, x = idx - y * w;
+  x0 = min(x0, x); x1 = max(x1, x);
+  y0 = min(y0, y); y1 = max(y1, y);
+}

@@ -15,6 +15,7 @@ import track_model as TM
 import util
 from fealess_amd import _lib as L
 from fealess_amd import api, synth
+from util import p13 as _p13, pose as _pose
 
 pytestmark = pytest.mark.gpu
 
@@ -29,15 +30,6 @@ POSES = [(10, -5, 720, 0.30, 0.35, 0.10), (-60, 30, 690, -0.50, 0.20, 0.30), (80
          (0, 0, 700, 0.00, 0.30, 0.00), (-100, -60, 760, 1.40, 0.10, 0.25), (120, 70, 680, -1.10, 0.45, -0.15)]
 # how far the scene's object is from the pose a track comes in with: translation (mm), yaw / tilt / roll (rad)
 OFFSETS = [(MOTION_T, MOTION_A), ((-3.0, 3.0, -2.0), (-0.015, 0.01, 0.01)), ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))]
-
-
-def _pose(p, off=((0, 0, 0), (0, 0, 0))):
-    (dx, dy, dz), (da, db, dc) = off
-    return synth.object_pose(p[0] + dx, p[1] + dy, p[2] + dz, p[3] + da, p[4] + db, p[5] + dc)
-
-
-def _p13(p, off=((0, 0, 0), (0, 0, 0))):
-    return synth.pose13(*_pose(p, off))
 
 
 @pytest.fixture(scope="module")

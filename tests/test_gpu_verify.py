@@ -11,9 +11,11 @@ import os
 import numpy as np
 import pytest
 
+import track_model as TM
 import verify_model as VM
 from fealess_amd import _lib as L
 from fealess_amd import api, synth
+from util import p13 as _p13, pose as _pose
 
 pytestmark = pytest.mark.gpu
 
@@ -27,15 +29,6 @@ POSES = [(10, -5, 720, 0.30, 0.35, 0.10), (-60, 30, 690, -0.50, 0.20, 0.30), (80
          (0, 0, 700, 0.00, 0.30, 0.00), (-100, -60, 760, 1.40, 0.10, 0.25), (120, 70, 680, -1.10, 0.45, -0.15)]
 MOTION = ((4.0, -2.0, 3.0), (0.02, -0.01, 0.015))
 YAW, SHIFT = ((0, 0, 0), (1.0, 0, 0)), ((150, 0, 0), (0, 0, 0))
-
-
-def _pose(p, off=((0, 0, 0), (0, 0, 0))):
-    (dx, dy, dz), (da, db, dc) = off
-    return synth.object_pose(p[0] + dx, p[1] + dy, p[2] + dz, p[3] + da, p[4] + db, p[5] + dc)
-
-
-def _p13(p, off=((0, 0, 0), (0, 0, 0))):
-    return synth.pose13(*_pose(p, off))
 
 
 @pytest.fixture(scope="module")
@@ -284,6 +277,36 @@ def test_tracking_is_unchanged_by_a_verify_call_between(tracker, mesh, scenes):
     moved = tracker.verify(scenes, np.arange(6), after["pose"].reshape(-1, 4, 4), K0)
     _same(moved, VM.verify(mesh, scenes, np.arange(6), api.poses13_of(after), K0))
     assert (moved["inlier_ratio"] > got["inlier_ratio"][::-1]).all()
+
+
+def test_verification_is_unchanged_by_a_tracking_call_between(small, mesh, small_case):
+    """The other direction: fl_track_batch leaves its renders x 10 in the images verification renders into, its own poses and
+    frame indices in the arrays both stage through, and the frames in the slots.  Three tracks, two passes, at poses the MODEL
+    camera (608 / 608 / 320 / 240, which is what fl_track_batch renders with) sees inside the 160 x 120 image: t = (-276, -207,
+    700) mm projects to (80, 60).  Then the same verification again, and a shorter one without groups: stale groups, stale
+    poses beyond n and stale accumulators would all show."""
+    c = small_case
+    gf = [0, 5, 5, 12]
+    exp = VM.pick(c["exp"][:12].copy(), gf)
+    v1 = small.verify(c["frames"], c["fof"][:12], c["poses"][:12], KS, group_first=gf)
+    _same(v1, exp)
+    assert exp["best"].sum() == 2 and exp["accepted"].sum() > 2                     # the pick did choose
+    # the tracks' frames show the object where their poses put it, through the model camera: both passes then have something
+    # to hold on to (track_model.step on these frames, two chained steps: tracked, dist_mean 0.99 - 1.06, rects of 157 - 160 x 120)
+    ps = [(-276, -207, 700, 0.3, 0.35, 0.1), (-270, -200, 720, -0.5, 0.2, 0.3), (-282, -212, 690, 0.9, 0.5, -0.2)]
+    tracks = np.stack([_p13(p) for p in ps])
+    fx, fy, cx, cy = TM.MODEL_K
+    seen = [synth.render(WS, HS, *_pose(p), seed=90 + i, fx=fx, fy=fy, cx=cx, cy=cy)[0] for i, p in enumerate(ps)]
+    for p in tracks:                                                                # on the CPU: the model camera sees them
+        r = TM.rects(TM.render(mesh, p, WS, HS), p, TM.MODEL_K, 12)
+        assert r is not None and r[0][2] > 0 and r[0][3] > 0
+    got = small.track(seen, [1, 2, 0], tracks[[1, 2, 0]], TM.MODEL_K, passes=2)
+    print(got[["status", "tracked", "rect_model"]])
+    assert (got["rect_model"][:, 2] > 0).all() and (got["rect_model"][:, 3] > 0).all()
+    v2 = small.verify(c["frames"], c["fof"][:12], c["poses"][:12], KS, group_first=gf)
+    assert v1.tobytes() == v2.tobytes()
+    _same(v2, exp)
+    _same(small.verify(c["frames"], c["fof"][:5], c["poses"][:5], KS), c["exp"][:5])
 
 
 def test_more_poses_than_max_tracks_is_refused(tracker, scenes):

@@ -10,16 +10,12 @@ import pytest
 import verify_model as VM
 from fealess_amd import _lib as L
 from fealess_amd import synth
+from util import p13 as _p13
 
 W, H = 640, 480
 K0 = (608.0, 608.0, 320.0, 240.0)
 POSE = (10, -5, 720, 0.30, 0.35, 0.10)                           # POSES[0] of tests/test_gpu_track.py
 MOTION = ((4.0, -2.0, 3.0), (0.02, -0.01, 0.015))                # that file's one-frame motion: mm, and rad of yaw / tilt / roll
-
-
-def _p13(p, off=((0, 0, 0), (0, 0, 0))):
-    (dx, dy, dz), (da, db, dc) = off
-    return synth.pose13(*synth.object_pose(p[0] + dx, p[1] + dy, p[2] + dz, p[3] + da, p[4] + db, p[5] + dc))
 
 
 @pytest.fixture(scope="module")
@@ -147,12 +143,12 @@ def host_tracker():
     lib.fl_tracker_destroy(h)
 
 
-def _call(lib, trk, **over):
-    """fl_verify_batch with valid arguments (two frames, three poses, two groups) except for what `over` replaces.  Returns (rc,
-    results untouched?)."""
+def _call(lib, tracker, entry="verify", **over):
+    """fl_verify_batch with valid arguments (two frames, three poses, two groups) except for what `over` replaces; entry =
+    "track": fl_track_batch with the arguments the two have in common (its params: NULL).  Returns (rc, results untouched?)."""
     a = dict(n_frames=2, depth=[np.full((TH, TW), 700, np.uint16)] * 2, mem=L.FL_MEM_HOST, n_poses=3, frame_of=[0, 1, 1],
              poses=np.stack([_p13((0, 0, 700, 0.3, 0.35, 0.1))] * 3), n_groups=2, group_first=[0, 1, 3], K=(TW, TH, 60.0, 61.0, 32.0, 24.0),
-             params=(10, 1, 0.0, 0.0), results=True)
+             params=(10, 1, 0.0, 0.0), results=True, trk=tracker)
     a.update(over)
     dp = None
     if a["depth"] is not None:
@@ -162,10 +158,13 @@ def _call(lib, trk, **over):
     gf = None if a["group_first"] is None else np.ascontiguousarray(a["group_first"], np.int32)
     k = None if a["K"] is None else L.Intrinsics(*a["K"])
     prm = None if a["params"] is None else L.VerifyParams(*a["params"])
-    out = np.full(MAX_TRACKS * 64, 0xA5, np.uint8)
-    rc = lib.fl_verify_batch(trk, a["n_frames"], dp, a["mem"], a["n_poses"], None if fof is None else fof.ctypes.data,
-                             None if poses is None else poses.ctypes.data, a["n_groups"], None if gf is None else gf.ctypes.data,
-                             None if k is None else C.byref(k), None if prm is None else C.byref(prm), out.ctypes.data if a["results"] else None)
+    out = np.full(MAX_TRACKS * C.sizeof(L.TrackResult if entry == "track" else L.VerifyResult), 0xA5, np.uint8)
+    common = (a["trk"], a["n_frames"], dp, a["mem"], a["n_poses"], None if fof is None else fof.ctypes.data, None if poses is None else poses.ctypes.data)
+    if entry == "track":
+        rc = lib.fl_track_batch(*common, None if k is None else C.byref(k), None, out.ctypes.data if a["results"] else None)
+    else:
+        rc = lib.fl_verify_batch(*common, a["n_groups"], None if gf is None else gf.ctypes.data, None if k is None else C.byref(k),
+                                 None if prm is None else C.byref(prm), out.ctypes.data if a["results"] else None)
     return rc, bool((out == 0xA5).all())
 
 
@@ -176,7 +175,9 @@ def _bad_pose(value, at):
 
 
 NAN, INF = float("nan"), float("inf")
-INVALID = {
+# what fl_track_batch and fl_verify_batch check alike (fl_tracker_check_call): run against both below
+COMMON_INVALID = {
+    "tracker null": dict(trk=None), "fx negative": dict(K=(TW, TH, -60.0, 61.0, 32.0, 24.0)),
     "depth null": dict(depth=None), "frame_of null": dict(frame_of=None), "poses null": dict(poses=None), "K null": dict(K=None),
     "results null": dict(results=False), "a null frame": dict(depth=[np.zeros((TH, TW), np.uint16), None]),
     "n_frames 0": dict(n_frames=0), "n_frames above max_frames": dict(n_frames=MAX_FRAMES + 1, depth=[np.zeros((TH, TW), np.uint16)] * 3),
@@ -187,8 +188,12 @@ INVALID = {
     "fx nan": dict(K=(TW, TH, NAN, 61.0, 32.0, 24.0)), "fy inf": dict(K=(TW, TH, 60.0, INF, 32.0, 24.0)),
     "cx nan": dict(K=(TW, TH, 60.0, 61.0, NAN, 24.0)), "cy -inf": dict(K=(TW, TH, 60.0, 61.0, 32.0, -INF)),
     "fx 0": dict(K=(TW, TH, 0.0, 61.0, 32.0, 24.0)), "fy negative": dict(K=(TW, TH, 60.0, -61.0, 32.0, 24.0)),
-    "fx 0 as a float": dict(K=(TW, TH, 1e-60, 61.0, 32.0, 24.0)), "cx inf as a float": dict(K=(TW, TH, 60.0, 61.0, 1e300, 24.0)),
     "K width": dict(K=(TW + 1, TH, 60.0, 61.0, 32.0, 24.0)), "K height": dict(K=(TW, TH - 1, 60.0, 61.0, 32.0, 24.0)),
+    "mem 2": dict(mem=2), "mem -1": dict(mem=-1),
+}
+# fl_verify_batch alone: K as floats (what its rasteriser gets), the groups, its parameters
+INVALID = dict(COMMON_INVALID, **{
+    "fx 0 as a float": dict(K=(TW, TH, 1e-60, 61.0, 32.0, 24.0)), "cx inf as a float": dict(K=(TW, TH, 60.0, 61.0, 1e300, 24.0)),
     "group_first[0] != 0": dict(group_first=[1, 1, 3]), "group_first decreasing": dict(group_first=[0, 2, 1, 3], n_groups=3),
     "group_first beyond n_poses in the middle": dict(group_first=[0, 4, 3]),
     "group_first ends before n_poses": dict(group_first=[0, 1, 2]), "group_first ends after n_poses": dict(group_first=[0, 1, 4]),
@@ -197,8 +202,10 @@ INVALID = {
     "tau -1": dict(params=(-1, 1, 0.0, 0.0)), "tau 65536": dict(params=(65536, 1, 0.0, 0.0)), "min_model_px 0": dict(params=(10, 0, 0.0, 0.0)),
     "min_inlier_ratio nan": dict(params=(10, 1, NAN, 0.0)), "max_behind_ratio inf": dict(params=(10, 1, 0.0, INF)),
     "min_inlier_ratio -inf": dict(params=(10, 1, -INF, 0.0)),
-    "mem 2": dict(mem=2), "mem -1": dict(mem=-1),
-}
+})
+# in range for both entry points: the 13th pose float is ignored, frames may be device memory, every slot may be used
+COMMON_VALID = [dict(), dict(poses=_bad_pose(NAN, 12)), dict(mem=L.FL_MEM_DEVICE), dict(n_frames=1, frame_of=[0, 0, 0]),
+                dict(n_poses=MAX_TRACKS, frame_of=[0, 1, 0, 1], poses=np.stack([_p13((0, 0, 700, 0.3, 0.35, 0.1))] * 4), group_first=[0, 2, 4])]
 
 
 @pytest.mark.parametrize("case", sorted(INVALID))
@@ -221,6 +228,28 @@ def test_valid_arguments_reach_the_device_check(host_tracker):
         rc, untouched = _call(lib, trk, **over)
         assert rc == L.FL_ERR_NO_DEVICE and untouched, over
     assert lib.fl_verify_batch(None, 1, None, 0, 1, None, None, 0, None, None, None, None) == L.FL_ERR_INVALID
+
+
+@pytest.mark.parametrize("entry", ["track", "verify"])
+def test_the_common_checks_are_shared_by_both_entry_points(host_tracker, entry):
+    """One list of bad and one of good argument lists against fl_track_batch and fl_verify_batch on one tracker: each refuses
+    the bad ones (FL_ERR_INVALID) and passes the good ones on to the device check (FL_ERR_NO_DEVICE), nothing written."""
+    lib, trk = host_tracker
+    for case, over in COMMON_INVALID.items():
+        rc, untouched = _call(lib, trk, entry, **over)
+        assert rc == L.FL_ERR_INVALID and untouched, (entry, case)
+    for over in COMMON_VALID:
+        rc, untouched = _call(lib, trk, entry, **over)
+        assert rc == L.FL_ERR_NO_DEVICE and untouched, (entry, over)
+
+
+def test_the_one_difference_between_the_entry_points_checks_of_K(host_tracker):
+    """fx = 1e-60 is a positive double and a zero float.  fl_verify_batch hands K to the rasteriser as floats and refuses it;
+    fl_track_batch renders at the model camera and reads the scene's K in fp64, so it passes its argument checks."""
+    lib, trk = host_tracker
+    tiny = dict(K=(TW, TH, 1e-60, 61.0, 32.0, 24.0))
+    assert _call(lib, trk, "verify", **tiny) == (L.FL_ERR_INVALID, True)
+    assert _call(lib, trk, "track", **tiny) == (L.FL_ERR_NO_DEVICE, True)
 
 
 def test_result_record_layout():

@@ -4,6 +4,7 @@ import os
 
 import numpy as np
 
+from fealess_amd import synth
 from fealess_amd.bank import TemplateBank
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -25,6 +26,17 @@ def options(c, opts):
     finally:
         for k, v in before.items():
             c.set_option(k, v)
+
+
+def pose(p, off=((0, 0, 0), (0, 0, 0))):
+    """(R, t) of the synthetic object at p = (tx, ty, tz, yaw, tilt, roll), moved by off = ((dx, dy, dz), (dyaw, dtilt, droll)):
+    what the tracker and verification tests place their objects and hypotheses with."""
+    (dx, dy, dz), (da, db, dc) = off
+    return synth.object_pose(p[0] + dx, p[1] + dy, p[2] + dz, p[3] + da, p[4] + db, p[5] + dc)
+
+
+def p13(p, off=((0, 0, 0), (0, 0, 0))):
+    return synth.pose13(*pose(p, off))
 
 
 def bank_from_arrays(templates, features, poses, levels, modalities, class_id="obj", model_depths=None):

@@ -3,8 +3,8 @@ caller without verification runs to get icp.dist_mean / px_ratio).  Frames of th
 (640 x 480, noise and background on), one pose per frame, each coming in with the previous frame's true pose, frames by device
 pointer, warm, median of --reps calls of the host wall time, for 1, 8 and 64 poses:
   verify  fl_verify_batch with the default parameters, every pose its own group, and once more with groups of up to eight (the
-          pick kernel), with the device time of the last call by stage (copy, render, score, finish; fl_dev_tracker_verify_ms);
-  track   fl_track_batch, one pass, FL_ICP_POINT_TO_PLANE (the default) and FL_ICP_PARITY, with its device time by stage.
+          pick kernel), with the median device time by stage (copy, render, score, finish; fl_dev_tracker_verify_ms);
+  track   fl_track_batch, one pass, FL_ICP_POINT_TO_PLANE (the default) and FL_ICP_PARITY, with its median device time by stage.
 FEALESS_HIP_LIB may name an older build of the library: the entry points it lacks are skipped (only `track` is printed)."""
 import argparse
 import ctypes as C
@@ -41,19 +41,23 @@ def gt(k):
                              0.1 + MOTION_A[2] * k)
 
 
-def median_ms(fn):
+def median_ms(fn, stages):
+    """(median, min, max) of the host wall time of fn() over --reps calls, and the median of every entry of stages(), the device
+    time by stage of the call just made, read outside the timed region."""
     for _ in range(args.warmup):
         fn()
-    t = []
+    t, st = [], []
     for _ in range(args.reps):
         t0 = time.perf_counter()
         fn()
         t.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(t), min(t), max(t)
+        st.append(stages())
+    return statistics.median(t), min(t), max(t), {k: round(statistics.median(s[k] for s in st), 4) for k in st[0]}
 
 
 def line(med, **fields):
-    print(json.dumps(dict(fields, reps=args.reps, median_ms=round(med[0], 3), min_ms=round(med[1], 3), max_ms=round(med[2], 3))), flush=True)
+    print(json.dumps(dict(fields, reps=args.reps, median_ms=round(med[0], 3), min_ms=round(med[1], 3), max_ms=round(med[2], 3), stage_ms=med[3])),
+          flush=True)
 
 
 n_max = max(args.sizes)
@@ -82,9 +86,9 @@ for n in args.sizes:
                                                   C.byref(K), None, out.ctypes.data))
             fn()
             assert (out["n_model"] > 5000).all() and (out["inlier_ratio"] > 0.8).all()
-            med = median_ms(fn)
+            med = median_ms(fn, trk.verify_ms)
             line(med, what="verify", groups=0 if groups is None else len(groups) - 1, poses=n, per_pose_ms=round(med[0] / n, 4),
-                 n_model=int(out["n_model"][0]), stage_ms={k: round(v, 4) for k, v in trk.verify_ms().items()})
+                 n_model=int(out["n_model"][0]))
     out = np.zeros(n, api.TRACK_DTYPE)
     for mode, name in ((L.FL_ICP_POINT_TO_PLANE, "point_to_plane"), (L.FL_ICP_PARITY, "parity")):
         prm = L.TrackParams(12, 1, 10, 0.5, 0.01, mode, 0.0, 0.0)
@@ -94,7 +98,7 @@ for n in args.sizes:
                                              out.ctypes.data))
         fn()
         assert out["tracked"].all()
-        med = median_ms(fn)
-        line(med, what="track", mode=name, passes=1, poses=n, per_pose_ms=round(med[0] / n, 4), stage_ms={k: round(v, 4) for k, v in trk.stage_ms().items()})
+        med = median_ms(fn, trk.stage_ms)
+        line(med, what="track", mode=name, passes=1, poses=n, per_pose_ms=round(med[0] / n, 4))
 trk.close()
 ctx.close()
