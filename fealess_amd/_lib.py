@@ -198,6 +198,10 @@ DEV_SIGNATURES = {
     "fl_dev_cq_window_addr": (None, [C.c_uint, _I, _I, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_I)]),
     "fl_dev_cq_window_taps": (None, [_P, C.c_uint, _I, _I, _I, _I, _P]),
     "fl_dev_scan_items": (_I, [_P, _I, _I, _I, C.c_uint, _P, _I, _P, _I, _P]),
+    "fl_dev_refine_pitch": (_I, [_I, _I]),
+    "fl_dev_refine_plan": (_I, [_P, _I, _I, C.c_long, _I, _P]),
+    "fl_dev_refine_kernel": (_I, [_P, _I]),
+    "fl_dev_refine_window_max": (C.c_long, [_P, _I]),
 }
 
 

@@ -113,6 +113,8 @@ static const FlOptionName fl_option_names[] = {
   {"pipeline_icp", "FL_PIPELINE_ICP", &fl_context::Options::pipeline_icp, false, 0, 3},
   {"frontend_chunk_rows", "FL_FRONTEND_CHUNK_ROWS", &fl_context::Options::frontend_chunk_rows, false, 0, 60 * 1024},
   {"scan_run", "FL_SCAN_RUN", &fl_context::Options::scan_run, false, 0, 64},
+  {"refine_lds", "FL_REFINE_LDS", &fl_context::Options::refine_lds, false, 0, 2},
+  {"refine_lds_bytes", "FL_REFINE_LDS_BYTES", &fl_context::Options::refine_lds_bytes, false, 0, FL_REFINE_LDS_BYTES},
 };
 
 // A value outside an option's range is refused rather than taken for "default": a forced kernel variant with a mistyped
@@ -254,6 +256,7 @@ static void free_device_tables(fl_detector *det)
   (void)hipFree(det->d_scan_items);
   (void)hipFree(det->d_scan_off);
   (void)hipFree(det->d_fine_hdr);
+  (void)hipFree(det->d_fine_box);
   (void)hipFree(det->d_fine_feat);
   (void)hipFree(det->d_pyr);
   (void)hipFree(det->d_poses);
@@ -268,6 +271,7 @@ static void free_device_tables(fl_detector *det)
   det->scan_item_g.clear();
   det->d_scan_off = nullptr;
   det->d_fine_hdr = nullptr;
+  det->d_fine_box = nullptr;
   det->d_fine_feat = nullptr;
   det->d_pyr = nullptr;
   det->d_poses = nullptr;
@@ -634,6 +638,8 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
   std::vector<uint32_t> scan_off;
   std::vector<FlFineHdr> fine_hdr;
   std::vector<FlFineFeat> fine_feat;
+  std::vector<FlFineBox> fine_box;
+  for (int l = 0; l < FL_MAX_LEVELS; ++l) det->refine_window_max[l] = 0;
   std::vector<FlPyrInfo> pyr;
   std::vector<float> poses;
   std::vector<const uint16_t *> depth_ptrs;
@@ -700,8 +706,10 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
       }
       // finer levels: refinement tables (similarityLocal(), linemod.cpp:1226-1300)
       for (int l = 0; l < L - 1; ++l) {
+        FlRect all = {0, 0, -1, -1};                       // the boxes of this pyramid's modalities at this level, united
         for (int m = 0; m < M; ++m) {
           const fl_template &t = tp[l * M + m];
+          FlRect box = {0, 0, -1, -1};
           FlFineHdr h;
           h.feat_begin = (int)fine_feat.size();
           h.feat_count = t.feat_count;
@@ -723,8 +731,21 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
               ff.pad = 0;
             }
             fine_feat.push_back(ff);
+            const FlRect one = {ff.x, ff.y, ff.x, ff.y};
+            box = fl_rect_union(box, one);
           }
           fine_hdr.push_back(h);
+          fine_box.push_back(FlFineBox{(int16_t)box.x0, (int16_t)box.y0, (int16_t)box.x1, (int16_t)box.y1});
+          all = fl_rect_union(all, box);
+        }
+        if (all.x1 >= all.x0) {
+          // the largest window a candidate of this pyramid can ask for: its box grown by a patch's span, no wider or taller
+          // than the image, starting up to 3 bytes early (the window starts at a multiple of 4)
+          const FlLevelGeom &gl = det->geom[l];
+          const int ww = std::min(all.x1 - all.x0 + 15 * gl.T + 1 + 3, (gl.w + 3) & ~3);
+          const int hh = std::min(all.y1 - all.y0 + 15 * gl.T + 1, gl.h);
+          const long bytes = (long)fl_refine_pitch(ww, fl_refine_qmask(gl.T)) * hh;
+          det->refine_window_max[l] = std::max(det->refine_window_max[l], bytes);
         }
       }
     }
@@ -744,6 +765,7 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
   if ((rc = upload(ctx, scan_off, &det->d_scan_off))) return rc;
   if ((rc = upload(ctx, fine_hdr, &det->d_fine_hdr))) return rc;
   if ((rc = upload(ctx, fine_feat, &det->d_fine_feat))) return rc;
+  if ((rc = upload(ctx, fine_box, &det->d_fine_box))) return rc;
   if ((rc = upload(ctx, pyr, &det->d_pyr))) return rc;
   if ((rc = upload(ctx, poses, &det->d_poses))) return rc;
   if ((rc = upload(ctx, class_first, &det->d_class_first))) return rc;

@@ -49,6 +49,9 @@ struct fl_context {
                                 // the launch still fills the device several times over, else 60; a multiple of 60 is used as given
     long scan_run = 0;          // FL_SCAN_RUN: work items a wave of k_scan walks; 0 = FL_SCAN_RUN_AUTO where the launch still fills the
                                 // device several times over, else a shorter run (fl_scan_run); 1 .. 64 is used as given
+    long refine_lds = 0;        // FL_REFINE_LDS: 0 = k_refine_lds where the level's windows fit and the batch fills the device
+                                // (fl_refine_use_lds), 1 = always k_refine, 2 = k_refine_lds wherever the windows fit
+    long refine_lds_bytes = 0;  // FL_REFINE_LDS_BYTES: 0 = the compiled window budget, otherwise a smaller one (tests: group boundaries)
   } opt;
   int detectors = 0;            // live fl_detector objects on this context
   bool destroy_pending = false; // fl_context_destroy was called while detectors were alive: the last one releases the context
@@ -118,6 +121,9 @@ struct FlFineHdr {       // one per (pyramid g, level l < L-1, modality m)
   int32_t feat_begin, feat_count;
   int32_t width, height; // of this template (tp[start].width/height are taken from m == 0)
 };
+struct FlFineBox {       // beside FlFineHdr, same index: bounding box of the features' (x, y); x1 < x0: no features
+  int16_t x0, y0, x1, y1;
+};
 struct FlPyrInfo {       // one per pyramid g
   int32_t class_idx, template_id;
   int32_t off_x0, off_y0, width0, height0;   // template[0]: rect_model_raw (obj_reco_lmicp.cpp:129)
@@ -134,6 +140,80 @@ struct FlRefineJob {     // fl_refine_matches: refine `match` (class-local templ
   int32_t frame;
   fl_match match;
 };
+
+// ---- k_refine_lds: a group of candidates reads its spread bytes from one LDS window --------------------------------
+// A candidate's in-bounds patches lie in a rectangle known before any feature is read: the features' box moved by the
+// candidate's offsets, grown by the 15 * T a patch spans, clipped to the image.  Rectangles are inclusive; x1 < x0: empty.
+#define FL_REFINE_LDS_BYTES 65536  // window budget of a workgroup; with the sort and planning state below it stays under the
+                                   // 70 KB that one retired ICP workgroup leaves on a CU
+#define FL_REFINE_GROUP_MAX 8      // candidates per group: two per wave, whose first modality's sums wait in LDS
+#define FL_REFINE_BLOCK 256        // candidates ordered by location at a time: one per thread
+struct FlRect { int x0, y0, x1, y1; };
+// Pitch rule.  The window starts at x0 rounded down to a multiple of 4 and a row takes `pitch` bytes: a multiple of 16, so the
+// 16-byte staging stores stay inside their row, whose quarter q = pitch / 4 has its bit (q mod 32) set in qmask: the residues
+// at which the 8 rows x 4 column groups that one LDS cycle serves fall on the fewest common banks for this T (fl_refine_qmask).
+__host__ __device__ inline int fl_refine_pitch(int width, uint32_t qmask)
+{
+  int q = (width + 3) >> 2;
+  while (!((qmask >> (q & 31)) & 1u)) ++q;
+  return q * 4;
+}
+// lane (row, cg) of a 32-lane group reads byte row * T * pitch + cg * 4 * T + const: bank (T * (row * q + cg)) mod 32
+__host__ __device__ inline uint32_t fl_refine_qmask(int T)
+{
+  uint32_t mask = 0;
+  int best = 33;
+  for (int q = 0; q < 32; q += 4) {
+    int n[32] = {0}, worst = 0;
+    for (int row = 0; row < 8; ++row)
+      for (int cg = 0; cg < 4; ++cg) {
+        const int b = (T * (row * q + cg)) & 31;
+        if (++n[b] > worst) worst = n[b];
+      }
+    if (worst < best) { best = worst; mask = 0; }
+    if (worst == best) mask |= 1u << q;
+  }
+  return mask;
+}
+__host__ __device__ inline FlRect fl_rect_union(FlRect a, FlRect b)
+{
+  if (a.x1 < a.x0) return b;
+  if (b.x1 < b.x0) return a;
+  FlRect r;
+  r.x0 = a.x0 < b.x0 ? a.x0 : b.x0;
+  r.y0 = a.y0 < b.y0 ? a.y0 : b.y0;
+  r.x1 = a.x1 > b.x1 ? a.x1 : b.x1;
+  r.y1 = a.y1 > b.y1 ? a.y1 : b.y1;
+  return r;
+}
+__host__ __device__ inline long fl_refine_window_bytes(FlRect r, uint32_t qmask)
+{
+  if (r.x1 < r.x0) return 0;
+  return (long)fl_refine_pitch(r.x1 - (r.x0 & ~3) + 1, qmask) * (r.y1 - r.y0 + 1);
+}
+// The planner: the longest prefix of rects[0 .. n) (4 coordinates each, processing order), at most max_len long, whose union
+// window fits `budget` bytes.  At least 1: finalize keeps a level whose largest single window does not fit on k_refine.
+// *uni: the union of the prefix returned.
+template <typename C>
+__host__ __device__ inline int fl_refine_plan(const C *rects, int n, int max_len, long budget, uint32_t qmask, FlRect *uni)
+{
+  FlRect u = {rects[0], rects[1], rects[2], rects[3]};
+  int len = 1;
+  while (len < n && len < max_len) {
+    const C *c = rects + 4 * len;
+    const FlRect r = {c[0], c[1], c[2], c[3]};
+    const FlRect v = fl_rect_union(u, r);
+    if (fl_refine_window_bytes(v, qmask) > budget) break;
+    u = v;
+    ++len;
+  }
+  *uni = u;
+  return len;
+}
+extern "C" int fl_dev_refine_pitch(int width, int T);
+extern "C" int fl_dev_refine_plan(const int32_t *rects, int n, int max_len, long budget, int T, int32_t *uni);
+extern "C" int fl_dev_refine_kernel(const fl_detector *det, int level);   // refine_ran[level]; -1: no such fine level
+extern "C" long fl_dev_refine_window_max(const fl_detector *det, int level);   // refine_window_max[level]; -1: no such fine level
 
 #define FL_TILE 60                 // tile edge in pixels (= CQ_COLS = CQ_CH of k_color_quantize)
 #define FL_TILE_WORDS 16           // bitmap words per frame, level and kind: up to 512 tiles (1280x960: 352)
@@ -194,6 +274,9 @@ struct fl_detector {
   std::vector<int32_t> scan_item_g;      // the items' pyramids on the host (fl_apply_class_filter)
   uint32_t *d_scan_off = nullptr;        // every (pyramid, modality)'s offsets, padded to groups of 8, + FL_SCAN_OFF_PAD
   FlFineHdr *d_fine_hdr = nullptr;       // n_pyr * (L-1) * M, index (g*(L-1)+l)*M+m
+  FlFineBox *d_fine_box = nullptr;       // same index as d_fine_hdr
+  long refine_window_max[FL_MAX_LEVELS] = {0};   // per fine level: LDS bytes of the largest single-candidate window over the bank (fl_refine_window_bytes)
+  int refine_ran[FL_MAX_LEVELS] = {0};   // per fine level, last match stage: 0 none, 1 k_refine, 2 k_refine_lds (fl_dev_refine_kernel)
   FlFineFeat *d_fine_feat = nullptr;
   FlPyrInfo *d_pyr = nullptr;            // n_pyr
   int *d_class_first = nullptr;          // first global pyramid index of each class

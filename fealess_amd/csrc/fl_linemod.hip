@@ -4,6 +4,7 @@
 //   k_build_lm     spread + computeResponseMaps + linearize x8 fused        (:950-1088)
 //   k_scan         similarity + addSimilarities + coarse threshold          (:1130-1214, 1322-1338, 1483-1506)
 //   k_refine       similarityLocal + 16x16 argmax + filter, one level       (:1226-1300, 1509-1573)
+//   k_refine_lds   the same on spread bytes staged in LDS, a group of candidates per window
 //   k_sort_unique  std::sort + std::unique of the surviving matches         (:1437-1439)
 //
 // Data layout in HBM (per frame, per level, per modality): the 8 linear memories
@@ -742,6 +743,289 @@ __global__ __launch_bounds__(256) void k_refine(RefineArgs a)
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// k_refine_lds: k_refine's arithmetic on spread bytes staged in LDS, one 256-thread workgroup per frame.  A frame's
+// candidates sit on a few objects and their windows are nearly the same region, which k_refine fetches again for every
+// candidate, a cache line per lane.  Here the candidates are taken FL_REFINE_BLOCK at a time, ordered by location (a
+// rank sort of (x / T, y / T), column-major, one candidate per thread; erased ones last), and cut into groups: the longest
+// run whose united rectangle fits the window budget (fl_refine_plan, at most FL_REFINE_GROUP_MAX).  Per group and
+// modality the rectangle is staged with coalesced 16-byte loads, then the four waves take the group's candidates
+// round-robin.  Each candidate is refined on its own and written back in place, so neither the order nor the grouping
+// can change a result.  What k_refine reads through refine_slow_path is read from global memory here too.
+// The resources are those one retired ICP workgroup leaves on a CU: 256 threads, <= 128 VGPRs,
+// <= 70 KB of LDS.
+static_assert(FL_MAX_MODALITIES == 2, "the first modality's packed sums wait in LDS while the second is staged");
+static_assert(FL_REFINE_LDS_BYTES + 4 * 64 * FL_REFINE_GROUP_MAX + 10 * FL_REFINE_BLOCK + 64 <= 70 * 1024, "LDS beside three ICP workgroups");
+
+// 16 bytes at p of which only those before `end` exist
+__device__ __noinline__ uint4 refine_stage_tail(const uint8_t *p, const uint8_t *end)
+{
+  uint32_t v[4] = {0, 0, 0, 0};
+  for (int i = 0; i < 16; ++i)
+    if (p + i < end) v[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+  return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// The four responses of a lane to one feature, on its four spread bytes packed in a dword.  The label is the same for the whole
+// wave: every byte is rotated right by it (the reference's LUT is indexed by the rotated byte), then the tests for bit 0
+// (response 4), bits 0x82 (2) and bits 0x44 (1) run on all four bytes at once.  lab is 0 .. 7.
+__device__ __forceinline__ uint32_t refine_resp4(uint32_t p, int lab)
+{
+  const uint32_t M = 0x01010101u;
+  const uint32_t lo = (0xFFu >> lab) * M;                                 // the bits of a byte that a right shift by lab keeps
+  const uint32_t rot = ((p >> lab) & lo) | ((p << (8 - lab)) & ~lo);
+  const uint32_t t1 = rot & M;
+  const uint32_t t2 = ((rot >> 1) | (rot >> 7)) & M;
+  const uint32_t t3 = ((rot >> 2) | (rot >> 6)) & M;
+  const uint32_t n1 = t1 ^ M, n2 = t2 ^ M;
+  return (t1 << 2) | (((t2 << 1) | (t3 & n2)) & ((n1 << 1) | n1));
+}
+
+#ifdef FL_REFINE_STATS
+// development aid: per launch {frames with a candidate, groups, bytes staged (all modalities), candidates refined}, printed by the
+// launcher after a stream synchronisation (tools/dev/README.md)
+__device__ unsigned long long d_refine_stats[4];
+#endif
+
+template <int TT>
+__attribute__((amdgpu_num_vgpr(128)))
+__global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBox *box, int budget, uint32_t qmask)
+{
+  __shared__ __attribute__((aligned(16))) uint8_t s_win[FL_REFINE_LDS_BYTES];
+  // the block's keys while it is ordered, then the groups' packed sums of modality 0 (group slot, lane)
+  __shared__ uint32_t s_keyacc[64 * FL_REFINE_GROUP_MAX > FL_REFINE_BLOCK ? 64 * FL_REFINE_GROUP_MAX : FL_REFINE_BLOCK];
+  __shared__ int16_t s_rect[4 * FL_REFINE_BLOCK];          // in processing order
+  __shared__ uint16_t s_idx[FL_REFINE_BLOCK];              // processing order -> index in the block
+  __shared__ int s_plan[5];                                // the group: length, united rectangle
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  uint8_t *ws = a.ws + (size_t)blockIdx.x * a.ws_stride;
+  const int n = min(*(const int *)(ws + a.off_count), a.cap);
+  FlCand *cand = (FlCand *)(ws + a.off_cand);
+  const int row = lane >> 2, col4 = (lane & 3) * 4;
+  const int T = TT ? TT : a.T, W = a.W, H = a.H;
+  const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
+  for (int blk = 0; blk < n; blk += FL_REFINE_BLOCK) {
+    const int nb = min(FL_REFINE_BLOCK, n - blk);
+    // this thread's candidate: where it is, and the rectangle its in-bounds patches lie in
+    uint32_t key = 0xFFFFFFFFu;
+    FlRect rc = {0, 0, -1, -1};
+    if (tid < nb) {
+      const FlCand cd = cand[blk + tid];
+      if (cd.g >= 0) {
+        const size_t hi = ((size_t)cd.g * a.Lm1 + a.level) * a.M;
+        int x = cd.x * 2 + 1, y = cd.y * 2 + 1;
+        x = max(x, border);
+        y = max(y, border);
+        x = min(x, a.w - a.hdr[hi].width - border);
+        y = min(y, a.h - a.hdr[hi].height - border);
+        const int offset_x = (x / T - 8) * T, offset_y = (y / T - 8) * T;
+        FlRect b = {0, 0, -1, -1};
+        for (int m = 0; m < a.M; ++m) {
+          const FlFineBox fb = box[hi + m];
+          const FlRect one = {fb.x0, fb.y0, fb.x1, fb.y1};
+          b = fl_rect_union(b, one);
+        }
+        if (b.x1 >= b.x0) {
+          rc.x0 = max(0, b.x0 + offset_x);
+          rc.y0 = max(0, b.y0 + offset_y);
+          rc.x1 = min(a.w - 1, b.x1 + offset_x + 15 * T);
+          rc.y1 = min(a.h - 1, b.y1 + offset_y + 15 * T);
+          if (rc.x1 < rc.x0 || rc.y1 < rc.y0) rc = FlRect{0, 0, -1, -1};
+        }
+        key = ((uint32_t)((x / T + 0x4000) & 0x7FFF) << 16) | (uint32_t)((y / T + 0x4000) & 0x7FFF);
+      }
+    }
+    s_keyacc[tid] = key;
+    __syncthreads();
+    if (tid < nb) {
+      int rank = 0;
+      for (int u = 0; u < nb; ++u) {
+        const uint32_t k = s_keyacc[u];
+        rank += (k < key || (k == key && u < tid)) ? 1 : 0;
+      }
+      s_idx[rank] = (uint16_t)tid;
+      s_rect[4 * rank + 0] = (int16_t)rc.x0;
+      s_rect[4 * rank + 1] = (int16_t)rc.y0;
+      s_rect[4 * rank + 2] = (int16_t)rc.x1;
+      s_rect[4 * rank + 3] = (int16_t)rc.y1;
+    }
+    const int nvalid = __syncthreads_count(key != 0xFFFFFFFFu);
+    for (int gs = 0; gs < nvalid;) {
+      if (tid == 0) {
+        FlRect u;
+        s_plan[0] = fl_refine_plan(s_rect + 4 * gs, nvalid - gs, FL_REFINE_GROUP_MAX, (long)budget, qmask, &u);
+        s_plan[1] = u.x0 & ~3;
+        s_plan[2] = u.y0;
+        s_plan[3] = u.x1;
+        s_plan[4] = u.y1;
+      }
+      __syncthreads();
+      const int len = s_plan[0], ux0 = s_plan[1], uy0 = s_plan[2], ux1 = s_plan[3], uy1 = s_plan[4];
+      const bool have = ux1 >= ux0;
+      const int pitch = have ? fl_refine_pitch(ux1 - ux0 + 1, qmask) : 16;
+      const int lane_lds = row * T * pitch + col4 * T;
+#ifdef FL_REFINE_STATS
+      if (tid == 0) {
+        if (blk == 0 && gs == 0) atomicAdd(&d_refine_stats[0], 1ull);
+        atomicAdd(&d_refine_stats[1], 1ull);
+        atomicAdd(&d_refine_stats[2], have ? (unsigned long long)a.M * pitch * (uy1 - uy0 + 1) : 0ull);
+        atomicAdd(&d_refine_stats[3], (unsigned long long)len);
+      }
+#endif
+      for (int m = 0; m < a.M; ++m) {
+        const uint8_t *sp = ws + a.spread_off[m];
+        if (have) {
+          // chunk c = 16 bytes of window row c / cpr; it lands at LDS byte 16 c.  Four loads are in flight per thread before the
+          // first store.  Nothing before the image is read (coordinates are not negative); what would lie past its last byte is
+          // not read either.
+          const int cpr = pitch >> 4, total = (uy1 - uy0 + 1) * cpr;
+          const uint8_t *end = sp + (size_t)a.w * a.h;
+          for (int c0 = tid; c0 < total; c0 += 4 * 256) {
+            uint4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int c = c0 + u * 256;
+              if (c < total) {
+                const int r = c / cpr, j = c - r * cpr;
+                const uint8_t *p = sp + (size_t)(uy0 + r) * a.w + (size_t)(ux0 + 16 * j);
+                v[u] = p + 16 <= end ? ld16(p) : refine_stage_tail(p, end);
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int c = c0 + u * 256;
+              if (c < total) *(uint4 *)(s_win + 16 * (size_t)c) = v[u];
+            }
+          }
+        }
+        __syncthreads();
+        for (int j = wave; j < len; j += 4) {
+          const int ci = blk + s_idx[gs + j];
+          FlCand cd = cand[ci];
+          const int g = __builtin_amdgcn_readfirstlane(cd.g);
+          const FlFineHdr *hdr = a.hdr + ((size_t)g * a.Lm1 + a.level) * a.M;
+          const int max_x = a.w - hdr[0].width - border;                      // :1517-1518 (tp[start])
+          const int max_y = a.h - hdr[0].height - border;
+          int x = __builtin_amdgcn_readfirstlane(cd.x) * 2 + 1, y = __builtin_amdgcn_readfirstlane(cd.y) * 2 + 1;
+          x = max(x, border);
+          y = max(y, border);
+          x = min(x, max_x);
+          y = min(y, max_y);
+          const int offset_x = (x / T - 8) * T, offset_y = (y / T - 8) * T;   // C division (trunc), :1240
+          const int offx_t = offset_x / T, offy_t = offset_y / T;
+          const FlFineHdr h = hdr[m];
+          const FlFineFeat *ff = a.feat + h.feat_begin;
+          const int feat_count = __builtin_amdgcn_readfirstlane(h.feat_count);
+          uint32_t acc = 0;
+          // lane l holds feature l; a feature is then read out of that lane into scalar registers (no LDS round trip between the
+          // window reads of one feature and the next: a step's 32 byte reads are in flight together), so its address arithmetic
+          // and its tests are scalar work
+          int f_xy = 0, f_q = 0, f_g = 0;
+          if (lane < feat_count) {
+            const FlFineFeat f = ff[lane];
+            f_xy = (int)(uint16_t)f.x | ((int)(uint16_t)f.y << 16);
+            f_q = (int)(uint16_t)f.qx | ((int)(uint16_t)f.qy << 16);
+            f_g = (int)f.gx | ((int)f.gy << 8) | ((int)f.label << 16);
+          }
+          // The usual candidate: every patch stays inside the image and its linear memory, which the modality's box tells
+          // without looking at a feature.  Lane l then holds its feature's offset in the window, and a feature costs two lane
+          // reads, one address add, four byte reads and refine_resp4.
+          const FlFineBox fb = box[((size_t)g * a.Lm1 + a.level) * a.M + m];
+          const bool usual = fb.x0 + offset_x >= 0 && fb.y0 + offset_y >= 0 && fb.x1 + offset_x + 16 * T <= a.w &&
+                             fb.y1 + offset_y + 16 * T <= a.h && feat_count <= 64 && __all(((f_g >> 16) & 0xFF) < 8);
+          if (__builtin_amdgcn_readfirstlane((int)usual)) {
+            const int f_off = ((f_xy >> 16) + offset_y - uy0) * pitch + ((int)(int16_t)(f_xy & 0xFFFF) + offset_x - ux0);
+            for (int k = 0; k < feat_count; k += 8) {
+              uint32_t b[8][4];
+#pragma unroll
+              for (int u = 0; u < 8; ++u) {
+                const uint8_t *p0 = s_win + __builtin_amdgcn_readlane(f_off, min(k + u, feat_count - 1)) + lane_lds;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) b[u][c] = p0[c * T];
+              }
+#pragma unroll
+              for (int u = 0; u < 8; ++u) {
+                const int lab = (__builtin_amdgcn_readlane(f_g, min(k + u, feat_count - 1)) >> 16) & 0xFF;
+                const uint32_t r = refine_resp4(b[u][0] | (b[u][1] << 8) | (b[u][2] << 16) | (b[u][3] << 24), lab);
+                acc += k + u < feat_count ? r : 0u;                              // 4 packed u8 adds
+              }
+            }
+          } else
+          for (int k = 0; k < feat_count; k += 8) {
+            uint32_t b[8][4];
+            int lab[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+              const int idx = min(k + u, feat_count - 1);
+              const int xy = __builtin_amdgcn_readlane(f_xy, idx), qq = __builtin_amdgcn_readlane(f_q, idx), gl = __builtin_amdgcn_readlane(f_g, idx);
+              const int fx = (int)(int16_t)(xy & 0xFFFF) + offset_x, fy = (int)(int16_t)(xy >> 16) + offset_y;
+              const bool in = (k + u < feat_count) && fx >= 0 && fy >= 0 && fx < a.w && fy < a.h;   // :1257
+              lab[u] = (gl >> 16) & 0xFF;
+              const int gx = gl & 0xFF, gy = (gl >> 8) & 0xFF;
+              const int lm_x = (int)(int16_t)(qq & 0xFFFF) + offx_t, lm_y = (int)(int16_t)(qq >> 16) + offy_t;
+              if (in && lm_x + 15 < W && lm_y + 15 < H) {                      // wave-uniform: the usual case
+                // position (row, col4 + c) is the pixel (fy + row*T, fx + (col4 + c)*T), inside the staged rectangle
+                const uint8_t *p0 = s_win + ((fy - uy0) * pitch + (fx - ux0)) + lane_lds;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) b[u][c] = p0[c * T];
+              } else {
+                uint32_t r4 = refine_slow_path(sp, in, lm_x + col4, lm_y + row, gx, gy, T, W, H, a.w);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) b[u][c] = (r4 >> (8 * c)) & 0xFFu;
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+              uint32_t packed = 0;
+#pragma unroll
+              for (int c = 0; c < 4; ++c) {
+                const unsigned bb = b[u][c] | (b[u][c] << 8);
+                const unsigned rot = (bb >> lab[u]) & 0xFFu;
+                const unsigned r = (rot & 1u) ? 4u : ((rot & 0x82u) ? 2u : ((rot & 0x44u) ? 1u : 0u));
+                packed |= r << (8 * c);
+              }
+              acc += packed;                                                   // 4 packed u8 adds
+            }
+          }
+          if (m + 1 < a.M) {
+            s_keyacc[j * 64 + lane] = acc;                                     // read back by this lane only
+            continue;
+          }
+          const uint32_t acc0 = a.M > 1 ? s_keyacc[j * 64 + lane] : 0u;
+          const uint32_t tot0 = (acc0 & 0xFFu) + (acc & 0xFFu), tot1 = ((acc0 >> 8) & 0xFFu) + ((acc >> 8) & 0xFFu);
+          const uint32_t tot2 = ((acc0 >> 16) & 0xFFu) + ((acc >> 16) & 0xFFu), tot3 = (acc0 >> 24) + (acc >> 24);
+          int numFeatures = 0;
+          for (int mm = 0; mm < a.M; ++mm) numFeatures += hdr[mm].feat_count;
+          // first strict maximum in row-major order (:1547-1562): key = score << 8 | (255 - pos)
+          const int pos = row * 16 + col4;
+          uint32_t best = (tot0 << 8) | (uint32_t)(255 - pos);
+          best = max(best, (tot1 << 8) | (uint32_t)(254 - pos));
+          best = max(best, (tot2 << 8) | (uint32_t)(253 - pos));
+          best = max(best, (tot3 << 8) | (uint32_t)(252 - pos));
+#pragma unroll
+          for (int s = 32; s >= 1; s >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, s, 64));
+          const int best_score = (int)(best >> 8);
+          int best_r = -1, best_c = -1;                                       // Q4: all-zero patch
+          if (best_score > 0) {
+            const int bp = 255 - (int)(best & 0xFFu);
+            best_r = bp >> 4;
+            best_c = bp & 15;
+          }
+          if (lane == 0) {
+            cd.x = (x / T - 8 + best_c) * T + offset;                         // :1564-1566
+            cd.y = (y / T - 8 + best_r) * T + offset;
+            cd.sim = (best_score * 100.f) / (4 * numFeatures);
+            if (cd.sim < a.threshold) cd.g = -1;                              // MatchPredicate :1447
+            cand[ci] = cd;
+          }
+        }
+        __syncthreads();
+      }
+      gs += len;
+    }
+  }
+}
+
 // k_mark_tiles (lazy fine levels): which 60x60 tiles of level a.level will k_refine read?  One workgroup per
 // frame, one wave per candidate, lane = feature, with k_refine's own arithmetic: a feature whose 16x16 patch stays
 // inside its linear memory reads the spread bytes (fy + r*T, fx + c*T), r, c < 16; the candidate's features span a
@@ -976,6 +1260,38 @@ static int fl_scan_run(const fl_context *ctx, int items, int n_frames)
   return run;
 }
 
+// Which refinement kernel a fine level gets.  k_refine_lds needs every candidate's window to fit the budget (decided from
+// the bank at finalize: refine_window_max) and, being one workgroup per frame, a batch that fills the device: below
+// FL_REFINE_LDS_FRAMES_PER_CU frames per CU k_refine's 4 .. 256 workgroups per frame are faster (profiles/README.md).
+// Option refine_lds: 1 = never, 2 = wherever the windows fit; refine_lds_bytes: a smaller budget.
+#ifndef FL_REFINE_LDS_FRAMES_PER_CU
+#define FL_REFINE_LDS_FRAMES_PER_CU 1
+#endif
+static bool fl_refine_use_lds(const fl_detector *det, int level, int n_frames, long *budget)
+{
+  const fl_context *ctx = det->ctx;
+  *budget = ctx->opt.refine_lds_bytes ? ctx->opt.refine_lds_bytes : (long)FL_REFINE_LDS_BYTES;
+  if (ctx->opt.refine_lds == 1 || det->refine_window_max[level] > *budget) return false;
+  return ctx->opt.refine_lds == 2 || n_frames >= FL_REFINE_LDS_FRAMES_PER_CU * ctx->cus;
+}
+
+extern "C" int fl_dev_refine_pitch(int width, int T) { return fl_refine_pitch(width, fl_refine_qmask(T)); }
+extern "C" int fl_dev_refine_plan(const int32_t *rects, int n, int max_len, long budget, int T, int32_t *uni)
+{
+  FlRect u;
+  const int len = fl_refine_plan(rects, n, max_len, budget, fl_refine_qmask(T), &u);
+  if (uni) { uni[0] = u.x0; uni[1] = u.y0; uni[2] = u.x1; uni[3] = u.y1; }
+  return len;
+}
+extern "C" int fl_dev_refine_kernel(const fl_detector *det, int level)
+{
+  return det && level >= 0 && level < det->L - 1 ? det->refine_ran[level] : -1;
+}
+extern "C" long fl_dev_refine_window_max(const fl_detector *det, int level)
+{
+  return det && level >= 0 && level < det->L - 1 ? det->refine_window_max[level] : -1;
+}
+
 static int launch_scan_refine_sort(fl_detector *det, int n_frames, float threshold, uint16_t *dbg, int dbg_first,
                                    int dbg_count)
 {
@@ -1054,10 +1370,35 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
       if (rc) return rc;
       if (det->have_times) FL_HIP(ctx, hipEventRecord(det->ev[9 + 2 * l], ctx->stream));
     }
-    // few workgroups per frame: candidates are typically tens per frame and idle workgroups are not
-    // free (every wave still fetches the frame's counter); heavy frames just loop longer
-    dim3 grid(n_frames >= 64 ? 4 : (n_frames >= 8 ? 32 : 256), n_frames);
-    hipLaunchKernelGGL(k_refine, grid, dim3(256), 0, ctx->stream, a);
+    long budget;
+    if (fl_refine_use_lds(det, l, n_frames, &budget)) {
+      const uint32_t qmask = fl_refine_qmask(g.T);
+      const dim3 grid(n_frames), block(256);
+      switch (g.T) {
+      case 4: hipLaunchKernelGGL(k_refine_lds<4>, grid, block, 0, ctx->stream, a, det->d_fine_box, (int)budget, qmask); break;
+      case 5: hipLaunchKernelGGL(k_refine_lds<5>, grid, block, 0, ctx->stream, a, det->d_fine_box, (int)budget, qmask); break;
+      case 8: hipLaunchKernelGGL(k_refine_lds<8>, grid, block, 0, ctx->stream, a, det->d_fine_box, (int)budget, qmask); break;
+      default: hipLaunchKernelGGL(k_refine_lds<0>, grid, block, 0, ctx->stream, a, det->d_fine_box, (int)budget, qmask); break;
+      }
+      det->refine_ran[l] = 2;
+#ifdef FL_REFINE_STATS
+      {
+        unsigned long long st[4], zero[4] = {0, 0, 0, 0};
+        FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FL_HIP(ctx, hipMemcpyFromSymbol(st, HIP_SYMBOL(d_refine_stats), sizeof(st)));
+        FL_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(d_refine_stats), zero, sizeof(zero)));
+        fprintf(stderr, "k_refine_lds level %d: %d frames, %llu with candidates, %.2f groups per such frame, %.0f bytes staged per group, "
+                "%.2f candidates per group\n", l, n_frames, st[0], st[0] ? (double)st[1] / st[0] : 0.0, st[1] ? (double)st[2] / st[1] : 0.0,
+                st[1] ? (double)st[3] / st[1] : 0.0);
+      }
+#endif
+    } else {
+      // few workgroups per frame: candidates are typically tens per frame and idle workgroups are not
+      // free (every wave still fetches the frame's counter); heavy frames just loop longer
+      dim3 grid(n_frames >= 64 ? 4 : (n_frames >= 8 ? 32 : 256), n_frames);
+      hipLaunchKernelGGL(k_refine, grid, dim3(256), 0, ctx->stream, a);
+      det->refine_ran[l] = 1;
+    }
     FL_HIP(ctx, hipGetLastError());
   }
   if (det->have_times) FL_HIP(ctx, hipEventRecord(det->ev[4], ctx->stream));

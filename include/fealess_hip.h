@@ -148,14 +148,17 @@ fl_context *fl_detector_get_context(fl_detector *det);
  * the same with that stream at the highest / lowest priority of hipDeviceGetStreamPriorityRange), "frontend_chunk_rows" (0 = a
  * whole-image quantiser launch walks chunks of 120 rows where the batch still fills the device several times over, of 60 otherwise;
  * else that many rows), "scan_run" (0 = a wave of the coarse scan walks 8 work items where the batch still fills the device several
- * times over, and 4, 2 or 1 otherwise; else that many items: 1 is one item per wave), and -- sampled by fl_detector_finalize -- "eager_frontend" (1 = finer pyramid
+ * times over, and 4, 2 or 1 otherwise; else that many items: 1 is one item per wave), "refine_lds" (0 = a fine level is refined by the
+ * kernel that reads a group of candidates' spread bytes from one LDS window where every window of the bank fits it and the batch
+ * has a frame per CU, by the one that reads global memory otherwise; 1 = always the latter; 2 = the former wherever the windows
+ * fit), "refine_lds_bytes" (0 = the compiled window budget of 65536 bytes; else a smaller one), and -- sampled by fl_detector_finalize -- "eager_frontend" (1 = finer pyramid
  * levels in full before the scan, the reference's order), "dev_poison" (1 = what the lazy path leaves uncomputed is filled
  * with 0xFF), "ws_pad" (extra bytes of frame-workspace stride).  Their INITIAL values are read once from the environment
  * when the context is created (FL_SCAN_PRUNE, FL_SCAN_PRUNE_MID (hex), FL_ICP_WIDE, FL_ICP_OCC, FL_ICP_ORDER, FL_ICP_WG_PER_CU,
- * FL_PIPELINE_ICP, FL_FRONTEND_CHUNK_ROWS, FL_SCAN_RUN, FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
+ * FL_PIPELINE_ICP, FL_FRONTEND_CHUNK_ROWS, FL_SCAN_RUN, FL_REFINE_LDS, FL_REFINE_LDS_BYTES, FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
  * process later on changes nothing.  Unknown names: FL_ERR_INVALID.
  * Accepted values: scan_prune, icp_order, eager_frontend, dev_poison {0, 1}; scan_prune_mid -1 .. 0xFF; icp_wide {-1, 0, 1};
- * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; pipeline_icp 0 .. 3; frontend_chunk_rows 0 and the multiples of 60 up to 61440; scan_run 0 .. 64; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
+ * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; pipeline_icp 0 .. 3; frontend_chunk_rows 0 and the multiples of 60 up to 61440; scan_run 0 .. 64; refine_lds 0 .. 2; refine_lds_bytes 0 .. 65536; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
  * FL_ERR_INVALID and leaves the option as it was; an environment value outside its range keeps the built-in default. */
 int  fl_context_set_option(fl_context *ctx, const char *name, long value);
 int  fl_context_get_option(const fl_context *ctx, const char *name, long *value);
