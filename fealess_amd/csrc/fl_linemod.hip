@@ -607,6 +607,71 @@ struct RefineArgs {
   float threshold;
 };
 
+// The reference's refinement arithmetic, once for k_refine, k_refine_lds and k_mark_tiles.
+// Where a candidate of the coarser level lands on this one: doubled, clamped so that the template and the 16x16 patch of
+// T-steps around it stay inside the image, and the patch's first position.
+struct RefinePlace { int x, y, offset_x, offset_y; };
+
+__device__ __forceinline__ RefinePlace refine_place(const RefineArgs &a, const FlFineHdr *hdr, int cx, int cy, int T)
+{
+  const int border = 8 * T;
+  const int max_x = a.w - hdr[0].width - border;                        // :1517-1518 (tp[start])
+  const int max_y = a.h - hdr[0].height - border;
+  RefinePlace p;
+  p.x = min(max(cx * 2 + 1, border), max_x);
+  p.y = min(max(cy * 2 + 1, border), max_y);
+  p.offset_x = (p.x / T - 8) * T;                                       // C division (trunc), :1240
+  p.offset_y = (p.y / T - 8) * T;
+  return p;
+}
+
+// Lane l's feature of a modality in three ints: x | y << 16, qx | qy << 16, gx | gy << 8 | label << 16; zero past the last
+// feature.  One coalesced 12-byte load per lane (<= 63 features <= 64 lanes), after which every feature is read out of a
+// lane's registers -- no per-feature memory round trip.
+struct RefineFeat { int xy, q, g; };
+
+__device__ __forceinline__ RefineFeat refine_load_feat(const FlFineFeat *ff, int feat_count, int lane)
+{
+  RefineFeat r = {0, 0, 0};
+  if (lane < feat_count) {
+    const FlFineFeat f = ff[lane];
+    r.xy = (int)(uint16_t)f.x | ((int)(uint16_t)f.y << 16);
+    r.q = (int)(uint16_t)f.qx | ((int)(uint16_t)f.qy << 16);
+    r.g = (int)f.gx | ((int)f.gy << 8) | ((int)f.label << 16);
+  }
+  return r;
+}
+
+// The end of a candidate: the first strict maximum of the 256 totals in row-major order, the position and similarity written
+// back into its slot, and the filter.
+__device__ __forceinline__ void refine_finish(const RefineArgs &a, uint32_t tot0, uint32_t tot1, uint32_t tot2, uint32_t tot3,
+                                              int numFeatures, const RefinePlace &place, int T, int lane, FlCand cd, FlCand *slot)
+{
+  // first strict maximum in row-major order (:1547-1562): key = score << 8 | (255 - pos)
+  const int pos = (lane >> 2) * 16 + (lane & 3) * 4;
+  uint32_t key = (tot0 << 8) | (uint32_t)(255 - pos);
+  key = max(key, (tot1 << 8) | (uint32_t)(254 - pos));
+  key = max(key, (tot2 << 8) | (uint32_t)(253 - pos));
+  key = max(key, (tot3 << 8) | (uint32_t)(252 - pos));
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, s, 64));
+  const int best_score = (int)(key >> 8);
+  int best_r = -1, best_c = -1;                                         // Q4: all-zero patch
+  if (best_score > 0) {
+    const int bp = 255 - (int)(key & 0xFFu);
+    best_r = bp >> 4;
+    best_c = bp & 15;
+  }
+  if (lane == 0) {
+    const int offset = T / 2 + (T % 2 - 1);
+    cd.x = (place.x / T - 8 + best_c) * T + offset;                     // :1564-1566
+    cd.y = (place.y / T - 8 + best_r) * T + offset;
+    cd.sim = (best_score * 100.f) / (4 * numFeatures);
+    if (cd.sim < a.threshold) cd.g = -1;                                // MatchPredicate :1447
+    *slot = cd;
+  }
+}
+
 #ifndef FL_REFINE_WPE
 #define FL_REFINE_WPE 6           // waves per SIMD; measured (ms per 1280 frames): 4: 0.92, 5 (the compiler's choice): 0.80, 6: 0.76, 8: 1.03
 #endif
@@ -619,55 +684,40 @@ __global__ __launch_bounds__(256) void k_refine(RefineArgs a)
   const int n = min(*(const int *)(ws + a.off_count), a.cap);
   FlCand *cand = (FlCand *)(ws + a.off_cand);
   const int row = lane >> 2, col4 = (lane & 3) * 4;
-  const int T = a.T, W = a.W;
-  const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
+  const int T = a.T, W = a.W, H = a.H;
+  const size_t lane_off = (size_t)row * T * a.w + (size_t)col4 * T;
   for (int ci = blockIdx.x * 4 + wave; ci < n; ci += gridDim.x * 4) {
-    FlCand cd = cand[ci];
+    const FlCand cd = cand[ci];
     const int g = __builtin_amdgcn_readfirstlane(cd.g);
     if (g < 0) continue;
     const FlFineHdr *hdr = a.hdr + ((size_t)g * a.Lm1 + a.level) * a.M;
-    const int max_x = a.w - hdr[0].width - border;                      // :1517-1518 (tp[start])
-    const int max_y = a.h - hdr[0].height - border;
-    int x = __builtin_amdgcn_readfirstlane(cd.x) * 2 + 1, y = __builtin_amdgcn_readfirstlane(cd.y) * 2 + 1;
-    x = max(x, border);
-    y = max(y, border);
-    x = min(x, max_x);
-    y = min(y, max_y);
-    const int offset_x = (x / T - 8) * T, offset_y = (y / T - 8) * T;   // C division (trunc), :1240
+    const RefinePlace place = refine_place(a, hdr, __builtin_amdgcn_readfirstlane(cd.x), __builtin_amdgcn_readfirstlane(cd.y), T);
     uint32_t tot0 = 0, tot1 = 0, tot2 = 0, tot3 = 0;                    // u16 totals of 4 positions
     int numFeatures = 0;
-    const int H = a.H;
-    const int offx_t = offset_x / T, offy_t = offset_y / T;
-    const size_t lane_off = (size_t)row * T * a.w + (size_t)col4 * T;
+    const int offx_t = place.offset_x / T, offy_t = place.offset_y / T;
     for (int m = 0; m < a.M; ++m) {
       const FlFineHdr h = hdr[m];
       numFeatures += h.feat_count;
       const uint8_t *sp = ws + a.spread_off[m];
-      const FlFineFeat *ff = a.feat + h.feat_begin;
+      const RefineFeat feat = refine_load_feat(a.feat + h.feat_begin, h.feat_count, lane);
       uint32_t acc = 0;
       // The reference reads 16 rows x 16 bytes of the feature's linear memory at stride W starting at
       // lm_index (:1260-1297).  Here the same linear index is mapped back to the pixel it was
       // linearised from -- grid cell g, position k = yt*W + xt -> (yt*T + g/T, xt*T + g%T) -- and the
       // response LUT is evaluated on the spread byte.  Running past a row (xt >= W) or past the
       // memory (yt >= H -> next grid cell, past the last one: 0) follows the linear layout exactly.
-      // lane l holds feature l of this template (<= 63 features <= 64 lanes): one coalesced 12-byte
-      // load per lane, after which every feature is broadcast from registers -- no per-feature
-      // memory round trip.  Then 8 features x 4 positions = 32 independent byte loads per step.
-      int f_xy = 0, f_q = 0, f_g = 0;
-      if (lane < h.feat_count) {
-        const FlFineFeat f = ff[lane];
-        f_xy = (int)(uint16_t)f.x | ((int)(uint16_t)f.y << 16);
-        f_q = (int)(uint16_t)f.qx | ((int)(uint16_t)f.qy << 16);
-        f_g = (int)f.gx | ((int)f.gy << 8) | ((int)f.label << 16);
-      }
+      // Every feature is broadcast from the lane that holds it; then 8 features x 4 positions = 32
+      // independent byte loads per step.  k_refine_lds walks the same way (its else branch): shared as one
+      // function template, the walk compiled differently (the LUT as selects) and both kernels measured
+      // slower (profiles/README.md), so each kernel keeps its own.
       for (int k = 0; k < h.feat_count; k += 8) {
         uint32_t b[8][4];
         int lab[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int idx = min(k + u, h.feat_count - 1);                    // wave-uniform
-          const int xy = __shfl(f_xy, idx, 64), qq = __shfl(f_q, idx, 64), gl = __shfl(f_g, idx, 64);
-          const int fx = (int)(int16_t)(xy & 0xFFFF) + offset_x, fy = (int)(int16_t)(xy >> 16) + offset_y;
+          const int xy = __shfl(feat.xy, idx, 64), qq = __shfl(feat.q, idx, 64), gl = __shfl(feat.g, idx, 64);
+          const int fx = (int)(int16_t)(xy & 0xFFFF) + place.offset_x, fy = (int)(int16_t)(xy >> 16) + place.offset_y;
           const bool in = (k + u < h.feat_count) && fx >= 0 && fy >= 0 && fx < a.w && fy < a.h;   // :1257
           lab[u] = (gl >> 16) & 0xFF;
           // offsets are multiples of T, so (f + offset) mod T and div T follow from the stored residues
@@ -718,28 +768,7 @@ __global__ __launch_bounds__(256) void k_refine(RefineArgs a)
       tot2 += (acc >> 16) & 0xFFu;
       tot3 += acc >> 24;
     }
-    // first strict maximum in row-major order (:1547-1562): key = score << 8 | (255 - pos)
-    const int pos = row * 16 + col4;
-    uint32_t key = (tot0 << 8) | (uint32_t)(255 - pos);
-    key = max(key, (tot1 << 8) | (uint32_t)(254 - pos));
-    key = max(key, (tot2 << 8) | (uint32_t)(253 - pos));
-    key = max(key, (tot3 << 8) | (uint32_t)(252 - pos));
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, s, 64));
-    const int best_score = (int)(key >> 8);
-    int best_r = -1, best_c = -1;                                       // Q4: all-zero patch
-    if (best_score > 0) {
-      const int bp = 255 - (int)(key & 0xFFu);
-      best_r = bp >> 4;
-      best_c = bp & 15;
-    }
-    if (lane == 0) {
-      cd.x = (x / T - 8 + best_c) * T + offset;                         // :1564-1566
-      cd.y = (y / T - 8 + best_r) * T + offset;
-      cd.sim = (best_score * 100.f) / (4 * numFeatures);
-      if (cd.sim < a.threshold) cd.g = -1;                              // MatchPredicate :1447
-      cand[ci] = cd;
-    }
+    refine_finish(a, tot0, tot1, tot2, tot3, numFeatures, place, T, lane, cd, cand + ci);
   }
 }
 
@@ -803,7 +832,6 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
   FlCand *cand = (FlCand *)(ws + a.off_cand);
   const int row = lane >> 2, col4 = (lane & 3) * 4;
   const int T = TT ? TT : a.T, W = a.W, H = a.H;
-  const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
   for (int blk = 0; blk < n; blk += FL_REFINE_BLOCK) {
     const int nb = min(FL_REFINE_BLOCK, n - blk);
     // this thread's candidate: where it is, and the rectangle its in-bounds patches lie in
@@ -813,12 +841,8 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
       const FlCand cd = cand[blk + tid];
       if (cd.g >= 0) {
         const size_t hi = ((size_t)cd.g * a.Lm1 + a.level) * a.M;
-        int x = cd.x * 2 + 1, y = cd.y * 2 + 1;
-        x = max(x, border);
-        y = max(y, border);
-        x = min(x, a.w - a.hdr[hi].width - border);
-        y = min(y, a.h - a.hdr[hi].height - border);
-        const int offset_x = (x / T - 8) * T, offset_y = (y / T - 8) * T;
+        const RefinePlace place = refine_place(a, a.hdr + hi, cd.x, cd.y, T);
+        const int offset_x = place.offset_x, offset_y = place.offset_y;
         FlRect b = {0, 0, -1, -1};
         for (int m = 0; m < a.M; ++m) {
           const FlFineBox fb = box[hi + m];
@@ -832,7 +856,7 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
           rc.y1 = min(a.h - 1, b.y1 + offset_y + 15 * T);
           if (rc.x1 < rc.x0 || rc.y1 < rc.y0) rc = FlRect{0, 0, -1, -1};
         }
-        key = ((uint32_t)((x / T + 0x4000) & 0x7FFF) << 16) | (uint32_t)((y / T + 0x4000) & 0x7FFF);
+        key = ((uint32_t)((place.x / T + 0x4000) & 0x7FFF) << 16) | (uint32_t)((place.y / T + 0x4000) & 0x7FFF);
       }
     }
     s_keyacc[tid] = key;
@@ -901,40 +925,26 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
         __syncthreads();
         for (int j = wave; j < len; j += 4) {
           const int ci = blk + s_idx[gs + j];
-          FlCand cd = cand[ci];
+          const FlCand cd = cand[ci];
           const int g = __builtin_amdgcn_readfirstlane(cd.g);
           const FlFineHdr *hdr = a.hdr + ((size_t)g * a.Lm1 + a.level) * a.M;
-          const int max_x = a.w - hdr[0].width - border;                      // :1517-1518 (tp[start])
-          const int max_y = a.h - hdr[0].height - border;
-          int x = __builtin_amdgcn_readfirstlane(cd.x) * 2 + 1, y = __builtin_amdgcn_readfirstlane(cd.y) * 2 + 1;
-          x = max(x, border);
-          y = max(y, border);
-          x = min(x, max_x);
-          y = min(y, max_y);
-          const int offset_x = (x / T - 8) * T, offset_y = (y / T - 8) * T;   // C division (trunc), :1240
-          const int offx_t = offset_x / T, offy_t = offset_y / T;
+          const RefinePlace place = refine_place(a, hdr, __builtin_amdgcn_readfirstlane(cd.x), __builtin_amdgcn_readfirstlane(cd.y), T);
+          const int offx_t = place.offset_x / T, offy_t = place.offset_y / T;
           const FlFineHdr h = hdr[m];
-          const FlFineFeat *ff = a.feat + h.feat_begin;
           const int feat_count = __builtin_amdgcn_readfirstlane(h.feat_count);
           uint32_t acc = 0;
           // lane l holds feature l; a feature is then read out of that lane into scalar registers (no LDS round trip between the
           // window reads of one feature and the next: a step's 32 byte reads are in flight together), so its address arithmetic
           // and its tests are scalar work
-          int f_xy = 0, f_q = 0, f_g = 0;
-          if (lane < feat_count) {
-            const FlFineFeat f = ff[lane];
-            f_xy = (int)(uint16_t)f.x | ((int)(uint16_t)f.y << 16);
-            f_q = (int)(uint16_t)f.qx | ((int)(uint16_t)f.qy << 16);
-            f_g = (int)f.gx | ((int)f.gy << 8) | ((int)f.label << 16);
-          }
+          const RefineFeat feat = refine_load_feat(a.feat + h.feat_begin, feat_count, lane);
           // The usual candidate: every patch stays inside the image and its linear memory, which the modality's box tells
           // without looking at a feature.  Lane l then holds its feature's offset in the window, and a feature costs two lane
           // reads, one address add, four byte reads and refine_resp4.
           const FlFineBox fb = box[((size_t)g * a.Lm1 + a.level) * a.M + m];
-          const bool usual = fb.x0 + offset_x >= 0 && fb.y0 + offset_y >= 0 && fb.x1 + offset_x + 16 * T <= a.w &&
-                             fb.y1 + offset_y + 16 * T <= a.h && feat_count <= 64 && __all(((f_g >> 16) & 0xFF) < 8);
+          const bool usual = fb.x0 + place.offset_x >= 0 && fb.y0 + place.offset_y >= 0 && fb.x1 + place.offset_x + 16 * T <= a.w &&
+                             fb.y1 + place.offset_y + 16 * T <= a.h && feat_count <= 64 && __all(((feat.g >> 16) & 0xFF) < 8);
           if (__builtin_amdgcn_readfirstlane((int)usual)) {
-            const int f_off = ((f_xy >> 16) + offset_y - uy0) * pitch + ((int)(int16_t)(f_xy & 0xFFFF) + offset_x - ux0);
+            const int f_off = ((feat.xy >> 16) + place.offset_y - uy0) * pitch + ((int)(int16_t)(feat.xy & 0xFFFF) + place.offset_x - ux0);
             for (int k = 0; k < feat_count; k += 8) {
               uint32_t b[8][4];
 #pragma unroll
@@ -945,7 +955,7 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
               }
 #pragma unroll
               for (int u = 0; u < 8; ++u) {
-                const int lab = (__builtin_amdgcn_readlane(f_g, min(k + u, feat_count - 1)) >> 16) & 0xFF;
+                const int lab = (__builtin_amdgcn_readlane(feat.g, min(k + u, feat_count - 1)) >> 16) & 0xFF;
                 const uint32_t r = refine_resp4(b[u][0] | (b[u][1] << 8) | (b[u][2] << 16) | (b[u][3] << 24), lab);
                 acc += k + u < feat_count ? r : 0u;                              // 4 packed u8 adds
               }
@@ -957,8 +967,8 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
               const int idx = min(k + u, feat_count - 1);
-              const int xy = __builtin_amdgcn_readlane(f_xy, idx), qq = __builtin_amdgcn_readlane(f_q, idx), gl = __builtin_amdgcn_readlane(f_g, idx);
-              const int fx = (int)(int16_t)(xy & 0xFFFF) + offset_x, fy = (int)(int16_t)(xy >> 16) + offset_y;
+              const int xy = __builtin_amdgcn_readlane(feat.xy, idx), qq = __builtin_amdgcn_readlane(feat.q, idx), gl = __builtin_amdgcn_readlane(feat.g, idx);
+              const int fx = (int)(int16_t)(xy & 0xFFFF) + place.offset_x, fy = (int)(int16_t)(xy >> 16) + place.offset_y;
               const bool in = (k + u < feat_count) && fx >= 0 && fy >= 0 && fx < a.w && fy < a.h;   // :1257
               lab[u] = (gl >> 16) & 0xFF;
               const int gx = gl & 0xFF, gy = (gl >> 8) & 0xFF;
@@ -996,28 +1006,7 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
           const uint32_t tot2 = ((acc0 >> 16) & 0xFFu) + ((acc >> 16) & 0xFFu), tot3 = (acc0 >> 24) + (acc >> 24);
           int numFeatures = 0;
           for (int mm = 0; mm < a.M; ++mm) numFeatures += hdr[mm].feat_count;
-          // first strict maximum in row-major order (:1547-1562): key = score << 8 | (255 - pos)
-          const int pos = row * 16 + col4;
-          uint32_t best = (tot0 << 8) | (uint32_t)(255 - pos);
-          best = max(best, (tot1 << 8) | (uint32_t)(254 - pos));
-          best = max(best, (tot2 << 8) | (uint32_t)(253 - pos));
-          best = max(best, (tot3 << 8) | (uint32_t)(252 - pos));
-#pragma unroll
-          for (int s = 32; s >= 1; s >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, s, 64));
-          const int best_score = (int)(best >> 8);
-          int best_r = -1, best_c = -1;                                       // Q4: all-zero patch
-          if (best_score > 0) {
-            const int bp = 255 - (int)(best & 0xFFu);
-            best_r = bp >> 4;
-            best_c = bp & 15;
-          }
-          if (lane == 0) {
-            cd.x = (x / T - 8 + best_c) * T + offset;                         // :1564-1566
-            cd.y = (y / T - 8 + best_r) * T + offset;
-            cd.sim = (best_score * 100.f) / (4 * numFeatures);
-            if (cd.sim < a.threshold) cd.g = -1;                              // MatchPredicate :1447
-            cand[ci] = cd;
-          }
+          refine_finish(a, tot0, tot1, tot2, tot3, numFeatures, place, T, lane, cd, cand + ci);
         }
         __syncthreads();
       }
@@ -1027,7 +1016,7 @@ __global__ __launch_bounds__(256) void k_refine_lds(RefineArgs a, const FlFineBo
 }
 
 // k_mark_tiles (lazy fine levels): which 60x60 tiles of level a.level will k_refine read?  One workgroup per
-// frame, one wave per candidate, lane = feature, with k_refine's own arithmetic: a feature whose 16x16 patch stays
+// frame, one wave per candidate, lane = feature, with k_refine's own arithmetic (placement: refine_place): a feature whose 16x16 patch stays
 // inside its linear memory reads the spread bytes (fy + r*T, fx + c*T), r, c < 16; the candidate's features span a
 // rectangle, its tiles go into bitmap 0 ("spread bytes read") and the tiles of the rectangle grown by T-1 to the
 // right and below into bitmap 1 ("quantised pixels those spreads are made of").  Anything unusual -- a feature
@@ -1048,28 +1037,21 @@ __global__ __launch_bounds__(256) void k_mark_tiles(RefineArgs a, size_t off_til
   const int n = min(*(const int *)(ws + a.off_count), a.cap);
   const FlCand *cand = (const FlCand *)(ws + a.off_cand);
   const int T = a.T, W = a.W, H = a.H;
-  const int border = 8 * T;
   const int nstrips = (a.w + FL_TILE - 1) / FL_TILE, nchunks = (a.h + FL_TILE - 1) / FL_TILE;
   for (int ci = wave; ci < n; ci += 4) {
     const FlCand cd = cand[ci];
     const int g = __builtin_amdgcn_readfirstlane(cd.g);
     if (g < 0) continue;
     const FlFineHdr *hdr = a.hdr + ((size_t)g * a.Lm1 + a.level) * a.M;
-    const int max_x = a.w - hdr[0].width - border, max_y = a.h - hdr[0].height - border;
-    int x = __builtin_amdgcn_readfirstlane(cd.x) * 2 + 1, y = __builtin_amdgcn_readfirstlane(cd.y) * 2 + 1;
-    x = max(x, border);
-    y = max(y, border);
-    x = min(x, max_x);
-    y = min(y, max_y);
-    const int offset_x = (x / T - 8) * T, offset_y = (y / T - 8) * T;
-    const int offx_t = offset_x / T, offy_t = offset_y / T;
+    const RefinePlace place = refine_place(a, hdr, __builtin_amdgcn_readfirstlane(cd.x), __builtin_amdgcn_readfirstlane(cd.y), T);
+    const int offx_t = place.offset_x / T, offy_t = place.offset_y / T;
     int x0 = INT_MAX, y0 = INT_MAX, x1 = -1, y1 = -1;
     bool odd = false;
     for (int m = 0; m < a.M; ++m) {
       const FlFineHdr h = hdr[m];
       if (lane < h.feat_count) {
         const FlFineFeat f = a.feat[h.feat_begin + lane];
-        const int fx = (int)f.x + offset_x, fy = (int)f.y + offset_y;
+        const int fx = (int)f.x + place.offset_x, fy = (int)f.y + place.offset_y;
         const bool in = fx >= 0 && fy >= 0 && fx < a.w && fy < a.h;
         const int lm_x = (int)f.qx + offx_t, lm_y = (int)f.qy + offy_t;
         if (in && lm_x + 15 < W && lm_y + 15 < H) {
@@ -1113,10 +1095,8 @@ __global__ __launch_bounds__(256) void k_mark_tiles(RefineArgs a, size_t off_til
     out[i] = v;
   }
   for (int i = threadIdx.x; i < 2 * 32 * FL_TILE_WORDS; i += 256) {
-    const int tile = i % (32 * FL_TILE_WORDS);
     uint32_t v = ((uint32_t)rlo[0][i] << 16) | (uint32_t)rhi[0][i];
     if (all) v = (uint32_t)(a.h - 1);                       // rows 0 .. h-1: the consumers clip to their own tile
-    (void)tile;
     out[2 * FL_TILE_WORDS + i] = v;
   }
 }

@@ -70,23 +70,25 @@ def _check(ctx, det, levels, run, exp, n_exp, extra=()):
 
 
 # ---- the cases: quantised pyramid, bank, threshold (also used on the CPU with the oracle alone) ------------------------------
-def case_group_splits():
+def case_group_splits(T=(5, 8), w0=160, h0=160, far=(100, 100), n=40):
     """Two levels at 160 x 160 (the reference asserts that 8 divides the coarse level's 80 rows), 40 templates, half planted
-    around (8, 8) and half around (100, 100)."""
-    w0, h0, T = 160, 160, [5, 8]
+    around (8, 8) and half around (100, 100).  With another fine T (and a size it divides) the fine level takes the paths of
+    "every other T": k_refine's byte loads and k_refine_lds<0>."""
+    T = list(T)
     rng = np.random.default_rng(21)
     qs = _quant_pyramid(rng, w0, h0, 2, 2)
     bank = TemplateBank("obj", 2, 2)
-    for i in range(40):
-        ox, oy = ((8, 8), (100, 100))[i % 2]
+    for i in range(n):
+        ox, oy = ((8, 8), far)[i % 2]
         bank.add_pyramid(_planted_at(rng, qs, 2, 2, ox + 2 * (i % 5), oy + 2 * (i % 3), 32))
     return w0, h0, T, qs, bank, 70.0
 
 
-def case_edges():
+def case_edges(T=(5, 4)):
     """200 x 120 at T = [5, 4]: templates planted at the four image edges and in the corners, and one as large as the image with
-    features outside it, whose patches leave the linear memory (test_quirks_overread_oob_and_big_template)."""
-    w0, h0, T = 200, 120, [5, 4]
+    features outside it, whose patches leave the linear memory (test_quirks_overread_oob_and_big_template).  At T = [2, 4] the
+    same clamping and slow path run under the instantiation for every other T."""
+    w0, h0, T = 200, 120, list(T)
     rng = np.random.default_rng(22)
     qs = _quant_pyramid(rng, w0, h0, 2, 2, density=0.5)
     bank = TemplateBank("obj", 2, 2)
@@ -128,7 +130,10 @@ def case_long_list():
     return w0, h0, T, qs, bank, -100.0
 
 
-CASES = dict(group_splits=case_group_splits, edges=case_edges, three_levels=case_three_levels, one_modality=case_one_modality)
+CASES = dict(group_splits=case_group_splits, edges=case_edges, three_levels=case_three_levels, one_modality=case_one_modality,
+             group_splits_T2=lambda: case_group_splits(T=(2, 8), n=12),
+             group_splits_T6=lambda: case_group_splits(T=(6, 8), w0=192, h0=144, far=(120, 80), n=15),
+             edges_T2=lambda: case_edges(T=(2, 4)))
 
 
 def _detector(ctx, T, M, bank, w0, h0, **kw):
@@ -144,15 +149,15 @@ def test_match_list_equals_oracle_under_every_kernel_and_budget(ctx, oracle, nam
     M = len(qs) // len(T)
     exp, n_exp = oracle.match_quantized(qs, w0, h0, T, [bank], thr)
     assert n_exp > 0, "test is vacuous: no matches"
-    if name == "group_splits":                       # matches at both places
+    if name.startswith("group_splits"):              # matches at both places
         assert (exp["x"] < 60).any() and (exp["x"] > 90).any()
-    if name == "edges":                              # matches whose candidates were clamped on every side, and the big template's
+    if name.startswith("edges"):                     # matches whose candidates were clamped on every side, and the big template's
         assert (exp["x"] < 40).any() and (exp["x"] > w0 - 74).any() and (exp["y"] < 40).any() and (exp["y"] > h0 - 74).any()
         assert (exp["template_id"] == 6).any()
     det = _detector(ctx, T, M, bank, w0, h0)
     try:
         extra = ()
-        if name == "group_splits":                   # one group per frame, several, and the tightest budget the level allows
+        if name.startswith("group_splits"):          # one group per frame, several, and the tightest budget the level allows
             extra = (_window_max(det, 0) + 16 * 108, _window_max(det, 0) * 2)
         _check(ctx, det, len(T), lambda: det.match_quantized(qs, thr), exp, n_exp, extra)
         if name == "three_levels":                   # level 0 meets candidates that level 1 erased
