@@ -89,6 +89,15 @@ class VerifyResult(C.Structure):       # 64 bytes
                 ("sum_abs_inlier", C.c_int64), ("inlier_ratio", C.c_float), ("behind_ratio", C.c_float)]
 
 
+class InstanceVerifyParams(C.Structure):
+    _fields_ = [("verify", VerifyParams), ("class_idx", C.c_int32), ("reserved", C.c_int32)]
+
+
+class VerifiedInstanceResult(C.Structure):
+    _fields_ = [("inst", InstanceResult), ("verify", VerifyResult), ("nms_rank", C.c_int32), ("verified", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
 class StageTimes(C.Structure):
     _fields_ = [("frontend_ms", C.c_float), ("linmem_ms", C.c_float), ("scan_ms", C.c_float), ("refine_ms", C.c_float),
                 ("sort_ms", C.c_float), ("backproject_ms", C.c_float), ("icp_ms", C.c_float), ("total_ms", C.c_float),
@@ -170,6 +179,9 @@ SIGNATURES = {
     "fl_group_matches": (_I, [_P, _P, _I, _I, C.POINTER(InstanceParams), _P, _P, _P]),
     "fl_recognize_batch_instances": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams),
                                           C.POINTER(InstanceParams), _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "fl_recognize_batch_instances_verified": (_I, [_P, _P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics), C.POINTER(RecognitionParams),
+                                                   C.POINTER(InstanceParams), C.POINTER(InstanceVerifyParams), _P, C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), _P]),
     "fl_tracker_create": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_tracker_destroy": (None, [_P]),
     "fl_track_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams), _P]),
@@ -195,6 +207,8 @@ DEV_SIGNATURES = {
     "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_tracker_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
+    "fl_dev_instances_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
+    "fl_dev_pick_verified": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "fl_dev_cq_window_addr": (None, [C.c_uint, _I, _I, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_I)]),
     "fl_dev_cq_window_taps": (None, [_P, C.c_uint, _I, _I, _I, _I, _P]),
     "fl_dev_scan_items": (_I, [_P, _I, _I, _I, C.c_uint, _P, _I, _P, _I, _P]),

@@ -610,6 +610,57 @@ class Detector:
                              n_members=int(res[f * G + g].n_members), n_refined=int(res[f * G + g].n_refined)) for g in range(cnt[f])])
         return (out, [int(v) for v in drop]) if with_dropped else out
 
+    def recognize_batch_instances_verified(self, tracker, bgrs, depths, K, max_instances, min_dist_px, hyp_per_instance, class_idx=-1,
+                                           member_records=False, threshold=75.0, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01,
+                                           mode=L.FL_ICP_PARITY, mem=L.FL_MEM_HOST, **verify):
+        """fl_recognize_batch_instances_verified: recognize_batch_instances whose pick among a group's members is the
+        verification's, against `tracker`'s mesh (a Tracker of the detector's frame size on the same context; only its mesh is
+        used).  verify: the fields of fl_verify_params (tau_mm, min_model_px, min_inlier_ratio, max_behind_ratio), the rest at
+        the library's defaults; class_idx >= 0: only that class's groups are verified.  A list per frame of result dicts as
+        recognize_batch_instances returns them, plus verify (a VERIFY_DTYPE record), nms_rank and verified, in group order.
+        member_records: also a VERIFY_DTYPE array of shape (n_frames, max_instances, hyp_per_instance), every job slot's record."""
+        unknown = set(verify) - set(_VERIFY_DEFAULTS)
+        if unknown:
+            raise TypeError(f"recognize_batch_instances_verified: unknown parameters {sorted(unknown)}")
+        if mem == L.FL_MEM_HOST:
+            bs = [np.ascontiguousarray(b, np.uint8) for b in bgrs]
+            ds = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            bptrs, dptrs = [b.ctypes.data for b in bs], [d.ctypes.data for d in ds]
+        else:
+            bptrs, dptrs = bgrs, depths
+        n = len(bptrs)
+        bp = (C.c_void_p * n)(*bptrs)
+        dp = (C.c_void_p * n)(*dptrs)
+        kk = L.Intrinsics(self.w0, self.h0, *K)
+        p = self._params(threshold, icp_it_thr, dist_mean_thr, dist_diff_thr, mode)
+        ip = L.InstanceParams(max_instances, min_dist_px, hyp_per_instance)
+        vp = L.InstanceVerifyParams(L.VerifyParams(**dict(_VERIFY_DEFAULTS, **verify)), class_idx, 0)
+        G, h = max(1, max_instances), max(1, hyp_per_instance)
+        res = (L.VerifiedInstanceResult * (n * G))()
+        cnt = (C.c_int32 * n)()
+        drop = (C.c_int32 * n)()
+        members = np.zeros((n, G, h), VERIFY_DTYPE) if member_records else None
+        self.ctx.check(self.lib.fl_recognize_batch_instances_verified(self.h, None if tracker is None else tracker.handle, n, bp, dp, mem,
+                                                                      C.byref(kk), C.byref(p), C.byref(ip), C.byref(vp), res, cnt, drop,
+                                                                      None if members is None else _ptr(members)))
+        out = []
+        for f in range(n):
+            row = []
+            for g in range(cnt[f]):
+                r = res[f * G + g]
+                row.append(dict(recognition_result_to_dict(r.inst.reco), rank=int(r.inst.rank), n_members=int(r.inst.n_members),
+                                n_refined=int(r.inst.n_refined), verify=np.frombuffer(bytes(r.verify), VERIFY_DTYPE)[0],
+                                nms_rank=int(r.nms_rank), verified=int(r.verified)))
+            out.append(row)
+        return (out, members) if member_records else out
+
+    def instances_verify_ms(self):
+        """DEVELOPMENT ONLY (fl_dev_instances_verify_ms, not part of the C ABI): device time of the verification stage of the
+        last recognize_batch_instances_verified: dict(fused, finish) in ms."""
+        out = (C.c_float * 2)()
+        self.ctx.check(L.dev(self.lib, "fl_dev_instances_verify_ms")(self.h, out))
+        return dict(fused=float(out[0]), finish=float(out[1]))
+
     def nms(self, n, th_obj_dist):
         """nonMaximumSuppression (ICP/NMS.cpp:6-40) over the first n hypotheses of the last recognize_topk call."""
         win = (C.c_int * max(1, n))()

@@ -245,4 +245,14 @@ struct CadRecoVerifyResult {
 int CadRecoVerify(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult,
                   float tau_mm, vector<CadRecoVerifyResult> *out);
 
+// Opt-in: the verification decides what the multi-instance mode returns (fl_recognize_batch_instances_verified,
+// include/fealess_hip.h).  Every refined member of every group is verified against the mesh of CadRecoSetTrackingMesh behind the
+// frame's one ICP launch, with tau_mm and the two gates (<= 0: no test) as CadRecoVerify and fl_verify_params state them; a
+// group's member is picked by the verification, and Recognition() / CadRecoRecognitionBatch return only the instances whose
+// picked member was accepted, in group order.  Needs CadRecoSetMultiInstance (more than {1, ., 1}) and CadRecoSetTrackingMesh
+// first, and frames that are 640 x 480 after the zoom: ERROR_INVALID_PARAM otherwise, as for tau_mm outside 0..65535 or a
+// threshold that is not finite.  on = 0 switches it off, and Recognition() is again what the multi-instance mode returns;
+// leaving the multi-instance mode switches it off too.
+int CadRecoSetVerifiedPick(CObjRecoCAD *handle, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio);
+
 #endif  // FEALESS_CADRECO_H

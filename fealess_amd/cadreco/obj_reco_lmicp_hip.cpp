@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <sstream>
@@ -196,8 +197,33 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
       // opt-in extension (CadRecoSetMultiInstance): the match list grouped on the device, a few members of each group
       // refined, one result per group in group order
       const int G = m_instances.max_instances;
-      std::vector<fl_instance_result> res((size_t)n * G);
       std::vector<int32_t> cnt(n), dropped(n);
+      if (m_verified) {
+        // opt-in on top of it (CadRecoSetVerifiedPick): each group's member picked by its verification against the tracking mesh,
+        // and only the accepted instances returned
+        std::vector<fl_verified_instance_result> vres((size_t)n * G);
+        const fl_instance_verify_params vp = {m_vparams, -1, 0};
+        if (fl_recognize_batch_instances_verified(m_det, m_tracker, n, bp.data(), dp.data(), FL_MEM_HOST, &k, &m_params, &m_instances, &vp, vres.data(),
+                                                  cnt.data(), dropped.data(), nullptr) != FL_OK) {
+          fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
+          return (int)ERROR_INVALID_PARAM;
+        }
+        for (int i = 0; i < n; ++i) {
+          if (frame_rc) (*frame_rc)[i] = 0;
+          for (int g = 0; g < cnt[i]; ++g) {
+            const fl_verified_instance_result &v = vres[(size_t)i * G + g];
+            const fl_recognition_result &h = v.inst.reco;
+            if (h.status != FL_OK && h.status != FL_ERR_ASSERT) return (int)ERROR_INVALID_PARAM;
+            if (!h.found || !v.verify.accepted) continue;
+            TObjRecoResult o;
+            o.strObjTag = m_class_ids[h.best.class_idx];
+            memcpy(o.tWorld2Cam, h.pose, sizeof(o.tWorld2Cam));
+            out[i].push_back(o);
+          }
+        }
+        return 0;
+      }
+      std::vector<fl_instance_result> res((size_t)n * G);
       if (fl_recognize_batch_instances(m_det, n, bp.data(), dp.data(), FL_MEM_HOST, &k, &m_params, &m_instances, res.data(), cnt.data(),
                                        dropped.data()) != FL_OK) {
         fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
@@ -316,7 +342,22 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return SUCCESS;
   }
 
+  // CadRecoSetVerifiedPick: needs the multi-instance mode and a tracking mesh
+  int SetVerifiedPick(int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio)
+  {
+    if (!on) { m_verified = false; return SUCCESS; }
+    const bool multi_instance = m_instances.max_instances > 1 || m_instances.hyp_per_instance > 1;
+    if (!m_ctx || !multi_instance || !m_tracker || !(tau_mm >= 0.f && tau_mm < 65536.f) || !std::isfinite(min_inlier_ratio) ||
+        !std::isfinite(max_behind_ratio))
+      return (int)ERROR_INVALID_PARAM;
+    m_vparams = fl_verify_params{(int32_t)tau_mm, 1, min_inlier_ratio, max_behind_ratio};
+    m_verified = true;
+    return SUCCESS;
+  }
+
   fl_recognition_params m_params;
+  bool m_verified = false;   // CadRecoSetVerifiedPick; leaving the multi-instance mode clears it
+  fl_verify_params m_vparams = {10, 1, 0.f, 0.f};
   int m_topk = 1;            // > 1: multi-hypothesis mode (CadRecoSetMultiHypothesis)
   float m_nms_dist = 20.0f;  // th_obj_dist of nonMaximumSuppression, mm
   fl_instance_params m_instances = {1, 48, 1};   // max_instances or hyp_per_instance > 1: multi-instance mode (CadRecoSetMultiInstance)
@@ -365,6 +406,7 @@ int CadRecoSetMultiHypothesis(CObjRecoCAD *handle, int k, float nms_dist_mm)
   h->m_topk = k;
   h->m_nms_dist = nms_dist_mm;
   h->m_instances.max_instances = h->m_instances.hyp_per_instance = 1;      // the two modes exclude each other
+  h->m_verified = false;
   return 0;
 }
 
@@ -377,7 +419,15 @@ int CadRecoSetMultiInstance(CObjRecoCAD *handle, int max_instances, int min_dist
   h->m_instances.min_dist_px = min_dist_px;
   h->m_instances.hyp_per_instance = hyp_per_instance;
   h->m_topk = 1;                                                             // the two modes exclude each other
+  if (max_instances == 1 && hyp_per_instance == 1) h->m_verified = false;
   return 0;
+}
+
+int CadRecoSetVerifiedPick(CObjRecoCAD *handle, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h) return (int)ERROR_INVALID_PARAM;
+  return h->SetVerifiedPick(on, tau_mm, min_inlier_ratio, max_behind_ratio);
 }
 
 namespace {
@@ -649,6 +699,10 @@ int cadreco_verify(void *h, const unsigned short *depth, int w, int h_, double t
   const int rc = CadRecoVerify((CObjRecoCAD *)h, d, K, res, tau_mm, &v);
   if (rc == SUCCESS && !v.empty()) memcpy(out, v.data(), v.size() * sizeof(CadRecoVerifyResult));
   return rc;
+}
+int cadreco_set_verified_pick(void *h, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio)
+{
+  return CadRecoSetVerifiedPick((CObjRecoCAD *)h, on, tau_mm, min_inlier_ratio, max_behind_ratio);
 }
 int cadreco_set_tracking_mesh(void *h, const char *obj_path, float scale)
 {

@@ -115,6 +115,8 @@ static const FlOptionName fl_option_names[] = {
   {"scan_run", "FL_SCAN_RUN", &fl_context::Options::scan_run, false, 0, 64},
   {"refine_lds", "FL_REFINE_LDS", &fl_context::Options::refine_lds, false, 0, 2},
   {"refine_lds_bytes", "FL_REFINE_LDS_BYTES", &fl_context::Options::refine_lds_bytes, false, 0, FL_REFINE_LDS_BYTES},
+  {"verify_fused", "FL_VERIFY_FUSED", &fl_context::Options::verify_fused, false, 0, 1},
+  {"verify_fused_px", "FL_VERIFY_FUSED_PX", &fl_context::Options::verify_fused_px, false, 0, FL_VERIFY_FUSED_PX},
 };
 
 // A value outside an option's range is refused rather than taken for "default": a forced kernel variant with a mistyped
@@ -123,6 +125,7 @@ static bool fl_option_valid(const FlOptionName &o, long v)
 {
   if (v < o.lo || v > o.hi) return false;
   if (o.field == &fl_context::Options::frontend_chunk_rows) return v % 60 == 0;
+  if (o.field == &fl_context::Options::verify_fused_px) return v == 0 || v >= FL_WAVE;
   return o.field != &fl_context::Options::icp_occ || v == 0 || v >= 4;
 }
 

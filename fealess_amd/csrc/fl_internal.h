@@ -52,7 +52,12 @@ struct fl_context {
     long refine_lds = 0;        // FL_REFINE_LDS: 0 = k_refine_lds where the level's windows fit and the batch fills the device
                                 // (fl_refine_use_lds), 1 = always k_refine, 2 = k_refine_lds wherever the windows fit
     long refine_lds_bytes = 0;  // FL_REFINE_LDS_BYTES: 0 = the compiled window budget, otherwise a smaller one (tests: group boundaries)
+    long verify_fused = 0;      // FL_VERIFY_FUSED: 1 = fl_verify_batch renders and scores a pose in one workgroup's LDS (k_verify_fused)
+                                // in place of the whole-image render and k_verify_score
+    long verify_fused_px = 0;   // FL_VERIFY_FUSED_PX: 0 = the compiled band budget FL_VERIFY_FUSED_PX, otherwise a smaller one, from
+                                // one wave's 64 pixels up (tests: band boundaries)
   } opt;
+  bool verify_fused_attr = false;   // k_verify_fused's dynamic-LDS limit is set on this context's device (fl_launch_verify_fused)
   int detectors = 0;            // live fl_detector objects on this context
   bool destroy_pending = false; // fl_context_destroy was called while detectors were alive: the last one releases the context
 };
@@ -344,6 +349,7 @@ struct fl_detector {
   hipEvent_t ev[FL_NUM_EVENTS] = {nullptr};   // 0..6 stage boundaries, 7 start of the ICP launches (fl_recognize_submit), 8 + 2l / 9 + 2l around the lazy work of fine level l
   fl_stage_times times;
   bool have_times = false;
+  bool verify_timed = false;             // the last instances call was the verified one: ev[18], ev[19], ev[6] bound its verification (fl_dev_instances_verify_ms)
   double scan_bytes_per_frame = 0;       // SURVEY 8(d) B_tmpl summed over the bank
 };
 
@@ -506,3 +512,31 @@ int fl_render_chunk_views(int w, int h);
 int fl_launch_render_chunk(fl_context *ctx, const FlRenderMesh &mesh, const float *d_poses13, int n_views, int w, int h, float fx, float fy,
                            float cx, float cy, const float light[3], float ambient, unsigned long long *keys, uint8_t *bgr, uint16_t *depth,
                            uint8_t *mask, int32_t *tri);
+// verify
+// k_verify_fused (fl_verify.hip): the mesh rendered at a pose into LDS and scored against the pose's frame, one workgroup per
+// pose, on arrays that are already on the device.  Pose t is the 12 floats [R|t] (row-major, mm) at pose + t * pose_stride;
+// its frame is the w * h u16 at frames + frame_stride * (frame_of ? frame_of[t] : t / per_frame).  With job_idx: pose t is
+// live only when job_idx[t] >= 0, res[t].found == 1 and (class_idx < 0 or res[t].best.class_idx == class_idx); a pose that is
+// not live leaves its accumulator as it is.  acc: FL_VERIFY_ACC_BYTES per pose, written whole for a live pose.
+#define FL_VERIFY_FUSED_PX 36864   // pixels of a band: a 144 KiB z-buffer, one workgroup per CU
+constexpr size_t FL_VERIFY_ACC_BYTES = 48;   // sizeof(FlVerifyAcc), which fl_verify.hip defines and asserts
+struct FlVerifyFusedJob {
+  int n_poses, w, h, tau;
+  float fx, fy, cx, cy;
+  FlRenderMesh mesh;                            // vtx, tri and n_t are read
+  const float *pose;
+  int pose_stride;                              // in floats
+  const uint8_t *frames;
+  size_t frame_stride;                          // in bytes
+  const int32_t *frame_of;
+  int per_frame;
+  const int32_t *job_idx;
+  const fl_recognition_result *res;
+  int class_idx;
+  void *acc;
+};
+int fl_launch_verify_fused(fl_context *ctx, const FlVerifyFusedJob &j);
+// the records of n_poses accumulators (k_verify_finish: rect, ratios, accepted; best = accepted), and fl_verify_params' ranges
+int fl_launch_verify_finish(fl_context *ctx, int n_poses, int w, int h, const fl_verify_params &P, const void *acc, fl_verify_result *out);
+bool fl_verify_params_ok(const fl_verify_params &P);
+#define FL_VERIFY_PARAMS_TEXT "fl_verify_params: tau_mm 0..65535, min_model_px >= 1, finite thresholds"

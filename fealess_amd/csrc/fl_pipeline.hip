@@ -17,7 +17,7 @@
 // when device frames had to be gathered into the frame workspaces (ICP reads the depth there).
 // Every other entry point first makes the context's stream wait for the ICP stream
 // (fl_pipeline_join / fl_context_join).
-#include "fl_internal.h"
+#include "fl_track_internal.h"
 #include <cmath>
 #include <vector>
 #include <string.h>
@@ -542,21 +542,104 @@ __global__ __launch_bounds__(64) void k_pick_instances(const fl_recognition_resu
   out[t] = v;
 }
 
+// The verified pick (fl_recognize_batch_instances_verified, see the header), one thread per (frame, group).  vres: the finished
+// record of every job slot, best = accepted as k_verify_finish leaves it; a verified group's `best` fields are rewritten here.
+// The group's class is its leader's, which every member shares (the grouping rule).
+__global__ __launch_bounds__(64) void k_pick_verified(const fl_recognition_result *__restrict__ res, const FlRefineJob *__restrict__ jobs,
+                                                      const int32_t *__restrict__ job_idx, const int32_t *__restrict__ group_size,
+                                                      const int32_t *__restrict__ info, int n_frames, int G, int h, int class_idx,
+                                                      fl_verify_result *vres, fl_verified_instance_result *__restrict__ out)
+{
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n_frames * G) return;
+  const int f = t / G, g = t - f * G;
+  const int32_t *fi = info + 4 * (size_t)f;
+  if (g == 0) {
+    int32_t *tail = (int32_t *)(out + (size_t)n_frames * G);
+    tail[f] = fi[0];
+    tail[n_frames + f] = fi[1];
+    tail[2 * n_frames + f] = fi[2];
+  }
+  if (g >= fi[0]) return;                                  // the slot stays zeroed
+  const size_t first = (size_t)t * h;
+  int o = -1, size_th = 0, n_refined = 0;                  // k_pick_instances' pick
+  for (int r = 0; r < h && job_idx[first + r] >= 0; ++r) {
+    ++n_refined;
+    const fl_recognition_result &c = res[first + r];
+    if (!c.found) continue;
+    if (o < 0) { o = r; size_th = (int)((double)(float)c.det.n_points * 0.85); }
+    else if (c.det.n_points > size_th && c.det.icp.dist_mean < res[first + o].det.icp.dist_mean) o = r;
+  }
+  if (o < 0) o = 0;
+  const int verified = class_idx < 0 || jobs[first].match.class_idx == class_idx;
+  int pick = o, best = -1;
+  if (verified) {
+    long long bi = 0, bm = 1;
+    for (int r = 0; r < n_refined; ++r) {
+      const fl_verify_result &v = vres[first + r];
+      if (!res[first + r].found || !v.accepted) continue;  // accepted: n_model >= min_model_px >= 1
+      if (best < 0 || (long long)v.n_inlier * bm > bi * (long long)v.n_model) { best = r; bi = v.n_inlier; bm = v.n_model; }
+    }
+    for (int r = 0; r < n_refined; ++r) vres[first + r].best = r == best;
+    if (best >= 0) pick = best;
+  }
+  fl_verified_instance_result v;
+  v.inst.reco = res[first + pick];
+  v.inst.reco.n_matches = fi[3];
+  v.inst.rank = job_idx[first + pick];
+  v.inst.n_members = group_size[t];
+  v.inst.n_refined = n_refined;
+  v.inst.reserved = 0;
+  if (verified) v.verify = vres[first + pick];
+  else memset(&v.verify, 0, sizeof(v.verify));
+  v.nms_rank = job_idx[first + o];
+  v.verified = verified;
+  v.reserved[0] = 0; v.reserved[1] = 0;
+  out[t] = v;
+}
+
+// What fl_recognize_batch_instances_verified adds to the call below (null: fl_recognize_batch_instances as it always was).
+struct InstVerify {
+  fl_tracker *mesh;
+  const fl_instance_verify_params *vp;
+  fl_verified_instance_result *results;
+  fl_verify_result *member_verify;                         // may be null
+};
+
 static int recognize_batch_instances_once(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth, int mem,
                                           const fl_intrinsics *K, const fl_recognition_params *params, const fl_instance_params *ip,
-                                          fl_instance_result *results, int32_t *n_instances, int32_t *n_dropped)
+                                          fl_instance_result *results, int32_t *n_instances, int32_t *n_dropped, const InstVerify *v = nullptr)
 {
-  if (!det || !bgr || n_frames <= 0 || !K || !params || !ip || !results || !n_instances || !n_dropped) return FL_ERR_INVALID;
+  if (!det || !bgr || n_frames <= 0 || !K || !params || !ip || !(v ? (void *)v->results : (void *)results) || !n_instances || !n_dropped)
+    return FL_ERR_INVALID;
   fl_context *ctx = det->ctx;
   if (det->M != 2) return fl_set_error(ctx, FL_ERR_INVALID, "needs the colour + depth modalities");
   if (!fl_instance_params_ok(ip)) return fl_set_error(ctx, FL_ERR_INVALID, FL_INSTANCE_PARAMS_TEXT);
+  float kf[4] = {0.f, 0.f, 0.f, 0.f};                       // the scene camera as floats, which is what the rasteriser gets
+  if (v) {                                                 // refusals that need no device, and so no finalized detector either
+    const char *who = "fl_recognize_batch_instances_verified";
+    if (!v->mesh || !v->vp) return fl_set_error(ctx, FL_ERR_INVALID, "%s: null tracker or fl_instance_verify_params", who);
+    if (!fl_verify_params_ok(v->vp->verify)) return fl_set_error(ctx, FL_ERR_INVALID, FL_VERIFY_PARAMS_TEXT);
+    kf[0] = (float)K->fx; kf[1] = (float)K->fy; kf[2] = (float)K->cx; kf[3] = (float)K->cy;
+    if (!(std::isfinite(kf[0]) && kf[0] > 0.f && std::isfinite(kf[1]) && kf[1] > 0.f && std::isfinite(kf[2]) && std::isfinite(kf[3])))
+      return fl_set_error(ctx, FL_ERR_INVALID, "%s: fx, fy must be finite and > 0, cx, cy finite, as floats too", who);
+    if (v->vp->class_idx < -1 || v->vp->class_idx >= (int)det->classes.size())
+      return fl_set_error(ctx, FL_ERR_INVALID, "%s: class_idx %d outside [-1, %d)", who, v->vp->class_idx, (int)det->classes.size());
+    if (v->mesh->ctx != ctx) return fl_set_error(ctx, FL_ERR_INVALID, "%s: the tracker is on another context", who);
+    if (v->mesh->w != det->w0 || v->mesh->h != det->h0 || v->mesh->w != K->width || v->mesh->h != K->height)
+      return fl_set_error(ctx, FL_ERR_INVALID, "%s: the tracker's %d x %d is not the detector's %d x %d or not K's %d x %d", who, v->mesh->w,
+                          v->mesh->h, det->w0, det->h0, K->width, K->height);
+  }
   int rc = fl_check_frames(det, n_frames);
   if (rc) return rc;
   // Everything that can refuse or fail without the batch comes BEFORE the batch is queued: a return between stage_and_match
   // and input_done would leave the input buffer's read event unrecorded.
   const int G = ip->max_instances, h = ip->hyp_per_instance;
   const size_t jobs = (size_t)n_frames * G * h, ws_one = fl_align(fl_icp_ws_bytes(det->n_pts_max), 256);
-  const size_t icp_bytes = ws_one * jobs, out_bytes = instances_out_bytes(n_frames, G);
+  // the verified variant's output block: its results, the same three ints per frame, then (8-aligned) every slot's record
+  const size_t vout_bytes = fl_align(sizeof(fl_verified_instance_result) * (size_t)n_frames * G + sizeof(int32_t) * 3 * (size_t)n_frames, 8);
+  const size_t icp_bytes = ws_one * jobs, out_bytes = v ? vout_bytes + sizeof(fl_verify_result) * jobs : instances_out_bytes(n_frames, G);
+  const size_t copy_bytes = v && !v->member_verify ? vout_bytes : out_bytes;
   if (jobs > (1u << 20) || icp_bytes > ((size_t)96 << 30))
     return fl_set_error(ctx, FL_ERR_INVALID, "%d frames x %d instances x %d hypotheses need %zu MB of ICP workspaces", n_frames, G, h, icp_bytes >> 20);
   // one scratch block: ICP workspaces, their results, the job list and its list indices, sizes, counters, output -- and the
@@ -567,9 +650,10 @@ static int recognize_batch_instances_once(fl_detector *det, int n_frames, const 
   const size_t o_res = take(sizeof(fl_recognition_result) * jobs), o_jobs = take(sizeof(FlRefineJob) * jobs), o_idx = take(sizeof(int32_t) * jobs);
   const size_t o_gof = take(need_gof ? sizeof(int32_t) * (size_t)det->cap * n_frames : 0), o_size = take(sizeof(int32_t) * (size_t)n_frames * G);
   const size_t o_info = take(sizeof(int32_t) * 4 * (size_t)n_frames), o_out = take(out_bytes);
+  const size_t o_acc = take(v ? FL_VERIFY_ACC_BYTES * jobs : 0);
   void *sv = nullptr, *hv = nullptr;
   FL_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = fl_scratch(ctx, off, &sv)) || (rc = fl_pinned(ctx, out_bytes, &hv))) return rc;
+  if ((rc = fl_scratch(ctx, off, &sv)) || (rc = fl_pinned(ctx, copy_bytes, &hv))) return rc;
   uint8_t *s = (uint8_t *)sv;
   const uint16_t *depth_base = nullptr;
   size_t depth_stride = 0;
@@ -578,6 +662,7 @@ static int recognize_batch_instances_once(fl_detector *det, int n_frames, const 
   fl_recognition_result *d_res = (fl_recognition_result *)(s + o_res);
   FL_HIP(ctx, hipMemsetAsync(d_res, 0, sizeof(fl_recognition_result) * jobs, ctx->stream));
   FL_HIP(ctx, hipMemsetAsync(s + o_out, 0, out_bytes, ctx->stream));
+  if (v) FL_HIP(ctx, hipMemsetAsync(s + o_acc, 0, FL_VERIFY_ACC_BYTES * jobs, ctx->stream));   // a slot that is not live keeps zeros
   FL_HIP(ctx, hipEventRecord(det->ev[16], ctx->stream));
   FlGroupArgs a = fl_group_args(det, ip);
   a.n = det->cap;
@@ -594,19 +679,40 @@ static int recognize_batch_instances_once(fl_detector *det, int n_frames, const 
   if ((rc = fl_launch_group_matches(det, n_frames, a))) return rc;
   FL_HIP(ctx, hipEventRecord(det->ev[17], ctx->stream));
   if ((rc = fl_launch_detection(det, (int)jobs, K, params, depth_base, depth_stride, s, ws_one, 1, a.jobs, d_res, false))) return rc;
-  if ((rc = input_done(det, host_buf))) return rc;
+  if (!v && (rc = input_done(det, host_buf))) return rc;   // the verification reads the frames too
   FL_HIP(ctx, hipEventRecord(det->ev[18], ctx->stream));
-  hipLaunchKernelGGL(k_pick_instances, dim3((n_frames * G + 63) / 64), dim3(64), 0, ctx->stream, d_res, a.job_idx, a.group_size, a.info, n_frames, G, h,
-                     (fl_instance_result *)(s + o_out));
+  if (v) {
+    // every live slot rendered and scored where its pose and its frame lie, the records, then the pick
+    fl_verify_result *d_vres = (fl_verify_result *)(s + o_out + vout_bytes);
+    const fl_tracker *m = v->mesh;
+    const FlVerifyFusedJob j = {(int)jobs, m->w, m->h, v->vp->verify.tau_mm, kf[0], kf[1], kf[2], kf[3], {m->d_vtx, nullptr, nullptr, m->d_tri, m->n_t},
+                                d_res->pose, (int)(sizeof(fl_recognition_result) / sizeof(float)), (const uint8_t *)depth_base, depth_stride, nullptr,
+                                G * h, a.job_idx, d_res, v->vp->class_idx, s + o_acc};
+    if ((rc = fl_launch_verify_fused(ctx, j))) { (void)input_done(det, host_buf); return rc; }   // the frames' last reader, queued or not
+    if ((rc = input_done(det, host_buf))) return rc;
+    FL_HIP(ctx, hipEventRecord(det->ev[19], ctx->stream));
+    if ((rc = fl_launch_verify_finish(ctx, (int)jobs, m->w, m->h, v->vp->verify, s + o_acc, d_vres))) return rc;
+    hipLaunchKernelGGL(k_pick_verified, dim3((n_frames * G + 63) / 64), dim3(64), 0, ctx->stream, d_res, a.jobs, a.job_idx, a.group_size, a.info, n_frames,
+                       G, h, v->vp->class_idx, d_vres, (fl_verified_instance_result *)(s + o_out));
+  } else {
+    hipLaunchKernelGGL(k_pick_instances, dim3((n_frames * G + 63) / 64), dim3(64), 0, ctx->stream, d_res, a.job_idx, a.group_size, a.info, n_frames, G, h,
+                       (fl_instance_result *)(s + o_out));
+  }
   FL_HIP(ctx, hipGetLastError());
   FL_HIP(ctx, hipEventRecord(det->ev[6], ctx->stream));
-  FL_HIP(ctx, hipMemcpyAsync(hv, s + o_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(hv, s + o_out, copy_bytes, hipMemcpyDeviceToHost, ctx->stream));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const fl_instance_result *h_res = (const fl_instance_result *)hv;
-  const int32_t *tail = (const int32_t *)(h_res + (size_t)n_frames * G);
+  det->verify_timed = v != nullptr;
+  const size_t res_size = v ? sizeof(fl_verified_instance_result) : sizeof(fl_instance_result);
+  const int32_t *tail = (const int32_t *)((const uint8_t *)hv + res_size * (size_t)n_frames * G);
   for (int f = 0; f < n_frames; ++f)
     if (tail[2 * n_frames + f] == FL_ERR_OVERFLOW) return fl_set_error(ctx, FL_ERR_OVERFLOW, "frame %d: more than %d candidates", f, det->cap);
-  memcpy(results, h_res, sizeof(fl_instance_result) * (size_t)n_frames * G);
+  if (v) {
+    memcpy(v->results, hv, res_size * (size_t)n_frames * G);
+    if (v->member_verify) memcpy(v->member_verify, (const uint8_t *)hv + vout_bytes, sizeof(fl_verify_result) * jobs);
+  } else {
+    memcpy(results, hv, res_size * (size_t)n_frames * G);
+  }
   memcpy(n_instances, tail, sizeof(int32_t) * (size_t)n_frames);
   memcpy(n_dropped, tail + n_frames, sizeof(int32_t) * (size_t)n_frames);
   // stage times: the ICP stage of this call is grouping + ICP + pick; group_ms is the two new kernels' part of it
@@ -616,7 +722,7 @@ static int recognize_batch_instances_once(fl_detector *det, int n_frames, const 
   if (hipEventElapsedTime(&ms, det->ev[18], det->ev[6]) == hipSuccess) det->times.group_ms += ms;
   for (int f = 0; f < n_frames; ++f)
     for (int g = 0; g < n_instances[f]; ++g) {
-      const fl_recognition_result &r = results[(size_t)f * G + g].reco;
+      const fl_recognition_result &r = v ? v->results[(size_t)f * G + g].inst.reco : results[(size_t)f * G + g].reco;
       det->times.icp_iters_total += r.found ? r.det.icp.iters : 0;        // of the picked hypotheses
     }
   return FL_OK;
@@ -631,6 +737,66 @@ extern "C" int fl_recognize_batch_instances(fl_detector *det, int n_frames, cons
     int rc = recognize_batch_instances_once(det, n_frames, bgr, depth, mem, K, params, ip, results, n_instances, n_dropped);
     if (!fl_grow_after_overflow(det, n_frames, attempt, &rc)) return rc;
   }
+}
+
+extern "C" int fl_recognize_batch_instances_verified(fl_detector *det, fl_tracker *mesh, int n_frames, const uint8_t *const *bgr,
+                                                     const uint16_t *const *depth, int mem, const fl_intrinsics *K,
+                                                     const fl_recognition_params *params, const fl_instance_params *ip,
+                                                     const fl_instance_verify_params *vp, fl_verified_instance_result *results,
+                                                     int32_t *n_instances, int32_t *n_dropped, fl_verify_result *member_verify)
+{
+  const InstVerify v = {mesh, vp, results, member_verify};
+  for (int attempt = 0;; ++attempt) {
+    int rc = recognize_batch_instances_once(det, n_frames, bgr, depth, mem, K, params, ip, nullptr, n_instances, n_dropped, &v);
+    if (!fl_grow_after_overflow(det, n_frames, attempt, &rc)) return rc;
+  }
+}
+
+// device time of the verification stage of the last fl_recognize_batch_instances_verified: {fused verify, finish + pick} in ms
+extern "C" int fl_dev_instances_verify_ms(fl_detector *det, float out[2])
+{
+  if (!det || !out || !det->verify_timed) return FL_ERR_INVALID;
+  if (hipEventElapsedTime(out, det->ev[18], det->ev[19]) != hipSuccess || hipEventElapsedTime(out + 1, det->ev[19], det->ev[6]) != hipSuccess)
+    return FL_ERR_HIP;
+  return FL_OK;
+}
+
+// k_pick_verified on caller-supplied records: n_groups groups of h slots each, laid out as one frame of n_groups groups.  Host
+// arrays: res and jobs and job_idx and vres have n_groups * h entries (vres is read and written back: the `best` fields),
+// group_size n_groups; out n_groups records.  Every group counts as present.
+extern "C" int fl_dev_pick_verified(fl_context *ctx, int n_groups, int h, int class_idx, const fl_recognition_result *res, const FlRefineJob *jobs,
+                                    const int32_t *job_idx, const int32_t *group_size, fl_verify_result *vres, fl_verified_instance_result *out)
+{
+  if (!ctx || n_groups < 1 || n_groups > (1 << 20) || h < 1 || h > FL_GROUP_HYP_MAX || !res || !jobs || !job_idx || !group_size || !vres || !out)
+    return FL_ERR_INVALID;
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_dev_pick_verified: no device");
+  const size_t n = (size_t)n_groups * h;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = fl_align(off + bytes, 256); return o; };
+  const size_t o_res = take(sizeof(*res) * n), o_jobs = take(sizeof(*jobs) * n), o_idx = take(4 * n), o_size = take(4 * (size_t)n_groups), o_info = take(16);
+  const size_t o_vres = take(sizeof(*vres) * n), o_out = take(sizeof(*out) * (size_t)n_groups + 12);
+  void *sv = nullptr;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = fl_context_join(ctx);
+  if (rc || (rc = fl_scratch(ctx, off, &sv))) return rc;
+  uint8_t *s = (uint8_t *)sv;
+  const int32_t info[4] = {n_groups, 0, 0, 0};
+  hipStream_t st = ctx->stream;
+  FL_HIP(ctx, hipMemcpyAsync(s + o_res, res, sizeof(*res) * n, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(s + o_jobs, jobs, sizeof(*jobs) * n, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(s + o_idx, job_idx, 4 * n, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(s + o_size, group_size, 4 * (size_t)n_groups, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(s + o_info, info, 16, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(s + o_vres, vres, sizeof(*vres) * n, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipStreamSynchronize(st));                   // info is on the stack, and the caller's arrays are pageable
+  hipLaunchKernelGGL(k_pick_verified, dim3((n_groups + 63) / 64), dim3(64), 0, st, (const fl_recognition_result *)(s + o_res),
+                     (const FlRefineJob *)(s + o_jobs), (const int32_t *)(s + o_idx), (const int32_t *)(s + o_size), (const int32_t *)(s + o_info), 1,
+                     n_groups, h, class_idx, (fl_verify_result *)(s + o_vres), (fl_verified_instance_result *)(s + o_out));
+  FL_HIP(ctx, hipGetLastError());
+  FL_HIP(ctx, hipMemcpyAsync(vres, s + o_vres, sizeof(*vres) * n, hipMemcpyDeviceToHost, st));
+  FL_HIP(ctx, hipMemcpyAsync(out, s + o_out, sizeof(*out) * (size_t)n_groups, hipMemcpyDeviceToHost, st));
+  FL_HIP(ctx, hipStreamSynchronize(st));
+  return FL_OK;
 }
 
 // nonMaximumSuppression (ICP/NMS.cpp:6-40) over refined hypotheses, in list order.  winners[g] = index of the

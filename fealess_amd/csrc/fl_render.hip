@@ -29,8 +29,7 @@
 // Schedule: the key image of a chunk of views is cleared to 0xFF..; k_raster runs one wave per (view, triangle): the
 // setup is wave-uniform, the lanes stride over the bounding box; k_resolve then turns each pixel's key into the outputs,
 // recomputing the winner's setup for the shading.  The depth test is the vector 64-bit atomic (global_atomic_umin_x2).
-#include "fl_internal.h"
-#include <math.h>
+#include "fl_raster.h"
 #include <algorithm>
 #include <map>
 #include <vector>
@@ -40,83 +39,10 @@ namespace {
 constexpr int RB = 256;                         // k_raster: 4 waves per block, one triangle each
 constexpr unsigned long long KEY_EMPTY = ~0ull;
 
-struct RenderArgs {
-  const float *vtx;                             // n_v * 3
-  const float *nrm;                             // n_v * 3 or NULL
-  const uint8_t *col;                           // n_v * 3 or NULL
-  const int32_t *tri;                           // n_t * 3
-  const float *pose;                            // the chunk's views, 13 floats each
-  int n_t, w, h;
-  float fx, fy, cx, cy, ifx, ify;
-  float lx, ly, lz, ambient;
-};
+// RenderArgs, tri_setup and cover: fl_raster.h, which k_verify_fused (fl_verify.hip) shares
 
-struct F3 { float x, y, z; };
-
-__device__ __forceinline__ F3 cross3(F3 a, F3 b)
-{
-  return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ float dot3(F3 a, F3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ F3 neg3(F3 a) { return F3{-a.x, -a.y, -a.z}; }
-
-__device__ __forceinline__ F3 xform(const float *p, F3 v, bool with_t)
-{
-  F3 o;
-  o.x = (p[0] * v.x + p[1] * v.y) + p[2] * v.z;
-  o.y = (p[4] * v.x + p[5] * v.y) + p[6] * v.z;
-  o.z = (p[8] * v.x + p[9] * v.y) + p[10] * v.z;
-  if (with_t) { o.x = o.x + p[3]; o.y = o.y + p[7]; o.z = o.z + p[11]; }
-  return o;
-}
-
-__device__ __forceinline__ F3 load3(const float *a, int i) { return F3{a[3 * i], a[3 * i + 1], a[3 * i + 2]}; }
-
-struct TriSetup {
-  F3 P[3], c[3], n;
-  float D;
-  bool ok;                                      // false: edge-on (D == 0 or NaN)
-};
-
-__device__ __forceinline__ TriSetup tri_setup(const RenderArgs &a, const float *pose, int t)
-{
-  TriSetup s;
-  for (int k = 0; k < 3; ++k) s.P[k] = xform(pose, load3(a.vtx, a.tri[3 * t + k]), true);
-  s.c[0] = cross3(s.P[1], s.P[2]);
-  s.c[1] = cross3(s.P[2], s.P[0]);
-  s.c[2] = cross3(s.P[0], s.P[1]);
-  const F3 e1{s.P[1].x - s.P[0].x, s.P[1].y - s.P[0].y, s.P[1].z - s.P[0].z};
-  const F3 e2{s.P[2].x - s.P[0].x, s.P[2].y - s.P[0].y, s.P[2].z - s.P[0].z};
-  s.n = cross3(e1, e2);
-  s.D = dot3(s.P[0], s.n);
-  s.ok = s.D > 0.f || s.D < 0.f;
-  if (s.D < 0.f) {
-    for (int k = 0; k < 3; ++k) s.c[k] = neg3(s.c[k]);
-    s.n = neg3(s.n);
-    s.D = -s.D;
-  }
-  return s;
-}
-
-__device__ __forceinline__ bool edge_in(F3 c, float e)
-{
-  return e > 0.f || (e == 0.f && (c.x > 0.f || (c.x == 0.f && c.y > 0.f)));
-}
-
-// Coverage of pixel ray (dx, dy, 1); z and the edge values on success.
-__device__ __forceinline__ bool cover(const TriSetup &s, float dx, float dy, float E[3], float *z)
-{
-  bool in = true;
-  for (int k = 0; k < 3; ++k) {
-    E[k] = (s.c[k].x * dx + s.c[k].y * dy) + s.c[k].z;
-    in = in && edge_in(s.c[k], E[k]);
-  }
-  const float S = (s.n.x * dx + s.n.y * dy) + s.n.z;
-  if (!in || !(S > 0.f)) return false;
-  *z = s.D / S;
-  return *z > 0.f && *z < INFINITY;
-}
-
+// The rejection and the bounding box below are restated by tri_box (fl_verify.hip), whose window is the union of these boxes:
+// the two are bound to each other.
 __global__ __launch_bounds__(RB) void k_raster(RenderArgs a, unsigned long long *keys)
 {
   const int t = blockIdx.x * (RB / FL_WAVE) + (int)(threadIdx.x / FL_WAVE);

@@ -8,7 +8,6 @@
 
 constexpr int FL_TRACK_EVENTS = 2 + 4 * FL_TRACK_MAX_PASSES;   // start, inputs on the device, then per pass render / rects / ICP / finish
 constexpr int FL_VERIFY_EVENTS = 5;                            // start, inputs on the device, render, score, finish and pick
-constexpr size_t FL_VERIFY_ACC_BYTES = 48;                     // sizeof(FlVerifyAcc), which fl_verify.hip defines and asserts
 
 // p = base + off (base null: a sizing pass, p is left alone); off moves on by bytes rounded up to 256
 template <class T>

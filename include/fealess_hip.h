@@ -151,14 +151,16 @@ fl_context *fl_detector_get_context(fl_detector *det);
  * times over, and 4, 2 or 1 otherwise; else that many items: 1 is one item per wave), "refine_lds" (0 = a fine level is refined by the
  * kernel that reads a group of candidates' spread bytes from one LDS window where every window of the bank fits it and the batch
  * has a frame per CU, by the one that reads global memory otherwise; 1 = always the latter; 2 = the former wherever the windows
- * fit), "refine_lds_bytes" (0 = the compiled window budget of 65536 bytes; else a smaller one), and -- sampled by fl_detector_finalize -- "eager_frontend" (1 = finer pyramid
+ * fit), "refine_lds_bytes" (0 = the compiled window budget of 65536 bytes; else a smaller one), "verify_fused" (0; 1 = fl_verify_batch renders
+ * and scores every pose in the LDS of one workgroup, band by band, in place of the whole-image render and the scoring kernel),
+ * "verify_fused_px" (0 = the compiled band budget of 36864 pixels; else a smaller one), and -- sampled by fl_detector_finalize -- "eager_frontend" (1 = finer pyramid
  * levels in full before the scan, the reference's order), "dev_poison" (1 = what the lazy path leaves uncomputed is filled
  * with 0xFF), "ws_pad" (extra bytes of frame-workspace stride).  Their INITIAL values are read once from the environment
  * when the context is created (FL_SCAN_PRUNE, FL_SCAN_PRUNE_MID (hex), FL_ICP_WIDE, FL_ICP_OCC, FL_ICP_ORDER, FL_ICP_WG_PER_CU,
- * FL_PIPELINE_ICP, FL_FRONTEND_CHUNK_ROWS, FL_SCAN_RUN, FL_REFINE_LDS, FL_REFINE_LDS_BYTES, FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
+ * FL_PIPELINE_ICP, FL_FRONTEND_CHUNK_ROWS, FL_SCAN_RUN, FL_REFINE_LDS, FL_REFINE_LDS_BYTES, FL_VERIFY_FUSED, FL_VERIFY_FUSED_PX, FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
  * process later on changes nothing.  Unknown names: FL_ERR_INVALID.
  * Accepted values: scan_prune, icp_order, eager_frontend, dev_poison {0, 1}; scan_prune_mid -1 .. 0xFF; icp_wide {-1, 0, 1};
- * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; pipeline_icp 0 .. 3; frontend_chunk_rows 0 and the multiples of 60 up to 61440; scan_run 0 .. 64; refine_lds 0 .. 2; refine_lds_bytes 0 .. 65536; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
+ * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; pipeline_icp 0 .. 3; frontend_chunk_rows 0 and the multiples of 60 up to 61440; scan_run 0 .. 64; refine_lds 0 .. 2; refine_lds_bytes 0 .. 65536; verify_fused {0, 1}; verify_fused_px 0 and 64 .. 36864; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
  * FL_ERR_INVALID and leaves the option as it was; an environment value outside its range keeps the built-in default. */
 int  fl_context_set_option(fl_context *ctx, const char *name, long value);
 int  fl_context_get_option(const fl_context *ctx, const char *name, long *value);
@@ -569,6 +571,44 @@ int  fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth
                      int n_poses, const int32_t *frame_of_pose, const float *poses13,
                      int n_groups, const int32_t *group_first, const fl_intrinsics *K,
                      const fl_verify_params *params, fl_verify_result *results);
+/* ---- verified instance pick: fl_recognize_batch_instances whose pick among a group's members is the verification's -----------
+ * The call chain of fl_recognize_batch_instances up to and including its ONE ICP launch, then, all on the device and on the
+ * same n_frames * max_instances * hyp_per_instance job slots: the verification of every LIVE slot -- its job exists, its
+ * result has found = 1 and its class passes class_idx -- exactly as fl_verify_batch states it (render at the scene camera
+ * (float)K->fx .., score, finish), with the pose read from the slot's fl_recognition_result::pose (its first 12 floats are the
+ * poses13 layout in mm) and the frame read where the detector's batch has it; then the pick, one copy and one wait.  The
+ * render of a slot stays in the LDS of one workgroup (see the context option verify_fused).  `mesh` supplies its mesh, its
+ * w x h and its context only: none of its frame slots, render images or ICP workspaces is touched, there is no max_tracks
+ * limit, and a fl_track_batch or fl_verify_batch before or after is unaffected.  Accumulators and records come out of the
+ * context's scratch beside the ICP results.
+ * Pick -- a group is VERIFIED when class_idx < 0 or its class is class_idx.  Among a verified group's refined members with
+ * found = 1 and accepted = 1, in list order, a beats b when (int64)n_inlier_a * n_model_b > (int64)n_inlier_b * n_model_a; a
+ * tie goes to the earlier member (fl_verify_batch's rule).  inst.reco / inst.rank are that member's, verify is its record with
+ * best = 1.  A verified group without an accepted member reports fl_recognize_batch_instances' pick with that member's record
+ * (accepted = 0, best = 0; zeros when that member was not found).  A group that is not verified reports that pick, verified = 0
+ * and a zero record.  nms_rank is always the list index fl_recognize_batch_instances picks.  member_verify (NULL: not wanted):
+ * member_verify[(f * max_instances + g) * hyp_per_instance + r] = the finished record of slot r of group g of frame f, best =
+ * 1 on a group's picked accepted member only, all zero for a slot that is absent or not live.
+ * FL_ERR_INVALID, nothing written: what fl_recognize_batch_instances refuses; mesh or vp NULL; a tracker on another context;
+ * the tracker's w x h not the detector's frame size or not K's; the fl_verify_params ranges of fl_verify_batch; fx, fy not
+ * finite and > 0 or cx, cy not finite as floats; class_idx outside [-1, classes). */
+typedef struct {
+  fl_verify_params verify;             /* tau_mm, min_model_px, min_inlier_ratio, max_behind_ratio, as fl_verify_batch */
+  int32_t class_idx;                   /* >= 0: only groups of this class are verified against the mesh; -1: every group */
+  int32_t reserved;
+} fl_instance_verify_params;
+typedef struct {
+  fl_instance_result inst;             /* as fl_recognize_batch_instances, but inst.reco / inst.rank = the verified pick */
+  fl_verify_result verify;             /* of the picked member; zeros when verified == 0 */
+  int32_t nms_rank;                    /* the list index nonMaximumSuppression's rule picks (fl_recognize_batch_instances' rank) */
+  int32_t verified;                    /* 1: the group's members were verified; 0: its class is not class_idx */
+  int32_t reserved[2];
+} fl_verified_instance_result;
+int  fl_recognize_batch_instances_verified(fl_detector *det, fl_tracker *mesh, int n_frames, const uint8_t *const *bgr,
+                                           const uint16_t *const *depth, int mem, const fl_intrinsics *K,
+                                           const fl_recognition_params *params, const fl_instance_params *ip,
+                                           const fl_instance_verify_params *vp, fl_verified_instance_result *results,
+                                           int32_t *n_instances, int32_t *n_dropped, fl_verify_result *member_verify);
 /* After fl_match_frame / fl_recognize_submit: copy frame `frame`'s first k sorted matches into a
  * device buffer (k * sizeof(fl_match) bytes, padded with template_id = -1) for an RCCL
  * all-gather by the caller; template ids are offset by template_id_base (the shard's first

@@ -3,7 +3,9 @@ caller without verification runs to get icp.dist_mean / px_ratio).  Frames of th
 (640 x 480, noise and background on), one pose per frame, each coming in with the previous frame's true pose, frames by device
 pointer, warm, median of --reps calls of the host wall time, for 1, 8 and 64 poses:
   verify  fl_verify_batch with the default parameters, every pose its own group, and once more with groups of up to eight (the
-          pick kernel), with the median device time by stage (copy, render, score, finish; fl_dev_tracker_verify_ms);
+          pick kernel), with the median device time by stage (copy, render, score, finish; fl_dev_tracker_verify_ms); where the
+          library has the option, with verify_fused 0 and 1 (then `score` is k_verify_fused and `render` is empty), the latter at
+          every band budget of --fused-px (0 = the compiled one);
   track   fl_track_batch, one pass, FL_ICP_POINT_TO_PLANE (the default) and FL_ICP_PARITY, with its median device time by stage.
 FEALESS_HIP_LIB may name an older build of the library: the entry points it lacks are skipped (only `track` is printed)."""
 import argparse
@@ -30,6 +32,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=25)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--sizes", type=int, nargs="+", default=[1, 8, 64])
+ap.add_argument("--fused-px", type=int, nargs="+", default=[0])
 args = ap.parse_args()
 
 W, H, K0 = 640, 480, (608.0, 608.0, 320.0, 240.0)
@@ -72,6 +75,11 @@ ctx = api.Context(0)
 mesh = synth.object_mesh(2)
 trk = api.Tracker(ctx, mesh["vertices"], mesh["triangles"], W, H, n_max, n_max, 40000)
 K = L.Intrinsics(W, H, *K0)
+try:
+    ctx.get_option("verify_fused")
+    variants = [(0, 0)] + [(1, px) for px in args.fused_px]
+except api.FealessError:
+    variants = [(None, None)]
 for n in args.sizes:
     dp = (C.c_void_p * n)(*dptr[:n])
     fof = np.arange(n, dtype=np.int32)
@@ -79,7 +87,11 @@ for n in args.sizes:
     if "fl_verify_batch" in L.SIGNATURES:
         out = np.zeros(n, api.VERIFY_DTYPE)
         gf = np.ascontiguousarray(list(range(0, n, 8)) + [n], np.int32)
-        for groups in (None, gf):
+        for groups, (fused, px) in ((g, v) for g in (None, gf) for v in variants):
+            if fused is not None:
+                ctx.set_option("verify_fused", fused)
+                ctx.set_option("verify_fused_px", px)
+
             def fn():           # raw ctypes: the same host work as the track call below
                 ctx.check(trk.lib.fl_verify_batch(trk.handle, n, dp, L.FL_MEM_DEVICE, n, fof.ctypes.data, p13.ctypes.data,
                                                   0 if groups is None else len(groups) - 1, None if groups is None else groups.ctypes.data,
@@ -87,8 +99,11 @@ for n in args.sizes:
             fn()
             assert (out["n_model"] > 5000).all() and (out["inlier_ratio"] > 0.8).all()
             med = median_ms(fn, trk.verify_ms)
-            line(med, what="verify", groups=0 if groups is None else len(groups) - 1, poses=n, per_pose_ms=round(med[0] / n, 4),
-                 n_model=int(out["n_model"][0]))
+            line(med, what="verify", fused=fused, fused_px=px, groups=0 if groups is None else len(groups) - 1, poses=n,
+                 per_pose_ms=round(med[0] / n, 4), n_model=int(out["n_model"][0]))
+        if variants[0][0] is not None:
+            ctx.set_option("verify_fused", 0)
+            ctx.set_option("verify_fused_px", 0)
     out = np.zeros(n, api.TRACK_DTYPE)
     for mode, name in ((L.FL_ICP_POINT_TO_PLANE, "point_to_plane"), (L.FL_ICP_PARITY, "parity")):
         prm = L.TrackParams(12, 1, 10, 0.5, 0.01, mode, 0.0, 0.0)
