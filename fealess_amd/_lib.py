@@ -216,6 +216,7 @@ DEV_SIGNATURES = {
     "fl_dev_refine_plan": (_I, [_P, _I, _I, C.c_long, _I, _P]),
     "fl_dev_refine_kernel": (_I, [_P, _I]),
     "fl_dev_refine_window_max": (C.c_long, [_P, _I]),
+    "fl_dev_build_lm_band": (_I, [_I, _I, _I, _I, _I]),
 }
 
 

@@ -999,12 +999,7 @@ int fl_launch_lazy_level(fl_detector *det, int n_frames, int level)
                                  det->d_ws + g.quant_off[0], det->ws_stride, n_frames, g.w, g.h, 10.0f, nullptr,
                                  tiles, tstride);
   if (rc) return rc;
-  for (int m = 0; m < det->M; ++m) {
-    rc = fl_launch_spread_tiles(ctx, det->d_ws + g.quant_off[m], det->ws_stride, det->d_ws + g.spread_off[m], det->ws_stride, n_frames,
-                                g.w, g.h, g.T, tiles, tstride);
-    if (rc) return rc;
-  }
-  return FL_OK;
+  return fl_launch_spread_tiles(ctx, fl_level_planes(det, g, g.spread_off), det->M, n_frames, g.w, g.h, g.T, tiles, tstride);
 }
 
 // ---- single-image stage entry points ----------------------------------------------------------

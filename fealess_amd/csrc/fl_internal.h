@@ -393,10 +393,27 @@ void fl_update_stage_times(fl_detector *det, int n_frames, const fl_recognition_
 
 // ---- stage launchers (defined in the per-domain .hip files) ---------------------------------
 // linemod
-int fl_launch_build_lm(fl_context *ctx, const uint8_t *quant, size_t quant_stride, uint8_t *lm,
-                       size_t lm_stride, int n_frames, int w, int h, int T);
-int fl_launch_spread(fl_context *ctx, const uint8_t *quant, size_t quant_stride, uint8_t *spread,
-                     size_t spread_stride, int n_frames, int w, int h, int T);
+// The input and output planes of one stage at one level, all modalities: plane m of frame f is at base + f * stride + off[m].
+struct FlPlanes {
+  const uint8_t *in;
+  uint8_t *out;
+  size_t in_stride, out_stride;
+  size_t in_off[FL_MAX_MODALITIES], out_off[FL_MAX_MODALITIES];
+};
+// quantised images of level g in, linear memories (g.lm_off) or spread images (g.spread_off) out, in the frame workspaces
+inline FlPlanes fl_level_planes(const fl_detector *det, const FlLevelGeom &g, const size_t *out_off)
+{
+  FlPlanes pl{det->d_ws, det->d_ws, det->ws_stride, det->ws_stride, {}, {}};
+  for (int m = 0; m < FL_MAX_MODALITIES; ++m) {
+    pl.in_off[m] = g.quant_off[m < det->M ? m : 0];
+    pl.out_off[m] = out_off[m < det->M ? m : 0];
+  }
+  return pl;
+}
+// one launch each for the n_mod modalities of a level; tiles: see fl_launch_spread_tiles in fl_linemod.hip
+int fl_launch_build_lm(fl_context *ctx, const FlPlanes &pl, int n_mod, int n_frames, int w, int h, int T);
+int fl_launch_spread_tiles(fl_context *ctx, const FlPlanes &pl, int n_mod, int n_frames, int w, int h, int T, const uint32_t *tiles,
+                           size_t tiles_stride);
 int fl_launch_match_core(fl_detector *det, int n_frames, float threshold);
 int fl_launch_lazy_level(fl_detector *det, int n_frames, int level);   // frontend: colour quantisation + spreads of the marked tiles
 // Multi-instance grouping (fl_group_matches, fl_recognize_batch_instances): one workgroup per frame groups that frame's
@@ -475,8 +492,6 @@ int fl_launch_quantized_orientations_mag(fl_context *ctx, const uint8_t *bgr, si
                                          int n_frames, int w, int h, float weak_threshold, float *mag_out);
 int fl_launch_frontend(fl_detector *det, int n_frames, const uint8_t *bgr, size_t bgr_stride,
                        const uint16_t *depth, size_t depth_stride, bool allow_lazy);
-int fl_launch_spread_tiles(fl_context *ctx, const uint8_t *quant, size_t quant_stride, uint8_t *spread, size_t spread_stride,
-                           int n_frames, int w, int h, int T, const uint32_t *tiles, size_t tiles_stride);
 int fl_launch_resize_linear_bgr8(fl_context *ctx, const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh);
 int fl_launch_resize_linear_u16(fl_context *ctx, const uint16_t *src, int sw, int sh, uint16_t *dst, int dw, int dh);
 // icp
