@@ -98,11 +98,13 @@ int fl_icp_stream(fl_context *ctx, hipStream_t *out)
 extern "C" int fl_abi_version(void) { return FL_ABI_VERSION; }
 
 // name, environment variable, field, environment value in hex, accepted values lo .. hi (icp_occ: 0, 4 or 5;
-// frontend_chunk_rows: multiples of 60; scan_run: 0 = automatic)
+// frontend_chunk_rows: multiples of 60; scan_run: 0 = automatic; scan_prune_step: 0 = automatic, 2, 4 or 8)
 struct FlOptionName { const char *name, *env; long fl_context::Options::*field; bool hex; long lo, hi; };
 static const FlOptionName fl_option_names[] = {
   {"scan_prune", "FL_SCAN_PRUNE", &fl_context::Options::scan_prune, false, 0, 1},
   {"scan_prune_mid", "FL_SCAN_PRUNE_MID", &fl_context::Options::scan_prune_mid, true, -1, 0xFF},
+  {"scan_prune_lanes", "FL_SCAN_PRUNE_LANES", &fl_context::Options::scan_prune_lanes, false, 0, 1},
+  {"scan_prune_step", "FL_SCAN_PRUNE_STEP", &fl_context::Options::scan_prune_step, false, 0, 8},
   {"icp_wide", "FL_ICP_WIDE", &fl_context::Options::icp_wide, false, -1, 1},
   {"icp_occ", "FL_ICP_OCC", &fl_context::Options::icp_occ, false, 0, 5},
   {"icp_order", "FL_ICP_ORDER", &fl_context::Options::icp_order, false, 0, 1},
@@ -126,6 +128,7 @@ static bool fl_option_valid(const FlOptionName &o, long v)
   if (v < o.lo || v > o.hi) return false;
   if (o.field == &fl_context::Options::frontend_chunk_rows) return v % 60 == 0;
   if (o.field == &fl_context::Options::verify_fused_px) return v == 0 || v >= FL_WAVE;
+  if (o.field == &fl_context::Options::scan_prune_step) return v == 0 || v == 2 || v == 4 || v == 8;
   return o.field != &fl_context::Options::icp_occ || v == 0 || v >= 4;
 }
 

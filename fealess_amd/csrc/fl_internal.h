@@ -33,6 +33,10 @@ struct fl_context {
   struct Options {
     long scan_prune = 1;        // FL_SCAN_PRUNE: k_scan's exact pruning
     long scan_prune_mid = -1;   // FL_SCAN_PRUNE_MID: bit mask of the 8-feature groups after which a modality checks the bound (-1: built-in)
+    long scan_prune_lanes = 1;  // FL_SCAN_PRUNE_LANES: 1 = a lane whose own 16 positions miss the bound stops loading, 0 = a wave stops as a
+                                // whole or not at all
+    long scan_prune_step = 0;   // FL_SCAN_PRUNE_STEP: feature loads between two checks behind a modality's first eight: 8, 4 or 2;
+                                // 0 = 4 from 256 frames on, else 8 (fl_scan_step)
     long icp_wide = -1;         // FL_ICP_WIDE: -1 by batch size, 0 / 1 force the 256- / 1024-thread ICP kernel
     long icp_occ = 0;           // FL_ICP_OCC: 0 by batch size, 4 / 5 force the 256-thread parity kernel built for 4 / 5 workgroups per CU
     long icp_order = 1;         // FL_ICP_ORDER: ICP jobs dealt longest first

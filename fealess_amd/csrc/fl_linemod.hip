@@ -504,6 +504,13 @@ int fl_launch_build_lm(fl_context *ctx, const FlPlanes &pl, int n_mod, int n_fra
 // inside an item the next group's eight offsets -- the next modality's first group behind a modality's last -- are
 // requested before the current group's vector loads are waited for.  An early-pruned item then costs the two vector
 // round trips of its two groups; the record, the flag and the offsets arrive underneath them.
+//
+// The bound is per lane (a lane's own 16 positions), so a lane that misses it stops loading for itself (ScanArgs::prune_lanes),
+// and behind a modality's first eight features the checks come every STEP features (the kernel's second template parameter,
+// fl_scan_step): see `alive` in the kernel.  What this buys is load instructions and lanes not issued; the launch is NOT bound by
+// the vector cache's line lookups (a quarter fewer of them moved the time by 1 %, profiles/README.md).  What did bind it was the
+// scalar cache: lane 63's tail dword, one scalar load per feature at an address all over the linear memories, is now fetched
+// only where lane 63 loads.
 struct ScanArgs {
   const FlScanItem *items;   // work list: one record per (pyramid, chunk)
   int n_items;
@@ -519,6 +526,7 @@ struct ScanArgs {
   float threshold;
   int prune;                 // stop a (template, chunk) between modalities once no position can reach the threshold (exact)
   unsigned prune_mid;        // ... and inside a modality after the 8-feature groups whose bit is set (same bound, same exactness)
+  int prune_lanes;           // a lane whose own 16 positions miss the bound stops loading (0: the wave stops as a whole or not at all)
   uint16_t *dbg;             // optional raw u16 maps of pyramids [dbg_first, dbg_first+dbg_count); null: dbg_count = 0
   int dbg_first, dbg_count;
 };
@@ -563,9 +571,28 @@ __device__ __forceinline__ uint32_t rl(uint32_t v, int l) { return (uint32_t)__b
 #ifndef FL_SCAN_WPE_PRUNED
 #define FL_SCAN_WPE_PRUNED 6
 #endif
-template <int WPE>
+#ifndef FL_SCAN_STEP
+#define FL_SCAN_STEP 4            // feature loads between two checks behind a modality's first eight (option scan_prune_step: 8, 4 or 2)
+#endif
+#ifndef FL_SCAN_TAIL_ALWAYS
+#define FL_SCAN_TAIL_ALWAYS 0     // 1 (comparison builds): lane 63's tail dword is loaded for every feature, needed or not
+#endif
+#ifdef FL_SCAN_STATS
+// development aid: per launch {items, feature-load instructions, lane-loads (lanes in EXEC), items that ran to their end}, then
+// the items ended by a check after f features of all modalities (f = 0 .. 126); printed by the launcher after a stream
+// synchronisation (tools/dev/README.md)
+#define FL_SCAN_STATS_N (4 + 2 * FL_MAX_FEATURES + 1)
+__device__ unsigned long long d_scan_stats[FL_SCAN_STATS_N];
+#define FL_SCAN_STAT(i, v) do { if (lane == 0) atomicAdd(&d_scan_stats[i], (unsigned long long)(v)); } while (0)
+#else
+#define FL_SCAN_STAT(i, v) do { } while (0)
+#endif
+template <int N> struct ScanInt { static constexpr int value = N; };
+// STEP: behind a modality's first group of eight, the feature loads between two checks of the bound (8, 4 or 2)
+template <int WPE, int STEP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_scan(ScanArgs a)
 {
+  static_assert(STEP == 8 || STEP == 4 || STEP == 2, "a group of eight offsets is cut into equal parts");
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // XCD-aware block mapping: workgroups are dealt round-robin over the 8 XCDs, each with its own
   // 4 MB L2.  All blocks of one frame are given the same residue mod 8, so a frame's linear
@@ -615,6 +642,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     const bool tapped = (unsigned)(g - dbg_first) < dbg_count;
     const bool prune = a.prune && !tapped;
     const unsigned mid = prune ? a.prune_mid : 0u;
+    // Per lane: the bound is computed for a lane's own 16 positions, so a lane that misses it can stop for itself.  `alive`
+    // holds the lanes that still own a reachable position, wave-uniform in a scalar register pair.  A check removes lanes and
+    // never brings one back; the item ends when none is left.  The loads of the groups that follow run under
+    // alive | alive << 1 (a lane's bytes 16..19 are its upper neighbour's first dword), so a dead lane's accumulators go
+    // stale or, next to a live lane, take in a wrong tail: it has no say in later checks and is kept out of the emission.
+    // (Even unguarded it could not emit where its tail is right: its stale totals are below its true totals, which are below
+    // the threshold.)  Without a.prune_lanes a check keeps every lane or none, the wave-wide rule.
+    const bool by_lane = prune && a.prune_lanes;
+    uint64_t alive = ~0ull;
+    auto still = [&](bool reachable) {                     // one check: false = the item is over
+      const uint64_t b = __ballot(reachable) & alive;
+      alive = by_lane || b == 0ull ? b : ~0ull;
+      return alive != 0ull;
+    };
+    [[maybe_unused]] int f_done = 0;                                     // (FL_SCAN_STATS: features added so far)
+    FL_SCAN_STAT(0, 1);
     // the group of eight offsets in flight (lanes 0..7) and where in a.offs it is from: the record brings modality 0's first
     uint32_t ov = r;
     int o_at = (rN[0] & 0xFFFFu) ? rB[0] : -1;
@@ -627,7 +670,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       if (prune && m > 0) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) mx_tot = max(mx_tot, tot[i]);
-        if (__ballot((int)mx_tot + 4 * (nf_all - nf) > prune_threshold) == 0ull) return;    // wave-uniform
+        if (!still((int)mx_tot + 4 * (nf_all - nf) > prune_threshold)) {                      // wave-uniform
+          FL_SCAN_STAT(4 + f_done, 1);
+          return;
+        }
       }
       nf += h_nf;
       if (chunk * 1024 >= P) continue;                    // wave-uniform; lanes past P load along (masked below): the
@@ -648,7 +694,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       // not a select per load (measured in round 1: that serialised the eight loads in flight) -- and the masked lanes' loads
       // are simply not issued: 19 % less L2 traffic.
       const int lanes_on = min(64, ((P - chunk * 1024 + 15) >> 4) + 1);
-      const bool on = lane < lanes_on;
+      const uint64_t lanes_mask = lanes_on >= 64 ? ~0ull : (1ull << lanes_on) - 1ull;
       // behind this modality's last group the next modality's first is requested (whether or not that one then runs)
       const int next_begin = rB[m + 1 < FL_MAX_MODALITIES ? m + 1 : m];
       for (int k = 0; k < n_pad; k += 8) {
@@ -659,49 +705,92 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         // n_pad is never turned into a load.
         const int nxt_at = k + 8 < n_pad ? at + 8 : next_begin;
         const uint32_t nxt = a.offs[nxt_at + l7];
-        uint32_t o[8];
+        // N of the group's loads from its offset S0 on, under one EXEC region: the lanes that are alive and their upper
+        // neighbours, of those this modality has positions for
+        auto add_features = [&](auto s0_, auto n_) {
+          constexpr int S0 = decltype(s0_)::value, N = decltype(n_)::value;
+          uint32_t o[N];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) o[u] = rl(ov, u);
-        if (on) {
-        uint4 v[8];
-        uint32_t e[8];
-        unsigned mis_all = 0;                              // the eight misalignments, four bits each: one scalar register
+          for (int u = 0; u < N; ++u) o[u] = rl(ov, S0 + u);
+          const uint64_t need = (alive | alive << 1) & lanes_mask;
+          FL_SCAN_STAT(1, N);
+          FL_SCAN_STAT(2, N * __builtin_popcountll(need));
+          // Lane 63's bytes 16..19 have no upper neighbour to come from: a scalar load per feature, at an address all over the
+          // linear memories, i.e. a miss of the scalar cache that goes to L2 -- sixteen per item.  They are needed only
+          // where lane 63 loads at all: not for a template whose positions end below the chunk's last lane (52 lanes of a
+          // bench template), nor once lane 63 is dead.  Elsewhere the lane the DPP has no source for keeps a zero.
+          const bool tail_on = FL_SCAN_TAIL_ALWAYS || (need >> 63) != 0ull;   // wave-uniform
+          uint32_t tail[N];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const unsigned off = o[u];
-          const unsigned mis_u = (lm_mis + off) & 3u;
-          mis_all |= mis_u << (4 * u);
-          // buffer_load ... v_lane_off, s[rsrc], s_feature_off offen: the lane's byte offset is one loop-invariant VGPR and the
-          // feature's offset a scalar operand -- no per-lane 64-bit address arithmetic (it was 2 of the 10 VALU instructions
-          // per feature)
-          const u32x4 ld = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, off - mis_u + 4u, 0);   // 4-byte aligned
-          v[u] = make_uint4(ld.x, ld.y, ld.z, ld.w);
-          const uint32_t tail = sload1(lm_u + off - mis_u + 1024);
-          e[u] = (uint32_t)__builtin_amdgcn_update_dpp((int)tail, (int)v[u].x, 0x130, 0xF, 0xF, false);   // wave_shl:1
-        }
+          for (int u = 0; u < N; ++u) tail[u] = 0u;
+          if (__builtin_amdgcn_inverse_ballot_w64(need)) {
+          uint4 v[N];
+          uint32_t e[N];
+          unsigned mis_all = 0;                            // the misalignments, four bits each: one scalar register
+          if (tail_on) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const unsigned mis_u = (mis_all >> (4 * u)) & 3u;
-          a0 += __builtin_amdgcn_alignbyte(v[u].y, v[u].x, mis_u);
-          a1 += __builtin_amdgcn_alignbyte(v[u].z, v[u].y, mis_u);
-          a2 += __builtin_amdgcn_alignbyte(v[u].w, v[u].z, mis_u);
-          a3 += __builtin_amdgcn_alignbyte(e[u], v[u].w, mis_u);
-        }
-        asm volatile("" :: "v"(nxt));                      // (keeps the request above in front of this group's loads)
-        }
-        ov = nxt;
-        o_at = FL_SCAN_OFFSETS_AHEAD ? nxt_at : -1;
-        if ((mid >> (k >> 3)) & 1u) {                      // wave-uniform
-          // the same bound inside the modality: the lane's largest byte so far on top of its largest finished total
-          // (an over-estimate of its largest partial total, so nothing reachable is ever dropped)
+            for (int u = 0; u < N; ++u) tail[u] = sload1(lm_u + o[u] - ((lm_mis + o[u]) & 3u) + 1024);
+          }
+#pragma unroll
+          for (int u = 0; u < N; ++u) {
+            const unsigned off = o[u];
+            const unsigned mis_u = (lm_mis + off) & 3u;
+            mis_all |= mis_u << (4 * u);
+            // buffer_load ... v_lane_off, s[rsrc], s_feature_off offen: the lane's byte offset is one loop-invariant VGPR and
+            // the feature's offset a scalar operand -- no per-lane 64-bit address arithmetic (it was 2 of the 10 VALU
+            // instructions per feature)
+            const u32x4 ld = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, off - mis_u + 4u, 0);   // 4-byte aligned
+            v[u] = make_uint4(ld.x, ld.y, ld.z, ld.w);
+            e[u] = (uint32_t)__builtin_amdgcn_update_dpp((int)tail[u], (int)v[u].x, 0x130, 0xF, 0xF, false);   // wave_shl:1
+          }
+#pragma unroll
+          for (int u = 0; u < N; ++u) {
+            const unsigned mis_u = (mis_all >> (4 * u)) & 3u;
+            a0 += __builtin_amdgcn_alignbyte(v[u].y, v[u].x, mis_u);
+            a1 += __builtin_amdgcn_alignbyte(v[u].z, v[u].y, mis_u);
+            a2 += __builtin_amdgcn_alignbyte(v[u].w, v[u].z, mis_u);
+            a3 += __builtin_amdgcn_alignbyte(e[u], v[u].w, mis_u);
+          }
+          if (S0 == 0) asm volatile("" :: "v"(nxt));       // (keeps the request above in front of this group's loads)
+          }
+          f_done += N;
+        };
+        // the same bound inside the modality, `done` of its (padded) features in: the lane's largest byte so far on top of its
+        // largest finished total (an over-estimate of its largest partial total, so nothing reachable is ever dropped)
+        auto reachable = [&](int done) {
           const u16x2 b0 = pk_bytes_max(a0), b1 = pk_bytes_max(a1), b2 = pk_bytes_max(a2), b3 = pk_bytes_max(a3);
           const u16x2 bm = __builtin_elementwise_max(__builtin_elementwise_max(b0, b1), __builtin_elementwise_max(b2, b3));
           const int part = (int)max(bm.x, bm.y);
-          const int left = nf_all - nf + max(0, h_nf - (k + 8));
-          // (every lane votes: one past this modality's template_positions adds nothing here, its bound is simply generous --
-          // it may still collect from a modality whose template_positions reach further)
-          if (__ballot((int)mx_tot + part + 4 * left > prune_threshold) == 0ull) return;          // wave-uniform
+          const int left = nf_all - nf + max(0, h_nf - done);
+          // (every live lane votes: one past this modality's template_positions adds nothing here, its bound is simply
+          // generous -- it may still collect from a modality whose template_positions reach further)
+          if (still((int)mx_tot + part + 4 * left > prune_threshold)) return true;                // wave-uniform
+          FL_SCAN_STAT(4 + f_done, 1);
+          return false;
+        };
+        // a modality's first eight features in one piece (no item ends before them), the groups behind them STEP at a time;
+        // bit g of `mid` enables the checks inside and at the end of group g
+        const bool chk = (mid >> (k >> 3)) & 1u;           // wave-uniform
+        if (STEP == 8 || k == 0) {
+          add_features(ScanInt<0>{}, ScanInt<8>{});
+          if (chk && !reachable(k + 8)) return;
+        } else if (STEP == 4) {
+          add_features(ScanInt<0>{}, ScanInt<4>{});
+          if (chk && !reachable(k + 4)) return;
+          add_features(ScanInt<4>{}, ScanInt<4>{});
+          if (chk && !reachable(k + 8)) return;
+        } else {
+          add_features(ScanInt<0>{}, ScanInt<2>{});
+          if (chk && !reachable(k + 2)) return;
+          add_features(ScanInt<2>{}, ScanInt<2>{});
+          if (chk && !reachable(k + 4)) return;
+          add_features(ScanInt<4>{}, ScanInt<2>{});
+          if (chk && !reachable(k + 6)) return;
+          add_features(ScanInt<6>{}, ScanInt<2>{});
+          if (chk && !reachable(k + 8)) return;
         }
+        ov = nxt;
+        o_at = FL_SCAN_OFFSETS_AHEAD ? nxt_at : -1;
       }
       const uint32_t acc[4] = {a0, a1, a2, a3};
 #pragma unroll
@@ -724,7 +813,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     uint32_t mx = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) mx = max(mx, tot[i]);
-    if ((int)mx <= raw_threshold) return;
+    FL_SCAN_STAT(3, 1);
+    if ((int)mx <= raw_threshold || !__builtin_amdgcn_inverse_ballot_w64(alive)) return;   // dead lanes emit nothing (see `alive`)
     const FL_CONST_AS ScanArgs *kr = ka;
     asm volatile("" : "+s"(kr));
     const int W = kr->W, WH = kr->WH, T = kr->T, cap = kr->cap;
@@ -1425,6 +1515,20 @@ static int fl_scan_run(const fl_context *ctx, int items, int n_frames)
   return run;
 }
 
+// Feature loads between two of k_scan's checks behind a modality's first eight (the STEP the kernel is built for).  A finer step
+// trades a dependent round trip for load instructions not issued, which pays where the launch keeps every CU's vector memory
+// path busy: from FL_SCAN_STEP_FRAMES frames on (measured at 256 and 4096); below, where an item costs its round trips and
+// nothing else, groups of eight (the scan of 1 and of 64 frames: 0.017 against 0.020 ms, 0.111 against 0.113 ms,
+// profiles/README.md).  Option scan_prune_step != 0 forces a step.
+#ifndef FL_SCAN_STEP_FRAMES
+#define FL_SCAN_STEP_FRAMES 256
+#endif
+static int fl_scan_step(const fl_context *ctx, int n_frames)
+{
+  if (ctx->opt.scan_prune_step) return (int)ctx->opt.scan_prune_step;
+  return n_frames >= FL_SCAN_STEP_FRAMES ? FL_SCAN_STEP : 8;
+}
+
 // Which refinement kernel a fine level gets.  k_refine_lds needs every candidate's window to fit the budget (decided from
 // the bank at finalize: refine_window_max) and, being one workgroup per frame, a batch that fills the device: below
 // FL_REFINE_LDS_FRAMES_PER_CU frames per CU k_refine's 4 .. 256 workgroups per frame are faster (profiles/README.md).
@@ -1480,6 +1584,7 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
     a.threshold = threshold;
     a.prune = ctx->opt.scan_prune != 0;                   // development switches (fl_context_set_option)
     a.prune_mid = ctx->opt.scan_prune_mid >= 0 ? (unsigned)ctx->opt.scan_prune_mid : FL_SCAN_PRUNE_MID;
+    a.prune_lanes = ctx->opt.scan_prune_lanes != 0;
     a.dbg = dbg;
     a.dbg_first = dbg_first;
     a.dbg_count = dbg ? dbg_count : 0;
@@ -1499,9 +1604,26 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
 #endif
       a.n_frames = n_frames;
       dim3 grid((unsigned)(a.bpf * ((n_frames + 7) / 8) * 8));
-      if (a.prune) hipLaunchKernelGGL(k_scan<FL_SCAN_WPE_PRUNED>, grid, dim3(256), 0, ctx->stream, a);
-      else hipLaunchKernelGGL(k_scan<FL_SCAN_WPE>, grid, dim3(256), 0, ctx->stream, a);
+      if (!a.prune) hipLaunchKernelGGL((k_scan<FL_SCAN_WPE, 8>), grid, dim3(256), 0, ctx->stream, a);
+      else switch (fl_scan_step(ctx, n_frames)) {
+      case 2: hipLaunchKernelGGL((k_scan<FL_SCAN_WPE_PRUNED, 2>), grid, dim3(256), 0, ctx->stream, a); break;
+      case 4: hipLaunchKernelGGL((k_scan<FL_SCAN_WPE_PRUNED, 4>), grid, dim3(256), 0, ctx->stream, a); break;
+      default: hipLaunchKernelGGL((k_scan<FL_SCAN_WPE_PRUNED, 8>), grid, dim3(256), 0, ctx->stream, a); break;
+      }
       FL_HIP(ctx, hipGetLastError());
+#ifdef FL_SCAN_STATS
+      {
+        unsigned long long st[FL_SCAN_STATS_N], zero[FL_SCAN_STATS_N] = {0};
+        FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        FL_HIP(ctx, hipMemcpyFromSymbol(st, HIP_SYMBOL(d_scan_stats), sizeof(st)));
+        FL_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(d_scan_stats), zero, sizeof(zero)));
+        fprintf(stderr, "k_scan: %d frames, %llu items, %.2f feature loads and %.1f lane-loads per item, %llu items to their end; ended "
+                "after f features:", n_frames, st[0], st[0] ? (double)st[1] / st[0] : 0.0, st[0] ? (double)st[2] / st[0] : 0.0, st[3]);
+        for (int f = 0; f + 4 < FL_SCAN_STATS_N; ++f)
+          if (st[4 + f]) fprintf(stderr, " %d: %llu", f, st[4 + f]);
+        fprintf(stderr, "\n");
+      }
+#endif
     }
   }
   if (det->have_times) FL_HIP(ctx, hipEventRecord(det->ev[3], ctx->stream));
