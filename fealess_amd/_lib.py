@@ -89,6 +89,15 @@ class VerifyResult(C.Structure):       # 64 bytes
                 ("sum_abs_inlier", C.c_int64), ("inlier_ratio", C.c_float), ("behind_ratio", C.c_float)]
 
 
+class TrackVerifyParams(C.Structure):
+    _fields_ = [("verify", VerifyParams), ("keep_input", C.c_int32), ("reserved", C.c_int32)]
+
+
+class VerifiedTrackResult(C.Structure):       # 368 bytes
+    _fields_ = [("track", TrackResult), ("verify", VerifyResult), ("verify_in", VerifyResult), ("icp_tracked", C.c_int32),
+                ("kept_input", C.c_int32), ("best", C.c_int32), ("reserved", C.c_int32)]
+
+
 class InstanceVerifyParams(C.Structure):
     _fields_ = [("verify", VerifyParams), ("class_idx", C.c_int32), ("reserved", C.c_int32)]
 
@@ -186,6 +195,8 @@ SIGNATURES = {
     "fl_tracker_destroy": (None, [_P]),
     "fl_track_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams), _P]),
     "fl_verify_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(VerifyParams), _P]),
+    "fl_track_batch_verified": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams),
+                                     C.POINTER(TrackVerifyParams), _P]),
     "fl_nms": (_I, [_P, _I, _F, C.POINTER(_I), C.POINTER(_I)]),
     "fl_export_topk": (_I, [_P, _I, _I, _I, _P]),
     "fl_merge_topk": (_I, [_P, _I, _P, _I]),
@@ -207,6 +218,7 @@ DEV_SIGNATURES = {
     "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_tracker_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
+    "fl_dev_tracker_track_verified_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_instances_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_pick_verified": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "fl_dev_cq_window_addr": (None, [C.c_uint, _I, _I, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_I)]),

@@ -27,6 +27,10 @@ VERIFY_DTYPE = np.dtype([("status", "<i4"), ("accepted", "<i4"), ("best", "<i4")
                          ("n_inlier", "<i4"), ("n_front", "<i4"), ("n_behind", "<i4"), ("sum_abs_inlier", "<i8"), ("inlier_ratio", "<f4"),
                          ("behind_ratio", "<f4")])
 assert VERIFY_DTYPE.itemsize == C.sizeof(L.VerifyResult) == 64
+# numpy view of fl_verified_track_result
+VERIFIED_TRACK_DTYPE = np.dtype([("track", TRACK_DTYPE), ("verify", VERIFY_DTYPE), ("verify_in", VERIFY_DTYPE), ("icp_tracked", "<i4"),
+                                 ("kept_input", "<i4"), ("best", "<i4"), ("reserved", "<i4")])
+assert VERIFIED_TRACK_DTYPE.itemsize == C.sizeof(L.VerifiedTrackResult) == 368
 
 
 class FealessError(RuntimeError):
@@ -932,6 +936,36 @@ class Tracker:
                                                 None if gf is None else _ptr(gf), C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
         return out[:n]
 
+    def track_verified(self, depths, frame_of_track, poses13, K, group_first=None, keep_input=0, tau_mm=10, min_model_px=1,
+                       min_inlier_ratio=0.0, max_behind_ratio=0.0, **track_params):
+        """One step of every track whose `tracked` is the verification's (fl_track_batch_verified): track()'s passes, then on
+        the device the pose each tracked track came out with rendered at the scene camera and laid over its frame, as verify()
+        does it; a track whose pose is not accepted comes back lost.  keep_input = 1: the pose a track came in with is verified
+        too and kept where it verifies strictly better.  group_first: None, or verify()'s groups over the tracks (several start
+        poses for one object); one track per group at most comes back with best = 1.  tau_mm .. max_behind_ratio: the fields of
+        fl_verify_params; track_params: the fields of fl_track_params.  Returns a VERIFIED_TRACK_DTYPE array, one record per
+        track; poses13_of(result["track"]) feeds the next frame."""
+        who = "Tracker.track_verified"
+        (n_frames, dp, mem, n, fof, p), k, out = self._batch(who, "track", depths, frame_of_track, poses13, K, VERIFIED_TRACK_DTYPE)
+        gf = None
+        if group_first is not None:
+            gf = np.ascontiguousarray(group_first, np.int32).ravel()
+            if len(gf) < 2:
+                raise ValueError(f"{who}: group_first has n_groups + 1 entries")
+        prm = _params_struct(who, L.TrackParams, _TRACK_DEFAULTS, track_params)
+        vp = L.TrackVerifyParams(L.VerifyParams(int(tau_mm), int(min_model_px), float(min_inlier_ratio), float(max_behind_ratio)), int(keep_input), 0)
+        self.ctx.check(self.lib.fl_track_batch_verified(self.handle, n_frames, dp, mem, n, _ptr(fof), _ptr(p), 0 if gf is None else len(gf) - 1,
+                                                        None if gf is None else _ptr(gf), C.byref(k), None if prm is None else C.byref(prm),
+                                                        C.byref(vp), _ptr(out)))
+        return out[:n]
+
+    def track_verified_ms(self):
+        """DEVELOPMENT ONLY (fl_dev_tracker_track_verified_ms, not part of the C ABI): device time of the stages the last
+        track_verified() ran after its passes: dict(fused, finish) in ms; stage_ms() has the passes."""
+        out = (C.c_float * 2)()
+        self.ctx.check(L.dev(self.lib, "fl_dev_tracker_track_verified_ms")(self.handle, out))
+        return dict(zip(("fused", "finish"), [float(v) for v in out]))
+
     def verify_ms(self):
         """DEVELOPMENT ONLY (fl_dev_tracker_verify_ms, not part of the C ABI): device time of the last verify() by stage:
         dict(copy, render, score, finish) in ms."""
@@ -953,7 +987,8 @@ class Tracker:
 
 
 def poses13_of(track_results):
-    """The (n, 13) pose array that feeds a TRACK_DTYPE result array back into Tracker.track."""
+    """The (n, 13) pose array that feeds a TRACK_DTYPE result array (Tracker.track's, or the "track" part of
+    Tracker.track_verified's) back into either."""
     r = np.atleast_1d(track_results)
     out = np.zeros((len(r), 13), np.float32)
     out[:, :12] = r["pose"][:, :12]

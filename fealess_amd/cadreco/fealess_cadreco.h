@@ -255,4 +255,13 @@ int CadRecoVerify(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrin
 // leaving the multi-instance mode switches it off too.
 int CadRecoSetVerifiedPick(CObjRecoCAD *handle, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio);
 
+// Opt-in: the verification decides what CadRecoTrack reports (fl_track_batch_verified, include/fealess_hip.h).  After the ICP the
+// pose every followed entry came out with is verified against the depth frame on the device, with tau_mm and the two gates
+// (<= 0: no test) as CadRecoVerify and fl_verify_params state them; (*tracked)[i] = 1 only where a pose was accepted, and an
+// entry whose pose was not keeps the pose it came in with, like any lost entry.  keep_input = 1: the pose an entry came in with
+// is verified too and kept (tracked = 1) where it verifies strictly better than the ICP's -- an object that stands still then
+// does not jitter.  Needs CadRecoSetTrackingMesh first: ERROR_INVALID_PARAM otherwise, as for tau_mm outside 0..65535, a
+// threshold that is not finite or keep_input outside {0, 1}.  on = 0 switches it off, and CadRecoTrack is again fl_track_batch.
+int CadRecoSetVerifiedTracking(CObjRecoCAD *handle, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio, int keep_input);
+
 #endif  // FEALESS_CADRECO_H

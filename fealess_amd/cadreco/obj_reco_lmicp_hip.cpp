@@ -285,7 +285,8 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return SUCCESS;
   }
 
-  // CadRecoTrack: one fl_track_batch over the previous frame's results, library defaults (point-to-plane, one pass)
+  // CadRecoTrack: one fl_track_batch over the previous frame's results, library defaults (point-to-plane, one pass); with
+  // CadRecoSetVerifiedTracking one fl_track_batch_verified, whose `tracked` and pose are the verification's
   int Track(const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult, vector<int> *tracked)
   {
     if (tracked) tracked->assign(vtResult.size(), 0);
@@ -300,7 +301,15 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     const fl_intrinsics k = {PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, K.dFx, K.dFy, K.dCx, K.dCy};
     const uint16_t *frame = tDepth.pData;
     std::vector<fl_track_result> res(n);
-    const int rc = fl_track_batch(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), &k, nullptr, res.data());
+    int rc;
+    if (m_verified_tracking) {
+      std::vector<fl_verified_track_result> vres(n);
+      rc = fl_track_batch_verified(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), 0, nullptr, &k, nullptr, &m_tvparams,
+                                   vres.data());
+      for (int i = 0; i < n; ++i) res[i] = vres[i].track;
+    } else {
+      rc = fl_track_batch(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), &k, nullptr, res.data());
+    }
     if (rc != FL_OK) {
       fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
       return rc == FL_ERR_INVALID ? (int)ERROR_INVALID_PARAM : (int)ERROR_UNKNOW;
@@ -355,9 +364,23 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return SUCCESS;
   }
 
+  // CadRecoSetVerifiedTracking: needs a tracking mesh
+  int SetVerifiedTracking(int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio, int keep_input)
+  {
+    if (!on) { m_verified_tracking = false; return SUCCESS; }
+    if (!m_ctx || !m_tracker || !(tau_mm >= 0.f && tau_mm < 65536.f) || !std::isfinite(min_inlier_ratio) || !std::isfinite(max_behind_ratio) ||
+        (keep_input != 0 && keep_input != 1))
+      return (int)ERROR_INVALID_PARAM;
+    m_tvparams = fl_track_verify_params{{(int32_t)tau_mm, 1, min_inlier_ratio, max_behind_ratio}, keep_input, 0};
+    m_verified_tracking = true;
+    return SUCCESS;
+  }
+
   fl_recognition_params m_params;
   bool m_verified = false;   // CadRecoSetVerifiedPick; leaving the multi-instance mode clears it
   fl_verify_params m_vparams = {10, 1, 0.f, 0.f};
+  bool m_verified_tracking = false;   // CadRecoSetVerifiedTracking
+  fl_track_verify_params m_tvparams = {{10, 1, 0.f, 0.f}, 0, 0};
   int m_topk = 1;            // > 1: multi-hypothesis mode (CadRecoSetMultiHypothesis)
   float m_nms_dist = 20.0f;  // th_obj_dist of nonMaximumSuppression, mm
   fl_instance_params m_instances = {1, 48, 1};   // max_instances or hyp_per_instance > 1: multi-instance mode (CadRecoSetMultiInstance)
@@ -428,6 +451,13 @@ int CadRecoSetVerifiedPick(CObjRecoCAD *handle, int on, float tau_mm, float min_
   CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
   if (!h) return (int)ERROR_INVALID_PARAM;
   return h->SetVerifiedPick(on, tau_mm, min_inlier_ratio, max_behind_ratio);
+}
+
+int CadRecoSetVerifiedTracking(CObjRecoCAD *handle, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio, int keep_input)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h) return (int)ERROR_INVALID_PARAM;
+  return h->SetVerifiedTracking(on, tau_mm, min_inlier_ratio, max_behind_ratio, keep_input);
 }
 
 namespace {
@@ -703,6 +733,10 @@ int cadreco_verify(void *h, const unsigned short *depth, int w, int h_, double t
 int cadreco_set_verified_pick(void *h, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio)
 {
   return CadRecoSetVerifiedPick((CObjRecoCAD *)h, on, tau_mm, min_inlier_ratio, max_behind_ratio);
+}
+int cadreco_set_verified_tracking(void *h, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio, int keep_input)
+{
+  return CadRecoSetVerifiedTracking((CObjRecoCAD *)h, on, tau_mm, min_inlier_ratio, max_behind_ratio, keep_input);
 }
 int cadreco_set_tracking_mesh(void *h, const char *obj_path, float scale)
 {

@@ -537,6 +537,9 @@ int fl_launch_render_chunk(fl_context *ctx, const FlRenderMesh &mesh, const floa
 // its frame is the w * h u16 at frames + frame_stride * (frame_of ? frame_of[t] : t / per_frame).  With job_idx: pose t is
 // live only when job_idx[t] >= 0, res[t].found == 1 and (class_idx < 0 or res[t].best.class_idx == class_idx); a pose that is
 // not live leaves its accumulator as it is.  acc: FL_VERIFY_ACC_BYTES per pose, written whole for a live pose.
+// With skip (the tracker's form, which needs frame_of and takes no job_idx): the launch is over n_poses workgroups of which the
+// first `split` are items 0 .. split - 1 at `pose` and the rest are items 0 .. n_poses - split - 1 again at `pose_in`; workgroup
+// t of item u reads frame_of[u], is live when skip[u] == 0 and writes acc[t].  A workgroup that is not live exits at once.
 #define FL_VERIFY_FUSED_PX 36864   // pixels of a band: a 144 KiB z-buffer, one workgroup per CU
 constexpr size_t FL_VERIFY_ACC_BYTES = 48;   // sizeof(FlVerifyAcc), which fl_verify.hip defines and asserts
 struct FlVerifyFusedJob {
@@ -553,6 +556,9 @@ struct FlVerifyFusedJob {
   const fl_recognition_result *res;
   int class_idx;
   void *acc;
+  const int32_t *skip;                          // null: the liveness rule above
+  int split;
+  const float *pose_in;
 };
 int fl_launch_verify_fused(fl_context *ctx, const FlVerifyFusedJob &j);
 // the records of n_poses accumulators (k_verify_finish: rect, ratios, accepted; best = accepted), and fl_verify_params' ranges

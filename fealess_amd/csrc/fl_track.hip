@@ -2,8 +2,8 @@
 // rasteriser of fl_render.hip and the ICP workgroup per job of fl_icp.hip, joined on the device.  No counterpart in the
 // reference, which links a 2-D KCF box tracker it never calls (test/linemod_acq.cpp:108-150).
 //
-// Here: the tracker, the steps every call on one shares (fl_track_internal.h: checks, staging, render, results), and
-// fl_track_batch.  fl_verify_batch, the other user of those steps, is fl_verify.hip.
+// Here: the tracker, the steps every call on one shares (fl_track_internal.h: checks, staging, render, results),
+// fl_track_batch and fl_track_batch_verified.  fl_verify_batch, the other user of those steps, is fl_verify.hip.
 //
 // One pass of a call, all on the context's stream:
 //   fl_tracker_render        the mesh at every track's pose, depth only, K = 608 / 608 / 320 / 240 (the K crop_clouds
@@ -14,6 +14,13 @@
 //   fl_launch_detection_tables   k_icp_pipeline over the n_tracks slots, through its job list: class_first = {0}, so slot t's
 //                            "template" is g = t
 //   k_track_finish           one thread per track: the lost rule, the result record, the pose of the next pass
+// fl_track_batch_verified runs the same passes (track_passes), then on the same stream, with no host step in between:
+//   k_verify_fused_tracks    (fl_verify.hip, through fl_launch_verify_fused) ONE launch over n_tracks workgroups, 2 n_tracks with
+//                            keep_input: the poses k_track_finish left in d_poses, then the poses of d_poses_in, each rendered at
+//                            the scene camera in LDS and scored against its frame; a workgroup whose track is lost exits at once
+//   k_track_verified_finish  one thread per track: k_verify_finish's record of one or two accumulators, the decision, the whole
+//                            fl_verified_track_result (its fl_track_result copied from the passes' record)
+//   k_track_verified_pick    one thread per group, only with groups
 // The rectangle rule is stated in integers in include/fealess_hip.h and in numpy in tests/track_model.py; the shift is fp64,
 // one IEEE operation per operator (the Makefile's -ffp-contract=off: hipcc would contract a * b + c otherwise).
 #include "fl_track_internal.h"
@@ -174,6 +181,57 @@ __global__ __launch_bounds__(64) void k_track_finish(TrackArgs a)
   o->tracked = 0;
   pose_to_4x4(a.poses_in + 13 * (size_t)t, o->pose);
 }
+
+struct TrackVerifiedArgs {
+  int n_tracks, n_groups, w, h, min_model_px, keep_input;
+  float min_inlier_ratio, max_behind_ratio;
+  const fl_track_result *track;                 // the passes' records
+  const float *poses_in;
+  const FlVerifyAcc *acc;                       // n_tracks of the passes' poses, then n_tracks of the input poses
+  const int32_t *group_first;                   // null: best = tracked
+  fl_verified_track_result *out;
+};
+
+__global__ __launch_bounds__(64) void k_track_verified_finish(TrackVerifiedArgs a)
+{
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= a.n_tracks) return;
+  fl_verified_track_result *o = a.out + t;
+  memset(o, 0, sizeof(*o));
+  o->track = a.track[t];
+  if (!o->track.tracked) return;                // lost in the passes: its record stands, the pose it came in with included
+  o->icp_tracked = 1;
+  fl_verify_result v = fl_verify_record(a.acc[t], a.w, a.h, a.min_model_px, a.min_inlier_ratio, a.max_behind_ratio), vi;
+  v.best = v.accepted;
+  o->verify = v;
+  memset(&vi, 0, sizeof(vi));
+  if (a.keep_input) {
+    vi = fl_verify_record(a.acc[a.n_tracks + t], a.w, a.h, a.min_model_px, a.min_inlier_ratio, a.max_behind_ratio);
+    vi.best = vi.accepted;
+    o->verify_in = vi;
+  }
+  const bool A = v.accepted, B = vi.accepted;
+  const bool keep = B && (!A || (long long)vi.n_inlier * v.n_model > (long long)v.n_inlier * vi.n_model);
+  o->kept_input = keep;
+  o->track.tracked = A || B;
+  if (keep || !(A || B)) pose_to_4x4(a.poses_in + 13 * (size_t)t, o->track.pose);
+  o->best = a.group_first ? 0 : o->track.tracked;
+}
+
+__global__ __launch_bounds__(64) void k_track_verified_pick(TrackVerifiedArgs a)
+{
+  const int g = blockIdx.x * 64 + threadIdx.x;
+  if (g >= a.n_groups) return;
+  int best = -1;
+  long long bi = 0, bm = 1;
+  for (int i = a.group_first[g]; i < a.group_first[g + 1]; ++i) {
+    const fl_verified_track_result &r = a.out[i];
+    if (!r.track.tracked) continue;             // tracked: the chosen record is accepted, n_model >= min_model_px >= 1
+    const fl_verify_result &c = r.kept_input ? r.verify_in : r.verify;
+    if (best < 0 || (long long)c.n_inlier * bm > bi * (long long)c.n_model) { best = i; bi = c.n_inlier; bm = c.n_model; }
+  }
+  if (best >= 0) a.out[best].best = 1;
+}
 }  // namespace
 
 static const fl_track_params k_track_defaults = {12, 1, 10, 0.5f, 0.01f, FL_ICP_POINT_TO_PLANE, 0.f, 0.f};
@@ -205,7 +263,8 @@ static fl_tracker *tracker_new(fl_context *ctx, bool owns_ctx, int w, int h, int
 }
 
 // The tracker's device memory, every part named once: the mesh of n_vertices and n_t triangles, the frame slots, per track a
-// render image, an ICP workspace and the small records, per render chunk the depth keys.  base null: the sizing pass.
+// render image, an ICP workspace and the small records (two verification accumulators: fl_track_batch_verified scores a track's
+// input pose too, and writes its records straight into d_vout), per render chunk the depth keys.  base null: the sizing pass.
 static size_t carve_device(fl_tracker *trk, uint8_t *base, int n_vertices)
 {
   const size_t px = (size_t)trk->w * trk->h, T = (size_t)trk->max_tracks;
@@ -219,7 +278,8 @@ static size_t carve_device(fl_tracker *trk, uint8_t *base, int n_vertices)
   take(trk->d_frame_of, T * 4); take(trk->d_lost, T * 4); take(trk->d_class_first, 4);
   take(trk->d_pyr, T * sizeof(FlPyrInfo)); take(trk->d_depth_ptrs, T * sizeof(void *)); take(trk->d_jobs, T * sizeof(FlRefineJob));
   take(trk->d_res, T * sizeof(fl_recognition_result)); take(trk->d_out, T * sizeof(fl_track_result));
-  take(trk->d_vacc, T * FL_VERIFY_ACC_BYTES); take(trk->d_vres, T * sizeof(fl_verify_result)); take(trk->d_group_first, (T + 1) * 4);
+  take(trk->d_vacc, 2 * T * sizeof(FlVerifyAcc)); take(trk->d_vres, T * sizeof(fl_verify_result)); take(trk->d_group_first, (T + 1) * 4);
+  take(trk->d_vout, T * sizeof(fl_verified_track_result));
   return off;
 }
 
@@ -365,21 +425,25 @@ extern "C" int fl_dev_tracker_stage_ms(fl_tracker *trk, float out[5])
   return FL_OK;
 }
 
-extern "C" int fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
-                              const int32_t *frame_of_track, const float *poses13, const fl_intrinsics *K, const fl_track_params *params,
-                              fl_track_result *results)
+// fl_track_params as given or the defaults, refused where out of range
+static int track_params(fl_context *ctx, const fl_track_params *params, fl_track_params &P)
 {
-  int rc = fl_tracker_check_call(trk, "fl_track_batch", n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, results);
-  if (rc) return rc;
-  fl_context *ctx = trk->ctx;
-  const fl_track_params P = params ? *params : k_track_defaults;
+  P = params ? *params : k_track_defaults;
   if (P.passes < 1 || P.passes > FL_TRACK_MAX_PASSES || P.margin_px < 0 || P.margin_px > FL_RENDER_MAX_DIM || P.icp_it_thr < 0 ||
       !std::isfinite(P.dist_mean_thr) || !std::isfinite(P.dist_diff_thr) || !std::isfinite(P.max_dist_mean) || !std::isfinite(P.min_px_ratio) ||
       (P.icp_mode != FL_ICP_PARITY && P.icp_mode != FL_ICP_FAST && P.icp_mode != FL_ICP_POINT_TO_PLANE))
     return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_params: passes 1..%d, margin_px 0..%d, icp_it_thr >= 0, finite thresholds, a known icp_mode",
                         FL_TRACK_MAX_PASSES, FL_RENDER_MAX_DIM);
-  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_track_batch: the tracker has no device");
+  return FL_OK;
+}
 
+// Steps 1 to 5 of a tracking call, queued: the inputs, then P.passes passes.  Afterwards d_out holds the records, d_lost who is
+// not tracked and d_poses the pose of every track that is.
+static int track_passes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks, const int32_t *frame_of_track,
+                        const float *poses13, const fl_intrinsics *K, const fl_track_params &P)
+{
+  fl_context *ctx = trk->ctx;
+  int rc;
   // 1. the inputs; the poses stay in d_poses_in too (a lost track reports the pose it came in with)
   if ((rc = fl_tracker_stage(trk, trk->ev[0], n_frames, depth, mem, n_tracks, frame_of_track, poses13, trk->d_poses_in))) return rc;
   const size_t T = (size_t)n_tracks;
@@ -414,8 +478,87 @@ extern "C" int fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *con
     FL_HIP(ctx, hipGetLastError());
     FL_HIP(ctx, hipEventRecord(ev[3], st));
   }
+  return FL_OK;
+}
+
+extern "C" int fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
+                              const int32_t *frame_of_track, const float *poses13, const fl_intrinsics *K, const fl_track_params *params,
+                              fl_track_result *results)
+{
+  int rc = fl_tracker_check_call(trk, "fl_track_batch", n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, results);
+  if (rc) return rc;
+  fl_context *ctx = trk->ctx;
+  fl_track_params P;
+  if ((rc = track_params(ctx, params, P))) return rc;
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_track_batch: the tracker has no device");
+  if ((rc = track_passes(trk, n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, P))) return rc;
   // 6. one copy, one wait
-  if ((rc = fl_tracker_results(trk, trk->d_out, T * sizeof(fl_track_result), results))) return rc;
+  if ((rc = fl_tracker_results(trk, trk->d_out, (size_t)n_tracks * sizeof(fl_track_result), results))) return rc;
   trk->last_passes = P.passes;
+  trk->track_verified = false;
+  return FL_OK;
+}
+
+// device time of the stages the last fl_track_batch_verified ran after its passes: {fused render and score, finish and pick} in
+// ms; the passes themselves are fl_dev_tracker_stage_ms's
+extern "C" int fl_dev_tracker_track_verified_ms(fl_tracker *trk, float out[2])
+{
+  if (!trk || !out || !trk->track_verified) return FL_ERR_INVALID;
+  const hipEvent_t *ev = trk->ev + FL_TRACK_EVENTS + FL_VERIFY_EVENTS;
+  for (int k = 0; k < 2; ++k)
+    if (hipEventElapsedTime(out + k, ev[k], ev[k + 1]) != hipSuccess) return FL_ERR_HIP;
+  return FL_OK;
+}
+
+static const fl_track_verify_params k_track_verify_defaults = {{10, 1, 0.f, 0.f}, 0, 0};
+
+extern "C" int fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
+                                       const int32_t *frame_of_track, const float *poses13, int n_groups, const int32_t *group_first,
+                                       const fl_intrinsics *K, const fl_track_params *params, const fl_track_verify_params *vparams,
+                                       fl_verified_track_result *results)
+{
+  int rc = fl_tracker_check_call(trk, "fl_track_batch_verified", n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, results);
+  if (rc || (rc = fl_verify_check_call(trk, "fl_track_batch_verified", K, n_tracks, n_groups, group_first))) return rc;
+  fl_context *ctx = trk->ctx;
+  fl_track_params P;
+  if ((rc = track_params(ctx, params, P))) return rc;
+  const fl_track_verify_params V = vparams ? *vparams : k_track_verify_defaults;
+  if (!fl_verify_params_ok(V.verify)) return fl_set_error(ctx, FL_ERR_INVALID, FL_VERIFY_PARAMS_TEXT);
+  if (V.keep_input != 0 && V.keep_input != 1) return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_verify_params: keep_input is 0 or 1");
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_track_batch_verified: the tracker has no device");
+
+  if ((rc = track_passes(trk, n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, P))) return rc;
+  // 6. the groups, and clear accumulators: a lost track's workgroups leave theirs alone
+  hipStream_t st = ctx->stream;
+  hipEvent_t *ev = trk->ev + FL_TRACK_EVENTS + FL_VERIFY_EVENTS;
+  const int n_wg = V.keep_input ? 2 * n_tracks : n_tracks;
+  if (group_first) {
+    memcpy(trk->stage.group_first, group_first, ((size_t)n_groups + 1) * 4);
+    FL_HIP(ctx, hipMemcpyAsync(trk->d_group_first, trk->stage.group_first, ((size_t)n_groups + 1) * 4, hipMemcpyHostToDevice, st));
+  }
+  FL_HIP(ctx, hipMemsetAsync(trk->d_vacc, 0, (size_t)n_wg * sizeof(FlVerifyAcc), st));
+  FL_HIP(ctx, hipEventRecord(ev[0], st));
+  // 7. every tracked pose, and with keep_input every tracked track's input pose, rendered at the scene's K in LDS and scored: one
+  // launch, always the fused kernel (the render images hold the passes' model-camera renders x 10)
+  const FlVerifyFusedJob j = {n_wg, trk->w, trk->h, V.verify.tau_mm, (float)K->fx, (float)K->fy, (float)K->cx, (float)K->cy,
+                              {trk->d_vtx, nullptr, nullptr, trk->d_tri, trk->n_t}, trk->d_poses, 13, trk->d_frames, trk->frame_stride, trk->d_frame_of, 1,
+                              nullptr, nullptr, -1, trk->d_vacc, trk->d_lost, n_tracks, trk->d_poses_in};
+  if ((rc = fl_launch_verify_fused(ctx, j))) return rc;
+  FL_HIP(ctx, hipEventRecord(ev[1], st));
+  // 8. the records and the decision per track, then the best of every group
+  const TrackVerifiedArgs a = {n_tracks, group_first ? n_groups : 0, trk->w, trk->h, V.verify.min_model_px, V.keep_input, V.verify.min_inlier_ratio,
+                               V.verify.max_behind_ratio, trk->d_out, trk->d_poses_in, (const FlVerifyAcc *)trk->d_vacc,
+                               group_first ? trk->d_group_first : nullptr, trk->d_vout};      // in TrackVerifiedArgs' order
+  hipLaunchKernelGGL(k_track_verified_finish, dim3((n_tracks + 63) / 64), dim3(64), 0, st, a);
+  FL_HIP(ctx, hipGetLastError());
+  if (group_first) {
+    hipLaunchKernelGGL(k_track_verified_pick, dim3((n_groups + 63) / 64), dim3(64), 0, st, a);
+    FL_HIP(ctx, hipGetLastError());
+  }
+  FL_HIP(ctx, hipEventRecord(ev[2], st));
+  // 9. one copy, one wait
+  if ((rc = fl_tracker_results(trk, trk->d_vout, (size_t)n_tracks * sizeof(fl_verified_track_result), results))) return rc;
+  trk->last_passes = P.passes;
+  trk->track_verified = true;
   return FL_OK;
 }

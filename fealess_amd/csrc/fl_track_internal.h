@@ -1,5 +1,5 @@
-// fl_track_internal.h -- what the tracker's entry points share (fl_track.hip: fl_track_batch, fl_verify.hip: fl_verify_batch;
-// not part of the ABI): the tracker, the layout of its pinned block, and the steps of a call, which fl_track.hip defines.
+// fl_track_internal.h -- what the tracker's entry points share (fl_track.hip: fl_track_batch and fl_track_batch_verified,
+// fl_verify.hip: fl_verify_batch; not part of the ABI): the tracker, the layout of its pinned block, and the steps of a call, which fl_track.hip defines.
 #pragma once
 #include "fl_internal.h"
 #include <math.h>
@@ -8,6 +8,7 @@
 
 constexpr int FL_TRACK_EVENTS = 2 + 4 * FL_TRACK_MAX_PASSES;   // start, inputs on the device, then per pass render / rects / ICP / finish
 constexpr int FL_VERIFY_EVENTS = 5;                            // start, inputs on the device, render, score, finish and pick
+constexpr int FL_TRACK_VERIFIED_EVENTS = 3;                    // fl_track_batch_verified after its passes: accumulators clear, fused, finish and pick
 
 // p = base + off (base null: a sizing pass, p is left alone); off moves on by bytes rounded up to 256
 template <class T>
@@ -18,7 +19,8 @@ inline void fl_carve(T *&p, uint8_t *base, size_t &off, size_t bytes)
 }
 
 // The pinned block a call's inputs leave through and its records come back through, and the one statement of its layout:
-// max_tracks poses of 13 floats | frame indices | records (of fl_track_batch or of fl_verify_batch) | max_tracks + 1 group starts
+// max_tracks poses of 13 floats | frame indices | records (of fl_track_batch, fl_verify_batch or fl_track_batch_verified) |
+// max_tracks + 1 group starts
 struct FlTrackStage { float *poses; int32_t *frame_of; uint8_t *results; int32_t *group_first; };
 inline size_t fl_track_stage(FlTrackStage &s, uint8_t *base, int max_tracks)   // returns the bytes; base null: nothing else
 {
@@ -26,7 +28,7 @@ inline size_t fl_track_stage(FlTrackStage &s, uint8_t *base, int max_tracks)   /
   size_t off = 0;
   fl_carve(s.poses, base, off, T * 13 * 4);
   fl_carve(s.frame_of, base, off, T * 4);
-  fl_carve(s.results, base, off, T * std::max(sizeof(fl_track_result), sizeof(fl_verify_result)));
+  fl_carve(s.results, base, off, T * std::max({sizeof(fl_track_result), sizeof(fl_verify_result), sizeof(fl_verified_track_result)}));
   fl_carve(s.group_first, base, off, (T + 1) * 4);
   return off;
 }
@@ -52,14 +54,16 @@ struct fl_tracker {
   FlRefineJob *d_jobs = nullptr;
   fl_recognition_result *d_res = nullptr;
   fl_track_result *d_out = nullptr;
-  uint8_t *d_vacc = nullptr;                    // FL_VERIFY_ACC_BYTES per pose: fl_verify.hip's accumulators
+  uint8_t *d_vacc = nullptr;                    // 2 * max_tracks FlVerifyAcc: a pose's, and with fl_track_batch_verified its input pose's
   fl_verify_result *d_vres = nullptr;
+  fl_verified_track_result *d_vout = nullptr;   // max_tracks records of fl_track_batch_verified
   int32_t *d_group_first = nullptr;             // max_tracks + 1 entries
   uint8_t *h_stage = nullptr;                   // the one pinned allocation
   FlTrackStage stage = {};                      // its parts
-  hipEvent_t ev[FL_TRACK_EVENTS + FL_VERIFY_EVENTS] = {nullptr};   // fl_track_batch's, then fl_verify_batch's
-  int last_passes = 0;                          // of the last fl_track_batch; 0: none yet
+  hipEvent_t ev[FL_TRACK_EVENTS + FL_VERIFY_EVENTS + FL_TRACK_VERIFIED_EVENTS] = {nullptr};   // fl_track_batch's, fl_verify_batch's, the verified stages'
+  int last_passes = 0;                          // of the last fl_track_batch or fl_track_batch_verified; 0: none yet
   bool verified = false;                        // an fl_verify_batch has completed
+  bool track_verified = false;                  // the last call that ran passes was an fl_track_batch_verified
 };
 
 // The steps of a call, in the order an entry point takes them.
@@ -70,6 +74,9 @@ struct fl_tracker {
 // FL_ERR_INVALID or FL_OK, no HIP call.  The entry point's own checks follow, and the device check (FL_ERR_NO_DEVICE) after all.
 int fl_tracker_check_call(fl_tracker *trk, const char *who, int n_frames, const uint16_t *const *depth, int mem, int n, const int32_t *frame_of,
                           const float *poses13, const fl_intrinsics *K, const void *results);
+// 1b. What fl_verify_batch and fl_track_batch_verified ask on top of that: K as floats, which is what the rasteriser gets (fx, fy
+// finite and > 0, cx, cy finite), and with group_first its rules against n poses.  FL_ERR_INVALID or FL_OK, no HIP call.
+int fl_verify_check_call(fl_tracker *trk, const char *who, const fl_intrinsics *K, int n, int n_groups, const int32_t *group_first);
 // 2. hipSetDevice, the context's streams joined, ev_start, the frames into their slots, then poses13 and frame_of through the
 // pinned block into d_poses and d_frame_of.  poses_keep (null: none): a second device array the poses pass through on their way
 // to d_poses and stay in.
@@ -86,4 +93,34 @@ __device__ __forceinline__ void bbox_add(int idx, int w, int &x0, int &x1, int &
   const int y = idx / w, x = idx - y * w;
   x0 = min(x0, x); x1 = max(x1, x);
   y0 = min(y0, y); y1 = max(y1, y);
+}
+
+// A pose's verification accumulators, zeroed before the launch.  box = {w - x0, h - y0, x1 + 1, y1 + 1}: zero means "no pixel"
+// and every entry grows, so one atomicMax serves the four sides.
+struct FlVerifyAcc {
+  int32_t n[5];                                 // model, missing, inlier, front, behind
+  int32_t box[4];
+  int32_t pad;
+  unsigned long long sum;                       // of |d| over the inliers
+};
+static_assert(sizeof(FlVerifyAcc) == FL_VERIFY_ACC_BYTES, "what fl_tracker_create and the detector's scratch allocate per pose");
+
+// The finish of fl_verify_batch on one accumulator: rect, counts, ratios, accepted; best is left 0 (k_verify_finish,
+// k_track_verified_finish)
+__device__ __forceinline__ fl_verify_result fl_verify_record(const FlVerifyAcc &c, int w, int h, int min_model_px, float min_inlier_ratio,
+                                                             float max_behind_ratio)
+{
+  fl_verify_result o;
+  memset(&o, 0, sizeof(o));                     // status = FL_OK; an empty render leaves every other field zero too
+  if (c.n[0] > 0) {
+    const int x0 = w - c.box[0], y0 = h - c.box[1];
+    o.rect[0] = x0; o.rect[1] = y0; o.rect[2] = c.box[2] - x0; o.rect[3] = c.box[3] - y0;
+    o.n_model = c.n[0]; o.n_missing = c.n[1]; o.n_inlier = c.n[2]; o.n_front = c.n[3]; o.n_behind = c.n[4];
+    o.sum_abs_inlier = (int64_t)c.sum;
+    o.inlier_ratio = (float)c.n[2] / (float)c.n[0];
+    o.behind_ratio = (float)c.n[4] / (float)c.n[0];
+    o.accepted = c.n[0] >= min_model_px && (min_inlier_ratio <= 0.f || o.inlier_ratio >= min_inlier_ratio) &&
+                 (max_behind_ratio <= 0.f || o.behind_ratio <= max_behind_ratio);
+  }
+  return o;
 }

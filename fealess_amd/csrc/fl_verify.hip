@@ -17,6 +17,8 @@
 // With the context's verify_fused option, k_verify_fused (below) takes the place of the render and k_verify_score: it fills the
 // same accumulators from a render that stays in LDS.  fl_recognize_batch_instances_verified (fl_pipeline.hip) runs it on the
 // refined poses of a batch where they lie, through fl_launch_verify_fused, and finishes them through fl_launch_verify_finish.
+// fl_track_batch_verified (fl_track.hip) runs the same body as k_verify_fused_tracks, through the same launcher: the poses its
+// passes left on the device and, in the same launch, the poses it came in with, a lost track's workgroups exiting at once.
 #include "fl_track_internal.h"
 #include "fl_raster.h"
 
@@ -25,15 +27,6 @@ namespace {
 constexpr int VB = 256;                         // k_verify_score: threads per workgroup
 constexpr int V_LOADS = 4;                      // loads in flight per thread
 constexpr int V_STRIP_PX = VB * V_LOADS * 8;    // pixels per strip, on both paths
-
-// A pose's accumulators, zeroed before the launch.  box = {w - x0, h - y0, x1 + 1, y1 + 1}: zero means "no pixel" and every
-// entry grows, so one atomicMax serves the four sides.
-struct FlVerifyAcc {
-  int32_t n[5];                                 // model, missing, inlier, front, behind
-  int32_t box[4];
-  int32_t pad;
-  unsigned long long sum;                       // of |d| over the inliers
-};
 
 struct VerifyArgs {
   int n_poses, n_groups, w, h, n_strips, tau, min_model_px;
@@ -233,7 +226,9 @@ __device__ __forceinline__ void raster_box(const RenderArgs &r, const TriSetup &
   }
 }
 
-__global__ __launch_bounds__(VF) void k_verify_fused(FusedArgs a)
+// One pose by one workgroup: the mesh at `pose` against the frame `scn`, the counts into accumulator t.  The whole of both
+// kernels below but for which pose, which frame and whether at all.
+__device__ __forceinline__ void verify_fused_pose(const FusedArgs &a, int t, const float *pose, const uint16_t *scn)
 {
   extern __shared__ unsigned zbuf[];            // a band's z-buffer, a.budget words
   __shared__ int red[9][VF_WAVES];
@@ -241,17 +236,7 @@ __global__ __launch_bounds__(VF) void k_verify_fused(FusedArgs a)
   __shared__ float queue[VF_QUEUE][VF_ENTRY];   // the triangles the whole workgroup walks
   __shared__ int q_n;
   const FlVerifyFusedJob &j = a.j;
-  // Workgroups go to the device's eight XCDs in turn.  The live slots of a recognition batch are the same few slots of every
-  // frame, so in slot order some XCDs would get twice the poses of others; walking the frames first deals them out evenly.
-  int t = blockIdx.x;
-  if (!j.frame_of) {
-    const int n_frames = j.n_poses / j.per_frame, slot = t / n_frames;
-    t = (t - slot * n_frames) * j.per_frame + slot;
-  }
-  if (j.job_idx && !(j.job_idx[t] >= 0 && j.res[t].found == 1 && (j.class_idx < 0 || j.res[t].best.class_idx == j.class_idx))) return;
   const int tid = threadIdx.x, lane = tid & (FL_WAVE - 1), wave = tid / FL_WAVE;
-  const float *pose = j.pose + (size_t)t * j.pose_stride;
-  const uint16_t *scn = (const uint16_t *)(j.frames + j.frame_stride * (size_t)(j.frame_of ? j.frame_of[t] : t / j.per_frame));
   RenderArgs r;
   r.vtx = j.mesh.vtx; r.nrm = nullptr; r.col = nullptr; r.tri = j.mesh.tri; r.pose = j.pose;
   r.n_t = j.mesh.n_t; r.w = j.w; r.h = j.h;
@@ -400,23 +385,37 @@ __global__ __launch_bounds__(VF) void k_verify_fused(FusedArgs a)
   ((FlVerifyAcc *)j.acc)[t] = o;
 }
 
+// the poses of a recognition batch or of fl_verify_batch
+__global__ __launch_bounds__(VF) void k_verify_fused(FusedArgs a)
+{
+  const FlVerifyFusedJob &j = a.j;
+  // Workgroups go to the device's eight XCDs in turn.  The live slots of a recognition batch are the same few slots of every
+  // frame, so in slot order some XCDs would get twice the poses of others; walking the frames first deals them out evenly.
+  int t = blockIdx.x;
+  if (!j.frame_of) {
+    const int n_frames = j.n_poses / j.per_frame, slot = t / n_frames;
+    t = (t - slot * n_frames) * j.per_frame + slot;
+  }
+  if (j.job_idx && !(j.job_idx[t] >= 0 && j.res[t].found == 1 && (j.class_idx < 0 || j.res[t].best.class_idx == j.class_idx))) return;
+  verify_fused_pose(a, t, j.pose + (size_t)t * j.pose_stride,
+                    (const uint16_t *)(j.frames + j.frame_stride * (size_t)(j.frame_of ? j.frame_of[t] : t / j.per_frame)));
+}
+
+// a tracker's tracks (FlVerifyFusedJob::skip): the poses the passes returned, then the poses the call came in with
+__global__ __launch_bounds__(VF) void k_verify_fused_tracks(FusedArgs a)
+{
+  const FlVerifyFusedJob &j = a.j;
+  const int t = blockIdx.x, u = t < j.split ? t : t - j.split;
+  if (j.skip[u]) return;                        // lost in the passes: no mesh walk (uniform per workgroup)
+  verify_fused_pose(a, t, (t < j.split ? j.pose : j.pose_in) + (size_t)u * j.pose_stride,
+                    (const uint16_t *)(j.frames + j.frame_stride * (size_t)j.frame_of[u]));
+}
+
 __global__ __launch_bounds__(64) void k_verify_finish(VerifyArgs a)
 {
   const int t = blockIdx.x * 64 + threadIdx.x;
   if (t >= a.n_poses) return;
-  const FlVerifyAcc c = a.acc[t];
-  fl_verify_result o;
-  memset(&o, 0, sizeof(o));                     // status = FL_OK; an empty render leaves every other field zero too
-  if (c.n[0] > 0) {
-    const int x0 = a.w - c.box[0], y0 = a.h - c.box[1];
-    o.rect[0] = x0; o.rect[1] = y0; o.rect[2] = c.box[2] - x0; o.rect[3] = c.box[3] - y0;
-    o.n_model = c.n[0]; o.n_missing = c.n[1]; o.n_inlier = c.n[2]; o.n_front = c.n[3]; o.n_behind = c.n[4];
-    o.sum_abs_inlier = (int64_t)c.sum;
-    o.inlier_ratio = (float)c.n[2] / (float)c.n[0];
-    o.behind_ratio = (float)c.n[4] / (float)c.n[0];
-    o.accepted = c.n[0] >= a.min_model_px && (a.min_inlier_ratio <= 0.f || o.inlier_ratio >= a.min_inlier_ratio) &&
-                 (a.max_behind_ratio <= 0.f || o.behind_ratio <= a.max_behind_ratio);
-  }
+  fl_verify_result o = fl_verify_record(a.acc[t], a.w, a.h, a.min_model_px, a.min_inlier_ratio, a.max_behind_ratio);
   o.best = a.group_first ? 0 : o.accepted;
   a.out[t] = o;
 }
@@ -436,19 +435,20 @@ __global__ __launch_bounds__(64) void k_verify_pick(VerifyArgs a)
 }
 }  // namespace
 
-static_assert(sizeof(FlVerifyAcc) == FL_VERIFY_ACC_BYTES, "what fl_tracker_create allocates per pose");
 static_assert(sizeof(fl_verify_result) == 64, "fl_verify_result is 64 bytes (include/fealess_hip.h)");
+static_assert(sizeof(fl_verified_track_result) == 368, "fl_verified_track_result is 368 bytes (include/fealess_hip.h)");
 static const fl_verify_params k_verify_defaults = {10, 1, 0.f, 0.f};
 
 int fl_launch_verify_fused(fl_context *ctx, const FlVerifyFusedJob &j)
 {
-  // LDS above 64 KB is the kernel's to ask for, once per device, and for the compiled budget whatever this launch uses
+  // LDS above 64 KB is a kernel's to ask for, once per device, and for the compiled budget whatever this launch uses
   if (!ctx->verify_fused_attr) {
     FL_HIP(ctx, hipFuncSetAttribute((const void *)k_verify_fused, hipFuncAttributeMaxDynamicSharedMemorySize, FL_VERIFY_FUSED_PX * 4));
+    FL_HIP(ctx, hipFuncSetAttribute((const void *)k_verify_fused_tracks, hipFuncAttributeMaxDynamicSharedMemorySize, FL_VERIFY_FUSED_PX * 4));
     ctx->verify_fused_attr = true;
   }
   FusedArgs a = {j, 1.0f / j.fx, 1.0f / j.fy, (int)(ctx->opt.verify_fused_px ? ctx->opt.verify_fused_px : FL_VERIFY_FUSED_PX)};   // ifx, ify: as fl_launch_render_chunk
-  hipLaunchKernelGGL(k_verify_fused, dim3((unsigned)j.n_poses), dim3(VF), (size_t)a.budget * 4, ctx->stream, a);
+  hipLaunchKernelGGL(j.skip ? k_verify_fused_tracks : k_verify_fused, dim3((unsigned)j.n_poses), dim3(VF), (size_t)a.budget * 4, ctx->stream, a);
   FL_HIP(ctx, hipGetLastError());
   return FL_OK;
 }
@@ -463,6 +463,23 @@ int fl_launch_verify_finish(fl_context *ctx, int n_poses, int w, int h, const fl
   a.out = out;
   hipLaunchKernelGGL(k_verify_finish, dim3((n_poses + 63) / 64), dim3(64), 0, ctx->stream, a);
   FL_HIP(ctx, hipGetLastError());
+  return FL_OK;
+}
+
+int fl_verify_check_call(fl_tracker *trk, const char *who, const fl_intrinsics *K, int n, int n_groups, const int32_t *group_first)
+{
+  fl_context *ctx = trk->ctx;
+  // 1e-60 is a positive double and a zero float, 1e300 an infinite one
+  const float fx = (float)K->fx, fy = (float)K->fy, cx = (float)K->cx, cy = (float)K->cy;
+  if (!(std::isfinite(fx) && fx > 0.f && std::isfinite(fy) && fy > 0.f && std::isfinite(cx) && std::isfinite(cy)))
+    return fl_set_error(ctx, FL_ERR_INVALID, "%s: fx, fy must be finite and > 0, cx, cy finite, as floats too", who);
+  if (group_first) {
+    bool ok = n_groups >= 1 && n_groups <= trk->max_tracks && group_first[0] == 0;
+    for (int g = 0; ok && g < n_groups; ++g) ok = group_first[g + 1] >= group_first[g] && group_first[g + 1] <= n;
+    if (!ok || group_first[n_groups] != n)
+      return fl_set_error(ctx, FL_ERR_INVALID, "%s: group_first must have n_groups + 1 (n_groups 1..%d) non-decreasing entries from 0 to the number of poses",
+                          who, trk->max_tracks);
+  }
   return FL_OK;
 }
 
@@ -488,18 +505,9 @@ extern "C" int fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *co
 {
   int rc = fl_tracker_check_call(trk, "fl_verify_batch", n_frames, depth, mem, n_poses, frame_of_pose, poses13, K, results);
   if (rc) return rc;
+  if ((rc = fl_verify_check_call(trk, "fl_verify_batch", K, n_poses, n_groups, group_first))) return rc;
   fl_context *ctx = trk->ctx;
-  // K as floats, which is what the rasteriser gets: 1e-60 is a positive double and a zero float, 1e300 an infinite one
   const float fx = (float)K->fx, fy = (float)K->fy, cx = (float)K->cx, cy = (float)K->cy;
-  if (!(std::isfinite(fx) && fx > 0.f && std::isfinite(fy) && fy > 0.f && std::isfinite(cx) && std::isfinite(cy)))
-    return fl_set_error(ctx, FL_ERR_INVALID, "fl_verify_batch: fx, fy must be finite and > 0, cx, cy finite, as floats too");
-  if (group_first) {
-    bool ok = n_groups >= 1 && n_groups <= trk->max_tracks && group_first[0] == 0;
-    for (int g = 0; ok && g < n_groups; ++g) ok = group_first[g + 1] >= group_first[g] && group_first[g + 1] <= n_poses;
-    if (!ok || group_first[n_groups] != n_poses)
-      return fl_set_error(ctx, FL_ERR_INVALID, "fl_verify_batch: group_first must have n_groups + 1 (n_groups 1..%d) non-decreasing entries from 0 to n_poses",
-                          trk->max_tracks);
-  }
   const fl_verify_params P = params ? *params : k_verify_defaults;
   if (!fl_verify_params_ok(P))
     return fl_set_error(ctx, FL_ERR_INVALID, "fl_verify_params: tau_mm 0..65535, min_model_px >= 1, finite thresholds");

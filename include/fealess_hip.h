@@ -574,6 +574,55 @@ int  fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth
                      int n_poses, const int32_t *frame_of_pose, const float *poses13,
                      int n_groups, const int32_t *group_first, const fl_intrinsics *K,
                      const fl_verify_params *params, fl_verify_result *results);
+/* ---- verified tracking: fl_track_batch whose `tracked` is the verification's ---------------------------------------------------
+ * Opt-in; fl_track_batch and fl_verify_batch are unchanged.  depth, mem, frame_of_track, poses13, K and params are as
+ * fl_track_batch takes them, n_groups and group_first as fl_verify_batch takes them; vparams == NULL: the defaults below.
+ * Everything is queued on the context's stream and the call waits once, at the end; it allocates nothing.
+ *   passes   all params->passes passes of fl_track_batch, with its lost rule and its gates.  icp_tracked is that call's
+ *            `tracked`; track.status, the rects and track.det are that call's.
+ *   verify   once, after the last pass, on the device: every track with icp_tracked = 1 has the pose the passes returned
+ *            (det.R_final | det.T_final, the twelve floats fl_track_batch would report) verified against its frame exactly as
+ *            fl_verify_batch states it -- the render at the SCENE camera (float)K->fx .., not at the model camera the passes
+ *            render with, then score and finish -> `verify`.  With keep_input = 1 the pose the track came in with is verified
+ *            against the same frame -> `verify_in`.  The render of a pose stays in the LDS of one workgroup whatever the
+ *            context option verify_fused says.  Both records carry best = accepted.  A track with icp_tracked = 0 is not
+ *            verified: both records zero, tracked = 0, pose = the input pose, kept_input = 0.
+ *   decide   per track with icp_tracked = 1, A = verify.accepted and B = keep_input && verify_in.accepted:
+ *              neither    tracked = 0, pose = the input pose, kept_input = 0
+ *              only A     tracked = 1, pose = the passes' pose
+ *              only B     tracked = 1, pose = the input pose as a 4x4, kept_input = 1
+ *              both       the input pose is kept (kept_input = 1) only when it verifies strictly better,
+ *                         (int64)verify_in.n_inlier * verify.n_model > (int64)verify.n_inlier * verify_in.n_model;
+ *                         a tie keeps the passes' pose
+ *            A track's CHOSEN record is verify_in where kept_input = 1, else verify.
+ *   pick     groups as fl_verify_batch's (several start poses for one object, say the previous pose and a motion model's
+ *            prediction): best = 1 for at most one track of a group, among its tracked = 1 tracks the one whose chosen record
+ *            has the largest n_inlier / n_model, compared exactly as fl_verify_batch compares, a tie to the lower index; a group
+ *            without a tracked member has no best.  group_first == NULL (n_groups is ignored): best = tracked.
+ * With the default gates every non-empty render is accepted: the call then reports what fl_track_batch reports, plus figures
+ * (a pose whose render at the scene camera is empty is not accepted, and its track comes back with tracked = 0).
+ * FL_ERR_INVALID, nothing written, before the first HIP call: everything fl_track_batch refuses; fx, fy not finite and > 0 or
+ * cx, cy not finite as floats; fl_verify_batch's rules for n_groups and group_first; fl_verify_params' ranges; keep_input
+ * outside {0, 1}. */
+typedef struct {
+  fl_verify_params verify;             /* tau_mm, min_model_px, min_inlier_ratio, max_behind_ratio: ranges and defaults of fl_verify_batch */
+  int32_t keep_input;                  /* 1: the pose a track came in with is verified too and kept where it verifies strictly better; default 0 */
+  int32_t reserved;
+} fl_track_verify_params;
+typedef struct {
+  fl_track_result track;               /* status, rects, det: exactly what fl_track_batch reports; tracked and pose: by the rule above */
+  fl_verify_result verify;             /* of the pose the passes returned; zeros when icp_tracked == 0 */
+  fl_verify_result verify_in;          /* of the input pose; zeros when keep_input == 0 or icp_tracked == 0 */
+  int32_t icp_tracked;                 /* what fl_track_batch's `tracked` is for this track */
+  int32_t kept_input;                  /* 1: pose is the input pose because it verified better (or alone) */
+  int32_t best;                        /* the group pick */
+  int32_t reserved;
+} fl_verified_track_result;            /* 368 bytes */
+int  fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
+                             int n_tracks, const int32_t *frame_of_track, const float *poses13,
+                             int n_groups, const int32_t *group_first, const fl_intrinsics *K,
+                             const fl_track_params *params, const fl_track_verify_params *vparams,
+                             fl_verified_track_result *results);
 /* ---- verified instance pick: fl_recognize_batch_instances whose pick among a group's members is the verification's -----------
  * The call chain of fl_recognize_batch_instances up to and including its ONE ICP launch, then, all on the device and on the
  * same n_frames * max_instances * hyp_per_instance job slots: the verification of every LIVE slot -- its job exists, its
