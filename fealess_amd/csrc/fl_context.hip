@@ -98,13 +98,15 @@ int fl_icp_stream(fl_context *ctx, hipStream_t *out)
 extern "C" int fl_abi_version(void) { return FL_ABI_VERSION; }
 
 // name, environment variable, field, environment value in hex, accepted values lo .. hi (icp_occ: 0, 4 or 5;
-// frontend_chunk_rows: multiples of 60; scan_run: 0 = automatic; scan_prune_step: 0 = automatic, 2, 4 or 8)
+// frontend_chunk_rows: multiples of 60; scan_run: 0 = automatic; scan_prune_step: 0 = automatic, 2, 4 or 8;
+// scan_first: 0 = automatic, 8, 12, 14 or 16)
 struct FlOptionName { const char *name, *env; long fl_context::Options::*field; bool hex; long lo, hi; };
 static const FlOptionName fl_option_names[] = {
   {"scan_prune", "FL_SCAN_PRUNE", &fl_context::Options::scan_prune, false, 0, 1},
   {"scan_prune_mid", "FL_SCAN_PRUNE_MID", &fl_context::Options::scan_prune_mid, true, -1, 0xFF},
   {"scan_prune_lanes", "FL_SCAN_PRUNE_LANES", &fl_context::Options::scan_prune_lanes, false, 0, 1},
   {"scan_prune_step", "FL_SCAN_PRUNE_STEP", &fl_context::Options::scan_prune_step, false, 0, 8},
+  {"scan_first", "FL_SCAN_FIRST", &fl_context::Options::scan_first, false, 0, 16},
   {"icp_wide", "FL_ICP_WIDE", &fl_context::Options::icp_wide, false, -1, 1},
   {"icp_occ", "FL_ICP_OCC", &fl_context::Options::icp_occ, false, 0, 5},
   {"icp_order", "FL_ICP_ORDER", &fl_context::Options::icp_order, false, 0, 1},
@@ -129,6 +131,7 @@ static bool fl_option_valid(const FlOptionName &o, long v)
   if (o.field == &fl_context::Options::frontend_chunk_rows) return v % 60 == 0;
   if (o.field == &fl_context::Options::verify_fused_px) return v == 0 || v >= FL_WAVE;
   if (o.field == &fl_context::Options::scan_prune_step) return v == 0 || v == 2 || v == 4 || v == 8;
+  if (o.field == &fl_context::Options::scan_first) return v == 0 || v == 8 || v == 12 || v == 14 || v == 16;
   return o.field != &fl_context::Options::icp_occ || v == 0 || v >= 4;
 }
 
@@ -766,6 +769,10 @@ extern "C" int fl_detector_finalize(fl_detector *det, int w0, int h0, int max_ba
     det->n_scan_items = (int)items.size();
     det->scan_item_g.clear();
     for (const FlScanItem &it : items) det->scan_item_g.push_back(it.g);
+    std::vector<int> nfs;
+    for (const FlScanItem &it : items) nfs.push_back((int)(it.chunk_nf >> 16));
+    if (!nfs.empty()) std::nth_element(nfs.begin(), nfs.begin() + nfs.size() / 2, nfs.end());
+    det->scan_nf_typical = nfs.empty() ? 0 : nfs[nfs.size() / 2];
     if ((rc = upload(ctx, items, &det->d_scan_items))) return rc;
   }
   if ((rc = upload(ctx, scan_off, &det->d_scan_off))) return rc;

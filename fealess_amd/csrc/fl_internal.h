@@ -37,6 +37,8 @@ struct fl_context {
                                 // whole or not at all
     long scan_prune_step = 0;   // FL_SCAN_PRUNE_STEP: feature loads between two checks behind a modality's first eight: 8, 4 or 2;
                                 // 0 = 4 from 256 frames on, else 8 (fl_scan_step)
+    long scan_first = 0;        // FL_SCAN_FIRST: features of a modality's first piece, streamed and with one check behind it: 8, 12, 14
+                                // or 16; 0 = by batch size, bank and threshold (fl_scan_first)
     long icp_wide = -1;         // FL_ICP_WIDE: -1 by batch size, 0 / 1 force the 256- / 1024-thread ICP kernel
     long icp_occ = 0;           // FL_ICP_OCC: 0 by batch size, 4 / 5 force the 256-thread parity kernel built for 4 / 5 workgroups per CU
     long icp_order = 1;         // FL_ICP_ORDER: ICP jobs dealt longest first
@@ -280,6 +282,7 @@ struct fl_detector {
   // device tables
   FlScanItem *d_scan_items = nullptr;    // (pyramid g, 1024-position chunk) pairs that have positions to scan: k_scan's work list
   int n_scan_items = 0;
+  int scan_nf_typical = 0;    // the median over the work items of a pyramid's features at the coarsest level (fl_scan_first)
   std::vector<int32_t> scan_item_g;      // the items' pyramids on the host (fl_apply_class_filter)
   uint32_t *d_scan_off = nullptr;        // every (pyramid, modality)'s offsets, padded to groups of 8, + FL_SCAN_OFF_PAD
   FlFineHdr *d_fine_hdr = nullptr;       // n_pyr * (L-1) * M, index (g*(L-1)+l)*M+m

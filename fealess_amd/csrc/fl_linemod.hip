@@ -563,14 +563,16 @@ __device__ __forceinline__ uint32_t rl(uint32_t v, int l) { return (uint32_t)__b
 #endif
 // Waves per SIMD.  Without pruning the kernel is bound by the rate of its vector loads and five waves are the optimum (measured
 // after the DPP change, ms per 1280 frames x 360 templates: 3: 2.32, 4: 1.95, 5: 1.71, 6: 1.77, 8: 2.17).  With pruning an item is
-// two or three round trips and little else, the launch is bound by how many of them are in flight, and six beat five
-// (profiles/README.md): the same code built twice, the launch picks by ScanArgs::prune.
+// two or three round trips and little else, the launch is bound by how many of them are in flight, and six beat five, eight
+// beat seven where the first piece is short (profiles/README.md): the same code built twice, the launch picks by ScanArgs::prune.
 #ifndef FL_SCAN_WPE
 #define FL_SCAN_WPE 5
 #endif
 #ifndef FL_SCAN_WPE_PRUNED
-#define FL_SCAN_WPE_PRUNED 6
+#define FL_SCAN_WPE_PRUNED 8
 #endif
+// (The attribute makes the compiler pad a build's register allocation to its waves: a build for fewer than eight waves holds
+// fewer although its code fits 64 vector and 80 scalar registers.)
 #ifndef FL_SCAN_STEP
 #define FL_SCAN_STEP 4            // feature loads between two checks behind a modality's first eight (option scan_prune_step: 8, 4 or 2)
 #endif
@@ -581,18 +583,20 @@ __device__ __forceinline__ uint32_t rl(uint32_t v, int l) { return (uint32_t)__b
 // development aid: per launch {items, feature-load instructions, lane-loads (lanes in EXEC), items that ran to their end}, then
 // the items ended by a check after f features of all modalities (f = 0 .. 126); printed by the launcher after a stream
 // synchronisation (tools/dev/README.md)
-#define FL_SCAN_STATS_N (4 + 2 * FL_MAX_FEATURES + 1)
+#define FL_SCAN_STATS_N (4 + 2 * FL_MAX_FEATURES + 1 + 1)
 __device__ unsigned long long d_scan_stats[FL_SCAN_STATS_N];
 #define FL_SCAN_STAT(i, v) do { if (lane == 0) atomicAdd(&d_scan_stats[i], (unsigned long long)(v)); } while (0)
 #else
 #define FL_SCAN_STAT(i, v) do { } while (0)
 #endif
 template <int N> struct ScanInt { static constexpr int value = N; };
-// STEP: behind a modality's first group of eight, the feature loads between two checks of the bound (8, 4 or 2)
-template <int WPE, int STEP>
+// STEP: behind a modality's first piece, the feature loads between two checks of the bound (8, 4 or 2)
+// FIRST: the features of a modality's first piece, which has one check, behind it (8, 12, 14 or 16; fl_scan_first)
+template <int WPE, int STEP, int FIRST>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_scan(ScanArgs a)
 {
   static_assert(STEP == 8 || STEP == 4 || STEP == 2, "a group of eight offsets is cut into equal parts");
+  static_assert(FIRST == 8 || FIRST == 12 || FIRST == 14 || FIRST == 16, "the first piece ends inside the second group, at an even feature");
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // XCD-aware block mapping: workgroups are dealt round-robin over the 8 XCDs, each with its own
   // 4 MB L2.  All blocks of one frame are given the same residue mod 8, so a frame's linear
@@ -605,31 +609,55 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   if (it >= a.n_items) return;
   // lanes 0..15: the dwords of item `idx`'s record; the others: the dword that holds its class-filter flag
   const int l7 = lane & 7;
+  // What only an item with candidates or a tapped one needs is read from the kernel arguments when it is needed: in scalar
+  // registers for the whole loop it would crowd out the offsets and records the loop keeps in flight, and above 80 scalar
+  // registers a SIMD holds seven waves, not eight.  (Not what EVERY item needs: a scalar load in front of an item's first
+  // vector loads is a round trip of its own -- the switches read per item made the launch 14 % slower.)
+  const FL_CONST_AS ScanArgs *ka = (const FL_CONST_AS ScanArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+  auto kargs = [&]() {
+    const FL_CONST_AS ScanArgs *kr = ka;
+    asm volatile("" : "+s"(kr));
+    return kr;
+  };
   auto request_item = [&](int idx) {
     const uint32_t *p = lane < 16 ? (const uint32_t *)(a.items + idx) + lane : (const uint32_t *)(a.enabled + (idx & ~3));
     return *p;
   };
+  // the launch's switches in one scalar register: bits 0..7 the mask of the groups with checks, then F_*
+  enum : unsigned { F_PRUNE = 0x100u, F_BY_LANE = 0x200u, F_TAPPED = 0x400u, F_TAPS = 0x800u, F_M2 = 0x1000u };
+  const unsigned kflags = (a.prune ? F_PRUNE | (a.prune_mid & 0xFFu) | (a.prune_lanes ? F_BY_LANE : 0u) : 0u) | (a.dbg_count ? F_TAPS : 0u) |
+                          (a.M > 1 ? F_M2 : 0u);
   uint32_t rec = request_item(it);
   const uint8_t *lm[FL_MAX_MODALITIES];                  // the frame's linear memories
   for (int m = 0; m < FL_MAX_MODALITIES; ++m) lm[m] = a.ws + (size_t)frame * a.ws_stride + a.lm_off[m];
   const float thr100 = a.threshold / 100.f;
   const unsigned lane_off = (unsigned)lane * 16u;
-  const int dbg_first = a.dbg_first;
-  const unsigned dbg_count = (unsigned)a.dbg_count;
-  // What only an item with candidates or a tapped one needs is read from the kernel arguments when it is needed: in scalar
-  // registers for the whole loop it would crowd out the offsets and records the loop keeps in flight.
-  const FL_CONST_AS ScanArgs *ka = (const FL_CONST_AS ScanArgs *)__builtin_amdgcn_kernarg_segment_ptr();
 
   // One work item.  `return` = on to the wave's next item; every per-item value starts from zero in here.
   auto scan_item = [&](const uint32_t r) {
+    // The record stays in its vector register for the whole item and a field is read from it (v_readlane) where it is used:
+    // all of them in scalar registers from the start were nine held for modality 1 and the emission while modality 0 runs.
+    auto field = [&](int i) {
+      uint32_t rr = r;
+      asm volatile("" : "+v"(rr));
+      return rl(rr, i);
+    };
     const int g = (int)rl(r, 8), chunk = (int)(rl(r, 9) & 0xFFFFu), nf_all = (int)(rl(r, 9) >> 16);
-    const int rP[FL_MAX_MODALITIES] = {(int)rl(r, 10), (int)rl(r, 13)}, rB[FL_MAX_MODALITIES] = {(int)rl(r, 11), (int)rl(r, 14)};
-    const uint32_t rN[FL_MAX_MODALITIES] = {rl(r, 12), rl(r, 15)};
     const int j0 = chunk * 1024 + lane * 16;
 
-    uint32_t tot[16];
+    // The lane's 16 totals, two per register: a total is at most 4 x 126 = 504, so position 4 q + b sits in the 16-bit half
+    // b >> 1 of tp[2 q + (b & 1)] -- the even and the odd bytes of accumulator word q, each added with one 32-bit add that never
+    // carries from one half into the other.  Eight registers instead of sixteen are what lets the kernel live in 64.
+    uint32_t tp[8];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) tot[i] = 0;
+    for (int i = 0; i < 8; ++i) tp[i] = 0;
+    auto tot_at = [&](int i) { return (tp[2 * (i >> 2) + (i & 1)] >> (((i >> 1) & 1) * 16)) & 0xFFFFu; };
+    auto tot_max = [&]() {                                 // the lane's largest total (v_pk_max_u16)
+      u16x2 m = __builtin_bit_cast(u16x2, tp[0]);
+#pragma unroll
+      for (int i = 1; i < 8; ++i) m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2, tp[i]));
+      return (uint32_t)max(m.x, m.y);
+    };
     // Exact pruning between modalities: a feature adds at most 4 to a position (SIMILARITY_LUT's largest entry), so once the
     // largest total of this wave's 1024 positions plus 4 x (the features of the modalities still to come) cannot exceed the
     // coarse threshold, no position of the chunk can become a candidate (`raw > raw_threshold`, linemod.cpp:1490-1492) and the
@@ -639,9 +667,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     // colour edges stop after 16 features).  Not when the raw maps are tapped (fl_similarity_maps), and FL_SCAN_PRUNE=0
     // switches it off (a.prune).
     const int prune_threshold = (int)(2 * nf_all + thr100 * (2 * nf_all) + 0.5f);   // = raw_threshold below
-    const bool tapped = (unsigned)(g - dbg_first) < dbg_count;
-    const bool prune = a.prune && !tapped;
-    const unsigned mid = prune ? a.prune_mid : 0u;
+    // The item's switches live in ONE scalar register and are tested where they are used: as booleans of their own the
+    // compiler keeps each in a register pair from here to the item's end.  A tapped item (only a launch with taps can have
+    // one) does not prune.
+    unsigned flags_ = kflags;
+    const unsigned flags_m2 = kflags & F_M2;
+    if (kflags & F_TAPS) {
+      const FL_CONST_AS ScanArgs *ki = kargs();
+      if ((unsigned)(g - ki->dbg_first) < (unsigned)ki->dbg_count) flags_ = F_TAPPED | flags_m2;
+    }
+    const unsigned flags = flags_;
+    auto flag = [&](unsigned bits) {
+      unsigned f = flags;
+      asm volatile("" : "+s"(f));
+      return (f & bits) != 0u;
+    };
     // Per lane: the bound is computed for a lane's own 16 positions, so a lane that misses it can stop for itself.  `alive`
     // holds the lanes that still own a reachable position, wave-uniform in a scalar register pair.  A check removes lanes and
     // never brings one back; the item ends when none is left.  The loads of the groups that follow run under
@@ -649,27 +689,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     // stale or, next to a live lane, take in a wrong tail: it has no say in later checks and is kept out of the emission.
     // (Even unguarded it could not emit where its tail is right: its stale totals are below its true totals, which are below
     // the threshold.)  Without a.prune_lanes a check keeps every lane or none, the wave-wide rule.
-    const bool by_lane = prune && a.prune_lanes;
     uint64_t alive = ~0ull;
     auto still = [&](bool reachable) {                     // one check: false = the item is over
       const uint64_t b = __ballot(reachable) & alive;
-      alive = by_lane || b == 0ull ? b : ~0ull;
+      alive = flag(F_BY_LANE) || b == 0ull ? b : ~0ull;
       return alive != 0ull;
     };
     [[maybe_unused]] int f_done = 0;                                     // (FL_SCAN_STATS: features added so far)
     FL_SCAN_STAT(0, 1);
     // the group of eight offsets in flight (lanes 0..7) and where in a.offs it is from: the record brings modality 0's first
     uint32_t ov = r;
-    int o_at = (rN[0] & 0xFFFFu) ? rB[0] : -1;
+    int o_at = (rl(r, 12) & 0xFFFFu) ? (int)rl(r, 11) : -1;
     int nf = 0;
 #pragma unroll
     for (int m = 0; m < FL_MAX_MODALITIES; ++m) {
-      if (m >= a.M) break;
-      const int P = rP[m], off_begin = rB[m], n_pad = (int)(rN[m] & 0xFFFFu), h_nf = (int)(rN[m] >> 16);
+      if (m > 0 && !flag(F_M2)) break;                     // (FL_MAX_MODALITIES is 2)
+      const uint32_t rN = m == 0 ? rl(r, 12) : field(12 + 3 * m);
+      const int P = (int)(m == 0 ? rl(r, 10) : field(10 + 3 * m)), off_begin = (int)(m == 0 ? rl(r, 11) : field(11 + 3 * m));
+      const int n_pad = (int)(rN & 0xFFFFu), h_nf = (int)(rN >> 16);
       uint32_t mx_tot = 0;                                 // the lane's largest total of the modalities done
-      if (prune && m > 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mx_tot = max(mx_tot, tot[i]);
+      if (m > 0 && flag(F_PRUNE)) {
+        mx_tot = tot_max();
         if (!still((int)mx_tot + 4 * (nf_all - nf) > prune_threshold)) {                      // wave-uniform
           FL_SCAN_STAT(4 + f_done, 1);
           return;
@@ -696,68 +736,89 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
       const int lanes_on = min(64, ((P - chunk * 1024 + 15) >> 4) + 1);
       const uint64_t lanes_mask = lanes_on >= 64 ? ~0ull : (1ull << lanes_on) - 1ull;
       // behind this modality's last group the next modality's first is requested (whether or not that one then runs)
-      const int next_begin = rB[m + 1 < FL_MAX_MODALITIES ? m + 1 : m];
-      for (int k = 0; k < n_pad; k += 8) {
-        const int at = off_begin + k;
-        if (o_at != at) ov = a.offs[at + l7];              // rare: the modality before this one added nothing in this chunk
-        // The group after this one, requested before this group's vector loads are waited for: a group costs one memory
-        // round trip, not two.  Past a bank's last group this reads the table's FL_SCAN_OFF_PAD entries; an offset beyond
-        // n_pad is never turned into a load.
-        const int nxt_at = k + 8 < n_pad ? at + 8 : next_begin;
-        const uint32_t nxt = a.offs[nxt_at + l7];
-        // N of the group's loads from its offset S0 on, under one EXEC region: the lanes that are alive and their upper
-        // neighbours, of those this modality has positions for
-        auto add_features = [&](auto s0_, auto n_) {
-          constexpr int S0 = decltype(s0_)::value, N = decltype(n_)::value;
-          uint32_t o[N];
-#pragma unroll
-          for (int u = 0; u < N; ++u) o[u] = rl(ov, S0 + u);
-          const uint64_t need = (alive | alive << 1) & lanes_mask;
-          FL_SCAN_STAT(1, N);
-          FL_SCAN_STAT(2, N * __builtin_popcountll(need));
-          // Lane 63's bytes 16..19 have no upper neighbour to come from: a scalar load per feature, at an address all over the
-          // linear memories, i.e. a miss of the scalar cache that goes to L2 -- sixteen per item.  They are needed only
-          // where lane 63 loads at all: not for a template whose positions end below the chunk's last lane (52 lanes of a
-          // bench template), nor once lane 63 is dead.  Elsewhere the lane the DPP has no source for keeps a zero.
-          const bool tail_on = FL_SCAN_TAIL_ALWAYS || (need >> 63) != 0ull;   // wave-uniform
-          uint32_t tail[N];
-#pragma unroll
-          for (int u = 0; u < N; ++u) tail[u] = 0u;
-          if (__builtin_amdgcn_inverse_ballot_w64(need)) {
-          uint4 v[N];
-          uint32_t e[N];
-          unsigned mis_all = 0;                            // the misalignments, four bits each: one scalar register
-          if (tail_on) {
-#pragma unroll
-            for (int u = 0; u < N; ++u) tail[u] = sload1(lm_u + o[u] - ((lm_mis + o[u]) & 3u) + 1024);
-          }
-#pragma unroll
-          for (int u = 0; u < N; ++u) {
-            const unsigned off = o[u];
+      auto next_begin = [&]() { return m + 1 < FL_MAX_MODALITIES ? (int)field(11 + 3 * (m + 1)) : off_begin; };
+      // The group after the one in work is requested before that one's vector loads are waited for: a group costs one memory
+      // round trip, not two.  Past a bank's last group this reads the table's FL_SCAN_OFF_PAD entries; an offset beyond
+      // n_pad is never turned into a load.
+      uint32_t nxt = 0;
+      auto request = [&](int at) { return a.offs[at + l7]; };
+      {
+        // One piece: N features from offset S0 of `ov` on -- those behind the group's eighth from `ov2`, the group after it --
+        // under one EXEC region: the lanes that are alive and their upper neighbours, of those this modality has positions
+        // for.  The first eight loads are issued at once; load 8 + u is issued when load u has been added, into the registers
+        // that one leaves, so a long piece keeps eight loads in flight and the load registers stay 32.  No branch stands
+        // between the loads of a piece.
+        // TAIL: lane 63 loads, and its bytes 16..19 have no upper neighbour to come from.  Lane f of the wave then fetches
+        // the dword behind lane 63's sixteen bytes of the feature at offset f -- ONE vector load in front of the piece's
+        // feature loads (vector loads return in order), taken apart with v_readlane and a select when the feature is
+        // added.  The addresses are all over the linear memories; as one scalar load per feature they were misses of the
+        // scalar cache, sixteen per item, and sixteen address pairs and results in scalar registers.  They are needed only
+        // where lane 63 loads at all: not for a template whose positions end below the chunk's last lane (52 lanes of a
+        // bench template), nor once lane 63 is dead.  Elsewhere the lane the DPP has no source for takes a zero.
+        auto piece = [&](auto s0_, auto n_, auto tail_, const uint32_t ov2, const uint32_t tv) {
+          constexpr int S0 = decltype(s0_)::value, N = decltype(n_)::value, InFlight = N < 8 ? N : 8;
+          constexpr bool TAIL = decltype(tail_)::value != 0;
+          uint4 v[InFlight];
+          unsigned mis_all = 0;                            // the misalignments, two bits each: one scalar register
+          auto issue = [&](const int u) {
+            unsigned off = rl(S0 + u < 8 ? ov : ov2, (S0 + u) & 7);
+            // (a streamed load waits for the sums of the one whose registers it takes: without this the compiler issues the
+            // piece's loads all at once, into twice the registers.  The tie is on the scalar offset, not on the vector register
+            // it is read from: a copy of that one made under the piece's EXEC would leave out the dead lanes it is read from.)
+            if (u >= InFlight) asm("" : "+s"(off) : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
             const unsigned mis_u = (lm_mis + off) & 3u;
-            mis_all |= mis_u << (4 * u);
+            mis_all |= mis_u << (2 * u);
             // buffer_load ... v_lane_off, s[rsrc], s_feature_off offen: the lane's byte offset is one loop-invariant VGPR and
             // the feature's offset a scalar operand -- no per-lane 64-bit address arithmetic (it was 2 of the 10 VALU
             // instructions per feature)
             const u32x4 ld = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, off - mis_u + 4u, 0);   // 4-byte aligned
-            v[u] = make_uint4(ld.x, ld.y, ld.z, ld.w);
-            e[u] = (uint32_t)__builtin_amdgcn_update_dpp((int)tail[u], (int)v[u].x, 0x130, 0xF, 0xF, false);   // wave_shl:1
-          }
+            v[u % InFlight] = make_uint4(ld.x, ld.y, ld.z, ld.w);
+          };
+          auto take = [&](const int u) {
+            const unsigned mis_u = (mis_all >> (2 * u)) & 3u;
+            const uint4 x = v[u % InFlight];
+            uint32_t e = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x.x, 0x130, 0xF, 0xF, true);        // wave_shl:1
+            if (TAIL) {
+              const uint32_t t = rl(tv, S0 + u);           // (read for the wave, then selected: no branch)
+              e = lane == 63 ? t : e;
+            }
+            a0 += __builtin_amdgcn_alignbyte(x.y, x.x, mis_u);
+            a1 += __builtin_amdgcn_alignbyte(x.z, x.y, mis_u);
+            a2 += __builtin_amdgcn_alignbyte(x.w, x.z, mis_u);
+            a3 += __builtin_amdgcn_alignbyte(e, x.w, mis_u);
+          };
+#pragma unroll
+          for (int u = 0; u < InFlight; ++u) issue(u);
 #pragma unroll
           for (int u = 0; u < N; ++u) {
-            const unsigned mis_u = (mis_all >> (4 * u)) & 3u;
-            a0 += __builtin_amdgcn_alignbyte(v[u].y, v[u].x, mis_u);
-            a1 += __builtin_amdgcn_alignbyte(v[u].z, v[u].y, mis_u);
-            a2 += __builtin_amdgcn_alignbyte(v[u].w, v[u].z, mis_u);
-            a3 += __builtin_amdgcn_alignbyte(e[u], v[u].w, mis_u);
+            take(u);
+            if (u + InFlight < N) issue(u + InFlight);
           }
-          if (S0 == 0) asm volatile("" :: "v"(nxt));       // (keeps the request above in front of this group's loads)
+        };
+        auto add_features = [&](auto s0_, auto n_, const uint32_t ov2) {
+          constexpr int S0 = decltype(s0_)::value, N = decltype(n_)::value;
+          const uint64_t need = (alive | alive << 1) & lanes_mask;
+          FL_SCAN_STAT(1, N);
+          FL_SCAN_STAT(2, N * __builtin_popcountll(need));
+          const bool tail_on = FL_SCAN_TAIL_ALWAYS || (need >> 63) != 0ull;   // wave-uniform
+          // (by lanes S0 .. S0 + N - 1 whether or not they are alive.  A first piece above eight takes lanes 8 .. 15's addresses
+          // from `ov2`, the request just issued, and so waits for it in front of the piece: a round trip only a launch in
+          // which lane 63 loads pays; not measured apart, profiles/README.md)
+          uint32_t tv = 0;
+          if (tail_on && (unsigned)(lane - S0) < (unsigned)N) {
+            const uint32_t of = lane < 8 ? ov : ov2;
+            tv = __builtin_amdgcn_raw_buffer_load_b32(rsrc, of - ((lm_mis + of) & 3u) + 4u + 1024u, 0, 0);
+          }
+          if (__builtin_amdgcn_inverse_ballot_w64(need)) {
+            if (tail_on) piece(s0_, n_, ScanInt<1>{}, ov2, tv);
+            else piece(s0_, n_, ScanInt<0>{}, ov2, tv);
+            if (S0 == 0) asm volatile("" :: "v"(nxt));     // (keeps the request above in front of this group's loads)
           }
           f_done += N;
         };
         // the same bound inside the modality, `done` of its (padded) features in: the lane's largest byte so far on top of its
         // largest finished total (an over-estimate of its largest partial total, so nothing reachable is ever dropped)
-        auto reachable = [&](int done) {
+        auto reachable = [&](int done, [[maybe_unused]] bool first_piece) {
           const u16x2 b0 = pk_bytes_max(a0), b1 = pk_bytes_max(a1), b2 = pk_bytes_max(a2), b3 = pk_bytes_max(a3);
           const u16x2 bm = __builtin_elementwise_max(__builtin_elementwise_max(b0, b1), __builtin_elementwise_max(b2, b3));
           const int part = (int)max(bm.x, bm.y);
@@ -766,57 +827,103 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
           // generous -- it may still collect from a modality whose template_positions reach further)
           if (still((int)mx_tot + part + 4 * left > prune_threshold)) return true;                // wave-uniform
           FL_SCAN_STAT(4 + f_done, 1);
+          if (first_piece) FL_SCAN_STAT(FL_SCAN_STATS_N - 1, 1);
           return false;
         };
-        // a modality's first eight features in one piece (no item ends before them), the groups behind them STEP at a time;
-        // bit g of `mid` enables the checks inside and at the end of group g
-        const bool chk = (mid >> (k >> 3)) & 1u;           // wave-uniform
-        if (STEP == 8 || k == 0) {
-          add_features(ScanInt<0>{}, ScanInt<8>{});
-          if (chk && !reachable(k + 8)) return;
-        } else if (STEP == 4) {
-          add_features(ScanInt<0>{}, ScanInt<4>{});
-          if (chk && !reachable(k + 4)) return;
-          add_features(ScanInt<4>{}, ScanInt<4>{});
-          if (chk && !reachable(k + 8)) return;
-        } else {
-          add_features(ScanInt<0>{}, ScanInt<2>{});
-          if (chk && !reachable(k + 2)) return;
-          add_features(ScanInt<2>{}, ScanInt<2>{});
-          if (chk && !reachable(k + 4)) return;
-          add_features(ScanInt<4>{}, ScanInt<2>{});
-          if (chk && !reachable(k + 6)) return;
-          add_features(ScanInt<6>{}, ScanInt<2>{});
-          if (chk && !reachable(k + 8)) return;
+        // A modality's first piece has no check inside: FIRST features where the modality has a second group, its first eight
+        // where it has not.  No item of the bench bank ends before its ninth feature, so the check behind eight only costs a
+        // round trip; 16 end nearly every item after ONE round trip and are the slowest, because every lane then loads what the
+        // checks at 12 and 14 would have spared most of them: 12 measure best (profiles/README.md).  Its check, and those of the
+        // rest of that group, go by the bit of the group that holds feature FIRST - 1.  Behind it the pieces end at the multiples of STEP; bit g of
+        // `mid` enables the checks inside and at the end of group g.
+        int k = 0;
+        if (n_pad > 0) {
+          if (o_at != off_begin) ov = request(off_begin);  // rare: the modality before this one added nothing in this chunk
+          const int nxt_at = 8 < n_pad ? off_begin + 8 : next_begin();
+          nxt = request(nxt_at);
+          if (FIRST > 8 && n_pad > 8) {
+            const int nx2_at = 16 < n_pad ? off_begin + 16 : next_begin();   // the group behind the two this piece reads
+            const uint32_t nx2 = request(nx2_at);
+            add_features(ScanInt<0>{}, ScanInt<FIRST>{}, nxt);
+            asm volatile("" :: "v"(nx2));
+            if (flag(2u) && !reachable(FIRST, true)) return;
+            ov = nxt;
+            if (FIRST == 12 && STEP == 2) {
+              add_features(ScanInt<4>{}, ScanInt<2>{}, 0u);
+              if (flag(2u) && !reachable(14, false)) return;
+            } else if (FIRST == 12) {
+              add_features(ScanInt<4>{}, ScanInt<4>{}, 0u);
+              if (flag(2u) && !reachable(16, false)) return;
+            }
+            if (FIRST == 14 || (FIRST == 12 && STEP == 2)) {
+              add_features(ScanInt<6>{}, ScanInt<2>{}, 0u);
+              if (flag(2u) && !reachable(16, false)) return;
+            }
+            ov = nx2;
+            o_at = FL_SCAN_OFFSETS_AHEAD ? nx2_at : -1;
+            k = 16;
+          } else {
+            add_features(ScanInt<0>{}, ScanInt<8>{}, 0u);
+            if (flag(1u) && !reachable(8, true)) return;
+            ov = nxt;
+            o_at = FL_SCAN_OFFSETS_AHEAD ? nxt_at : -1;
+            k = 8;
+          }
         }
-        ov = nxt;
-        o_at = FL_SCAN_OFFSETS_AHEAD ? nxt_at : -1;
+        for (; k < n_pad; k += 8) {
+          const int at = off_begin + k;
+          if (o_at != at) ov = request(at);                // (FL_SCAN_OFFSETS_AHEAD = 0)
+          const int nxt_at = k + 8 < n_pad ? at + 8 : next_begin();
+          nxt = request(nxt_at);
+          const bool chk = flag(1u << (k >> 3));           // wave-uniform (k < 64: a bit of the mask)
+          if (STEP == 8) {
+            add_features(ScanInt<0>{}, ScanInt<8>{}, 0u);
+            if (chk && !reachable(k + 8, false)) return;
+          } else if (STEP == 4) {
+            add_features(ScanInt<0>{}, ScanInt<4>{}, 0u);
+            if (chk && !reachable(k + 4, false)) return;
+            add_features(ScanInt<4>{}, ScanInt<4>{}, 0u);
+            if (chk && !reachable(k + 8, false)) return;
+          } else {
+            add_features(ScanInt<0>{}, ScanInt<2>{}, 0u);
+            if (chk && !reachable(k + 2, false)) return;
+            add_features(ScanInt<2>{}, ScanInt<2>{}, 0u);
+            if (chk && !reachable(k + 4, false)) return;
+            add_features(ScanInt<4>{}, ScanInt<2>{}, 0u);
+            if (chk && !reachable(k + 6, false)) return;
+            add_features(ScanInt<6>{}, ScanInt<2>{}, 0u);
+            if (chk && !reachable(k + 8, false)) return;
+          }
+          ov = nxt;
+          o_at = FL_SCAN_OFFSETS_AHEAD ? nxt_at : -1;
+        }
       }
       const uint32_t acc[4] = {a0, a1, a2, a3};
+      const int nv = P - j0;                          // the lane's positions below template_positions: cells >= it stay 0 (:1160)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        uint32_t byte = (acc[i >> 2] >> ((i & 3) * 8)) & 0xFFu;
-        tot[i] += (j0 + i < P) ? byte : 0u;          // cells >= template_positions stay 0 (:1160)
+      for (int q = 0; q < 4; ++q) {
+        const int c = nv - 4 * q;                     // ... of them in word q
+        const uint32_t w = acc[q] & (c >= 4 ? ~0u : c <= 0 ? 0u : (1u << (8 * c)) - 1u);
+        tp[2 * q] += w & 0x00FF00FFu;
+        tp[2 * q + 1] += (w >> 8) & 0x00FF00FFu;
       }
     }
-    if (tapped) {
-      const FL_CONST_AS ScanArgs *kr = ka;
-      asm volatile("" : "+s"(kr));
+    // (the pyramid's index is read from the record again where it is needed: the record stays in its vector register)
+    const int g_end = (int)field(8);
+    if (flag(F_TAPPED)) {
+      const FL_CONST_AS ScanArgs *kr = kargs();
       const int WH = kr->WH;
-      uint16_t *d = kr->dbg + ((size_t)frame * dbg_count + (g - dbg_first)) * WH;
+      uint16_t *d = kr->dbg + ((size_t)frame * (unsigned)kr->dbg_count + (g_end - kr->dbg_first)) * WH;
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        if (j0 + i < WH) d[j0 + i] = (uint16_t)tot[i];
+        if (j0 + i < WH) d[j0 + i] = (uint16_t)tot_at(i);
     }
     // coarse threshold (linemod.cpp:1483-1506), float expression evaluated as written
     const int raw_threshold = (int)(2 * nf + thr100 * (2 * nf) + 0.5f);
-    uint32_t mx = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) mx = max(mx, tot[i]);
+    const uint32_t mx = tot_max();
     FL_SCAN_STAT(3, 1);
     if ((int)mx <= raw_threshold || !__builtin_amdgcn_inverse_ballot_w64(alive)) return;   // dead lanes emit nothing (see `alive`)
-    const FL_CONST_AS ScanArgs *kr = ka;
-    asm volatile("" : "+s"(kr));
+    const FL_CONST_AS ScanArgs *kr = kargs();
     const int W = kr->W, WH = kr->WH, T = kr->T, cap = kr->cap;
     uint8_t *ws = kr->ws + (size_t)frame * kr->ws_stride;
     int *count = (int *)(ws + kr->off_count);
@@ -824,7 +931,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     const int offset = T / 2 + (T % 2 - 1);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int raw = (int)tot[i];
+      const int raw = (int)tot_at(i);
       const int j = j0 + i;
       if (raw > raw_threshold && j < WH) {
         const int rr = j / W, c = j - rr * W;
@@ -833,7 +940,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
           FlCand cd;
           cd.x = c * T + offset;
           cd.y = rr * T + offset;
-          cd.g = g;
+          cd.g = g_end;
           cd.sim = (raw * 100.f) / (4 * nf) + 0.5f;                               // :1502
           cand[idx] = cd;
         }
@@ -1506,10 +1613,11 @@ __global__ __launch_bounds__(1024) void k_sort_unique(SortArgs a)
 #define FL_SCAN_STRIDED 1
 #endif
 #define FL_SCAN_FILL 4
+#define FL_SCAN_FILL_WAVES 6      // (the pruned scan's waves per SIMD when the run lengths were measured: the small batches keep them)
 static int fl_scan_run(const fl_context *ctx, int items, int n_frames)
 {
   if (ctx->opt.scan_run) return (int)ctx->opt.scan_run;
-  const long need = (long)FL_SCAN_FILL * ctx->cus * 4 * (ctx->opt.scan_prune ? FL_SCAN_WPE_PRUNED : FL_SCAN_WPE);
+  const long need = (long)FL_SCAN_FILL * ctx->cus * 4 * (ctx->opt.scan_prune ? FL_SCAN_FILL_WAVES : FL_SCAN_WPE);
   int run = FL_SCAN_RUN_AUTO;
   while (run > 1 && (long)n_frames * ((items + run - 1) / run) < need) run /= 2;
   return run;
@@ -1527,6 +1635,25 @@ static int fl_scan_step(const fl_context *ctx, int n_frames)
 {
   if (ctx->opt.scan_prune_step) return (int)ctx->opt.scan_prune_step;
   return n_frames >= FL_SCAN_STEP_FRAMES ? FL_SCAN_STEP : 8;
+}
+
+// Features of a modality's first piece (the FIRST the kernel is built for).  A longer piece pays where the check behind eight
+// features ends no item: where a position may lose more than seven features' worth of points (4 nf - raw_threshold > 28, from
+// the bank's typical feature count and the call's threshold), so that only a lane that has scored next to nothing goes there.
+// Measured both ways (profiles/README.md): the 62-feature bench bank at 75 % may lose 31 points and gains 5 % with 12; the
+// 30-feature coarsest level of the three-level bank may lose 15, most of its items end behind eight features, and 12 cost it
+// 20 % of the scan.  The boundary at 28 lies between these two measured points and has not been measured itself.
+// FL_SCAN_FIRST from FL_SCAN_STEP_FRAMES frames on, eight below.  Option scan_first != 0 forces a length.
+#ifndef FL_SCAN_FIRST
+#define FL_SCAN_FIRST 12
+#endif
+static int fl_scan_first(const fl_detector *det, int n_frames, float threshold)
+{
+  const fl_context *ctx = det->ctx;
+  if (ctx->opt.scan_first) return (int)ctx->opt.scan_first;
+  const int nf = det->scan_nf_typical;
+  const int raw_threshold = (int)(2 * nf + threshold / 100.f * (2 * nf) + 0.5f);
+  return n_frames >= FL_SCAN_STEP_FRAMES && 4 * nf - raw_threshold > 28 ? FL_SCAN_FIRST : 8;
 }
 
 // Which refinement kernel a fine level gets.  k_refine_lds needs every candidate's window to fit the budget (decided from
@@ -1604,12 +1731,23 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
 #endif
       a.n_frames = n_frames;
       dim3 grid((unsigned)(a.bpf * ((n_frames + 7) / 8) * 8));
-      if (!a.prune) hipLaunchKernelGGL((k_scan<FL_SCAN_WPE, 8>), grid, dim3(256), 0, ctx->stream, a);
-      else switch (fl_scan_step(ctx, n_frames)) {
-      case 2: hipLaunchKernelGGL((k_scan<FL_SCAN_WPE_PRUNED, 2>), grid, dim3(256), 0, ctx->stream, a); break;
-      case 4: hipLaunchKernelGGL((k_scan<FL_SCAN_WPE_PRUNED, 4>), grid, dim3(256), 0, ctx->stream, a); break;
-      default: hipLaunchKernelGGL((k_scan<FL_SCAN_WPE_PRUNED, 8>), grid, dim3(256), 0, ctx->stream, a); break;
+#define FL_SCAN_LAUNCH(WPE, STEP, FIRST) hipLaunchKernelGGL((k_scan<WPE, STEP, FIRST>), grid, dim3(256), 0, ctx->stream, a)
+#define FL_SCAN_LAUNCH_STEP(STEP) \
+      switch (first) { \
+      case 12: FL_SCAN_LAUNCH(FL_SCAN_WPE_PRUNED, STEP, 12); break; \
+      case 14: FL_SCAN_LAUNCH(FL_SCAN_WPE_PRUNED, STEP, 14); break; \
+      case 16: FL_SCAN_LAUNCH(FL_SCAN_WPE_PRUNED, STEP, 16); break; \
+      default: FL_SCAN_LAUNCH(FL_SCAN_WPE_PRUNED, STEP, 8); break; \
       }
+      const int first = fl_scan_first(det, n_frames, threshold);
+      if (!a.prune) FL_SCAN_LAUNCH(FL_SCAN_WPE, 8, 8);
+      else switch (fl_scan_step(ctx, n_frames)) {
+      case 2: FL_SCAN_LAUNCH_STEP(2); break;
+      case 4: FL_SCAN_LAUNCH_STEP(4); break;
+      default: FL_SCAN_LAUNCH_STEP(8); break;
+      }
+#undef FL_SCAN_LAUNCH_STEP
+#undef FL_SCAN_LAUNCH
       FL_HIP(ctx, hipGetLastError());
 #ifdef FL_SCAN_STATS
       {
@@ -1618,8 +1756,9 @@ static int launch_scan_refine_sort(fl_detector *det, int n_frames, float thresho
         FL_HIP(ctx, hipMemcpyFromSymbol(st, HIP_SYMBOL(d_scan_stats), sizeof(st)));
         FL_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(d_scan_stats), zero, sizeof(zero)));
         fprintf(stderr, "k_scan: %d frames, %llu items, %.2f feature loads and %.1f lane-loads per item, %llu items to their end; ended "
-                "after f features:", n_frames, st[0], st[0] ? (double)st[1] / st[0] : 0.0, st[0] ? (double)st[2] / st[0] : 0.0, st[3]);
-        for (int f = 0; f + 4 < FL_SCAN_STATS_N; ++f)
+                "by a first piece's check %llu; after f features:", n_frames, st[0], st[0] ? (double)st[1] / st[0] : 0.0,
+                st[0] ? (double)st[2] / st[0] : 0.0, st[3], st[FL_SCAN_STATS_N - 1]);
+        for (int f = 0; f + 5 < FL_SCAN_STATS_N; ++f)
           if (st[4 + f]) fprintf(stderr, " %d: %llu", f, st[4 + f]);
         fprintf(stderr, "\n");
       }
