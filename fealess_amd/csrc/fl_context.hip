@@ -109,6 +109,7 @@ static const FlOptionName fl_option_names[] = {
   {"scan_first", "FL_SCAN_FIRST", &fl_context::Options::scan_first, false, 0, 16},
   {"icp_wide", "FL_ICP_WIDE", &fl_context::Options::icp_wide, false, -1, 1},
   {"icp_occ", "FL_ICP_OCC", &fl_context::Options::icp_occ, false, 0, 5},
+  {"icp_idx16", "FL_ICP_IDX16", &fl_context::Options::icp_idx16, false, -1, 1},
   {"icp_order", "FL_ICP_ORDER", &fl_context::Options::icp_order, false, 0, 1},
   {"icp_wg_per_cu", "FL_ICP_WG_PER_CU", &fl_context::Options::icp_wg_per_cu, false, 0, 3},
   {"eager_frontend", "FL_EAGER_FRONTEND", &fl_context::Options::eager_frontend, false, 0, 1},

@@ -113,6 +113,13 @@ __device__ __forceinline__ void tile_barrier()
 //   perm   n x i32    organised search: model indices in 16x4-pixel tile order, column by column inside a tile (build_tile_order)
 //   cell_start / cell_cur   CSR offsets of the x/y cell grid (grid search)
 //   nrm   n x 3 f32   unit normals of the reference cloud, index order (FL_ICP_POINT_TO_PLANE only; 0 = unknown)
+// The 16-bit builds of the 256-thread parity kernel (k_icp_pipeline<.., uint16_t>: n <= 65535, so every crop pixel and point index
+// fits 16 bits and 0xFFFF names none) use the same slots at the same offsets:
+//   nn     n x u16    crop pixel of the partner, 0xFFFF = none (read back as -1)
+//   perm   n x u16    model indices in tile order
+//   dterm  n x u16    pix: crop pixel of point i  } written by crop_clouds; l2dist_phase rebuilds ref[i] from them (org_point)
+//   nd     n x f32    zref: its depth factor      } every iteration instead of loading its 12 bytes; that kernel neither defers
+//                                                    the dist_mean chain nor searches ahead of it, so the two slots are free
 struct IcpWsLayout {
   size_t ref, mod, sref, zimg, nn, bnd, nd, dterm, perm, cell_start, cell_cur, nrm, total;
   int ncell_max;
@@ -570,9 +577,11 @@ __device__ __forceinline__ float chain_deferred(const float *__restrict__ dterm,
 // DEFER (parity mode, organised search): the terms go to dterm[] in HBM instead of LDS tiles and are NOT added here;
 // every thread produces, the valid / inlier counts are left in S.cnt / S.inl, and the chain wave adds the terms later
 // (chain_deferred) while the other waves already search for the next iteration.
-template <int MODE, bool DEFER, class SH>
+// REFPIX (the 16-bit builds, every call but the initial one): reference point i is not read from ref[] (12 bytes) but rebuilt from
+// its crop pixel pix[i] and depth factor zref[i] (6 bytes) by org_point, crop_clouds' own expression: bit for bit what ref[i] holds.
+template <int MODE, bool DEFER, bool REFPIX, class SH>
 __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *ref, bnd_t *bnd, float *dterm, int n, float thr,
-                                             const float *Ropt, const float *Topt)
+                                             const float *Ropt, const float *Topt, const uint16_t *pix, const float *zref, const OrgGeom &og)
 {
   constexpr bool parity = MODE == FL_ICP_PARITY && !DEFER;   // chains in this phase
   constexpr int TQ = parity ? SH::TQ : SH::BS;           // rows per tile
@@ -602,18 +611,27 @@ __device__ __forceinline__ float l2dist_phase(SH &S, float *mod, const float *re
   // memory queue (s_waitcnt vmcnt(0)) once per tile (see the A2 phase in icp_run).  With chains in this phase (parity) the
   // tile barrier is a raw s_barrier behind an lgkmcnt wait: the LDS tile must be complete, the global stores of this
   // phase (mod, bnd) need not be before the phase ends.
-  struct Row { F3 a, b; float bnd; };
+  struct Row { F3 a, b; float bnd; int p; };              // REFPIX: b.x = the depth factor, p = the crop pixel, until row_process
+  const float inv_cw = REFPIX ? uniform_f(1.0f / (float)max(og.cw, 1)) : 0.0f;
   auto row_load = [&](Row &w, int t) {
     const int i = min(t * TQ + slot, n - 1);              // clamped: unused past the end
     w.a = ld3_u32(mod, i);
-    w.b = ld3_u32(ref, i);
+    if (REFPIX) { w.p = ld_u32(pix, i); w.b.x = ld_u32(zref, i); }
+    else w.b = ld3_u32(ref, i);
     w.bnd = Ropt ? bnd_ld(bnd, i) : 0.0f;
   };
   auto row_process = [&](const Row &w, int t) {
     const int i = t * TQ + slot;
     float term = 0.0f;
     float a[3] = {w.a.x, w.a.y, w.a.z};
-    const float b0 = w.b.x, b1 = w.b.y, b2 = w.b.z;
+    F3 rp = w.b;
+    if (REFPIX) {
+      // the pixel's crop row by a float reciprocal and one correction step (phase A2's row_write): exact, the pixel is below 2^16
+      int vv = (int)(((float)w.p + 0.5f) * inv_cw), uu = w.p - __mul24(vv, og.cw);
+      if (uu < 0) { --vv; uu += og.cw; } else if (uu >= og.cw) { ++vv; uu -= og.cw; }
+      rp = org_point(og, uu, vv, w.b.x);
+    }
+    const float b0 = rp.x, b1 = rp.y, b2 = rp.z;
     if (i < n) {
       if (Ropt) {
         float move = 0.0f;
@@ -825,7 +843,11 @@ __device__ __forceinline__ void icp_result_none(fl_icp_result *res)
 // ---- icpCloudToCloud_Ex (ICP.cpp:617-809) --------------------------------------------------------
 // ORG: the reference cloud is also available as the image `og` describes (sref = image of points + image of indices, perm = tile order), see
 // "Organised search" at the top; otherwise the grid is built here and searched.
-template <int MODE, bool ORG, class SH>
+// IDX: the type nn[] and perm[] are stored in: int, or uint16_t in the 16-bit builds of the 256-thread parity kernel ("none" is
+// IDX(-1), read back as -1: nn_get), which also rebuild phase B's reference point from pix[] / zref[] (l2dist_phase<REFPIX>).
+template <class IDX>
+__device__ __forceinline__ int nn_get(IDX v) { return sizeof(IDX) == 2 && (int)v == 0xFFFF ? -1 : (int)v; }
+template <int MODE, bool ORG, class IDX, class SH>
 __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &L, int n_ref, int n_model,
                         int it_thr, float dmt, float ddt, fl_icp_result *res, const OrgGeom &og)
 {
@@ -836,10 +858,15 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   // the grid search by its index (ref[]); idximg maps a pixel to its index (point-to-plane: normals are stored by index)
   const float *jsrc = ORG ? (const float *)sref : ref;
   const int *idximg = ORG ? (const int *)((const uint8_t *)sref + org_idximg_offset(og.cw * og.ch)) : nullptr;
-  int *nn = (int *)(wsb + L.nn);
+  constexpr bool IDX16 = sizeof(IDX) == 2;
+  static_assert(!IDX16 || (MODE == FL_ICP_PARITY && ORG && SH::NW < 8), "16-bit indices: the 256-thread parity kernel of the organised search only");
+  IDX *nn = (IDX *)(wsb + L.nn);
   bnd_t *bnd = (bnd_t *)(wsb + L.bnd);
   float *nd = (float *)(wsb + L.nd), *dterm = (float *)(wsb + L.dterm);
-  const int *perm = (const int *)(wsb + L.perm);
+  const IDX *perm = (const IDX *)(wsb + L.perm);
+  // 16-bit builds: the crop pixel and depth factor of point i, in the regions this kernel leaves unused (crop_clouds)
+  const uint16_t *pix = (const uint16_t *)(wsb + L.dterm);
+  const float *zref = (const float *)(wsb + L.nd);
   const float *nrm = (const float *)(wsb + L.nrm);
   int *cell_start = (int *)(wsb + L.cell_start), *cell_cur = (int *)(wsb + L.cell_cur);
   constexpr bool plane = MODE == FL_ICP_POINT_TO_PLANE;
@@ -886,13 +913,14 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   // Only the 1024-thread workgroup (batches that leave CUs idle) does this: with four 256-thread workgroups per CU the
   // other workgroups already fill the chain's shadow, and the extra traffic (dterm, nd) costs 7 % there (profiles/README.md).
   constexpr bool SPEC = BS >= ICP_BS_WIDE && MODE == FL_ICP_PARITY && ORG;
-  float mean_ub = l2dist_phase<MODE, SPEC>(S, mod, ref, bnd, dterm, n_model, FLT_MAX, nullptr, nullptr);             // :670
+  static_assert(!(IDX16 && SPEC), "pix[] / zref[] live where the deferred chain keeps dterm[] / nd[]");
+  float mean_ub = l2dist_phase<MODE, SPEC, false>(S, mod, ref, bnd, dterm, n_model, FLT_MAX, nullptr, nullptr, pix, zref, og);   // :670
   int pending = SPEC ? 1 : 0;                            // 1: the initial distances await their chain, 2: an iteration's
   bool have_nn = false;                                  // nn[] / nd[] hold the neighbours of the current model cloud
   float old_mean = 0.0f;                                 // dist_mean before the pending distances (pending == 2)
 
   // what the organised searches read (fl_icp_search.h); the pairs they find go to the `found` callables below
-  const OrgSearchCtx ctx = org_search_ctx(mod, bnd, perm, (const float *)sref, (const float *)(wsb + L.zimg), n_model, og);
+  const auto ctx = org_search_ctx(mod, bnd, perm, (const float *)sref, (const float *)(wsb + L.zimg), n_model, og);
   // the deferred dist_mean chain of the pending distances (chain wave), then -- every wave -- the search for the next iteration
   auto chain_and_search = [&](const int pend, const bool want, const float r_lim, const float old_mean_) {
     if (pend && threadIdx.x < 64) {
@@ -915,7 +943,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     if (want)
       org_search<SH, SPEC>(S, ctx, r_lim, true, [&](bool active, int i, float, float, float, int j, float d) {
         if (active) {
-          nn[i] = j;
+          nn[i] = (IDX)j;
           nd[i] = d;
           if (j >= 0) bnd_st(bnd, i, sqrt_upper(d));             // else: the old partner is still within the old bound
         }
@@ -990,7 +1018,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       auto on_found = [&](bool active, int i, float qx, float qy, float qz, int j, float d) {
         const bool keep = d <= thr;                       // dists[i][0] <= dist_thr (:268)
         if (active) {
-          nn[i] = keep ? j : -1;
+          nn[i] = (IDX)(keep ? j : -1);
           if (j >= 0) bnd_st(bnd, i, sqrt_upper(d));      // else: the old partner is still within the old bound
         }
         if (keep) {
@@ -1058,7 +1086,8 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
         w.m = ld3_u32(mod, ic);
       };
       auto row_gather = [&](Row &w) {                      // SPEC: nn[] holds the neighbour whatever its distance; the pair is kept
-        if (!(w.in && (!SPEC || w.d <= thr))) w.j = -1;    // if d <= dist_thr (:268; NaN = none found)
+        if (!(w.in && (!SPEC || w.d <= thr)) || (IDX16 && w.j == 0xFFFF)) w.j = -1;   // if d <= dist_thr (:268; NaN = none found);
+                                                           // 16-bit builds: "none" was stored as 0xFFFF
         if (ZIMG) w.r.x = ld_u32(zimg, max(w.j, 0));      // 4 bytes: the partner pixel's depth factor (rebuilt in row_write)
         else w.r = ld3_u32(jsrc, max(w.j, 0));
       };
@@ -1139,7 +1168,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
             }
             if (vvalid(ref[3 * i + 2])) { r[0] = ref[3 * i]; r[1] = ref[3 * i + 1]; r[2] = ref[3 * i + 2]; }
           } else {
-            const int j = nn[i];
+            const int j = nn_get(nn[i]);
             if (j >= 0) {
               have_m = have_pair = true;
               m[0] = mod[3 * i]; m[1] = mod[3 * i + 1]; m[2] = mod[3 * i + 2];
@@ -1202,7 +1231,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     for (int k = 0; k < 3; ++k) To[k] = S.Topt[k];
     old_mean = S.dist_mean;
     __syncthreads();
-    mean_ub = l2dist_phase<MODE, SPEC>(S, mod, ref, bnd, dterm, n_model, 3 * old_mean, Ro, To);           // :756, :778-780
+    mean_ub = l2dist_phase<MODE, SPEC, IDX16>(S, mod, ref, bnd, dterm, n_model, 3 * old_mean, Ro, To, pix, zref, og);   // :756, :778-780
     TSTAMP(5);
     if (SPEC) {                                          // the chain, dist_diff and the pose update follow at the loop head
       pending = 2;
@@ -1271,7 +1300,8 @@ __device__ __forceinline__ void scene_normal(const uint16_t *__restrict__ scene,
 
 template <class SH>
 __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16_t *scene, const uint16_t *model, bool model_01mm,
-                           const int *rm, const int *rr, float *ref, float *mod, float *nrm, float *rimg, int *idximg, float *zimg)
+                           const int *rm, const int *rr, float *ref, float *mod, float *nrm, float *rimg, int *idximg, float *zimg,
+                           uint16_t *pix, float *zref)
 {
   constexpr int BS = SH::BS, NW = SH::NW;
   const int cw = rm[2], ch = rm[3], np = cw * ch;
@@ -1328,6 +1358,7 @@ __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16
       const int k = kept_before + before + in_wave;
       ref[3 * k] = A[0]; ref[3 * k + 1] = A[1]; ref[3 * k + 2] = A[2];
       mod[3 * k] = B[0]; mod[3 * k + 1] = B[1]; mod[3 * k + 2] = B[2];
+      if (pix) { pix[k] = (uint16_t)p; zref[k] = zsf_keep; }      // 16-bit builds: what l2dist_phase rebuilds ref[k] from
       if (nrm) {
         float nv[3];
         scene_normal(scene, a.w, a.h, rr[0] + p % cw, rr[1] + p / cw, a.fx, a.fy, a.cx, a.cy, nv);
@@ -1346,8 +1377,8 @@ __device__ __forceinline__ int crop_clouds(SH &S, const IcpArgs &a, const uint16
 // are neighbours; inside a tile column by column): the 64 queries a wave takes per step then project into a
 // compact window of the reference image.
 // Index k of crop pixel p is idximg[p] (the paired compaction keeps the same pixels of both clouds).
-template <class SH>
-__device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int cw, int ch, int n, int *perm)
+template <class SH, class IDX>
+__device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int cw, int ch, int n, IDX *perm)
 {
   constexpr int BS = SH::BS, NW = SH::NW;
   int *cnt = (int *)&S.prod[0][0][0];
@@ -1356,7 +1387,17 @@ __device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int c
   static_assert(TW * TH == 64 && (TW & (TW - 1)) == 0, "a tile is one wavefront of pixels");
   const int ntx = (cw + TW - 1) / TW, nty = (ch + TH - 1) / TH, ntile = ntx * nty;
   if (ntile > CAP) {                                       // more tiles than the scratch holds (crops beyond 1.5 Mpixel): index order
-    for (int i = threadIdx.x; i < n; i += BS) perm[i] = i;
+    if constexpr (sizeof(IDX) == 2) {
+      // (a 32-bit byte offset the compiler cannot turn into a 64-bit pointer walk: that one widened a register pair the kernel
+      // spills during set-up to four registers in the 16-bit builds)
+      for (unsigned i = threadIdx.x; i < (unsigned)n; i += BS) {
+        unsigned o = 2 * i;
+        asm volatile("" : "+v"(o));
+        *(IDX *)((char *)perm + (size_t)o) = (IDX)i;
+      }
+    } else {
+      for (int i = threadIdx.x; i < n; i += BS) perm[i] = i;
+    }
     __syncthreads();
     return;
   }
@@ -1407,7 +1448,7 @@ __device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int c
     bool has;
     const int k = tile_index(t, has);
     const unsigned long long bal = __ballot(has);
-    if (has) perm[cnt[t] + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = k;
+    if (has) perm[cnt[t] + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = (IDX)k;
   }
   __syncthreads();
 }
@@ -1428,13 +1469,15 @@ __global__ __launch_bounds__(BS) void k_icp_clouds(IcpArgs a)
   const OrgGeom none = {};
   if (threadIdx.x == 0) S.cw = 0;                         // the chain wave (IcpSharedT::cw)
   __syncthreads();
-  icp_run<MODE, false>(S, wsb, L, a.job.n_ref, a.job.n_model, a.it_thr, a.dmt, a.ddt, &a.results[blockIdx.x].det.icp, none);
+  icp_run<MODE, false, int>(S, wsb, L, a.job.n_ref, a.job.n_model, a.it_thr, a.dmt, a.ddt, &a.results[blockIdx.x].det.icp, none);
 }
 
 // WPE: waves per SIMD this instance is compiled for.  The 256-thread parity kernel exists twice, for 4 (128 VGPRs) and for 5
 // (96 VGPRs, a few more spills) workgroups per CU: 5 per CU finish a full round of 5 x #CUs frames 4 % faster per frame,
 // 4 per CU win when the batch is not a multiple of that (icp_small_wpe).
-template <int MODE, int BS, int WPE = ICP_WPE(MODE, BS)>
+// IDX: int, or uint16_t for the two 256-thread parity instances the launcher picks when the workspace capacity a.n_max is at most
+// 65535 points (icp_idx16): every crop pixel and point index then fits 16 bits, 0xFFFF is free for "none".
+template <int MODE, int BS, int WPE = ICP_WPE(MODE, BS), class IDX = int>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(WPE, WPE > 4 ? WPE : 4)))
 void k_icp_pipeline(IcpArgs a)
 {
@@ -1520,13 +1563,14 @@ void k_icp_pipeline(IcpArgs a)
   const int np = crop_clouds(S, a, scene, model, model_01mm, S.rect_m, S.rect_r, ref, mod,
                              MODE == FL_ICP_POINT_TO_PLANE ? (float *)(wsb + L.nrm) : nullptr, rimg,
                              (int *)((uint8_t *)rimg + org_idximg_offset(S.rect_m[2] * S.rect_m[3])),
-                             MODE == FL_ICP_PARITY && BS < ICP_BS_WIDE ? (float *)(wsb + L.zimg) : nullptr);
+                             MODE == FL_ICP_PARITY && BS < ICP_BS_WIDE ? (float *)(wsb + L.zimg) : nullptr,
+                             sizeof(IDX) == 2 ? (uint16_t *)(wsb + L.dterm) : nullptr, (float *)(wsb + L.nd));
   // wave-uniform values read from LDS are VGPRs unless told otherwise: the search loop keeps them in SGPRs
   const OrgGeom og = {__builtin_amdgcn_readfirstlane(S.rect_r[2]), __builtin_amdgcn_readfirstlane(S.rect_r[3]),
                       uniform_f((float)S.rect_r[0] - a.cx), uniform_f((float)S.rect_r[1] - a.cy), a.fx, a.fy,
                       __builtin_amdgcn_readfirstlane(S.rect_r[0]), __builtin_amdgcn_readfirstlane(S.rect_r[1]), a.cx, a.cy,
                       uniform_f(1.0f / a.fx), uniform_f(1.0f / a.fy)};
-  build_tile_order(S, (const int *)((const uint8_t *)rimg + org_idximg_offset(og.cw * og.ch)), og.cw, og.ch, np, (int *)(wsb + L.perm));
+  build_tile_order(S, (const int *)((const uint8_t *)rimg + org_idximg_offset(og.cw * og.ch)), og.cw, og.ch, np, (IDX *)(wsb + L.perm));
   // getMean x2 (detection.cpp:165-166), t_match_tmp = r - m (:177), t_init (:199)
   float mc[3] = {0, 0, 0}, rc[3] = {0, 0, 0};
   if (MODE == FL_ICP_PARITY) {
@@ -1578,7 +1622,7 @@ void k_icp_pipeline(IcpArgs a)
     mod[3 * i + 2] = o[2] + t_tmp[2];
   }
   __syncthreads();
-  icp_run<MODE, true>(S, wsb, L, np, np, a.it_thr, a.dmt, a.ddt, &res->det.icp, og);      // :228
+  icp_run<MODE, true, IDX>(S, wsb, L, np, np, a.it_thr, a.dmt, a.ddt, &res->det.icp, og);      // :228
   if (threadIdx.x == 0) {
     const fl_icp_result &ic = res->det.icp;
     float Rt[3];
@@ -1772,13 +1816,25 @@ static int icp_small_wpe(fl_context *ctx, int n_jobs)
   const int r4 = (n_jobs + 4 * cus - 1) / (4 * cus), r5 = (n_jobs + 5 * cus - 1) / (5 * cus);
   return 1.25 * r5 < 1.0 * r4 ? 5 : 4;
 }
+// 16-bit pixel and order indices in the 256-thread parity kernel: chosen per launch by the workspace capacity (no crop of the
+// launch has more pixels: the kernel refuses one that does), so that 0xFFFF names no pixel.  Option icp_idx16 = 0 keeps the
+// 32-bit build; 1 asks for what the default does, and beyond 65535 points still gets the 32-bit build.
+static bool icp_idx16(fl_context *ctx, const IcpArgs &a)
+{
+  return ctx->opt.icp_idx16 != 0 && a.n_max <= 65535;
+}
 template <int MODE>
 static int icp_launch_mode(fl_context *ctx, int n_jobs, const IcpArgs &a)
 {
   const bool wide = icp_wide(ctx, n_jobs);
-  if constexpr (MODE == FL_ICP_PARITY) {              // the 5-per-CU build exists for the parity kernel only
-    if (a.job.kind != 2 && !wide && icp_small_wpe(ctx, n_jobs) == 5)
-      return icp_launch_one<ICP_BS_SMALL>(ctx, k_icp_pipeline<MODE, ICP_BS_SMALL, 5>, n_jobs, a);
+  if constexpr (MODE == FL_ICP_PARITY) {              // the 5-per-CU and the 16-bit builds exist for the parity kernel only
+    if (a.job.kind != 2 && !wide) {
+      const bool five = icp_small_wpe(ctx, n_jobs) == 5;
+      if (icp_idx16(ctx, a))
+        return five ? icp_launch_one<ICP_BS_SMALL>(ctx, k_icp_pipeline<MODE, ICP_BS_SMALL, 5, uint16_t>, n_jobs, a)
+                    : icp_launch_one<ICP_BS_SMALL>(ctx, k_icp_pipeline<MODE, ICP_BS_SMALL, ICP_PARITY_WPE, uint16_t>, n_jobs, a);
+      if (five) return icp_launch_one<ICP_BS_SMALL>(ctx, k_icp_pipeline<MODE, ICP_BS_SMALL, 5>, n_jobs, a);
+    }
   }
   if (a.job.kind == 2)
     return wide ? icp_launch_one<ICP_BS_WIDE>(ctx, k_icp_clouds<MODE, ICP_BS_WIDE>, n_jobs, a)

@@ -442,10 +442,12 @@ __device__ __forceinline__ bool org_window2(const OrgGeom &g, float cul, float c
 // ---- the organised searches: PointsCorresponding (:193-279) for every model point, exact 1-NN within min(bnd[i], r_lim) ----
 // What a search reads (built once per icp_run).  The caller's found(active, i, qx, qy, qz, j, d) owns nn[] / nd[] and the stores
 // into bnd[]; j = -1 and d = NaN when no reference point lies within the radius.
+// IDX: the type perm[] is stored in (int, or uint16_t in the 16-bit builds of the 256-thread parity kernel: ld_u32 zero-extends it)
+template <class IDX>
 struct OrgSearchCtx {
   const float *mod;                  // the queries, their radius bounds (read only: found() stores them), their tile order
   const bnd_t *bnd;
-  const int *perm;
+  const IDX *perm;
   const float *rimg, *zimg;          // the reference image: 12-byte points / depth factors (org_search_pipe only)
   int n_model;
   OrgGeom og;
@@ -453,8 +455,9 @@ struct OrgSearchCtx {
   float cwf;                         // (float)og.cw
   bool small_crop;                   // every position of the image is below 2^24: exact in float32 (slot_pos)
 };
-__device__ __forceinline__ OrgSearchCtx org_search_ctx(const float *mod, const bnd_t *bnd, const int *perm, const float *rimg, const float *zimg,
-                                                       int n_model, const OrgGeom &og)
+template <class IDX>
+__device__ __forceinline__ OrgSearchCtx<IDX> org_search_ctx(const float *mod, const bnd_t *bnd, const IDX *perm, const float *rimg, const float *zimg,
+                                                            int n_model, const OrgGeom &og)
 {
   return {mod, bnd, perm, rimg, zimg, n_model, og, n_model - 1, og.cw * og.ch + NN_OVERRUN - 1, (float)og.cw,
           (long long)og.cw * og.ch + NN_OVERRUN < (1 << 24)};
@@ -469,7 +472,8 @@ __device__ __forceinline__ float4 *org_stage(SH &S, int wv)
   return (float4 *)&S.prod[0][0][0] + wv * ICP_STAGE_CAP;
 }
 // the searchable point of image position pos, from the 12-byte image
-__device__ __forceinline__ float4 org_image_point(const OrgSearchCtx &c, int pos)
+template <class IDX>
+__device__ __forceinline__ float4 org_image_point(const OrgSearchCtx<IDX> &c, int pos)
 {
   const F3 pt = ld3_u32(c.rimg, pos);
   return nn_point(pt.x, pt.y, pt.z, pt.x == INFINITY ? NN_IDX_NONE : pos);
@@ -478,7 +482,8 @@ __device__ __forceinline__ float4 org_image_point(const OrgSearchCtx &c, int pos
 // The L2 fallback, when the union rectangle does not fit the wave's stage (the first iterations, where sqrt(3 dist_mean) is several
 // pixels): every lane's window enumerated in lockstep, maxh rows of maxw positions, ICP_NBQ positions per batch (lanes with a
 // smaller window re-read their own last column / row: duplicates do not change a minimum), straight from the 12-byte image
-__device__ __forceinline__ unsigned long long org_scan(const OrgSearchCtx &c, float qx, float qy, float qz, int u_lo, int u_hi, int v_lo, int v_hi,
+template <class IDX>
+__device__ __forceinline__ unsigned long long org_scan(const OrgSearchCtx<IDX> &c, float qx, float qy, float qz, int u_lo, int u_hi, int v_lo, int v_hi,
                                                        int maxw, int maxh)
 {
   constexpr int NBQ = ICP_NBQ;
@@ -559,8 +564,8 @@ __device__ __forceinline__ unsigned long long scan_batches(const float4 *row0, i
 //  * the window arithmetic has its constants folded and leaves the clamping to the saturating float -> int conversion.
 // It stages from the 12-byte image (the 1024-thread kernel: a frame alone on its CU waits for points rebuilt from the 4-byte
 // image -- 2.92 against 2.67 ms per 8 frames -- where four workgroups per CU gain from the bytes: 32.9 against 34.2 ms per 4096).
-template <class SH, bool SPEC, class F>
-__device__ __forceinline__ void org_search(SH &S, const OrgSearchCtx &c, const float r_lim, const bool poll_stop, F &&found)
+template <class SH, bool SPEC, class IDX, class F>
+__device__ __forceinline__ void org_search(SH &S, const OrgSearchCtx<IDX> &c, const float r_lim, const bool poll_stop, F &&found)
 {
   const OrgGeom &og = c.og;
   const int n_model = c.n_model;
@@ -726,8 +731,8 @@ struct Prep {                                // a prepared step
   bool any, staged;
   float z[ICP_PIPE_NP];                    // depth factors of the staged slots lane + 64 p (in flight until finish)
 };
-template <class SH, class F>
-__device__ __forceinline__ void org_search_pipe(SH &S, const OrgSearchCtx &c, const float r_lim, F &&found)
+template <class SH, class IDX, class F>
+__device__ __forceinline__ void org_search_pipe(SH &S, const OrgSearchCtx<IDX> &c, const float r_lim, F &&found)
 {
   const OrgGeom &og = c.og;
   const int n_model = c.n_model, last_pt = c.last_pt;

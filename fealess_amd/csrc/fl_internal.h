@@ -41,6 +41,9 @@ struct fl_context {
                                 // or 16; 0 = by batch size, bank and threshold (fl_scan_first)
     long icp_wide = -1;         // FL_ICP_WIDE: -1 by batch size, 0 / 1 force the 256- / 1024-thread ICP kernel
     long icp_occ = 0;           // FL_ICP_OCC: 0 by batch size, 4 / 5 force the 256-thread parity kernel built for 4 / 5 workgroups per CU
+    long icp_idx16 = -1;        // FL_ICP_IDX16: -1 / 1 the 256-thread parity kernel keeps nn[] / perm[] as 16-bit values and rebuilds the
+                                // distance phase's reference point from a 16-bit pixel where the workspace capacity is at most 65535
+                                // points (the 32-bit build beyond), 0 = always the 32-bit build
     long icp_order = 1;         // FL_ICP_ORDER: ICP jobs dealt longest first
     long icp_wg_per_cu = 0;     // FL_ICP_WG_PER_CU: 0 = as many 256-thread ICP workgroups per CU as fit (4); 1 .. 3 = at most that many, the
                                 // rest of the CU left to kernels of other streams (two pipelines on one GPU)

@@ -145,7 +145,9 @@ fl_context *fl_detector_get_context(fl_detector *det);
  * first eight: 8, 4 or 2; 0 = 4 from 256 frames on, 8 below; bit g of scan_prune_mid enables the checks inside and at the end of
  * group g), "scan_first" (features of a modality's first piece, which is loaded without a check inside: 8, 12, 14 or 16; 0 = by
  * batch size, bank and threshold; its check goes by the bit of scan_prune_mid of the group that holds its last feature), "icp_wide" (-1 = by batch size; 0 / 1 force the 256- / 1024-thread ICP workgroup),
- * "icp_occ" (0 = by batch size; 4 / 5 force the 256-thread kernel built for that many workgroups per CU), "icp_order" (1 = ICP
+ * "icp_occ" (0 = by batch size; 4 / 5 force the 256-thread kernel built for that many workgroups per CU), "icp_idx16" (-1 = the 256-thread kernel of FL_ICP_PARITY holds pixel and order
+ * indices in 16 bits wherever the crop's capacity is at most 65535 points; 0 = never; 1 = wherever the capacity allows, which is what -1
+ * does: a larger crop runs the 32-bit build whatever the value), "icp_order" (1 = ICP
  * jobs dealt longest first; 0 = frame order), "icp_wg_per_cu" (0 = as many 256-thread ICP workgroups per CU as fit; 1 .. 3 = at
  * most that many, the rest of the CU left to the kernels of other streams), "pipeline_icp" (3; how fl_recognize_submit queues a batch: 0 = every
  * stage on the context's stream; 1 = the ICP stage on a second stream of the context, beside the next batch's LINEMOD stages; 2 / 3 =
@@ -160,10 +162,10 @@ fl_context *fl_detector_get_context(fl_detector *det);
  * "verify_fused_px" (0 = the compiled band budget of 36864 pixels; else a smaller one), and -- sampled by fl_detector_finalize -- "eager_frontend" (1 = finer pyramid
  * levels in full before the scan, the reference's order), "dev_poison" (1 = what the lazy path leaves uncomputed is filled
  * with 0xFF), "ws_pad" (extra bytes of frame-workspace stride).  Their INITIAL values are read once from the environment
- * when the context is created (FL_SCAN_PRUNE, FL_SCAN_PRUNE_MID (hex), FL_SCAN_PRUNE_LANES, FL_SCAN_PRUNE_STEP, FL_SCAN_FIRST, FL_ICP_WIDE, FL_ICP_OCC, FL_ICP_ORDER, FL_ICP_WG_PER_CU,
+ * when the context is created (FL_SCAN_PRUNE, FL_SCAN_PRUNE_MID (hex), FL_SCAN_PRUNE_LANES, FL_SCAN_PRUNE_STEP, FL_SCAN_FIRST, FL_ICP_WIDE, FL_ICP_OCC, FL_ICP_IDX16, FL_ICP_ORDER, FL_ICP_WG_PER_CU,
  * FL_PIPELINE_ICP, FL_FRONTEND_CHUNK_ROWS, FL_SCAN_RUN, FL_REFINE_LDS, FL_REFINE_LDS_BYTES, FL_VERIFY_FUSED, FL_VERIFY_FUSED_PX, FL_EAGER_FRONTEND, FL_DEV_POISON, FL_DEV_WS_PAD); nothing reads the environment after that, so a variable set in a host
  * process later on changes nothing.  Unknown names: FL_ERR_INVALID.
- * Accepted values: scan_prune, scan_prune_lanes, icp_order, eager_frontend, dev_poison {0, 1}; scan_prune_mid -1 .. 0xFF; scan_prune_step {0, 2, 4, 8}; scan_first {0, 8, 12, 14, 16}; icp_wide {-1, 0, 1};
+ * Accepted values: scan_prune, scan_prune_lanes, icp_order, eager_frontend, dev_poison {0, 1}; scan_prune_mid -1 .. 0xFF; scan_prune_step {0, 2, 4, 8}; scan_first {0, 8, 12, 14, 16}; icp_wide, icp_idx16 {-1, 0, 1};
  * icp_occ {0, 4, 5}; icp_wg_per_cu 0 .. 3; pipeline_icp 0 .. 3; frontend_chunk_rows 0 and the multiples of 60 up to 61440; scan_run 0 .. 64; refine_lds 0 .. 2; refine_lds_bytes 0 .. 65536; verify_fused {0, 1}; verify_fused_px 0 and 64 .. 36864; ws_pad 0 .. 16 MiB.  fl_context_set_option refuses any other value with
  * FL_ERR_INVALID and leaves the option as it was; an environment value outside its range keeps the built-in default. */
 int  fl_context_set_option(fl_context *ctx, const char *name, long value);
