@@ -420,11 +420,15 @@ inline FlPlanes fl_level_planes(const fl_detector *det, const FlLevelGeom &g, co
   }
   return pl;
 }
-// one launch each for the n_mod modalities of a level; tiles: see fl_launch_spread_tiles in fl_linemod.hip
+// one launch each for the n_mod modalities of a level; tiles: see fl_launch_spread_tiles in fl_linmem.hip
 int fl_launch_build_lm(fl_context *ctx, const FlPlanes &pl, int n_mod, int n_frames, int w, int h, int T);
 int fl_launch_spread_tiles(fl_context *ctx, const FlPlanes &pl, int n_mod, int n_frames, int w, int h, int T, const uint32_t *tiles,
                            size_t tiles_stride);
-int fl_launch_match_core(fl_detector *det, int n_frames, float threshold);
+int fl_launch_match_core(fl_detector *det, int n_frames, float threshold);   // fl_match.hip: the two above, then the three below
+// fl_scan.hip; dbg (fl_similarity_maps): the raw u16 maps of pyramids [dbg_first, dbg_first + dbg_count), else null
+int fl_launch_scan(fl_detector *det, int n_frames, float threshold, uint16_t *dbg, int dbg_first, int dbg_count);
+int fl_launch_refine(fl_detector *det, int n_frames, float threshold);        // fl_refine.hip: every fine level, lazy levels included
+int fl_launch_sort(fl_detector *det, int n_frames);                           // fl_match.hip
 int fl_launch_lazy_level(fl_detector *det, int n_frames, int level);   // frontend: colour quantisation + spreads of the marked tiles
 // Multi-instance grouping (fl_group_matches, fl_recognize_batch_instances): one workgroup per frame groups that frame's
 // match list.  The list is `matches[0 .. n)` (frame_ws == nullptr, one frame) or the sorted list the match stage left in

@@ -1,4 +1,4 @@
-"""k_scan's schedule with a streamed first piece restated in numpy (fl_linemod.hip: scan_item), no GPU.
+"""k_scan's schedule with a streamed first piece restated in numpy (fl_scan.hip: scan_item), no GPU.
 
 tests/scan_prune_model.py with one more argument: `first`, the features of a modality's first piece (8, 12, 14 or 16).  A
 modality with more than eight padded features adds its first `first` features in one piece, with no check inside, and checks

@@ -1,4 +1,4 @@
-"""k_scan's exact pruning restated in numpy (fl_linemod.hip: scan_item), no GPU.
+"""k_scan's exact pruning restated in numpy (fl_scan.hip: scan_item), no GPU.
 
 A work item is a (pyramid, 1024-position chunk) pair.  Lane i of the wave owns the chunk's positions 16 i .. 16 i + 15.  After the
 first eight features of a modality, then every `step` features (inside the 8-feature groups whose bit is set in `mid`), and

@@ -1,5 +1,5 @@
 """The linear memories (k_build_lm) and the spread images (k_spread) byte for byte against the oracle, at the smallest shapes
-on which the fast kernels of fl_linemod.hip can go wrong: every edge of their launch rules, runs that are no multiples of
+on which the fast kernels of fl_linmem.hip can go wrong: every edge of their launch rules, runs that are no multiples of
 16 bytes, one grid row, several bands with a short last one, batches whose frames and modalities differ, stale memory, and
 the lazy fine level's marked tiles (everything outside them is poisoned under the test suite, tests/conftest.py).
 
@@ -19,7 +19,7 @@ POISON = 0xFF                                # what a lazy batch leaves in the b
                                              # too: such a byte passes as either)
 THR = 60.0
 
-# fl_launch_build_lm (build_lm_band in fl_linemod.hip), for n_frames * n_mod = 1 as Context.build_linear_memories launches it:
+# fl_launch_build_lm (build_lm_band in fl_linmem.hip), for n_frames * n_mod = 1 as Context.build_linear_memories launches it:
 #   generic kernel unless w % 4 == 0, W = w / T >= 4, W % 4 == 0, H = h / T >= 1 and 2 <= T <= 8;
 #   HB = the most rows yt whose LDS, max(align16(HB * (w + 16)), 2048) + T * HB * W, stays within 20 KiB (at least 1; generic
 #        if one row needs more than 64 KiB);

@@ -1,7 +1,7 @@
 """GPU parity with the REFERENCE ITSELF, bit for bit: the HIP kernels against the outputs recorded from the reference's compiled
 linemod.cpp (tests/golden/reference_linemod.npz; always run) and against the compiled reference live (oracle/_ref/, which
 travels with the tree; tests/reference_py.require decides what its absence means), on seeded cases placed on the kernels'
-dispatch edges as fl_linemod.hip states them.  Neither part reads a reference source tree.
+dispatch edges as fl_linmem.hip, fl_scan.hip and fl_refine.hip state them.  Neither part reads a reference source tree.
 
 The ICP half the same way (tests/golden/reference_icp.npz and oracle/_ref/libfealess_ref_icp.so, the reference's compiled ICP.cpp,
 common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp): FL_ICP_PARITY under every build of the ICP kernels that test_gpu_icp.py's
