@@ -107,6 +107,10 @@ class VerifiedInstanceResult(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class Mesh(C.Structure):               # fl_mesh
+    _fields_ = [("vertices", C.c_void_p), ("triangles", C.c_void_p), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32)]
+
+
 class StageTimes(C.Structure):
     _fields_ = [("frontend_ms", C.c_float), ("linmem_ms", C.c_float), ("scan_ms", C.c_float), ("refine_ms", C.c_float),
                 ("sort_ms", C.c_float), ("backproject_ms", C.c_float), ("icp_ms", C.c_float), ("total_ms", C.c_float),
@@ -122,6 +126,7 @@ class DevSelectJob(C.Structure):       # fl_internal.h fl_dev_select_job
 
 FL_RENDER_AMBIENT = 0.2    # include/fealess_hip.h: fl_render_views' ambient when no fl_render_params is given
 FL_TRACK_MAX_PASSES = 4    # include/fealess_hip.h: fl_track_params.passes
+FL_TRACK_MAX_MESHES = 256  # include/fealess_hip.h: fl_tracker_create_meshes
 FL_TOPK_OVERFLOW = -2      # fl_export_topk_batch: template id of record 0 of a frame whose candidate buffers overflowed
 
 _P = C.c_void_p
@@ -197,6 +202,15 @@ SIGNATURES = {
     "fl_verify_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(VerifyParams), _P]),
     "fl_track_batch_verified": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams),
                                      C.POINTER(TrackVerifyParams), _P]),
+    "fl_tracker_create_meshes": (_I, [_P, C.POINTER(Mesh), _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "fl_tracker_num_meshes": (_I, [_P]),
+    "fl_track_batch_meshes": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams), _P]),
+    "fl_verify_batch_meshes": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(VerifyParams), _P]),
+    "fl_track_batch_verified_meshes": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(TrackParams),
+                                            C.POINTER(TrackVerifyParams), _P]),
+    "fl_recognize_batch_instances_verified_meshes": (_I, [_P, _P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics),
+                                                          C.POINTER(RecognitionParams), C.POINTER(InstanceParams), C.POINTER(InstanceVerifyParams),
+                                                          _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "fl_nms": (_I, [_P, _I, _F, C.POINTER(_I), C.POINTER(_I)]),
     "fl_export_topk": (_I, [_P, _I, _I, _I, _P]),
     "fl_merge_topk": (_I, [_P, _I, _P, _I]),
@@ -216,6 +230,7 @@ DEV_SIGNATURES = {
     "fl_dev_extract_select": (_I, [_P, _I, _P]),
     "fl_dev_front_images": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t]),
     "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "fl_dev_tracker_create_host_meshes": (_I, [C.POINTER(Mesh), _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_tracker_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_tracker_track_verified_ms": (_I, [_P, C.POINTER(C.c_float)]),

@@ -616,11 +616,13 @@ class Detector:
 
     def recognize_batch_instances_verified(self, tracker, bgrs, depths, K, max_instances, min_dist_px, hyp_per_instance, class_idx=-1,
                                            member_records=False, threshold=75.0, icp_it_thr=10, dist_mean_thr=0.5, dist_diff_thr=0.01,
-                                           mode=L.FL_ICP_PARITY, mem=L.FL_MEM_HOST, **verify):
+                                           mode=L.FL_ICP_PARITY, mem=L.FL_MEM_HOST, mesh_of_class=None, **verify):
         """fl_recognize_batch_instances_verified: recognize_batch_instances whose pick among a group's members is the
         verification's, against `tracker`'s mesh (a Tracker of the detector's frame size on the same context; only its mesh is
         used).  verify: the fields of fl_verify_params (tau_mm, min_model_px, min_inlier_ratio, max_behind_ratio), the rest at
-        the library's defaults; class_idx >= 0: only that class's groups are verified.  A list per frame of result dicts as
+        the library's defaults; class_idx >= 0: only that class's groups are verified.  mesh_of_class (then class_idx stays -1;
+        fl_recognize_batch_instances_verified_meshes): one entry per class of the detector, the mesh of `tracker` its groups are
+        verified against or -1 for none.  A list per frame of result dicts as
         recognize_batch_instances returns them, plus verify (a VERIFY_DTYPE record), nms_rank and verified, in group order.
         member_records: also a VERIFY_DTYPE array of shape (n_frames, max_instances, hyp_per_instance), every job slot's record."""
         unknown = set(verify) - set(_VERIFY_DEFAULTS)
@@ -644,9 +646,16 @@ class Detector:
         cnt = (C.c_int32 * n)()
         drop = (C.c_int32 * n)()
         members = np.zeros((n, G, h), VERIFY_DTYPE) if member_records else None
-        self.ctx.check(self.lib.fl_recognize_batch_instances_verified(self.h, None if tracker is None else tracker.handle, n, bp, dp, mem,
-                                                                      C.byref(kk), C.byref(p), C.byref(ip), C.byref(vp), res, cnt, drop,
-                                                                      None if members is None else _ptr(members)))
+        trk_h, mem_p = None if tracker is None else tracker.handle, None if members is None else _ptr(members)
+        if mesh_of_class is None:
+            self.ctx.check(self.lib.fl_recognize_batch_instances_verified(self.h, trk_h, n, bp, dp, mem, C.byref(kk), C.byref(p), C.byref(ip),
+                                                                          C.byref(vp), res, cnt, drop, mem_p))
+        else:
+            moc = np.ascontiguousarray(mesh_of_class, np.int32).ravel()
+            if len(moc) != self.lib.fl_detector_num_classes(self.h):
+                raise ValueError("recognize_batch_instances_verified: mesh_of_class has one entry per class of the detector")
+            self.ctx.check(self.lib.fl_recognize_batch_instances_verified_meshes(self.h, trk_h, n, bp, dp, mem, C.byref(kk), C.byref(p), C.byref(ip),
+                                                                                 C.byref(vp), _ptr(moc), res, cnt, drop, mem_p))
         out = []
         for f in range(n):
             row = []
@@ -862,17 +871,43 @@ def _params_struct(who, struct, defaults, params):
 class Tracker:
     """fl_tracker: follows objects from frame to frame against their CAD mesh (render at the previous pose, crop, detection()
     from that pose).  Owns its device memory: the mesh, max_frames depth frames of w x h, max_tracks renders and ICP workspaces
-    for crops of up to max_crop_px pixels."""
+    for crops of up to max_crop_px pixels.  Tracker(ctx, vertices, triangles, w, ...) holds one mesh; Tracker(ctx,
+    meshes=[(vertices, triangles), ...], w=..., ...) holds several (fl_tracker_create_meshes), which share everything but the
+    mesh itself: track(), verify() and track_verified() then take mesh_of, the mesh of every track or pose."""
 
-    def __init__(self, ctx, vertices, triangles, w, h, max_frames, max_tracks, max_crop_px):
+    def __init__(self, ctx, vertices=None, triangles=None, w=None, h=None, max_frames=None, max_tracks=None, max_crop_px=None, meshes=None):
         self.ctx = ctx
         self.lib = ctx.lib
-        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
-        t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        if (meshes is None) == (vertices is None) or (meshes is None and triangles is None):
+            raise TypeError("Tracker: give vertices and triangles, or meshes=[(vertices, triangles), ...]")
+        if None in (w, h, max_frames, max_tracks, max_crop_px):
+            raise TypeError("Tracker: w, h, max_frames, max_tracks and max_crop_px are required")
         self.w, self.h, self.max_frames, self.max_tracks, self.max_crop_px = w, h, max_frames, max_tracks, max_crop_px
         h_ = C.c_void_p()
-        ctx.check(self.lib.fl_tracker_create(ctx.h, _ptr(v), len(v), _ptr(t), len(t), w, h, max_frames, max_tracks, max_crop_px, C.byref(h_)))
+        if meshes is None:
+            v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+            t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+            ctx.check(self.lib.fl_tracker_create(ctx.h, _ptr(v), len(v), _ptr(t), len(t), w, h, max_frames, max_tracks, max_crop_px, C.byref(h_)))
+        else:
+            keep = [(np.ascontiguousarray(v, np.float32).reshape(-1, 3), np.ascontiguousarray(t, np.int32).reshape(-1, 3)) for v, t in meshes]
+            arr = (L.Mesh * max(1, len(keep)))(*[L.Mesh(v.ctypes.data, t.ctypes.data, len(v), len(t)) for v, t in keep])
+            ctx.check(self.lib.fl_tracker_create_meshes(ctx.h, arr, len(keep), w, h, max_frames, max_tracks, max_crop_px, C.byref(h_)))
         self.handle = h_
+
+    @property
+    def num_meshes(self):
+        """fl_tracker_num_meshes: the number of meshes the tracker holds."""
+        return int(self.lib.fl_tracker_num_meshes(self.handle))
+
+    @staticmethod
+    def _mesh_of(who, mesh_of, n):
+        """The mesh_of argument of a call over n poses: None, or an int32 array of n mesh indices."""
+        if mesh_of is None:
+            return None
+        m = np.ascontiguousarray(mesh_of, np.int32).ravel()
+        if len(m) != n:
+            raise ValueError(f"{who}: one mesh index per pose")
+        return m
 
     def _frames(self, depths, who):
         """(n, pointer array, device?) of a list of frames: (h, w) u16 numpy arrays, or device tensors, all of one kind.  The
@@ -905,8 +940,9 @@ class Tracker:
         k = L.Intrinsics(self.w, self.h, *[float(x) for x in K])
         return (n_frames, dp, L.FL_MEM_DEVICE if device else L.FL_MEM_HOST, len(fof), fof, p), k, np.zeros(max(1, len(fof)), dtype)
 
-    def track(self, depths, frame_of_track, poses13, K, **params):
-        """One step of every track (fl_track_batch).  depths: the frames, (h, w) u16 numpy arrays in mm, or device tensors
+    def track(self, depths, frame_of_track, poses13, K, mesh_of=None, **params):
+        """One step of every track (fl_track_batch_meshes; mesh_of: the mesh of every track on a tracker of several, None:
+        mesh 0).  depths: the frames, (h, w) u16 numpy arrays in mm, or device tensors
         (anything with data_ptr(): all of one kind); frame_of_track: the frame each track looks at; poses13: (n_tracks, 13)
         or (n_tracks, 4, 4) poses to start from; K = (fx, fy, cx, cy) of the scene camera.  params: the fields of
         fl_track_params (margin_px, passes, icp_it_thr, dist_mean_thr, dist_diff_thr, icp_mode, max_dist_mean, min_px_ratio);
@@ -914,12 +950,13 @@ class Tracker:
         (poses13_of) for the next frame."""
         (n_frames, dp, mem, n, fof, p), k, out = self._batch("Tracker.track", "track", depths, frame_of_track, poses13, K, TRACK_DTYPE)
         prm = _params_struct("Tracker.track", L.TrackParams, _TRACK_DEFAULTS, params)
-        self.ctx.check(self.lib.fl_track_batch(self.handle, n_frames, dp, mem, n, _ptr(fof), _ptr(p), C.byref(k),
-                                               None if prm is None else C.byref(prm), _ptr(out)))
+        mo = self._mesh_of("Tracker.track", mesh_of, n)
+        self.ctx.check(self.lib.fl_track_batch_meshes(self.handle, n_frames, dp, mem, n, _ptr(fof), None if mo is None else _ptr(mo), _ptr(p),
+                                                      C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
         return out[:n]
 
-    def verify(self, depths, frame_of_pose, poses, K, group_first=None, **params):
-        """Hypothesis verification (fl_verify_batch): the mesh rendered at every pose with the scene camera K = (fx, fy, cx, cy)
+    def verify(self, depths, frame_of_pose, poses, K, group_first=None, mesh_of=None, **params):
+        """Hypothesis verification (fl_verify_batch_meshes; mesh_of: the mesh of every pose, None: mesh 0): the mesh rendered at every pose with the scene camera K = (fx, fy, cx, cy)
         and laid over the pose's depth frame.  depths, frame_of_pose and poses ((n, 13) or (n, 4, 4): the `pose` fields of
         recognize_instances / track results feed straight in) are as track() takes them.  group_first: None (every pose is its
         own group, best = accepted) or n_groups + 1 non-decreasing indices from 0 to n; one pose per group at most comes back
@@ -932,18 +969,20 @@ class Tracker:
             if len(gf) < 2:
                 raise ValueError("Tracker.verify: group_first has n_groups + 1 entries")
         prm = _params_struct("Tracker.verify", L.VerifyParams, _VERIFY_DEFAULTS, params)
-        self.ctx.check(self.lib.fl_verify_batch(self.handle, n_frames, dp, mem, n, _ptr(fof), _ptr(p), 0 if gf is None else len(gf) - 1,
-                                                None if gf is None else _ptr(gf), C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
+        mo = self._mesh_of("Tracker.verify", mesh_of, n)
+        self.ctx.check(self.lib.fl_verify_batch_meshes(self.handle, n_frames, dp, mem, n, _ptr(fof), None if mo is None else _ptr(mo), _ptr(p),
+                                                       0 if gf is None else len(gf) - 1, None if gf is None else _ptr(gf), C.byref(k),
+                                                       None if prm is None else C.byref(prm), _ptr(out)))
         return out[:n]
 
     def track_verified(self, depths, frame_of_track, poses13, K, group_first=None, keep_input=0, tau_mm=10, min_model_px=1,
-                       min_inlier_ratio=0.0, max_behind_ratio=0.0, **track_params):
+                       min_inlier_ratio=0.0, max_behind_ratio=0.0, mesh_of=None, **track_params):
         """One step of every track whose `tracked` is the verification's (fl_track_batch_verified): track()'s passes, then on
         the device the pose each tracked track came out with rendered at the scene camera and laid over its frame, as verify()
         does it; a track whose pose is not accepted comes back lost.  keep_input = 1: the pose a track came in with is verified
         too and kept where it verifies strictly better.  group_first: None, or verify()'s groups over the tracks (several start
         poses for one object); one track per group at most comes back with best = 1.  tau_mm .. max_behind_ratio: the fields of
-        fl_verify_params; track_params: the fields of fl_track_params.  Returns a VERIFIED_TRACK_DTYPE array, one record per
+        fl_verify_params; mesh_of: the mesh of every track (None: mesh 0); track_params: the fields of fl_track_params.  Returns a VERIFIED_TRACK_DTYPE array, one record per
         track; poses13_of(result["track"]) feeds the next frame."""
         who = "Tracker.track_verified"
         (n_frames, dp, mem, n, fof, p), k, out = self._batch(who, "track", depths, frame_of_track, poses13, K, VERIFIED_TRACK_DTYPE)
@@ -954,9 +993,10 @@ class Tracker:
                 raise ValueError(f"{who}: group_first has n_groups + 1 entries")
         prm = _params_struct(who, L.TrackParams, _TRACK_DEFAULTS, track_params)
         vp = L.TrackVerifyParams(L.VerifyParams(int(tau_mm), int(min_model_px), float(min_inlier_ratio), float(max_behind_ratio)), int(keep_input), 0)
-        self.ctx.check(self.lib.fl_track_batch_verified(self.handle, n_frames, dp, mem, n, _ptr(fof), _ptr(p), 0 if gf is None else len(gf) - 1,
-                                                        None if gf is None else _ptr(gf), C.byref(k), None if prm is None else C.byref(prm),
-                                                        C.byref(vp), _ptr(out)))
+        mo = self._mesh_of(who, mesh_of, n)
+        self.ctx.check(self.lib.fl_track_batch_verified_meshes(self.handle, n_frames, dp, mem, n, _ptr(fof), None if mo is None else _ptr(mo),
+                                                               _ptr(p), 0 if gf is None else len(gf) - 1, None if gf is None else _ptr(gf),
+                                                               C.byref(k), None if prm is None else C.byref(prm), C.byref(vp), _ptr(out)))
         return out[:n]
 
     def track_verified_ms(self):

@@ -10,6 +10,7 @@
 #define FEALESS_CADRECO_H
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #ifndef __COMMON_H__            // the reference's lotus_common.h guard: do not redefine its types
@@ -223,9 +224,17 @@ int CadRecoTrainMesh(CObjRecoCAD *handle, const string &dir, const string &class
 // must be 640 x 480 (the image of the model camera 608 / 608 / 320 / 240 that detection() assumes for the render); K is the
 // frame's camera.  ERROR_INVALID_PARAM: no mesh set, another frame size, an invalid image, more than
 // FEALESS_TRACK_MAX_OBJECTS entries.  An empty vtResult is SUCCESS.
+// CadRecoSetTrackingMeshes: several object types on one table.  One (class id, OBJ path) pair per type, every OBJ read with
+// fealess::ReadObj at `scale`; ONE tracker holds all the meshes (fl_tracker_create_meshes: they share its frame slot, render
+// images and ICP workspaces), and it replaces the tracker of an earlier call of either kind.  CadRecoTrack and CadRecoVerify
+// then take each entry's mesh from its strObjTag -- an entry whose tag has no mesh: ERROR_INVALID_PARAM, nothing tracked -- and
+// CadRecoSetVerifiedPick verifies the groups of every class whose id has a mesh against that mesh; groups of the other classes
+// are returned as the multi-instance mode returns them.  CadRecoSetTrackingMesh keeps its meaning: one mesh, used for every
+// tag.  ERROR_INVALID_PARAM also for an empty list, an id given twice, or meshes beyond the library's limits.
 #define FEALESS_TRACK_MAX_OBJECTS 16
 #define FEALESS_TRACK_MAX_CROP_PX (320 * 240)
 int CadRecoSetTrackingMesh(CObjRecoCAD *handle, const string &obj_path, float scale);
+int CadRecoSetTrackingMeshes(CObjRecoCAD *handle, const vector<std::pair<string, string>> &class_id_and_obj_path, float scale);
 int CadRecoTrack(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult,
                  vector<int> *tracked);
 

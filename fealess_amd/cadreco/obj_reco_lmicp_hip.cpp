@@ -201,10 +201,14 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
       if (m_verified) {
         // opt-in on top of it (CadRecoSetVerifiedPick): each group's member picked by its verification against the tracking mesh,
         // and only the accepted instances returned
+        // With CadRecoSetTrackingMeshes every class whose id has a mesh is verified against it; the groups of the other classes
+        // come back as the multi-instance mode returns them.
         std::vector<fl_verified_instance_result> vres((size_t)n * G);
         const fl_instance_verify_params vp = {m_vparams, -1, 0};
-        if (fl_recognize_batch_instances_verified(m_det, m_tracker, n, bp.data(), dp.data(), FL_MEM_HOST, &k, &m_params, &m_instances, &vp, vres.data(),
-                                                  cnt.data(), dropped.data(), nullptr) != FL_OK) {
+        std::vector<int32_t> mesh_of_class;
+        for (const std::string &id : m_class_ids) mesh_of_class.push_back(MeshOfTag(id));
+        if (fl_recognize_batch_instances_verified_meshes(m_det, m_tracker, n, bp.data(), dp.data(), FL_MEM_HOST, &k, &m_params, &m_instances, &vp,
+                                                         mesh_of_class.data(), vres.data(), cnt.data(), dropped.data(), nullptr) != FL_OK) {
           fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
           return (int)ERROR_INVALID_PARAM;
         }
@@ -214,7 +218,7 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
             const fl_verified_instance_result &v = vres[(size_t)i * G + g];
             const fl_recognition_result &h = v.inst.reco;
             if (h.status != FL_OK && h.status != FL_ERR_ASSERT) return (int)ERROR_INVALID_PARAM;
-            if (!h.found || !v.verify.accepted) continue;
+            if (!h.found || (v.verified && !v.verify.accepted)) continue;
             TObjRecoResult o;
             o.strObjTag = m_class_ids[h.best.class_idx];
             memcpy(o.tWorld2Cam, h.pose, sizeof(o.tWorld2Cam));
@@ -282,10 +286,54 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     }
     if (m_tracker) fl_tracker_destroy(m_tracker);
     m_tracker = trk;
+    m_mesh_ids.clear();
     return SUCCESS;
   }
 
-  // CadRecoTrack: one fl_track_batch over the previous frame's results, library defaults (point-to-plane, one pass); with
+  // CadRecoSetTrackingMeshes: one tracker of all the meshes, mesh i for the entries tagged ids[i]; replaces the tracker
+  int SetTrackingMeshes(const std::vector<std::string> &ids, const std::vector<fealess::Mesh> &meshes)
+  {
+    if (!m_ctx) return (int)ERROR_UNKNOW;
+    if (ids.empty() || ids.size() != meshes.size()) return (int)ERROR_INVALID_PARAM;
+    for (size_t i = 0; i < ids.size(); ++i)
+      if (std::find(ids.begin(), ids.begin() + i, ids[i]) != ids.begin() + i) return (int)ERROR_INVALID_PARAM;   // an id twice
+    std::vector<fl_mesh> ms;
+    for (const fealess::Mesh &m : meshes)
+      ms.push_back(fl_mesh{m.vertices.data(), m.triangles.data(), (int32_t)(m.vertices.size() / 3), (int32_t)(m.triangles.size() / 3)});
+    fl_tracker *trk = nullptr;
+    const int rc = fl_tracker_create_meshes(m_ctx, ms.data(), (int)ms.size(), PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, 1, FEALESS_TRACK_MAX_OBJECTS,
+                                            FEALESS_TRACK_MAX_CROP_PX, &trk);
+    if (rc == FL_ERR_INVALID) return (int)ERROR_INVALID_PARAM;
+    if (rc != FL_OK) {
+      fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
+      return (int)ERROR_UNKNOW;
+    }
+    if (m_tracker) fl_tracker_destroy(m_tracker);
+    m_tracker = trk;
+    m_mesh_ids = ids;
+    return SUCCESS;
+  }
+
+  // the tracker's mesh for an entry tagged `tag`: after CadRecoSetTrackingMesh the one mesh whatever the tag, after
+  // CadRecoSetTrackingMeshes the tag's mesh or -1
+  int MeshOfTag(const std::string &tag) const
+  {
+    if (m_mesh_ids.empty()) return 0;
+    const auto it = std::find(m_mesh_ids.begin(), m_mesh_ids.end(), tag);
+    return it == m_mesh_ids.end() ? -1 : (int)(it - m_mesh_ids.begin());
+  }
+  // one mesh index per entry; false: an entry's tag has no mesh
+  bool MeshesOf(const vector<TObjRecoResult> &vtResult, std::vector<int32_t> &mesh_of) const
+  {
+    mesh_of.clear();
+    for (const TObjRecoResult &r : vtResult) {
+      mesh_of.push_back(MeshOfTag(r.strObjTag));
+      if (mesh_of.back() < 0) return false;
+    }
+    return true;
+  }
+
+  // CadRecoTrack: one fl_track_batch_meshes over the previous frame's results, each with the mesh of its strObjTag, library defaults (point-to-plane, one pass); with
   // CadRecoSetVerifiedTracking one fl_track_batch_verified, whose `tracked` and pose are the verification's
   int Track(const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult, vector<int> *tracked)
   {
@@ -296,7 +344,8 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     const int n = (int)vtResult.size();
     if (n == 0) return SUCCESS;
     std::vector<float> poses((size_t)n * 13, 0.f);
-    std::vector<int32_t> frame_of(n, 0);
+    std::vector<int32_t> frame_of(n, 0), mesh_of;
+    if (!MeshesOf(vtResult, mesh_of)) return (int)ERROR_INVALID_PARAM;         // a tag without a mesh
     for (int i = 0; i < n; ++i) memcpy(poses.data() + (size_t)13 * i, vtResult[i].tWorld2Cam, 12 * sizeof(float));
     const fl_intrinsics k = {PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, K.dFx, K.dFy, K.dCx, K.dCy};
     const uint16_t *frame = tDepth.pData;
@@ -304,11 +353,11 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     int rc;
     if (m_verified_tracking) {
       std::vector<fl_verified_track_result> vres(n);
-      rc = fl_track_batch_verified(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), 0, nullptr, &k, nullptr, &m_tvparams,
-                                   vres.data());
+      rc = fl_track_batch_verified_meshes(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), mesh_of.data(), poses.data(), 0, nullptr, &k,
+                                          nullptr, &m_tvparams, vres.data());
       for (int i = 0; i < n; ++i) res[i] = vres[i].track;
     } else {
-      rc = fl_track_batch(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), &k, nullptr, res.data());
+      rc = fl_track_batch_meshes(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), mesh_of.data(), poses.data(), &k, nullptr, res.data());
     }
     if (rc != FL_OK) {
       fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
@@ -322,7 +371,7 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return SUCCESS;
   }
 
-  // CadRecoVerify: one fl_verify_batch over the entries, every pose its own group, the library's default gates
+  // CadRecoVerify: one fl_verify_batch_meshes over the entries, each with the mesh of its strObjTag, every pose its own group, the library's default gates
   int Verify(const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult, float tau_mm,
              vector<CadRecoVerifyResult> *out)
   {
@@ -333,13 +382,15 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     const int n = (int)vtResult.size();
     if (n == 0) return SUCCESS;
     std::vector<float> poses((size_t)n * 13, 0.f);
-    std::vector<int32_t> frame_of(n, 0);
+    std::vector<int32_t> frame_of(n, 0), mesh_of;
+    if (!MeshesOf(vtResult, mesh_of)) return (int)ERROR_INVALID_PARAM;         // a tag without a mesh
     for (int i = 0; i < n; ++i) memcpy(poses.data() + (size_t)13 * i, vtResult[i].tWorld2Cam, 12 * sizeof(float));
     const fl_intrinsics k = {PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, K.dFx, K.dFy, K.dCx, K.dCy};
     const uint16_t *frame = tDepth.pData;
     const fl_verify_params prm = {(int32_t)tau_mm, 1, 0.f, 0.f};
     std::vector<fl_verify_result> res(n);
-    const int rc = fl_verify_batch(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), poses.data(), 0, nullptr, &k, &prm, res.data());
+    const int rc = fl_verify_batch_meshes(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), mesh_of.data(), poses.data(), 0, nullptr, &k, &prm,
+                                          res.data());
     if (rc != FL_OK) {
       fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
       return rc == FL_ERR_INVALID ? (int)ERROR_INVALID_PARAM : (int)ERROR_UNKNOW;
@@ -391,7 +442,8 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
   std::vector<std::string> m_class_ids;
   std::string m_path;
   int m_w = 0, m_h = 0, m_batch = 1;
-  fl_tracker *m_tracker = nullptr;   // CadRecoSetTrackingMesh
+  fl_tracker *m_tracker = nullptr;   // CadRecoSetTrackingMesh, CadRecoSetTrackingMeshes
+  std::vector<std::string> m_mesh_ids;   // CadRecoSetTrackingMeshes: the class id of every mesh of the tracker; empty: one mesh for every tag
 };
 
 // ---- factory (CadReco/obj_reco_temp.cpp:6-35) -------------------------------------------------
@@ -697,6 +749,24 @@ int CadRecoSetTrackingMesh(CObjRecoCAD *handle, const string &obj_path, float sc
   return h->SetTrackingMesh(mesh);
 }
 
+int CadRecoSetTrackingMeshes(CObjRecoCAD *handle, const vector<std::pair<string, string>> &class_id_and_obj_path, float scale)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h) return (int)ERROR_INVALID_PARAM;
+  std::vector<std::string> ids;
+  std::vector<fealess::Mesh> meshes(class_id_and_obj_path.size());
+  for (size_t i = 0; i < class_id_and_obj_path.size(); ++i) {
+    std::string err;
+    const int rc = fealess::ReadObj(class_id_and_obj_path[i].second, scale, meshes[i], &err);
+    if (rc != SUCCESS) {
+      fprintf(stderr, "[cadreco] %s\n", err.c_str());
+      return rc;
+    }
+    ids.push_back(class_id_and_obj_path[i].first);
+  }
+  return h->SetTrackingMeshes(ids, meshes);
+}
+
 int CadRecoTrack(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, vector<TObjRecoResult> &vtResult,
                  vector<int> *tracked)
 {
@@ -729,6 +799,36 @@ int cadreco_verify(void *h, const unsigned short *depth, int w, int h_, double t
   const int rc = CadRecoVerify((CObjRecoCAD *)h, d, K, res, tau_mm, &v);
   if (rc == SUCCESS && !v.empty()) memcpy(out, v.data(), v.size() * sizeof(CadRecoVerifyResult));
   return rc;
+}
+// cadreco_verify with a class id per pose (tags: n strings): what picks each pose's mesh after cadreco_set_tracking_meshes
+int cadreco_verify_tagged(void *h, const unsigned short *depth, int w, int h_, double ts, double fx, double fy, double cx, double cy, int n,
+                          const float *poses16, const char *const *tags, float tau_mm, void *out)
+{
+  if (n < 0 || (n > 0 && (!poses16 || !tags || !out))) return (int)ERROR_INVALID_PARAM;
+  TImageU16 d = {ts, (unsigned short *)depth, w, h_};
+  TCamIntrinsicParam K;
+  K.nWidth = w; K.nHeight = h_; K.dFx = fx; K.dFy = fy; K.dCx = cx; K.dCy = cy;
+  std::vector<TObjRecoResult> res(n);
+  for (int i = 0; i < n; ++i) {
+    if (!tags[i]) return (int)ERROR_INVALID_PARAM;
+    res[i].strObjTag = tags[i];
+    memcpy(res[i].tWorld2Cam, poses16 + 16 * i, 16 * sizeof(float));
+  }
+  std::vector<CadRecoVerifyResult> v;
+  const int rc = CadRecoVerify((CObjRecoCAD *)h, d, K, res, tau_mm, &v);
+  if (rc == SUCCESS && !v.empty()) memcpy(out, v.data(), v.size() * sizeof(CadRecoVerifyResult));
+  return rc;
+}
+// CadRecoSetTrackingMeshes on n (class id, OBJ path) pairs
+int cadreco_set_tracking_meshes(void *h, int n, const char *const *class_ids, const char *const *obj_paths, float scale)
+{
+  if (n < 1 || !class_ids || !obj_paths) return (int)ERROR_INVALID_PARAM;
+  std::vector<std::pair<std::string, std::string>> v;
+  for (int i = 0; i < n; ++i) {
+    if (!class_ids[i] || !obj_paths[i]) return (int)ERROR_INVALID_PARAM;
+    v.emplace_back(class_ids[i], obj_paths[i]);
+  }
+  return CadRecoSetTrackingMeshes((CObjRecoCAD *)h, v, scale);
 }
 int cadreco_set_verified_pick(void *h, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio)
 {

@@ -535,18 +535,28 @@ int fl_launch_detection_tables(fl_context *ctx, const FlDetectionTables &t, int 
 // fl_render_chunk_views(w, h) views on arrays that are already on the device: clears the chunk's depth keys (8 bytes per
 // pixel and view), rasterises, resolves into the outputs that are not null (views back to back).  light: unit vector.
 struct FlRenderMesh { const float *vtx, *nrm; const uint8_t *col; const int32_t *tri; int n_t; };
+// One mesh of several that share a vertex array and a triangle array (a tracker's, fl_track.hip): its triangles are
+// tri_first .. tri_first + n_t - 1 of the triangle array, their vertex indices already rebased into the shared vertex array.
+struct FlMeshRange { int32_t tri_first, n_t; };
 int fl_render_check_mesh(fl_context *ctx, const char *who, const float *vertices, const float *normals, int n_vertices,
                          const int32_t *triangles, int n_triangles);
 int fl_render_chunk_views(int w, int h);
 int fl_launch_render_chunk(fl_context *ctx, const FlRenderMesh &mesh, const float *d_poses13, int n_views, int w, int h, float fx, float fy,
                            float cx, float cy, const float light[3], float ambient, unsigned long long *keys, uint8_t *bgr, uint16_t *depth,
-                           uint8_t *mask, int32_t *tri);
+                           uint8_t *mask, int32_t *tri, const FlMeshRange *ranges = nullptr, const int32_t *mesh_of = nullptr, int max_n_t = 0);
+// With ranges (device, depth-only renders: nrm, col, bgr and tri null): view v of the chunk renders the triangles of
+// ranges[mesh_of[v]] (mesh_of: device, the chunk's first view at [0]) and not mesh.tri .. mesh.n_t; max_n_t = the largest n_t of
+// the table, which sizes the launch.  A depth key then carries the triangle's index inside its own mesh.
 // verify
 // k_verify_fused (fl_verify.hip): the mesh rendered at a pose into LDS and scored against the pose's frame, one workgroup per
 // pose, on arrays that are already on the device.  Pose t is the 12 floats [R|t] (row-major, mm) at pose + t * pose_stride;
 // its frame is the w * h u16 at frames + frame_stride * (frame_of ? frame_of[t] : t / per_frame).  With job_idx: pose t is
-// live only when job_idx[t] >= 0, res[t].found == 1 and (class_idx < 0 or res[t].best.class_idx == class_idx); a pose that is
-// not live leaves its accumulator as it is.  acc: FL_VERIFY_ACC_BYTES per pose, written whole for a live pose.
+// live only when job_idx[t] >= 0, res[t].found == 1 and m = mesh_of[res[t].best.class_idx] >= 0 (mesh_of is then a map from
+// the detector's classes to meshes, device memory); a pose that is not live leaves its accumulator as it is.  acc:
+// FL_VERIFY_ACC_BYTES per pose, written whole for a live pose.
+// The mesh of a pose: mesh.tri .. mesh.n_t when `ranges` is null (one mesh, the launch as it was before there were several).
+// With ranges (device): the triangles of ranges[m], m as above for a recognition slot, m = mesh_of[t] without job_idx and
+// m = mesh_of[u] with skip (mesh_of null: m = 0).
 // With skip (the tracker's form, which needs frame_of and takes no job_idx): the launch is over n_poses workgroups of which the
 // first `split` are items 0 .. split - 1 at `pose` and the rest are items 0 .. n_poses - split - 1 again at `pose_in`; workgroup
 // t of item u reads frame_of[u], is live when skip[u] == 0 and writes acc[t].  A workgroup that is not live exits at once.
@@ -564,11 +574,12 @@ struct FlVerifyFusedJob {
   int per_frame;
   const int32_t *job_idx;
   const fl_recognition_result *res;
-  int class_idx;
+  const int32_t *mesh_of;                       // per class with job_idx, else per pose / item; see above
   void *acc;
   const int32_t *skip;                          // null: the liveness rule above
   int split;
   const float *pose_in;
+  const FlMeshRange *ranges;                    // null: one mesh
 };
 int fl_launch_verify_fused(fl_context *ctx, const FlVerifyFusedJob &j);
 // the records of n_poses accumulators (k_verify_finish: rect, ratios, accepted; best = accepted), and fl_verify_params' ranges

@@ -544,11 +544,12 @@ __global__ __launch_bounds__(64) void k_pick_instances(const fl_recognition_resu
 
 // The verified pick (fl_recognize_batch_instances_verified, see the header), one thread per (frame, group).  vres: the finished
 // record of every job slot, best = accepted as k_verify_finish leaves it; a verified group's `best` fields are rewritten here.
-// The group's class is its leader's, which every member shares (the grouping rule).
+// The group's class is its leader's, which every member shares (the grouping rule); mesh_of_class maps it to the mesh the
+// group is verified against, negative: not verified.
 __global__ __launch_bounds__(64) void k_pick_verified(const fl_recognition_result *__restrict__ res, const FlRefineJob *__restrict__ jobs,
                                                       const int32_t *__restrict__ job_idx, const int32_t *__restrict__ group_size,
-                                                      const int32_t *__restrict__ info, int n_frames, int G, int h, int class_idx,
-                                                      fl_verify_result *vres, fl_verified_instance_result *__restrict__ out)
+                                                      const int32_t *__restrict__ info, int n_frames, int G, int h,
+                                                      const int32_t *__restrict__ mesh_of_class, fl_verify_result *vres, fl_verified_instance_result *__restrict__ out)
 {
   const int t = blockIdx.x * 64 + threadIdx.x;
   if (t >= n_frames * G) return;
@@ -571,7 +572,7 @@ __global__ __launch_bounds__(64) void k_pick_verified(const fl_recognition_resul
     else if (c.det.n_points > size_th && c.det.icp.dist_mean < res[first + o].det.icp.dist_mean) o = r;
   }
   if (o < 0) o = 0;
-  const int verified = class_idx < 0 || jobs[first].match.class_idx == class_idx;
+  const int verified = mesh_of_class[jobs[first].match.class_idx] >= 0;
   int pick = o, best = -1;
   if (verified) {
     long long bi = 0, bm = 1;
@@ -604,6 +605,8 @@ struct InstVerify {
   const fl_instance_verify_params *vp;
   fl_verified_instance_result *results;
   fl_verify_result *member_verify;                         // may be null
+  bool by_map;                                             // fl_recognize_batch_instances_verified_meshes: mesh_of_class, not vp->class_idx
+  const int32_t *mesh_of_class;                            // host, one entry per class of the detector
 };
 
 static int recognize_batch_instances_once(fl_detector *det, int n_frames, const uint8_t *const *bgr, const uint16_t *const *depth, int mem,
@@ -623,8 +626,16 @@ static int recognize_batch_instances_once(fl_detector *det, int n_frames, const 
     kf[0] = (float)K->fx; kf[1] = (float)K->fy; kf[2] = (float)K->cx; kf[3] = (float)K->cy;
     if (!(std::isfinite(kf[0]) && kf[0] > 0.f && std::isfinite(kf[1]) && kf[1] > 0.f && std::isfinite(kf[2]) && std::isfinite(kf[3])))
       return fl_set_error(ctx, FL_ERR_INVALID, "%s: fx, fy must be finite and > 0, cx, cy finite, as floats too", who);
-    if (v->vp->class_idx < -1 || v->vp->class_idx >= (int)det->classes.size())
+    if (v->by_map) {
+      if (!v->mesh_of_class) return fl_set_error(ctx, FL_ERR_INVALID, "%s_meshes: null mesh_of_class", who);
+      if (v->vp->class_idx != -1)
+        return fl_set_error(ctx, FL_ERR_INVALID, "%s_meshes: class_idx %d must be -1, the map says which classes are verified", who, v->vp->class_idx);
+      for (int c = 0; c < (int)det->classes.size(); ++c)
+        if (v->mesh_of_class[c] < -1 || v->mesh_of_class[c] >= v->mesh->n_meshes)
+          return fl_set_error(ctx, FL_ERR_INVALID, "%s_meshes: mesh_of_class[%d] = %d outside [-1, %d)", who, c, v->mesh_of_class[c], v->mesh->n_meshes);
+    } else if (v->vp->class_idx < -1 || v->vp->class_idx >= (int)det->classes.size()) {
       return fl_set_error(ctx, FL_ERR_INVALID, "%s: class_idx %d outside [-1, %d)", who, v->vp->class_idx, (int)det->classes.size());
+    }
     if (v->mesh->ctx != ctx) return fl_set_error(ctx, FL_ERR_INVALID, "%s: the tracker is on another context", who);
     if (v->mesh->w != det->w0 || v->mesh->h != det->h0 || v->mesh->w != K->width || v->mesh->h != K->height)
       return fl_set_error(ctx, FL_ERR_INVALID, "%s: the tracker's %d x %d is not the detector's %d x %d or not K's %d x %d", who, v->mesh->w,
@@ -651,10 +662,18 @@ static int recognize_batch_instances_once(fl_detector *det, int n_frames, const 
   const size_t o_gof = take(need_gof ? sizeof(int32_t) * (size_t)det->cap * n_frames : 0), o_size = take(sizeof(int32_t) * (size_t)n_frames * G);
   const size_t o_info = take(sizeof(int32_t) * 4 * (size_t)n_frames), o_out = take(out_bytes);
   const size_t o_acc = take(v ? FL_VERIFY_ACC_BYTES * jobs : 0);
+  // the verified variant's map from classes to meshes: behind the records in the pinned block, and from there into the scratch
+  const size_t map_bytes = v ? sizeof(int32_t) * det->classes.size() : 0, h_map = fl_align(copy_bytes, 256), o_map = take(map_bytes);
   void *sv = nullptr, *hv = nullptr;
   FL_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = fl_scratch(ctx, off, &sv)) || (rc = fl_pinned(ctx, copy_bytes, &hv))) return rc;
+  if ((rc = fl_scratch(ctx, off, &sv)) || (rc = fl_pinned(ctx, v ? h_map + map_bytes : copy_bytes, &hv))) return rc;
   uint8_t *s = (uint8_t *)sv;
+  if (v) {                                                 // without a map: class_idx -> mesh 0, every other class -> none; -1: every class -> mesh 0
+    int32_t *hm = (int32_t *)((uint8_t *)hv + h_map);
+    for (int c = 0; c < (int)det->classes.size(); ++c)
+      hm[c] = v->by_map ? v->mesh_of_class[c] : (v->vp->class_idx < 0 || v->vp->class_idx == c ? 0 : -1);
+    FL_HIP(ctx, hipMemcpyAsync(s + o_map, hm, map_bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
   const uint16_t *depth_base = nullptr;
   size_t depth_stride = 0;
   int host_buf = -1;
@@ -687,13 +706,14 @@ static int recognize_batch_instances_once(fl_detector *det, int n_frames, const 
     const fl_tracker *m = v->mesh;
     const FlVerifyFusedJob j = {(int)jobs, m->w, m->h, v->vp->verify.tau_mm, kf[0], kf[1], kf[2], kf[3], {m->d_vtx, nullptr, nullptr, m->d_tri, m->n_t},
                                 d_res->pose, (int)(sizeof(fl_recognition_result) / sizeof(float)), (const uint8_t *)depth_base, depth_stride, nullptr,
-                                G * h, a.job_idx, d_res, v->vp->class_idx, s + o_acc};
+                                G * h, a.job_idx, d_res, (const int32_t *)(s + o_map), s + o_acc, nullptr, 0, nullptr,
+                                m->n_meshes > 1 ? m->d_ranges : nullptr};
     if ((rc = fl_launch_verify_fused(ctx, j))) { (void)input_done(det, host_buf); return rc; }   // the frames' last reader, queued or not
     if ((rc = input_done(det, host_buf))) return rc;
     FL_HIP(ctx, hipEventRecord(det->ev[19], ctx->stream));
     if ((rc = fl_launch_verify_finish(ctx, (int)jobs, m->w, m->h, v->vp->verify, s + o_acc, d_vres))) return rc;
     hipLaunchKernelGGL(k_pick_verified, dim3((n_frames * G + 63) / 64), dim3(64), 0, ctx->stream, d_res, a.jobs, a.job_idx, a.group_size, a.info, n_frames,
-                       G, h, v->vp->class_idx, d_vres, (fl_verified_instance_result *)(s + o_out));
+                       G, h, (const int32_t *)(s + o_map), d_vres, (fl_verified_instance_result *)(s + o_out));
   } else {
     hipLaunchKernelGGL(k_pick_instances, dim3((n_frames * G + 63) / 64), dim3(64), 0, ctx->stream, d_res, a.job_idx, a.group_size, a.info, n_frames, G, h,
                        (fl_instance_result *)(s + o_out));
@@ -745,7 +765,21 @@ extern "C" int fl_recognize_batch_instances_verified(fl_detector *det, fl_tracke
                                                      const fl_instance_verify_params *vp, fl_verified_instance_result *results,
                                                      int32_t *n_instances, int32_t *n_dropped, fl_verify_result *member_verify)
 {
-  const InstVerify v = {mesh, vp, results, member_verify};
+  const InstVerify v = {mesh, vp, results, member_verify, false, nullptr};
+  for (int attempt = 0;; ++attempt) {
+    int rc = recognize_batch_instances_once(det, n_frames, bgr, depth, mem, K, params, ip, nullptr, n_instances, n_dropped, &v);
+    if (!fl_grow_after_overflow(det, n_frames, attempt, &rc)) return rc;
+  }
+}
+
+extern "C" int fl_recognize_batch_instances_verified_meshes(fl_detector *det, fl_tracker *mesh, int n_frames, const uint8_t *const *bgr,
+                                                            const uint16_t *const *depth, int mem, const fl_intrinsics *K,
+                                                            const fl_recognition_params *params, const fl_instance_params *ip,
+                                                            const fl_instance_verify_params *vp, const int32_t *mesh_of_class,
+                                                            fl_verified_instance_result *results, int32_t *n_instances, int32_t *n_dropped,
+                                                            fl_verify_result *member_verify)
+{
+  const InstVerify v = {mesh, vp, results, member_verify, true, mesh_of_class};
   for (int attempt = 0;; ++attempt) {
     int rc = recognize_batch_instances_once(det, n_frames, bgr, depth, mem, K, params, ip, nullptr, n_instances, n_dropped, &v);
     if (!fl_grow_after_overflow(det, n_frames, attempt, &rc)) return rc;
@@ -771,10 +805,19 @@ extern "C" int fl_dev_pick_verified(fl_context *ctx, int n_groups, int h, int cl
     return FL_ERR_INVALID;
   if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_dev_pick_verified: no device");
   const size_t n = (size_t)n_groups * h;
+  // the kernel's map from classes to meshes, as the entry point builds it from class_idx, over the classes the leaders name
+  int n_cls = 1;
+  for (int g = 0; g < n_groups; ++g) {
+    const int c = jobs[(size_t)g * h].match.class_idx;
+    if (c < 0 || c >= (1 << 20)) return fl_set_error(ctx, FL_ERR_INVALID, "fl_dev_pick_verified: group %d has class %d", g, c);
+    n_cls = std::max(n_cls, c + 1);
+  }
+  std::vector<int32_t> map((size_t)n_cls);
+  for (int c = 0; c < n_cls; ++c) map[c] = class_idx < 0 || class_idx == c ? 0 : -1;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off = fl_align(off + bytes, 256); return o; };
   const size_t o_res = take(sizeof(*res) * n), o_jobs = take(sizeof(*jobs) * n), o_idx = take(4 * n), o_size = take(4 * (size_t)n_groups), o_info = take(16);
-  const size_t o_vres = take(sizeof(*vres) * n), o_out = take(sizeof(*out) * (size_t)n_groups + 12);
+  const size_t o_vres = take(sizeof(*vres) * n), o_out = take(sizeof(*out) * (size_t)n_groups + 12), o_map = take(4 * (size_t)n_cls);
   void *sv = nullptr;
   FL_HIP(ctx, hipSetDevice(ctx->device));
   int rc = fl_context_join(ctx);
@@ -788,10 +831,11 @@ extern "C" int fl_dev_pick_verified(fl_context *ctx, int n_groups, int h, int cl
   FL_HIP(ctx, hipMemcpyAsync(s + o_size, group_size, 4 * (size_t)n_groups, hipMemcpyHostToDevice, st));
   FL_HIP(ctx, hipMemcpyAsync(s + o_info, info, 16, hipMemcpyHostToDevice, st));
   FL_HIP(ctx, hipMemcpyAsync(s + o_vres, vres, sizeof(*vres) * n, hipMemcpyHostToDevice, st));
+  FL_HIP(ctx, hipMemcpyAsync(s + o_map, map.data(), 4 * (size_t)n_cls, hipMemcpyHostToDevice, st));
   FL_HIP(ctx, hipStreamSynchronize(st));                   // info is on the stack, and the caller's arrays are pageable
   hipLaunchKernelGGL(k_pick_verified, dim3((n_groups + 63) / 64), dim3(64), 0, st, (const fl_recognition_result *)(s + o_res),
                      (const FlRefineJob *)(s + o_jobs), (const int32_t *)(s + o_idx), (const int32_t *)(s + o_size), (const int32_t *)(s + o_info), 1,
-                     n_groups, h, class_idx, (fl_verify_result *)(s + o_vres), (fl_verified_instance_result *)(s + o_out));
+                     n_groups, h, (const int32_t *)(s + o_map), (fl_verify_result *)(s + o_vres), (fl_verified_instance_result *)(s + o_out));
   FL_HIP(ctx, hipGetLastError());
   FL_HIP(ctx, hipMemcpyAsync(vres, s + o_vres, sizeof(*vres) * n, hipMemcpyDeviceToHost, st));
   FL_HIP(ctx, hipMemcpyAsync(out, s + o_out, sizeof(*out) * (size_t)n_groups, hipMemcpyDeviceToHost, st));

@@ -43,10 +43,19 @@ constexpr unsigned long long KEY_EMPTY = ~0ull;
 
 // The rejection and the bounding box below are restated by tri_box (fl_verify.hip), whose window is the union of these boxes:
 // the two are bound to each other.
-__global__ __launch_bounds__(RB) void k_raster(RenderArgs a, unsigned long long *keys)
+// MULTI (a tracker of several meshes, fl_track.hip): view v walks the triangles of ranges[mesh_of[v]], t counted inside that
+// mesh, so that the key's tie rule stays the mesh's own; the grid is sized by the largest mesh and a wave past its view's mesh
+// exits.  MULTI = false takes neither argument and is the kernel as it was.
+template <bool MULTI>
+__global__ __launch_bounds__(RB) void k_raster(RenderArgs a, unsigned long long *keys, const FlMeshRange *ranges, const int32_t *mesh_of)
 {
   const int t = blockIdx.x * (RB / FL_WAVE) + (int)(threadIdx.x / FL_WAVE);
   const int lane = threadIdx.x % FL_WAVE;
+  if (MULTI) {                                  // uniform per workgroup: blockIdx.y alone decides
+    const FlMeshRange r = ranges[mesh_of[blockIdx.y]];
+    a.tri += 3 * (size_t)r.tri_first;
+    a.n_t = r.n_t;
+  }
   if (t >= a.n_t) return;
   const int v = blockIdx.y;
   const float *pose = a.pose + 13 * v;
@@ -159,7 +168,7 @@ int fl_render_check_mesh(fl_context *ctx, const char *who, const float *vertices
 // One chunk of views on device arrays: clear the keys, k_raster, k_resolve (queued on the context's stream).
 int fl_launch_render_chunk(fl_context *ctx, const FlRenderMesh &mesh, const float *d_poses13, int n_views, int w, int h, float fx, float fy,
                            float cx, float cy, const float light[3], float ambient, unsigned long long *keys, uint8_t *bgr, uint16_t *depth,
-                           uint8_t *mask, int32_t *tri)
+                           uint8_t *mask, int32_t *tri, const FlMeshRange *ranges, const int32_t *mesh_of, int max_n_t)
 {
   RenderArgs a;
   a.vtx = mesh.vtx;
@@ -177,7 +186,11 @@ int fl_launch_render_chunk(fl_context *ctx, const FlRenderMesh &mesh, const floa
   a.ambient = ambient;
   const size_t cpx = (size_t)n_views * w * h;
   FL_HIP(ctx, hipMemsetAsync(keys, 0xFF, cpx * 8, ctx->stream));
-  hipLaunchKernelGGL(k_raster, dim3((mesh.n_t + RB / FL_WAVE - 1) / (RB / FL_WAVE), n_views), dim3(RB), 0, ctx->stream, a, keys);
+  if (ranges)
+    hipLaunchKernelGGL(k_raster<true>, dim3((max_n_t + RB / FL_WAVE - 1) / (RB / FL_WAVE), n_views), dim3(RB), 0, ctx->stream, a, keys, ranges, mesh_of);
+  else
+    hipLaunchKernelGGL(k_raster<false>, dim3((mesh.n_t + RB / FL_WAVE - 1) / (RB / FL_WAVE), n_views), dim3(RB), 0, ctx->stream, a, keys,
+                       (const FlMeshRange *)nullptr, (const int32_t *)nullptr);
   FL_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_resolve, dim3((unsigned)((cpx + 255) / 256)), dim3(256), 0, ctx->stream, a, (const unsigned long long *)keys,
                      (long long)cpx, bgr, depth, mask, tri);

@@ -2,6 +2,10 @@
 // rasteriser of fl_render.hip and the ICP workgroup per job of fl_icp.hip, joined on the device.  No counterpart in the
 // reference, which links a 2-D KCF box tracker it never calls (test/linemod_acq.cpp:108-150).
 //
+// A tracker holds one mesh or several (fl_tracker_create_meshes): the meshes lie back to back in one vertex and one triangle
+// array, a mesh is a range of triangles (FlMeshRange), and a pose names its mesh through d_mesh_of; frame slots, render images,
+// keys and ICP workspaces are shared.  Only the two kernels that read triangles know: k_raster<true> and the k_verify_fused pair.
+//
 // Here: the tracker, the steps every call on one shares (fl_track_internal.h: checks, staging, render, results),
 // fl_track_batch and fl_track_batch_verified.  fl_verify_batch, the other user of those steps, is fl_verify.hip.
 //
@@ -24,6 +28,8 @@
 // The rectangle rule is stated in integers in include/fealess_hip.h and in numpy in tests/track_model.py; the shift is fp64,
 // one IEEE operation per operator (the Makefile's -ffp-contract=off: hipcc would contract a * b + c otherwise).
 #include "fl_track_internal.h"
+#include <stdio.h>
+#include <vector>
 
 namespace {
 
@@ -251,6 +257,27 @@ static int tracker_sizes_ok(fl_context *ctx, int w, int h, int max_frames, int m
   return FL_OK;
 }
 
+// The argument checks of fl_tracker_create_meshes that concern the meshes (shared with fl_dev_tracker_create_host_meshes): each
+// mesh by fl_render_check_mesh's rules, an index inside its own mesh's vertices, then the sums.  name_mesh: the text says which.
+static int tracker_meshes_ok(fl_context *ctx, const char *who, bool name_mesh, const fl_mesh *meshes, int n_meshes)
+{
+  if (!meshes) return fl_set_error(ctx, FL_ERR_INVALID, "%s: null meshes", who);
+  if (n_meshes < 1 || n_meshes > FL_TRACK_MAX_MESHES)
+    return fl_set_error(ctx, FL_ERR_INVALID, "%s: n_meshes %d outside 1..%d", who, n_meshes, FL_TRACK_MAX_MESHES);
+  long long nv = 0, nt = 0;
+  for (int m = 0; m < n_meshes; ++m) {
+    char w[96];
+    if (name_mesh) snprintf(w, sizeof(w), "%s: mesh %d", who, m);
+    else snprintf(w, sizeof(w), "%s", who);
+    if (int rc = fl_render_check_mesh(ctx, w, meshes[m].vertices, nullptr, meshes[m].n_vertices, meshes[m].triangles, meshes[m].n_triangles)) return rc;
+    nv += meshes[m].n_vertices;
+    nt += meshes[m].n_triangles;
+  }
+  if (nv > FL_RENDER_MAX_PRIMS || nt > FL_RENDER_MAX_PRIMS)
+    return fl_set_error(ctx, FL_ERR_INVALID, "%s: %lld vertices or %lld triangles over the %d meshes pass %d", who, nv, nt, n_meshes, FL_RENDER_MAX_PRIMS);
+  return FL_OK;
+}
+
 // a tracker that knows its sizes and owns nothing yet (what fl_tracker_create and fl_dev_tracker_create_host both start from)
 static fl_tracker *tracker_new(fl_context *ctx, bool owns_ctx, int w, int h, int max_frames, int max_tracks, int max_crop_px)
 {
@@ -262,20 +289,21 @@ static fl_tracker *tracker_new(fl_context *ctx, bool owns_ctx, int w, int h, int
   return trk;
 }
 
-// The tracker's device memory, every part named once: the mesh of n_vertices and n_t triangles, the frame slots, per track a
+// The tracker's device memory, every part named once: the meshes' n_vertices vertices and n_triangles triangles and their range
+// table, the frame slots, per track a
 // render image, an ICP workspace and the small records (two verification accumulators: fl_track_batch_verified scores a track's
 // input pose too, and writes its records straight into d_vout), per render chunk the depth keys.  base null: the sizing pass.
-static size_t carve_device(fl_tracker *trk, uint8_t *base, int n_vertices)
+static size_t carve_device(fl_tracker *trk, uint8_t *base, size_t n_vertices, size_t n_triangles)
 {
   const size_t px = (size_t)trk->w * trk->h, T = (size_t)trk->max_tracks;
   size_t off = 0;
   auto take = [&](auto *&p, size_t bytes) { fl_carve(p, base, off, bytes); };
-  take(trk->d_vtx, (size_t)n_vertices * 3 * 4); take(trk->d_tri, (size_t)trk->n_t * 3 * 4);
+  take(trk->d_vtx, n_vertices * 3 * 4); take(trk->d_tri, n_triangles * 3 * 4); take(trk->d_ranges, (size_t)trk->n_meshes * sizeof(FlMeshRange));
   take(trk->d_frames, trk->frame_stride * trk->max_frames);
   take(trk->d_render, T * px * 2); take(trk->d_keys, (size_t)trk->chunk * px * 8);
   take(trk->d_icp, trk->ws_one * T);
   take(trk->d_poses, T * 13 * 4); take(trk->d_poses_in, T * 13 * 4);
-  take(trk->d_frame_of, T * 4); take(trk->d_lost, T * 4); take(trk->d_class_first, 4);
+  take(trk->d_frame_of, T * 4); take(trk->d_mesh_of, T * 4); take(trk->d_lost, T * 4); take(trk->d_class_first, 4);
   take(trk->d_pyr, T * sizeof(FlPyrInfo)); take(trk->d_depth_ptrs, T * sizeof(void *)); take(trk->d_jobs, T * sizeof(FlRefineJob));
   take(trk->d_res, T * sizeof(fl_recognition_result)); take(trk->d_out, T * sizeof(fl_track_result));
   take(trk->d_vacc, 2 * T * sizeof(FlVerifyAcc)); take(trk->d_vres, T * sizeof(fl_verify_result)); take(trk->d_group_first, (T + 1) * 4);
@@ -298,39 +326,70 @@ extern "C" void fl_tracker_destroy(fl_tracker *trk)
   delete trk;
 }
 
-extern "C" int fl_tracker_create(fl_context *ctx, const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
-                                 int w, int h, int max_frames, int max_tracks, int max_crop_px, fl_tracker **out)
+// fl_tracker_create_meshes, `who` in the texts; name_mesh: a refusal says which mesh (fl_tracker_create's texts stay as they were)
+static int tracker_create(fl_context *ctx, const char *who, bool name_mesh, const fl_mesh *meshes, int n_meshes, int w, int h, int max_frames,
+                          int max_tracks, int max_crop_px, fl_tracker **out)
 {
   if (!ctx || !out) return FL_ERR_INVALID;
-  int rc = fl_render_check_mesh(ctx, "fl_tracker_create", vertices, nullptr, n_vertices, triangles, n_triangles);
+  int rc = tracker_meshes_ok(ctx, who, name_mesh, meshes, n_meshes);
   if (rc || (rc = tracker_sizes_ok(ctx, w, h, max_frames, max_tracks, max_crop_px))) return rc;
-  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_tracker_create: the context has no device");
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "%s: the context has no device", who);
   FL_HIP(ctx, hipSetDevice(ctx->device));
+  // the meshes back to back, every triangle's indices moved on by its mesh's first vertex, and the range of each
+  std::vector<float> vtx;
+  std::vector<int32_t> tri;
+  std::vector<FlMeshRange> ranges((size_t)n_meshes);
+  int max_n_t = 0;
+  for (int m = 0; m < n_meshes; ++m) {
+    const int32_t v_first = (int32_t)(vtx.size() / 3);
+    ranges[m] = FlMeshRange{(int32_t)(tri.size() / 3), meshes[m].n_triangles};
+    max_n_t = std::max(max_n_t, meshes[m].n_triangles);
+    vtx.insert(vtx.end(), meshes[m].vertices, meshes[m].vertices + (size_t)meshes[m].n_vertices * 3);
+    for (size_t i = 0; i < (size_t)meshes[m].n_triangles * 3; ++i) tri.push_back(meshes[m].triangles[i] + v_first);
+  }
   fl_tracker *trk = tracker_new(ctx, false, w, h, max_frames, max_tracks, max_crop_px);
-  trk->n_t = n_triangles;
+  trk->n_meshes = n_meshes;
+  trk->n_t = meshes[0].n_triangles;
+  trk->max_n_t = max_n_t;
   trk->chunk = std::min(max_tracks, fl_render_chunk_views(w, h));
   trk->frame_stride = fl_align((size_t)w * h * 2, 256);
   trk->ws_one = fl_align(fl_icp_ws_bytes(max_crop_px), 256);
   auto fail = [&](hipError_t e, const char *what) {
-    fl_set_error(ctx, FL_ERR_HIP, "fl_tracker_create: %s -> %s", what, hipGetErrorString(e));
+    fl_set_error(ctx, FL_ERR_HIP, "%s: %s -> %s", who, what, hipGetErrorString(e));
     fl_tracker_destroy(trk);
     return FL_ERR_HIP;
   };
   hipError_t e;
-  if ((e = hipMalloc((void **)&trk->d_mem, carve_device(trk, nullptr, n_vertices))) != hipSuccess) { trk->d_mem = nullptr; return fail(e, "hipMalloc"); }
+  if ((e = hipMalloc((void **)&trk->d_mem, carve_device(trk, nullptr, vtx.size() / 3, tri.size() / 3))) != hipSuccess) { trk->d_mem = nullptr; return fail(e, "hipMalloc"); }
   if ((e = hipHostMalloc((void **)&trk->h_stage, fl_track_stage(trk->stage, nullptr, max_tracks), hipHostMallocDefault)) != hipSuccess) { trk->h_stage = nullptr; return fail(e, "hipHostMalloc"); }
   for (hipEvent_t &v : trk->ev)
     if ((e = hipEventCreate(&v)) != hipSuccess) { v = nullptr; return fail(e, "hipEventCreate"); }
-  carve_device(trk, trk->d_mem, n_vertices);
+  carve_device(trk, trk->d_mem, vtx.size() / 3, tri.size() / 3);
   fl_track_stage(trk->stage, trk->h_stage, max_tracks);
-  // the mesh, once; the one class every slot's "template" belongs to starts at g = 0
-  if ((e = hipMemcpyAsync((void *)trk->d_vtx, vertices, (size_t)n_vertices * 3 * 4, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync((void *)trk->d_tri, triangles, (size_t)n_triangles * 3 * 4, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+  // the meshes, once; the one class every slot's "template" belongs to starts at g = 0
+  if ((e = hipMemcpyAsync((void *)trk->d_vtx, vtx.data(), vtx.size() * 4, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync((void *)trk->d_tri, tri.data(), tri.size() * 4, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync((void *)trk->d_ranges, ranges.data(), ranges.size() * sizeof(FlMeshRange), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
       (e = hipMemsetAsync(trk->d_class_first, 0, 4, ctx->stream)) != hipSuccess || (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
     return fail(e, "mesh upload");
   *out = trk;
   return FL_OK;
 }
+
+extern "C" int fl_tracker_create_meshes(fl_context *ctx, const fl_mesh *meshes, int n_meshes, int w, int h, int max_frames, int max_tracks,
+                                        int max_crop_px, fl_tracker **out)
+{
+  return tracker_create(ctx, "fl_tracker_create_meshes", true, meshes, n_meshes, w, h, max_frames, max_tracks, max_crop_px, out);
+}
+
+extern "C" int fl_tracker_create(fl_context *ctx, const float *vertices, int n_vertices, const int32_t *triangles, int n_triangles,
+                                 int w, int h, int max_frames, int max_tracks, int max_crop_px, fl_tracker **out)
+{
+  const fl_mesh mesh = {vertices, triangles, n_vertices, n_triangles};
+  return tracker_create(ctx, "fl_tracker_create", false, &mesh, 1, w, h, max_frames, max_tracks, max_crop_px, out);
+}
+
+extern "C" int fl_tracker_num_meshes(const fl_tracker *trk) { return trk ? trk->n_meshes : FL_ERR_INVALID; }
 
 // Development / test aid, exported but not part of the ABI: a tracker without a device (its own context, device = -1), for the
 // argument checks of fl_track_batch and fl_verify_batch, which come before their first HIP call.  fl_tracker_destroy releases both.
@@ -344,9 +403,27 @@ extern "C" int fl_dev_tracker_create_host(int w, int h, int max_frames, int max_
   return FL_OK;
 }
 
+// The same with fl_tracker_create_meshes' mesh checks in front and the number of meshes kept: for the refusals of the *_meshes
+// entry points.  A refusal's text dies with the context it was written to; fl_tracker_create_meshes on a context without a
+// device gives the same refusals with their text.
+extern "C" int fl_dev_tracker_create_host_meshes(const fl_mesh *meshes, int n_meshes, int w, int h, int max_frames, int max_tracks, int max_crop_px,
+                                                 fl_tracker **out)
+{
+  if (!out) return FL_ERR_INVALID;
+  fl_context *ctx = new fl_context();
+  ctx->device = -1;
+  if (tracker_meshes_ok(ctx, "fl_dev_tracker_create_host_meshes", true, meshes, n_meshes) ||
+      tracker_sizes_ok(ctx, w, h, max_frames, max_tracks, max_crop_px)) { delete ctx; return FL_ERR_INVALID; }
+  fl_tracker *trk = tracker_new(ctx, true, w, h, max_frames, max_tracks, max_crop_px);
+  trk->n_meshes = n_meshes;
+  trk->n_t = meshes[0].n_triangles;
+  *out = trk;
+  return FL_OK;
+}
+
 // ---- the steps of a call (fl_track_internal.h) ---------------------------------------------------------------------------------
 int fl_tracker_check_call(fl_tracker *trk, const char *who, int n_frames, const uint16_t *const *depth, int mem, int n, const int32_t *frame_of,
-                          const float *poses13, const fl_intrinsics *K, const void *results)
+                          const int32_t *mesh_of, const float *poses13, const fl_intrinsics *K, const void *results)
 {
   if (!trk) return FL_ERR_INVALID;
   fl_context *ctx = trk->ctx;
@@ -359,6 +436,9 @@ int fl_tracker_check_call(fl_tracker *trk, const char *who, int n_frames, const 
   for (int t = 0; t < n; ++t)
     if (frame_of[t] < 0 || frame_of[t] >= n_frames)
       return fl_set_error(ctx, FL_ERR_INVALID, "%s: frame index %d of pose %d outside [0, %d)", who, frame_of[t], t, n_frames);
+  for (int t = 0; mesh_of && t < n; ++t)
+    if (mesh_of[t] < 0 || mesh_of[t] >= trk->n_meshes)
+      return fl_set_error(ctx, FL_ERR_INVALID, "%s: mesh index %d of pose %d outside [0, %d)", who, mesh_of[t], t, trk->n_meshes);
   for (int t = 0; t < n; ++t)
     if (!fl_finite_all(poses13 + (size_t)13 * t, 12)) return fl_set_error(ctx, FL_ERR_INVALID, "%s: non-finite pose %d", who, t);
   if (K->width != trk->w || K->height != trk->h)
@@ -369,7 +449,7 @@ int fl_tracker_check_call(fl_tracker *trk, const char *who, int n_frames, const 
 }
 
 int fl_tracker_stage(fl_tracker *trk, hipEvent_t ev_start, int n_frames, const uint16_t *const *depth, int mem, int n, const int32_t *frame_of,
-                     const float *poses13, float *poses_keep)
+                     const int32_t *mesh_of, const float *poses13, float *poses_keep)
 {
   fl_context *ctx = trk->ctx;
   FL_HIP(ctx, hipSetDevice(ctx->device));
@@ -385,6 +465,14 @@ int fl_tracker_stage(fl_tracker *trk, hipEvent_t ev_start, int n_frames, const u
   FL_HIP(ctx, hipMemcpyAsync(poses_keep ? poses_keep : trk->d_poses, trk->stage.poses, T * 13 * 4, hipMemcpyHostToDevice, st));
   if (poses_keep) FL_HIP(ctx, hipMemcpyAsync(trk->d_poses, poses_keep, T * 13 * 4, hipMemcpyDeviceToDevice, st));
   FL_HIP(ctx, hipMemcpyAsync(trk->d_frame_of, trk->stage.frame_of, T * 4, hipMemcpyHostToDevice, st));
+  // the meshes only where there is a choice: a tracker of one mesh, or a call that names none, runs the one-mesh kernels on mesh 0
+  const bool multi = mesh_of && trk->n_meshes > 1;
+  trk->call_ranges = multi ? trk->d_ranges : nullptr;
+  trk->call_mesh_of = multi ? trk->d_mesh_of : nullptr;
+  if (multi) {
+    memcpy(trk->stage.mesh_of, mesh_of, T * 4);
+    FL_HIP(ctx, hipMemcpyAsync(trk->d_mesh_of, trk->stage.mesh_of, T * 4, hipMemcpyHostToDevice, st));
+  }
   return FL_OK;
 }
 
@@ -395,7 +483,8 @@ int fl_tracker_render(fl_tracker *trk, int n, float fx, float fy, float cx, floa
   const size_t px = (size_t)trk->w * trk->h;
   for (int v0 = 0; v0 < n; v0 += trk->chunk)
     if (int rc = fl_launch_render_chunk(trk->ctx, mesh, trk->d_poses + (size_t)13 * v0, std::min(trk->chunk, n - v0), trk->w, trk->h, fx, fy, cx, cy,
-                                        headlight, FL_RENDER_AMBIENT, trk->d_keys, nullptr, trk->d_render + (size_t)v0 * px, nullptr, nullptr))
+                                        headlight, FL_RENDER_AMBIENT, trk->d_keys, nullptr, trk->d_render + (size_t)v0 * px, nullptr, nullptr,
+                                        trk->call_ranges, trk->call_mesh_of ? trk->call_mesh_of + v0 : nullptr, trk->max_n_t))
       return rc;
   return FL_OK;
 }
@@ -440,12 +529,12 @@ static int track_params(fl_context *ctx, const fl_track_params *params, fl_track
 // Steps 1 to 5 of a tracking call, queued: the inputs, then P.passes passes.  Afterwards d_out holds the records, d_lost who is
 // not tracked and d_poses the pose of every track that is.
 static int track_passes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks, const int32_t *frame_of_track,
-                        const float *poses13, const fl_intrinsics *K, const fl_track_params &P)
+                        const int32_t *mesh_of_track, const float *poses13, const fl_intrinsics *K, const fl_track_params &P)
 {
   fl_context *ctx = trk->ctx;
   int rc;
   // 1. the inputs; the poses stay in d_poses_in too (a lost track reports the pose it came in with)
-  if ((rc = fl_tracker_stage(trk, trk->ev[0], n_frames, depth, mem, n_tracks, frame_of_track, poses13, trk->d_poses_in))) return rc;
+  if ((rc = fl_tracker_stage(trk, trk->ev[0], n_frames, depth, mem, n_tracks, frame_of_track, mesh_of_track, poses13, trk->d_poses_in))) return rc;
   const size_t T = (size_t)n_tracks;
   hipStream_t st = ctx->stream;
   FL_HIP(ctx, hipMemsetAsync(trk->d_lost, 0, T * 4, st));
@@ -481,22 +570,29 @@ static int track_passes(fl_tracker *trk, int n_frames, const uint16_t *const *de
   return FL_OK;
 }
 
-extern "C" int fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
-                              const int32_t *frame_of_track, const float *poses13, const fl_intrinsics *K, const fl_track_params *params,
-                              fl_track_result *results)
+extern "C" int fl_track_batch_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
+                                     const int32_t *frame_of_track, const int32_t *mesh_of_track, const float *poses13, const fl_intrinsics *K,
+                                     const fl_track_params *params, fl_track_result *results)
 {
-  int rc = fl_tracker_check_call(trk, "fl_track_batch", n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, results);
+  int rc = fl_tracker_check_call(trk, "fl_track_batch", n_frames, depth, mem, n_tracks, frame_of_track, mesh_of_track, poses13, K, results);
   if (rc) return rc;
   fl_context *ctx = trk->ctx;
   fl_track_params P;
   if ((rc = track_params(ctx, params, P))) return rc;
   if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_track_batch: the tracker has no device");
-  if ((rc = track_passes(trk, n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, P))) return rc;
+  if ((rc = track_passes(trk, n_frames, depth, mem, n_tracks, frame_of_track, mesh_of_track, poses13, K, P))) return rc;
   // 6. one copy, one wait
   if ((rc = fl_tracker_results(trk, trk->d_out, (size_t)n_tracks * sizeof(fl_track_result), results))) return rc;
   trk->last_passes = P.passes;
   trk->track_verified = false;
   return FL_OK;
+}
+
+extern "C" int fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
+                              const int32_t *frame_of_track, const float *poses13, const fl_intrinsics *K, const fl_track_params *params,
+                              fl_track_result *results)
+{
+  return fl_track_batch_meshes(trk, n_frames, depth, mem, n_tracks, frame_of_track, nullptr, poses13, K, params, results);
 }
 
 // device time of the stages the last fl_track_batch_verified ran after its passes: {fused render and score, finish and pick} in
@@ -512,12 +608,12 @@ extern "C" int fl_dev_tracker_track_verified_ms(fl_tracker *trk, float out[2])
 
 static const fl_track_verify_params k_track_verify_defaults = {{10, 1, 0.f, 0.f}, 0, 0};
 
-extern "C" int fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
-                                       const int32_t *frame_of_track, const float *poses13, int n_groups, const int32_t *group_first,
-                                       const fl_intrinsics *K, const fl_track_params *params, const fl_track_verify_params *vparams,
-                                       fl_verified_track_result *results)
+extern "C" int fl_track_batch_verified_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
+                                              const int32_t *frame_of_track, const int32_t *mesh_of_track, const float *poses13, int n_groups,
+                                              const int32_t *group_first, const fl_intrinsics *K, const fl_track_params *params,
+                                              const fl_track_verify_params *vparams, fl_verified_track_result *results)
 {
-  int rc = fl_tracker_check_call(trk, "fl_track_batch_verified", n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, results);
+  int rc = fl_tracker_check_call(trk, "fl_track_batch_verified", n_frames, depth, mem, n_tracks, frame_of_track, mesh_of_track, poses13, K, results);
   if (rc || (rc = fl_verify_check_call(trk, "fl_track_batch_verified", K, n_tracks, n_groups, group_first))) return rc;
   fl_context *ctx = trk->ctx;
   fl_track_params P;
@@ -527,7 +623,7 @@ extern "C" int fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint
   if (V.keep_input != 0 && V.keep_input != 1) return fl_set_error(ctx, FL_ERR_INVALID, "fl_track_verify_params: keep_input is 0 or 1");
   if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_track_batch_verified: the tracker has no device");
 
-  if ((rc = track_passes(trk, n_frames, depth, mem, n_tracks, frame_of_track, poses13, K, P))) return rc;
+  if ((rc = track_passes(trk, n_frames, depth, mem, n_tracks, frame_of_track, mesh_of_track, poses13, K, P))) return rc;
   // 6. the groups, and clear accumulators: a lost track's workgroups leave theirs alone
   hipStream_t st = ctx->stream;
   hipEvent_t *ev = trk->ev + FL_TRACK_EVENTS + FL_VERIFY_EVENTS;
@@ -542,7 +638,7 @@ extern "C" int fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint
   // launch, always the fused kernel (the render images hold the passes' model-camera renders x 10)
   const FlVerifyFusedJob j = {n_wg, trk->w, trk->h, V.verify.tau_mm, (float)K->fx, (float)K->fy, (float)K->cx, (float)K->cy,
                               {trk->d_vtx, nullptr, nullptr, trk->d_tri, trk->n_t}, trk->d_poses, 13, trk->d_frames, trk->frame_stride, trk->d_frame_of, 1,
-                              nullptr, nullptr, -1, trk->d_vacc, trk->d_lost, n_tracks, trk->d_poses_in};
+                              nullptr, nullptr, trk->call_mesh_of, trk->d_vacc, trk->d_lost, n_tracks, trk->d_poses_in, trk->call_ranges};
   if ((rc = fl_launch_verify_fused(ctx, j))) return rc;
   FL_HIP(ctx, hipEventRecord(ev[1], st));
   // 8. the records and the decision per track, then the best of every group
@@ -561,4 +657,13 @@ extern "C" int fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint
   trk->last_passes = P.passes;
   trk->track_verified = true;
   return FL_OK;
+}
+
+extern "C" int fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_tracks,
+                                       const int32_t *frame_of_track, const float *poses13, int n_groups, const int32_t *group_first,
+                                       const fl_intrinsics *K, const fl_track_params *params, const fl_track_verify_params *vparams,
+                                       fl_verified_track_result *results)
+{
+  return fl_track_batch_verified_meshes(trk, n_frames, depth, mem, n_tracks, frame_of_track, nullptr, poses13, n_groups, group_first, K, params,
+                                        vparams, results);
 }

@@ -19,15 +19,16 @@ inline void fl_carve(T *&p, uint8_t *base, size_t &off, size_t bytes)
 }
 
 // The pinned block a call's inputs leave through and its records come back through, and the one statement of its layout:
-// max_tracks poses of 13 floats | frame indices | records (of fl_track_batch, fl_verify_batch or fl_track_batch_verified) |
-// max_tracks + 1 group starts
-struct FlTrackStage { float *poses; int32_t *frame_of; uint8_t *results; int32_t *group_first; };
+// max_tracks poses of 13 floats | frame indices | mesh indices | records (of fl_track_batch, fl_verify_batch or
+// fl_track_batch_verified) | max_tracks + 1 group starts
+struct FlTrackStage { float *poses; int32_t *frame_of, *mesh_of; uint8_t *results; int32_t *group_first; };
 inline size_t fl_track_stage(FlTrackStage &s, uint8_t *base, int max_tracks)   // returns the bytes; base null: nothing else
 {
   const size_t T = (size_t)max_tracks;
   size_t off = 0;
   fl_carve(s.poses, base, off, T * 13 * 4);
   fl_carve(s.frame_of, base, off, T * 4);
+  fl_carve(s.mesh_of, base, off, T * 4);
   fl_carve(s.results, base, off, T * std::max({sizeof(fl_track_result), sizeof(fl_verify_result), sizeof(fl_verified_track_result)}));
   fl_carve(s.group_first, base, off, (T + 1) * 4);
   return off;
@@ -36,11 +37,16 @@ inline size_t fl_track_stage(FlTrackStage &s, uint8_t *base, int max_tracks)   /
 struct fl_tracker {
   fl_context *ctx = nullptr;
   bool owns_ctx = false;                        // fl_dev_tracker_create_host: a context without a device, released with the tracker
-  int w = 0, h = 0, max_frames = 0, max_tracks = 0, max_crop_px = 0, n_t = 0;
+  int w = 0, h = 0, max_frames = 0, max_tracks = 0, max_crop_px = 0;
+  int n_meshes = 1, n_t = 0, max_n_t = 0;       // n_t: of mesh 0, which starts both arrays; max_n_t: of the largest mesh
   int chunk = 0;                                // views per render launch
   uint8_t *d_mem = nullptr;                     // the one device allocation (carve_device, fl_track.hip)
   const float *d_vtx = nullptr;
-  const int32_t *d_tri = nullptr;
+  const int32_t *d_tri = nullptr;               // every mesh's vertices and triangles back to back, indices rebased
+  FlMeshRange *d_ranges = nullptr;              // n_meshes entries
+  int32_t *d_mesh_of = nullptr;                 // max_tracks entries: the mesh of every pose of a call that names meshes
+  const FlMeshRange *call_ranges = nullptr;     // of the call being queued (fl_tracker_stage): d_ranges and d_mesh_of when it
+  const int32_t *call_mesh_of = nullptr;        // named meshes on a tracker that has several, else null: mesh 0 for every pose
   uint8_t *d_frames = nullptr;
   size_t frame_stride = 0;
   uint16_t *d_render = nullptr;
@@ -68,21 +74,22 @@ struct fl_tracker {
 
 // The steps of a call, in the order an entry point takes them.
 // 1. The checks both entry points make, `who` in the text: null pointers (`results` is only tested for null), mem, n_frames and n
-// against the tracker's limits, a null frame, frame_of outside [0, n_frames), a non-finite pose (floats 0..11), K's size against
+// against the tracker's limits, a null frame, frame_of outside [0, n_frames), mesh_of (null: every pose is mesh 0) outside
+// [0, n_meshes), a non-finite pose (floats 0..11), K's size against
 // the tracker's, fx, fy finite and > 0 and cx, cy finite AS DOUBLES.  fl_verify_batch then asks the same of them as floats, which
 // is what it hands the rasteriser; fl_track_batch renders at the model camera and reads K in fp64: that one difference is meant.
 // FL_ERR_INVALID or FL_OK, no HIP call.  The entry point's own checks follow, and the device check (FL_ERR_NO_DEVICE) after all.
 int fl_tracker_check_call(fl_tracker *trk, const char *who, int n_frames, const uint16_t *const *depth, int mem, int n, const int32_t *frame_of,
-                          const float *poses13, const fl_intrinsics *K, const void *results);
+                          const int32_t *mesh_of, const float *poses13, const fl_intrinsics *K, const void *results);
 // 1b. What fl_verify_batch and fl_track_batch_verified ask on top of that: K as floats, which is what the rasteriser gets (fx, fy
 // finite and > 0, cx, cy finite), and with group_first its rules against n poses.  FL_ERR_INVALID or FL_OK, no HIP call.
 int fl_verify_check_call(fl_tracker *trk, const char *who, const fl_intrinsics *K, int n, int n_groups, const int32_t *group_first);
 // 2. hipSetDevice, the context's streams joined, ev_start, the frames into their slots, then poses13 and frame_of through the
-// pinned block into d_poses and d_frame_of.  poses_keep (null: none): a second device array the poses pass through on their way
-// to d_poses and stay in.
+// pinned block into d_poses and d_frame_of, and on a tracker of several meshes mesh_of (unless null) into d_mesh_of the same way.
+// poses_keep (null: none): a second device array the poses pass through on their way to d_poses and stay in.
 int fl_tracker_stage(fl_tracker *trk, hipEvent_t ev_start, int n_frames, const uint16_t *const *depth, int mem, int n, const int32_t *frame_of,
-                     const float *poses13, float *poses_keep);
-// 3. the mesh at the first n poses of d_poses, depth only, into d_render, a chunk of views per launch
+                     const int32_t *mesh_of, const float *poses13, float *poses_keep);
+// 3. every pose's mesh at the first n poses of d_poses, depth only, into d_render, a chunk of views per launch
 int fl_tracker_render(fl_tracker *trk, int n, float fx, float fy, float cx, float cy);
 // 4. bytes of records from d_records to the caller through the pinned block: one copy, one wait for the stream
 int fl_tracker_results(fl_tracker *trk, const void *d_records, size_t bytes, void *results);

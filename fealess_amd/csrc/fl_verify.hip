@@ -226,9 +226,9 @@ __device__ __forceinline__ void raster_box(const RenderArgs &r, const TriSetup &
   }
 }
 
-// One pose by one workgroup: the mesh at `pose` against the frame `scn`, the counts into accumulator t.  The whole of both
-// kernels below but for which pose, which frame and whether at all.
-__device__ __forceinline__ void verify_fused_pose(const FusedArgs &a, int t, const float *pose, const uint16_t *scn)
+// One pose by one workgroup: the mesh tri .. n_t (of the job's vertex array) at `pose` against the frame `scn`, the counts into
+// accumulator t.  The whole of both kernels below but for which pose, which frame, which mesh and whether at all.
+__device__ __forceinline__ void verify_fused_pose(const FusedArgs &a, int t, const float *pose, const uint16_t *scn, const int32_t *tri, int n_t)
 {
   extern __shared__ unsigned zbuf[];            // a band's z-buffer, a.budget words
   __shared__ int red[9][VF_WAVES];
@@ -238,8 +238,8 @@ __device__ __forceinline__ void verify_fused_pose(const FusedArgs &a, int t, con
   const FlVerifyFusedJob &j = a.j;
   const int tid = threadIdx.x, lane = tid & (FL_WAVE - 1), wave = tid / FL_WAVE;
   RenderArgs r;
-  r.vtx = j.mesh.vtx; r.nrm = nullptr; r.col = nullptr; r.tri = j.mesh.tri; r.pose = j.pose;
-  r.n_t = j.mesh.n_t; r.w = j.w; r.h = j.h;
+  r.vtx = j.mesh.vtx; r.nrm = nullptr; r.col = nullptr; r.tri = tri; r.pose = j.pose;
+  r.n_t = n_t; r.w = j.w; r.h = j.h;
   r.fx = j.fx; r.fy = j.fy; r.cx = j.cx; r.cy = j.cy; r.ifx = a.ifx; r.ify = a.ify;
   r.lx = 0.f; r.ly = 0.f; r.lz = 0.f; r.ambient = 0.f;
 
@@ -396,9 +396,23 @@ __global__ __launch_bounds__(VF) void k_verify_fused(FusedArgs a)
     const int n_frames = j.n_poses / j.per_frame, slot = t / n_frames;
     t = (t - slot * n_frames) * j.per_frame + slot;
   }
-  if (j.job_idx && !(j.job_idx[t] >= 0 && j.res[t].found == 1 && (j.class_idx < 0 || j.res[t].best.class_idx == j.class_idx))) return;
+  int m = 0;                                    // the pose's mesh: wave-uniform, as t is
+  if (j.job_idx) {
+    if (!(j.job_idx[t] >= 0 && j.res[t].found == 1)) return;
+    m = j.mesh_of[j.res[t].best.class_idx];     // the map from classes to meshes; found = 1: the class is on the detector
+    if (m < 0) return;
+  } else if (j.mesh_of) {
+    m = j.mesh_of[t];
+  }
+  const int32_t *tri = j.mesh.tri;
+  int n_t = j.mesh.n_t;
+  if (j.ranges) {
+    const FlMeshRange r = j.ranges[m];
+    tri += 3 * (size_t)r.tri_first;
+    n_t = r.n_t;
+  }
   verify_fused_pose(a, t, j.pose + (size_t)t * j.pose_stride,
-                    (const uint16_t *)(j.frames + j.frame_stride * (size_t)(j.frame_of ? j.frame_of[t] : t / j.per_frame)));
+                    (const uint16_t *)(j.frames + j.frame_stride * (size_t)(j.frame_of ? j.frame_of[t] : t / j.per_frame)), tri, n_t);
 }
 
 // a tracker's tracks (FlVerifyFusedJob::skip): the poses the passes returned, then the poses the call came in with
@@ -407,8 +421,15 @@ __global__ __launch_bounds__(VF) void k_verify_fused_tracks(FusedArgs a)
   const FlVerifyFusedJob &j = a.j;
   const int t = blockIdx.x, u = t < j.split ? t : t - j.split;
   if (j.skip[u]) return;                        // lost in the passes: no mesh walk (uniform per workgroup)
+  const int32_t *tri = j.mesh.tri;
+  int n_t = j.mesh.n_t;
+  if (j.ranges) {
+    const FlMeshRange r = j.ranges[j.mesh_of ? j.mesh_of[u] : 0];
+    tri += 3 * (size_t)r.tri_first;
+    n_t = r.n_t;
+  }
   verify_fused_pose(a, t, (t < j.split ? j.pose : j.pose_in) + (size_t)u * j.pose_stride,
-                    (const uint16_t *)(j.frames + j.frame_stride * (size_t)j.frame_of[u]));
+                    (const uint16_t *)(j.frames + j.frame_stride * (size_t)j.frame_of[u]), tri, n_t);
 }
 
 __global__ __launch_bounds__(64) void k_verify_finish(VerifyArgs a)
@@ -499,11 +520,11 @@ extern "C" int fl_dev_tracker_verify_ms(fl_tracker *trk, float out[4])
   return FL_OK;
 }
 
-extern "C" int fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_poses,
-                               const int32_t *frame_of_pose, const float *poses13, int n_groups, const int32_t *group_first,
-                               const fl_intrinsics *K, const fl_verify_params *params, fl_verify_result *results)
+extern "C" int fl_verify_batch_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_poses,
+                                      const int32_t *frame_of_pose, const int32_t *mesh_of_pose, const float *poses13, int n_groups,
+                                      const int32_t *group_first, const fl_intrinsics *K, const fl_verify_params *params, fl_verify_result *results)
 {
-  int rc = fl_tracker_check_call(trk, "fl_verify_batch", n_frames, depth, mem, n_poses, frame_of_pose, poses13, K, results);
+  int rc = fl_tracker_check_call(trk, "fl_verify_batch", n_frames, depth, mem, n_poses, frame_of_pose, mesh_of_pose, poses13, K, results);
   if (rc) return rc;
   if ((rc = fl_verify_check_call(trk, "fl_verify_batch", K, n_poses, n_groups, group_first))) return rc;
   fl_context *ctx = trk->ctx;
@@ -515,7 +536,7 @@ extern "C" int fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *co
 
   // 1. the inputs, and the groups after them
   hipEvent_t *ev = trk->ev + FL_TRACK_EVENTS;
-  if ((rc = fl_tracker_stage(trk, ev[0], n_frames, depth, mem, n_poses, frame_of_pose, poses13, nullptr))) return rc;
+  if ((rc = fl_tracker_stage(trk, ev[0], n_frames, depth, mem, n_poses, frame_of_pose, mesh_of_pose, poses13, nullptr))) return rc;
   const size_t px = (size_t)trk->w * trk->h, T = (size_t)n_poses;
   hipStream_t st = ctx->stream;
   if (group_first) {
@@ -534,7 +555,8 @@ extern "C" int fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *co
                   group_first ? trk->d_group_first : nullptr, (FlVerifyAcc *)trk->d_vacc, trk->d_vres};               // in VerifyArgs' order
   if (fused) {                                  // render and counts in one kernel, poses and frames where fl_tracker_stage put them
     const FlVerifyFusedJob j = {n_poses, trk->w, trk->h, P.tau_mm, fx, fy, cx, cy, {trk->d_vtx, nullptr, nullptr, trk->d_tri, trk->n_t},
-                                trk->d_poses, 13, trk->d_frames, trk->frame_stride, trk->d_frame_of, 1, nullptr, nullptr, -1, trk->d_vacc};
+                                trk->d_poses, 13, trk->d_frames, trk->frame_stride, trk->d_frame_of, 1, nullptr, nullptr, trk->call_mesh_of, trk->d_vacc,
+                                nullptr, 0, nullptr, trk->call_ranges};
     if ((rc = fl_launch_verify_fused(ctx, j))) return rc;
   } else {
     hipLaunchKernelGGL(k_verify_score, dim3((unsigned)(n_poses * a.n_strips)), dim3(VB), 0, st, a);   // <= 2^16 * 2^13 workgroups
@@ -553,4 +575,11 @@ extern "C" int fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *co
   if ((rc = fl_tracker_results(trk, trk->d_vres, T * sizeof(fl_verify_result), results))) return rc;
   trk->verified = true;
   return FL_OK;
+}
+
+extern "C" int fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_poses,
+                               const int32_t *frame_of_pose, const float *poses13, int n_groups, const int32_t *group_first,
+                               const fl_intrinsics *K, const fl_verify_params *params, fl_verify_result *results)
+{
+  return fl_verify_batch_meshes(trk, n_frames, depth, mem, n_poses, frame_of_pose, nullptr, poses13, n_groups, group_first, K, params, results);
 }

@@ -527,6 +527,34 @@ void fl_tracker_destroy(fl_tracker *trk);
 int  fl_track_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
                     int n_tracks, const int32_t *frame_of_track, const float *poses13,
                     const fl_intrinsics *K, const fl_track_params *params, fl_track_result *results);
+/* ---- several meshes on one tracker ---------------------------------------------------------------------------------------
+ * fl_tracker_create_meshes is fl_tracker_create for n_meshes meshes (fl_tracker_create IS this call with one mesh): each mesh
+ * as fl_tracker_create takes it, a triangle's indices inside its own mesh's vertices.  The meshes share every other buffer of
+ * the tracker -- frame slots, render images, depth keys, ICP workspaces -- so device memory grows by the extra meshes and a
+ * table of n_meshes ranges only.  FL_ERR_INVALID on top of fl_tracker_create's refusals: meshes NULL, n_meshes outside
+ * 1..FL_TRACK_MAX_MESHES, a mesh that breaks fl_tracker_create's mesh rules (the error text says which mesh), more than
+ * FL_RENDER_MAX_PRIMS vertices or triangles over all meshes.  All of them precede the device check (FL_ERR_NO_DEVICE).
+ * fl_tracker_num_meshes: the number of meshes (FL_ERR_INVALID for NULL).
+ * fl_track_batch_meshes, fl_verify_batch_meshes and fl_track_batch_verified_meshes (the latter two are declared below, after
+ * the calls they extend) are fl_track_batch, fl_verify_batch and fl_track_batch_verified with one more argument: mesh_of_track
+ * / mesh_of_pose, host memory, the mesh of every track or pose, each in [0, n_meshes); NULL: mesh 0 for all of them.  The three
+ * calls without the argument are these with NULL, so on a tracker of several meshes they use mesh 0.  An entry out of range:
+ * FL_ERR_INVALID, nothing written, before the first HIP call like the other argument checks.
+ * CONTRACT: the record of a track or pose whose mesh is m is, byte for byte, the record the call without the argument returns
+ * for that pose and frame on a tracker created from mesh m alone (a key's tie rule "equal depths go to the lower triangle
+ * index" counts triangles inside mesh m).  Groups (group_first) may mix meshes; the pick compares records as it always does. */
+typedef struct {
+  const float   *vertices;             /* n_vertices * 3, mm */
+  const int32_t *triangles;            /* n_triangles * 3, 0-based into this mesh's vertices */
+  int32_t n_vertices, n_triangles;
+} fl_mesh;
+#define FL_TRACK_MAX_MESHES 256
+int  fl_tracker_create_meshes(fl_context *ctx, const fl_mesh *meshes, int n_meshes, int w, int h,
+                              int max_frames, int max_tracks, int max_crop_px, fl_tracker **out);
+int  fl_tracker_num_meshes(const fl_tracker *trk);
+int  fl_track_batch_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
+                           int n_tracks, const int32_t *frame_of_track, const int32_t *mesh_of_track, const float *poses13,
+                           const fl_intrinsics *K, const fl_track_params *params, fl_track_result *results);
 /* ---- verification: is the object where a pose says it is?  (No counterpart in the reference, whose check is visual.) -----
  * The ICP's dist_mean and px_ratio are measured over the point pairs the ICP kept: they say how well the kept points fit,
  * not whether the object is there.  fl_verify_batch renders the tracker's mesh at every pose and lays the render over the
@@ -577,6 +605,11 @@ int  fl_verify_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth
                      int n_poses, const int32_t *frame_of_pose, const float *poses13,
                      int n_groups, const int32_t *group_first, const fl_intrinsics *K,
                      const fl_verify_params *params, fl_verify_result *results);
+/* with a mesh per pose: see "several meshes on one tracker" above for mesh_of_pose and the contract */
+int  fl_verify_batch_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
+                            int n_poses, const int32_t *frame_of_pose, const int32_t *mesh_of_pose, const float *poses13,
+                            int n_groups, const int32_t *group_first, const fl_intrinsics *K,
+                            const fl_verify_params *params, fl_verify_result *results);
 /* ---- verified tracking: fl_track_batch whose `tracked` is the verification's ---------------------------------------------------
  * Opt-in; fl_track_batch and fl_verify_batch are unchanged.  depth, mem, frame_of_track, poses13, K and params are as
  * fl_track_batch takes them, n_groups and group_first as fl_verify_batch takes them; vparams == NULL: the defaults below.
@@ -626,6 +659,13 @@ int  fl_track_batch_verified(fl_tracker *trk, int n_frames, const uint16_t *cons
                              int n_groups, const int32_t *group_first, const fl_intrinsics *K,
                              const fl_track_params *params, const fl_track_verify_params *vparams,
                              fl_verified_track_result *results);
+/* with a mesh per track: see "several meshes on one tracker" above for mesh_of_track and the contract; the passes and the
+ * verification of a track use the same mesh */
+int  fl_track_batch_verified_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem,
+                                    int n_tracks, const int32_t *frame_of_track, const int32_t *mesh_of_track, const float *poses13,
+                                    int n_groups, const int32_t *group_first, const fl_intrinsics *K,
+                                    const fl_track_params *params, const fl_track_verify_params *vparams,
+                                    fl_verified_track_result *results);
 /* ---- verified instance pick: fl_recognize_batch_instances whose pick among a group's members is the verification's -----------
  * The call chain of fl_recognize_batch_instances up to and including its ONE ICP launch, then, all on the device and on the
  * same n_frames * max_instances * hyp_per_instance job slots: the verification of every LIVE slot -- its job exists, its
@@ -664,6 +704,20 @@ int  fl_recognize_batch_instances_verified(fl_detector *det, fl_tracker *mesh, i
                                            const fl_recognition_params *params, const fl_instance_params *ip,
                                            const fl_instance_verify_params *vp, fl_verified_instance_result *results,
                                            int32_t *n_instances, int32_t *n_dropped, fl_verify_result *member_verify);
+/* The same with a mesh per class: `mesh` is a tracker of several meshes (fl_tracker_create_meshes) and mesh_of_class, host
+ * memory, has fl_detector_num_classes(det) entries, each a mesh of the tracker or -1.  A slot is LIVE when its job exists, its
+ * result has found = 1 and mesh_of_class[its class] >= 0, and is verified against that mesh; a group is VERIFIED when its class
+ * maps to a mesh.  Everything else -- the pick, nms_rank, member_verify, a verified group without an accepted member -- is as
+ * stated above.  fl_recognize_batch_instances_verified is this call with the map "every class -> mesh 0" (class_idx = -1) or
+ * "class_idx -> mesh 0, every other class -> -1".  The map travels with the call's other inputs: no further wait, no allocation
+ * beyond the context's scratch and pinned blocks.  FL_ERR_INVALID on top of the refusals above: mesh_of_class NULL, an entry
+ * outside [-1, n_meshes), vp->class_idx other than -1 (the map says it). */
+int  fl_recognize_batch_instances_verified_meshes(fl_detector *det, fl_tracker *mesh, int n_frames, const uint8_t *const *bgr,
+                                                  const uint16_t *const *depth, int mem, const fl_intrinsics *K,
+                                                  const fl_recognition_params *params, const fl_instance_params *ip,
+                                                  const fl_instance_verify_params *vp, const int32_t *mesh_of_class,
+                                                  fl_verified_instance_result *results, int32_t *n_instances, int32_t *n_dropped,
+                                                  fl_verify_result *member_verify);
 /* After fl_match_frame / fl_recognize_submit: copy frame `frame`'s first k sorted matches into a
  * device buffer (k * sizeof(fl_match) bytes, padded with template_id = -1) for an RCCL
  * all-gather by the caller; template ids are offset by template_id_base (the shard's first
