@@ -7,11 +7,13 @@
  * links, loads or calls it and has no CPU fallback.
  *
  * PARITY: the LINEMOD half (spread .. Detector::match on quantized images, quantizedNormals, hysteresisGradient,
- * cropTemplates) is pinned bit for bit to the reference's own compiled code: oracle/ref builds the reference's linemod.cpp
- * against a container-only opencv2/ stand-in (tests/test_reference_cpu.py, tests/golden/reference_linemod.npz).  UNPINNED
- * remain the un-vendored OpenCV 3.x calls (GaussianBlur, Sobel, fastAtan2, pyrDown, resize, erode, distanceTransform,
- * JacobiSVD, FLANN exact NN), restated here from their published algorithms -- stated explicitly where used -- and with
- * them the whole ICP half.  Every function cites the file:line of the reference it follows.
+ * cropTemplates) and template extraction (quantizedOrientations' channel choice, the two extractTemplate methods,
+ * selectScatteredFeatures, Detector::addTemplate) are pinned bit for bit to the reference's own compiled code: oracle/ref builds
+ * the reference's linemod.cpp against a container-only opencv2/ stand-in (tests/test_reference_cpu.py,
+ * tests/golden/reference_linemod.npz, reference_extract.npz).  UNPINNED remain the un-vendored OpenCV 3.x calls (GaussianBlur,
+ * Sobel, fastAtan2, pyrDown, resize, erode, distanceTransform, JacobiSVD, FLANN exact NN), restated here from their published
+ * algorithms -- stated explicitly where used; the stand-in delegates them to these very functions -- and the ICP half's
+ * third-party arithmetic (oracle/ref/icp_harness.cpp).  Every function cites the file:line of the reference it follows.
  *
  * All paths are relative to /root/reference.
  */
@@ -90,6 +92,8 @@ void orc_hysteresis_gradient(const float *magnitude, const float *angle, int w, 
 void orc_pyrdown_bgr(const uint8_t *src, int w, int h, uint8_t *dst);       /* cv::pyrDown 8UC3 */
 void orc_resize_nn_half(const uint8_t *src, int w, int h, uint8_t *dst);    /* linemod.cpp:731  */
 void orc_gaussian7_bgr(const uint8_t *src, int w, int h, uint8_t *dst);
+/* cv::Sobel(CV_16S, ksize 3, BORDER_REPLICATE) on 8UC3 (linemod.cpp:248-249): d/dx (vertical == 0) or d/dy; dst is w*h*3 */
+void orc_sobel3_bgr(const uint8_t *src, int w, int h, int vertical, int16_t *dst);
 void orc_median5(const uint8_t *src, int w, int h, uint8_t *dst);
 float orc_fast_atan2(float y, float x);
 /* Detector::match from BGR + depth16 with the two default modalities

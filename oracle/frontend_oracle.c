@@ -107,28 +107,44 @@ void orc_hysteresis_gradient(const float *magnitude, const float *angle, int w, 
   free(qu);
 }
 
+/* cv::Sobel(src, dst, CV_16S, 1, 0, 3, 1, 0, BORDER_REPLICATE) (vertical == 0) or (.., 0, 1, 3, ..) (vertical != 0) on CV_8UC3
+ * (linemod.cpp:248-249): the 3x3 kernel [-1 0 1] x [1 2 1] in integers; |value| <= 1020, so CV_16S never saturates */
+void orc_sobel3_bgr(const uint8_t *src, int w, int h, int vertical, int16_t *dst)
+{
+  for (int y = 0; y < h; ++y) {
+    int ym = clampi(y - 1, 0, h - 1), yp = clampi(y + 1, 0, h - 1);
+    for (int x = 0; x < w; ++x) {
+      int xm = clampi(x - 1, 0, w - 1), xp = clampi(x + 1, 0, w - 1);
+      for (int c = 0; c < 3; ++c) {
+#define S(yy, xx) ((int)src[((size_t)(yy) * w + (xx)) * 3 + c])
+        int d = vertical ? (S(yp, xm) - S(ym, xm)) + 2 * (S(yp, x) - S(ym, x)) + (S(yp, xp) - S(ym, xp))
+                         : (S(ym, xp) - S(ym, xm)) + 2 * (S(y, xp) - S(y, xm)) + (S(yp, xp) - S(yp, xm));
+#undef S
+        dst[((size_t)y * w + x) * 3 + c] = (int16_t)d;
+      }
+    }
+  }
+}
+
 /* quantizedOrientations (linemod.cpp:230-305), ending in hysteresisGradient */
 void orc_quantized_orientations(const uint8_t *bgr, int w, int h, float weak_threshold,
                                 uint8_t *dst, float *magnitude_out)
 {
   size_t n = (size_t)w * h;
   uint8_t *sm = (uint8_t *)malloc(n * 3);
+  int16_t *sdx = (int16_t *)malloc(sizeof(int16_t) * n * 3), *sdy = (int16_t *)malloc(sizeof(int16_t) * n * 3);
   float *mag = (float *)malloc(sizeof(float) * n);
   float *ag = (float *)malloc(sizeof(float) * n);
   orc_gaussian7_bgr(bgr, w, h, sm);
+  orc_sobel3_bgr(sm, w, h, 0, sdx);
+  orc_sobel3_bgr(sm, w, h, 1, sdy);
 
   for (int y = 0; y < h; ++y) {
-    int ym = clampi(y - 1, 0, h - 1), yp = clampi(y + 1, 0, h - 1);
     for (int x = 0; x < w; ++x) {
-      int xm = clampi(x - 1, 0, w - 1), xp = clampi(x + 1, 0, w - 1);
       int best_dx = 0, best_dy = 0, best_mag = 0;
       int dxs[3], dys[3], mags[3];
       for (int c = 0; c < 3; ++c) {
-        /* cv::Sobel(.., CV_16S, 1,0,3) / (0,1,3), BORDER_REPLICATE (linemod.cpp:248-249) */
-#define S(yy, xx) ((int)sm[((size_t)(yy) * w + (xx)) * 3 + c])
-        int dx = (S(ym, xp) - S(ym, xm)) + 2 * (S(y, xp) - S(y, xm)) + (S(yp, xp) - S(yp, xm));
-        int dy = (S(yp, xm) - S(ym, xm)) + 2 * (S(yp, x) - S(ym, x)) + (S(yp, xp) - S(ym, xp));
-#undef S
+        int dx = sdx[((size_t)y * w + x) * 3 + c], dy = sdy[((size_t)y * w + x) * 3 + c];
         dxs[c] = dx;
         dys[c] = dy;
         mags[c] = dx * dx + dy * dy;
@@ -144,6 +160,8 @@ void orc_quantized_orientations(const uint8_t *bgr, int w, int h, float weak_thr
   orc_hysteresis_gradient(mag, ag, w, h, weak_threshold * weak_threshold, dst);  /* :304 */
   if (magnitude_out) memcpy(magnitude_out, mag, sizeof(float) * n);
   free(sm);
+  free(sdx);
+  free(sdy);
   free(mag);
   free(ag);
 }

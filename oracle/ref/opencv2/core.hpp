@@ -20,13 +20,21 @@
 //        their inputs by construction and assert it, so this definition decides nothing that is checked;
 //      - medianBlur(src, dst, 5) on CV_8UC1 is the plain median of the 25 values of the 5x5 window with a replicated
 //        border (quantizedNormals, linemod.cpp:684).  A median of 25 values has no rounding and no tie to break.
+//      - subtract (saturating), bitwise_and, countNonZero and Mat::setTo(value, mask) on CV_8UC1 (the two
+//        extractTemplate methods, linemod.cpp:468, :761-762, :815): integer operations per element, nothing to round.
 //    They are OURS, not OpenCV's code, and are named here so that nobody takes them for more than that.
 //
+//  * THE OPERATIONS OF TEMPLATE EXTRACTION whose kernel, work type or rounding is OpenCV's choice are DELEGATED to the
+//    oracle's restatement in ../liboracle.so, for exactly the argument patterns linemod.cpp uses (anything else aborts):
+//    phase in degrees -> orc_fast_atan2 (here); GaussianBlur 7x7 -> orc_gaussian7_bgr, Sobel CV_16S ksize 3 ->
+//    orc_sobel3_bgr, pyrDown -> orc_pyrdown_bgr, resize INTER_NEAREST to exact halves -> orc_resize_nn_half, erode 3x3 ->
+//    orc_erode_rect, distanceTransform(DIST_C, 3) -> orc_distance_transform_c3 (opencv2/imgproc.hpp).  Both sides then
+//    run the same code for them: that arithmetic is NOT PINNED.  What the compiled reference pins around them is its own
+//    control flow, comparisons, operand order and conversions (oracle/ref/ref_harness.cpp lists both, item by item).
+//
 //  * EVERYTHING ELSE linemod.cpp names is DECLARED ONLY and given a body that aborts with its name (FEALESS_REF_UNPINNED):
-//    GaussianBlur, Sobel, phase, pyrDown, resize, erode, subtract, bitwise_and, add, distanceTransform, countNonZero,
-//    every other Mat::convertTo, FileStorage/FileNode I/O and format.  OpenCV's choice of kernels, work types and
-//    roundings for those stays UNPINNED; this stand-in does not re-implement OpenCV arithmetic a second time and call it
-//    a reference.
+//    add, cvtColor, every other Mat::convertTo, every other argument pattern of the operations above, FileStorage/FileNode
+//    I/O and format.  This stand-in does not re-implement OpenCV arithmetic a second time and call it a reference.
 //
 //  * FOR THE ICP SOURCES (oracle/ref/icp_harness.cpp lists, item by item, which of these is OpenCV's header text restated
 //    and which is a choice of ours): Vec<T,n> and Matx<T,m,n> with the element-wise operators and the products of
@@ -81,6 +89,7 @@ typedef unsigned char uchar;
 typedef unsigned short ushort;
 #include <stdint.h>
 typedef int64_t int64;
+#include "../../fealess_oracle.h"  // the orc_* restatements that the delegated operations call (../liboracle.so)
 
 #define CV_MAJOR_VERSION 3
 
@@ -100,6 +109,7 @@ typedef int64_t int64;
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
 #define CV_16UC3 CV_MAKETYPE(CV_16U, 3)
 #define CV_16SC1 CV_MAKETYPE(CV_16S, 1)
+#define CV_16SC3 CV_MAKETYPE(CV_16S, 3)
 #define CV_32FC2 CV_MAKETYPE(CV_32F, 2)
 #define CV_32FC3 CV_MAKETYPE(CV_32F, 3)
 #define CV_64FC1 CV_MAKETYPE(CV_64F, 1)
@@ -726,12 +736,53 @@ class FileStorage {
 template <typename T> inline FileStorage &operator<<(FileStorage &, const T &) { FEALESS_REF_UNPINNED("FileStorage"); }
 inline String format(const char *, ...) { FEALESS_REF_UNPINNED("format"); }
 
-// ---- declared only: array arithmetic ----------------------------------------------------------------------------
-inline void subtract(const Mat &, const Mat &, Mat &) { FEALESS_REF_UNPINNED("subtract"); }
-inline void bitwise_and(const Mat &, const Mat &, Mat &) { FEALESS_REF_UNPINNED("bitwise_and"); }
+// ---- array arithmetic of template extraction: CV_8UC1 only, each with one possible answer ---------------------------
+inline bool fealess_same_8u(const Mat &a, const Mat &b)
+{
+  return !a.empty() && a.type() == CV_8UC1 && b.type() == CV_8UC1 && a.rows == b.rows && a.cols == b.cols;
+}
+// saturating a - b; dst may be a or b (ColorGradientPyramid::extractTemplate, linemod.cpp:468)
+inline void subtract(const Mat &a, const Mat &b, Mat &dst)
+{
+  if (!fealess_same_8u(a, b)) FEALESS_REF_UNPINNED("subtract (other than CV_8UC1 of one size)");
+  Mat out(a.rows, a.cols, CV_8UC1);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) {
+      const int v = (int)a.ptr(r)[c] - (int)b.ptr(r)[c];
+      out.ptr(r)[c] = (uchar)(v < 0 ? 0 : v);
+    }
+  dst = out;
+}
+// a & b; dst may be a or b (DepthNormalPyramid::extractTemplate, linemod.cpp:762)
+inline void bitwise_and(const Mat &a, const Mat &b, Mat &dst)
+{
+  if (!fealess_same_8u(a, b)) FEALESS_REF_UNPINNED("bitwise_and (other than CV_8UC1 of one size)");
+  Mat out(a.rows, a.cols, CV_8UC1);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) out.ptr(r)[c] = (uchar)(a.ptr(r)[c] & b.ptr(r)[c]);
+  dst = out;
+}
+inline int countNonZero(const Mat &a)
+{
+  if (a.type() != CV_8UC1) FEALESS_REF_UNPINNED("countNonZero (other than CV_8UC1)");
+  int n = 0;
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) n += a.ptr(r)[c] != 0;
+  return n;
+}
 inline void add(const Mat &, const Mat &, Mat &, const _OutputArray &, int) { FEALESS_REF_UNPINNED("add"); }
-inline int countNonZero(const Mat &) { FEALESS_REF_UNPINNED("countNonZero"); }
-inline void phase(const Mat &, const Mat &, Mat &, bool) { FEALESS_REF_UNPINNED("phase"); }
+
+// ---- delegated to the oracle (../liboracle.so): OpenCV's arithmetic, restated there and NOT pinned --------------------
+// cv::phase(x, y, angle, true) on CV_32FC1 -> orc_fast_atan2(y, x) per element (quantizedOrientations, linemod.cpp:303)
+inline void phase(const Mat &x, const Mat &y, Mat &angle, bool degrees)
+{
+  if (!degrees || x.empty() || x.type() != CV_32FC1 || y.type() != CV_32FC1 || x.rows != y.rows || x.cols != y.cols)
+    FEALESS_REF_UNPINNED("phase (other than CV_32FC1 in degrees)");
+  Mat out(x.rows, x.cols, CV_32FC1);
+  for (int r = 0; r < x.rows; ++r)
+    for (int c = 0; c < x.cols; ++c) out.ptr<float>(r)[c] = orc_fast_atan2(y.ptr<float>(r)[c], x.ptr<float>(r)[c]);
+  angle = out;
+}
 
 }  // namespace cv
 #endif

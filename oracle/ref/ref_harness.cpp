@@ -4,9 +4,32 @@
 // include path at build time (-I$(FEALESS_REFERENCE_ROOT)/linemod), so that its file-static functions are visible; no
 // line of it is in this repository, and the libraries built from this file (oracle/_ref/) are never committed.
 //
-// Every entry point returns 0, or -1 when the reference threw (CV_Assert / CV_Error).  Inputs are copied into Mats of
-// the stand-in, whose allocator appends a zeroed guard (opencv2/core.hpp): reads past the last grid row of a linear
-// memory (quirk Q2) are undefined behaviour in the reference and read 0 here.
+// TEMPLATE EXTRACTION runs here too: quantizedOrientations, std::stable_sort + selectScatteredFeatures, the two
+// extractTemplate methods on caller-supplied images, Detector::addTemplate.
+// WHAT IS PINNED by it: the reference's text, compiled -- `score > threshold_sq` (strong^2 itself is no candidate),
+// `score >= extract_threshold`, labels 0 and 255 left out, mask - erode(mask) as the colour mask, candidates.size() /
+// num_features + 1 in size_t, sqrtf(area) / sqrtf(num_features) + 1.5f with area = total() or countNonZero of the eroded
+// mask, the relaxation loop of selectScatteredFeatures (distance -= 1.0f through fractions and below zero) and its `>=`
+// keep rule on an int compared with a float, std::stable_sort on Candidate::operator<, score /= label_counts[label],
+// num_features /= 2 and extract_threshold /= 2 per level, the else-if chain that picks a colour channel on equal
+// magnitudes (mag1 >= mag2 && mag1 >= mag3, then mag2), `min_x % 2 == 1` in cropTemplates, the order in which
+// addTemplate walks modalities and levels and gives up.
+// WHAT STAYS UNPINNED: OpenCV arithmetic the reference only CALLS, which the stand-in delegates to the oracle's
+// restatement in ../liboracle.so (this library links it, so both sides run the same code), item by item:
+//   * cv::GaussianBlur 7x7, sigma 0, BORDER_REPLICATE, 8UC3   -> orc_gaussian7_bgr;
+//   * cv::Sobel CV_16S, ksize 3, BORDER_REPLICATE, 8UC3        -> orc_sobel3_bgr;
+//   * cv::phase in degrees                                      -> orc_fast_atan2 per element;
+//   * cv::pyrDown 8UC3 to exact halves                          -> orc_pyrdown_bgr;
+//   * cv::resize INTER_NEAREST 8UC1 to exact halves             -> orc_resize_nn_half;
+//   * cv::erode, default 3x3, 1 or 2 iterations, replicated     -> orc_erode_rect;
+//   * cv::distanceTransform(DIST_C, 3)                          -> orc_distance_transform_c3.
+// Plain code of the stand-in, each with one possible answer: subtract (saturating u8), bitwise_and, countNonZero,
+// Mat::setTo(value, mask), and the two conversions and the median that opencv2/core.hpp describes.
+//
+// Every entry point returns 0, or -1 when the reference threw (CV_Assert / CV_Error); the extraction entries return the
+// oracle's 1 (features written) / 0 (too few candidates) and -1 for a throw; ref_add_template returns addTemplate's -1.
+// Inputs are copied into Mats of the stand-in, whose allocator appends a zeroed guard (opencv2/core.hpp): reads past the
+// last grid row of a linear memory (quirk Q2) are undefined behaviour in the reference and read 0 here.
 #include "linemod.cpp"  // the reference's, found by include path
 
 #include <map>
@@ -116,6 +139,57 @@ class OpenDetector : public Detector {
         if (it != class_templates.end()) matchClass(lm_pyramid, sizes, threshold, matches, it->first, it->second);
       }
     }
+  }
+};
+
+void out_features(const std::vector<Feature> &fs, orc_feature *out)
+{
+  for (size_t i = 0; i < fs.size(); ++i) {
+    out[i].x = fs[i].x;
+    out[i].y = fs[i].y;
+    out[i].label = fs[i].label;
+  }
+}
+
+// Candidate and selectScatteredFeatures are protected in QuantizedPyramid: reached from a derived class.  The sort is
+// the one both extractTemplate methods run (std::stable_sort on Candidate::operator<, linemod.cpp:501, :812).
+class OpenSelection : public GivenPyramid {
+ public:
+  static void run(const int *x, const int *y, const int *label, const float *score, int n, int num_features, float distance,
+                  std::vector<Feature> &features)
+  {
+    std::vector<Candidate> candidates;
+    for (int i = 0; i < n; ++i) candidates.push_back(Candidate(x[i], y[i], label[i], score[i]));
+    std::stable_sort(candidates.begin(), candidates.end());
+    selectScatteredFeatures(candidates, features, (size_t)num_features, distance);
+  }
+};
+
+// The two pyramids with their protected members replaced by the caller's images: constructed on a small blank source
+// (the constructors quantize it), then assigned.
+class OpenColorPyramid : public ColorGradientPyramid {
+ public:
+  OpenColorPyramid(const Mat &quantized, const Mat &magnitude_, const Mat &mask_, float strong, int nf)
+      : ColorGradientPyramid(Mat::zeros(8, 8, CV_8UC3), Mat(), 10.0f, (size_t)nf, strong)
+  {
+    angle = quantized;
+    magnitude = magnitude_;
+    mask = mask_;
+    num_features = (size_t)nf;
+    strong_threshold = strong;
+    pyramid_level = 0;
+  }
+};
+
+class OpenDepthPyramid : public DepthNormalPyramid {
+ public:
+  OpenDepthPyramid(const Mat &normal_, const Mat &mask_, int extract, int nf)
+      : DepthNormalPyramid(Mat::zeros(16, 16, CV_16UC1), Mat(), 2000, 50, (size_t)nf, extract)
+  {
+    normal = normal_;
+    mask = mask_;
+    num_features = (size_t)nf;
+    extract_threshold = extract;
   }
 };
 
@@ -274,6 +348,107 @@ int ref_hysteresis_gradient(const float *magnitude, const float *angle, int w, i
     }
     hysteresisGradient(mag, q, ang, threshold);
     out_u8(q, dst);
+    return 0;
+  } catch (const cv::Exception &) { return -1; }
+}
+
+// quantizedOrientations (the file-static, linemod.cpp:230-305): the quantized image and the squared magnitude
+int ref_quantized_orientations(const uint8_t *bgr, int w, int h, float weak_threshold, uint8_t *dst, float *magnitude)
+{
+  try {
+    Mat src(h, w, CV_8UC3), mag, q;
+    for (int r = 0; r < h; ++r) std::memcpy(src.ptr(r), bgr + (size_t)r * w * 3, (size_t)w * 3);
+    quantizedOrientations(src, mag, q, weak_threshold);
+    out_u8(q, dst);
+    if (magnitude)
+      for (int r = 0; r < h; ++r) std::memcpy(magnitude + (size_t)r * w, mag.ptr<float>(r), sizeof(float) * w);
+    return 0;
+  } catch (const cv::Exception &) { return -1; }
+}
+
+// std::stable_sort on Candidate::operator<, then selectScatteredFeatures (linemod.cpp:135-164), on a candidate list in
+// arrival order.  1, or 0 when n < num_features or num_features < 1: the reference's callers guard that (:498, :802);
+// unguarded it would index past the list, so the refusal is made here, before the reference is entered.  -1: it threw
+int ref_select_scattered_list(const int *x, const int *y, const int *label, const float *score, int n, int num_features,
+                              float distance, orc_feature *out)
+{
+  if (num_features < 1 || n < num_features) return 0;
+  try {
+    std::vector<Feature> fs;
+    OpenSelection::run(x, y, label, score, n, num_features, distance, fs);
+    out_features(fs, out);
+    return 1;
+  } catch (const cv::Exception &) { return -1; }
+}
+
+// ColorGradientPyramid::extractTemplate (linemod.cpp:461-513) on the caller's quantized image, squared magnitude and
+// mask (NULL: empty).  1 / 0 (too few candidates) / -1 (threw: getLabel on a byte that is not one-hot)
+int ref_extract_template_color(const uint8_t *quantized, const float *magnitude, const uint8_t *mask, int w, int h,
+                               float strong_threshold, int num_features, orc_feature *out)
+{
+  if (num_features < 1) return 0;
+  try {
+    Mat mag(h, w, CV_32F);
+    for (int r = 0; r < h; ++r) std::memcpy(mag.ptr(r), magnitude + (size_t)r * w, sizeof(float) * w);
+    OpenColorPyramid p(mat_u8(quantized, w, h), mag, mask ? mat_u8(mask, w, h) : Mat(), strong_threshold, num_features);
+    Template t;
+    if (!p.extractTemplate(t)) return 0;
+    out_features(t.features, out);
+    return 1;
+  } catch (const cv::Exception &) { return -1; }
+}
+
+// DepthNormalPyramid::extractTemplate (linemod.cpp:747-825) on the caller's quantized normals and mask (NULL: empty)
+int ref_extract_template_depth(const uint8_t *normal, const uint8_t *mask, int w, int h, int extract_threshold, int num_features,
+                               orc_feature *out)
+{
+  if (num_features < 1) return 0;
+  try {
+    OpenDepthPyramid p(mat_u8(normal, w, h), mask ? mat_u8(mask, w, h) : Mat(), extract_threshold, num_features);
+    Template t;
+    if (!p.extractTemplate(t)) return 0;
+    out_features(t.features, out);
+    return 1;
+  } catch (const cv::Exception &) { return -1; }
+}
+
+// Detector::addTemplate (linemod.cpp:1579-1615) with the two default modalities, ColorGradient() and DepthNormal()
+// (:515-519, :827-832); mask NULL: empty.  templates[levels * 2] ordered [l * 2 + m] and the bounding box are read back
+// with getTemplates; the feature slot of template k is feats + 63 * k.  0, or -1 where addTemplate returned -1 (too few
+// candidates at some level: a result, recorded) or the reference threw
+int ref_add_template(const uint8_t *bgr, const uint16_t *depth, const uint8_t *mask, int w0, int h0, int levels,
+                     orc_template *templates, orc_feature *feats, int bb[4])
+{
+  if (levels < 1 || levels > 3) return -1;
+  try {
+    std::vector<Mat> sources(2);
+    sources[0].create(h0, w0, CV_8UC3);
+    sources[1].create(h0, w0, CV_16UC1);
+    for (int r = 0; r < h0; ++r) {
+      std::memcpy(sources[0].ptr(r), bgr + (size_t)r * w0 * 3, (size_t)w0 * 3);
+      std::memcpy(sources[1].ptr(r), depth + (size_t)r * w0, sizeof(uint16_t) * w0);
+    }
+    std::vector<Ptr<Modality> > mods;
+    mods.push_back(makePtr<ColorGradient>());
+    mods.push_back(makePtr<DepthNormal>());
+    Detector det(mods, std::vector<int>(levels, 4));       // T plays no part in training
+    const float pose[13] = {0};
+    Rect box;
+    const int id = det.addTemplate(sources, "obj", mask ? mat_u8(mask, w0, h0) : Mat(), pose, &box);
+    if (id < 0) return -1;
+    const std::vector<Template> &tp = det.getTemplates("obj", id);
+    for (size_t k = 0; k < tp.size(); ++k) {
+      orc_template &t = templates[k];
+      t.width = tp[k].width;
+      t.height = tp[k].height;
+      t.offset_x = tp[k].offset_x;
+      t.offset_y = tp[k].offset_y;
+      t.pyramid_level = tp[k].pyramid_level;
+      t.feat_begin = (int)k * 63;
+      t.feat_count = (int)tp[k].features.size();
+      out_features(tp[k].features, feats + t.feat_begin);
+    }
+    bb[0] = box.x; bb[1] = box.y; bb[2] = box.width; bb[3] = box.height;
     return 0;
   } catch (const cv::Exception &) { return -1; }
 }

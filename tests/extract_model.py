@@ -33,7 +33,8 @@ def sort_order(score):
 def select_model(x, y, label, score, num_features, distance):
     """Returns (features (num_features, 3), stats) or (None, None) when the list is too short.  stats: relaxations = how
     often the distance was lowered, wraps_after_take = how often that happened right after the last sorted candidate
-    was taken, full_passes = how often it happened after a candidate that was not taken."""
+    was taken, full_passes = how often it happened after a candidate that was not taken, kept_at_equal = how many features
+    were kept with a chosen feature at exactly the required distance."""
     n = len(x)
     if n < num_features:
         return None, None
@@ -45,17 +46,21 @@ def select_model(x, y, label, score, num_features, distance):
     dsq = float(F32(distance * distance))
     fx, fy, out = [], [], []
     i = 0
-    stats = dict(relaxations=0, wraps_after_take=0, full_passes=0)
+    stats = dict(relaxations=0, wraps_after_take=0, full_passes=0, kept_at_equal=0)
     while len(out) < num_features:
         px, py = cx[i], cy[i]
         keep = True
+        equal = False
         for j in range(len(fx)):
             dx, dy = px - fx[j], py - fy[j]
             d2 = dx * dx + dy * dy
-            if not ((d2 if d2 < (1 << 24) else float(F32(d2))) >= dsq):      # (float)(int) >= float
+            d2 = d2 if d2 < (1 << 24) else float(F32(d2))
+            if not (d2 >= dsq):                                              # (float)(int) >= float
                 keep = False
                 break
+            equal |= d2 == dsq
         if keep:
+            stats["kept_at_equal"] += equal                                  # `>=` decided: `>` would have refused
             fx.append(px)
             fy.append(py)
             out.append((px, py, cl[i]))

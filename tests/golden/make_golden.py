@@ -14,7 +14,7 @@ symbols of a CadReco caller compiled against DIR/CadReco's headers (cadreco_refe
 the outputs of DIR/linemod/linemod.cpp, compiled against the stand-in of oracle/ref, on the cases of tests/reference_cases.py
 (reference_linemod.npz), and those of DIR/ICP's ICP.cpp, common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp, compiled the same
 way, on the ICP cases of that module (reference_icp.npz: results only, written with fixed time stamps so that a second run gives
-the same bytes).
+the same bytes), and those of linemod.cpp's template extraction on the extraction cases (reference_extract.npz, same writer).
 """
 import io
 import os
@@ -131,6 +131,7 @@ def reference_fixtures(ref):
     print("reference fixtures:", len(layout), "layout rows,", len(syms), "symbols")
     reference_linemod_fixture(ref)
     reference_icp_fixture(ref)
+    reference_extract_fixture(ref)
 
 
 def reference_linemod_fixture(ref):
@@ -184,6 +185,26 @@ def reference_icp_fixture(ref):
     path = os.path.join(HERE, "reference_icp.npz")
     save_npz_reproducibly(path, rec)
     print("reference icp fixture:", len(rec), "entries,", os.path.getsize(path) // 1024, "KiB")
+
+
+def reference_extract_fixture(ref):
+    """Outputs of the reference's COMPILED template extraction (linemod.cpp through oracle/ref/ref_harness.cpp, built here from
+    `ref`) on the extraction case list of tests/reference_cases.py -> reference_extract.npz.  One member per case (RC.recorded
+    with RC.is_image): a digest of the inputs, the feature lists, templates and bounding boxes in full, refusals as such,
+    images as digests.  Both builds must agree before anything is written."""
+    import reference_cases as RC
+    import reference_py as R
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle", "ref")], env=dict(os.environ, FEALESS_REFERENCE_ROOT=os.path.abspath(ref)))
+    scalar, simd = R.lib(False), R.lib(True)
+    rec = {}
+    for g, (cases, fn) in RC.extract_groups().items():
+        for name, c in cases:
+            out = fn(scalar, c)
+            assert RC.same(out, fn(simd, c)) is None, name
+            rec[f"{g}/{name}"] = RC.recorded(out, RC.is_image)
+    path = os.path.join(HERE, "reference_extract.npz")
+    save_npz_reproducibly(path, rec)
+    print("reference extract fixture:", len(rec), "entries,", os.path.getsize(path) // 1024, "KiB")
 
 
 if __name__ == "__main__":

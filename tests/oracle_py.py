@@ -236,6 +236,14 @@ def select_scattered_list(x, y, label, score, num_features, distance):
     return out if ok else None
 
 
+def sobel3_bgr(bgr, vertical):
+    """cv::Sobel(CV_16S, ksize 3, BORDER_REPLICATE) of an (h, w, 3) u8 image: d/dx (vertical = False) or d/dy, int16."""
+    b = np.ascontiguousarray(bgr, np.uint8)
+    out = np.zeros(b.shape, np.int16)
+    lib().orc_sobel3_bgr(_p(b), b.shape[1], b.shape[0], int(bool(vertical)), _p(out))
+    return out
+
+
 def quantized_orientations_mag(bgr, weak_threshold=10.0):
     b = np.ascontiguousarray(bgr, np.uint8)
     out = np.zeros(b.shape[:2], np.uint8)

@@ -29,12 +29,17 @@ that property of the input (never of an output):
 
 The ICP half (icp_groups) follows the same pattern on tests/golden/reference_icp.npz: that record holds digests of the inputs
 and RESULTS ONLY (float bit patterns as uint32, ints, digests of the clouds depthTo3d returns), no cloud and no image.
+
+Template extraction (extract_groups) the same way on tests/golden/reference_extract.npz: digests of the inputs, the feature
+lists, templates and bounding boxes in full, refusals as such, images as digests; its conditions are listed where it begins.
 """
 import functools
 import hashlib
 
 import numpy as np
 
+import extract_model as EM
+import oracle_py as O
 from fealess_amd import synth
 from fealess_amd.bank import FEATURE_DTYPE, MATCH_DTYPE, TEMPLATE_DTYPE, TemplateBank
 
@@ -977,21 +982,26 @@ def compute_nms(B, case):
     return _with_inputs({"winners": np.array(B.nms(t, npts, dist, th), np.int32)}, t, npts, dist, np.array([th], np.float32))
 
 
-def recorded(out):
+def _large(key, value):
+    return value.size > 256
+
+
+def recorded(out, digested=_large):
     """What tests/golden/reference_icp.npz keeps of one case's outputs, as one uint8 array: per key in sorted order the array
     itself while it is small (poses, counts, winners) or its digest beyond 256 elements (clouds, pair lists), behind a table
-    of their byte lengths.  One array per case keeps the file small: the container's cost is per member."""
+    of their byte lengths.  One array per case keeps the file small: the container's cost is per member.
+    tests/golden/reference_extract.npz has the same layout with digested = is_image: images as digests, all else in full."""
     parts = []
     for k in sorted(out):
         v = np.ascontiguousarray(out[k])
-        parts.append((v if v.size <= 256 else digest(v)).tobytes())
+        parts.append((digest(v) if digested(k, v) else v).tobytes())
     table = np.array([len(parts)] + [len(p) for p in parts], np.uint32).tobytes()
     return np.frombuffer(table + b"".join(parts), np.uint8).copy()
 
 
-def same_as_record(out, rec, group, name):
+def same_as_record(out, rec, group, name, digested=_large):
     """The outputs of one case against the record; returns the first key that differs, or None."""
-    a, b = recorded(out), rec[f"{group}/{name}"]
+    a, b = recorded(out, digested), rec[f"{group}/{name}"]
     if a.tobytes() == b.tobytes():
         return None
     n = int(b[:4].view(np.uint32)[0])
@@ -1001,10 +1011,26 @@ def same_as_record(out, rec, group, name):
     pos = 4 + 4 * n
     for k, ln in zip(sorted(out), lens):
         v = np.ascontiguousarray(out[k])
-        if (v if v.size <= 256 else digest(v)).tobytes() != b[pos:pos + int(ln)].tobytes():
+        if (digest(v) if digested(k, v) else v).tobytes() != b[pos:pos + int(ln)].tobytes():
             return k
         pos += int(ln)
     return "layout"
+
+
+def record_lengths(b):
+    """The byte lengths of the members of one recorded case, in the sorted order of their keys."""
+    n = int(b[:4].view(np.uint32)[0])
+    return [int(v) for v in b[4:4 + 4 * n].view(np.uint32)]
+
+
+def record_parts(rec, group, name, keys):
+    """The recorded bytes of one case per output key; `keys` are all the keys the case's outputs have."""
+    b = rec[f"{group}/{name}"]
+    n = int(b[:4].view(np.uint32)[0])
+    assert n == len(keys), (name, n, keys)
+    lens = b[4:4 + 4 * n].view(np.uint32)
+    ends = 4 + 4 * n + np.cumsum(lens)
+    return {k: b[int(e - ln):int(e)].tobytes() for k, e, ln in zip(sorted(keys), ends, lens)}
 
 
 class OracleIcpBackend:
@@ -1052,3 +1078,484 @@ def icp_groups():
         "depth3d": ([(c[0], c) for c in depth3d_cases()], compute_depth3d),
         "nms": ([(c[0], c) for c in nms_cases()], compute_nms),
     }
+
+
+# ======================================================================================================================
+# Template extraction: the sort and the scattered selection, the two extractTemplate methods, quantizedOrientations with
+# its magnitude, Detector::addTemplate (tests/golden/reference_extract.npz; extract_groups)
+# ======================================================================================================================
+# The cases sit on the reference's decision edges and on the dispatch edges fl_extract.hip states (2048-key LDS sort blocks,
+# 1024-thread selection, 64-wide tiles); check_extract_cases proves on the CPU, from tests/extract_model.py and the oracle's
+# stage functions, that every case is on the edge it is named for.  Excluded by construction, and asserted there:
+#   * selectScatteredFeatures with fewer candidates than features, or with num_features == 0, walks past its list: the
+#     reference's callers guard it (linemod.cpp:498, :802) and the select entry of both back ends refuses first;
+#   * a depth list with a pixel twice and a start distance of k + 0.5 never ends (0 >= 0.25 is false at 0.5 and at -0.5);
+#   * a quantized byte that is not one-hot throws in getLabel; the NORMAL_LUT and convertTo conditions of the header hold for
+#     every image a case quantizes (every level of an add_template case).
+EXW, EXH = 128, 96
+STRONG = 55.0
+
+
+def feats3(f):
+    """(n, 3) int32 of a feature array (FEATURE_DTYPE / FEAT_DTYPE records or (n, 3) ints) or of a list of them."""
+    if isinstance(f, list):
+        return np.concatenate([feats3(a) for a in f])
+    f = np.asarray(f)
+    if f.dtype.names:
+        return np.stack([f["x"], f["y"], f["label"]], 1).astype(np.int32)
+    return f.astype(np.int32).reshape(-1, 3)
+
+
+def _taken_or_refused(f):
+    return {"refused": np.ones(1, np.uint8)} if f is None else {"features": feats3(f)}
+
+
+# ---- select: std::stable_sort + selectScatteredFeatures on a list ------------------------------------------------------
+def _select_job(name, w, h, xy, score, nf, mode=0, area=0, seed=1):
+    xy = np.asarray(xy, np.int64)
+    return EM.make_job(name, w, h, xy[:, 1] * w + xy[:, 0], score, num_features=nf, depth_mode=mode, area=area, seed=seed)
+
+
+def _block_job(name, bw, bh, n, nf, mode, area, seed, kind="depth"):
+    """n candidates packed into a bw x bh block of a 40 x 30 image, in shuffled arrival order."""
+    rng = np.random.default_rng(seed)
+    r = rng.permutation(EM.block_rasters(40, bw, bh))[:n]
+    lab = EM.label_image(40, 30, seed)
+    s = EM.depth_scores(lab, r, 40, rng) if kind == "depth" else EM.scores(kind, n, rng)
+    return EM.make_job(name, 40, 30, r, s, num_features=nf, depth_mode=mode, area=area, seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def select_jobs():
+    """The jobs of the select group, in the form fl_dev_extract_select takes them (tests/extract_model.make_job): the start
+    distance is the job's own (EM.job_distance), the candidates reach the CPU back ends in raster order."""
+    out = [j for nf in (63, 31, 15, 7) for j in EM.rule_jobs(nf)]                    # n = nf - 1 (refused), nf, nf + 1, 2 nf - 1, 2 nf
+    out += [EM.sort_job(n, "three", "shuffled") for n in EM.SORT_COUNTS]               # every row of SORT_COUNTS, ties everywhere
+    out += [EM.sort_job(2049, "equal", "reversed"), EM.sort_job(4097, "distinct", "raster")]
+    out.append(EM.deep_jobs()[2])                                                      # n = nf = 63, colour: all taken
+    out.append(_block_job("all-taken-from-5.5", 8, 8, 63, 63, 2, 1008, 21))            # n = nf after the wraps 5.5 .. 0.5, ends on -0.5
+    out.append(_block_job("half-3.5-nf7", 4, 3, 12, 7, 2, 28, 22))                     # 3.5, 2.5, 1.5, 0.5
+    out.append(_block_job("half-2.5-nf7-all-taken", 3, 3, 7, 7, 2, 7, 23))             # n = nf: the last wrap leaves -0.5
+    out.append(_block_job("half-4.5-nf31", 7, 6, 40, 31, 2, 279, 24))
+    out.append(_block_job("ten-wraps", 28, 27, 756, 63, 0, 0, 25, kind="five"))        # colour: 756 / 63 + 1 = 13 on a dense block
+    out.append(_block_job("ten-wraps-equal", 28, 27, 756, 63, 0, 0, 26, kind="equal"))
+    # 3-4-5: the two best candidates are (5, 5) and (8, 9), the start distance is 30 / 7 + 1 = 5: 25 >= 25 keeps the second
+    rng = np.random.default_rng(27)
+    rest = rng.permutation(EM.block_rasters(40, 30, 20, 6, 6))[:28]
+    rest = rest[(rest != 5 * 40 + 5) & (rest != 9 * 40 + 8)]
+    xy = [(5, 5), (8, 9)] + [(int(r % 40), int(r // 40)) for r in rest]
+    s = np.concatenate([np.array([30000.0, 20000.0], np.float32), EM.scores("three", len(rest), rng)])
+    out.append(_select_job("three-four-five", 40, 30, xy, s, 7, seed=27))
+    return {j["name"]: j for j in out}
+
+
+def select_lists(job):
+    """(x, y, label, score) of a job in raster order: the order in which the reference meets its candidates."""
+    x, y, label = EM.job_xyl(job)
+    o = np.argsort(job["raster"], kind="stable")
+    return x[o], y[o], label[o], job["score"][o]
+
+
+def select_record(job, f):
+    x, y, label, score = select_lists(job)
+    par = np.array([job["w"], job["h"], job["num_features"], job["depth_mode"], job["area"]], np.int32)
+    return _with_inputs(_taken_or_refused(f), x, y, label, score, par, np.array([EM.job_distance(job)], np.float32))
+
+
+def compute_select(B, job):
+    return select_record(job, B.select_scattered_list(*select_lists(job), job["num_features"], EM.job_distance(job)))
+
+
+def check_select_jobs():
+    jobs = select_jobs()
+    ns = {len(j["raster"]) for j in jobs.values()}
+    assert set(EM.SORT_COUNTS) <= ns
+    for nf in (63, 31, 15, 7):
+        assert {nf - 1, nf} <= {len(j["raster"]) for j in jobs.values() if j["num_features"] == nf}
+    stats = {}
+    for name, j in jobs.items():
+        n, nf = len(j["raster"]), j["num_features"]
+        assert 1 <= nf <= 63 and (j["score"] != 0).all() and (j["raster"] >= 0).all() and (j["raster"] < j["w"] * j["h"]).all(), name
+        if j["depth_mode"]:
+            assert len(np.unique(j["raster"])) == n, name                      # a repeated pixel never ends from k + 0.5
+        if n >= nf:
+            fn = EM.select_model if n <= 800 else EM.select_walk
+            stats[name] = fn(*select_lists(j), nf, EM.job_distance(j))[1]
+    start = {k: float(EM.job_distance(jobs[k])) for k in jobs}
+    assert start["all-taken-from-5.5"] == 5.5 and start["half-3.5-nf7"] == 3.5 and start["half-2.5-nf7-all-taken"] == 2.5 and start["half-4.5-nf31"] == 4.5
+    assert start["all-taken-from-5.5"] - stats["all-taken-from-5.5"]["relaxations"] == -0.5 and stats["all-taken-from-5.5"]["wraps_after_take"] >= 1
+    assert start["half-2.5-nf7-all-taken"] - stats["half-2.5-nf7-all-taken"]["relaxations"] == -0.5
+    assert start["half-3.5-nf7"] - stats["half-3.5-nf7"]["relaxations"] == 0.5          # the pass at 0.5 fills the list
+    assert start["half-4.5-nf31"] - stats["half-4.5-nf31"]["relaxations"] == 0.5
+    assert stats["deep-all-taken"]["wraps_after_take"] >= 1
+    assert stats["ten-wraps"]["relaxations"] >= 10 and stats["ten-wraps-equal"]["relaxations"] >= 10
+    assert start["three-four-five"] == 5.0 and stats["three-four-five"]["kept_at_equal"] >= 1
+    # equal scores: the best score is shared, and the arrival order is not the raster order that must decide
+    for k in ("sort-2049-equal-reversed", "ten-wraps-equal", "sort-2049-three-shuffled"):
+        s = jobs[k]["score"]
+        assert (s == s.max()).sum() >= 2 and not np.array_equal(jobs[k]["raster"], np.sort(jobs[k]["raster"])), k
+
+
+# ---- extract_color: ColorGradientPyramid::extractTemplate on given images ----------------------------------------------
+def extract_mask(kind, w=EXW, h=EXH):
+    if kind == "none":
+        return None
+    m = np.zeros((h, w), np.uint8)
+    if kind == "rect":
+        m[20:70, 30:100] = 255
+    elif kind == "centre":                                  # mirror-symmetric about the middle column
+        m[20:76, 24:104] = 255
+    elif kind == "values":                                  # three non-zero values side by side: borders INSIDE the mask
+        m[20:70, 30:64], m[20:70, 64:100], m[40:50, 50:80] = 128, 7, 1
+    elif kind == "border":                                  # flush with the image's top-left and bottom-right corners
+        m[0:50, 0:60], m[60:h, 100:w] = 255, 255
+    elif kind == "hole":
+        m[20:70, 30:100] = 255
+        m[35:55, 50:80] = 0
+    elif kind == "line":                                    # one pixel wide: all of it is border, none survives a 5x5 erosion
+        m[48, 10:118], m[10:90, 64] = 255, 255
+    else:
+        raise ValueError(kind)
+    return m
+
+
+def extract_color_cases():
+    """(name, seed, mask kind, magnitude kind, num_features, exact candidate count or None)."""
+    out = [("color_edge_nomask", 30, "none", "edge", 63, None), ("color_edge_rect", 31, "rect", "edge", 63, None),
+           ("color_q0_rect_nf31", 32, "rect", "q0", 31, None), ("color_mask_values", 33, "values", "edge", 63, None),
+           ("color_mask_at_border_nf31", 34, "border", "edge", 31, None), ("color_mask_hole_nf15", 35, "hole", "edge", 15, None),
+           ("color_mask_line_nf31", 36, "line", "edge", 31, None), ("color_mask_line_nf7", 37, "line", "q0", 7, None)]
+    for nf in (63, 31):
+        out += [(f"color_exactly_{nf}_of_{nf}", 40 + nf, "none", "exact", nf, nf), (f"color_refused_{nf - 1}_of_{nf}", 41 + nf, "none", "exact", nf, nf - 1)]
+    out += [("color_exactly_63_in_rect", 38, "rect", "exact", 63, 63), ("color_refused_62_in_rect", 39, "rect", "exact", 63, 62)]
+    return out
+
+
+def extract_color_input(case):
+    """(quantized, magnitude, mask).  Magnitudes are what the reference's are: integers (sums of two squares) as floats."""
+    name, seed, mk, kind, nf, exact = case
+    rng = np.random.default_rng(seed)
+    q = (1 << rng.integers(0, 8, (EXH, EXW))).astype(np.uint8)
+    q[rng.random((EXH, EXW)) < 0.3] = 0
+    mask = extract_mask(mk)
+    if kind == "exact":                                     # 3025 = 55^2 everywhere (not a candidate), `exact` pixels above it
+        mag = np.full((EXH, EXW), 3025.0, np.float32)
+        ok = q > 0 if mask is None else (q > 0) & (mask > O.erode_rect(mask, 1))
+        idx = rng.permutation(np.flatnonzero(ok))[:exact]
+        mag.ravel()[idx] = rng.choice(np.array([3026.0, 4000.0, 9000.0], np.float32), exact)
+        assert len(idx) == exact
+    else:
+        mag = rng.choice(np.array([0.0, 3000.0, 3025.0, 3026.0, 4000.0, 20000.0], np.float32), (EXH, EXW))
+        if kind == "q0":
+            mag[q == 0] = np.float32(1.0e6)
+    return q, mag, mask
+
+
+def compute_extract_color(B, case):
+    q, mag, mask = extract_color_input(case)
+    out = _taken_or_refused(B.extract_template_color(q, mag, mask, STRONG, case[4]))
+    return _with_inputs(out, q, mag, np.zeros(0, np.uint8) if mask is None else mask, np.array([case[4]]))
+
+
+def check_extract_color_case(case):
+    name, seed, mk, kind, nf, exact = case
+    q, mag, mask = extract_color_input(case)
+    assert np.isin(q, [0, 1, 2, 4, 8, 16, 32, 64, 128]).all(), name
+    local = None if mask is None else np.where(mask > O.erode_rect(mask, 1), mask - O.erode_rect(mask, 1), 0)
+    inb = np.ones(q.shape, bool) if local is None else local > 0
+    cand = EM.color_candidates(q, mag, mask)
+    assert np.array_equal(cand, inb & (q > 0) & (mag > np.float32(3025.0))), name
+    if kind == "exact":
+        assert cand.sum() == exact and (inb & (q > 0) & (mag == 3025)).any(), name
+    else:
+        assert (inb & (q > 0) & (mag == 3025)).any() and (inb & (q > 0) & (mag == 3026)).any(), name     # either side of 55^2
+        assert cand.sum() > nf, name
+    if kind == "q0":
+        assert (inb & (q == 0) & (mag > 3025)).any(), name
+    if mk == "values":
+        er = O.erode_rect(mask, 1)
+        assert set(np.unique(mask)) - {0, 255} and ((local > 0) & (er > 0)).any(), name      # a border between two non-zero values
+    if mk == "border":
+        edge = np.zeros(q.shape, bool)
+        edge[0], edge[-1], edge[:, 0], edge[:, -1] = True, True, True, True
+        assert (edge & (mask > 0) & (local == 0)).any(), name                 # the replicated border made it interior
+    if mk == "hole":
+        assert local[34, 60] > 0 and local[55, 60] > 0 and mask[45, 60] == 0, name
+    if mk == "line":
+        assert np.array_equal(local, mask) and (O.erode_rect(mask, 2) == 0).all(), name
+
+
+# ---- extract_depth: DepthNormalPyramid::extractTemplate on given images ------------------------------------------------
+def extract_depth_cases():
+    """(name, seed, mask kind, extract_threshold, num_features, labels in use, layout)."""
+    every = (0, 1, 2, 3, 4, 5, 6, 7)
+    out = []
+    for thr, nf in ((2, 63), (1, 31), (0, 15)):
+        out.append((f"depth_thr{thr}_nomask_nf{nf}", 50 + thr, "none", thr, nf, every, "blocks"))
+        out.append((f"depth_thr{thr}_rect_nf{nf}", 53 + thr, "rect", thr, nf, every, "blocks"))
+    out.append(("depth_label_absent", 56, "hole", 2, 63, (0, 1, 2, 4, 5, 7), "blocks"))
+    out.append(("depth_equal_scores_across_labels", 57, "none", 2, 63, (2, 5), "halves"))
+    out.append(("depth_equal_scores_masked_nf7", 58, "centre", 1, 7, (1, 6), "halves"))
+    out.append(("depth_mask_values", 59, "values", 2, 31, every, "blocks"))
+    out.append(("depth_mask_at_border", 60, "border", 2, 63, every, "blocks"))
+    out.append(("depth_refused_mask_erodes_to_nothing", 61, "line", 0, 7, every, "blocks"))
+    out.append(("depth_refused_too_few_nomask", 62, "none", 2, 63, every, "speckle"))
+    return out
+
+
+def extract_depth_input(case):
+    name, seed, mk, thr, nf, labels, layout = case
+    rng = np.random.default_rng(seed)
+    if layout == "halves":                                  # two labels on mirror-image halves: equal counts, equal distances
+        n = np.full((EXH, EXW), 1 << labels[0], np.uint8)
+        n[:, EXW // 2:] = 1 << labels[1]
+    elif layout == "speckle":                               # no pixel two steps inside its label, bar one 5 x 5 block
+        n = (1 << rng.integers(0, 8, (EXH, EXW))).astype(np.uint8)
+        n[10:15, 10:15] = 4
+    else:
+        idx = rng.choice(np.array(labels), (EXH // 12 + 1, EXW // 16 + 1)).repeat(12, 0).repeat(16, 1)[:EXH, :EXW]
+        n = (1 << idx).astype(np.uint8)
+        n[:, 45:48], n[40:43, :] = 0, 255                   # background and shadow, also inside every mask
+    return n, extract_mask(mk)
+
+
+def compute_extract_depth(B, case):
+    n, mask = extract_depth_input(case)
+    out = _taken_or_refused(B.extract_template_depth(n, mask, case[3], case[4]))
+    return _with_inputs(out, n, np.zeros(0, np.uint8) if mask is None else mask, np.array([case[3], case[4]]))
+
+
+def check_extract_depth_case(case):
+    name, seed, mk, thr, nf, labels, layout = case
+    n, mask = extract_depth_input(case)
+    assert np.isin(n, [0, 1, 2, 4, 8, 16, 32, 64, 128, 255]).all(), name
+    cand, dist, area = EM.depth_candidates(n, mask, thr)
+    inside = np.ones(n.shape, bool) if mask is None else O.erode_rect(mask, 2) != 0
+    assert area == (n.size if mask is None else int(inside.sum())), name
+    if "refused" in name:
+        assert cand.sum() < nf, name
+        assert (area == 0) == (mk == "line") and (mk != "none" or cand.sum() > 0), name
+        return
+    assert cand.sum() >= nf, name
+    if layout == "blocks":
+        assert (inside & (n == 0)).any() and (inside & (n == 255)).any(), name            # labels 0 and 255 are there to be left out
+    lab = np.log2(np.where(cand, n, 1).astype(np.float64)).astype(np.int64)
+    if thr > 0:
+        assert (cand & (dist == thr)).any() and (inside & ~cand & (n != 0) & (n != 255) & (dist == thr - 1)).any() == (thr > 1), name
+    else:
+        assert dist[cand].min() >= 1, name                  # a labelled pixel is never at distance 0: no score can EQUAL threshold 0
+    counts = np.bincount(lab[cand], minlength=8)
+    if name == "depth_label_absent":
+        assert (counts == 0).sum() >= 2, name
+    if layout == "halves":
+        score = dist[cand] / counts[lab[cand]].astype(np.float32)
+        a, b = (score[lab[cand] == l] for l in labels)
+        assert counts[labels[0]] == counts[labels[1]] and a.max() == b.max() and len(np.intersect1d(a, b)) >= 2, name
+    if mk == "values":
+        assert set(np.unique(mask[inside])) - {0, 255}, name
+
+
+# ---- orientations: quantizedOrientations, quantized image and magnitude ------------------------------------------------
+def orientation_cases():
+    """(name, kind, w, h, seed)."""
+    return [("orient_ties_128x96", "ties", 128, 96, 70), ("orient_ties_97x61", "ties", 97, 61, 71), ("orient_weak_edge_128x96", "weak", 128, 96, 72),
+            ("orient_flat_64x48", "flat", 64, 48, 73), ("orient_noise_33x18", "noise", 33, 18, 74), ("orient_noise_97x61", "noise", 97, 61, 75),
+            ("orient_blocks_128x96", "blocks", 128, 96, 76)]
+
+
+def orientation_input(case):
+    name, kind, w, h, seed = case
+    rng = np.random.default_rng(seed)
+    if kind == "flat":
+        return np.full((h, w, 3), 93, np.uint8)
+    if kind == "noise":
+        return rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    if kind == "blocks":
+        return EM.block_noise_bgr(seed, w, h)
+    # low contrast: small integer gradients, so that different (dx, dy) of two channels often have one squared magnitude
+    # (5^2 + 0^2 = 3^2 + 4^2), and a quarter of the frame in grey, where all three channels tie
+    amp = 60 if kind == "ties" else 24
+    b = rng.integers(0, amp, ((h + 2) // 3, (w + 2) // 3, 3)).repeat(3, 0).repeat(3, 1)[:h, :w].astype(np.uint8) + 90
+    b[: h // 2, : w // 2] = b[: h // 2, : w // 2, :1]
+    return np.ascontiguousarray(b)
+
+
+def orientation_channels(bgr):
+    """Per channel the Sobel pair and the squared magnitude, as quantizedOrientations forms them (linemod.cpp:247-273)."""
+    sm = O.gaussian7_bgr(bgr)
+    dx, dy = O.sobel3_bgr(sm, False).astype(np.int32), O.sobel3_bgr(sm, True).astype(np.int32)
+    return dx, dy, dx * dx + dy * dy
+
+
+def fast_angles(dy, dx):
+    """cv::phase in degrees per element, through the oracle's orc_fast_atan2 on the distinct pairs."""
+    pairs, inv = np.unique(np.stack([dy.ravel(), dx.ravel()], 1), axis=0, return_inverse=True)
+    a = np.array([O.lib().orc_fast_atan2(float(p[0]), float(p[1])) for p in pairs], np.float32)
+    return a[inv.ravel()].reshape(dy.shape)
+
+
+def orientation_tie_counts(bgr, weak=10.0):
+    """Strong interior pixels per kind of tie among the channel magnitudes, and how many of them would get another angle bin
+    from the other tied channel: {(first, other): (pixels, pixels where the choice shows)}; (0, 1, 2) is the three-way tie."""
+    dx, dy, mag = orientation_channels(bgr)
+    m0, m1, m2 = mag[..., 0], mag[..., 1], mag[..., 2]
+    inner = np.zeros(m0.shape, bool)
+    inner[1:-1, 1:-1] = True
+    ang = fast_angles(dy, dx)
+    bins = np.rint(ang.astype(np.float64) * (16.0 / 360.0)).astype(np.int64) & 7
+    sel = {(0, 1): (m0 == m1) & (m0 > m2), (0, 2): (m0 == m2) & (m0 > m1), (1, 2): (m1 == m2) & (m1 > m0), (0, 1, 2): (m0 == m1) & (m1 == m2)}
+    out = {}
+    for k, s in sel.items():
+        s = s & inner & (mag[..., k[0]] > weak * weak)
+        shows = s & np.any([bins[..., k[0]] != bins[..., o] for o in k[1:]], axis=0)
+        out[k] = (int(s.sum()), int(shows.sum()))
+    return out
+
+
+def compute_orientations(B, case):
+    bgr = orientation_input(case)
+    q, mag = B.quantized_orientations_mag(bgr, 10.0)
+    return _with_inputs({"img_q": q, "img_mag": fbits(mag)}, bgr)
+
+
+def orientations_defined(bgr):
+    """No angle of the image is one of the two floats on which a float and a double product round apart (the header)."""
+    dx, dy, mag = orientation_channels(bgr)
+    return angles_unambiguous(fast_angles(dy, dx))
+
+
+def check_orientation_case(case):
+    name, kind, w, h, seed = case
+    bgr = orientation_input(case)
+    assert bgr.shape == (h, w, 3) and orientations_defined(bgr), name
+    dx, dy, mag = orientation_channels(bgr)
+    best = mag.max(2)
+    if kind == "flat":
+        assert best.max() == 0, name
+    if kind == "ties":
+        t = orientation_tie_counts(bgr)
+        assert all(t[k][0] >= 1 for k in t), (name, t)                          # every pairwise tie and the three-way tie, above weak^2
+        assert all(t[k][1] >= 1 for k in ((0, 1), (0, 2), (1, 2))), (name, t)   # and each pairwise one where the chain's choice shows
+    if kind == "weak":
+        # a pixel at exactly weak^2 = 100 that `>=` would let through: the vote passes there once the threshold is lowered
+        ang = fast_angles(np.take_along_axis(dy, mag.argmax(2)[..., None], 2)[..., 0], np.take_along_axis(dx, mag.argmax(2)[..., None], 2)[..., 0])
+        lo, at = O.hysteresis_gradient(best.astype(np.float32), ang, 99.5), O.hysteresis_gradient(best.astype(np.float32), ang, 100.0)
+        assert ((best == 100) & (lo != 0) & (at == 0)).any(), name
+
+
+# ---- add_template: Detector::addTemplate with the two default modalities -----------------------------------------------
+def _safe_depth(d):
+    d = d.copy()
+    for _ in range(64):
+        bad = normals_unsafe(d, 2000, 50)
+        if not bad.any():
+            return d
+        d[bad] = 65535
+    raise AssertionError("depth")
+
+
+@functools.lru_cache(maxsize=None)
+def add_template_cases():
+    """name -> dict(bgr, depth, mask, levels, expect): expect is None (a template), or the job l * 2 + m that fails first in
+    the reference's order (all colour levels, then all depth levels)."""
+    out = {}
+
+    def add(name, seed, w, h, levels, mask, expect=None):
+        out[name] = dict(bgr=EM.block_noise_bgr(seed, w, h), depth=_safe_depth(EM.tilted_patch_depth(seed, w, h)), mask=mask, levels=levels, expect=expect)
+
+    for levels, (w, h) in ((1, (EXW, EXH)), (2, (EXW, EXH)), (3, (160, 120))):
+        add(f"add_L{levels}_nomask", 100 + levels, w, h, levels, None)
+        add(f"add_L{levels}_mask_odd", 103 + levels, w, h, levels, EM.rect_mask(w, h, 9, 7, w - 30, h - 24))
+        add(f"add_L{levels}_mask_even", 106 + levels, w, h, levels, EM.rect_mask(w, h, 12, 10, w - 30, h - 24))
+    # masks of the extract_color / extract_depth groups on whole views (the kernels take no quantized images from a caller)
+    for seed, mk in ((93, "values"), (90, "border"), (95, "hole")):
+        add(f"add_L2_mask_{mk}", seed, EXW, EXH, 2, extract_mask(mk))
+    add("add_L2_refused_depth_mask_line", 93, EXW, EXH, 2, extract_mask("line"), expect=1)       # colour passes on both levels, depth has no area
+    # a job at exactly its rule, one below (refused) and one above, every other job with candidates to spare (96 x 80, two levels)
+    for job, target in EM.THRESHOLD_CASES:
+        c = EM.threshold_case(job, target)
+        assert c is not None, (job, target)
+        nf = 63 >> (job // 2)
+        out[f"add_job{job}_{'colour' if job % 2 == 0 else 'depth'}_L{job // 2}_{target}_of_{nf}"] = dict(
+            bgr=c["bgr"], depth=c["depth"], mask=c["mask"], levels=2, expect=job if target < nf else None, counts=tuple(c["counts"]))
+    return out
+
+
+def add_template_record(case, r):
+    if r is None:
+        out = {"refused": np.ones(1, np.uint8)}
+    else:
+        t, feats, bb = r
+        out = {"templates": np.stack([np.asarray(t[k], np.int32) for k in ("width", "height", "offset_x", "offset_y", "pyramid_level", "feat_count")], 1),
+               "features": feats3(list(feats)), "bb": np.array(bb, np.int32)}
+    mask = np.zeros(0, np.uint8) if case["mask"] is None else case["mask"]
+    return _with_inputs(out, case["bgr"], case["depth"], mask, np.array([case["levels"]]))
+
+
+def compute_add_template(B, case):
+    return add_template_record(case, B.add_template(case["bgr"], case["depth"], case["mask"], case["levels"]))
+
+
+def check_add_template_cases():
+    cases = add_template_cases()
+    parity = set()
+    for name, c in cases.items():
+        h, w = c["depth"].shape
+        assert c["bgr"].shape == (h, w, 3) and 1 <= c["levels"] <= 3, name
+        assert not normals_unsafe(c["depth"], 2000, 50).any(), name
+        src = c["bgr"]
+        for l in range(c["levels"]):
+            src = src if l == 0 else O.pyrdown_bgr(src)
+            assert orientations_defined(src), (name, l)
+        counts = EM.candidate_counts(c["bgr"], c["depth"], c["mask"], c["levels"])
+        th = EM.thresholds(c["levels"])
+        failing = [k for k in list(range(0, 2 * c["levels"], 2)) + list(range(1, 2 * c["levels"], 2)) if counts[k] < th[k]]
+        assert (failing[0] if failing else None) == c["expect"], (name, counts, c["expect"])
+        if "counts" in c:
+            assert tuple(counts) == c["counts"], name
+        r = O.add_template(c["bgr"], c["depth"], c["mask"], c["levels"])
+        if r is not None:
+            t, feats, bb = r
+            raw_x = min(int((f["x"] + t[k]["offset_x"]).min()) << int(t[k]["pyramid_level"]) for k, f in enumerate(feats))
+            raw_y = min(int((f["y"] + t[k]["offset_y"]).min()) << int(t[k]["pyramid_level"]) for k, f in enumerate(feats))
+            assert bb[0] == raw_x - raw_x % 2 and bb[1] == raw_y - raw_y % 2, name
+            parity |= {("x", raw_x % 2), ("y", raw_y % 2)}
+    assert parity == {("x", 0), ("x", 1), ("y", 0), ("y", 1)}                   # min_x % 2 == 1 decides both ways, and min_y
+    expects = {c["expect"] for c in cases.values()}
+    assert {None, 0, 1, 2, 3} <= expects                                          # colour level 0, depth level 0, level 1 only (colour, depth)
+    assert {(c["levels"], c["mask"] is None) for c in cases.values() if c["expect"] is None} >= {(l, m) for l in (1, 2, 3) for m in (True, False)}
+
+
+def check_extract_cases():
+    check_select_jobs()
+    for c in extract_color_cases():
+        check_extract_color_case(c)
+    for c in extract_depth_cases():
+        check_extract_depth_case(c)
+    for c in orientation_cases():
+        check_orientation_case(c)
+    check_add_template_cases()
+
+
+class OracleExtractBackend:
+    """oracle_py under the method names of reference_py.Ref."""
+
+    def __init__(self, O_):
+        for k in ("select_scattered_list", "extract_template_color", "extract_template_depth", "quantized_orientations_mag", "add_template"):
+            setattr(self, k, getattr(O_, k))
+
+
+def extract_groups():
+    """group -> (list of (name, case), compute): the case list of template extraction, in one place."""
+    return {
+        "select": (list(select_jobs().items()), compute_select),
+        "extract_color": ([(c[0], c) for c in extract_color_cases()], compute_extract_color),
+        "extract_depth": ([(c[0], c) for c in extract_depth_cases()], compute_extract_depth),
+        "orientations": ([(c[0], c) for c in orientation_cases()], compute_orientations),
+        "add_template": (list(add_template_cases().items()), compute_add_template),
+    }
+
+
+def is_image(key, value):
+    """What tests/golden/reference_extract.npz keeps as a digest: the images (keys img_*); everything else in full."""
+    return key.startswith("img_")

@@ -131,6 +131,53 @@ class Ref:
         self._ok(self.l.ref_crop_templates(_p(t), len(t), _p(f), bb))
         return t, f, tuple(bb)
 
+    # ---- template extraction: 1 = features, 0 = refused (too few candidates), -1 = the reference threw ----
+    def _taken(self, rc, out):
+        if rc < 0:
+            raise AssertionError("reference CV_Assert")
+        return out if rc else None
+
+    def select_scattered_list(self, x, y, label, score, num_features, distance):
+        x, y, label = (np.ascontiguousarray(a, np.int32) for a in (x, y, label))
+        score = np.ascontiguousarray(score, np.float32)
+        out = np.zeros(num_features, FEAT_DTYPE)
+        return self._taken(self.l.ref_select_scattered_list(_p(x), _p(y), _p(label), _p(score), len(x), num_features, C.c_float(distance),
+                                                            _p(out)), out)
+
+    def extract_template_color(self, quantized, magnitude, mask, strong_threshold, num_features):
+        q = np.ascontiguousarray(quantized, np.uint8)
+        mg = np.ascontiguousarray(magnitude, np.float32)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        out = np.zeros(num_features, FEAT_DTYPE)
+        return self._taken(self.l.ref_extract_template_color(_p(q), _p(mg), None if mk is None else _p(mk), q.shape[1], q.shape[0],
+                                                             C.c_float(strong_threshold), num_features, _p(out)), out)
+
+    def extract_template_depth(self, normal, mask, extract_threshold, num_features):
+        q = np.ascontiguousarray(normal, np.uint8)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        out = np.zeros(num_features, FEAT_DTYPE)
+        return self._taken(self.l.ref_extract_template_depth(_p(q), None if mk is None else _p(mk), q.shape[1], q.shape[0], extract_threshold,
+                                                             num_features, _p(out)), out)
+
+    def quantized_orientations_mag(self, bgr, weak_threshold=10.0):
+        b = np.ascontiguousarray(bgr, np.uint8)
+        out, mag = np.zeros(b.shape[:2], np.uint8), np.zeros(b.shape[:2], np.float32)
+        self._ok(self.l.ref_quantized_orientations(_p(b), b.shape[1], b.shape[0], C.c_float(weak_threshold), _p(out), _p(mag)))
+        return out, mag
+
+    def add_template(self, bgr, depth, mask, levels):
+        """As oracle_py.add_template: (templates, features per template, bb), or None where addTemplate returned -1."""
+        b = np.ascontiguousarray(bgr, np.uint8)
+        d = np.ascontiguousarray(depth, np.uint16)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        h, w = d.shape
+        t = np.zeros(levels * 2, TEMPL_DTYPE)
+        f = np.zeros(levels * 2 * 63, FEAT_DTYPE)
+        bb = (C.c_int * 4)()
+        if self.l.ref_add_template(_p(b), _p(d), None if mk is None else _p(mk), w, h, levels, _p(t), _p(f), bb):
+            return None
+        return t, [f[t[k]["feat_begin"]:t[k]["feat_begin"] + t[k]["feat_count"]].copy() for k in range(levels * 2)], tuple(bb)
+
     @staticmethod
     def _ok(rc):
         if rc:

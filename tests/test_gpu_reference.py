@@ -7,11 +7,19 @@ The ICP half the same way (tests/golden/reference_icp.npz and oracle/_ref/libfea
 common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp): FL_ICP_PARITY under every build of the ICP kernels that test_gpu_icp.py's
 `width` fixture selects, on cloud sizes on the wave and workgroup strides of those builds; ctx.detection, ctx.depth_to_3d and
 fl_nms.  Every comparison is equality of bit patterns or of ints.
+
+Template extraction the same way (tests/golden/reference_extract.npz, RC.extract_groups): fl_dev_extract_select on every `select`
+case, ctx.quantized_orientations on the `orientations` cases, ctx.extract_template_pyramid and extract_template_batch on the
+`add_template` cases.  No entry point of fl_extract.hip takes quantized images from a caller, so the `extract_color` and
+`extract_depth` cases do not run here as they are: their edges are reached through whole views instead, the add_template cases
+with those groups' masks (values other than 255, flush with the image border, a hole, a one-pixel line) and the views with a
+job at exactly its rule, one below and one above.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
+import torch
 
 import reference_cases as RC
 import reference_py as R
@@ -23,6 +31,7 @@ from util import golden
 pytestmark = pytest.mark.gpu
 GROUPS = RC.groups()
 ICP_GROUPS = RC.icp_groups()
+EXTRACT_GROUPS = RC.extract_groups()
 
 
 def _detector(ctx, case):
@@ -241,3 +250,114 @@ def test_icp_half_equals_live_reference(ctx, group):
     for name, case in cases:
         diff = RC.same(fn(KernelIcpBackend(ctx), case), fn(ref, case))
         assert diff is None, (name, diff)
+
+
+# ---- template extraction ---------------------------------------------------------------------------------------------------
+FILL = -7
+
+
+class KernelExtractBackend:
+    """The HIP entry points under the method names of reference_py.Ref, for the groups the kernels have an entry for."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def select_job(self, job):
+        """fl_dev_extract_select on one job, candidates in the job's own arrival order: the features, or None (refused)."""
+        n_out, feats, keys = self.ctx.dev_extract_select([job], fill=FILL)[0]
+        if n_out == -1:
+            assert (feats == FILL).all()
+            return None
+        assert n_out == job["num_features"] and (feats[n_out:] == FILL).all()
+        return feats[:n_out]
+
+    @staticmethod
+    def as_record(got):
+        """(templates, features per template, bb) of reference_cases.add_template_record from a kernel result."""
+        if got is None:
+            return None
+        tl, bb = got
+        t = {k: np.array([d[k] for d in tl], np.int32) for k in ("width", "height", "offset_x", "offset_y", "pyramid_level")}
+        t["feat_count"] = np.array([len(d["features"]) for d in tl], np.int32)
+        return t, [np.asarray(d["features"], np.int32).reshape(-1, 3) for d in tl], bb
+
+    def add_template(self, bgr, depth, mask, levels):
+        return self.as_record(self.ctx.extract_template_pyramid(bgr, depth, mask, levels))
+
+
+def _extract_names(group):
+    return [n for n, _ in EXTRACT_GROUPS[group][0]]
+
+
+def _extract_case(group, name):
+    return dict(EXTRACT_GROUPS[group][0])[name]
+
+
+def _against_extract_record(out, group, name):
+    diff = RC.same_as_record(out, golden("reference_extract.npz"), group, name, RC.is_image)
+    assert diff is None, (name, diff)
+
+
+@pytest.mark.parametrize("name", _extract_names("select"))
+def test_extract_select_equals_recorded_reference(ctx, name):
+    """std::stable_sort + selectScatteredFeatures: the features, or the refusal where the list is shorter than num_features."""
+    job = _extract_case("select", name)
+    _against_extract_record(RC.select_record(job, KernelExtractBackend(ctx).select_job(job)), "select", name)
+
+
+@pytest.mark.parametrize("name", _extract_names("orientations"))
+def test_quantized_orientations_equal_recorded_reference(ctx, name):
+    """The quantized image of quantizedOrientations (the entry point returns no magnitude)."""
+    case = _extract_case("orientations", name)
+    rec = RC.record_parts(golden("reference_extract.npz"), "orientations", name, ["__in__", "img_mag", "img_q"])
+    bgr = RC.orientation_input(case)
+    assert RC._with_inputs({}, bgr)["__in__"].tobytes() == rec["__in__"]
+    assert RC.digest(ctx.quantized_orientations(bgr, 10.0)).tobytes() == rec["img_q"]
+
+
+@pytest.mark.parametrize("name", _extract_names("add_template"))
+def test_extract_template_pyramid_equals_recorded_reference(ctx, name):
+    """Detector::addTemplate: templates, features and bounding box in full, or the refusal."""
+    _against_extract_record(RC.compute_add_template(KernelExtractBackend(ctx), _extract_case("add_template", name)), "add_template", name)
+
+
+def _batches():
+    """The add_template cases by frame size and level count: one fl_extract_template_batch call takes one of each."""
+    out = {}
+    for name, c in EXTRACT_GROUPS["add_template"][0]:
+        out.setdefault((c["depth"].shape[1], c["depth"].shape[0], c["levels"]), []).append((name, c))
+    return out
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+def test_extract_template_batch_equals_recorded_reference(ctx, mem):
+    """Every add_template case of one geometry in one call, the refused views among the others, from host and from device frames."""
+    seen = refused_among_others = 0
+    for (w, h, levels), cases in _batches().items():
+        bgrs, depths, masks = ([c[k] for _, c in cases] for k in ("bgr", "depth", "mask"))
+        if mem == "device":
+            bgrs, depths = [torch.from_numpy(b).cuda() for b in bgrs], [torch.from_numpy(d).cuda() for d in depths]
+            masks = [None if m is None else torch.from_numpy(m).cuda() for m in masks]
+            torch.cuda.synchronize()
+        got = ctx.extract_template_batch(bgrs, depths, masks, levels, mem=L.FL_MEM_DEVICE if mem == "device" else L.FL_MEM_HOST)
+        assert len(got) == len(cases)
+        for (name, c), g in zip(cases, got):
+            _against_extract_record(RC.add_template_record(c, KernelExtractBackend.as_record(g)), "add_template", name)
+        none = [g is None for g in got]
+        refused_among_others += any(none[i] and not none[i - 1] and not none[i + 1] for i in range(1, len(none) - 1))
+        seen += len(cases)
+    assert seen == len(EXTRACT_GROUPS["add_template"][0]) and refused_among_others >= 1
+
+
+@pytest.mark.parametrize("group", ["select", "orientations", "add_template"])
+def test_extraction_equals_live_reference(ctx, group):
+    """The same cases against the compiled reference itself."""
+    ref, K = R.require(False), KernelExtractBackend(ctx)
+    for name, case in EXTRACT_GROUPS[group][0]:
+        if group == "select":
+            a, b = RC.select_record(case, K.select_job(case)), RC.compute_select(ref, case)
+        elif group == "orientations":
+            a, b = {"img_q": ctx.quantized_orientations(RC.orientation_input(case), 10.0)}, {"img_q": RC.compute_orientations(ref, case)["img_q"]}
+        else:
+            a, b = RC.compute_add_template(K, case), RC.compute_add_template(ref, case)
+        assert RC.same(a, b) is None, (name, RC.same(a, b))

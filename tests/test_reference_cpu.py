@@ -13,6 +13,12 @@ brute-force search, against the reference's compiled ICP.cpp, common.cpp, depth_
 or of ints: R, T, dist_mean and px_ratio of every prefix icp_it_thr = 0 .. N (the prefixes are the per-iteration states), `iter`
 on exit, n_points, the helpers' clouds and pair lists, the back-projected clouds, the NMS winners.  Exact nearest-neighbour ties
 (names starting with tie_) are DEFINED BY THE STAND-IN'S RULE (lowest index), UNSPECIFIED IN FLANN, and a group of their own.
+
+Template extraction the same way (RC.extract_groups; tests/golden/reference_extract.npz): the sort and scattered selection on
+lists, the two extractTemplate methods on given images, quantizedOrientations with its magnitude, Detector::addTemplate.  Both
+builds compile the same text there (it has no SSE branch), and both are compared.  Pinned: the reference's comparisons, start
+distances, relaxation loop, stable sort, score division, channel choice and cropping.  NOT pinned: GaussianBlur, Sobel, phase,
+pyrDown, resize, erode and distanceTransform, which the stand-in delegates to the oracle (oracle/ref/ref_harness.cpp).
 """
 import numpy as np
 import pytest
@@ -25,6 +31,10 @@ GROUPS = RC.groups()
 LIVE = [pytest.param(simd, g, name, id=f"{'simd' if simd else 'scalar'}-{name}") for simd in (False, True)
         for g, (cases, _) in GROUPS.items() for name, c in cases if not simd or RC.simd_takes(g, c)]
 ALL = [pytest.param(g, name, id=name) for g, (cases, _) in GROUPS.items() for name, _ in cases]
+EXTRACT_GROUPS = RC.extract_groups()
+EXTRACT_ALL = [pytest.param(g, name, id=name) for g, (cases, _) in EXTRACT_GROUPS.items() for name, _ in cases]
+EXTRACT_LIVE = [pytest.param(simd, g, name, id=f"{'simd' if simd else 'scalar'}-{name}") for simd in (False, True)
+                for g, (cases, _) in EXTRACT_GROUPS.items() for name, _ in cases]
 ICP_GROUPS = RC.icp_groups()
 ICP_ALL = [pytest.param(kd, g, name, id=f"{'kdtree' if kd else 'brute'}-{name}") for kd in (True, False)
            for g, (cases, _) in ICP_GROUPS.items() for name, _ in cases]
@@ -81,6 +91,35 @@ def test_icp_record_holds_exactly_the_case_list():
     assert sorted(rec.files) == sorted(f"{g}/{name}" for g, (cases, _) in ICP_GROUPS.items() for name, _ in cases)
 
 
+def _extract_case(g, name):
+    cases, fn = EXTRACT_GROUPS[g]
+    return dict(cases)[name], fn
+
+
+@pytest.mark.parametrize("simd,group,name", EXTRACT_LIVE)
+def test_extract_oracle_equals_compiled_reference(oracle, simd, group, name):
+    case, fn = _extract_case(group, name)
+    a, b = fn(RC.OracleExtractBackend(oracle), case), fn(R.require(simd), case)
+    assert RC.same(a, b) is None, (name, RC.same(a, b))
+
+
+@pytest.mark.parametrize("group,name", EXTRACT_ALL)
+def test_extract_oracle_equals_recorded_reference(oracle, group, name):
+    case, fn = _extract_case(group, name)
+    diff = RC.same_as_record(fn(RC.OracleExtractBackend(oracle), case), golden("reference_extract.npz"), group, name, RC.is_image)
+    assert diff is None, (name, diff)
+
+
+def test_extract_record_holds_exactly_the_case_list():
+    rec = golden("reference_extract.npz")
+    assert sorted(rec.files) == sorted(f"{g}/{name}" for g, (cases, _) in EXTRACT_GROUPS.items() for name, _ in cases)
+    # a refusal is part of the record: two members, the input digest and the one byte of `refused`
+    refused = [k for k in rec.files if RC.record_lengths(rec[k]) == [32, 1]]
+    assert len(refused) >= 12 and all("refused" in k or "_of_" in k or k.startswith("select/rule-") for k in refused), refused
+    full = [k for k in rec.files if k.startswith(("select/", "extract_")) and k not in refused]
+    assert all(RC.record_lengths(rec[k])[1] % 12 == 0 and RC.record_lengths(rec[k])[1] >= 7 * 12 for k in full)   # feature lists in full
+
+
 @pytest.mark.parametrize("group", ["spread", "lut", "linearize", "similarity", "local", "total", "match"])
 def test_scalar_and_simd_builds_agree(group):
     """The functions with SSE branches, on every case both builds take."""
@@ -122,6 +161,9 @@ def test_inputs_keep_the_reference_defined(oracle):
     for c in RC.depth3d_cases():
         d = RC.depth3d_input(c)
         assert d.shape == (c[2], c[1]) and {0, 1, 65535} <= set(d.ravel().tolist()), c[0]
+    # template extraction: every case is on the edge it is named for, and none leaves the reference undefined (one check per
+    # case, from tests/extract_model.py and the oracle's stage functions: reference_cases.check_extract_cases)
+    RC.check_extract_cases()
 
 
 @pytest.mark.parametrize("simd", [False, True], ids=["scalar", "simd"])
