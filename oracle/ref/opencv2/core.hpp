@@ -10,6 +10,13 @@
 //    step1(), create, zeros, clone, copyTo, setTo, size(), total(), empty(), ROI operator()(Rect)), Mat_<T>, Size, Point,
 //    Rect, Vec3b, Ptr/makePtr, String, CV_Assert/CV_Error (throw cv::Exception), alignSize, checkHardwareSupport,
 //    OutputArrayOfArrays/noArray() with needed/create/getMatRef.  The arithmetic linemod.cpp does on them is its own C++.
+//    For the OpenCV-typed adapter header and the caller that runs it against the compiled reference
+//    (tests/dropin/tu_cv_caller.cpp): Mat(rows, cols, type, data, step) over caller memory (no ownership, no guard),
+//    Mat::isContinuous(), Mat::copyTo(OutputArray) for a Mat target, Error::StsError and Exception::code, Scalar(b, g, r)
+//    and CV_RGB, convertTo CV_32F -> CV_64F and CV_64F -> CV_64F with alpha 1 (exact), empty forwarding headers for what
+//    linemod_if.h includes (imgproc/imgproc_c.h, objdetect.hpp, highgui.hpp), and a cv::circle (opencv2/imgproc.hpp) that
+//    draws nothing and appends its arguments to a process-wide log: the calls are compared, OpenCV's rasterisation is
+//    not restated.  FileStorage stays declared only.
 //
 //  * THE OPERATIONS the pinned functions call are defined here, because each has one possible answer:
 //      - Mat::convertTo(CV_8U -> CV_16U) widens every byte (addSimilarities with one modality, linemod.cpp:1326);
@@ -143,12 +150,13 @@ inline FealessRefCounters &fealess_ref_counters()
 
 class Exception : public std::runtime_error {
  public:
-  explicit Exception(const std::string &what_) : std::runtime_error(what_) {}
+  explicit Exception(const std::string &what_, int code_ = 0) : std::runtime_error(what_), code(code_) {}
+  int code;  // the cv::Error::Code it was raised with
 };
-namespace Error { enum Code { StsBadArg = -5, StsAssert = -215 }; }
+namespace Error { enum Code { StsError = -2, StsBadArg = -5, StsAssert = -215 }; }
 [[noreturn]] inline void error(int code, const String &msg, const char *file, int line)
 {
-  throw Exception(String(file) + ":" + std::to_string(line) + ": error " + std::to_string(code) + ": " + msg);
+  throw Exception(String(file) + ":" + std::to_string(line) + ": error " + std::to_string(code) + ": " + msg, code);
 }
 
 #define CV_Error(code, msg) cv::error((code), (msg), __FILE__, __LINE__)
@@ -194,6 +202,7 @@ struct Scalar {
   double val[4];
   Scalar(double a = 0, double b = 0, double c = 0, double d = 0) { val[0] = a; val[1] = b; val[2] = c; val[3] = d; }
 };
+#define CV_RGB(r, g, b) cv::Scalar((b), (g), (r), 0)
 
 enum BorderTypes { BORDER_CONSTANT = 0, BORDER_REPLICATE = 1, BORDER_REFLECT = 2, BORDER_REFLECT_101 = 4, BORDER_DEFAULT = 4 };
 
@@ -347,6 +356,11 @@ class Mat {
   Mat() : rows(0), cols(0), data(NULL), step(0), size(this), type_(0) {}
   Mat(int r, int c, int type) : rows(0), cols(0), data(NULL), step(0), size(this), type_(0) { create(r, c, type); }
   Mat(Size s, int type) : rows(0), cols(0), data(NULL), step(0), size(this), type_(0) { create(s.height, s.width, type); }
+  // a header over the caller's memory: no ownership, no guard behind it; step 0 = rows back to back
+  Mat(int r, int c, int type, void *data_, size_t step_ = 0)
+      : rows(r), cols(c), data(static_cast<uchar *>(data_)), step(step_ ? step_ : (size_t)c * depthSize(type) * CV_MAT_CN(type)), size(this), type_(type)
+  {
+  }
   Mat(const Mat &m) : rows(m.rows), cols(m.cols), data(m.data), step(m.step), size(this), type_(m.type_), buf_(m.buf_) {}
   Mat &operator=(const Mat &m)
   {
@@ -385,6 +399,7 @@ class Mat {
   size_t step1() const { return step / elemSize1(); }
   size_t total() const { return (size_t)rows * cols; }
   bool empty() const { return data == NULL || rows == 0 || cols == 0; }
+  bool isContinuous() const { return rows <= 1 || step == (size_t)cols * elemSize(); }
 
   // A fresh buffer unless the shape and type already fit (as cv::Mat::create).  Zero-filled, 64-byte aligned, followed
   // by a zeroed guard of two rows + 4 KiB (see the header comment: quirk Q2).
@@ -473,12 +488,13 @@ class Mat {
   // defined for CV_8U -> CV_16U (alpha 1) and CV_32F -> CV_8U (any alpha), beta 0, one channel (see the header comment),
   // and for what the ICP sources convert: a copy (same depth, alpha 1), CV_64F -> CV_32F (alpha 1) and CV_16U -> CV_32F
   // with a scale, float(v) * float(alpha): the scale narrowed to the destination's type before the product, which is
-  // what a cv::Mat::convertTo to CV_32F does.  Any other conversion is OpenCV's
+  // what a cv::Mat::convertTo to CV_32F does; and CV_32F -> CV_64F (alpha 1), which is exact (the adapter header widens
+  // K with it).  Any other conversion is OpenCV's
   void convertTo(Mat &dst, int rtype, double alpha = 1, double beta = 0) const
   {
     const int ddepth = CV_MAT_DEPTH(rtype), cn = channels();
     if (beta == 0 && !empty() && ((ddepth == depth() && alpha == 1) || (depth() == CV_64F && ddepth == CV_32F && alpha == 1) ||
-                                  (depth() == CV_16U && ddepth == CV_32F))) {
+                                  (depth() == CV_32F && ddepth == CV_64F && alpha == 1) || (depth() == CV_16U && ddepth == CV_32F))) {
       Mat src(*this);                                      // dst may be *this
       dst.create(src.rows, src.cols, CV_MAKETYPE(ddepth, cn));
       const float a = (float)alpha;
@@ -486,6 +502,7 @@ class Mat {
         for (int c = 0; c < src.cols * cn; ++c) {
           if (ddepth == src.depth()) std::memmove(dst.ptr(r) + src.elemSize1() * c, src.ptr(r) + src.elemSize1() * c, src.elemSize1());
           else if (src.depth() == CV_64F) dst.ptr<float>(r)[c] = (float)src.ptr<double>(r)[c];
+          else if (src.depth() == CV_32F) dst.ptr<double>(r)[c] = (double)src.ptr<float>(r)[c];
           else dst.ptr<float>(r)[c] = (float)src.ptr<ushort>(r)[c] * a;
         }
       return;
@@ -631,6 +648,7 @@ class _OutputArray : public _InputArray {
   }
   void create(Size s, int type) const { create(s.height, s.width, type); }
   Mat &getMatRef(int i) const { return (*vec_)[i]; }
+  Mat *fealessMatTarget() const { return out_; }  // the Mat this output stands for, NULL for a vector or for nothing
 
  private:
   std::vector<Mat> *vec_;
@@ -644,7 +662,11 @@ inline const _OutputArray &noArray()
   static const _OutputArray none;
   return none;
 }
-inline void Mat::copyTo(const _OutputArray &) const { FEALESS_REF_UNPINNED("Mat::copyTo(OutputArray)"); }
+inline void Mat::copyTo(const _OutputArray &dst) const
+{
+  if (!dst.fealessMatTarget()) FEALESS_REF_UNPINNED("Mat::copyTo(OutputArray) (other than a Mat target)");
+  copyTo(*dst.fealessMatTarget());
+}
 
 // ---- defined for the ICP sources -----------------------------------------------------------------------------------
 // Mat * Mat on one-channel CV_32F: cv::gemm keeps double accumulators for float matrices, k ascending
@@ -731,6 +753,7 @@ class FileStorage {
  public:
   enum Mode { READ = 0, WRITE = 1 };
   FileStorage(const String &, int) { FEALESS_REF_UNPINNED("FileStorage"); }
+  FileNode operator[](const char *) const { FEALESS_REF_UNPINNED("FileStorage"); }
   FileNode root() const { FEALESS_REF_UNPINNED("FileStorage"); }
 };
 template <typename T> inline FileStorage &operator<<(FileStorage &, const T &) { FEALESS_REF_UNPINNED("FileStorage"); }

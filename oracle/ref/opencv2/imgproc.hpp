@@ -119,5 +119,24 @@ inline void distanceTransform(const Mat &src, Mat &dst, int distance_type, int m
 
 inline void cvtColor(const Mat &, Mat &, int) { FEALESS_REF_UNPINNED("cvtColor"); }
 
+// cv::circle draws NOTHING here: it appends its arguments to a process-wide log that the caller reads and clears
+// (tests/dropin/tu_cv_caller.cpp compares the order and arguments of drawResponse's calls; rasterisation is OpenCV's)
+struct FealessCircleCall {
+  Point center;
+  int radius;
+  Scalar color;
+  int thickness;
+};
+inline std::vector<FealessCircleCall> &fealess_circle_log()
+{
+  static std::vector<FealessCircleCall> log;
+  return log;
+}
+inline void circle(Mat &, Point center, int radius, const Scalar &color, int thickness = 1, int = 8, int = 0)
+{
+  const FealessCircleCall c = {center, radius, color, thickness};
+  fealess_circle_log().push_back(c);
+}
+
 }  // namespace cv
 #endif

@@ -14,7 +14,9 @@ symbols of a CadReco caller compiled against DIR/CadReco's headers (cadreco_refe
 the outputs of DIR/linemod/linemod.cpp, compiled against the stand-in of oracle/ref, on the cases of tests/reference_cases.py
 (reference_linemod.npz), and those of DIR/ICP's ICP.cpp, common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp, compiled the same
 way, on the ICP cases of that module (reference_icp.npz: results only, written with fixed time stamps so that a second run gives
-the same bytes), and those of linemod.cpp's template extraction on the extraction cases (reference_extract.npz, same writer).
+the same bytes), and those of linemod.cpp's template extraction on the extraction cases (reference_extract.npz, same writer),
+and those of the OpenCV-typed caller tests/dropin/tu_cv_caller.cpp built against DIR's headers and compiled code on the cases of
+tests/cv_caller_cases.py (reference_cv_caller.npz, same writer).
 """
 import io
 import os
@@ -132,6 +134,7 @@ def reference_fixtures(ref):
     reference_linemod_fixture(ref)
     reference_icp_fixture(ref)
     reference_extract_fixture(ref)
+    reference_cv_caller_fixture(ref)
 
 
 def reference_linemod_fixture(ref):
@@ -205,6 +208,24 @@ def reference_extract_fixture(ref):
     path = os.path.join(HERE, "reference_extract.npz")
     save_npz_reproducibly(path, rec)
     print("reference extract fixture:", len(rec), "entries,", os.path.getsize(path) // 1024, "KiB")
+
+
+def reference_cv_caller_fixture(ref):
+    """Outputs of tests/dropin/tu_cv_caller.cpp compiled against the reference's own headers and compiled code
+    (oracle/_ref/ref_cv_caller, built here from `ref`) on the case list of tests/cv_caller_cases.py -> reference_cv_caller.npz.
+    Case outputs only (cv_caller_cases.recorded): match lists in canonical order, the long one as count, first and last 64
+    entries and a digest; images above 8 KiB as digests; everything else in full."""
+    import cv_caller_cases as CC
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle", "ref")], env=dict(os.environ, FEALESS_REFERENCE_ROOT=os.path.abspath(ref)))
+    tmp = tempfile.mkdtemp()
+    try:
+        CC.write_case_dir(os.path.join(tmp, "in"), O)
+        rec = CC.recorded(CC.run_caller(CC.REF_CALLER, os.path.join(tmp, "in"), os.path.join(tmp, "out")))
+    finally:
+        shutil.rmtree(tmp)
+    path = os.path.join(HERE, "reference_cv_caller.npz")
+    save_npz_reproducibly(path, rec)
+    print("reference cv caller fixture:", len(rec), "entries,", os.path.getsize(path) // 1024, "KiB")
 
 
 if __name__ == "__main__":
