@@ -107,6 +107,14 @@ class VerifiedInstanceResult(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class SceneParams(C.Structure):        # fl_scene_params
+    _fields_ = [("verify", VerifyParams), ("max_shared_ratio", C.c_float), ("min_shared_px", C.c_int32)]
+
+
+class SceneResult(C.Structure):        # fl_scene_result, 80 bytes
+    _fields_ = [("verify", VerifyResult), ("kept", C.c_int32), ("order", C.c_int32), ("rival", C.c_int32), ("n_shared", C.c_int32)]
+
+
 class Mesh(C.Structure):               # fl_mesh
     _fields_ = [("vertices", C.c_void_p), ("triangles", C.c_void_p), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32)]
 
@@ -211,6 +219,8 @@ SIGNATURES = {
     "fl_recognize_batch_instances_verified_meshes": (_I, [_P, _P, _I, C.POINTER(_P), C.POINTER(_P), _I, C.POINTER(Intrinsics),
                                                           C.POINTER(RecognitionParams), C.POINTER(InstanceParams), C.POINTER(InstanceVerifyParams),
                                                           _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "fl_verify_scene_batch": (_I, [_P, _I, C.POINTER(_P), _I, _I, _P, _P, _P, _I, _P, C.POINTER(Intrinsics), C.POINTER(SceneParams), _P]),
+    "fl_scene_pick": (_I, [_P, _I, _I, _P, _P, C.POINTER(SceneParams), _P]),
     "fl_nms": (_I, [_P, _I, _F, C.POINTER(_I), C.POINTER(_I)]),
     "fl_export_topk": (_I, [_P, _I, _I, _I, _P]),
     "fl_merge_topk": (_I, [_P, _I, _P, _I]),
@@ -234,7 +244,9 @@ DEV_SIGNATURES = {
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_tracker_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_tracker_track_verified_ms": (_I, [_P, C.POINTER(C.c_float)]),
-    "fl_dev_instances_verify_ms": (_I, [_P, C.POINTER(C.c_float)]),
+    "fl_dev_tracker_scene_shared": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "fl_dev_tracker_scene_ms": (_I, [_P, C.POINTER(C.c_float)]),
+    "fl_dev_instances_verify_ms":(_I, [_P, C.POINTER(C.c_float)]),
     "fl_dev_pick_verified": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "fl_dev_cq_window_addr": (None, [C.c_uint, _I, _I, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_I)]),
     "fl_dev_cq_window_taps": (None, [_P, C.c_uint, _I, _I, _I, _I, _P]),

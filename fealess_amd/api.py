@@ -31,6 +31,9 @@ assert VERIFY_DTYPE.itemsize == C.sizeof(L.VerifyResult) == 64
 VERIFIED_TRACK_DTYPE = np.dtype([("track", TRACK_DTYPE), ("verify", VERIFY_DTYPE), ("verify_in", VERIFY_DTYPE), ("icp_tracked", "<i4"),
                                  ("kept_input", "<i4"), ("best", "<i4"), ("reserved", "<i4")])
 assert VERIFIED_TRACK_DTYPE.itemsize == C.sizeof(L.VerifiedTrackResult) == 368
+# numpy view of fl_scene_result
+SCENE_DTYPE = np.dtype([("verify", VERIFY_DTYPE), ("kept", "<i4"), ("order", "<i4"), ("rival", "<i4"), ("n_shared", "<i4")])
+assert SCENE_DTYPE.itemsize == C.sizeof(L.SceneResult) == 80
 
 
 class FealessError(RuntimeError):
@@ -868,6 +871,58 @@ def _params_struct(who, struct, defaults, params):
     return struct(**dict(defaults, **params))
 
 
+_SCENE_DEFAULTS = dict(_VERIFY_DEFAULTS, max_shared_ratio=0.5, min_shared_px=1)    # k_scene_defaults
+
+
+def _scene_params(who, params):
+    """fl_scene_params from keyword arguments (the fields of fl_verify_params, max_shared_ratio, min_shared_px), the fields not
+    named at the library's defaults; None when no keyword is given."""
+    if not params:
+        return None
+    unknown = set(params) - set(_SCENE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"{who}: unknown parameters {sorted(unknown)}")
+    P = dict(_SCENE_DEFAULTS, **params)
+    return L.SceneParams(L.VerifyParams(*[P[k] for k in _VERIFY_DEFAULTS]), P["max_shared_ratio"], P["min_shared_px"])
+
+
+def scene_pick(records, scene_first, shared, **params):
+    """fl_scene_pick, host only: the order and the suppression of Tracker.verify_scene alone, on a VERIFY_DTYPE array, the
+    scenes and the compact shared array (None where no scene has a pair).  Returns a SCENE_DTYPE array."""
+    lib = L.load()
+    rec = np.ascontiguousarray(records, VERIFY_DTYPE).ravel()
+    sf = np.ascontiguousarray(scene_first, np.int32).ravel()
+    sh = None if shared is None else np.ascontiguousarray(shared, np.int32).ravel()
+    m = np.diff(sf.astype(np.int64))
+    if len(sf) < 2 or (sh is not None and len(sh) < int((m * (m - 1) // 2).sum())):
+        raise ValueError("scene_pick: scene_first has n_scenes + 1 entries, shared one entry per pair")
+    prm = _scene_params("scene_pick", params)
+    out = np.zeros(max(1, len(rec)), SCENE_DTYPE)
+    rc = lib.fl_scene_pick(_ptr(rec) if len(rec) else _ptr(np.zeros(1, VERIFY_DTYPE)), len(rec), len(sf) - 1, _ptr(sf), None if sh is None else _ptr(sh),
+                           None if prm is None else C.byref(prm), _ptr(out))
+    if rc != L.FL_OK:
+        raise FealessError(rc, "fl_scene_pick")
+    return out[:len(rec)]
+
+
+def scene_of_instances(results, n_instances, mesh_of_class):
+    """What Tracker.verify_scene takes, from the output of Detector.recognize_batch_instances_verified: results, a list per
+    frame of result dicts; n_instances, the number of instances of every frame (None: all of each list); mesh_of_class, the
+    mesh of every class or -1.  Returns (frame_of_pose, poses13, scene_first, mesh_of) over the instances with found == 1 whose
+    class has a mesh, in list order, one scene per frame (a frame without such an instance: an empty scene)."""
+    frame_of, poses, mesh_of, scene_first = [], [], [], [0]
+    for f, row in enumerate(results):
+        for r in row[:len(row) if n_instances is None else int(n_instances[f])]:
+            m = int(mesh_of_class[int(r["best"]["class_idx"])]) if r["found"] == 1 else -1
+            if m >= 0:
+                frame_of.append(f)
+                poses.append(np.asarray(r["pose"], np.float32).reshape(4, 4))
+                mesh_of.append(m)
+        scene_first.append(len(frame_of))
+    p = _poses13(np.stack(poses)) if poses else np.zeros((0, 13), np.float32)
+    return np.array(frame_of, np.int32), p, np.array(scene_first, np.int32), np.array(mesh_of, np.int32)
+
+
 class Tracker:
     """fl_tracker: follows objects from frame to frame against their CAD mesh (render at the previous pose, crop, detection()
     from that pose).  Owns its device memory: the mesh, max_frames depth frames of w x h, max_tracks renders and ICP workspaces
@@ -998,6 +1053,44 @@ class Tracker:
                                                                _ptr(p), 0 if gf is None else len(gf) - 1, None if gf is None else _ptr(gf),
                                                                C.byref(k), None if prm is None else C.byref(prm), C.byref(vp), _ptr(out)))
         return out[:n]
+
+    def verify_scene(self, depths, frame_of_pose, poses, K, scene_first, mesh_of=None, **params):
+        """Scene arbitration (fl_verify_scene_batch): every pose verified as verify() verifies it (mesh_of: the mesh of every
+        pose, None: mesh 0), then per scene -- the poses scene_first[s] .. scene_first[s + 1] - 1, all on one frame, 64 at the
+        most -- the accepted poses in the order of their n_inlier, a pose suppressed when a kept pose before it shares at least
+        min_shared_px and max_shared_ratio of its supporting pixels.  params: the fields of fl_verify_params (tau_mm,
+        min_model_px, min_inlier_ratio, max_behind_ratio) and max_shared_ratio (0.5), min_shared_px (1); none given = the
+        library's defaults.  Returns a SCENE_DTYPE array, one record per pose: verify (verify()'s record), kept, order, rival,
+        n_shared."""
+        who = "Tracker.verify_scene"
+        (n_frames, dp, mem, n, fof, p), k, out = self._batch(who, "frame index", depths, frame_of_pose, poses, K, SCENE_DTYPE)
+        sf = np.ascontiguousarray(scene_first, np.int32).ravel()
+        if len(sf) < 2:
+            raise ValueError(f"{who}: scene_first has n_scenes + 1 entries")
+        prm = _scene_params(who, params)
+        mo = self._mesh_of(who, mesh_of, n)
+        self.ctx.check(self.lib.fl_verify_scene_batch(self.handle, n_frames, dp, mem, n, _ptr(fof), None if mo is None else _ptr(mo), _ptr(p),
+                                                      len(sf) - 1, _ptr(sf), C.byref(k), None if prm is None else C.byref(prm), _ptr(out)))
+        return out[:n]
+
+    def dev_scene_shared(self):
+        """DEVELOPMENT ONLY (fl_dev_tracker_scene_shared, not part of the C ABI): the compact shared array of the last
+        verify_scene(), int32: the pair of local indices i < j of scene s at pair_first(s) + j (j - 1) / 2 + i."""
+        fn = L.dev(self.lib, "fl_dev_tracker_scene_shared")
+        n = C.c_int(0)
+        rc = fn(self.handle, None, 0, C.byref(n))
+        if rc != L.FL_ERR_OVERFLOW:
+            self.ctx.check(rc)
+        out = np.zeros(max(1, n.value), np.int32)
+        self.ctx.check(fn(self.handle, _ptr(out), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def scene_ms(self):
+        """DEVELOPMENT ONLY (fl_dev_tracker_scene_ms, not part of the C ABI): device time of the last verify_scene() by stage:
+        dict(copy, render, score, finish, overlap, pick) in ms."""
+        out = (C.c_float * 6)()
+        self.ctx.check(L.dev(self.lib, "fl_dev_tracker_scene_ms")(self.handle, out))
+        return dict(zip(("copy", "render", "score", "finish", "overlap", "pick"), [float(v) for v in out]))
 
     def track_verified_ms(self):
         """DEVELOPMENT ONLY (fl_dev_tracker_track_verified_ms, not part of the C ABI): device time of the stages the last

@@ -254,6 +254,24 @@ struct CadRecoVerifyResult {
 int CadRecoVerify(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult,
                   float tau_mm, vector<CadRecoVerifyResult> *out);
 
+// ---- arbitration: which of the results explain the same surface? ---------------------------------------------------------------
+// Two classes that fire on one physical object (a bracket whose mesh is part of a housing) both verify well.  CadRecoArbitrate
+// verifies every entry as CadRecoVerify does, each with the mesh of its strObjTag, and then treats the frame as ONE scene of
+// fl_verify_scene_batch (include/fealess_hip.h, which states the rule): the accepted entries in the order of their n_inlier, an
+// entry suppressed (kept = 0) when an entry kept before it shares at least max_shared_ratio of the frame pixels that support
+// it.  rival = the index in vtResult of the entry that suppressed it -- for a kept entry, of the kept entry it shares most
+// with -- or -1; n_shared = the pixels the two share.  Recognise verified (CadRecoSetVerifiedPick), then arbitrate, then keep
+// the entries with kept = 1.  vtResult is not changed.  The same limits and error codes as CadRecoVerify; max_shared_ratio not
+// finite or outside (0, 1]: ERROR_INVALID_PARAM.
+struct CadRecoSceneResult {
+  int accepted;
+  int n_model, n_missing, n_inlier, n_front, n_behind;
+  float inlier_ratio, behind_ratio;
+  int kept, rival, n_shared;
+};
+int CadRecoArbitrate(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult,
+                     float tau_mm, float max_shared_ratio, vector<CadRecoSceneResult> *out);
+
 // Opt-in: the verification decides what the multi-instance mode returns (fl_recognize_batch_instances_verified,
 // include/fealess_hip.h).  Every refined member of every group is verified against the mesh of CadRecoSetTrackingMesh behind the
 // frame's one ICP launch, with tau_mm and the two gates (<= 0: no test) as CadRecoVerify and fl_verify_params state them; a

@@ -402,6 +402,41 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return SUCCESS;
   }
 
+  // CadRecoArbitrate: one fl_verify_scene_batch over the entries, the frame one scene, each entry with the mesh of its strObjTag
+  int Arbitrate(const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult, float tau_mm, float max_shared_ratio,
+                vector<CadRecoSceneResult> *out)
+  {
+    if (out) out->clear();
+    if (!out || !m_ctx || !m_tracker || !check_image_u16(tDepth) || tDepth.nWidth != PROC_IMG_WIDTH || tDepth.nHeight != TRACK_IMG_HEIGHT ||
+        (int)vtResult.size() > FEALESS_TRACK_MAX_OBJECTS || !(tau_mm >= 0.f && tau_mm < 65536.f) ||
+        !(std::isfinite(max_shared_ratio) && max_shared_ratio > 0.f && max_shared_ratio <= 1.f))
+      return (int)ERROR_INVALID_PARAM;
+    const int n = (int)vtResult.size();
+    if (n == 0) return SUCCESS;
+    std::vector<float> poses((size_t)n * 13, 0.f);
+    std::vector<int32_t> frame_of(n, 0), mesh_of;
+    if (!MeshesOf(vtResult, mesh_of)) return (int)ERROR_INVALID_PARAM;         // a tag without a mesh
+    for (int i = 0; i < n; ++i) memcpy(poses.data() + (size_t)13 * i, vtResult[i].tWorld2Cam, 12 * sizeof(float));
+    const fl_intrinsics k = {PROC_IMG_WIDTH, TRACK_IMG_HEIGHT, K.dFx, K.dFy, K.dCx, K.dCy};
+    const uint16_t *frame = tDepth.pData;
+    const fl_scene_params prm = {{(int32_t)tau_mm, 1, 0.f, 0.f}, max_shared_ratio, 1};
+    const int32_t scene_first[2] = {0, n};
+    std::vector<fl_scene_result> res(n);
+    const int rc = fl_verify_scene_batch(m_tracker, 1, &frame, FL_MEM_HOST, n, frame_of.data(), mesh_of.data(), poses.data(), 1, scene_first, &k, &prm,
+                                         res.data());
+    if (rc != FL_OK) {
+      fprintf(stderr, "[fealess_hip] %s\n", fl_last_error(m_ctx));
+      return rc == FL_ERR_INVALID ? (int)ERROR_INVALID_PARAM : (int)ERROR_UNKNOW;
+    }
+    out->resize(n);
+    for (int i = 0; i < n; ++i) {
+      const fl_verify_result &v = res[i].verify;
+      (*out)[i] = CadRecoSceneResult{v.accepted, v.n_model, v.n_missing, v.n_inlier, v.n_front, v.n_behind, v.inlier_ratio, v.behind_ratio,
+                                     res[i].kept, res[i].rival, res[i].n_shared};
+    }
+    return SUCCESS;
+  }
+
   // CadRecoSetVerifiedPick: needs the multi-instance mode and a tracking mesh
   int SetVerifiedPick(int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio)
   {
@@ -783,6 +818,14 @@ int CadRecoVerify(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrin
   return h->Verify(tDepth, K, vtResult, tau_mm, out);
 }
 
+int CadRecoArbitrate(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamIntrinsicParam &K, const vector<TObjRecoResult> &vtResult,
+                     float tau_mm, float max_shared_ratio, vector<CadRecoSceneResult> *out)
+{
+  CObjRecoLmICPHip *h = dynamic_cast<CObjRecoLmICPHip *>(handle);
+  if (!h) return (int)ERROR_INVALID_PARAM;
+  return h->Arbitrate(tDepth, K, vtResult, tau_mm, max_shared_ratio, out);
+}
+
 // ---- flat C shim so that the pytest harness (ctypes) can drive the C++ facade -------------------
 extern "C" {
 // CadRecoVerify on n poses (n 4x4 matrices); out: n CadRecoVerifyResult records (8 x 4 bytes each)
@@ -798,6 +841,26 @@ int cadreco_verify(void *h, const unsigned short *depth, int w, int h_, double t
   std::vector<CadRecoVerifyResult> v;
   const int rc = CadRecoVerify((CObjRecoCAD *)h, d, K, res, tau_mm, &v);
   if (rc == SUCCESS && !v.empty()) memcpy(out, v.data(), v.size() * sizeof(CadRecoVerifyResult));
+  return rc;
+}
+// CadRecoArbitrate on n poses (n 4x4 matrices; tags: n class ids, or NULL for none); out: n CadRecoSceneResult records (11 x 4
+// bytes each)
+int cadreco_arbitrate(void *h, const unsigned short *depth, int w, int h_, double ts, double fx, double fy, double cx, double cy, int n,
+                      const float *poses16, const char *const *tags, float tau_mm, float max_shared_ratio, void *out)
+{
+  if (n < 0 || (n > 0 && (!poses16 || !out))) return (int)ERROR_INVALID_PARAM;
+  TImageU16 d = {ts, (unsigned short *)depth, w, h_};
+  TCamIntrinsicParam K;
+  K.nWidth = w; K.nHeight = h_; K.dFx = fx; K.dFy = fy; K.dCx = cx; K.dCy = cy;
+  std::vector<TObjRecoResult> res(n);
+  for (int i = 0; i < n; ++i) {
+    if (tags && !tags[i]) return (int)ERROR_INVALID_PARAM;
+    if (tags) res[i].strObjTag = tags[i];
+    memcpy(res[i].tWorld2Cam, poses16 + 16 * i, 16 * sizeof(float));
+  }
+  std::vector<CadRecoSceneResult> v;
+  const int rc = CadRecoArbitrate((CObjRecoCAD *)h, d, K, res, tau_mm, max_shared_ratio, &v);
+  if (rc == SUCCESS && !v.empty()) memcpy(out, v.data(), v.size() * sizeof(CadRecoSceneResult));
   return rc;
 }
 // cadreco_verify with a class id per pose (tags: n strings): what picks each pose's mesh after cadreco_set_tracking_meshes

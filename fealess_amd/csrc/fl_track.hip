@@ -319,6 +319,8 @@ extern "C" void fl_tracker_destroy(fl_tracker *trk)
     (void)hipStreamSynchronize(trk->ctx->stream);
     for (hipEvent_t e : trk->ev)
       if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : trk->ev_scene)
+      if (e) (void)hipEventDestroy(e);
     if (trk->d_mem) (void)hipFree(trk->d_mem);
     if (trk->h_stage) (void)hipHostFree(trk->h_stage);
   }

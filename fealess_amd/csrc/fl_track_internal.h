@@ -1,5 +1,6 @@
 // fl_track_internal.h -- what the tracker's entry points share (fl_track.hip: fl_track_batch and fl_track_batch_verified,
-// fl_verify.hip: fl_verify_batch; not part of the ABI): the tracker, the layout of its pinned block, and the steps of a call, which fl_track.hip defines.
+// fl_verify.hip: fl_verify_batch; fl_scene.hip: fl_verify_scene_batch; not part of the ABI): the tracker, the layout of its pinned block, and the
+// steps of a call, which fl_track.hip defines.
 #pragma once
 #include "fl_internal.h"
 #include <math.h>
@@ -9,6 +10,7 @@
 constexpr int FL_TRACK_EVENTS = 2 + 4 * FL_TRACK_MAX_PASSES;   // start, inputs on the device, then per pass render / rects / ICP / finish
 constexpr int FL_VERIFY_EVENTS = 5;                            // start, inputs on the device, render, score, finish and pick
 constexpr int FL_TRACK_VERIFIED_EVENTS = 3;                    // fl_track_batch_verified after its passes: accumulators clear, fused, finish and pick
+constexpr int FL_SCENE_EVENTS = FL_VERIFY_EVENTS + 2;          // fl_verify_scene_batch: fl_verify_batch's, then overlap, then pick
 
 // p = base + off (base null: a sizing pass, p is left alone); off moves on by bytes rounded up to 256
 template <class T>
@@ -20,7 +22,7 @@ inline void fl_carve(T *&p, uint8_t *base, size_t &off, size_t bytes)
 
 // The pinned block a call's inputs leave through and its records come back through, and the one statement of its layout:
 // max_tracks poses of 13 floats | frame indices | mesh indices | records (of fl_track_batch, fl_verify_batch or
-// fl_track_batch_verified) | max_tracks + 1 group starts
+// fl_track_batch_verified, the largest; fl_verify_scene_batch's 80-byte records fit) | max_tracks + 1 group or scene starts
 struct FlTrackStage { float *poses; int32_t *frame_of, *mesh_of; uint8_t *results; int32_t *group_first; };
 inline size_t fl_track_stage(FlTrackStage &s, uint8_t *base, int max_tracks)   // returns the bytes; base null: nothing else
 {
@@ -70,6 +72,12 @@ struct fl_tracker {
   int last_passes = 0;                          // of the last fl_track_batch or fl_track_batch_verified; 0: none yet
   bool verified = false;                        // an fl_verify_batch has completed
   bool track_verified = false;                  // the last call that ran passes was an fl_track_batch_verified
+  // fl_verify_scene_batch (fl_scene.hip): its events, made by its first call, and where its last call left the compact shared
+  // array in the context's scratch block (scene_scratch: the block it was carved from, to tell a block that has moved since)
+  hipEvent_t ev_scene[FL_SCENE_EVENTS] = {nullptr};
+  const int32_t *scene_shared = nullptr;
+  const void *scene_scratch = nullptr;
+  int scene_pairs = -1;                         // -1: no fl_verify_scene_batch has completed
 };
 
 // The steps of a call, in the order an entry point takes them.
@@ -93,6 +101,14 @@ int fl_tracker_stage(fl_tracker *trk, hipEvent_t ev_start, int n_frames, const u
 int fl_tracker_render(fl_tracker *trk, int n, float fx, float fy, float cx, float cy);
 // 4. bytes of records from d_records to the caller through the pinned block: one copy, one wait for the stream
 int fl_tracker_results(fl_tracker *trk, const void *d_records, size_t bytes, void *results);
+// fl_verify_batch_meshes behind its checks (fl_verify.hip), queued and not waited for: step 2 (ev[0] at its start), `starts`
+// (group_first, or fl_verify_scene_batch's scene_first; n_starts + 1 entries, null: none) through the pinned block into
+// d_group_first, clear accumulators (ev[1]), the render at the scene camera unless fused (ev[2]), the counts (ev[3]), the
+// records, and with pick the best of every group of `starts` (ev[4]); without pick best = accepted.  Afterwards d_vres holds
+// the n_poses records and, unless fused, d_render their renders.  ev: five events.
+int fl_verify_queue(fl_tracker *trk, hipEvent_t *ev, int n_frames, const uint16_t *const *depth, int mem, int n_poses, const int32_t *frame_of_pose,
+                    const int32_t *mesh_of_pose, const float *poses13, int n_starts, const int32_t *starts, bool pick, bool fused,
+                    const fl_intrinsics *K, const fl_verify_params &P);
 
 // a pixel index into the bounding box of a w-wide image (k_track_rects, k_verify_score)
 __device__ __forceinline__ void bbox_add(int idx, int w, int &x0, int &x1, int &y0, int &y1)

@@ -8,6 +8,8 @@
 //                    in the workgroup, then one integer atomic per counter into the pose's FlVerifyAcc -- exact whatever the order
 //   k_verify_finish  one thread per pose: rect, ratios, accepted; best = accepted when there are no groups
 //   k_verify_pick    one thread per group: the best accepted member
+// fl_verify_queue is all of that behind the argument checks, queued and not waited for; fl_verify_scene_batch (fl_scene.hip) calls
+// it too and goes on with the records and the renders on the device.
 // The strip: k_track_rects walks a whole 640 x 480 render with one workgroup and is bound by the latency of its 19 rounds of
 // loads.  Here a thread issues its V_LOADS 16-byte render loads at once and never loops, so a workgroup lasts about two memory
 // round trips (render, then the scene under the non-zero groups) and a strip is VB * V_LOADS * 8 = 8192 pixels, 16 KB of
@@ -520,33 +522,27 @@ extern "C" int fl_dev_tracker_verify_ms(fl_tracker *trk, float out[4])
   return FL_OK;
 }
 
-extern "C" int fl_verify_batch_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_poses,
-                                      const int32_t *frame_of_pose, const int32_t *mesh_of_pose, const float *poses13, int n_groups,
-                                      const int32_t *group_first, const fl_intrinsics *K, const fl_verify_params *params, fl_verify_result *results)
+// fl_verify_batch_meshes behind its checks (fl_track_internal.h), queued and not waited for
+int fl_verify_queue(fl_tracker *trk, hipEvent_t *ev, int n_frames, const uint16_t *const *depth, int mem, int n_poses, const int32_t *frame_of_pose,
+                    const int32_t *mesh_of_pose, const float *poses13, int n_starts, const int32_t *starts, bool pick, bool fused,
+                    const fl_intrinsics *K, const fl_verify_params &P)
 {
-  int rc = fl_tracker_check_call(trk, "fl_verify_batch", n_frames, depth, mem, n_poses, frame_of_pose, mesh_of_pose, poses13, K, results);
-  if (rc) return rc;
-  if ((rc = fl_verify_check_call(trk, "fl_verify_batch", K, n_poses, n_groups, group_first))) return rc;
   fl_context *ctx = trk->ctx;
   const float fx = (float)K->fx, fy = (float)K->fy, cx = (float)K->cx, cy = (float)K->cy;
-  const fl_verify_params P = params ? *params : k_verify_defaults;
-  if (!fl_verify_params_ok(P))
-    return fl_set_error(ctx, FL_ERR_INVALID, "fl_verify_params: tau_mm 0..65535, min_model_px >= 1, finite thresholds");
-  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_verify_batch: the tracker has no device");
-
-  // 1. the inputs, and the groups after them
-  hipEvent_t *ev = trk->ev + FL_TRACK_EVENTS;
+  const int32_t *group_first = pick ? starts : nullptr;
+  const int n_groups = n_starts;
+  int rc;
+  // 1. the inputs, and the groups (or a scene call's scenes) after them
   if ((rc = fl_tracker_stage(trk, ev[0], n_frames, depth, mem, n_poses, frame_of_pose, mesh_of_pose, poses13, nullptr))) return rc;
   const size_t px = (size_t)trk->w * trk->h, T = (size_t)n_poses;
   hipStream_t st = ctx->stream;
-  if (group_first) {
-    memcpy(trk->stage.group_first, group_first, ((size_t)n_groups + 1) * 4);
-    FL_HIP(ctx, hipMemcpyAsync(trk->d_group_first, trk->stage.group_first, ((size_t)n_groups + 1) * 4, hipMemcpyHostToDevice, st));
+  if (starts) {
+    memcpy(trk->stage.group_first, starts, ((size_t)n_starts + 1) * 4);
+    FL_HIP(ctx, hipMemcpyAsync(trk->d_group_first, trk->stage.group_first, ((size_t)n_starts + 1) * 4, hipMemcpyHostToDevice, st));
   }
   FL_HIP(ctx, hipMemsetAsync(trk->d_vacc, 0, T * sizeof(FlVerifyAcc), st));
   FL_HIP(ctx, hipEventRecord(ev[1], st));
   // 2. the render, at the scene's K
-  const bool fused = ctx->opt.verify_fused != 0;
   if (!fused && (rc = fl_tracker_render(trk, n_poses, fx, fy, cx, cy))) return rc;
   FL_HIP(ctx, hipEventRecord(ev[2], st));
   // 3. the counts
@@ -571,8 +567,27 @@ extern "C" int fl_verify_batch_meshes(fl_tracker *trk, int n_frames, const uint1
     FL_HIP(ctx, hipGetLastError());
   }
   FL_HIP(ctx, hipEventRecord(ev[4], st));
+  return FL_OK;
+}
+
+extern "C" int fl_verify_batch_meshes(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_poses,
+                                      const int32_t *frame_of_pose, const int32_t *mesh_of_pose, const float *poses13, int n_groups,
+                                      const int32_t *group_first, const fl_intrinsics *K, const fl_verify_params *params, fl_verify_result *results)
+{
+  int rc = fl_tracker_check_call(trk, "fl_verify_batch", n_frames, depth, mem, n_poses, frame_of_pose, mesh_of_pose, poses13, K, results);
+  if (rc) return rc;
+  if ((rc = fl_verify_check_call(trk, "fl_verify_batch", K, n_poses, n_groups, group_first))) return rc;
+  fl_context *ctx = trk->ctx;
+  const fl_verify_params P = params ? *params : k_verify_defaults;
+  if (!fl_verify_params_ok(P))
+    return fl_set_error(ctx, FL_ERR_INVALID, "fl_verify_params: tau_mm 0..65535, min_model_px >= 1, finite thresholds");
+  if (ctx->device < 0) return fl_set_error(ctx, FL_ERR_NO_DEVICE, "fl_verify_batch: the tracker has no device");
+  // 1. to 4. the inputs, the render, the counts, the records and the best of every group
+  if ((rc = fl_verify_queue(trk, trk->ev + FL_TRACK_EVENTS, n_frames, depth, mem, n_poses, frame_of_pose, mesh_of_pose, poses13, group_first ? n_groups : 0,
+                            group_first, group_first != nullptr, ctx->opt.verify_fused != 0, K, P)))
+    return rc;
   // 5. one copy, one wait
-  if ((rc = fl_tracker_results(trk, trk->d_vres, T * sizeof(fl_verify_result), results))) return rc;
+  if ((rc = fl_tracker_results(trk, trk->d_vres, (size_t)n_poses * sizeof(fl_verify_result), results))) return rc;
   trk->verified = true;
   return FL_OK;
 }

@@ -718,6 +718,63 @@ int  fl_recognize_batch_instances_verified_meshes(fl_detector *det, fl_tracker *
                                                   const fl_instance_verify_params *vp, const int32_t *mesh_of_class,
                                                   fl_verified_instance_result *results, int32_t *n_instances, int32_t *n_dropped,
                                                   fl_verify_result *member_verify);
+/* ---- scene arbitration: one kept hypothesis per supported surface patch ----------------------------------------------------------
+ * Grouping, fl_nms and the picks above decide inside one class or by a distance between translations.  Two classes that fire on
+ * one physical object (a bracket whose mesh is part of a housing), or two tracks that drifted onto one object, each verify
+ * well.  fl_verify_scene_batch verifies every pose as fl_verify_batch_meshes does and then asks of every two accepted poses of
+ * one SCENE how many frame pixels support both; a pose whose support is largely another, stronger pose's is suppressed.  Opt-in:
+ * no other entry point changes.  depth, mem, frame_of_pose, mesh_of_pose (NULL: mesh 0), poses13 and K are as
+ * fl_verify_batch_meshes takes them; results (n_poses records) is host memory; params == NULL: the defaults below.  Everything
+ * is queued on the context's stream and the call waits once, at the end; it allocates nothing beyond the context's scratch
+ * and pinned blocks, which persist.  It writes the tracker's frame slots and render images, as fl_verify_batch does.
+ *   scenes   scene s is the poses scene_first[s] .. scene_first[s + 1] - 1 (scene_first: n_scenes + 1 entries, host memory,
+ *            non-decreasing, scene_first[0] == 0, scene_first[n_scenes] == n_poses).  A scene may be empty, has at most
+ *            FL_SCENE_MAX_POSES poses, and all of its poses name one frame.
+ *   verify   every pose gets exactly the render (at the SCENE camera), score and finish of fl_verify_batch_meshes with
+ *            group_first == NULL -> `verify`, byte for byte that call's record (best = accepted).  The context option
+ *            verify_fused is ignored here: the renders are read again afterwards, so they are always written to memory.
+ *   support  pixel p supports pose a when r_a(p) != 0 && s(p) != 0 && |s(p) - r_a(p)| <= tau_mm: the pixels n_inlier counts.
+ *   shared   shared(a, b) = the number of pixels that support both poses; symmetric; taken as 0 unless both poses are accepted.
+ *            Stored compactly: with m_s the size of scene s and pair_first(s) = sum over s' < s of m_s' (m_s' - 1) / 2, the
+ *            pair of local indices i < j of scene s is entry pair_first(s) + j (j - 1) / 2 + i.
+ *   order    among the accepted poses of a scene, a stands before b when n_inlier_a > n_inlier_b; or these are equal and
+ *            (int64)n_inlier_a * n_model_b > (int64)n_inlier_b * n_model_a; or both are equal and a has the lower index.
+ *            More explained surface goes first: a large object precedes its own part, whatever their ratios.  What keeps a
+ *            large WRONG pose from leading a scene is the gates of `verify` (min_inlier_ratio, max_behind_ratio), not the order.
+ *   suppress walk the order with an initially empty kept list.  For pose b: rival = -1, n_shared = 0; for every kept a, in the
+ *            order it was kept, n = shared(a, b): if n >= min_shared_px && (float)n / (float)n_inlier_b >= max_shared_ratio
+ *            (one float32 division, as the other ratios of this header), b is suppressed: kept = 0, rival = a, n_shared = n,
+ *            and the walk over the kept list stops; otherwise if n > n_shared, rival = a and n_shared = n.  A pose no kept pose
+ *            suppressed joins the kept list, kept = 1, rival = the kept pose it shares most with (the earliest kept of equals) or
+ *            -1.  A suppressed pose never suppresses another.  A pose that is not accepted: kept = 0, order = -1, rival = -1,
+ *            n_shared = 0.  rival is a pose index in the call, not in the scene.
+ * Returns FL_OK when the batch ran.  FL_ERR_INVALID, nothing written, before the first HIP call: everything
+ * fl_verify_batch_meshes refuses (its group rules aside); scene_first NULL, n_scenes outside 1..max_tracks, a scene_first that
+ * breaks the rules above, a scene of more than FL_SCENE_MAX_POSES poses or of two frames; max_shared_ratio not finite or outside
+ * (0, 1]; min_shared_px < 1.
+ * fl_scene_pick is the order and the suppression alone, host only (like fl_nms), on records and a compact shared array the
+ * caller has: results[i].verify = records[i], the other fields by the rules above.  It refuses (FL_ERR_INVALID, nothing
+ * written) null pointers -- shared may be NULL only when no scene has a pair --, the same scene_first (n_scenes >= 1) and params,
+ * and a shared entry of two accepted poses outside 0 .. min(n_inlier_a, n_inlier_b); entries of other pairs are ignored. */
+#define FL_SCENE_MAX_POSES 64
+typedef struct {
+  fl_verify_params verify;             /* per-pose rule and gates: ranges and defaults of fl_verify_batch */
+  float   max_shared_ratio;            /* suppressed when shared / n_inlier reaches it; finite, in (0, 1]; default 0.5 */
+  int32_t min_shared_px;               /* and shared is at least this; >= 1; default 1 */
+} fl_scene_params;
+typedef struct {
+  fl_verify_result verify;             /* byte for byte fl_verify_batch_meshes' record with group_first == NULL (best = accepted) */
+  int32_t kept;                        /* 1: survives the arbitration */
+  int32_t order;                       /* 0-based place in its scene's order; -1: not accepted */
+  int32_t rival;                       /* pose index in the call, or -1 */
+  int32_t n_shared;                    /* shared(rival, this pose); 0 when rival == -1 */
+} fl_scene_result;                     /* 80 bytes */
+int  fl_verify_scene_batch(fl_tracker *trk, int n_frames, const uint16_t *const *depth, int mem, int n_poses,
+                           const int32_t *frame_of_pose, const int32_t *mesh_of_pose, const float *poses13,
+                           int n_scenes, const int32_t *scene_first, const fl_intrinsics *K,
+                           const fl_scene_params *params, fl_scene_result *results);
+int  fl_scene_pick(const fl_verify_result *records, int n_poses, int n_scenes, const int32_t *scene_first,
+                   const int32_t *shared, const fl_scene_params *params, fl_scene_result *results);
 /* After fl_match_frame / fl_recognize_submit: copy frame `frame`'s first k sorted matches into a
  * device buffer (k * sizeof(fl_match) bytes, padded with template_id = -1) for an RCCL
  * all-gather by the caller; template ids are offset by template_id_base (the shard's first
