@@ -11,6 +11,7 @@ import zlib
 import numpy as np
 import pytest
 
+from cadreco_py import lib as _cad
 from fealess_amd import _lib as L
 from fealess_amd.bank import MATCH_DTYPE
 
@@ -114,13 +115,6 @@ def test_merge_topk_equals_global_sort_unique(oracle):
 
 
 # ---- CadReco adapter bank I/O --------------------------------------------------------------------
-def _cad():
-    path = os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so")
-    lib = C.CDLL(path)
-    lib.cadreco_version.restype = C.c_char_p
-    return lib
-
-
 def write_png16(path, img):
     img = np.ascontiguousarray(img, dtype=">u2")
     h, w = img.shape
@@ -131,6 +125,15 @@ def write_png16(path, img):
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 0, 0, 0, 0)) +
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def write_bank_dir(d, bank, T, depths):
+    """The directory AddObj reads: linemod_templates.yml of the bank(s) and depth/<id>.png for every depth render that is not None."""
+    (d / "depth").mkdir(parents=True)
+    write_linemod_yaml(str(d / "linemod_templates.yml"), bank, T)
+    for i, md in enumerate(depths):
+        if md is not None:
+            write_png16(str(d / "depth" / f"{i}.png"), md)
 
 
 def write_linemod_yaml(path, bank, T, modalities=("ColorGradient", "DepthNormal")):
@@ -213,7 +216,6 @@ def test_addobj_rejects_inconsistent_bank_files(tmp_path):
     refused before that (no GPU needed: the check precedes any device work; without a device AddObj fails anyway)."""
     from fealess_amd import synth
     lib = _cad()
-    lib.cadreco_create.restype = C.c_void_p
     bank = synth.make_bank("obj", 3, 2, 2, 640, 480, seed=3)
     d = tmp_path / "bank"
     d.mkdir()
@@ -255,7 +257,6 @@ def test_linemod_yaml_reader(tmp_path):
 
 def test_cadreco_factory_rejects_unsupported_types():
     lib = _cad()
-    lib.cadreco_create.restype = C.c_void_p
     for unsupported in (0, 2, 3):            # EObjReco_FEATURE, BB8, PoseNet -> nullptr (obj_reco_temp.cpp:13-30)
         assert not lib.cadreco_create(unsupported)
 

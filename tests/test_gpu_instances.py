@@ -2,23 +2,22 @@
 lists of every size class, and fl_recognize_batch_instances on the cluttered frames (tests/clutter.py) against the oracle's
 refinement of the same matches and its nonMaximumSuppression, bit for bit."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import cadreco_py
 import clutter
 import instances_model as M
 from fealess_amd import api
 from fealess_amd import _lib as L
 from fealess_amd.bank import MATCH_DTYPE
-from test_abi_cpu import write_linemod_yaml, write_png16
+from test_abi_cpu import write_bank_dir
 from test_instances_cpu import MIN_DIST, TABLE
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARAMS = ((75.0, 10, 0.5, 0.01), (75.0, 20, 0.0, -3.0e38))       # those of test_gpu_clutter.py
 NMS_DIST = 60.0
 LDS_MAX = 16384                  # FL_GROUP_LDS_MAX: group ids in LDS up to this many matches, in global memory beyond
@@ -275,32 +274,20 @@ def test_facade_returns_every_instance(tmp_path, scene, refined):
     """CadRecoSetMultiInstance(8, 48, 4) through the C++ facade: three results on frame a, in group order."""
     bank = scene["bank"]
     d = tmp_path / "obj"
-    (d / "depth").mkdir(parents=True)
-    write_linemod_yaml(str(d / "linemod_templates.yml"), bank, clutter.T)
-    for i, md in enumerate(bank.model_depths):
-        if md is not None:
-            write_png16(str(d / "depth" / f"{i}.png"), md)
-    lib = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    lib.cadreco_create.restype = C.c_void_p
-    lib.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
-    lib.cadreco_set_multi_instance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    lib.cadreco_set_multi_hypothesis.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    write_bank_dir(d, bank, clutter.T, bank.model_depths)
+    lib = cadreco_py.lib()
     h = C.c_void_p(lib.cadreco_create(1))
     assert h.value and lib.cadreco_add_obj(h, str(d).encode()) == 0
     bad = C.c_int(0x80000001).value
     for args in ((0, 48, 4), (65, 48, 4), (8, 0, 4), (8, 48, 0), (8, 48, 65)):
         assert lib.cadreco_set_multi_instance(h, *args) == bad, args
     bgr, depth = np.ascontiguousarray(scene["bgrs"][0]), np.ascontiguousarray(scene["depths"][0])
-    fx, fy, cx, cy = scene["K"]
     poses = np.zeros((8, 16), np.float32)
-    n = C.c_int(-1)
 
     def reco():
-        poses[:] = 0
-        rc = lib.cadreco_recognition_all(h, bgr.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), 640, 480, C.c_double(1.0), 640, 480,
-                                         C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.byref(n), poses.ctypes.data_as(C.c_void_p), 8)
+        rc, n, poses[:] = cadreco_py.recognition_all(h, bgr, depth, scene["K"])
         assert rc == 0
-        return n.value
+        return n
     ref = refined[0][0]
     assert reco() == 1 and np.abs(poses[0].reshape(4, 4) - ref[0]["pose"]).max() <= 1e-4          # the default: matches[0]
     assert lib.cadreco_set_multi_instance(h, 8, MIN_DIST, 4) == 0

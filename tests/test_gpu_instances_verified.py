@@ -9,12 +9,12 @@ hidden has n_front = 2387 of n_model = 11558 (the hiding instance stands in fron
 n_front = 19 and n_behind = 84 of 14921: the camera sees through neither, n_behind is silhouette pixels of the coarse mesh.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import cadreco_py
 import clutter
 import instances_model as M
 import multiclass
@@ -22,13 +22,12 @@ import verified_pick_model as VP
 import verify_model as VM
 from fealess_amd import _lib as L
 from fealess_amd import api, synth
-from test_abi_cpu import write_linemod_yaml, write_png16
+from test_abi_cpu import write_bank_dir
 from test_instances_cpu import MIN_DIST, TABLE
 from test_instances_verified_cpu import CASES, REFUSED, _call, _records
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 P = (75.0, 10, 0.5, 0.01)
 NF = len(clutter.FRAMES)
@@ -282,7 +281,7 @@ def test_tracking_is_unchanged_by_a_verified_recognition_between(cdet, trk, scen
 
 
 # ---- the facade ---------------------------------------------------------------------------------------------------------------
-INVALID = C.c_int(0x80000001).value
+INVALID = cadreco_py.INVALID
 
 
 def test_facade_verified_pick(ctx, cdet, scene, tmp_path):
@@ -291,40 +290,19 @@ def test_facade_verified_pick(ctx, cdet, scene, tmp_path):
     the accepted ones; switched off it returns what the multi-instance mode returned before, which is fl_recognize_batch_instances'."""
     bank = scene["bank"]
     d = tmp_path / "obj"
-    (d / "depth").mkdir(parents=True)
-    write_linemod_yaml(str(d / "linemod_templates.yml"), bank, clutter.T)
-    for i, md in enumerate(bank.model_depths):
-        if md is not None:
-            write_png16(str(d / "depth" / f"{i}.png"), md)
+    write_bank_dir(d, bank, clutter.T, bank.model_depths)
     obj = str(tmp_path / "object.obj")
     synth.write_obj(obj, synth.object_mesh(2))
-    lib = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    lib.cadreco_create.restype = C.c_void_p
-    lib.cadreco_destroy.argtypes = [C.c_void_p]
-    lib.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
-    lib.cadreco_set_params.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int]
-    lib.cadreco_set_multi_instance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    lib.cadreco_set_multi_hypothesis.argtypes = [C.c_void_p, C.c_int, C.c_float]
-    lib.cadreco_set_tracking_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
-    lib.cadreco_set_verified_pick.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
-    lib.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
-    nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-    assert lib.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0) == 0
-    V, N, T = np.zeros((nv.value, 3), np.float32), np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-    assert lib.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, N.ctypes.data, T.ctypes.data, nv.value, nt.value) == 0
+    lib = cadreco_py.lib()
+    V, N, T = cadreco_py.read_obj(obj)
     bgr, depth = np.ascontiguousarray(scene["bgrs"][0]), np.ascontiguousarray(scene["depths"][0])
-    fx, fy, cx, cy = scene["K"]
-    poses = np.zeros((8, 16), np.float32)
-    n = C.c_int(-1)
     h = C.c_void_p(lib.cadreco_create(1))
     assert h.value and lib.cadreco_add_obj(h, str(d).encode()) == 0 and lib.cadreco_set_params(h, *P, L.FL_ICP_PARITY) == 0
 
     def reco():
-        poses[:] = 0
-        rc = lib.cadreco_recognition_all(h, bgr.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), 640, 480, C.c_double(1.0), 640, 480,
-                                         C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.byref(n), poses.ctypes.data_as(C.c_void_p), 8)
+        rc, n, poses = cadreco_py.recognition_all(h, bgr, depth, scene["K"])
         assert rc == 0
-        return poses[:n.value].copy()
+        return poses[:n]
     trk = api.Tracker(ctx, V, T, clutter.W, clutter.H, 1, 4, 1000)
     try:
         # what it needs first

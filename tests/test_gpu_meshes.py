@@ -7,11 +7,11 @@ per call) against "the model with pose t's mesh" too.  The meshes and their orde
 tests/meshes.py's; tests/test_meshes_cpu.py shows that the choice of the mesh changes a record.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import cadreco_py
 import clutter
 import instances_model as M
 import meshes as MS
@@ -29,7 +29,6 @@ from util import p13 as _p13, pose as _pose
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 640, 480
 NAMES = "ABCD"
 IDX = MS.INDEX
@@ -371,72 +370,32 @@ def test_facade_picks_the_mesh_by_the_tag(ctx, meshes, tmp_path):
     """CadRecoSetTrackingMeshes with two class ids and two OBJ files: CadRecoVerify on a recognised result takes the mesh of the
     result's tag, and the record is the C ABI's on that mesh as the facade reads it; a tag without a mesh is refused."""
     from test_gpu_verify import FACADE_RESULT, INVALID
-    cad = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    cad.cadreco_create.restype = C.c_void_p
-    cad.cadreco_destroy.argtypes = [C.c_void_p]
-    cad.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
-    cad.cadreco_set_tracking_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
-    cad.cadreco_set_tracking_meshes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_float]
-    cad.cadreco_train_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                       C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    cad.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
-    verify_args = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double] + [C.c_double] * 4 + [C.c_int, C.c_void_p]
-    cad.cadreco_verify.argtypes = verify_args + [C.c_float, C.c_void_p]
-    cad.cadreco_verify_tagged.argtypes = verify_args + [C.POINTER(C.c_char_p), C.c_float, C.c_void_p]
+    cad = cadreco_py.lib()
     obj, box = str(tmp_path / "object.obj"), str(tmp_path / "box.obj")
     synth.write_obj(obj, synth.object_mesh(2))
     synth.write_obj(box, meshes["B"], with_normals=False)
-
-    def read(path):
-        nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-        assert cad.cadreco_read_obj(path.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0) == 0
-        V, N, T = np.zeros((nv.value, 3), np.float32), np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        assert cad.cadreco_read_obj(path.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, N.ctypes.data, T.ctypes.data, nv.value, nt.value) == 0
-        return V, N, T
 
     def verify(h, depth, poses16, tags):
         p = np.ascontiguousarray(poses16, np.float32)
         out = np.zeros(len(p), FACADE_RESULT)
         if tags is None:
-            return cad.cadreco_verify(h, depth.ctypes.data, W, H, 0.0, *K0, len(p), p.ctypes.data, 10.0, out.ctypes.data), out
+            return cad.cadreco_verify(h, *cadreco_py.frame_args(depth, 0.0, K0), len(p), p.ctypes.data, 10.0, out.ctypes.data), out
         tg = (C.c_char_p * len(p))(*tags)
-        return cad.cadreco_verify_tagged(h, depth.ctypes.data, W, H, 0.0, *K0, len(p), p.ctypes.data, tg, 10.0, out.ctypes.data), out
+        return cad.cadreco_verify_tagged(h, *cadreco_py.frame_args(depth, 0.0, K0), len(p), p.ctypes.data, tg, 10.0, out.ctypes.data), out
 
     h = C.c_void_p(cad.cadreco_create(1))
     assert h.value
     one = {}
     try:
-        P_ = api.view_sphere(0, [700.0], n_inplane=1, inplane_deg=0.0, upper_hemisphere=True)
-        dist = np.array([700.0], np.float32)
-        tov = np.full(len(P_), -9, np.int32)
-        d = str(tmp_path / "bank")
-        assert cad.cadreco_train_mesh(h, d.encode(), b"mesh", obj.encode(), 1.0, 0, 1, dist.ctypes.data, 1, 1, 0.0, 2, (C.c_int * 2)(5, 8),
-                                      tov.ctypes.data, len(P_)) == 0
-        assert (tov >= 0).any() and cad.cadreco_add_obj(h, d.encode()) == 0
-        V, N, T = read(obj)
-        Vb, _, Tb = read(box)
+        V, N, T, depth, pose = cadreco_py.recognised_mesh_frame(h, ctx, obj, str(tmp_path / "bank"))
+        Vb, _, Tb = cadreco_py.read_obj(box)
         assert len(T) == 332 and len(Tb) == 12
-        view = P_[int(np.flatnonzero(tov >= 0)[0])]
-        bgr, dep, msk, _ = ctx.render_views(V, T, view[None], K0, W, H, normals=N)
-        u, v = np.meshgrid(np.arange(float(W)), np.arange(float(H)))
-        m = msk[0] > 0
-        depth = np.ascontiguousarray(np.where(m, dep[0], np.rint(950.0 + 0.06 * u + 0.04 * v)).astype(np.uint16))
-        cell = (np.floor(u / 23.0) + 2 * np.floor(v / 17.0)) % 5
-        col = np.where(m[..., None], bgr[0].astype(np.float64), (70 + 30 * cell)[..., None] * np.array([1.0, 0.9, 0.75]))
-        col = np.ascontiguousarray(np.clip(np.rint(col), 0, 255).astype(np.uint8))
-        pose = np.zeros(16, np.float32)
-        tag = C.create_string_buffer(64)
-        nres = C.c_int(-1)
-        rc = cad.cadreco_recognition(h, col.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), W, H, C.c_double(1.0), W, H,
-                                     C.c_double(K0[0]), C.c_double(K0[1]), C.c_double(K0[2]), C.c_double(K0[3]), C.byref(nres),
-                                     pose.ctypes.data_as(C.c_void_p), tag, 64)
-        assert rc == 0 and nres.value == 1 and tag.value == b"mesh"
         poses = np.stack([pose, pose])
         ids, paths = (C.c_char_p * 2)(b"box", b"mesh"), (C.c_char_p * 2)(box.encode(), obj.encode())
         assert cad.cadreco_set_tracking_meshes(h, 2, (C.c_char_p * 2)(b"box", b"box"), paths, 1.0) == INVALID      # an id twice
         assert cad.cadreco_set_tracking_meshes(h, 0, ids, paths, 1.0) == INVALID
         assert cad.cadreco_set_tracking_meshes(h, 2, ids, paths, 1.0) == 0
-        rc, got = verify(h, depth, poses, [tag.value, b"box"])
+        rc, got = verify(h, depth, poses, [b"mesh", b"box"])
         assert rc == 0
         one = dict(mesh=api.Tracker(ctx, V, T, W, H, 1, 2, 1000), box=api.Tracker(ctx, Vb, Tb, W, H, 1, 2, 1000))
         p44 = pose.reshape(1, 4, 4)

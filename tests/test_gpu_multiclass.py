@@ -8,24 +8,23 @@ Class indices refined, per entry point (asserted below): fl_recognize_batch and 
 (then 0) under the class filter; fl_recognize_batch_topk / _topk 0, 1, 2 on frame a; fl_refine_matches 0, 1, 2;
 fl_recognize_batch_instances 0, 1, 2 on frame a; the facade 1 of {alpha, zeta}."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import cadreco_py
 import clutter
 import instances_model as M
 import multiclass
 from fealess_amd import api
 from fealess_amd import _lib as L
 from fealess_amd.bank import MATCH_DTYPE
-from test_abi_cpu import write_linemod_yaml, write_png16
+from test_abi_cpu import write_bank_dir
 from test_gpu_icp import width  # noqa: F401    the fixture that forces each build of the ICP kernels in turn
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = (75.0, 10, 0.5, 0.01)                      # Recognition()'s defaults
 TOPK, NMS_DIST, MIN_DIST = 16, 60.0, 48
 NF = len(clutter.FRAMES)
@@ -327,17 +326,11 @@ def test_template_sharding_refuses_several_classes(mc, det):
 
 def _facade_recognition(lib, directory, bgr, depth, K):
     """Create -> AddObj(directory) -> Recognition of one 640 x 480 frame: (number of results, tag, pose)."""
-    h = C.c_void_p(lib.cadreco_create(1))
-    assert h.value and lib.cadreco_add_obj(h, str(directory).encode()) == 0
-    pose = np.zeros(16, np.float32)
-    tag = C.create_string_buffer(64)
-    n = C.c_int(-1)
-    fx, fy, cx, cy = K
-    rc = lib.cadreco_recognition(h, bgr.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), W, H, C.c_double(1.0), W, H,
-                                 C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.byref(n), pose.ctypes.data_as(C.c_void_p), tag, 64)
-    lib.cadreco_destroy(h)
+    with cadreco_py.handle() as h:
+        assert lib.cadreco_add_obj(h, str(directory).encode()) == 0
+        rc, n, tag, pose = cadreco_py.recognition(h, bgr, depth, K)
     assert rc == 0
-    return n.value, tag.value, pose.reshape(4, 4)
+    return n, tag, pose.reshape(4, 4)
 
 
 def test_facade_translates_the_class_index(tmp_path, oracle, mc):
@@ -351,14 +344,9 @@ def test_facade_translates_the_class_index(tmp_path, oracle, mc):
     dirs = {}
     for name, banks in (("two", [zeta, rand]), ("one", zeta)):
         d = tmp_path / name
-        (d / "depth").mkdir(parents=True)
-        write_linemod_yaml(str(d / "linemod_templates.yml"), banks, clutter.T)
-        for i, md in enumerate(zeta.model_depths):                      # all classes of a directory share depth/<p>.png
-            write_png16(str(d / "depth" / f"{i}.png"), md)
+        write_bank_dir(d, banks, clutter.T, zeta.model_depths)          # all classes of a directory share depth/<p>.png
         dirs[name] = d
-    lib = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    lib.cadreco_create.restype = C.c_void_p
-    lib.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
+    lib = cadreco_py.lib()
     bgr, depth = np.ascontiguousarray(mc["bgrs"][0]), np.ascontiguousarray(mc["depths"][0])
     n2, tag2, pose2 = _facade_recognition(lib, dirs["two"], bgr, depth, mc["K"])
     n1, tag1, pose1 = _facade_recognition(lib, dirs["one"], bgr, depth, mc["K"])

@@ -4,11 +4,11 @@ tests/scene_model.py, the numpy statement of the contract: the records byte for 
 at which each piece can go wrong; tests/test_scene_cpu.py has the rule itself and the argument checks.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import cadreco_py
 import clutter
 import meshes as MS
 import multiclass
@@ -24,7 +24,6 @@ from util import p13 as _p13, pose as _pose
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDX = MS.INDEX
 KT = (60.8, 60.8, 32.0, 24.0)                    # the camera of the 64 x 48 cases
 
@@ -292,7 +291,7 @@ def test_recognised_instances_of_three_classes_are_arbitrated(ctx, oracle, meshe
 
 
 # ---- 7. the facade ---------------------------------------------------------------------------------------------------------------
-INVALID = C.c_int(0x80000001).value
+INVALID = cadreco_py.INVALID
 FACADE_SCENE = np.dtype([("accepted", "<i4"), ("n_model", "<i4"), ("n_missing", "<i4"), ("n_inlier", "<i4"), ("n_front", "<i4"), ("n_behind", "<i4"),
                          ("inlier_ratio", "<f4"), ("behind_ratio", "<f4"), ("kept", "<i4"), ("rival", "<i4"), ("n_shared", "<i4")])
 K0, W, H = (608.0, 608.0, 320.0, 240.0), 640, 480
@@ -301,16 +300,7 @@ K0, W, H = (608.0, 608.0, 320.0, 240.0), 640, 480
 def test_facade_arbitrate_on_a_recognised_frame(ctx, tmp_path):
     """Train a small bank from the OBJ, recognise a frame through the facade, then CadRecoArbitrate the recognised pose and a copy
     of it: the copy is suppressed by entry 0, the records equal the model on the mesh the facade read, and the limits hold."""
-    cad = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    cad.cadreco_create.restype = C.c_void_p
-    cad.cadreco_destroy.argtypes = [C.c_void_p]
-    cad.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
-    cad.cadreco_set_tracking_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
-    cad.cadreco_train_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                       C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    cad.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
-    cad.cadreco_arbitrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double] + [C.c_double] * 4 + \
-                                     [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+    cad = cadreco_py.lib()
     mesh = synth.object_mesh(2)
     obj = str(tmp_path / "object.obj")
     synth.write_obj(obj, mesh)
@@ -319,38 +309,11 @@ def test_facade_arbitrate_on_a_recognised_frame(ctx, tmp_path):
         p = np.ascontiguousarray(poses16, np.float32)
         n = len(p) if n is None else n
         out = np.zeros(max(1, n), FACADE_SCENE)
-        rc = cad.cadreco_arbitrate(h, depth.ctypes.data, depth.shape[1], depth.shape[0], ts, *K0, n, p.ctypes.data, None, tau, ratio, out.ctypes.data)
+        rc = cad.cadreco_arbitrate(h, *cadreco_py.frame_args(depth, ts, K0), n, p.ctypes.data, None, tau, ratio, out.ctypes.data)
         return rc, out[:n]
 
-    h = C.c_void_p(cad.cadreco_create(1))
-    assert h.value
-    try:
-        P = api.view_sphere(0, [700.0], n_inplane=1, inplane_deg=0.0, upper_hemisphere=True)
-        dist = np.array([700.0], np.float32)
-        Ta = (C.c_int * 2)(5, 8)
-        tov = np.full(len(P), -9, np.int32)
-        d = str(tmp_path / "bank")
-        assert cad.cadreco_train_mesh(h, d.encode(), b"mesh", obj.encode(), 1.0, 0, 1, dist.ctypes.data, 1, 1, 0.0, 2, Ta, tov.ctypes.data, len(P)) == 0
-        assert (tov >= 0).any() and cad.cadreco_add_obj(h, d.encode()) == 0
-        nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0) == 0
-        V, N, T = np.zeros((nv.value, 3), np.float32), np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, N.ctypes.data, T.ctypes.data, nv.value, nt.value) == 0
-        view = P[int(np.flatnonzero(tov >= 0)[0])]
-        bgr, dep, msk, _ = ctx.render_views(V, T, view[None], K0, W, H, normals=N)
-        u, v = np.meshgrid(np.arange(float(W)), np.arange(float(H)))
-        m = msk[0] > 0
-        depth = np.ascontiguousarray(np.where(m, dep[0], np.rint(950.0 + 0.06 * u + 0.04 * v)).astype(np.uint16))
-        cell = (np.floor(u / 23.0) + 2 * np.floor(v / 17.0)) % 5
-        col = np.where(m[..., None], bgr[0].astype(np.float64), (70 + 30 * cell)[..., None] * np.array([1.0, 0.9, 0.75]))
-        col = np.ascontiguousarray(np.clip(np.rint(col), 0, 255).astype(np.uint8))
-        pose = np.zeros(16, np.float32)
-        tag = C.create_string_buffer(64)
-        nres = C.c_int(-1)
-        rc = cad.cadreco_recognition(h, col.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), W, H, C.c_double(1.0), W, H,
-                                     C.c_double(K0[0]), C.c_double(K0[1]), C.c_double(K0[2]), C.c_double(K0[3]), C.byref(nres),
-                                     pose.ctypes.data_as(C.c_void_p), tag, 64)
-        assert rc == 0 and nres.value == 1 and tag.value == b"mesh"
+    with cadreco_py.handle() as h:
+        V, N, T, depth, pose = cadreco_py.recognised_mesh_frame(h, ctx, obj, str(tmp_path / "bank"))
         moved = pose.copy()
         moved[3] += 150.0
         poses = np.stack([pose, pose.copy(), moved])
@@ -376,5 +339,3 @@ def test_facade_arbitrate_on_a_recognised_frame(ctx, tmp_path):
             assert np.array_equal(got[name], want), name
         assert got["kept"][:2].tolist() == [1, 0] and got["rival"][1] == 0 and got["n_shared"][1] == got["n_inlier"][0] > 1000
         assert got["rival"][0] == -1 and got["inlier_ratio"][0] > 0.9
-    finally:
-        cad.cadreco_destroy(h)

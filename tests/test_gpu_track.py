@@ -6,11 +6,12 @@ tz = 680 .. 760 mm: detection() drops every point beyond 900 mm (vvalid, ICP/com
 would leave the ICP little or nothing to work on; at 720 mm a crop is about 190 x 145 pixels.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import cadreco_py
+from cadreco_py import INVALID, OPEN_FAILED
 import track_model as TM
 import util
 from fealess_amd import _lib as L
@@ -19,7 +20,6 @@ from util import p13 as _p13, pose as _pose
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 640, 480
 K0 = TM.MODEL_K
 MAX_CROP = 40000
@@ -350,16 +350,10 @@ def test_a_frame_without_the_object_is_lost_only_with_the_gate(tracker, sequence
 
 
 # ---- 8. the facade ------------------------------------------------------------------------------------------------------------
-INVALID, OPEN_FAILED = C.c_int(0x80000001).value, C.c_int(0x80000002).value
 
 
 def test_facade_track_equals_fl_track_batch(ctx, mesh, sequence, tmp_path):
-    cad = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    cad.cadreco_create.restype = C.c_void_p
-    cad.cadreco_destroy.argtypes = [C.c_void_p]
-    cad.cadreco_set_tracking_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
-    cad.cadreco_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double] + [C.c_double] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
-    cad.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
+    cad = cadreco_py.lib()
     obj = str(tmp_path / "object.obj")
     synth.write_obj(obj, mesh)
 
@@ -367,12 +361,10 @@ def test_facade_track_equals_fl_track_batch(ctx, mesh, sequence, tmp_path):
         p = np.ascontiguousarray(poses16, np.float32).copy()
         n = len(p) if n is None else n
         trk = np.full(max(1, n), -7, np.int32)
-        rc = cad.cadreco_track(h, depth.ctypes.data, depth.shape[1], depth.shape[0], ts, *K0, n, p.ctypes.data, trk.ctypes.data)
+        rc = cad.cadreco_track(h, *cadreco_py.frame_args(depth, ts, K0), n, p.ctypes.data, trk.ctypes.data)
         return rc, p, trk[:n]
 
-    h = cad.cadreco_create(1)
-    assert h
-    try:
+    with cadreco_py.handle() as h:
         p0 = TM.pose4x4(synth.pose13(sequence[0]["R"], sequence[0]["t"]))[None]
         scene1 = sequence[1]["scene"]
         assert track(h, scene1, p0)[0] == INVALID                                   # no mesh yet
@@ -384,10 +376,7 @@ def test_facade_track_equals_fl_track_batch(ctx, mesh, sequence, tmp_path):
         assert track(h, scene1, np.tile(p0, (17, 1, 1)))[0] == INVALID              # more than FEALESS_TRACK_MAX_OBJECTS
         assert track(h, scene1, p0, n=0)[0] == 0
         # the mesh as the facade reads it
-        nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0) == 0
-        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, None, T.ctypes.data, nv.value, nt.value) == 0
+        V, _, T = cadreco_py.read_obj(obj)
         ref = api.Tracker(ctx, V, T, W, H, 1, 16, 320 * 240)
         try:
             lost = TM.pose4x4(_p13(LOST_POSE))[None]
@@ -401,5 +390,3 @@ def test_facade_track_equals_fl_track_batch(ctx, mesh, sequence, tmp_path):
                 poses = out
         finally:
             ref.close()
-    finally:
-        cad.cadreco_destroy(h)

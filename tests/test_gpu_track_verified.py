@@ -5,11 +5,11 @@ The poses, scenes, sequence and special poses are those of tests/test_gpu_track.
 tests/test_track_verified_cpu.py derives from the models.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import cadreco_py
 import track_model as TM
 import track_verified_model as TVM
 import util
@@ -21,8 +21,6 @@ from test_track_verified_cpu import MAX_BEHIND, MIN_INLIER
 from util import p13 as _p13, pose as _pose
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -292,39 +290,28 @@ def test_neighbours_are_unaffected(ctx, tracker, mesh, moving, sequence, oracle)
 
 
 # ---- 10. the facade -----------------------------------------------------------------------------------------------------------
-INVALID = C.c_int(0x80000001).value
+INVALID = cadreco_py.INVALID
 
 
 def test_facade_verified_tracking(ctx, mesh, sequence, empty, tmp_path):
-    cad = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    cad.cadreco_create.restype = C.c_void_p
-    cad.cadreco_destroy.argtypes = [C.c_void_p]
-    cad.cadreco_set_tracking_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
-    cad.cadreco_set_verified_tracking.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]
-    cad.cadreco_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double] + [C.c_double] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
-    cad.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
+    cad = cadreco_py.lib()
     obj = str(tmp_path / "object.obj")
     synth.write_obj(obj, mesh)
 
     def track(h, depth, poses16):
         p = np.ascontiguousarray(poses16, np.float32).copy()
         trk = np.full(len(p), -7, np.int32)
-        rc = cad.cadreco_track(h, depth.ctypes.data, depth.shape[1], depth.shape[0], 0.0, *K0, len(p), p.ctypes.data, trk.ctypes.data)
+        rc = cad.cadreco_track(h, *cadreco_py.frame_args(depth, 0.0, K0), len(p), p.ctypes.data, trk.ctypes.data)
         return rc, p, trk
 
-    h = cad.cadreco_create(1)
-    assert h
-    try:
+    with cadreco_py.handle() as h:
         assert cad.cadreco_set_verified_tracking(h, 1, 10.0, 0.0, 0.0, 0) == INVALID          # no mesh yet
         assert cad.cadreco_set_verified_tracking(h, 0, 10.0, 0.0, 0.0, 0) == 0                # off is always fine
         assert cad.cadreco_set_tracking_mesh(h, obj.encode(), 1.0) == 0
         for bad in ((1, -1.0, 0.0, 0.0, 0), (1, 65536.0, 0.0, 0.0, 0), (1, float("nan"), 0.0, 0.0, 0), (1, 10.0, float("nan"), 0.0, 0),
                     (1, 10.0, 0.0, float("inf"), 0), (1, 10.0, 0.0, 0.0, 2), (1, 10.0, 0.0, 0.0, -1)):
             assert cad.cadreco_set_verified_tracking(h, *bad) == INVALID, bad
-        nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0) == 0
-        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, None, T.ctypes.data, nv.value, nt.value) == 0
+        V, _, T = cadreco_py.read_obj(obj)
         ref = api.Tracker(ctx, V, T, W, H, 1, 16, 320 * 240)
         try:
             poses = np.stack([TM.pose4x4(sequence[0]["pose"]), TM.pose4x4(_p13(LOST_POSE))])
@@ -351,5 +338,3 @@ def test_facade_verified_tracking(ctx, mesh, sequence, empty, tmp_path):
                 assert again[0] == rc and again[1].tobytes() == out.tobytes() and again[2].tolist() == trk.tolist()
         finally:
             ref.close()
-    finally:
-        cad.cadreco_destroy(h)

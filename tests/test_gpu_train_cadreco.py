@@ -7,24 +7,11 @@ import os
 import numpy as np
 import pytest
 
+from cadreco_py import INVALID, OPEN_FAILED, lib as _lib, recognition
 from fealess_amd import synth
 from fealess_amd.bank import TemplateBank
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID, OPEN_FAILED = C.c_int(0x80000001).value, C.c_int(0x80000002).value
-
-
-def _lib():
-    lib = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    lib.cadreco_create.restype = C.c_void_p
-    lib.cadreco_destroy.argtypes = [C.c_void_p]
-    lib.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
-    lib.cadreco_train_views.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.cadreco_read_linemod.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 4
-    lib.cadreco_read_png16.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    return lib
 
 
 def _views():
@@ -89,15 +76,10 @@ def test_train_views_then_add_obj_and_recognise(tmp_path, oracle):
     assert bank.n_pyramids == 4
 
     assert lib.cadreco_add_obj(h, str(d).encode()) == 0
-    pose = np.zeros(16, np.float32)
-    tag = C.create_string_buffer(64)
-    n = C.c_int(-1)
     for v in (1, 3):
         bgr, depth = views[v][0], views[v][1]
-        rc = lib.cadreco_recognition(h, bgr.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), 640, 480, C.c_double(1.0),
-                                     640, 480, C.c_double(synth.FX), C.c_double(synth.FY), C.c_double(synth.CX), C.c_double(synth.CY),
-                                     C.byref(n), pose.ctypes.data_as(C.c_void_p), tag, 64)
-        assert rc == 0 and n.value == 1 and tag.value == b"obj"
+        rc, n, tag, pose = recognition(h, bgr, depth, (synth.FX, synth.FY, synth.CX, synth.CY))
+        assert rc == 0 and n == 1 and tag == b"obj"
         exp = oracle.recognition(bgr, depth, (synth.FX, synth.FY, synth.CX, synth.CY), [5, 8], bank, 75.0, 10, 0.5, 0.01)
         assert exp["found"] == 1
         assert np.abs(pose.reshape(4, 4) - exp["pose"]).max() <= 1e-4

@@ -20,46 +20,17 @@ import re
 import numpy as np
 import pytest
 
+from cadreco_py import INVALID, OPEN_FAILED, lib as _lib, read_obj, recognition, train_mesh
 from fealess_amd import api, synth
 from fealess_amd.bank import TemplateBank
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID, OPEN_FAILED = C.c_int(0x80000001).value, C.c_int(0x80000002).value
 K0 = (synth.FX, synth.FY, synth.CX, synth.CY)
 SPHERE = dict(subdivisions=1, upper=1, distances=(600.0, 700.0), n_inplane=3, inplane_deg=10.0)
 
 
-def _lib():
-    lib = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    lib.cadreco_create.restype = C.c_void_p
-    lib.cadreco_destroy.argtypes = [C.c_void_p]
-    lib.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
-    lib.cadreco_train_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                       C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    lib.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
-    lib.cadreco_read_png16.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    return lib
-
-
 def _train(lib, h, d, obj, n_views, sphere=SPHERE, levels=2, T=(5, 8)):
-    dist = np.array(sphere["distances"], np.float32)
-    Ta = (C.c_int * len(T))(*T)
-    tov = np.full(n_views, -9, np.int32)
-    rc = lib.cadreco_train_mesh(h, str(d).encode(), b"mesh", str(obj).encode(), 1.0, sphere["subdivisions"], sphere["upper"],
-                                dist.ctypes.data, len(dist), sphere["n_inplane"], sphere["inplane_deg"], levels, Ta, tov.ctypes.data, n_views)
-    return rc, tov
-
-
-def _read_mesh(lib, path):
-    nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-    assert lib.cadreco_read_obj(str(path).encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0) == 0
-    V = np.zeros((nv.value, 3), np.float32)
-    N = np.zeros((nv.value, 3), np.float32)
-    T = np.zeros((nt.value, 3), np.int32)
-    assert lib.cadreco_read_obj(str(path).encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, N.ctypes.data, T.ctypes.data,
-                                nv.value, nt.value) == 0
-    return V, (N if hn.value else None), T
+    return train_mesh(h, d, obj, n_views, sphere, levels, T)
 
 
 def _yaml_poses(path):
@@ -108,7 +79,7 @@ def test_train_mesh_then_add_obj_and_recognise(tmp_path, ctx, oracle):
     assert sorted(os.listdir(d / "depth"), key=lambda s: int(s[:-4])) == [f"{i}.png" for i in range(ok.sum())]
 
     # the renders the trainer saw (the mesh as the OBJ reader gives it; no colours: FL_RENDER_GREY) and the oracle's bank
-    V, N, T = _read_mesh(lib, obj)
+    V, N, T = read_obj(obj)
     assert N is not None and len(T) == len(mesh["triangles"])
     bgr, dep, msk, _ = ctx.render_views(V, T, P, K0, 640, 480, normals=N)
     px = np.zeros(640 * 480, np.uint16)
@@ -129,9 +100,6 @@ def test_train_mesh_then_add_obj_and_recognise(tmp_path, ctx, oracle):
 
     assert lib.cadreco_add_obj(h, str(d).encode()) == 0
     grid = [p[:12].reshape(3, 4)[:, :3].astype(np.float64) for p in P[ok]]
-    pose = np.zeros(16, np.float32)
-    tag = C.create_string_buffer(64)
-    nres = C.c_int(-1)
     rng = np.random.default_rng(5)
     errs = []
     idx = np.flatnonzero(ok)
@@ -140,11 +108,9 @@ def test_train_mesh_then_add_obj_and_recognise(tmp_path, ctx, oracle):
         R = synth.rot_x(np.radians(rng.uniform(-4, 4))) @ synth.rot_y(np.radians(rng.uniform(-4, 4))) @ synth.rot_z(np.radians(rng.uniform(-4, 4))) @ R0
         t = np.array([rng.uniform(-40, 40), rng.uniform(-30, 30), dist + rng.uniform(-20, 20)])
         bgr_s, dep_s = _scene(ctx, V, N, T, R, t, seed=100 + k)
-        rc = lib.cadreco_recognition(h, bgr_s.ctypes.data_as(C.c_void_p), dep_s.ctypes.data_as(C.c_void_p), 640, 480, C.c_double(1.0), 640, 480,
-                                     C.c_double(K0[0]), C.c_double(K0[1]), C.c_double(K0[2]), C.c_double(K0[3]), C.byref(nres),
-                                     pose.ctypes.data_as(C.c_void_p), tag, 64)
+        rc, nres, tag, pose = recognition(h, bgr_s, dep_s, K0)
         exp = oracle.recognition(bgr_s, dep_s, K0, [5, 8], bank, 75.0, 10, 0.5, 0.01)
-        assert rc == 0 and nres.value == exp["found"] == 1 and tag.value == b"mesh", k
+        assert rc == 0 and nres == exp["found"] == 1 and tag == b"mesh", k
         assert np.abs(pose.reshape(4, 4) - exp["pose"]).max() <= 1e-4, k
         got = pose.reshape(4, 4).astype(np.float64)
         tid = int(exp["best"]["template_id"])

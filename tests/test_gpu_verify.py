@@ -6,11 +6,11 @@ load, a half-full last strip), 160 x 120 = 2.3 strips, 64 x 48 = less than one s
 multiple of eight (the pixel-by-pixel path) and leaves 0.83 of a last strip.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import cadreco_py
 import track_model as TM
 import verify_model as VM
 from fealess_amd import _lib as L
@@ -19,7 +19,6 @@ from util import p13 as _p13, pose as _pose
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 640, 480
 K0 = (608.0, 608.0, 320.0, 240.0)
 KS = (152.0, 152.0, 80.0, 60.0)                 # the same field of view at 160 x 120
@@ -318,8 +317,7 @@ def test_more_poses_than_max_tracks_is_refused(tracker, scenes):
 
 
 # ---- 8. the facade ------------------------------------------------------------------------------------------------------------
-INVALID = C.c_int(0x80000001).value
-SPHERE = dict(subdivisions=0, upper=1, distances=(700.0,), n_inplane=1, inplane_deg=0.0)
+INVALID = cadreco_py.INVALID
 FACADE_RESULT = np.dtype([("accepted", "<i4"), ("n_model", "<i4"), ("n_missing", "<i4"), ("n_inlier", "<i4"), ("n_front", "<i4"), ("n_behind", "<i4"),
                           ("inlier_ratio", "<f4"), ("behind_ratio", "<f4")])
 
@@ -328,15 +326,7 @@ def test_facade_verify_on_a_recognised_frame(ctx, tmp_path):
     """Train a small bank from the OBJ, recognise a frame through the facade, then CadRecoVerify the recognised pose and the
     same pose moved 150 mm: the records equal the model on the mesh the facade read, and a gate halfway between the model's two
     inlier ratios accepts the first and rejects the second."""
-    cad = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    cad.cadreco_create.restype = C.c_void_p
-    cad.cadreco_destroy.argtypes = [C.c_void_p]
-    cad.cadreco_add_obj.argtypes = [C.c_void_p, C.c_char_p]
-    cad.cadreco_set_tracking_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
-    cad.cadreco_train_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                       C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    cad.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
-    cad.cadreco_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double] + [C.c_double] * 4 + [C.c_int, C.c_void_p, C.c_float, C.c_void_p]
+    cad = cadreco_py.lib()
     mesh = synth.object_mesh(2)
     obj = str(tmp_path / "object.obj")
     synth.write_obj(obj, mesh)
@@ -345,40 +335,12 @@ def test_facade_verify_on_a_recognised_frame(ctx, tmp_path):
         p = np.ascontiguousarray(poses16, np.float32)
         n = len(p) if n is None else n
         out = np.zeros(max(1, n), FACADE_RESULT)
-        rc = cad.cadreco_verify(h, depth.ctypes.data, depth.shape[1], depth.shape[0], ts, *K0, n, p.ctypes.data, tau, out.ctypes.data)
+        rc = cad.cadreco_verify(h, *cadreco_py.frame_args(depth, ts, K0), n, p.ctypes.data, tau, out.ctypes.data)
         return rc, out[:n]
 
-    h = C.c_void_p(cad.cadreco_create(1))
-    assert h.value
-    try:
-        # train and load
-        P = api.view_sphere(0, list(SPHERE["distances"]), n_inplane=1, inplane_deg=0.0, upper_hemisphere=True)
-        dist = np.array(SPHERE["distances"], np.float32)
-        Ta = (C.c_int * 2)(5, 8)
-        tov = np.full(len(P), -9, np.int32)
-        d = str(tmp_path / "bank")
-        assert cad.cadreco_train_mesh(h, d.encode(), b"mesh", obj.encode(), 1.0, 0, 1, dist.ctypes.data, 1, 1, 0.0, 2, Ta, tov.ctypes.data, len(P)) == 0
-        assert (tov >= 0).any() and cad.cadreco_add_obj(h, d.encode()) == 0
-        # the mesh as the facade reads it, and a frame that shows it at a trained view
-        nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0) == 0
-        V, N, T = np.zeros((nv.value, 3), np.float32), np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        assert cad.cadreco_read_obj(obj.encode(), 1.0, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, N.ctypes.data, T.ctypes.data, nv.value, nt.value) == 0
-        view = P[int(np.flatnonzero(tov >= 0)[0])]
-        bgr, dep, msk, _ = ctx.render_views(V, T, view[None], K0, W, H, normals=N)
-        u, v = np.meshgrid(np.arange(float(W)), np.arange(float(H)))
-        m = msk[0] > 0
-        depth = np.ascontiguousarray(np.where(m, dep[0], np.rint(950.0 + 0.06 * u + 0.04 * v)).astype(np.uint16))
-        cell = (np.floor(u / 23.0) + 2 * np.floor(v / 17.0)) % 5
-        col = np.where(m[..., None], bgr[0].astype(np.float64), (70 + 30 * cell)[..., None] * np.array([1.0, 0.9, 0.75]))
-        col = np.ascontiguousarray(np.clip(np.rint(col), 0, 255).astype(np.uint8))
-        pose = np.zeros(16, np.float32)
-        tag = C.create_string_buffer(64)
-        nres = C.c_int(-1)
-        rc = cad.cadreco_recognition(h, col.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), W, H, C.c_double(1.0), W, H,
-                                     C.c_double(K0[0]), C.c_double(K0[1]), C.c_double(K0[2]), C.c_double(K0[3]), C.byref(nres),
-                                     pose.ctypes.data_as(C.c_void_p), tag, 64)
-        assert rc == 0 and nres.value == 1 and tag.value == b"mesh"
+    with cadreco_py.handle() as h:
+        # train and load, the mesh as the facade reads it, and a frame that shows it at a trained view
+        V, N, T, depth, pose = cadreco_py.recognised_mesh_frame(h, ctx, obj, str(tmp_path / "bank"))
         moved = pose.copy()
         moved[3] += 150.0
         poses = np.stack([pose, moved])
@@ -402,5 +364,3 @@ def test_facade_verify_on_a_recognised_frame(ctx, tmp_path):
         gate = (float(exp["inlier_ratio"][0]) + float(exp["inlier_ratio"][1])) / 2
         assert exp["inlier_ratio"][0] > gate > exp["inlier_ratio"][1] and exp["inlier_ratio"][0] > 0.9
         assert got["inlier_ratio"][0] >= gate > got["inlier_ratio"][1] and got["accepted"].tolist() == [1, 1]
-    finally:
-        cad.cadreco_destroy(h)

@@ -2,21 +2,13 @@
 with: it round-trips through cadreco_read_png16, and an independent zlib + struct decode of the file finds the PNG
 signature, an IHDR of 16-bit greyscale, valid chunk CRCs, filter byte 0 on every row and big-endian samples."""
 import ctypes as C
-import os
 import struct
 import zlib
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _cad():
-    lib = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    lib.cadreco_write_png16.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
-    lib.cadreco_read_png16.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    return lib
+from cadreco_py import lib as _cad
 
 
 def _decode(path):

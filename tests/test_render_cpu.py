@@ -2,18 +2,16 @@
 tessellated object; fl_view_sphere (counts, rotations, the optical axis, in-plane steps, the poles, the cap query, refusals);
 fealess::ReadObj through cadreco_read_obj (face forms, negative indices, polygons, normals, scale, malformed files)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import raster_model as RM
+from cadreco_py import INVALID, OPEN_FAILED, read_obj as _read
 from fealess_amd import _lib as L
 from fealess_amd import api, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K0 = (synth.FX, synth.FY, synth.CX, synth.CY)
-INVALID, OPEN_FAILED = C.c_int(0x80000001).value, C.c_int(0x80000002).value
 
 
 def _erode(m, r):
@@ -137,26 +135,6 @@ def test_view_sphere_cap_query_and_refusals():
     assert lib.fl_view_sphere(1, 0, d.ctypes.data, 1, 3, 15.0, None, 126, C.byref(n2)) == L.FL_ERR_INVALID
     with pytest.raises(api.FealessError):
         api.view_sphere(1, [-5.0])
-
-
-def _cad():
-    lib = C.CDLL(os.path.join(ROOT, "fealess_amd", "cadreco", "libcadreco_hip.so"))
-    lib.cadreco_read_obj.argtypes = [C.c_char_p, C.c_float] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2
-    return lib
-
-
-def _read(path, scale=1.0):
-    lib = _cad()
-    nv, nt, hn = C.c_int(), C.c_int(), C.c_int()
-    rc = lib.cadreco_read_obj(str(path).encode(), scale, C.byref(nv), C.byref(nt), C.byref(hn), None, None, None, 0, 0)
-    if rc:
-        return rc
-    V = np.zeros((nv.value, 3), np.float32)
-    N = np.zeros((nv.value, 3), np.float32)
-    T = np.zeros((nt.value, 3), np.int32)
-    assert lib.cadreco_read_obj(str(path).encode(), scale, C.byref(nv), C.byref(nt), C.byref(hn), V.ctypes.data, N.ctypes.data, T.ctypes.data,
-                                nv.value, nt.value) == 0
-    return V, (N if hn.value else None), T
 
 
 def test_read_obj_forms(tmp_path):
