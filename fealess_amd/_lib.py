@@ -239,6 +239,7 @@ DEV_SIGNATURES = {
     "fl_dev_group_jobs": (_I, [_P, _P, _I, C.POINTER(InstanceParams), _P, _P, _P, _P, _P]),
     "fl_dev_extract_select": (_I, [_P, _I, _P]),
     "fl_dev_front_images": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t]),
+    "fl_dev_ranged_math": (_I, [_P, _I, C.c_uint32, C.c_uint32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]),
     "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_dev_tracker_create_host_meshes": (_I, [C.POINTER(Mesh), _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "fl_dev_tracker_stage_ms": (_I, [_P, C.POINTER(C.c_float)]),

@@ -15,10 +15,12 @@
 // Both quantisers walk chunks of rows whose height a whole-image launch picks from the batch size (fl_eager_chunk_rows).
 //
 // The integer stages are exact; the float stages restate OpenCV 3.x's arithmetic operator by
-// operator (built with -ffp-contract=off; IEEE divide/sqrt are hipcc's default), so they equal
+// operator (built with -ffp-contract=off; IEEE divide/sqrt are hipcc's default, and the quantisers' square root, reciprocal
+// and quotient are those operations without their range handling: fl_ranged_math.h), so they equal
 // oracle/frontend_oracle.c bit for bit.  OpenCV itself is not available to compare with:
 // "parity unpinned" at this boundary.
 #include "fl_internal.h"
+#include "fl_ranged_math.h"
 #include <float.h>
 #include <type_traits>
 
@@ -45,7 +47,8 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
   // ax >= ay: c = ay / (ax + eps), a = poly(c); else c = ax / (ay + eps), a = 90 - poly(c) -- the same operations on swapped
   // operands, so one division and one polynomial serve both (as two branches a wave with lanes of both kinds ran each in turn)
   const bool steep = !(ax >= ay);
-  const float c = (steep ? ax : ay) / ((steep ? ay : ax) + (float)DBL_EPSILON);
+  // (div_rn: the correctly rounded quotient without the range handling of `/`; the operands are inside its stated domain)
+  const float c = div_rn(steep ? ax : ay, (steep ? ay : ax) + (float)DBL_EPSILON);
   const float c2 = c * c;
   const float poly = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
   float a = steep ? 90.f - poly : poly;
@@ -68,10 +71,9 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
 #define CQ_CH 60
 
 // Neighbour lanes by whole-wave DPP shifts (gfx9 wave_shr:1 / wave_shl:1): one v_mov_dpp instead of the
-// ds_bpermute + index arithmetic of __shfl_up / __shfl_down; lane 0 / lane 63 keep their own value, as those do.
-__device__ __forceinline__ unsigned wave_from_prev(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xF, 0xF, false); }
-__device__ __forceinline__ unsigned wave_from_next(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130, 0xF, 0xF, false); }
-// the same where lane 0 / lane 63 may receive anything (0): no copy of v into the destination first
+// ds_bpermute + index arithmetic of __shfl_up / __shfl_down.  Lane 0 / lane 63, which have no such neighbour, receive 0
+// (bound_ctrl): keeping their own value, as those do, costs a copy of v into the destination ahead of every shift, and nothing
+// that either quantiser stores depends on what these lanes get (see the callers).
 __device__ __forceinline__ unsigned wave_from_prev0(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true); }
 __device__ __forceinline__ unsigned wave_from_next0(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, true); }
 
@@ -636,6 +638,38 @@ static int ensure_normal_lut(fl_context *ctx)
 
 __device__ __forceinline__ unsigned dq_pattern(unsigned cls) { return cls >= 8u ? 0u : 0x11111111u << (4u * cls); }
 
+// a * b of factors that fit 24 bits (signed: -2^23 .. 2^23 - 1; unsigned: below 2^24), low 32 bits of the product: the
+// full-rate v_mul_i32_i24 / v_mul_u32_u24, whatever the compiler can or cannot prove about the factors (dq_normal_pattern)
+__device__ __forceinline__ int dq_mul_i24(int a, int b)
+{
+  int r;
+  asm("v_mul_i32_i24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ unsigned dq_mul_u24(unsigned a, unsigned b)
+{
+  unsigned r;
+  asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// K * b, K a constant of the instruction (no register holds it)
+template <int K>
+__device__ __forceinline__ int dq_mul_i24_by(int b)
+{
+  int r;
+  asm("v_mul_i32_i24 %0, %1, %2" : "=v"(r) : "n"(K), "v"(b));
+  return r;
+}
+// K * b + c, K an inline constant of the instruction (0 .. 64): v_mad_u32_u24
+template <unsigned K>
+__device__ __forceinline__ unsigned dq_mad_u24_by(unsigned b, unsigned c)
+{
+  static_assert(K <= 64, "not an inline constant");
+  unsigned r;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(b), "n"(K), "v"(c));
+  return r;
+}
+
 // The normal of one pixel from values: its depth d and the eight ring neighbours n0..n7, in the order (-,-) (0,-) (+,-) (-,0)
 // (+,0) (-,+) (0,+) (+,+).  interior: y >= 5 && y < h - 6 && x >= 5 && x < w - 6 (loop bounds :619, :624); of a lane that is not
 // interior, or whose d is not below distance_threshold, nothing is looked at (its taps are clamped into the image and mean
@@ -657,18 +691,22 @@ __device__ __forceinline__ unsigned dq_normal_pattern(bool interior, int d, int 
   const int m0 = g0 ? e0 : 0, m1 = g1 ? e1 : 0, m2 = g2 ? e2 : 0, m3 = g3 ? e3 : 0, m4 = g4 ? e4 : 0, m5 = g5 ? e5 : 0,
             m6 = g6 ? e6 : 0, m7 = g7 ? e7 : 0;
   const int corners = f0 + f2 + f5 + f7;
-  // every factor below fits 24 bits, so the products are v_mul_i32_i24 (full rate) instead of the quarter-rate 32-bit multiply
-  // the compiler has to assume: |A| <= 150, det <= 22500, and with t <= 400 |b| <= 30 * 399, |dd| < 3.0e6, d < 65536
-  const int A0 = __mul24(25, corners + f3 + f4), A3 = __mul24(25, corners + f1 + f6), A1 = __mul24(25, (f0 + f7) - (f2 + f5));
-  const int det = __mul24(A0, A3) - __mul24(A1, A1);       // <= 22500
+  // Every factor below fits 24 bits: |A| <= 150, 0 <= det <= 22500, and with t <= 400 |b| <= 30 * 399, |dd| < 3.0e6, d < 65536.
+  // The products of det and of the t <= 400 path are the full-rate 24-bit multiplies BY NAME (dq_mul_i24, dq_mul_u24).  __mul24 is a
+  // 32-bit multiply of the arguments' sign-extended low 24 bits, and what the compiler makes of it depends on what it knows
+  // of them: it folded the extension into a factor that was itself a product (5 * x became (x * (5 << 8)) >> 8) and, with d's
+  // 16 bits known, dropped it from det * d, and each time a v_mul_lo_u32 (quarter rate) was left.  The products by 5 and
+  // by 25 are plain C: v_lshl_add_u32, and 24-bit multiplies by the constant.
+  const int A0 = 25 * (corners + f3 + f4), A3 = 25 * (corners + f1 + f6), A1 = 25 * ((f0 + f7) - (f2 + f5));
+  const int det = (int)dq_mul_u24((unsigned)A0, (unsigned)A3) - dq_mul_i24(A1, A1);       // 0 <= det <= 22500: |A1| <= 25 * corners <= A0, A3
   float nx, ny, nz;
   if (t <= 400) {
     // |b| <= 30 * 399, |dd| <= 250 * |b| < 3.0e6: 617 * dd and det * d (<= 22500 * 65535) fit in int32
-    const int b0 = __mul24(5, (m2 + m4 + m7) - (m0 + m3 + m5)), b1 = __mul24(5, (m5 + m6 + m7) - (m0 + m1 + m2));
-    const int ddx = __mul24(A3, b0) - __mul24(A1, b1), ddy = __mul24(A0, b1) - __mul24(A1, b0);
-    nx = (float)__mul24(617, ddx);
-    ny = (float)__mul24(617, ddy);
-    nz = (float)(-__mul24(det, d));
+    const int b0 = 5 * ((m2 + m4 + m7) - (m0 + m3 + m5)), b1 = 5 * ((m5 + m6 + m7) - (m0 + m1 + m2));
+    const int ddx = dq_mul_i24(A3, b0) - dq_mul_i24(A1, b1), ddy = dq_mul_i24(A0, b1) - dq_mul_i24(A1, b0);
+    nx = (float)dq_mul_i24_by<617>(ddx);
+    ny = (float)dq_mul_i24_by<617>(ddy);
+    nz = (float)(-(int)dq_mul_u24((unsigned)det, (unsigned)d));
   } else {
     const int b0 = 5 * ((m2 + m4 + m7) - (m0 + m3 + m5)), b1 = 5 * ((m5 + m6 + m7) - (m0 + m1 + m2));
     const long long ddx = (long long)A3 * b0 - (long long)A1 * b1, ddy = -(long long)A1 * b0 + (long long)A0 * b1;
@@ -676,13 +714,17 @@ __device__ __forceinline__ unsigned dq_normal_pattern(bool interior, int d, int 
     ny = (float)(617LL * ddy);
     nz = (float)(-(long long)det * d);
   }
-  const float s = sqrtf(nx * nx + ny * ny + nz * nz);
-  if (!(s > 0)) return dq_pattern(0);                       // shadows of the depth sensor
+  // nx, ny, nz are integers (converted, beyond 2^24 rounded, to float): their sum of squares is 0 or in [1, 2^80) -- 617 * dd
+  // stays below 2^39 at any threshold, det * d below 2^31 -- and its root s is 0 exactly where the sum is, else in [1, 2^40):
+  // inside the domains of sqrt_rn and rcp_rn (fl_ranged_math.h), which give the bits of sqrtf(sum) and 1.0f / s
+  const float sum = nx * nx + ny * ny + nz * nz;
+  if (!(sum > 0)) return dq_pattern(0);                     // s == 0: shadows of the depth sensor
+  const float s = sqrt_rn(sum);
   // (Round 4 measured the LUT indices from a v_rsq_f32 ESTIMATE with the correctly rounded sqrtf + division only for lanes
   // within 4e-5 of a bin edge -- exact by construction, bit-equal in the tests -- and it was 2 % SLOWER (front-end 18.04
   // against 17.70 ms per 4096 eager frames): the test for "near an edge" costs what the two correctly rounded operations
   // cost, and a wavefront takes the exact branch whenever one of its 64 lanes is near an edge.  profiles/README.md.)
-  const float inv = 1.0f / s;
+  const float inv = rcp_rn(s);
   nx *= inv;
   ny *= inv;
   nz *= inv;
@@ -691,7 +733,8 @@ __device__ __forceinline__ unsigned dq_normal_pattern(bool interior, int d, int 
   const int v3 = (int)(nz * 20 + 20);
   // Q7: v3 == 20 is an out-of-bounds read in the reference; defined as 0 here
   if (!(v1 >= 0 && v1 <= 19 && v2 >= 0 && v2 <= 19 && v3 >= 0 && v3 <= 19)) return dq_pattern(0);
-  const unsigned v = lut[v2 * 20 + v1];
+  // index < 400: one v_mad_u32_u24 (as v2 * 20 + v1 the compiler widens it to a v_mad_u64_u32, quarter rate)
+  const unsigned v = lut[dq_mad_u24_by<20>((unsigned)v2, (unsigned)v1)];
   return dq_pattern(v ? (unsigned)(32 - __clz(v)) : 0u);   // 0 -> class 0, 1<<k -> class k+1 (ascending in value)
 }
 
@@ -747,7 +790,9 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t *__restri
   auto finish = [&](int yv) __attribute__((always_inline)) {
     if (yv < y0 + 2) return;                               // wave-uniform
     const unsigned col = p0 + p1 + p2 + p3 + p4;           // fields <= 5
-    const unsigned a1 = wave_from_next(col), b1 = wave_from_prev(col), a2 = wave_from_next(a1), b2 = wave_from_prev(b1);
+    // single DPP moves that leave 0 where a shift has no source lane: a1 of lane 63, a2 of lanes 62 and 63, b1 of lane 0, b2 of
+    // lanes 0 and 1.  The lanes that store are 2 .. 61: lane 61 takes col of lanes 59 .. 63, lane 2 of lanes 0 .. 4
+    const unsigned a1 = wave_from_next0(col), b1 = wave_from_prev0(col), a2 = wave_from_next0(a1), b2 = wave_from_prev0(b1);
     const unsigned s3 = col + a1 + b1, s2 = a2 + b2;       // fields <= 15, <= 10
     const unsigned te = (s3 & 0x0F0F0F0Fu) + (s2 & 0x0F0F0F0Fu) + 0x73737373u;
     const unsigned to = ((s3 >> 4) & 0x0F0F0F0Fu) + ((s2 >> 4) & 0x0F0F0F0Fu) + 0x73737373u;
@@ -978,6 +1023,68 @@ extern "C" int fl_dev_front_images(fl_context *ctx, const uint8_t *bgr, const ui
       if (l) FL_HIP(ctx, hipMemcpyAsync(out + 2 * px, im.bgr[l] + f * packed, 3 * px, hipMemcpyDeviceToHost, ctx->stream));
       out += (l ? 5 : 2) * px;
     }
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FL_OK;
+}
+
+// Development / test aid (not part of the ABI): the functions of fl_ranged_math.h against the compiler's own operations, which
+// this file's flags make correctly rounded, over EVERY argument first .. last of a domain (tests/test_gpu_ranged_math.py).
+//   which 0: sqrt_rn(x) against sqrtf(x), 1: rcp_rn(x) against 1.0f / x, x the float with the bit pattern a;
+//   which 2: div_rn(n, d) against n / d, n and d what fast_atan2_deg divides for |x| = a % 1021 and |y| = a / 1021 (both 0 .. 1020)
+// Adds the number of results that differ in any bit to *n_bad and keeps the smallest such a in *first_bad.
+#define FL_RM_SOBEL_MAX 1020u                              // |dx|, |dy| <= 4 * 255
+__global__ __launch_bounds__(256) void k_ranged_math(int which, uint32_t first, uint32_t last, unsigned long long *n_bad, uint32_t *first_bad)
+{
+  const uint64_t count = (uint64_t)last - first + 1, stride = (uint64_t)gridDim.x * blockDim.x;
+  unsigned bad = 0;
+  uint32_t lowest = 0xFFFFFFFFu;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const uint32_t a = first + (uint32_t)i;
+    float got, exp;
+    if (which == 0) {
+      const float x = __uint_as_float(a);
+      got = sqrt_rn(x);
+      exp = sqrtf(x);
+    } else if (which == 1) {
+      const float x = __uint_as_float(a);
+      got = rcp_rn(x);
+      exp = 1.0f / x;
+    } else {
+      const float ax = (float)(a % (FL_RM_SOBEL_MAX + 1u)), ay = (float)(a / (FL_RM_SOBEL_MAX + 1u));
+      const bool steep = !(ax >= ay);
+      const float n = steep ? ax : ay, d = (steep ? ay : ax) + (float)DBL_EPSILON;
+      got = div_rn(n, d);
+      exp = n / d;
+    }
+    if (__float_as_uint(got) != __float_as_uint(exp)) {
+      ++bad;
+      lowest = min(lowest, a);
+    }
+  }
+  if (bad) {
+    atomicAdd(n_bad, (unsigned long long)bad);
+    atomicMin(first_bad, lowest);
+  }
+}
+
+extern "C" int fl_dev_ranged_math(fl_context *ctx, int which, uint32_t first_bits, uint32_t last_bits, unsigned long long *n_mismatch,
+                                  uint32_t *first_bad_bits)
+{
+  if (!ctx || !n_mismatch || !first_bad_bits || which < 0 || which > 2 || first_bits > last_bits ||
+      (which == 2 && last_bits >= (FL_RM_SOBEL_MAX + 1u) * (FL_RM_SOBEL_MAX + 1u)))
+    return FL_ERR_INVALID;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  void *s = nullptr;
+  int rc = fl_scratch(ctx, 16, &s);
+  if (rc) return rc;
+  unsigned long long *d_bad = (unsigned long long *)s;
+  uint32_t *d_first = (uint32_t *)(d_bad + 1);
+  FL_HIP(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
+  FL_HIP(ctx, hipMemsetAsync(d_first, 0xFF, 4, ctx->stream));
+  hipLaunchKernelGGL(k_ranged_math, dim3(1024), dim3(256), 0, ctx->stream, which, first_bits, last_bits, d_bad, d_first);
+  FL_HIP(ctx, hipGetLastError());
+  FL_HIP(ctx, hipMemcpyAsync(n_mismatch, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(first_bad_bits, d_first, 4, hipMemcpyDeviceToHost, ctx->stream));
   FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return FL_OK;
 }
