@@ -24,7 +24,7 @@
 // distance chain" in icp_run), and a frame's latency drops to about what its two sequential chains cost.
 //
 // Where things are.  This file: workspace and LDS layout, the float32 chains (chain_tile, chain_deferred), l2dist_phase, the pose solvers,
-// icp_run (the algorithm: A1 search, A2 sums, solve, distances), crop_clouds / build_tile_order, the kernels, the host entries and, in one
+// first_pass (the 256-thread parity kernel's fused pre-translation, copyPoints, initial distances and iteration-1 sums), icp_run (the algorithm: A1 search, A2 sums, solve, distances), crop_clouds / build_tile_order, the kernels, the host entries and, in one
 // block at the end, the dev / test entries.  fl_icp_search.h (included here only): what the searches are made of -- loads, bnd[], the grid
 // and its search, the reference image, wave reductions, windows -- and the organised searches org_search / org_search_pipe themselves.
 // Built with -ffp-contract=off: one IEEE binary32/64 operation per operator.
@@ -42,6 +42,10 @@
 #define ICP_DT 512                 // terms per block of the deferred dist_mean chain (two float4 per lane of the chain wave)
 #ifdef FL_ICP_PHASES
 #define TSTAMP(k) do { if (threadIdx.x == 0) { long long now_ = clock64(); S.tacc[k] += now_ - S.tlast; S.tlast = now_; } } while (0)
+// set-up passes of k_icp_pipeline (S.tset[k]: 0 crop, 1 tile counts, 2 tile placing, 3 getMean, 4 pre-translation, 5 copyPoints,
+// 6 initial distances (fused: the whole first pass), 7 iteration 1's sums, 9 everything between them); summed over the launch's
+// workgroups in g_icp_setup and printed by the launcher
+#define SSTAMP(k) do { if (threadIdx.x == 0) { long long now_ = clock64(); S.tset[k] += now_ - S.tslast; S.tslast = now_; } } while (0)
 // chain phases: what the chain wave spends adding and at the tile barrier (S.hist[k], [k + 1]), and what the first producer
 // wave spends at the tile barriers (S.hist[k]; one barrier in `every` is timed); units of 16 cycles
 #define CH_STAMP_BEGIN long long c_add = 0, c_bar = 0, c_last = clock64()
@@ -56,6 +60,7 @@
 #define ST_STAMP_END { if ((threadIdx.x & 63) == 0) for (int k = 0; k < 5; ++k) atomicAdd(&S.stime[k], (unsigned long long)st_acc[k]); }
 #else
 #define TSTAMP(k) do { } while (0)
+#define SSTAMP(k) do { } while (0)
 #define CH_STAMP_BEGIN
 #define CH_STAMP(v) { }
 #define CH_STAMP_END(k) { }
@@ -240,11 +245,13 @@ struct IcpSharedT {
   static constexpr int STAGE_FLOATS = NW * 384 * 4, TILE_FLOATS = 2 * 15 * TS + 2 * TQ;
   alignas(16) float stage_pad[STAGE_FLOATS > TILE_FLOATS ? STAGE_FLOATS - TILE_FLOATS : 4];
   alignas(16) float dchain[2][ICP_DT];   // the deferred dist_mean chain's staging (chain wave only)
+  float first_sums[16];                  // 256-thread parity kernel: iteration 1's 15 sums, left by first_pass until the loop head has decided
 #ifdef FL_ICP_PHASES
   long long tacc[16], tlast, tkernel;   // tkernel: clock at kernel entry (k_icp_pipeline)
   long long wall0;                      // wall_clock64() (constant 100 MHz) at kernel entry
   unsigned long long stime[8];         // FL_ICP_PHASES: cycles of the search step's segments, summed over the workgroup's waves
   unsigned hist[40];                    // organised search: [0,16) union (W class x H class), [16,26) largest lane window height, [26,30) width class
+  long long tset[10], tslast;           // SSTAMP
 #endif
 };
 
@@ -840,6 +847,119 @@ __device__ __forceinline__ void icp_result_none(fl_icp_result *res)
   res->iters = 0; res->n_corr_last = 0;
 }
 
+// ---- the first pass of the 256-thread parity pipeline kernel ------------------------------------------------------------------
+// Four passes of the reference read the same rows in the same index order before the first searched iteration, and their 16
+// float32 chains are independent of each other: transformPoints(pts_mod, I, t_match_tmp) (detection.cpp:206), copyPoints
+// (ICP.cpp:666-667), the initial getL2distClouds (:670) and iteration 1's getMean x2 + covariance loop over the index pairs
+// (:700-704, :731-735).  Here they are ONE producer / chain pass shaped like l2dist_phase's: each model point is loaded raw,
+// pre-translated by `pre_t` with the very expression of the transform (mat_vec(I, v) + t), zeroed if its new z is not valid,
+// and stored once; the row's first bnd[], its 15 products (S.prod) and its distance term (S.dtile) follow from the registers.
+// Lanes 0 - 14 of the chain wave add their column of S.prod, lane 15 adds S.dtile: sixteen chains, one barrier per tile.
+// Leaves S.dist_mean / S.px as the initial l2dist_phase does and iteration 1's sums in S.first_sums (the loop head decides
+// whether the iteration runs; if not, they are dropped).  n >= 3; in the pipeline n_ref == n_model == n.
+template <class SH>
+__device__ __forceinline__ void first_pass(SH &S, float *mod, const float *ref, bnd_t *bnd, int n, const float *pre_t)
+{
+  constexpr int TQ = SH::TQ;
+  const int slot = S.producer_slot(), clane = S.chain_lane();
+  const int ntiles = (n + TQ - 1) / TQ;
+  const float thr = FLT_MAX;
+  int counter = 0, inl = 0;
+  float acc = 0.0f;
+  struct Row { F3 m, r; };
+  auto row_load = [&](Row &w, int t) {                   // issue only (see l2dist_phase)
+    const int i = min(t * TQ + slot, n - 1);              // clamped: unused past the end
+    w.m = ld3_u32(mod, i);
+    w.r = ld3_u32(ref, i);
+  };
+  auto row_process = [&](const Row &w, int t) {
+    const int i = t * TQ + slot;
+    float m[3] = {0.f, 0.f, 0.f}, r[3] = {0.f, 0.f, 0.f}, term = 0.0f;
+    if (i < n) {
+      float a[3] = {w.m.x, w.m.y, w.m.z};
+      if (vvalid(a[2])) {                                 // transformPoints(pts_mod, I, t_match_tmp) detection.cpp:206
+        const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        float o[3];
+        mat_vec(I, a, o);
+        a[0] = o[0] + pre_t[0];
+        a[1] = o[1] + pre_t[1];
+        a[2] = o[2] + pre_t[2];
+      }
+      if (!vvalid(a[2])) { a[0] = 0.f; a[1] = 0.f; a[2] = 0.f; }    // copyPoints :666-667: invalid points become Vec3f() = 0
+      mod[3 * i] = a[0];
+      mod[3 * i + 1] = a[1];
+      mod[3 * i + 2] = a[2];
+      const float b0 = w.r.x, b1 = w.r.y, b2 = w.r.z;
+      // first bound: the index pair; NaN/inf simply disable the bound
+      const float ex = a[0] - b0, ey = a[1] - b1, ez = a[2] - b2;
+      bnd_st(bnd, i, sqrt_upper(ex * ex + ey * ey + ez * ez));
+      if (vvalid(b2) && vvalid(a[2])) {                   // getL2distClouds :68-111, dist_thr = FLT_MAX
+        const float dx = a[0] - b0, dy = a[1] - b1, dz = a[2] - b2;
+        // cv::norm(Vec3f): squares accumulated in double, sqrt in double, stored to float (:88)
+        const float dist = (float)sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
+        if (dist <= thr) { term = dist; ++inl; }
+        ++counter;
+      }
+      // iteration 1 pairs by index, invalid -> 0 (:700-704)
+      if (vvalid(a[2])) { m[0] = a[0]; m[1] = a[1]; m[2] = a[2]; }
+      if (vvalid(b2)) { r[0] = b0; r[1] = b1; r[2] = b2; }
+    }
+    float (*tile)[SH::TS] = S.prod[t & 1];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) tile[p * 3 + q][slot] = m[p] * r[q];     // (*it_s) * (*it_ref).t()
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { tile[9 + q][slot] = m[q]; tile[12 + q][slot] = r[q]; }
+    S.dtile[t & 1][slot] = term;                          // non-inliers add an exact +0.0f
+  };
+  // the chain lane's column of tile t: one of the 15 of S.prod, or the distance terms
+  auto chain_step = [&](int t) {
+    const float *col = clane < 15 ? S.prod[t & 1][clane] : S.dtile[t & 1];
+    acc = chain_tile<SH::CHAIN_NBUF>(col, min(TQ, n - t * TQ), acc);
+  };
+  const bool chain_wave = __builtin_amdgcn_readfirstlane(clane) >= 0;
+  if (chain_wave) {
+    for (int t = 0; t < ntiles; ++t) {
+      if (t > 0 && clane < 16) chain_step(t - 1);
+      tile_barrier();
+    }
+  } else if (slot >= 0) {
+    // one tile of loads in flight per thread: two register sets trade roles by unrolling (see l2dist_phase)
+    Row A, B;
+    row_load(A, 0);
+    for (int t = 0; t < ntiles; t += 2) {
+      row_load(B, t + 1);
+      row_process(A, t);
+      tile_barrier();
+      if (t + 1 < ntiles) {
+        row_load(A, t + 2);
+        row_process(B, t + 1);
+        tile_barrier();
+      }
+    }
+  }
+  __syncthreads();                                         // the pass's stores (mod, bnd) are visible to the workgroup
+  if (chain_wave && clane < 16) chain_step(ntiles - 1);
+  counter = block_sum_int(S, counter);
+  inl = block_sum_int(S, inl);
+  if (clane >= 0 && clane < 15) S.first_sums[clane] = acc;
+  if (clane == 15) S.sums[0] = acc;
+  __syncthreads();
+  float dm = S.sums[0];
+  if (counter > 0) dm /= (float)inl;                       // 0/0 -> NaN ends the loop (Q9)
+  if (threadIdx.x == 0) {
+    if (counter > 0) {
+      S.dist_mean = dm;
+      S.px = (float)inl / (float)counter;
+    } else {
+      S.dist_mean = FLT_MAX;
+      S.px = 0.0f;
+    }
+  }
+  __syncthreads();
+}
+
 // ---- icpCloudToCloud_Ex (ICP.cpp:617-809) --------------------------------------------------------
 // ORG: the reference cloud is also available as the image `og` describes (sref = image of points + image of indices, perm = tile order), see
 // "Organised search" at the top; otherwise the grid is built here and searched.
@@ -847,9 +967,11 @@ __device__ __forceinline__ void icp_result_none(fl_icp_result *res)
 // IDX(-1), read back as -1: nn_get), which also rebuild phase B's reference point from pix[] / zref[] (l2dist_phase<REFPIX>).
 template <class IDX>
 __device__ __forceinline__ int nn_get(IDX v) { return sizeof(IDX) == 2 && (int)v == 0xFFFF ? -1 : (int)v; }
-template <int MODE, bool ORG, class IDX, class SH>
+// FIRST (the 256-thread parity pipeline kernel; n_ref == n_model): the caller has NOT applied its pre-translation `pre_t` to mod[];
+// first_pass applies it together with copyPoints, the initial distances and iteration 1's sums.  Everyone else passes null.
+template <int MODE, bool ORG, class IDX, bool FIRST = false, class SH>
 __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &L, int n_ref, int n_model,
-                        int it_thr, float dmt, float ddt, fl_icp_result *res, const OrgGeom &og)
+                        int it_thr, float dmt, float ddt, fl_icp_result *res, const OrgGeom &og, const float *pre_t = nullptr)
 {
   constexpr int BS = SH::BS, NW = SH::NW;
   float *ref = (float *)(wsb + L.ref), *mod = (float *)(wsb + L.mod);
@@ -894,14 +1016,17 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   }
   if (!ORG) build_grid(S, ref, n_ref, sref, cell_start, cell_cur, L.ncell_max);
   TSTAMP(0);
+  SSTAMP(9);
   // copyPoints(pts_model, pts_model_tmp) (:666-667): invalid points become Vec3f() = 0
-  for (int i = threadIdx.x; i < n_model; i += BS)
-    if (!vvalid(mod[3 * i + 2])) { mod[3 * i] = 0.f; mod[3 * i + 1] = 0.f; mod[3 * i + 2] = 0.f; }
+  if (!FIRST)
+    for (int i = threadIdx.x; i < n_model; i += BS)
+      if (!vvalid(mod[3 * i + 2])) { mod[3 * i] = 0.f; mod[3 * i + 1] = 0.f; mod[3 * i + 2] = 0.f; }
   if (threadIdx.x == 0) {
     S.R[0] = S.R[4] = S.R[8] = 1.f;                      // R = eye, T = 0 (:644-645)
     S.dist_diff = FLT_MAX;
   }
   __syncthreads();
+  SSTAMP(5);
   // Search ahead of the distance chain (parity mode, organised search).  getL2distClouds' dist_mean is one float32 chain over
   // all points: alone it costs a quarter of an iteration during which every wave but one waits.  So the terms are written
   // to dterm[] (l2dist_phase<DEFER>), and while the chain wave adds them the other waves already run PointsCorresponding for
@@ -914,7 +1039,11 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
   // other workgroups already fill the chain's shadow, and the extra traffic (dterm, nd) costs 7 % there (profiles/README.md).
   constexpr bool SPEC = BS >= ICP_BS_WIDE && MODE == FL_ICP_PARITY && ORG;
   static_assert(!(IDX16 && SPEC), "pix[] / zref[] live where the deferred chain keeps dterm[] / nd[]");
-  float mean_ub = l2dist_phase<MODE, SPEC, false>(S, mod, ref, bnd, dterm, n_model, FLT_MAX, nullptr, nullptr, pix, zref, og);   // :670
+  static_assert(!FIRST || (MODE == FL_ICP_PARITY && ORG && !SPEC), "first_pass: the 256-thread parity pipeline kernel only");
+  float mean_ub = 0.0f;
+  if constexpr (FIRST) first_pass(S, mod, ref, bnd, n_model, pre_t);      // :670 with what precedes and follows it
+  else mean_ub = l2dist_phase<MODE, SPEC, false>(S, mod, ref, bnd, dterm, n_model, FLT_MAX, nullptr, nullptr, pix, zref, og);   // :670
+  SSTAMP(6);
   int pending = SPEC ? 1 : 0;                            // 1: the initial distances await their chain, 2: an iteration's
   bool have_nn = false;                                  // nn[] / nd[] hold the neighbours of the current model cloud
   float old_mean = 0.0f;                                 // dist_mean before the pending distances (pending == 2)
@@ -1055,8 +1184,10 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     constexpr int TQ = parity ? SH::TQ : BS;
     const int slot = parity ? S.producer_slot() : (int)threadIdx.x;
     const int clane = parity ? S.chain_lane() : -1;      // lane of this thread in the chain wave, or -1
-    const int ntiles = (parity || index_pairs) ? (rows + TQ - 1) / TQ : 0;
+    const bool summed = FIRST && iter == 1;              // first_pass has left this iteration's sums in S.first_sums
+    const int ntiles = ((parity || index_pairs) && !summed) ? (rows + TQ - 1) / TQ : 0;
     float acc = 0.0f;                                    // chain accumulator of lane k < 15 of wave 0
+    SSTAMP(9);
     if (parity && iter > 1) {
       // Register pipeline of the producers: a tile row costs its nn / mod loads (coalesced) and then the dependent gather
       // ref[j]; with thousands of frames in flight both come from HBM (thousands of cycles under load) while the chain
@@ -1154,7 +1285,7 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
       }
       __syncthreads();                                     // (the loads still in flight belong to rows past the end)
     } else
-    for (int t = 0; t < ntiles; ++t) {
+    for (int t = 0; t < (FIRST ? 0 : ntiles); ++t) {
       if (slot >= 0) {
         const int i = t * TQ + slot;
         float m[3] = {0.f, 0.f, 0.f}, r[3] = {0.f, 0.f, 0.f};
@@ -1200,8 +1331,10 @@ __device__ __forceinline__ void icp_run(SH &S, uint8_t *wsb, const IcpWsLayout &
     }
     if (parity && ntiles > 0 && clane >= 0 && clane < 15)
       acc = chain_tile<SH::CHAIN_NBUF>(S.prod[(ntiles - 1) & 1][clane], min(TQ, rows - (ntiles - 1) * TQ), acc);
+    if (summed && clane >= 0 && clane < 15) acc = S.first_sums[clane];
     kept = block_sum_int(S, kept);
     TSTAMP(3);
+    if (iter == 1) SSTAMP(7);
     const int ncm = index_pairs ? n_model : kept, ncr = index_pairs ? n_ref : kept;
     if (threadIdx.x == 0) S.n_corr = ncm;
     if (ncr < 3 || ncm < 3) {                            // :711-715
@@ -1423,6 +1556,7 @@ __device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int c
     if (lane == 0) cnt[t] = __popcll(bal);
   }
   __syncthreads();
+  SSTAMP(1);
   // exclusive scan of cnt[0 .. ntile) in place: a contiguous chunk per thread, the thread totals scanned by shuffles and
   // one LDS round
   {
@@ -1451,8 +1585,12 @@ __device__ __forceinline__ void build_tile_order(SH &S, const int *idximg, int c
     if (has) perm[cnt[t] + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = (IDX)k;
   }
   __syncthreads();
+  SSTAMP(2);
 }
 
+#ifdef FL_ICP_PHASES
+__device__ unsigned long long g_icp_setup[12];       // SSTAMP slots 0..9, whole-kernel cycles, workgroups: sums over a launch
+#endif
 // waves per SIMD a kernel instance is compiled for: the 256-thread one shares a CU with up to ICP_MODE_WPE - 1 others,
 // a 1024-thread workgroup is 4 waves per SIMD by itself
 #define ICP_WPE(MODE, BS) ((BS) == ICP_BS_SMALL ? ICP_MODE_WPE(MODE) : (BS) / 256)
@@ -1485,8 +1623,13 @@ void k_icp_pipeline(IcpArgs a)
   using SH = IcpSharedT<BS>;
   SH &S = *(SH *)icp_smem;
 #ifdef FL_ICP_PHASES
-  if (threadIdx.x == 0) { S.tkernel = clock64(); S.wall0 = wall_clock64(); }
+  if (threadIdx.x == 0) {
+    S.tkernel = clock64(); S.wall0 = wall_clock64();
+    for (int i = 0; i < 10; ++i) S.tset[i] = 0;
+    S.tslast = S.tkernel;
+  }
 #endif
+  constexpr bool FIRST = MODE == FL_ICP_PARITY && BS == ICP_BS_SMALL;   // the 256-thread parity instances fuse their first pass (first_pass)
   const int job = a.order ? a.order[blockIdx.x] : (int)blockIdx.x, rank = a.job.kind == 0 && !a.jobs ? job % a.ranks : 0;
   const int frame = a.job.kind == 0 ? (a.jobs ? a.jobs[job].frame : job / a.ranks) : job;
   const IcpWsLayout L = icp_layout(a.n_max);
@@ -1560,11 +1703,13 @@ void k_icp_pipeline(IcpArgs a)
   if (threadIdx.x == 0) S.cw = 0;                         // the chain wave (IcpSharedT::cw)
   __syncthreads();
   float *rimg = (float *)(wsb + L.sref);                  // image of 12-byte points, then the image of their indices (16 bytes per pixel in all)
+  SSTAMP(9);
   const int np = crop_clouds(S, a, scene, model, model_01mm, S.rect_m, S.rect_r, ref, mod,
                              MODE == FL_ICP_POINT_TO_PLANE ? (float *)(wsb + L.nrm) : nullptr, rimg,
                              (int *)((uint8_t *)rimg + org_idximg_offset(S.rect_m[2] * S.rect_m[3])),
                              MODE == FL_ICP_PARITY && BS < ICP_BS_WIDE ? (float *)(wsb + L.zimg) : nullptr,
                              sizeof(IDX) == 2 ? (uint16_t *)(wsb + L.dterm) : nullptr, (float *)(wsb + L.nd));
+  SSTAMP(0);
   // wave-uniform values read from LDS are VGPRs unless told otherwise: the search loop keeps them in SGPRs
   const OrgGeom og = {__builtin_amdgcn_readfirstlane(S.rect_r[2]), __builtin_amdgcn_readfirstlane(S.rect_r[3]),
                       uniform_f((float)S.rect_r[0] - a.cx), uniform_f((float)S.rect_r[1] - a.cy), a.fx, a.fy,
@@ -1612,17 +1757,20 @@ void k_icp_pipeline(IcpArgs a)
   float t_tmp[3], t_init[3];
   for (int k = 0; k < 3; ++k) { t_tmp[k] = rc[k] - mc[k]; t_init[k] = t_tmp[k] + t_match[k]; }
   __syncthreads();
-  for (int i = threadIdx.x; i < np; i += BS) {           // transformPoints(pts_mod, I, t_match_tmp) :206
-    if (!vvalid(mod[3 * i + 2])) continue;
-    const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    float v[3] = {mod[3 * i], mod[3 * i + 1], mod[3 * i + 2]}, o[3];
-    mat_vec(I, v, o);
-    mod[3 * i] = o[0] + t_tmp[0];
-    mod[3 * i + 1] = o[1] + t_tmp[1];
-    mod[3 * i + 2] = o[2] + t_tmp[2];
-  }
+  SSTAMP(3);
+  if (!FIRST)                                            // (FIRST: icp_run's first pass applies t_tmp)
+    for (int i = threadIdx.x; i < np; i += BS) {         // transformPoints(pts_mod, I, t_match_tmp) :206
+      if (!vvalid(mod[3 * i + 2])) continue;
+      const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+      float v[3] = {mod[3 * i], mod[3 * i + 1], mod[3 * i + 2]}, o[3];
+      mat_vec(I, v, o);
+      mod[3 * i] = o[0] + t_tmp[0];
+      mod[3 * i + 1] = o[1] + t_tmp[1];
+      mod[3 * i + 2] = o[2] + t_tmp[2];
+    }
   __syncthreads();
-  icp_run<MODE, true, IDX>(S, wsb, L, np, np, a.it_thr, a.dmt, a.ddt, &res->det.icp, og);      // :228
+  SSTAMP(4);
+  icp_run<MODE, true, IDX, FIRST>(S, wsb, L, np, np, a.it_thr, a.dmt, a.ddt, &res->det.icp, og, FIRST ? t_tmp : nullptr);      // :228
   if (threadIdx.x == 0) {
     const fl_icp_result &ic = res->det.icp;
     float Rt[3];
@@ -1653,6 +1801,9 @@ void k_icp_pipeline(IcpArgs a)
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
       res->pose[4] = (float)(hwid & 0xffffff);
     }
+    for (int i = 0; i < 10; ++i) atomicAdd(&g_icp_setup[i], (unsigned long long)S.tset[i]);
+    atomicAdd(&g_icp_setup[10], (unsigned long long)(clock64() - S.tkernel));
+    atomicAdd(&g_icp_setup[11], 1ull);
 #endif
   }
 }
@@ -1793,6 +1944,21 @@ static int icp_launch_one(fl_context *ctx, K kern, int n_jobs, const IcpArgs &a)
   }
   hipLaunchKernelGGL(kern, dim3(n_jobs), dim3(BS), lds, ctx->stream, a);
   FL_HIP(ctx, hipGetLastError());
+#ifdef FL_ICP_PHASES
+  {
+    // dev build only (it waits for the stream: not for timing): the set-up passes' cycles per workgroup of this launch
+    unsigned long long h[12], zero[12] = {};
+    FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    FL_HIP(ctx, hipMemcpyFromSymbol(h, HIP_SYMBOL(g_icp_setup), sizeof(h)));
+    FL_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_icp_setup), zero, sizeof(zero)));
+    if (h[11]) {
+      const double w = (double)h[11];
+      fprintf(stderr, "icp set-up cycles per workgroup (%llu workgroups, life %.0f): crop %.0f, tile counts %.0f, tile placing %.0f, getMean %.0f, "
+              "pre-translation %.0f, copyPoints %.0f, initial distances / first pass %.0f, iteration 1 sums %.0f, between %.0f\n", h[11], h[10] / w,
+              h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w, h[6] / w, h[7] / w, h[9] / w);
+    }
+  }
+#endif
   return FL_OK;
 }
 // Workgroup width by batch size: with no more jobs than CUs every job runs alone on its CU whatever its width, so it
