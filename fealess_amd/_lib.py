@@ -132,6 +132,12 @@ class DevSelectJob(C.Structure):       # fl_internal.h fl_dev_select_job
                 ("n_out", C.c_void_p), ("features", C.c_void_p), ("sorted_keys", C.c_void_p)]
 
 
+class DevExtractView(C.Structure):     # fl_internal.h fl_dev_extract_view
+    _fields_ = [("quantized", C.c_void_p), ("magnitude", C.c_void_p), ("mask", C.c_void_p), ("local_mask", C.c_void_p),
+                ("counters", C.c_void_p), ("cand_raster", C.c_void_p), ("cand_score", C.c_void_p), ("sorted_keys", C.c_void_p),
+                ("features", C.c_void_p)]
+
+
 FL_RENDER_AMBIENT = 0.2    # include/fealess_hip.h: fl_render_views' ambient when no fl_render_params is given
 FL_TRACK_MAX_PASSES = 4    # include/fealess_hip.h: fl_track_params.passes
 FL_TRACK_MAX_MESHES = 256  # include/fealess_hip.h: fl_tracker_create_meshes
@@ -238,6 +244,8 @@ DEV_SIGNATURES = {
     "fl_dev_detector_create_host": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_P)]),
     "fl_dev_group_jobs": (_I, [_P, _P, _I, C.POINTER(InstanceParams), _P, _P, _P, _P, _P]),
     "fl_dev_extract_select": (_I, [_P, _I, _P]),
+    "fl_dev_extract_quantized": (_I, [_P, _I, _P, _I, _I, _I, _F, _I, _I]),
+    "fl_dev_quantized_orientations_mag": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
     "fl_dev_front_images": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t]),
     "fl_dev_ranged_math": (_I, [_P, _I, C.c_uint32, C.c_uint32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]),
     "fl_dev_tracker_create_host": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),

@@ -198,6 +198,65 @@ class Context:
         self.check(L.dev(self.lib, "fl_dev_extract_select")(self.h, n, arr))
         return [(int(k[3][0]), k[4], k[5][:len(k[0])]) for k in keep]
 
+    def dev_extract_quantized(self, modality, quantized, magnitudes, masks, threshold, num_features, fill=-7, w=None, h=None):
+        """DEVELOPMENT ONLY (fl_dev_extract_quantized, not part of the C ABI): the candidate kernels, the sort and the selection
+        of one pyramid level on caller-supplied quantized images, all views in one call.  modality 0 (colour; threshold =
+        strong_threshold, magnitudes = one (h, w) float32 image per view) or 1 (depth; threshold = extract_threshold, magnitudes
+        ignored); masks: None, or per view a mask or None.  w, h: sizes to pass instead of the images' own (refusal tests).
+        Returns per view a dict: local ((h, w) uint8, None without a mask), n_cand, label_counts (8), area, n_out, raster /
+        score (the n_cand candidates before the sort, in arrival order), keys (the sorted segment, None if the view was not
+        sorted), features ((64, 3) int32), tails_unwritten (the lists hold `fill` behind their n_cand entries); `fill` (its low byte
+        in `local`) wherever nothing was written.  A refusal's FealessError carries the untouched buffers as `buffers`."""
+        n = len(quantized)
+        masks = [None] * n if masks is None else list(masks)
+        qs = [np.ascontiguousarray(q, np.uint8) for q in quantized]
+        ih, iw = qs[0].shape
+        px = iw * ih
+        arr = (L.DevExtractView * n)()
+        kfill = np.int64(fill).astype(np.uint64)
+        keep = []
+        for v in range(n):
+            mg = None if modality != 0 else np.ascontiguousarray(magnitudes[v], np.float32)
+            mk = None if masks[v] is None else np.ascontiguousarray(masks[v], np.uint8)
+            assert qs[v].shape == (ih, iw) and (mg is None or mg.shape == (ih, iw)) and (mk is None or mk.shape == (ih, iw))
+            local = np.full((ih, iw), fill & 0xFF, np.uint8)
+            cnt = np.full(11, fill, np.int32)
+            raster, score = np.full(px, fill, np.int32), np.full(px, float(fill), np.float32)
+            keys = np.full(px, kfill, np.uint64)
+            feats = np.full((64, 3), fill, np.int32)
+            keep.append((qs[v], mg, mk, local, cnt, raster, score, keys, feats))
+            arr[v] = L.DevExtractView(qs[v].ctypes.data, None if mg is None else mg.ctypes.data, None if mk is None else mk.ctypes.data,
+                                      local.ctypes.data, cnt.ctypes.data, raster.ctypes.data, score.ctypes.data, keys.ctypes.data,
+                                      feats.ctypes.data)
+        strong, ext = (float(threshold), 0) if modality == 0 else (0.0, int(threshold))
+        rc = L.dev(self.lib, "fl_dev_extract_quantized")(self.h, n, arr, iw if w is None else w, ih if h is None else h, modality, strong,
+                                                         ext, num_features)
+        try:
+            self.check(rc)
+        except FealessError as e:                                # a refusal writes nothing: the caller may look
+            e.buffers = [dict(local=k[3], counters=k[4], raster=k[5], score=k[6], keys=k[7], features=k[8]) for k in keep]
+            raise
+        out = []
+        for (_, _, mk, local, cnt, raster, score, keys, feats) in keep:
+            nc = int(cnt[0])
+            unwritten = bool((raster[nc:] == fill).all() and (score[nc:] == float(fill)).all() and (keys[nc:] == kfill).all())
+            was_sorted = nc > 0 and bool((keys[:nc] != kfill).any())
+            out.append(dict(local=None if mk is None else local, n_cand=nc, label_counts=cnt[1:9].copy(), area=int(cnt[9]), n_out=int(cnt[10]),
+                            raster=raster[:nc], score=score[:nc], keys=keys[:nc] if was_sorted else None, features=feats,
+                            tails_unwritten=unwritten))
+        return out
+
+    def dev_quantized_orientations_mag(self, bgrs, weak_threshold=10.0, fill=0xEE):
+        """DEVELOPMENT ONLY (fl_dev_quantized_orientations_mag, not part of the C ABI): k_color_quantize<true, *>, the build
+        template extraction launches, on packed frames of one size.  Returns (quantized (n, h, w) uint8, magnitude (n, h, w)
+        float32); bytes the kernel did not write hold `fill`."""
+        b = np.ascontiguousarray(np.stack(bgrs), np.uint8)
+        n, h, w = b.shape[:3]
+        q = np.full((n, h, w), fill, np.uint8)
+        mag = np.full((n, h, w), fill * 0x01010101, np.uint32).view(np.float32)
+        self.check(L.dev(self.lib, "fl_dev_quantized_orientations_mag")(self.h, _ptr(b), n, w, h, weak_threshold, _ptr(q), _ptr(mag)))
+        return q, mag
+
     def dev_front_images(self, bgrs, depths, levels):
         """DEVELOPMENT ONLY (fl_dev_front_images, not part of the C ABI): the launches of an eager batch's front-end on frames
         of any size, also those no detector can be finalized for.  Returns per frame a list over the levels of dicts with the

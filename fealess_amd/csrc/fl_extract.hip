@@ -20,6 +20,9 @@
 //                        in its result but not in its work: every candidate keeps its squared distance to the nearest
 //                        chosen feature, the walk to the next passing candidate is a workgroup-wide min
 // A chunk makes two host round trips whatever its size: the candidate counts (they size the sort) and the results.
+// Two test entries outside the ABI (fl_internal.h) run parts of this on a caller's data through the same launch functions:
+// fl_dev_extract_select (the sort and the selection on candidate lists) and fl_dev_extract_quantized (the candidate kernels,
+// the sort and the selection of one level on quantized images).
 #include "fl_internal.h"
 #include <limits.h>
 #include <string.h>
@@ -408,6 +411,57 @@ static int launch_sort_select(fl_context *ctx, const ExtractJob *d_jobs, int nj,
   return FL_OK;
 }
 
+// One pyramid level of one modality for n views, queued on the context's stream: what extract_chunk runs per level and what
+// fl_dev_extract_quantized runs on a caller's quantized images.  View z's mask, local mask, normals, raster / score lists and
+// key segment sit at a pitch of vs bytes, its colour labels and magnitude at a pitch of w * h elements, its counters at
+// cnt + z * cnt_stride.  d_flags[z] = 0: the view has no mask; any_mask = false: none has, k_local_mask is not launched.
+static int launch_color_level(fl_context *ctx, const uint8_t *quantized, const float *mag, const uint8_t *mask, uint8_t *local, uint8_t *keys,
+                              size_t vs, const int *d_flags, bool any_mask, int n, int w, int h, float strong_threshold,
+                              ExtractCounters *cnt, int cnt_stride)
+{
+  const dim3 grid((w + 63) / 64, (h + 3) / 4, n), blk(256);
+  if (any_mask) hipLaunchKernelGGL(k_local_mask, grid, blk, 0, ctx->stream, mask, local, vs, d_flags, w, h, 1, 1);
+  hipLaunchKernelGGL(k_color_candidates, grid, blk, 0, ctx->stream, quantized, mag, local, vs, d_flags, w, h,
+                     strong_threshold * strong_threshold, keys, cnt, cnt_stride);
+  FL_HIP(ctx, hipGetLastError());
+  return FL_OK;
+}
+
+static int launch_depth_level(fl_context *ctx, const uint8_t *normal, const uint8_t *mask, uint8_t *local, uint8_t *raster, uint8_t *score,
+                              uint8_t *keys, size_t vs, const int *d_flags, bool any_mask, int n, int w, int h, int extract_threshold,
+                              ExtractCounters *cnt, int cnt_stride)
+{
+  const dim3 grid((w + 63) / 64, (h + 3) / 4, n), blk(256);
+  if (any_mask) hipLaunchKernelGGL(k_local_mask, grid, blk, 0, ctx->stream, mask, local, vs, d_flags, w, h, 2, 0);
+  hipLaunchKernelGGL(k_depth_candidates, grid, blk, 0, ctx->stream, normal, local, vs, d_flags, w, h, extract_threshold, raster, score, cnt,
+                     cnt_stride);
+  const int kb = (int)std::min<size_t>(((size_t)w * h + 255) / 256, 64);
+  hipLaunchKernelGGL(k_depth_keys, dim3(kb, 1, n), blk, 0, ctx->stream, normal, raster, score, vs, cnt, cnt_stride, keys);
+  FL_HIP(ctx, hipGetLastError());
+  return FL_OK;
+}
+
+// The record of one job, once its candidate count is known.  sortable = false: the job's view cannot yield a template
+// (this job or another of the view has fewer candidates than features), nothing is sorted or selected.
+static ExtractJob make_job(unsigned long long *keys, const uint8_t *labels, uint32_t *xy, int *mind2, ExtractCounters *cnt, fl_feature *out,
+                           int w, int total_px, int num_features, int depth_mode, int n_cand, bool sortable)
+{
+  ExtractJob jb;
+  jb.keys = keys;
+  jb.labels = labels;
+  jb.xy = xy;
+  jb.mind2 = mind2;
+  jb.cnt = cnt;
+  jb.out = out;
+  jb.w = w;
+  jb.num_features = num_features;
+  jb.depth_mode = depth_mode;
+  jb.total_px = total_px;
+  jb.n_pow2 = sortable ? next_pow2(n_cand) : 0;
+  jb.pad = 0;
+  return jb;
+}
+
 // Views [v0, v0 + n) of a batch, n <= FL_EXTRACT_CHUNK_VIEWS: outputs at the batch's indices (feat_begin absolute).
 static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *bgr, const uint16_t *const *depth, const uint8_t *const *mask,
                          int w0, int h0, int levels, int mem, fl_template *templates, fl_feature *features, int32_t *bb, int32_t *status)
@@ -449,7 +503,6 @@ static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *b
   }
   FL_HIP(ctx, hipMemcpyAsync(d_flags, h_flags, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
   FL_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(ExtractCounters) * n * J, ctx->stream));
-  const dim3 blk(256);
 
   // modality 0: ColorGradient(10, 63, 55) (:515-519); pyrDown :434-453.  The NN-halved mask pyramid made here is also
   // modality 1's: it halves the same level-0 mask the same way (:721-739).
@@ -465,11 +518,9 @@ static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *b
       }
       if ((rc = fl_launch_quantized_orientations_mag(ctx, vw + img, vs, s + o_quant[l], (size_t)w * h, n, w, h, 10.0f, (float *)(s + o_mag))))
         return rc;
-      const dim3 grid((w + 63) / 64, (h + 3) / 4, n);
-      if (any_mask) hipLaunchKernelGGL(k_local_mask, grid, blk, 0, ctx->stream, vw + lo.mask[l], vw + lo.local, vs, d_flags, w, h, 1, 1);
-      hipLaunchKernelGGL(k_color_candidates, grid, blk, 0, ctx->stream, s + o_quant[l], (const float *)(s + o_mag), vw + lo.local, vs, d_flags, w, h,
-                         55.0f * 55.0f, vw + lo.keys[l][0], d_cnt + l * M + 0, J);
-      FL_HIP(ctx, hipGetLastError());
+      if ((rc = launch_color_level(ctx, s + o_quant[l], (const float *)(s + o_mag), vw + lo.mask[l], vw + lo.local, vw + lo.keys[l][0], vs, d_flags,
+                                   any_mask, n, w, h, 55.0f, d_cnt + l * M + 0, J)))
+        return rc;
     }
   }
   // modality 1: DepthNormal(2000, 50, 63, 2) (:827-832)
@@ -483,15 +534,10 @@ static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *b
         w /= 2;
         h /= 2;
       }
-      const dim3 grid((w + 63) / 64, (h + 3) / 4, n);
-      if (any_mask) hipLaunchKernelGGL(k_local_mask, grid, blk, 0, ctx->stream, vw + lo.mask[l], vw + lo.local, vs, d_flags, w, h, 2, 0);
-      hipLaunchKernelGGL(k_depth_candidates, grid, blk, 0, ctx->stream, vw + lo.normal[l], vw + lo.local, vs, d_flags, w, h, 2 >> l,
-                         vw + lo.raster, vw + lo.score, d_cnt + l * M + 1, J);
-      // raster / score are reused by the next level, whose candidates queue behind these keys
-      const int kb = (int)std::min<size_t>(((size_t)w * h + 255) / 256, 64);
-      hipLaunchKernelGGL(k_depth_keys, dim3(kb, 1, n), blk, 0, ctx->stream, vw + lo.normal[l], vw + lo.raster, vw + lo.score, vs,
-                         d_cnt + l * M + 1, J, vw + lo.keys[l][1]);
-      FL_HIP(ctx, hipGetLastError());
+      // raster / score are reused by the next level, whose candidates queue behind this level's keys
+      if ((rc = launch_depth_level(ctx, vw + lo.normal[l], vw + lo.mask[l], vw + lo.local, vw + lo.raster, vw + lo.score, vw + lo.keys[l][1], vs,
+                                   d_flags, any_mask, n, w, h, 2 >> l, d_cnt + l * M + 1, J)))
+        return rc;
     }
   }
 
@@ -505,19 +551,11 @@ static int extract_chunk(fl_context *ctx, int v0, int n, const uint8_t *const *b
     uint8_t *b = vw + (size_t)v * vs;
     for (int k = 0; k < J; ++k) {
       const int l = k / M, m = k % M;
+      const int total_px = (w0 >> l) * (h0 >> l);
       ExtractJob &jb = h_jobs[v * J + k];
-      jb.keys = (unsigned long long *)(b + lo.keys[l][m]);
-      jb.labels = m == 0 ? s + o_quant[l] + (size_t)v * (w0 >> l) * (h0 >> l) : b + lo.normal[l];
-      jb.xy = (uint32_t *)(b + lo.xy[l][m]);
-      jb.mind2 = (int *)(b + lo.mind2[l][m]);
-      jb.cnt = d_cnt + v * J + k;
-      jb.out = d_feats + (size_t)64 * (v * J + k);
-      jb.w = w0 >> l;
-      jb.num_features = 63 >> l;
-      jb.depth_mode = m == 0 ? 0 : (h_flags[v] ? 2 : 1);
-      jb.total_px = (w0 >> l) * (h0 >> l);
-      jb.n_pow2 = view_ok ? next_pow2(h_cnt[v * J + k].n_cand) : 0;
-      jb.pad = 0;
+      jb = make_job((unsigned long long *)(b + lo.keys[l][m]), m == 0 ? s + o_quant[l] + (size_t)v * total_px : b + lo.normal[l],
+                    (uint32_t *)(b + lo.xy[l][m]), (int *)(b + lo.mind2[l][m]), d_cnt + v * J + k, d_feats + (size_t)64 * (v * J + k), w0 >> l,
+                    total_px, 63 >> l, m == 0 ? 0 : (h_flags[v] ? 2 : 1), h_cnt[v * J + k].n_cand, view_ok);
       max_np2 = std::max(max_np2, jb.n_pow2);
     }
   }
@@ -638,18 +676,9 @@ extern "C" int fl_dev_extract_select(fl_context *ctx, int n_jobs, const fl_dev_s
     h_cnt[k].area = j.area;
     memcpy(h_feats + (size_t)64 * k, j.features, sizeof(fl_feature) * 64);   // what the kernel does not write comes back as it went in
     ExtractJob &jb = h_jobs[k];
-    jb.keys = (unsigned long long *)(s + o_keys[k]);
-    jb.labels = s + o_labels[k];
-    jb.xy = (uint32_t *)(s + o_xy[k]);
-    jb.mind2 = (int *)(s + o_mind2[k]);
-    jb.cnt = (ExtractCounters *)(s + o_cnt) + k;
-    jb.out = (fl_feature *)(s + o_feats) + (size_t)64 * k;
-    jb.w = j.w;
-    jb.num_features = j.num_features;
-    jb.depth_mode = j.depth_mode;
-    jb.total_px = j.total_px;
-    jb.n_pow2 = j.n_cand >= j.num_features ? next_pow2(j.n_cand) : 0;
-    jb.pad = 0;
+    jb = make_job((unsigned long long *)(s + o_keys[k]), s + o_labels[k], (uint32_t *)(s + o_xy[k]), (int *)(s + o_mind2[k]),
+                  (ExtractCounters *)(s + o_cnt) + k, (fl_feature *)(s + o_feats) + (size_t)64 * k, j.w, j.total_px, j.num_features, j.depth_mode,
+                  j.n_cand, j.n_cand >= j.num_features);
     max_np2 = std::max(max_np2, jb.n_pow2);
   }
   FL_HIP(ctx, hipMemcpyAsync(s, p, mirrored, hipMemcpyHostToDevice, ctx->stream));
@@ -661,6 +690,130 @@ extern "C" int fl_dev_extract_select(fl_context *ctx, int n_jobs, const fl_dev_s
     *j.n_out = h_cnt[k].n_out;
     memcpy(j.features, h_feats + (size_t)64 * k, sizeof(fl_feature) * 64);
     if (h_jobs[k].n_pow2 > 0) memcpy(j.sorted_keys, p + o_keys[k], (size_t)j.n_cand * 8);
+  }
+  return FL_OK;
+}
+
+// see fl_internal.h
+extern "C" int fl_dev_extract_quantized(fl_context *ctx, int n_views, const fl_dev_extract_view *views, int w, int h, int modality,
+                                        float strong_threshold, int extract_threshold, int num_features)
+{
+  if (!ctx || !views || n_views < 1 || n_views > FL_EXTRACT_CHUNK_VIEWS || modality < 0 || modality > 1) return FL_ERR_INVALID;
+  if (num_features < 1 || num_features > FL_MAX_FEATURES) return FL_ERR_INVALID;
+  // the selection packs a candidate's x and y into 16 bits each; rasters are ints and every list holds w * h entries
+  if (w < 1 || h < 1 || w > 65536 || h > 65536 || (size_t)w * h > ((size_t)1 << 24)) return FL_ERR_INVALID;
+  bool any_mask = false;
+  for (int v = 0; v < n_views; ++v) {
+    const fl_dev_extract_view &vw = views[v];
+    if (!vw.quantized || (modality == 0 && !vw.magnitude) || (vw.mask && !vw.local_mask) || !vw.counters || !vw.cand_raster || !vw.cand_score ||
+        !vw.sorted_keys || !vw.features)
+      return FL_ERR_INVALID;
+    any_mask = any_mask || vw.mask;
+  }
+  const int n = n_views;
+  const size_t px = (size_t)w * h;
+  // a view's slab: mask | local mask | normals | depth candidates' raster, score | key segment | the selection's xy, mind2
+  size_t off = 0;
+  auto take = [&](size_t b) { size_t o = off; off += fl_align(b, 256); return o; };
+  const size_t v_mask = take(px), v_local = take(px), v_normal = take(px), v_raster = take(px * 4), v_score = take(px * 4),
+               v_keys = take((size_t)next_pow2((int)px) * 8), v_xy = take(px * 4), v_mind2 = take(px * 4), vs = off;
+  // device: view slabs | colour labels (n px) | magnitude (n 4 px) | then, also in pinned host memory at the same relative
+  // offsets: has_mask[n] | counters[n] | features[n 64] | jobs[n]
+  off = 0;
+  const size_t o_views = take(vs * n), o_quant = take(px * n), o_mag = take(px * 4 * n), o_flags = take(sizeof(int) * n),
+               o_cnt = take(sizeof(ExtractCounters) * n), o_feats = take(sizeof(fl_feature) * 64 * n), o_jobs = take(sizeof(ExtractJob) * n);
+  void *sv = nullptr, *pv = nullptr;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = fl_scratch(ctx, off, &sv);
+  if (rc) return rc;
+  if ((rc = fl_pinned(ctx, off - o_flags, &pv))) return rc;
+  uint8_t *s = (uint8_t *)sv, *slab = s + o_views;
+  auto pin = [&](size_t o) { return (uint8_t *)pv + (o - o_flags); };
+  int *d_flags = (int *)(s + o_flags), *h_flags = (int *)pin(o_flags);
+  ExtractCounters *d_cnt = (ExtractCounters *)(s + o_cnt), *h_cnt = (ExtractCounters *)pin(o_cnt);
+  fl_feature *d_feats = (fl_feature *)(s + o_feats), *h_feats = (fl_feature *)pin(o_feats);
+  ExtractJob *d_jobs = (ExtractJob *)(s + o_jobs), *h_jobs = (ExtractJob *)pin(o_jobs);
+
+  for (int v = 0; v < n; ++v) {
+    const fl_dev_extract_view &vw = views[v];
+    uint8_t *b = slab + (size_t)v * vs;
+    if (modality == 0) {
+      FL_HIP(ctx, hipMemcpyAsync(s + o_quant + v * px, vw.quantized, px, hipMemcpyHostToDevice, ctx->stream));
+      FL_HIP(ctx, hipMemcpyAsync(s + o_mag + v * px * 4, vw.magnitude, px * 4, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+      FL_HIP(ctx, hipMemcpyAsync(b + v_normal, vw.quantized, px, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (vw.mask) {
+      FL_HIP(ctx, hipMemcpyAsync(b + v_mask, vw.mask, px, hipMemcpyHostToDevice, ctx->stream));
+      // what k_local_mask does not write comes back as it went in; a view without a mask keeps whatever the slab holds
+      FL_HIP(ctx, hipMemcpyAsync(b + v_local, vw.local_mask, px, hipMemcpyHostToDevice, ctx->stream));
+    }
+    h_flags[v] = vw.mask != nullptr;
+    memcpy(h_feats + (size_t)64 * v, vw.features, sizeof(fl_feature) * 64);
+  }
+  FL_HIP(ctx, hipMemcpyAsync(d_flags, h_flags, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(d_feats, h_feats, sizeof(fl_feature) * 64 * n, hipMemcpyHostToDevice, ctx->stream));
+  FL_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(ExtractCounters) * n, ctx->stream));
+  if (modality == 0)
+    rc = launch_color_level(ctx, s + o_quant, (const float *)(s + o_mag), slab + v_mask, slab + v_local, slab + v_keys, vs, d_flags, any_mask, n,
+                            w, h, strong_threshold, d_cnt, 1);
+  else
+    rc = launch_depth_level(ctx, slab + v_normal, slab + v_mask, slab + v_local, slab + v_raster, slab + v_score, slab + v_keys, vs, d_flags,
+                            any_mask, n, w, h, extract_threshold, d_cnt, 1);
+  if (rc) return rc;
+
+  // host round trip 1: the candidate counts; the lists as they stand before the sort leave ahead of it in stream order
+  FL_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(ExtractCounters) * n, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<size_t> first(n + 1, 0);
+  for (int v = 0; v < n; ++v) {
+    if (h_cnt[v].n_cand < 0 || (size_t)h_cnt[v].n_cand > px) return fl_set_error(ctx, FL_ERR_INVALID, "view %d: %d candidates of %zu pixels", v, h_cnt[v].n_cand, px);
+    first[v + 1] = first[v] + (modality == 0 ? h_cnt[v].n_cand : 0);
+  }
+  std::vector<unsigned long long> unsorted(first[n]);      // colour: the candidates exist as keys only
+  int max_np2 = 0;
+  for (int v = 0; v < n; ++v) {
+    const fl_dev_extract_view &vw = views[v];
+    uint8_t *b = slab + (size_t)v * vs;
+    const int nc = h_cnt[v].n_cand;
+    h_jobs[v] = make_job((unsigned long long *)(b + v_keys), modality == 0 ? s + o_quant + v * px : b + v_normal, (uint32_t *)(b + v_xy),
+                         (int *)(b + v_mind2), d_cnt + v, d_feats + (size_t)64 * v, w, (int)px, num_features,
+                         modality == 0 ? 0 : (h_flags[v] ? 2 : 1), nc, nc >= num_features);
+    max_np2 = std::max(max_np2, h_jobs[v].n_pow2);
+    if (nc == 0) continue;
+    if (modality == 0) {
+      FL_HIP(ctx, hipMemcpyAsync(unsorted.data() + first[v], b + v_keys, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+      FL_HIP(ctx, hipMemcpyAsync(vw.cand_raster, b + v_raster, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+      FL_HIP(ctx, hipMemcpyAsync(vw.cand_score, b + v_score, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+  }
+  FL_HIP(ctx, hipMemcpyAsync(d_jobs, h_jobs, sizeof(ExtractJob) * n, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = launch_sort_select(ctx, d_jobs, n, max_np2))) {
+    (void)hipStreamSynchronize(ctx->stream);                  // copies into `unsorted` and the caller's lists may be in flight
+    return rc;
+  }
+
+  // host round trip 2: the counters (n_out), the features, the local masks and the sorted segments
+  FL_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(ExtractCounters) * n, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(h_feats, d_feats, sizeof(fl_feature) * 64 * n, hipMemcpyDeviceToHost, ctx->stream));
+  for (int v = 0; v < n; ++v) {
+    const fl_dev_extract_view &vw = views[v];
+    uint8_t *b = slab + (size_t)v * vs;
+    if (vw.mask) FL_HIP(ctx, hipMemcpyAsync(vw.local_mask, b + v_local, px, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_jobs[v].n_pow2 > 0)
+      FL_HIP(ctx, hipMemcpyAsync(vw.sorted_keys, b + v_keys, (size_t)h_cnt[v].n_cand * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int v = 0; v < n; ++v) {
+    const fl_dev_extract_view &vw = views[v];
+    static_assert(sizeof(ExtractCounters) == 11 * sizeof(int32_t), "fl_dev_extract_view.counters");
+    memcpy(vw.counters, &h_cnt[v], sizeof(ExtractCounters));
+    memcpy(vw.features, h_feats + (size_t)64 * v, sizeof(fl_feature) * 64);
+    for (size_t c = first[v]; c < first[v + 1]; ++c) {
+      vw.cand_raster[c - first[v]] = (int32_t)(unsorted[c] & 0xFFFFFFFFull);
+      vw.cand_score[c - first[v]] = __builtin_bit_cast(float, ~(unsigned)(unsorted[c] >> 32));
+    }
   }
   return FL_OK;
 }

@@ -1027,6 +1027,31 @@ extern "C" int fl_dev_front_images(fl_context *ctx, const uint8_t *bgr, const ui
   return FL_OK;
 }
 
+// Development / test aid (not part of the ABI): fl_launch_quantized_orientations_mag -- k_color_quantize<true, *>, the
+// instantiations template extraction launches -- on n_frames packed host frames of w x h.  quantized: n_frames * w * h
+// labels; magnitude: n_frames * w * h squared gradient magnitudes.  Both are uploaded as given and read back, so what the
+// kernel does not write returns unchanged.
+extern "C" int fl_dev_quantized_orientations_mag(fl_context *ctx, const uint8_t *bgr, int n_frames, int w, int h, float weak_threshold,
+                                                 uint8_t *quantized, float *magnitude)
+{
+  if (!ctx || !bgr || !quantized || !magnitude || n_frames < 1 || w < 3 || h < 3) return FL_ERR_INVALID;
+  FL_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t px = (size_t)w * h, in_b = fl_align(px * 3 * n_frames, 256), q_b = fl_align(px * n_frames, 256);
+  void *s = nullptr;
+  int rc = fl_scratch(ctx, in_b + q_b + px * 4 * n_frames, &s);
+  if (rc) return rc;
+  uint8_t *d_bgr = (uint8_t *)s, *d_q = d_bgr + in_b;
+  float *d_mag = (float *)(d_q + q_b);
+  FL_HIP(ctx, hipMemcpyAsync(d_bgr, bgr, px * 3 * n_frames, hipMemcpyHostToDevice, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(d_q, quantized, px * n_frames, hipMemcpyHostToDevice, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(d_mag, magnitude, px * 4 * n_frames, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = fl_launch_quantized_orientations_mag(ctx, d_bgr, px * 3, d_q, px, n_frames, w, h, weak_threshold, d_mag))) return rc;
+  FL_HIP(ctx, hipMemcpyAsync(quantized, d_q, px * n_frames, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipMemcpyAsync(magnitude, d_mag, px * 4 * n_frames, hipMemcpyDeviceToHost, ctx->stream));
+  FL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FL_OK;
+}
+
 // Development / test aid (not part of the ABI): the functions of fl_ranged_math.h against the compiler's own operations, which
 // this file's flags make correctly rounded, over EVERY argument first .. last of a domain (tests/test_gpu_ranged_math.py).
 //   which 0: sqrt_rn(x) against sqrtf(x), 1: rcp_rn(x) against 1.0f / x, x the float with the bit pattern a;

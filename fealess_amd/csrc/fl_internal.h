@@ -489,6 +489,41 @@ struct fl_dev_select_job {
   unsigned long long *sorted_keys;
 };
 extern "C" int fl_dev_extract_select(fl_context *ctx, int n_jobs, const fl_dev_select_job *jobs);
+// The stage between quantisation and the sort on caller-supplied QUANTIZED images: n_views (1..FL_EXTRACT_CHUNK_VIEWS) views
+// of one modality (0 colour, 1 depth) and one w x h go through the launches extract_chunk runs for one pyramid level of that
+// modality -- k_local_mask when any view has a mask, k_color_candidates or k_depth_candidates + k_depth_keys with the view in
+// blockIdx.z and the per-view has_mask flags, the count round trip, the job records, the sort and the selection -- by the
+// same functions (launch_color_level / launch_depth_level / make_job / launch_sort_select).  strong_threshold (colour; the
+// library's 55), extract_threshold (depth; 2 >> level) and num_features (1..63; 63 >> level) are extract_chunk's constants
+// as parameters.  Everything is host memory.  Per view, in: quantized (w * h labels), magnitude (colour: w * h floats; depth:
+// ignored), mask (w * h, or null).  Out:
+//   local_mask   w * h, where the view has a mask (else untouched, may be null): the border mask (colour) / the 5x5-eroded
+//                mask (depth); uploaded as given and read back
+//   counters     11 ints: n_cand, label_counts[8], area (counted under a depth view's mask only), n_out (num_features, or -1)
+//   cand_raster, cand_score   w * h entries each, the first n_cand written: the candidates as they stood before the sort, in
+//                the order the atomics gave them, with the score the candidate kernel produced (colour: the magnitude; depth:
+//                the undivided distance)
+//   sorted_keys  w * h entries, the first n_cand written and only for a view that was sorted (n_cand >= num_features)
+//   features     64 entries, uploaded as given and read back
+// What a kernel does not write returns unchanged.  FL_ERR_INVALID with nothing launched or written: null pointers, n_views
+// outside 1..FL_EXTRACT_CHUNK_VIEWS, a modality other than 0 / 1, num_features outside 1..63, w or h below 1 or beyond 65536
+// (the selection packs x and y into 16 bits each), more than 2^24 pixels.
+struct fl_dev_extract_view {
+  const uint8_t *quantized;
+  const float *magnitude;
+  const uint8_t *mask;
+  uint8_t *local_mask;
+  int32_t *counters;
+  int32_t *cand_raster;
+  float *cand_score;
+  unsigned long long *sorted_keys;
+  fl_feature *features;
+};
+extern "C" int fl_dev_extract_quantized(fl_context *ctx, int n_views, const fl_dev_extract_view *views, int w, int h, int modality,
+                                        float strong_threshold, int extract_threshold, int num_features);
+// fl_launch_quantized_orientations_mag (k_color_quantize<true, *>) on n_frames packed host frames: fl_frontend.hip
+extern "C" int fl_dev_quantized_orientations_mag(fl_context *ctx, const uint8_t *bgr, int n_frames, int w, int h, float weak_threshold,
+                                                 uint8_t *quantized, float *magnitude);
 // frontend
 int fl_launch_quantized_orientations(fl_context *ctx, const uint8_t *bgr, size_t in_stride,
                                      uint8_t *dst, size_t out_stride, int n_frames, int w, int h,

@@ -8,12 +8,15 @@ common.cpp, depth_to_3d.cpp, detection.cpp and NMS.cpp): FL_ICP_PARITY under eve
 `width` fixture selects, on cloud sizes on the wave and workgroup strides of those builds; ctx.detection, ctx.depth_to_3d and
 fl_nms.  Every comparison is equality of bit patterns or of ints.
 
-Template extraction the same way (tests/golden/reference_extract.npz, RC.extract_groups): fl_dev_extract_select on every `select`
-case, ctx.quantized_orientations on the `orientations` cases, ctx.extract_template_pyramid and extract_template_batch on the
-`add_template` cases.  No entry point of fl_extract.hip takes quantized images from a caller, so the `extract_color` and
-`extract_depth` cases do not run here as they are: their edges are reached through whole views instead, the add_template cases
-with those groups' masks (values other than 255, flush with the image border, a hole, a one-pixel line) and the views with a
-job at exactly its rule, one below and one above.
+Template extraction the same way (tests/golden/reference_extract.npz, RC.extract_groups), every group on the kernels:
+fl_dev_extract_select on the `select` cases; fl_dev_extract_quantized -- the candidate kernels, sort and selection of one level
+on quantized images from the caller, through the launch functions extract_chunk calls -- on the `extract_color` and
+`extract_depth` cases (magnitude exactly 55^2 against 55^2 + 1, q == 0 under a huge magnitude, labels 0 and 255,
+extract_threshold 2 / 1 / 0, distance exactly at the threshold, equal scores across labels, absent labels, mask values other
+than 255, masks flush with the border, a hole, a one-pixel line); ctx.quantized_orientations (k_color_quantize<false, *>) and
+fl_dev_quantized_orientations_mag (k_color_quantize<true, *>, labels and magnitude) on the `orientations` cases;
+ctx.extract_template_pyramid and extract_template_batch on the `add_template` cases.  tests/test_gpu_extract_candidates.py holds
+the intermediate products of the candidate stage to plain references.
 """
 import ctypes as C
 
@@ -284,6 +287,27 @@ class KernelExtractBackend:
     def add_template(self, bgr, depth, mask, levels):
         return self.as_record(self.ctx.extract_template_pyramid(bgr, depth, mask, levels))
 
+    def _extract_quantized(self, modality, quantized, magnitude, mask, threshold, num_features):
+        """fl_dev_extract_quantized on one view: the features, or None (refused: nothing sorted, nothing written)."""
+        g = self.ctx.dev_extract_quantized(modality, [quantized], [magnitude], None if mask is None else [mask], threshold, num_features, fill=FILL)[0]
+        assert g["tails_unwritten"]
+        if g["n_out"] == -1:
+            assert g["n_cand"] < num_features and g["keys"] is None and (g["features"] == FILL).all()
+            return None
+        assert g["n_out"] == num_features <= g["n_cand"] and (g["features"][num_features:] == FILL).all()
+        return g["features"][:num_features]
+
+    def extract_template_color(self, quantized, magnitude, mask, strong_threshold, num_features):
+        return self._extract_quantized(0, quantized, magnitude, mask, strong_threshold, num_features)
+
+    def extract_template_depth(self, normal, mask, extract_threshold, num_features):
+        return self._extract_quantized(1, normal, None, mask, extract_threshold, num_features)
+
+    def quantized_orientations_mag(self, bgr, weak_threshold=10.0):
+        """k_color_quantize<true, *>, the build extraction launches: (labels, squared magnitude)."""
+        q, mag = self.ctx.dev_quantized_orientations_mag([bgr], weak_threshold)
+        return q[0], mag[0]
+
 
 def _extract_names(group):
     return [n for n, _ in EXTRACT_GROUPS[group][0]]
@@ -307,12 +331,23 @@ def test_extract_select_equals_recorded_reference(ctx, name):
 
 @pytest.mark.parametrize("name", _extract_names("orientations"))
 def test_quantized_orientations_equal_recorded_reference(ctx, name):
-    """The quantized image of quantizedOrientations (the entry point returns no magnitude)."""
+    """quantizedOrientations: the quantized image from both builds of the colour quantiser, the public entry point's (it returns
+    no magnitude) and extraction's, and the magnitude image from extraction's."""
     case = _extract_case("orientations", name)
     rec = RC.record_parts(golden("reference_extract.npz"), "orientations", name, ["__in__", "img_mag", "img_q"])
     bgr = RC.orientation_input(case)
     assert RC._with_inputs({}, bgr)["__in__"].tobytes() == rec["__in__"]
     assert RC.digest(ctx.quantized_orientations(bgr, 10.0)).tobytes() == rec["img_q"]
+    q, mag = KernelExtractBackend(ctx).quantized_orientations_mag(bgr, 10.0)
+    assert RC.digest(q).tobytes() == rec["img_q"]
+    assert RC.digest(RC.fbits(mag)).tobytes() == rec["img_mag"]
+    _against_extract_record(RC.compute_orientations(KernelExtractBackend(ctx), case), "orientations", name)
+
+
+@pytest.mark.parametrize("group,name", [(g, n) for g in ("extract_color", "extract_depth") for n in _extract_names(g)])
+def test_extract_candidates_equal_recorded_reference(ctx, group, name):
+    """The two extractTemplate methods on given quantized images: the features in full, or the refusal."""
+    _against_extract_record(EXTRACT_GROUPS[group][1](KernelExtractBackend(ctx), _extract_case(group, name)), group, name)
 
 
 @pytest.mark.parametrize("name", _extract_names("add_template"))
@@ -349,7 +384,7 @@ def test_extract_template_batch_equals_recorded_reference(ctx, mem):
     assert seen == len(EXTRACT_GROUPS["add_template"][0]) and refused_among_others >= 1
 
 
-@pytest.mark.parametrize("group", ["select", "orientations", "add_template"])
+@pytest.mark.parametrize("group", ["select", "orientations", "add_template", "extract_color", "extract_depth"])
 def test_extraction_equals_live_reference(ctx, group):
     """The same cases against the compiled reference itself."""
     ref, K = R.require(False), KernelExtractBackend(ctx)
@@ -357,7 +392,13 @@ def test_extraction_equals_live_reference(ctx, group):
         if group == "select":
             a, b = RC.select_record(case, K.select_job(case)), RC.compute_select(ref, case)
         elif group == "orientations":
-            a, b = {"img_q": ctx.quantized_orientations(RC.orientation_input(case), 10.0)}, {"img_q": RC.compute_orientations(ref, case)["img_q"]}
-        else:
+            b = RC.compute_orientations(ref, case)
+            a = {"img_q": ctx.quantized_orientations(RC.orientation_input(case), 10.0)}
+            assert RC.same(a, {"img_q": b["img_q"]}) is None, (name, "img_q of the public entry point")
+            a = RC.compute_orientations(K, case)               # extraction's build: labels and magnitude
+        elif group == "add_template":
             a, b = RC.compute_add_template(K, case), RC.compute_add_template(ref, case)
+        else:
+            fn = EXTRACT_GROUPS[group][1]
+            a, b = fn(K, case), fn(ref, case)
         assert RC.same(a, b) is None, (name, RC.same(a, b))
