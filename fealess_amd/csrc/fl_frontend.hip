@@ -681,38 +681,54 @@ __device__ __forceinline__ unsigned dq_normal_pattern(bool interior, int d, int 
   if (!(d < distance_threshold)) return dq_pattern(0);
   const int t = difference_threshold;
   const unsigned span = t > 0 ? (unsigned)(2 * t - 1) : 0u;   // t <= 0 admits nothing
-  const int e0 = n0 - d, e1 = n1 - d, e2 = n2 - d, e3 = n3 - d, e4 = n4 - d, e5 = n5 - d, e6 = n6 - d, e7 = n7 - d;
-  // |e| < t  <=>  (unsigned)(e + t - 1) < 2t - 1                                                    :569
-  const bool g0 = (unsigned)(e0 + t - 1) < span, g1 = (unsigned)(e1 + t - 1) < span,
-             g2 = (unsigned)(e2 + t - 1) < span, g3 = (unsigned)(e3 + t - 1) < span,
-             g4 = (unsigned)(e4 + t - 1) < span, g5 = (unsigned)(e5 + t - 1) < span,
-             g6 = (unsigned)(e6 + t - 1) < span, g7 = (unsigned)(e7 + t - 1) < span;
-  const int f0 = g0, f1 = g1, f2 = g2, f3 = g3, f4 = g4, f5 = g5, f6 = g6, f7 = g7;
-  const int m0 = g0 ? e0 : 0, m1 = g1 ? e1 : 0, m2 = g2 ? e2 : 0, m3 = g3 ? e3 : 0, m4 = g4 ? e4 : 0, m5 = g5 ? e5 : 0,
-            m6 = g6 ? e6 : 0, m7 = g7 ? e7 : 0;
-  const int corners = f0 + f2 + f5 + f7;
-  // Every factor below fits 24 bits: |A| <= 150, 0 <= det <= 22500, and with t <= 400 |b| <= 30 * 399, |dd| < 3.0e6, d < 65536.
-  // The products of det and of the t <= 400 path are the full-rate 24-bit multiplies BY NAME (dq_mul_i24, dq_mul_u24).  __mul24 is a
-  // 32-bit multiply of the arguments' sign-extended low 24 bits, and what the compiler makes of it depends on what it knows
-  // of them: it folded the extension into a factor that was itself a product (5 * x became (x * (5 << 8)) >> 8) and, with d's
-  // 16 bits known, dropped it from det * d, and each time a v_mul_lo_u32 (quarter rate) was left.  The products by 5 and
-  // by 25 are plain C: v_lshl_add_u32, and 24-bit multiplies by the constant.
-  const int A0 = 25 * (corners + f3 + f4), A3 = 25 * (corners + f1 + f6), A1 = 25 * ((f0 + f7) - (f2 + f5));
-  const int det = (int)dq_mul_u24((unsigned)A0, (unsigned)A3) - dq_mul_i24(A1, A1);       // 0 <= det <= 22500: |A1| <= 25 * corners <= A0, A3
+  // |e| < t  <=>  (unsigned)(e + t - 1) < 2t - 1, e = n - d: u = n - (d - (t - 1)) is that left side                :569
+  const unsigned tm1 = (unsigned)t - 1u, lo = (unsigned)d - tm1;
+  const unsigned u0 = (unsigned)n0 - lo, u1 = (unsigned)n1 - lo, u2 = (unsigned)n2 - lo, u3 = (unsigned)n3 - lo,
+                 u4 = (unsigned)n4 - lo, u5 = (unsigned)n5 - lo, u6 = (unsigned)n6 - lo, u7 = (unsigned)n7 - lo;
   float nx, ny, nz;
-  if (t <= 400) {
-    // |b| <= 30 * 399, |dd| <= 250 * |b| < 3.0e6: 617 * dd and det * d (<= 22500 * 65535) fit in int32
-    const int b0 = 5 * ((m2 + m4 + m7) - (m0 + m3 + m5)), b1 = 5 * ((m5 + m6 + m7) - (m0 + m1 + m2));
-    const int ddx = dq_mul_i24(A3, b0) - dq_mul_i24(A1, b1), ddy = dq_mul_i24(A0, b1) - dq_mul_i24(A1, b0);
-    nx = (float)dq_mul_i24_by<617>(ddx);
-    ny = (float)dq_mul_i24_by<617>(ddy);
-    nz = (float)(-(int)dq_mul_u24((unsigned)det, (unsigned)d));
+  // Decided once per wave-step (one ballot over the lanes still here, of the largest of the eight u against the span): does
+  // every lane that got this far admit all eight neighbours?  Then for each of them f_k = 1 and m_k = e_k, so A0 = A3 = 150,
+  // A1 = 0, det = 22500, the three d on each side of b0 and b1 cancel, ddx = 150 * b0, ddy = 150 * b1, and the same integers
+  // come from the neighbours alone: nx = 617 * 150 * 5 * ((n2 + n4 + n7) - (n0 + n3 + n5)), ny likewise, nz = -22500 * d.
+  // With t <= 400 the bracket is at most 6 * 399, the factor 462750 fits 24 bits and the products 31 (22500 * 65535 < 2^31).
+  // Smooth surfaces are the common case.  Everything only the general path needs -- the differences e_k, the
+  // eight compares, the selects, the counts, A, det and their products -- stays behind this wave-uniform branch (eight masks
+  // ANDed on the scalar unit instead of the maximum kept sixteen more scalar and four more vector registers alive across it).
+  const unsigned umax = max(max(max(u0, u1), max(u2, u3)), max(max(u4, u5), max(u6, u7)));
+  if (t <= 400 && __builtin_amdgcn_ballot_w64(umax >= span) == 0) {
+    nx = (float)dq_mul_i24_by<462750>((n2 + n4 + n7) - (n0 + n3 + n5));
+    ny = (float)dq_mul_i24_by<462750>((n5 + n6 + n7) - (n0 + n1 + n2));
+    nz = (float)dq_mul_i24_by<-22500>(d);
   } else {
+    const int e0 = (int)(u0 - tm1), e1 = (int)(u1 - tm1), e2 = (int)(u2 - tm1), e3 = (int)(u3 - tm1), e4 = (int)(u4 - tm1),
+              e5 = (int)(u5 - tm1), e6 = (int)(u6 - tm1), e7 = (int)(u7 - tm1);
+    const bool g0 = u0 < span, g1 = u1 < span, g2 = u2 < span, g3 = u3 < span, g4 = u4 < span, g5 = u5 < span, g6 = u6 < span,
+               g7 = u7 < span;
+    const int f0 = g0, f1 = g1, f2 = g2, f3 = g3, f4 = g4, f5 = g5, f6 = g6, f7 = g7;
+    const int m0 = g0 ? e0 : 0, m1 = g1 ? e1 : 0, m2 = g2 ? e2 : 0, m3 = g3 ? e3 : 0, m4 = g4 ? e4 : 0, m5 = g5 ? e5 : 0,
+              m6 = g6 ? e6 : 0, m7 = g7 ? e7 : 0;
+    const int corners = f0 + f2 + f5 + f7;
+    // Every factor below fits 24 bits: |A| <= 150, 0 <= det <= 22500, and with t <= 400 |b| <= 30 * 399, |dd| < 3.0e6, d < 65536.
+    // The products of det and of the t <= 400 path are the full-rate 24-bit multiplies BY NAME (dq_mul_i24, dq_mul_u24).  __mul24 is a
+    // 32-bit multiply of the arguments' sign-extended low 24 bits, and what the compiler makes of it depends on what it knows
+    // of them: it folded the extension into a factor that was itself a product (5 * x became (x * (5 << 8)) >> 8) and, with d's
+    // 16 bits known, dropped it from det * d, and each time a v_mul_lo_u32 (quarter rate) was left.  The products by 5 and
+    // by 25 are plain C: v_lshl_add_u32, and 24-bit multiplies by the constant.
+    const int A0 = 25 * (corners + f3 + f4), A3 = 25 * (corners + f1 + f6), A1 = 25 * ((f0 + f7) - (f2 + f5));
+    const int det = (int)dq_mul_u24((unsigned)A0, (unsigned)A3) - dq_mul_i24(A1, A1);       // 0 <= det <= 22500: |A1| <= 25 * corners <= A0, A3
     const int b0 = 5 * ((m2 + m4 + m7) - (m0 + m3 + m5)), b1 = 5 * ((m5 + m6 + m7) - (m0 + m1 + m2));
-    const long long ddx = (long long)A3 * b0 - (long long)A1 * b1, ddy = -(long long)A1 * b0 + (long long)A0 * b1;
-    nx = (float)(617LL * ddx);
-    ny = (float)(617LL * ddy);
-    nz = (float)(-(long long)det * d);
+    if (t <= 400) {
+      // |b| <= 30 * 399, |dd| <= 250 * |b| < 3.0e6: 617 * dd and det * d (<= 22500 * 65535) fit in int32
+      const int ddx = dq_mul_i24(A3, b0) - dq_mul_i24(A1, b1), ddy = dq_mul_i24(A0, b1) - dq_mul_i24(A1, b0);
+      nx = (float)dq_mul_i24_by<617>(ddx);
+      ny = (float)dq_mul_i24_by<617>(ddy);
+      nz = (float)(-(int)dq_mul_u24((unsigned)det, (unsigned)d));
+    } else {
+      const long long ddx = (long long)A3 * b0 - (long long)A1 * b1, ddy = -(long long)A1 * b0 + (long long)A0 * b1;
+      nx = (float)(617LL * ddx);
+      ny = (float)(617LL * ddy);
+      nz = (float)(-(long long)det * d);
+    }
   }
   // nx, ny, nz are integers (converted, beyond 2^24 rounded, to float): their sum of squares is 0 or in [1, 2^80) -- 617 * dd
   // stays below 2^39 at any threshold, det * d below 2^31 -- and its root s is 0 exactly where the sum is, else in [1, 2^40):
