@@ -119,6 +119,14 @@ class Mesh(C.Structure):               # fl_mesh
     _fields_ = [("vertices", C.c_void_p), ("triangles", C.c_void_p), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32)]
 
 
+class Extrinsics(C.Structure):         # fl_extrinsics: X_colour = R * X_depth + t, mm
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3)]
+
+
+class RegisterParams(C.Structure):     # fl_register_params
+    _fields_ = [("fill_cracks", C.c_int32)]
+
+
 class StageTimes(C.Structure):
     _fields_ = [("frontend_ms", C.c_float), ("linmem_ms", C.c_float), ("scan_ms", C.c_float), ("refine_ms", C.c_float),
                 ("sort_ms", C.c_float), ("backproject_ms", C.c_float), ("icp_ms", C.c_float), ("total_ms", C.c_float),
@@ -141,6 +149,9 @@ class DevExtractView(C.Structure):     # fl_internal.h fl_dev_extract_view
 FL_RENDER_AMBIENT = 0.2    # include/fealess_hip.h: fl_render_views' ambient when no fl_render_params is given
 FL_TRACK_MAX_PASSES = 4    # include/fealess_hip.h: fl_track_params.passes
 FL_TRACK_MAX_MESHES = 256  # include/fealess_hip.h: fl_tracker_create_meshes
+FL_RENDER_MAX_DIM = 8192   # include/fealess_hip.h: the largest image width and height of fl_render_views and fl_register_depth_batch
+FL_REGISTER_MAX_SPLAT = 8  # include/fealess_hip.h: pixels a footprint of fl_register_depth_batch spans along an axis at most
+FL_REGISTER_CHUNK_FRAMES = 64   # include/fealess_hip.h: frames of one launch of fl_register_depth_batch
 FL_TOPK_OVERFLOW = -2      # fl_export_topk_batch: template id of record 0 of a frame whose candidate buffers overflowed
 
 _P = C.c_void_p
@@ -179,6 +190,9 @@ SIGNATURES = {
     "fl_view_sphere": (_I, [_I, _I, _P, _I, _I, _F, _P, _I, C.POINTER(_I)]),
     "fl_resize_linear_bgr8": (_I, [_P, _P, _I, _I, _P, _I, _I, _I]),
     "fl_resize_linear_u16": (_I, [_P, _P, _I, _I, _P, _I, _I, _I]),
+    "fl_register_depth_batch": (_I, [_P, _I, C.POINTER(_P), _I, C.POINTER(Intrinsics), C.POINTER(Intrinsics), C.POINTER(Extrinsics),
+                                     C.POINTER(RegisterParams), C.POINTER(_P)]),
+    "fl_register_check": (_I, [C.POINTER(Intrinsics), C.POINTER(Intrinsics), C.POINTER(Extrinsics), C.POINTER(RegisterParams)]),
     "fl_lm_label_stride": (C.c_size_t, [_I, _I, _I]),
     "fl_build_linear_memories": (_I, [_P, _P, _I, _I, _I, _P, _I]),
     "fl_depth_to_3d": (_I, [_P, _P, _I, _I, _D, _D, _D, _D, _P, _I]),

@@ -327,6 +327,42 @@ class Context:
             return res["bgr"], res["depth"], res["mask"], res["tri"]
         return res
 
+    def register_depth(self, depths, K_depth, K_color, R, t, fill_cracks=1, mem=L.FL_MEM_HOST, out=None):
+        """fl_register_depth_batch: raw depth frames re-expressed in the colour camera.  K_depth, K_color = (w, h, fx, fy, cx,
+        cy) of the two cameras; R (3, 3) and t (3,) take a point of the depth camera to the colour camera, X_colour = R X_depth
+        + t in mm.  mem=FL_MEM_HOST: depths are (hd, wd) u16 numpy arrays in mm and the result is an (n, hc, wc) u16 array (`out`,
+        when given, is that array to fill).  FL_MEM_DEVICE: depths and `out` are lists of device pointers (ints, or anything
+        with data_ptr()) to frames of wd * hd and wc * hc u16; the work is queued on this context's stream and `out` is returned."""
+        kd = L.Intrinsics(int(K_depth[0]), int(K_depth[1]), *[float(x) for x in K_depth[2:]])
+        kc = L.Intrinsics(int(K_color[0]), int(K_color[1]), *[float(x) for x in K_color[2:]])
+        Ra, ta = np.ascontiguousarray(R, np.float32).ravel(), np.ascontiguousarray(t, np.float32).ravel()
+        if Ra.size != 9 or ta.size != 3:
+            raise ValueError("register_depth: R is 3 x 3 and t has 3 entries")
+        ext = L.Extrinsics((C.c_float * 9)(*Ra), (C.c_float * 3)(*ta))
+        prm = L.RegisterParams(int(fill_cracks))
+        n = len(depths)
+        if not all(0 < v <= L.FL_RENDER_MAX_DIM for v in (kd.width, kd.height, kc.width, kc.height)):     # what the library refuses, before np.empty meets it
+            raise FealessError(L.FL_ERR_INVALID, f"register_depth: image sizes must be 1..{L.FL_RENDER_MAX_DIM}")
+        if mem == L.FL_MEM_HOST:
+            frames = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            for d in frames:
+                if d.shape != (kd.height, kd.width):
+                    raise ValueError(f"register_depth: frames must be {kd.height} x {kd.width}")
+            res = np.empty((n, kc.height, kc.width), np.uint16) if out is None else out
+            if res.dtype != np.uint16 or res.shape != (n, kc.height, kc.width) or not res.flags.c_contiguous:
+                raise ValueError(f"register_depth: out must be a contiguous ({n}, {kc.height}, {kc.width}) uint16 array")
+            ip = [d.ctypes.data for d in frames]
+            op = [res[i].ctypes.data for i in range(n)]
+        else:
+            if out is None or len(out) != n:
+                raise ValueError("register_depth: with FL_MEM_DEVICE `out` holds one device pointer per frame")
+            res = out
+            ip = [d.data_ptr() if hasattr(d, "data_ptr") else int(d) for d in depths]
+            op = [d.data_ptr() if hasattr(d, "data_ptr") else int(d) for d in out]
+        self.check(self.lib.fl_register_depth_batch(self.h, n, (C.c_void_p * max(1, n))(*ip), mem, C.byref(kd), C.byref(kc), C.byref(ext),
+                                                    C.byref(prm), (C.c_void_p * max(1, n))(*op)))
+        return res
+
     def build_linear_memories(self, quantized, T):
         q = np.ascontiguousarray(quantized, np.uint8)
         h, w = q.shape

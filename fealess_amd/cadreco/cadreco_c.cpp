@@ -1,6 +1,7 @@
 // cadreco_c.cpp -- the flat C shim of cadreco_c.h over the C++ facade, so that callers without a C++ compiler (the test
 // suite, through ctypes) can drive it.  Argument refusals come first, before anything touches the handle.
 #include "cadreco_c.h"
+#include "cadreco_depth_c.h"
 
 #include "cadreco_internal.h"
 
@@ -93,6 +94,26 @@ int cadreco_recognition_all(void *h, const unsigned char *bgr, const unsigned sh
   std::vector<TObjRecoResult> out;
   const int rc = recognition(h, bgr, depth, w, h_, ts, kw, kh, fx, fy, cx, cy, out, n_results);
   for (int i = 0; i < (int)out.size() && i < cap; ++i) memcpy(poses16 + 16 * i, out[i].tWorld2Cam, 16 * sizeof(float));
+  return rc;
+}
+
+int cadreco_set_depth_camera(void *h, int on, int dw, int dh, double fx, double fy, double cx, double cy, const float *R, const float *t,
+                             int fill_cracks)
+{
+  if ((on != 0 && on != 1) || (on && (!R || !t))) return (int)ERROR_INVALID_PARAM;
+  return CadRecoSetDepthCamera((CObjRecoCAD *)h, on, camera(dw, dh, fx, fy, cx, cy), R, t, fill_cracks);
+}
+int cadreco_recognition_depth(void *h, const unsigned char *bgr, int w, int h_, const unsigned short *depth, int dw, int dh_, double ts,
+                              double fx, double fy, double cx, double cy, int *n_results, float *pose16, char *tag, int tag_cap)
+{
+  if (!h || !n_results || !pose16 || !tag) return (int)ERROR_INVALID_PARAM;
+  std::vector<TObjRecoResult> out;
+  const int rc = ((CObjRecoCAD *)h)->Recognition(colour_image(bgr, w, h_, ts), depth_image(depth, dw, dh_, ts), camera(w, h_, fx, fy, cx, cy), out);
+  *n_results = (int)out.size();
+  if (!out.empty()) {
+    memcpy(pose16, out[0].tWorld2Cam, 16 * sizeof(float));
+    snprintf(tag, tag_cap, "%s", out[0].strObjTag.c_str());
+  }
   return rc;
 }
 

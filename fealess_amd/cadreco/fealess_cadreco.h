@@ -291,4 +291,19 @@ int CadRecoSetVerifiedPick(CObjRecoCAD *handle, int on, float tau_mm, float min_
 // threshold that is not finite or keep_input outside {0, 1}.  on = 0 switches it off, and CadRecoTrack is again fl_track_batch.
 int CadRecoSetVerifiedTracking(CObjRecoCAD *handle, int on, float tau_mm, float min_inlier_ratio, float max_behind_ratio, int keep_input);
 
+// ---- a depth camera of its own (the reference's callers run rs2::align(RS2_STREAM_COLOR) on every frameset before
+// Recognition: test/linemod_recon.cpp:38-51, test/linemod_acq.cpp:24-42) ----------------------------------------------------------
+// Every entry point above takes a depth image that is pixel-aligned with the colour image and expressed in tCamIntrinsic.  No
+// sensor delivers that.  With on = 1 the handle takes the depth image as the depth sensor delivers it: tDepth must then have
+// K_depth's size instead of tCamIntrinsic's, and is registered to tCamIntrinsic on the GPU (fl_register_depth_batch,
+// include/fealess_hip.h, which states the rule; host memory in and out) before anything else happens -- in Recognition,
+// CadRecoRecognitionBatch, CadRecoTrack, CadRecoVerify and CadRecoArbitrate.  R (9 floats, row-major) and t (3 floats, mm) take a
+// point of the depth camera to the colour camera, X_colour = R * X_depth + t; fill_cracks (0 / 1) as fl_register_params.  Lens
+// distortion is out of scope (vdDistCoeff is ignored, as everywhere).  on = 0 restores the behaviour without a depth camera byte
+// for byte; the other arguments are then ignored.  ERROR_INVALID_PARAM: not a handle of this library, on or fill_cracks outside
+// {0, 1}, and what fl_register_depth_batch refuses of a camera (a size outside 1..8192, fx or fy not finite and > 0, cx or cy not
+// finite, a null or non-finite R or t, an R that is not a rotation); while it is on, a tDepth that is not of K_depth's size.
+// ERROR_UNKNOW: no GPU, or a HIP error while a frame is registered.
+int CadRecoSetDepthCamera(CObjRecoCAD *handle, int on, const TCamIntrinsicParam &K_depth, const float R[9], const float t[3], int fill_cracks);
+
 #endif  // FEALESS_CADRECO_H

@@ -34,6 +34,12 @@ void append(vector<TObjRecoResult> &out, const fl_recognition_result &r, const s
 // a fl_verify_result as the initialisers of CadRecoVerifyResult, which are the first eight of CadRecoSceneResult too
 #define VERIFY_FIELDS(v) (v).accepted, (v).n_model, (v).n_missing, (v).n_inlier, (v).n_front, (v).n_behind, (v).inlier_ratio, (v).behind_ratio
 
+// depth frames registered to the colour camera (CadRecoSetDepthCamera): the pixels and the images that borrow them
+struct Registered {
+  std::vector<uint16_t> px;
+  std::vector<TImageU16> img;
+};
+
 // Batch's frames as the C ABI takes them: 640 wide already, or src_w x src_h for the call that zooms on the device
 struct Frames {
   int n, src_w, src_h;
@@ -143,6 +149,11 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     out.clear();
     if (frame_rc) frame_rc->assign(n > 0 ? n : 0, (int)ERROR_INVALID_PARAM);
     if (!m_ctx || !m_det || n <= 0) return (int)ERROR_INVALID_PARAM;
+    Registered reg;                                                          // CadRecoSetDepthCamera: depth as the sensor delivers it
+    if (m_depth_camera) {
+      if (const int rc = RegisterDepth(n, depth, K, reg)) return rc;
+      depth = reg.img.data();
+    }
     // PrepareInputData (:216-259)
     for (int i = 0; i < n; ++i) {
       if (!check_image(rgb[i]) || !check_image(depth[i])) return (int)ERROR_INVALID_PARAM;
@@ -223,7 +234,10 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
   {
     if (tracked) tracked->assign(vtResult.size(), 0);
     MeshCall c;
-    if (!BeginMeshCall(tDepth, K, vtResult, true, c)) return c.rc;
+    Registered reg;
+    int rrc = SUCCESS;
+    const TImageU16 &frame = Aligned(tDepth, K, reg, &rrc);
+    if (!BeginMeshCall(frame, K, vtResult, rrc == SUCCESS, c)) return rrc != SUCCESS ? rrc : c.rc;
     std::vector<fl_track_result> res(c.n);
     int rc;
     if (m_verified_tracking) {
@@ -250,7 +264,10 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
   {
     if (out) out->clear();
     MeshCall c;
-    if (!BeginMeshCall(tDepth, K, vtResult, out && tau_ok(tau_mm), c)) return c.rc;
+    Registered reg;
+    int rrc = SUCCESS;
+    const TImageU16 &frame = Aligned(tDepth, K, reg, &rrc);
+    if (!BeginMeshCall(frame, K, vtResult, rrc == SUCCESS && out && tau_ok(tau_mm), c)) return rrc != SUCCESS ? rrc : c.rc;
     const fl_verify_params prm = {(int32_t)tau_mm, 1, 0.f, 0.f};
     std::vector<fl_verify_result> res(c.n);
     const int rc = fl_verify_batch_meshes(m_tracker, 1, &c.frame, FL_MEM_HOST, c.n, c.frame_of.data(), c.mesh_of.data(), c.poses13.data(), 0, nullptr, &c.k, &prm,
@@ -268,7 +285,10 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     if (out) out->clear();
     const bool ratio_ok = std::isfinite(max_shared_ratio) && max_shared_ratio > 0.f && max_shared_ratio <= 1.f;
     MeshCall c;
-    if (!BeginMeshCall(tDepth, K, vtResult, out && tau_ok(tau_mm) && ratio_ok, c)) return c.rc;
+    Registered reg;
+    int rrc = SUCCESS;
+    const TImageU16 &frame = Aligned(tDepth, K, reg, &rrc);
+    if (!BeginMeshCall(frame, K, vtResult, rrc == SUCCESS && out && tau_ok(tau_mm) && ratio_ok, c)) return rrc != SUCCESS ? rrc : c.rc;
     const fl_scene_params prm = {{(int32_t)tau_mm, 1, 0.f, 0.f}, max_shared_ratio, 1};
     const int32_t scene_first[2] = {0, c.n};
     std::vector<fl_scene_result> res(c.n);
@@ -300,6 +320,26 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
       return (int)ERROR_INVALID_PARAM;
     m_tvparams = fl_track_verify_params{{(int32_t)tau_mm, 1, min_inlier_ratio, max_behind_ratio}, keep_input, 0};
     m_verified_tracking = true;
+    return SUCCESS;
+  }
+
+  // CadRecoSetDepthCamera
+  int SetDepthCamera(int on, const TCamIntrinsicParam &K_depth, const float *R, const float *t, int fill_cracks)
+  {
+    if (on != 0 && on != 1) return (int)ERROR_INVALID_PARAM;
+    if (!on) { m_depth_camera = false; return SUCCESS; }
+    if (!R || !t) return (int)ERROR_INVALID_PARAM;
+    const fl_intrinsics k = {K_depth.nWidth, K_depth.nHeight, K_depth.dFx, K_depth.dFy, K_depth.dCx, K_depth.dCy};
+    fl_extrinsics e;
+    memcpy(e.R, R, sizeof(e.R));
+    memcpy(e.t, t, sizeof(e.t));
+    const fl_register_params p = {fill_cracks};
+    if (fl_register_check(&k, nullptr, &e, &p) != FL_OK) return (int)ERROR_INVALID_PARAM;     // the library's own rules
+    if (!m_ctx) return (int)ERROR_UNKNOW;
+    m_k_depth = k;
+    m_depth_to_color = e;
+    m_register = p;
+    m_depth_camera = true;
     return SUCCESS;
   }
 
@@ -400,6 +440,37 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
     return first_rc;
   }
 
+  // While a depth camera is set: the n depth images, each of K_depth's size, registered to the camera K in one call; reg.img are
+  // the images to go on with.  SUCCESS, or the code the entry point returns.
+  CADRECO_LOCAL int RegisterDepth(int n, const TImageU16 *depth, const TCamIntrinsicParam &K, Registered &reg) const
+  {
+    if (!depth || K.nWidth < 1 || K.nHeight < 1 || K.nWidth > FL_RENDER_MAX_DIM || K.nHeight > FL_RENDER_MAX_DIM) return (int)ERROR_INVALID_PARAM;
+    for (int i = 0; i < n; ++i)
+      if (!check_image(depth[i]) || depth[i].nWidth != m_k_depth.width || depth[i].nHeight != m_k_depth.height) return (int)ERROR_INVALID_PARAM;
+    const size_t px = (size_t)K.nWidth * K.nHeight;
+    reg.px.resize(px * n);
+    std::vector<const uint16_t *> in(n);
+    std::vector<uint16_t *> out(n);
+    for (int i = 0; i < n; ++i) {
+      in[i] = depth[i].pData;
+      out[i] = reg.px.data() + px * i;
+      reg.img.push_back(TImageU16{depth[i].dTimestamp, out[i], K.nWidth, K.nHeight});
+    }
+    const fl_intrinsics kc = {K.nWidth, K.nHeight, K.dFx, K.dFy, K.dCx, K.dCy};
+    const int rc = fl_register_depth_batch(m_ctx, n, in.data(), FL_MEM_HOST, &m_k_depth, &kc, &m_depth_to_color, &m_register, out.data());
+    if (rc == FL_ERR_INVALID) return (int)ERROR_INVALID_PARAM;
+    return rc == FL_OK ? (int)SUCCESS : fl_fail(m_ctx, (int)ERROR_UNKNOW);
+  }
+
+  // the frame Track, Verify and Arbitrate go on with: tDepth, or while a depth camera is set its registration to K, kept in reg
+  // (*rc: RegisterDepth's code; on a failure tDepth itself comes back and the caller returns *rc)
+  CADRECO_LOCAL const TImageU16 &Aligned(const TImageU16 &tDepth, const TCamIntrinsicParam &K, Registered &reg, int *rc) const
+  {
+    if (!m_depth_camera) return tDepth;
+    *rc = RegisterDepth(1, &tDepth, K, reg);
+    return *rc == SUCCESS ? reg.img[0] : tDepth;
+  }
+
   // the tail of SetTrackingMesh and SetTrackingMeshes: rc and trk of the create call; ids: the class id of every mesh, or none
   CADRECO_LOCAL int ReplaceTracker(int rc, fl_tracker *trk, const std::vector<std::string> &ids)
   {
@@ -450,6 +521,10 @@ class CObjRecoLmICPHip : public CObjRecoCAD {
   std::string m_path;
   int m_w = 0, m_h = 0, m_batch = 1;
   fl_tracker *m_tracker = nullptr;   // CadRecoSetTrackingMesh, CadRecoSetTrackingMeshes
+  bool m_depth_camera = false;       // CadRecoSetDepthCamera: depth images arrive in the depth sensor's own camera
+  fl_intrinsics m_k_depth = {0, 0, 0.0, 0.0, 0.0, 0.0};
+  fl_extrinsics m_depth_to_color = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}};
+  fl_register_params m_register = {1};
   std::vector<std::string> m_mesh_ids;   // CadRecoSetTrackingMeshes: the class id of every mesh of the tracker; empty: one mesh for every tag
 };
 
@@ -582,4 +657,10 @@ int CadRecoArbitrate(CObjRecoCAD *handle, const TImageU16 &tDepth, const TCamInt
 {
   CObjRecoLmICPHip *h = handle_of(handle);
   return h ? h->Arbitrate(tDepth, K, vtResult, tau_mm, max_shared_ratio, out) : (int)ERROR_INVALID_PARAM;
+}
+
+int CadRecoSetDepthCamera(CObjRecoCAD *handle, int on, const TCamIntrinsicParam &K_depth, const float R[9], const float t[3], int fill_cracks)
+{
+  CObjRecoLmICPHip *h = handle_of(handle);
+  return h ? h->SetDepthCamera(on, K_depth, R, t, fill_cracks) : (int)ERROR_INVALID_PARAM;
 }

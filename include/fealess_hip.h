@@ -303,6 +303,53 @@ int  fl_view_sphere(int subdivisions, int upper_hemisphere, const float *distanc
  * that are not 640 wide (obj_reco_lmicp.cpp:39-45, 229-249: TImage2Mat(..., true)); BGR8 and u16 */
 int  fl_resize_linear_bgr8(fl_context *ctx, const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh, int mem);
 int  fl_resize_linear_u16(fl_context *ctx, const uint16_t *src, int sw, int sh, uint16_t *dst, int dw, int dh, int mem);
+/* ---- depth registration: raw sensor depth re-expressed in the colour camera (the reference leaves it to librealsense:
+ * rs2::align(RS2_STREAM_COLOR) on every frameset in front of Recognition, test/linemod_recon.cpp:38-51, test/linemod_acq.cpp:24-42)
+ * Every entry point that takes a depth frame assumes it is pixel-aligned with the colour frame and expressed in the colour
+ * camera's K.  fl_register_depth_batch makes n_frames such frames from what the depth sensor delivers, on the device.
+ * K_depth->width x height is the size of every input frame (wd x hd), K_color->width x height of every output frame
+ * (wc x hc).  depth and out are host arrays of n_frames pointers; mem says where the pixels of both live: host -- the call
+ * stages them and synchronises; device -- queued on the context's stream, no wait (an output frame must not overlap an input
+ * frame).  Depth is u16 millimetres, 0 = no measurement; the output uses the same convention.  depth_to_color: X_colour =
+ * R * X_depth + t in mm, R row-major.  Lens distortion is out of scope, as for fl_intrinsics everywhere.
+ * Arithmetic: everything is float32, one IEEE operation per operator, in the order written ('/' correctly rounded).
+ *   host      fx_d = (float)K_depth->fx and so on for the other intrinsics of both cameras; ifx = 1.0f / fx_d, ify = 1.0f / fy_d
+ *   points    a depth pixel (u, v) with d == 0 contributes nothing.  Otherwise z = (float)d and three points are formed, A, B
+ *             and C for o = -0.5f, +0.5f, 0 (the same o on both axes):
+ *               x = (((float)u + o) - cx_d) * ifx * z,  y = (((float)v + o) - cy_d) * ify * z
+ *               X = ((R[0]*x + R[1]*y) + R[2]*z) + t[0];  Y uses row 1 and t[1], Z row 2 and t[2]
+ *   reject    the pixel is skipped unless Z_A > 0, Z_B > 0 and Z_C >= 0.5f
+ *   value     val = (uint16)fminf(rintf(Z_C), 65535.f): the transformed depth, not the source depth
+ *   footprint p = X / Z * fx_c + cx_c and q = Y / Z * fy_c + cy_c, for A and B; the pixel is skipped if any of the four is
+ *             not finite.  x0 = ceilf(fminf(pA, pB)), x1 = floorf(fmaxf(pA, pB)); y0, y1 likewise from q.  Each is clamped in
+ *             float to [-1, wc] (y: [-1, hc]) before the conversion to int; then x0 = max(x0, 0) and x1 = min(x1, wc - 1,
+ *             x0 + FL_REGISTER_MAX_SPLAT - 1), y the same.  An empty range writes nothing.  With equal cameras and identity
+ *             extrinsics the footprint is the pixel itself, so the output equals the input.
+ *   z-buffer  every output pixel of a footprint takes the minimum of the values that land on it; a pixel nothing lands on
+ *             is 0.  The minimum is order-independent: the result does not depend on the schedule.
+ *   cracks    with fill_cracks = 1, evaluated on the unfilled image E, never on filled values.  A pixel with E == 0: if its
+ *             left and right neighbours both exist and are non-zero it takes their minimum; otherwise, if its upper and lower
+ *             neighbours both exist and are non-zero, it takes their minimum; otherwise it stays 0.
+ * FL_ERR_INVALID, before any HIP call, nothing written: n_frames < 1; a NULL argument other than params, or a NULL entry of
+ * either pointer list; mem outside {0, 1}; a size <= 0 or above FL_RENDER_MAX_DIM; a non-finite or non-positive fx or fy, or a
+ * non-finite cx or cy, of either camera (as doubles or as floats); a non-finite entry of R or t; an R that is not a rotation (an
+ * element of R^T R - I above 1e-3 in magnitude, or det <= 0); fill_cracks outside {0, 1}.
+ * Frames go through in chunks of FL_REGISTER_CHUNK_FRAMES, fewer when the pixels of a chunk's input or output frames would pass
+ * FL_RENDER_CHUNK_PIXELS; a chunk is one clear of its z-buffer and two kernel launches.  Device scratch (the context's, kept
+ * for later calls, independent of n_frames): 4 bytes per output pixel of a chunk, plus 2 bytes per input and per output pixel
+ * of a chunk for host frames -- 79 MB at 640x480, 157 MB with host frames.  Nothing is allocated once the scratch has that size. */
+typedef struct { float R[9]; float t[3]; } fl_extrinsics;     /* row-major; X_colour = R * X_depth + t, mm */
+typedef struct { int32_t fill_cracks; } fl_register_params;   /* NULL = {1} */
+#define FL_REGISTER_MAX_SPLAT 8
+#define FL_REGISTER_CHUNK_FRAMES 64
+int  fl_register_depth_batch(fl_context *ctx, int n_frames, const uint16_t *const *depth, int mem,
+                             const fl_intrinsics *K_depth, const fl_intrinsics *K_color,
+                             const fl_extrinsics *depth_to_color, const fl_register_params *params,
+                             uint16_t *const *out);
+/* The checks fl_register_depth_batch makes of its cameras, extrinsics and parameters, alone and on the host (like fl_nms): FL_OK,
+ * or FL_ERR_INVALID for a camera, depth_to_color or params that call refuses.  Each argument may be NULL: it is not checked. */
+int  fl_register_check(const fl_intrinsics *K_depth, const fl_intrinsics *K_color, const fl_extrinsics *depth_to_color,
+                       const fl_register_params *params);
 /* spread + computeResponseMaps + linearize x8 (linemod.cpp:950-1088) for one quantized image:
  * out = 8 * fl_lm_label_stride(w,h,T) bytes, layout [label][T*T grid][(w/T)*(h/T)] + zero pad */
 size_t fl_lm_label_stride(int w, int h, int T);
